@@ -1,9 +1,23 @@
 #!/usr/bin/env python
 """bench.py -- conformers/sec of the geometry hot path on the BASELINE config 3 workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode 0|1] [--config C3|C4|C5] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode 0|1] [--config C3|C4|C5] [--full [--no-cpu]] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (`python bench.py --gpus N` from a bare shell starts the N ranks itself, as child processes under torch.distributed.run.)
+
+A plain run does only what the line's headline needs: set-up, W warm-up steps, THE K timed steps, the outputs of the last of
+them if `--dump-outputs DIR` asks for them, and the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`,
+`config` with the survivor digest and its parity with the recorded oracle run, `roofline` from the timed region's own events).
+Everything else this file measures needs `--full`: the events-off repeat of the timed steps, the three detail steps
+(`stage_ms_per_step`, `passes`, `roofline_front`), the side legs (`steps_in_flight`, `c4`, `hard_workloads`; at N > 1 the leg
+that is not the line's value) and the CPU baseline (`cpu_baseline`).  `--no-cpu` / `--no-side-leg` trim a `--full` run.
+
+`--dump-outputs DIR`: after the timed steps, what the last of them handed its caller is written as DIR/<name>.npy -- `clash_mask`
+(float32, one verdict per pose), `keep_mask` (float32, the prune's verdict on every pose that passed), `structures` (float64, the
+passing poses in order, all atoms), `counts` (float64: n_pass, n_keep[, n_conformers of the C5 chain]) -- at most 64 MiB in all:
+an array beyond its share is written as a sample of rows drawn with a fixed seed, their indices beside it as <name>_rows.npy.
+The inputs are generated from fixed seeds, so two builds run with the same arguments can be compared file by file.  A sharded
+line (one ensemble over several ranks) writes `keep_mask` and `counts` only.
 
 A "step" is one pass of the hot path over one synthetic ensemble that is already resident in HBM:
 fused embed+clash verdicts -> ordered compaction of the passing poses -> prune_conformers_rmsd
@@ -35,10 +49,10 @@ a 30 s watchdog that names the collective that hung; then the library's own exch
 `--exchange`: used for the per-pass messages when it connects and agrees).
 
 The timed region (K steps between barrier + synchronize) carries the HIP start/stop events of every pair-kernel dispatch that
-`roofline.avg_launch_us` needs; the same K steps with those events off follow (`events_off`), then three steps with every
+`roofline.avg_launch_us` needs; with `--full` the same K steps with those events off follow (`events_off`), then three steps with every
 library event on for `stage_ms_per_step` and `passes[].ms` -- both outside the timed region.
 
-Rank 0 prints ONE JSON line.  The CPU baseline leg (rank 0, N = 1 only) times the oracle -- this repo's C restatement of the
+Rank 0 prints ONE JSON line.  The CPU baseline leg (`--full`; rank 0, N = 1 only) times the oracle -- this repo's C restatement of the
 reference algorithm, "port" -- on the SAME workload (full C3: about a minute on 16 threads; other configs on a bounded
 sample, extrapolation stated); it is a reported baseline, not the thing measured.
 """
@@ -115,13 +129,21 @@ def parse():
                     help="run the multi-rank protocol (sharded_step + torch.distributed collectives) even with one rank")
     ap.add_argument("--pass-timing", type=int, default=1,
                     help="library HIP events in the timed region: 1 = start/stop events on every pair-kernel dispatch (feeds the roofline), 0 = none")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the line's headline: the events-off repeat and the detail steps, the side legs and the CPU baseline "
+                         "(a plain run has none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (at most 64 MiB in all)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--cpu-sample", type=int, default=None, help="poses of the CPU baseline run (default: the whole workload for C3, 40000 otherwise)")
     ap.add_argument("--no-side-leg", action="store_true", help="N > 1: time only the leg that is the line's value")
     ap.add_argument("--in-flight", type=int, default=3,
                     help="N = 1 side figure `steps_in_flight`: this many independent steps at a time, each on its own library context, "
                          "HIP stream and buffers, driven by one host thread each (0 = skip).  Never the line's value.")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def csrc_digest():
@@ -134,6 +156,48 @@ def binary_digest():
     """The digest of the sources the LOADED libtscode_hip.so was built from (baked in by tscode_amd/build.py)."""
     from tscode_amd import _lib
     return _lib.load().tsc_build_digest().decode()
+
+
+DUMP_MAX_BYTES = 64 << 20            # --dump-outputs: everything written, at most
+DUMP_MASK_ROWS = 1 << 20             # a mask longer than this is written as a sample of its entries (with the indices: 12 MiB at most)
+DUMP_STRUCTURE_BYTES = 32 << 20      # the passing poses' coordinates beyond this: a sample of rows
+DUMP_SEED = 20261016                 # the samples' rows: the same on every run of the same arguments
+DUMP_NAMES = ("counts", "clash_mask", "keep_mask", "structures")
+
+
+def dump_outputs(pipe, res, sharded, out_dir):
+    """--dump-outputs: what the timed path handed its caller in its last step, after the timed region's closing synchronisation (see
+    the module docstring).  Returns {name: shape} of what was written."""
+    import numpy as np
+    import torch
+    n_pass, n_keep = int(res["n_pass"]), int(res["n_keep"])
+    counts = [n_pass, n_keep] + ([int(res["n_conformers"])] if res.get("n_conformers") is not None else [])
+    arrays = {"counts": np.array(counts, dtype=np.float64)}
+
+    def put(name, t, dtype, cap_rows):
+        """t: a tensor whose first axis is rows; more rows than cap_rows -> a sorted sample drawn with DUMP_SEED."""
+        n = t.shape[0]
+        if n > cap_rows:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=cap_rows, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+            arrays[name + "_rows"] = idx.astype(np.float64)
+        arrays[name] = t.cpu().numpy().astype(dtype)
+
+    put("keep_mask", pipe.h_keep[:n_pass], np.float32, DUMP_MASK_ROWS)
+    if not sharded:
+        put("clash_mask", pipe.d_clash, np.float32, DUMP_MASK_ROWS)
+        row_bytes = pipe.d_structures.shape[1] * pipe.d_structures.shape[2] * 8
+        put("structures", pipe.d_structures[:n_pass], np.float64, DUMP_STRUCTURE_BYTES // row_bytes)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name in DUMP_NAMES:                  # nothing left over from an earlier run into the same directory
+        for path in (os.path.join(out_dir, name + ".npy"), os.path.join(out_dir, name + "_rows.npy")):
+            if os.path.exists(path):
+                os.remove(path)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def cpu_baseline(cfg_name, n_sample, n_full, mode):
@@ -413,6 +477,7 @@ def main():
         use_ipc = args.exchange == "ipc" and world > 1
     exchange_form = "ipc" if use_ipc else "callback"
     notes = []
+    side_legs = args.full and not args.no_side_leg     # a plain run times the line's own leg and nothing beside it
 
     def configure(pipe, pass_timing):
         pipe.set_option("prune_algo", args.algo)
@@ -482,9 +547,10 @@ def main():
                 parity = bool(flag.item())
         return digest, parity
 
-    def run_leg(sharded, ens=ens, expected=expected, detail=True):
-        """One leg: its own pipeline, warm-up, THE timed region, then (detail) the same steps with the library's events off and
-        three steps with all of them on.  Returns a dict of everything measured."""
+    def run_leg(sharded, ens=ens, expected=expected, detail=True, dump=False):
+        """One leg: its own pipeline, warm-up, THE timed region, (dump) the last timed step's outputs for --dump-outputs, then
+        (detail, --full only) the same steps with the library's events off and three steps with all of them on.  Returns a dict of
+        everything measured."""
         if chain:
             from tscode_amd.pipeline import CsearchChain, ShardedCsearchChain
             n0 = ens.frag_coords[0].shape[1]
@@ -514,9 +580,11 @@ def main():
         dt, res, acc = timed_loop(pipe, args.steps, args.pass_timing)   # THE timed region (library events as --pass-timing says, sampled)
         pipe.set_option("pass_timing", args.pass_timing)
         leg = {"dt": dt, "res": res, "acc": acc, "pipe": pipe, "sharded": sharded, "events_off": None, "pass_ms": None, "stage_ms": acc["stage_ms"]}
+        if dump and args.dump_outputs and rank == 0:
+            leg["dumped"] = dump_outputs(pipe, res, sharded, args.dump_outputs)
         units = ens.n_poses * (1 if sharded else world)
         leg["units_per_step"] = units
-        if args.pass_timing != 0 and detail:
+        if args.pass_timing != 0 and detail and args.full:
             # the same K steps once more with every library event off: what a production caller sees (an event record on the
             # stream costs about 4 us on MI355X; the kernel durations of the roofline need them, the product does not)
             pipe.set_option("pass_timing", 0)
@@ -574,9 +642,9 @@ def main():
         # the replicas leg first (it cannot hang on a collective), then the sharded leg under a watchdog: if RCCL should hang
         # on some node, a line is still printed -- with the replicas figure as its value, the failure named (exit code 3 when the
         # sharded leg was to be the line's value)
-        replicas = run_leg(False) if (not main_sharded or not args.no_side_leg) else None
+        replicas = run_leg(False, dump=not main_sharded) if (not main_sharded or side_legs) else None
         sharded_leg = None
-        if main_sharded or not args.no_side_leg:
+        if main_sharded or side_legs:
             def bail():
                 if rank == 0:
                     line = {"metric": "conformers/sec, 100k x 50-atom prune_conformers pipeline (embed -> clash mask -> RMSD prune)",
@@ -594,7 +662,7 @@ def main():
             watchdog.start()
             try:
                 try:
-                    sharded_leg = run_leg(True)
+                    sharded_leg = run_leg(True, dump=main_sharded)
                 except Exception as exc_ipc:
                     # the library's own exchange is the newest part of the path and has met more than one GPU nowhere yet: should it fail in a
                     # real step after passing the self-test, the leg runs once more with the process group's collectives before anything is
@@ -604,7 +672,7 @@ def main():
                     notes.append(f"sharded leg with exchange = ipc failed ({type(exc_ipc).__name__}: {exc_ipc}); repeated with exchange = callback")
                     exchange_form = "callback"
                     torch.cuda.synchronize()
-                    sharded_leg = run_leg(True)
+                    sharded_leg = run_leg(True, dump=main_sharded)
             except Exception as exc:
                 error = f"sharded single-ensemble leg failed: {type(exc).__name__}: {exc}" + ("; value = replicas leg" if main_sharded else "")
                 exit_code = 3        # (also when the sharded leg was only the side figure: the RCCL path gates every N > 1 run)
@@ -620,7 +688,7 @@ def main():
             if sharded_leg is not None:
                 side = ("sharded_single_ensemble", leg_summary(sharded_leg, SHARDED_WHAT))
     else:
-        leg = run_leg(main_sharded)
+        leg = run_leg(main_sharded, dump=True)
 
     if selftest is not None and not selftest["all_ok"]:
         error = ((error + "; ") if error else "") + "collective self-test: a collective returned wrong data on the step's buffers (selftest_collectives)"
@@ -836,6 +904,11 @@ def main():
             "detail_note": "stage_ms_per_step and passes[].ms come from 3 extra steps with every library event on (pass_timing 2), "
                            "outside the timed regions; passes[].tile_ms (the pair kernel's own events) from the timed region (0 for passes the chunk-local kernel runs: its events are taken at pass_timing 2 only)",
         }
+        if not args.full:     # (figures of the events-off and detail steps, which only --full runs)
+            for k in ("events_off", "stage_ms_per_step", "roofline_front", "passes", "detail_note"):
+                del out[k]
+        if leg.get("dumped") is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": leg["dumped"]}
         if sharded_mode:
             out["rccl_world"] = dist.get_world_size() if use_dist else 1
             out["collective_backend"] = dist.get_backend() if use_dist else None
@@ -878,7 +951,7 @@ def main():
     # independent ensembles (TSCoDe embeds one per reactant pair / conformer set; multiembed runs them from several processes)
     # gives each its own context and stream, and the GPU overlaps one chain's latency with another's kernels.  Every step does
     # all of its work on its own buffers; the verdicts of every one are checked.  A side figure, never `value`.
-    if world == 1 and args.in_flight > 1 and not args.no_side_leg and not chain and rank == 0:
+    if world == 1 and args.in_flight > 1 and side_legs and not chain and rank == 0:
         try:
             D = args.in_flight
             pipes = [DevicePipeline(ens, device_index=local_rank, rank=0, world=1, mode=args.mode) for _ in range(D)]
@@ -918,7 +991,7 @@ def main():
     # beside the C3 line: config C4 (1M x 50), the workload large enough for sharding one ensemble to pay -- one GPU: the one-call
     # pipeline; N > 1: the same sharded protocol.  A side figure of the default run, so that every N of a scaling series has it.
     # Under a watchdog of its own: the line above is complete and is printed whatever happens here.
-    if args.config == "C3" and args.n_poses is None and not args.no_side_leg and not (world > 1 and args.backend != "nccl") and exit_code == 0:
+    if args.config == "C3" and args.n_poses is None and side_legs and not (world > 1 and args.backend != "nccl") and exit_code == 0:
         def bail4():
             if rank == 0:
                 out["c4"] = {"error": "the C4 side leg did not finish within 240 s"}
@@ -980,7 +1053,7 @@ def main():
     # children scattered around the threshold, and structures whose descriptors all coincide (reference-exact and cache-free mode),
     # each with the automatic kernel choice, the sieve and the all-pairs kernel, and the CPU port on a bounded sample.  Side
     # figures, never `value`.
-    if world == 1 and rank == 0 and args.config == "C3" and args.n_poses is None and not args.no_side_leg and not chain and exit_code == 0:
+    if world == 1 and rank == 0 and args.config == "C3" and args.n_poses is None and side_legs and not chain and exit_code == 0:
         try:
             leg["pipe"] = None
             from tools.hard_workloads import measure as hard_measure
@@ -996,7 +1069,7 @@ def main():
         except Exception as exc:
             out["hard_workloads"] = {"error": f"{type(exc).__name__}: {exc}"}
     if rank == 0:
-        if world == 1 and not args.no_cpu and not chain:
+        if world == 1 and args.full and not args.no_cpu and not chain:
             n_cpu = args.cpu_sample if args.cpu_sample else (ens.n_poses if args.config == "C3" else 40000)
             out["cpu_baseline"] = cpu_baseline(args.config, min(n_cpu, ens.n_poses), ens.n_poses, args.mode)
             cb = out["cpu_baseline"]

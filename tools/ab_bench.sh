@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs on the GPU box (through gpurun): the same bench command on the product library and on variants built by tools/build_variant.py, twice each,
 # interleaved (a box's clocks drift).   usage: tools/ab_bench.sh "bench.py arguments" NAME [NAME ...]     (NAME = tscode_amd/ab_libs/NAME.so; "base" = the product)
-ARGS=$1; shift
+ARGS="--full $1"; shift
 mkdir -p gpurun_out/ab
 for rep in 1 2; do
   for v in "$@"; do

@@ -5,7 +5,7 @@ set -e
 P=gpurun_out/$1; shift
 mkdir -p "$P"
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$P/trace" -- python3 bench.py --steps 10 --warmup 2 --no-cpu --no-side-leg $* > "$P/bench.json" 2> "$P/trace.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$P/trace" -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu --no-side-leg $* > "$P/bench.json" 2> "$P/trace.err"
 python3 - "$P" <<'PY'
 import csv, glob, sys
 import os

@@ -7,7 +7,7 @@ set -e
 P=gpurun_out/$1; shift
 mkdir -p "$P"
 export TMPDIR=/tmp
-ARGS="--steps 2 --warmup 1 --no-cpu --no-side-leg $*"
+ARGS="--full --steps 2 --warmup 1 --no-cpu --no-side-leg $*"
 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_READ_sum TCC_WRITE_sum TCP_TCC_READ_REQ_sum --output-format csv -d "$P/p1" -- python3 bench.py $ARGS > "$P/b1.json" 2> "$P/p1.err"
 rocprofv3 --pmc TCC_ATOMIC_sum TCC_EA0_ATOMIC_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum --output-format csv -d "$P/p2" -- python3 bench.py $ARGS > "$P/b2.json" 2> "$P/p2.err"
 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_DRAM_sum TCC_WRITEBACK_sum --output-format csv -d "$P/p3" -- python3 bench.py $ARGS > "$P/b3.json" 2> "$P/p3.err"

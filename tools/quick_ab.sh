@@ -5,8 +5,8 @@ set -e
 P=gpurun_out/$1; shift
 mkdir -p "$P"
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$P/trace" -- python3 bench.py --steps 10 --warmup 2 --no-cpu --no-side-leg $* > "$P/b_trace.json" 2> "$P/trace.err"
-python3 bench.py --steps 20 --warmup 5 --no-cpu --no-side-leg $* > "$P/b.json" 2> "$P/b.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$P/trace" -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu --no-side-leg $* > "$P/b_trace.json" 2> "$P/trace.err"
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu --no-side-leg $* > "$P/b.json" 2> "$P/b.err"
 python3 - "$P" <<'PY'
 import csv, glob, json, sys
 P = sys.argv[1]
