@@ -58,6 +58,7 @@ typedef enum {
 
 typedef struct tsc_ctx tsc_ctx;     /* one per (process, device); owns a stream and scratch memory */
 typedef struct tsc_prune tsc_prune; /* state of one prune_conformers_rmsd run (stepping API) */
+typedef struct tsc_rot_corr tsc_rot_corr; /* state of one prune_conformers_rmsd_rot_corr run */
 
 /* ---- library / context ------------------------------------------------------------------ */
 int tsc_version(void);
@@ -527,6 +528,38 @@ int tsc_pipeline_dev(tsc_ctx *ctx, const double *frags, const int64_t *frag_off_
                      double rmsd_thr, int mode, uint8_t *clash_mask, double *structures, uint8_t *keep_mask,
                      uint8_t *keep_mask_host, int64_t *n_pass_host, int64_t *n_keep_host, tsc_pass_stats *stats, int *n_passes,
                      float *timings_ms);
+
+
+/* Symmetry-corrected RMSD pruning (tscode/torsion_module.py:953-1161, prune_conformers_rmsd_rot_corr).
+ * The set-up is the caller's (the graph work of :1023-1049, once per call): coords f64[n_structs, n_atoms, 3] centred on their
+ * all-atom mean; heavy i32[n_heavy] the heavy atoms; torsions i32[n_tors, 4] the dummy torsions as the reference orients them;
+ * angles f64[n_tors, 6] with n_angles i32[n_tors] (1..6) used per row, in the reference's order (0 included); move_mask
+ * u8[n_tors, n_atoms] the atoms each torsion turns (_get_rotation_mask); torsion t's local heavy subgraph is
+ * sub_idx[sub_ptr[t] .. sub_ptr[t+1]) (sub_ptr i32[n_tors + 1], sub_ptr[0] = 0, every subgraph non-empty).
+ * Limits, refused with TSC_ERR_INVALID: n_tors <= 16, n_atoms <= 512, n_structs < 2^31.  Host arrays throughout.
+ *   tsc_rot_corr_begin    uploads the set-up and the structures; the run turns ITS copy in place, as the reference turns its array.
+ *   tsc_rot_corr_pass     one pass of the schedule (:1080-1152 without the graph step): chunk `step` is [d*step, d*(step+1)), the
+ *                         last one [d*(k-1), num_active); rows of a chunk in order, each row's j in order up to and including the
+ *                         first similar one (rmsd < max_rmsd), pairs found dissimilar in an earlier pass skipped (the cache).
+ *                         first i32[n_structs] = absolute index of row i's first similar j, or -1; pairs_evaluated = the pairs the
+ *                         reference would have computed in this pass.  Synchronous.
+ *   tsc_rot_corr_end      copies the run's (centred, turned) structures to coords_out f64[n_structs, n_atoms, 3].
+ *   tsc_rot_corr_destroy  frees the run.  A context lists its live runs and destroys them with itself: do not hand a run to
+ *                         tsc_rot_corr_destroy after its context is destroyed.
+ *   tsc_rot_corr_pairs    the value-level form: rotationally_corrected_rmsd(ref = coords[pairs[p, 0]], coord = coords[pairs[p, 1]])
+ *                         for every pair on a private copy of the coordinates (nothing is mutated): rmsd f64[n_pairs] and the best
+ *                         angle of every torsion, best_angle f64[n_pairs, n_tors]. */
+int tsc_rot_corr_begin(tsc_ctx *ctx, const double *coords, int64_t n_structs, int n_atoms, const int32_t *heavy, int n_heavy,
+                       const int32_t *torsions, int n_tors, const double *angles, const int32_t *n_angles, const uint8_t *move_mask,
+                       const int32_t *sub_ptr, const int32_t *sub_idx, tsc_rot_corr **out);
+int tsc_rot_corr_pass(tsc_rot_corr *run, int64_t d, int64_t k, int64_t num_active, double max_rmsd, int32_t *first,
+                      int64_t *pairs_evaluated);
+int tsc_rot_corr_end(tsc_rot_corr *run, double *coords_out);
+int tsc_rot_corr_destroy(tsc_rot_corr *run);
+int tsc_rot_corr_pairs(tsc_ctx *ctx, const double *coords, int64_t n_structs, int n_atoms, const int32_t *heavy, int n_heavy,
+                       const int32_t *torsions, int n_tors, const double *angles, const int32_t *n_angles, const uint8_t *move_mask,
+                       const int32_t *sub_ptr, const int32_t *sub_idx, const int32_t *pairs, int64_t n_pairs, double *rmsd,
+                       double *best_angle);
 
 #ifdef __cplusplus
 }

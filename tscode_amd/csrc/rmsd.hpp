@@ -245,9 +245,8 @@ __device__ inline void residual_rmsd_maxdev(const double *__restrict__ p, const 
     maxdev = sqrt(mx);  // max_a sqrt(d2_a) == sqrt(max_a d2_a): sqrt is monotone
 }
 
-__device__ inline void exact_rmsd_maxdev(const double *__restrict__ p, const double *__restrict__ q, int h, const double S[9],
-                                         double Gp, double Gq, double &rmsd, double &maxdev, int sub = 0, int lpp = 1) {
-    double e[4];
+// The quaternion e (w, x, y, z; any length) of the optimal proper rotation of p onto q, given S = p^T q and the squared norms
+__device__ inline void exact_quaternion(const double S[9], double Gp, double Gq, double e[4]) {
     if (!rotation_quaternion_fast(S, Gp, Gq, e)) {
         double N[4][4], M[16];
         horn_matrix(S, M);
@@ -257,6 +256,12 @@ __device__ inline void exact_rmsd_maxdev(const double *__restrict__ p, const dou
             for (int j = 0; j < 4; ++j) N[i][j] = M[4 * i + j];
         top_eigvec4(N, e);
     }
+}
+
+__device__ inline void exact_rmsd_maxdev(const double *__restrict__ p, const double *__restrict__ q, int h, const double S[9],
+                                         double Gp, double Gq, double &rmsd, double &maxdev, int sub = 0, int lpp = 1) {
+    double e[4];
+    exact_quaternion(S, Gp, Gq, e);
     residual_rmsd_maxdev(p, q, h, e, rmsd, maxdev, sub, lpp);
 }
 

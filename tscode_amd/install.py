@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import sys
 
-from . import algebra, embeds, numba_functions, optimization_methods, rmsd_pruning, torsion_module
+from . import algebra, embeds, numba_functions, optimization_methods, rmsd_pruning, rot_corr, torsion_module
 
 # attribute -> (replacement, modules that bind it)
 _PATCHES = {
@@ -46,20 +46,29 @@ _PATCHES = {
 _WHOLE_ENSEMBLE = ("prune_conformers_rmsd", "prune_conformers_tfd", "get_moi_similarity_matches", "_score_embed_poses", "string_embed",
                    "cyclical_embed")
 
+# Opt-in (install(rot_corr=True)): the symmetry-corrected prune of the refinement stage (tscode/embedder.py:1372-1382,
+# tscode/operators.py:571), bound by name in these three modules.  Off by default until it has a number from hardware.
+_ROT_CORR_PATCHES = {
+    "prune_conformers_rmsd_rot_corr": (rot_corr.prune_conformers_rmsd_rot_corr,
+                                       ("tscode.torsion_module", "tscode.embedder", "tscode.operators")),
+}
+
 _saved = {}
 
 
-def install(modules=None, per_item=False):
+def install(modules=None, per_item=False, rot_corr=False):
     """Replace the hot-path functions in every already-imported tscode module: by default those that work on a whole ensemble
     per call (prune_conformers_rmsd, prune_conformers_tfd, get_moi_similarity_matches, _score_embed_poses) and the two embed
     loops (string_embed, cyclical_embed: one GPU call each instead of one Python iteration per pose); with
     ``per_item=True`` also the per-pose / per-pair ones (compenetration_check, get_embed, rmsd_and_max_numba, ...), which are
-    equivalent but slower than the reference's jitted code when called one item at a time.
+    equivalent but slower than the reference's jitted code when called one item at a time; with ``rot_corr=True`` also
+    prune_conformers_rmsd_rot_corr (_ROT_CORR_PATCHES).
     Returns the list of (module, attribute) pairs that were patched."""
     mods = sys.modules if modules is None else modules
     done = []
-    for attr, (fn, names) in _PATCHES.items():
-        if not per_item and attr not in _WHOLE_ENSEMBLE:
+    table = list(_PATCHES.items()) + (list(_ROT_CORR_PATCHES.items()) if rot_corr else [])
+    for attr, (fn, names) in table:
+        if not per_item and attr not in _WHOLE_ENSEMBLE and attr not in _ROT_CORR_PATCHES:
             continue
         for name in names:
             mod = mods.get(name)

@@ -218,21 +218,31 @@ def _tfd_reject_graph(first, d, k, final_mask, chunks):
                     final_mask[i + off] = 0                              # :222-224
 
 
-def _tfd_schedule(structures, tf_mat, thresh, verbose, first_similar):
-    """The pass schedule of tscode/numba_functions.py:160-226 around a pair search `first_similar(tf_mat, d, k, num_active,
-    thresh) -> int32[N]` (the engine's kernel in the product; the tests also drive it with the CPU oracle's)."""
-    n = structures.shape[0]
+def _pass_schedule(n, verbose, first_similar, on_slot=None):
+    """The pass schedule of tscode/numba_functions.py:160-226 -- shared line for line by prune_conformers_rmsd_rot_corr
+    (tscode/torsion_module.py:1076-1152) -- around a pair search `first_similar(d, k, num_active) -> int32[n]` (absolute index of
+    each row's first similar j, -1: none).  on_slot(k, num_active), if given, sees the gate's count of every schedule slot.
+    Returns the final mask."""
     final_mask = np.ones(n, dtype=bool)
     for k in TFD_KS:
         num_active_str = int(np.count_nonzero(final_mask))
+        if on_slot is not None:
+            on_slot(k, num_active_str)
         if k == 1 or 5 * k < num_active_str:                              # :166
             d = int(n // k)                                               # :173
             if d == 0:
                 continue
             if verbose:
                 print(f"Working on subgroups with k={k} ({num_active_str} candidates left) {' ' * 10}", end="\r")
-            first = first_similar(tf_mat, d, int(k), num_active_str, thresh)
+            first = first_similar(d, int(k), num_active_str)
             _tfd_reject_matches(first, d, int(k), final_mask)
+    return final_mask
+
+
+def _tfd_schedule(structures, tf_mat, thresh, verbose, first_similar):
+    """The pass schedule of tscode/numba_functions.py:160-226 around a pair search `first_similar(tf_mat, d, k, num_active,
+    thresh) -> int32[N]` (the engine's kernel in the product; the tests also drive it with the CPU oracle's)."""
+    final_mask = _pass_schedule(structures.shape[0], verbose, lambda d, k, num_active: first_similar(tf_mat, d, k, num_active, thresh))
     return structures[final_mask], final_mask
 
 

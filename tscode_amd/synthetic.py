@@ -23,7 +23,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-__all__ = ["Ensemble", "make_fragment", "make_ensemble", "make_unscreenable", "CONFIGS", "make_config", "quat_to_mat"]
+__all__ = ["Ensemble", "make_fragment", "make_ensemble", "make_unscreenable", "CONFIGS", "make_config", "quat_to_mat", "make_rot_corr_ensemble"]
 
 
 def make_fragment(rng: np.random.Generator, n_atoms: int, step: float = 1.5, min_dist: float = 1.2) -> np.ndarray:
@@ -211,3 +211,42 @@ def make_config(name: str, n_poses: int | None = None, attempt: int = 0) -> Ense
     ens = make_ensemble(**cfg)
     ens.meta["config"] = name
     return ens
+
+
+def make_rot_corr_ensemble(base, torsions, angles, move_masks, n_clusters, per_cluster, turn=None, seed=0, spread=0.8, noise=0.005):
+    """A shuffled ensemble for the symmetry-corrected prune (tscode_amd.rot_corr) whose answer is known.  Cluster c is ``base``
+    with every coordinate moved by N(0, spread) -- except the atoms of the turned rotors (move_masks[t] and the bond atoms t1, t2
+    of every torsion with turn[t]), which keep their symmetry about their bond -- so clusters lie far apart in RMSD.  Each member
+    turns every such rotor by one of its torsion's angles (an exact symmetry turn when the rotor is symmetric in ``base``: the
+    atoms are permuted, the all-atom mean the prune centres on stays put, and the torsion search undoes the turn), then takes
+    uniform noise of at most ``noise`` per coordinate and a random rigid rotation.
+    Returns (structures f64[n_clusters * per_cluster, n, 3], labels int[...])."""
+    rng = np.random.default_rng(seed)
+    base = np.asarray(base, dtype=np.float64)
+    turn = [True] * len(torsions) if turn is None else list(turn)
+    keep = np.zeros(len(base), dtype=bool)
+    for t, tor in enumerate(torsions):
+        if turn[t]:
+            keep |= np.asarray(move_masks[t], dtype=bool)
+            keep[[int(tor[1]), int(tor[2])]] = True
+    out, labels = [], []
+    for c in range(n_clusters):
+        xc = base + np.where(keep[:, None], 0.0, rng.normal(0.0, spread, size=base.shape))
+        for _ in range(per_cluster):
+            x = xc.copy()
+            for t, (tor, angs, mask) in enumerate(zip(torsions, angles, move_masks)):
+                if not turn[t]:
+                    continue
+                i2, i3 = int(tor[1]), int(tor[2])
+                ax = x[i2] - x[i3]
+                ax = ax / np.linalg.norm(ax)
+                half = np.radians(float(angs[rng.integers(len(angs))])) / 2
+                R = quat_to_mat(np.array([[np.cos(half), *(np.sin(half) * ax)]]))[0]
+                m = np.asarray(mask, dtype=bool)
+                x[m] = (x[m] - x[i3]) @ R.T + x[i3]
+            x = x + rng.uniform(-noise, noise, size=x.shape)
+            q = rng.normal(size=4)
+            out.append(x @ quat_to_mat((q / np.linalg.norm(q))[None])[0].T)
+            labels.append(c)
+    perm = rng.permutation(len(out))
+    return np.array(out)[perm], np.array(labels)[perm]
