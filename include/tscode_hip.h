@@ -561,6 +561,51 @@ int tsc_rot_corr_pairs(tsc_ctx *ctx, const double *coords, int64_t n_structs, in
                        const int32_t *sub_ptr, const int32_t *sub_idx, const int32_t *pairs, int64_t n_pairs, double *rmsd,
                        double *best_angle);
 
+/* Ensemble alignment, k-means and the diverse-conformer pick: the end of a conformational search (tscode/torsion_module.py:849-924,
+ * most_diverse_conformers; csrc/diverse.hpp).  Host arrays throughout; fp64; every sum in a fixed order, so two calls on the same
+ * input return the same bits.  Limits, refused with TSC_ERR_INVALID before any launch: 1 <= k <= 300 (the reference's own gate,
+ * :863), k <= N, n_atoms <= 512 (D <= 1536), N < 2^31.
+ *   tsc_align_structures  align_structures (tscode/hypermolecule_class.py:38-72): every structure is centred on the mean of its
+ *                         indexed atoms (:53-55; indices NULL or n_idx == 0: all atoms, :51) and structures 1 .. N-1 are turned by the
+ *                         proper rotation that takes their indexed atoms onto structure 0's (rmsd's kabsch at :63, applied at :70).
+ *                         The LinAlgError branch (:65-67) has no counterpart: the solver (Horn's quaternion, csrc/rmsd.hpp) does not
+ *                         fail; where the optimum is not unique the result is finite and a proper rotation.  out f64[N, n, 3].
+ *   tsc_kmeans_lloyd      what KMeans(n_clusters = k, init = <array>, n_init = 1, algorithm = "lloyd").fit(X) computes (:889-890 with
+ *                         the initial centres given): X f64[N, D] and init f64[k, D] are mean-centred, tol_abs = mean(var(X, 0)) * tol;
+ *                         per iteration: nearest centre (ties: the lowest), per-cluster means, the j-th empty cluster (ascending)
+ *                         takes the row with the j-th largest distance to its own centre (ties: the lower row), which leaves its
+ *                         cluster's sum; stop when the labels repeat or the squared shift of the centres <= tol_abs, else after
+ *                         max_iter; unless the labels repeated, one more assignment.  labels i32[N], centers f64[k, D] (mean added
+ *                         back), *inertia = sum |x_i - centre|^2, *n_iter, *max_empty (optional) = the most clusters empty at once.
+ *   tsc_kmeans_seed       k-means++ without local trials, the uniforms u f64[k] in [0, 1) given by the caller (the library has no
+ *                         random numbers): rows[0] = floor(u[0] N); then rows[j] = the first row whose running sum (row order) of
+ *                         min_d2 = squared distance to the nearest seed so far exceeds u[j] * total.
+ *   tsc_diverse_pick      :894-922 on aligned f64[N, n, 3], labels i32[N] in [0, k), centers f64[k, n, 3]: picked[c] = the member of
+ *                         cluster c to keep, -1 for an empty cluster.  With energies f64[N]: the lowest energy, the first in row
+ *                         order on a tie (:901).  Without: the largest cumdist, the first on a tie (:919-921), where the member at
+ *                         position p of its cluster's list sums |centre_c[a] - member[a]| over the atoms and over the centres
+ *                         c != p -- the position, as :919 has it (`enumerate(cluster)`), not the member's own cluster.
+ *   tsc_diverse_select    :882-922 in one call, nothing but the loop control leaving the device in between: align (all atoms), Lloyd
+ *                         from the aligned rows init_rows, pick.  u == NULL: init_rows i32[k] is read.  u f64[k] given: the seeds
+ *                         are chosen on the aligned features by the rule of tsc_kmeans_seed and init_rows RECEIVES them.
+ *                         aligned_out f64[N, n, 3], labels i32[N], picked i32[k], *n_iter.
+ *   tsc_diverse_timings   under the context option "pass_timing" >= 1 the calls above time their stages with events (and synchronise
+ *                         for it): ms4 = align, first k_kmeans_assign launch (the kernel alone), first k_kmeans_update launch, device part
+ *                         of tsc_diverse_select, of the calling thread's latest call of one of the entries above (each resets all four);
+ *                         -1 where that call took none.
+ * Non-finite coordinates / X / init / centers, NaN energies and u outside [0, 1) are refused with TSC_ERR_INVALID before any launch. */
+int tsc_align_structures(tsc_ctx *ctx, const double *structures, int64_t n_structs, int n_atoms, const int32_t *indices, int n_idx,
+                         double *out);
+int tsc_kmeans_lloyd(tsc_ctx *ctx, const double *X, int64_t N, int64_t D, const double *init, int k, int max_iter, double tol,
+                     int32_t *labels, double *centers, double *inertia, int *n_iter, int *max_empty);
+int tsc_kmeans_seed(tsc_ctx *ctx, const double *X, int64_t N, int64_t D, int k, const double *u, int32_t *rows);
+int tsc_diverse_pick(tsc_ctx *ctx, const double *aligned, int64_t N, int n_atoms, const int32_t *labels, const double *centers, int k,
+                     const double *energies, int32_t *picked);
+int tsc_diverse_select(tsc_ctx *ctx, const double *structures, int64_t N, int n_atoms, int32_t *init_rows, const double *u, int k,
+                       const double *energies, int max_iter, double tol, double *aligned_out, int32_t *labels, int32_t *picked,
+                       int *n_iter);
+int tsc_diverse_timings(tsc_ctx *ctx, float *ms4);
+
 #ifdef __cplusplus
 }
 #endif

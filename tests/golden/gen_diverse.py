@@ -1,0 +1,348 @@
+"""G20: the reference's align_structures (tscode/hypermolecule_class.py:38-72) and most_diverse_conformers
+(tscode/torsion_module.py:849-924), and scikit-learn's Lloyd iteration from a given init, case by case.
+
+BUILD CONTAINER ONLY (imports the reference through tests/golden/_reference.py, and scikit-learn).  No test imports either.
+
+ASSUMPTION, not pinned by anything in this image (the same as G19's): the reference calls rmsd.kabsch (the `rmsd` package,
+setup.py pins rmsd==1.4), which is not installed here.  It is restated below from that release: C = P^T Q, SVD, the last column
+of V flipped when det(V) det(W) < 0, U = V W.
+
+The reference's KMeans(n_clusters=n) at :889 is scikit-learn's unseeded default and has no reproducible result.  While
+most_diverse_conformers runs, tm.KMeans is a wrapper whose fit(X) records X, draws init_rows from a recorded seed and runs the
+real sklearn.cluster.KMeans(n_clusters, init=X[init_rows], n_init=1, algorithm="lloyd").
+
+Ensembles: tscode_amd.synthetic.make_ensemble poses, every structure moved by a seeded random rigid motion.  Guard bands,
+enforced here (a case is drawn again with the next seed, the seed recorded) so that no test leaves a case out:
+  * label margin: at every Lloyd iteration, every row's second-smallest minus smallest squared distance >= 1e-6 A^2;
+  * at most one cluster empty at a time;
+  * the pick: best and second-best cumdist of a cluster differ by >= 1e-6, energies inside a cluster are distinct;
+  * Horn's top eigenvalue separated from the next by >= 1e-3 relative for every aligned pair.
+
+Files (each under 1 MiB): G20a (60 x 12 atoms k = 5; an index subset; two structures), G20b (400 x 30, k = 12, one init centre
+moved 50 A away: one cluster empty in iteration 1), G20c (600 x 24 through most_diverse_conformers, n = 20, both modes), G20d
+(1200 x 20, k = 40: the aligned features only), G20_diverse.json (the guard values, seeds, versions, and the modules that bind
+align_structures / most_diverse_conformers by name, read off the reference's import lines).
+
+Usage:  python -B tests/golden/gen_diverse.py
+"""
+import ast
+import io
+import json
+import os
+import sys
+import zipfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+import _reference as R  # noqa: E402
+
+R.install_standins(full=True)
+import networkx as nx  # noqa: E402
+if not hasattr(nx, "from_numpy_matrix"):
+    nx.from_numpy_matrix = nx.from_numpy_array
+
+
+def kabsch(P, Q):
+    """rmsd 1.4 kabsch(P, Q): the rotation U with P @ U ~ Q (see the module docstring)."""
+    C = np.dot(np.transpose(P), Q)
+    V, S, W = np.linalg.svd(C)
+    if (np.linalg.det(V) * np.linalg.det(W)) < 0.0:
+        S[-1] = -S[-1]
+        V[:, -1] = -V[:, -1]
+    return np.dot(V, W)
+
+
+sys.modules["rmsd"].kabsch = kabsch
+import sklearn  # noqa: E402
+from sklearn.cluster import KMeans as SkKMeans  # noqa: E402
+from threadpoolctl import threadpool_limits  # noqa: E402
+import tscode.hypermolecule_class as hc  # noqa: E402
+import tscode.torsion_module as tm  # noqa: E402
+
+from tscode_amd.synthetic import make_ensemble  # noqa: E402  (NumPy only)
+
+MARGIN_BAND, PICK_BAND, HORN_BAND = 1e-6, 1e-6, 1e-3
+
+
+# ------------------------------------------------------------------------------------------------------- inputs
+def moved_ensemble(n, atoms, seed, children):
+    """make_ensemble poses, each turned by a random rotation about its centroid and shifted by up to 5 A."""
+    x = make_ensemble(n, atoms, seed=seed, children=children).poses()
+    rng = np.random.default_rng(seed + 7)
+    q = rng.normal(size=(n, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    w, a, b, c = q.T
+    rot = np.array([[1 - 2 * (b * b + c * c), 2 * (a * b - c * w), 2 * (a * c + b * w)],
+                    [2 * (a * b + c * w), 1 - 2 * (a * a + c * c), 2 * (b * c - a * w)],
+                    [2 * (a * c - b * w), 2 * (b * c + a * w), 1 - 2 * (a * a + b * b)]]).transpose(2, 0, 1)
+    cen = x.mean(axis=1, keepdims=True)
+    return np.ascontiguousarray(np.einsum("nij,naj->nai", rot, x - cen) + cen + rng.uniform(-5, 5, size=(n, 1, 3)))
+
+
+def horn_gap(aligned_input_centred, idx):
+    """Smallest relative gap between the two largest eigenvalues of Horn's matrix over the pairs (structure t, structure 0)."""
+    ref = aligned_input_centred[0][idx]
+    worst = np.inf
+    for t in range(1, len(aligned_input_centred)):
+        S = aligned_input_centred[t][idx].T @ ref
+        N = np.array([[S[0, 0] + S[1, 1] + S[2, 2], S[1, 2] - S[2, 1], S[2, 0] - S[0, 2], S[0, 1] - S[1, 0]],
+                      [0, S[0, 0] - S[1, 1] - S[2, 2], S[0, 1] + S[1, 0], S[2, 0] + S[0, 2]],
+                      [0, 0, -S[0, 0] + S[1, 1] - S[2, 2], S[1, 2] + S[2, 1]],
+                      [0, 0, 0, -S[0, 0] - S[1, 1] + S[2, 2]]])
+        ev = np.linalg.eigvalsh(N + np.triu(N, 1).T)
+        worst = min(worst, (ev[-1] - ev[-2]) / abs(ev[-1]))
+    return float(worst)
+
+
+def reference_align(structures, indices):
+    """The reference on a copy: (output, the centred array it leaves behind, Horn gap)."""
+    work = structures.copy()
+    out = hc.align_structures(work, indices)
+    idx = slice(None) if indices is None or len(indices) == 0 else np.asarray(indices).ravel()
+    return out, work, horn_gap(work, idx)
+
+
+# ------------------------------------------------------------------------------------------------------- Lloyd, restated
+def lloyd_restated(X, init, max_iter=300, tol=1e-4):
+    """The Lloyd iteration as include/tscode_hip.h states it (tsc_kmeans_lloyd).  Returns labels, centres, inertia, n_iter, the smallest label margin over all
+    iterations and rows, the most clusters empty at once."""
+    mean = X.mean(0)
+    Xc, C = X - mean, init - mean
+    tol_abs = np.mean(np.var(Xc, axis=0)) * tol
+    k = len(C)
+    margin, max_empty, old, strict = np.inf, 0, None, False
+
+    def assign(C):
+        d2 = ((Xc[:, None, :] - C[None, :, :]) ** 2).sum(-1) if Xc.size * k < 4e7 else np.stack([((Xc - c) ** 2).sum(1) for c in C], axis=1)
+        lab = d2.argmin(1)
+        part = np.partition(d2, 1, axis=1) if k > 1 else np.concatenate([d2, d2 + np.inf], axis=1)
+        return lab, d2[np.arange(len(Xc)), lab], float((part[:, 1] - part[:, 0]).min())
+
+    for it in range(max_iter):
+        labels, own, m = assign(C)
+        margin = min(margin, m)
+        sums = np.zeros_like(C)
+        np.add.at(sums, labels, Xc)
+        counts = np.bincount(labels, minlength=k).astype(float)
+        empty = np.flatnonzero(counts == 0)
+        max_empty = max(max_empty, len(empty))
+        if len(empty):
+            far = np.lexsort((np.arange(len(Xc)), -own))[:len(empty)]
+            for e, f in zip(empty, far):
+                sums[labels[f]] -= Xc[f]
+                counts[labels[f]] -= 1
+                sums[e] = Xc[f]
+                counts[e] = 1
+        C_new = sums / counts[:, None]
+        shift = ((C_new - C) ** 2).sum()
+        C = C_new
+        if old is not None and np.array_equal(labels, old):
+            strict = True
+            break
+        if shift <= tol_abs:
+            break
+        old = labels
+    if not strict:
+        labels, own, m = assign(C)
+        margin = min(margin, m)
+    inertia = float(((Xc - C[labels]) ** 2).sum())
+    return labels.astype(np.int32), C + mean, inertia, it + 1, margin, max_empty
+
+
+def sklearn_lloyd(X, init):
+    with threadpool_limits(limits=1):                  # (its inertia is an OpenMP reduction: one thread, the same bytes every run)
+        km = SkKMeans(n_clusters=len(init), init=init, n_init=1, algorithm="lloyd").fit(X)
+    return km.labels_.astype(np.int32), km.cluster_centers_, float(km.inertia_), int(km.n_iter_)
+
+
+def kmeans_case(X, init):
+    """scikit-learn's result, checked against the restatement; None when a guard band is violated."""
+    labels, centres, inertia, n_iter = sklearn_lloyd(X, init)
+    r_labels, r_centres, r_inertia, r_iter, margin, max_empty = lloyd_restated(X, init)
+    if margin < MARGIN_BAND or max_empty > 1:
+        return None
+    assert np.array_equal(labels, r_labels) and n_iter == r_iter, "the restatement disagrees with scikit-learn"
+    assert np.abs(centres - r_centres).max() < 1e-10
+    return {"X": X, "init": init, "labels": labels, "centers": centres, "inertia": np.float64(inertia), "n_iter": np.int32(n_iter),
+            "margin": np.float64(margin), "max_empty": np.int32(max_empty)}
+
+
+# ------------------------------------------------------------------------------------------------------- the pick's guard
+def pick_guard(aligned, labels, centres, energies):
+    """(smallest gap between the best and second-best cumdist of a cluster under :919 as written, smallest energy gap inside a
+    cluster)."""
+    k = len(centres)
+    cen = centres.reshape(k, -1, 3)
+    r = np.arange(k)
+    gap, egap = np.inf, np.inf
+    for c in range(k):
+        members = np.flatnonzero(labels == c)
+        cum = sorted((np.sum(np.linalg.norm(cen[r != p] - aligned[m], axis=2)) for p, m in enumerate(members)), reverse=True)
+        if len(cum) > 1:
+            gap = min(gap, cum[0] - cum[1])
+        e = np.sort(energies[members])
+        if len(e) > 1:
+            egap = min(egap, np.diff(e).min())
+    return float(gap), float(egap)
+
+
+class RecordingKMeans:
+    """Stands in for tm.KMeans while most_diverse_conformers runs (module docstring)."""
+    seed = 0
+    last = None
+
+    def __init__(self, n_clusters):
+        self.n_clusters = n_clusters
+
+    def fit(self, X):
+        rows = np.sort(np.random.default_rng(RecordingKMeans.seed).choice(len(X), self.n_clusters, replace=False)).astype(np.int32)
+        with threadpool_limits(limits=1):
+            km = SkKMeans(n_clusters=self.n_clusters, init=X[rows], n_init=1, algorithm="lloyd").fit(X)
+        self.labels_, self.cluster_centers_ = km.labels_, km.cluster_centers_
+        RecordingKMeans.last = {"X": X.copy(), "init_rows": rows, "labels": km.labels_.astype(np.int32), "centers": km.cluster_centers_.copy(),
+                                "inertia": np.float64(km.inertia_), "n_iter": np.int32(km.n_iter_)}
+        return self
+
+
+# ------------------------------------------------------------------------------------------------------- cases
+def with_redraw(make, first_seed, what):
+    for attempt in range(20):
+        got = make(first_seed + 1000 * attempt)
+        if got is not None:
+            got["seed"] = np.int64(first_seed + 1000 * attempt)
+            return got
+        print(f"  {what}: seed {first_seed + 1000 * attempt} violates a guard band, drawn again")
+    raise SystemExit(f"{what}: no admissible draw in 20")
+
+
+def case_cluster(n, atoms, k, children, first_seed, far_centre=False, keep_input=True):
+    def make(seed):
+        s = moved_ensemble(n, atoms, seed, children)
+        out, left, gap = reference_align(s, None)
+        if gap < HORN_BAND:
+            return None
+        X = out.reshape(n, -1)
+        rows = np.sort(np.random.default_rng(seed).choice(n, k, replace=False)).astype(np.int32)
+        init = X[rows].copy()
+        if far_centre:
+            init[3] += 50.0 / np.sqrt(X.shape[1])       # 50 A away as a point of feature space
+        got = kmeans_case(X, init)
+        if got is None or (far_centre and got["max_empty"] != 1):
+            return None
+        got.update(init_rows=rows, horn_gap=np.float64(gap))
+        if keep_input:
+            got.update(structures=s, aligned=out, centred_input=left)
+            del got["X"]                               # (= aligned.reshape(n, -1))
+        return got
+    return with_redraw(make, first_seed, f"{n} x {sum(atoms)}")
+
+
+def case_align(n, atoms, indices, first_seed):
+    def make(seed):
+        s = moved_ensemble(n, atoms, seed, 2)
+        out, left, gap = reference_align(s, indices)
+        if gap < HORN_BAND:
+            return None
+        return {"structures": s, "indices": np.asarray(indices, dtype=np.int32), "aligned": out, "centred_input": left, "horn_gap": np.float64(gap)}
+    return with_redraw(make, first_seed, f"align {n} x {sum(atoms)}")
+
+
+def case_mdc(n_structs, atoms, n, first_seed):
+    quadruplets = np.array([[0, 1, 12, 13], [2, 3, 14, 15], [4, 5, 16, 17]], dtype=np.int32)
+
+    def make(seed):
+        s = moved_ensemble(n_structs, atoms, seed, 2)
+        energies = np.random.default_rng(seed + 1).uniform(0.0, 30.0, size=n_structs)
+        RecordingKMeans.seed = seed
+        saved = tm.KMeans
+        tm.KMeans = RecordingKMeans
+        try:
+            out_e = tm.most_diverse_conformers(n, s.copy(), quadruplets, energies=energies)
+            rec = RecordingKMeans.last
+            out_d = tm.most_diverse_conformers(n, s.copy(), quadruplets)
+            rec_d = RecordingKMeans.last
+        finally:
+            tm.KMeans = saved
+        assert np.array_equal(rec["labels"], rec_d["labels"]) and np.array_equal(rec["X"], rec_d["X"])
+        n_kept = len(rec["X"])
+        aligned = rec["X"].reshape(n_kept, -1, 3)
+        pruned, mask = tm.prune_conformers_tfd(s.copy(), quadruplets)
+        _, left, gap = reference_align(np.ascontiguousarray(pruned), None)
+        got = kmeans_case(rec["X"], rec["X"][rec["init_rows"]])
+        pgap, egap = pick_guard(aligned, rec["labels"], rec["centers"], energies[:n_kept])
+        if got is None or gap < HORN_BAND or pgap < PICK_BAND or egap <= 0.0 or got["max_empty"] != 0:
+            return None
+        assert np.array_equal(got["labels"], rec["labels"])
+        got.update(structures=s, energies=energies, quadruplets=quadruplets, init_rows=rec["init_rows"], n=np.int32(n), tfd_mask=mask,
+                   out_energies=out_e, out_diverse=out_d, horn_gap=np.float64(gap), pick_gap=np.float64(pgap), energy_gap=np.float64(egap))
+        del got["init"]                                # (= X[init_rows])
+        return got
+    return with_redraw(make, first_seed, f"most_diverse_conformers {n_structs} x {sum(atoms)}")
+
+
+# ------------------------------------------------------------------------------------------------------- binding sites
+def binding_sites(names):
+    """The reference's modules that bind each name at import time (`from tscode.x import name`) or define it, as gen_install_sites.py
+    reads them: off the import lines."""
+    root = os.path.dirname(tm.__file__)
+    sites = {name: [] for name in names}
+    for fn in sorted(os.listdir(root)):
+        if not fn.endswith(".py"):
+            continue
+        tree = ast.parse(open(os.path.join(root, fn), encoding="utf-8").read())
+        mod = "tscode." + fn[:-3]
+        for node in tree.body:
+            if isinstance(node, ast.ImportFrom) and node.module and node.module.startswith("tscode"):
+                for a in node.names:
+                    if a.name in sites and a.asname in (None, a.name):
+                        sites[a.name].append(mod)
+            elif isinstance(node, ast.FunctionDef) and node.name in sites:
+                sites[node.name].append(mod)
+    return {k: sorted(v) for k, v in sites.items()}
+
+
+def save_npz(path, arrays):
+    """np.savez_compressed with fixed time stamps: a rerun writes the same bytes."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(arrays[name]), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+    print(f"wrote {path} ({os.path.getsize(path) / 1e6:.2f} MB)")
+    assert os.path.getsize(path) < 1 << 20
+
+
+def main():
+    files = {"a": {}, "b": {}, "c": {}, "d": {}}
+    meta = {"sklearn": sklearn.__version__, "numpy": np.__version__, "bands": {"margin": MARGIN_BAND, "pick": PICK_BAND, "horn": HORN_BAND}, "cases": {}}
+
+    def put(key, case, got):
+        meta["cases"][case] = {"file": f"G20{key}_diverse.npz",
+                               **{f: (float(got[f]) if isinstance(got[f], np.floating) else int(got[f]))
+                                  for f in ("seed", "margin", "max_empty", "n_iter", "horn_gap", "pick_gap", "energy_gap", "inertia") if f in got}}
+        for f, v in got.items():
+            files[key][f"{case}/{f}"] = v
+
+    put("a", "small", case_cluster(60, (6, 6), 5, 3, 2101))
+    put("a", "subset", case_align(40, (9, 9), [0, 2, 3, 7, 9, 10, 12, 16], 2102))
+    put("a", "pair", case_align(2, (10, 10), [], 2103))
+    put("b", "empty", case_cluster(400, (15, 15), 12, 10, 2104, far_centre=True))
+    put("c", "mdc", case_mdc(600, (12, 12), 20, 2105))
+    put("d", "wide", case_cluster(1200, (10, 10), 40, 10, 2106, keep_input=False))
+    meta["sites"] = binding_sites(["align_structures", "most_diverse_conformers"])
+    for key, arrays in files.items():
+        save_npz(os.path.join(HERE, f"G20{key}_diverse.npz"), arrays)
+    with open(os.path.join(HERE, "G20_diverse.json"), "w") as f:
+        json.dump(meta, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(meta["cases"], indent=1))
+
+
+if __name__ == "__main__":
+    main()

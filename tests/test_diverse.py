@@ -1,0 +1,507 @@
+"""Ensemble alignment, k-means and the diverse-conformer pick (tscode_amd.hypermolecule_class / kmeans / torsion_module) against
+G20 (tests/golden/gen_diverse.py): the reference's align_structures (tscode/hypermolecule_class.py:38-72) and
+most_diverse_conformers (tscode/torsion_module.py:849-924), and scikit-learn's Lloyd iteration from a recorded init.  No test
+imports scikit-learn: the yardstick of the large case is the NumPy restatement below, itself pinned to G20 on the CPU."""
+
+import ctypes as C
+import json
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT
+
+MARGIN_BAND, PICK_BAND, HORN_BAND = 1e-6, 1e-6, 1e-3          # the generator's guard bands
+COORD_TOL = 1e-9                                              # VAL_TOL of tests/test_gpu_parity.py: Kabsch values against the reference
+KMEANS_CASES = ("small", "empty", "mdc", "wide")
+SITES = ("tscode.hypermolecule_class", "tscode.embedder", "tscode.operators", "tscode.torsion_module", "tscode.ase_manipulations",
+         "tscode.mep_relaxer", "tscode.atropisomer_module", "tscode.automep")
+SYMBOLS = ("tsc_align_structures", "tsc_kmeans_lloyd", "tsc_kmeans_seed", "tsc_diverse_pick", "tsc_diverse_select")
+
+_G20 = {}
+
+
+def g20(case):
+    if not _G20:
+        _G20["meta"] = json.load(open(os.path.join(GOLDEN, "G20_diverse.json")))
+        _G20["files"] = {}
+    meta = _G20["meta"]["cases"][case]
+    fn = meta["file"]
+    if fn not in _G20["files"]:
+        _G20["files"][fn] = np.load(os.path.join(GOLDEN, fn), allow_pickle=False)
+    z = _G20["files"][fn]
+    d = {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(case + "/")}
+    if "X" not in d and "aligned" in d:
+        d["X"] = d["aligned"].reshape(len(d["aligned"]), -1)
+    if "init" not in d and "init_rows" in d:
+        d["init"] = d["X"][d["init_rows"]]
+    return types.SimpleNamespace(meta=meta, **d)
+
+
+# ------------------------------------------------------------------------------------------------------- the restatement
+def lloyd_restated(X, init, max_iter=300, tol=1e-4, matmul=False):
+    """scikit-learn's dense Lloyd iteration as include/tscode_hip.h states it (tsc_kmeans_lloyd).  Returns labels, centres,
+    inertia, n_iter, the smallest label margin (second-smallest minus smallest squared distance) over all iterations and rows,
+    and the most clusters empty at once.  matmul: distances as |x|^2 - 2 x.c + |c|^2 (the large case), else by differences,
+    one centre at a time."""
+    mean = X.mean(0)
+    Xc, Cc = X - mean, init - mean
+    tol_abs = np.mean(np.var(Xc, axis=0)) * tol
+    k, rows = len(Cc), np.arange(len(Xc))
+    xn = (Xc * Xc).sum(1)
+    margin, max_empty, old, strict = np.inf, 0, None, False
+
+    def assign(Cc):
+        if matmul:
+            d2 = xn[:, None] - 2.0 * (Xc @ Cc.T) + (Cc * Cc).sum(1)[None, :]
+        else:
+            d2 = np.stack([((Xc - c) ** 2).sum(1) for c in Cc], axis=1)
+        lab = d2.argmin(1)                                           # (the lowest centre on a tie)
+        own = d2[rows, lab]
+        if k > 1:
+            d2[rows, lab] = np.inf
+            gap = float((d2.min(1) - own).min())
+        else:
+            gap = np.inf
+        return lab, own, gap
+
+    for it in range(max_iter):
+        labels, own, m = assign(Cc)
+        margin = min(margin, m)
+        order = np.argsort(labels, kind="stable")
+        counts = np.bincount(labels, minlength=k).astype(np.float64)
+        sums = np.zeros_like(Cc)
+        starts = np.concatenate(([0], np.cumsum(counts).astype(np.int64)))
+        for c in range(k):
+            if counts[c]:
+                sums[c] = Xc[order[starts[c]:starts[c + 1]]].sum(0)
+        empty = np.flatnonzero(counts == 0)
+        max_empty = max(max_empty, len(empty))
+        if len(empty):
+            own_exact = ((Xc - Cc[labels]) ** 2).sum(1)
+            far = np.lexsort((rows, -own_exact))[:len(empty)]       # decreasing distance, the lower row on a tie
+            for e, f in zip(empty, far):
+                sums[labels[f]] -= Xc[f]
+                counts[labels[f]] -= 1
+                sums[e] = Xc[f]
+                counts[e] = 1
+        C_new = sums / counts[:, None]
+        shift = ((C_new - Cc) ** 2).sum()
+        Cc = C_new
+        if old is not None and np.array_equal(labels, old):
+            strict = True
+            break
+        if shift <= tol_abs:
+            break
+        old = labels
+    if not strict:
+        labels, own, m = assign(Cc)
+        margin = min(margin, m)
+    inertia = float(((Xc - Cc[labels]) ** 2).sum())
+    return labels.astype(np.int32), Cc + mean, inertia, it + 1, margin, max_empty
+
+
+def seed_restated(X, u):
+    """k-means++ without local trials as include/tscode_hip.h states it (tsc_kmeans_seed).  Also returns the smallest relative
+    distance of a target u_j * total to the running-sum boundaries next to it."""
+    N, k = len(X), len(u)
+    rows = [min(N - 1, int(u[0] * N))]
+    min_d2 = ((X - X[rows[0]]) ** 2).sum(1)
+    clear = np.inf
+    for j in range(1, k):
+        if j > 1:
+            min_d2 = np.minimum(min_d2, ((X - X[rows[-1]]) ** 2).sum(1))
+        run = np.cumsum(min_d2)
+        target = u[j] * run[-1]
+        i = int(np.searchsorted(run, target, side="right"))        # the first row whose running sum exceeds the target
+        clear = min(clear, abs(run[i] - target) / run[-1], abs(target - (run[i - 1] if i else 0.0)) / run[-1])
+        rows.append(i)
+    return np.array(rows, dtype=np.int32), clear
+
+
+def moved(x, seed):
+    """Every structure turned by a seeded random rotation about its centroid and shifted."""
+    rng = np.random.default_rng(seed)
+    q = rng.normal(size=(len(x), 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    w, a, b, c = q.T
+    rot = np.array([[1 - 2 * (b * b + c * c), 2 * (a * b - c * w), 2 * (a * c + b * w)],
+                    [2 * (a * b + c * w), 1 - 2 * (a * a + c * c), 2 * (b * c - a * w)],
+                    [2 * (a * c - b * w), 2 * (b * c + a * w), 1 - 2 * (a * a + b * b)]]).transpose(2, 0, 1)
+    cen = x.mean(axis=1, keepdims=True)
+    return np.ascontiguousarray(np.einsum("nij,naj->nai", rot, x - cen) + cen + rng.uniform(-5, 5, size=(len(x), 1, 3)))
+
+
+def kabsch_align_numpy(structures):
+    """align_structures on all atoms, vectorised: centre, C = ref^T tgt, SVD with the rmsd-1.4 sign fix, out = tgt @ U^T."""
+    s = structures - structures.mean(axis=1, keepdims=True)
+    Cm = np.einsum("ai,naj->nij", s[0], s)
+    V, S, W = np.linalg.svd(Cm)
+    flip = np.linalg.det(V) * np.linalg.det(W) < 0.0
+    V[flip, :, -1] *= -1.0
+    U = V @ W
+    out = np.einsum("nij,naj->nai", U, s)
+    out[0] = s[0]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------- CPU
+def test_g20_loads_and_its_guard_values_are_inside_the_bands():
+    meta = json.load(open(os.path.join(GOLDEN, "G20_diverse.json")))
+    assert meta["bands"] == {"margin": MARGIN_BAND, "pick": PICK_BAND, "horn": HORN_BAND}
+    assert set(meta["cases"]) == {"small", "subset", "pair", "empty", "mdc", "wide"}
+    for name in meta["cases"]:
+        c = g20(name)
+        assert os.path.getsize(os.path.join(GOLDEN, c.meta["file"])) < 1 << 20
+        assert float(c.horn_gap) >= HORN_BAND
+        if name in KMEANS_CASES:
+            N, D = c.X.shape
+            k = len(c.init)
+            assert c.labels.shape == (N,) and c.centers.shape == (k, D) and c.labels.min() >= 0 and c.labels.max() < k
+            assert float(c.margin) >= MARGIN_BAND and int(c.max_empty) <= 1
+        if hasattr(c, "aligned"):
+            assert c.aligned.shape == c.structures.shape == c.centred_input.shape
+    assert g20("small").X.shape == (60, 36) and g20("empty").X.shape == (400, 90) and g20("wide").X.shape == (1200, 60)
+    assert g20("mdc").structures.shape == (600, 24, 3) and len(g20("pair").structures) == 2 and len(g20("subset").indices) == 8
+    assert int(g20("empty").max_empty) == 1, "the case with a forced empty cluster has lost it"
+    m = g20("mdc")
+    assert float(m.pick_gap) >= PICK_BAND and float(m.energy_gap) > 0.0 and int(m.max_empty) == 0
+    assert m.out_energies.shape == m.out_diverse.shape == (20, 24, 3) and len(m.X) == int(m.tfd_mask.sum()) > 20
+
+
+@pytest.mark.parametrize("case", KMEANS_CASES)
+def test_restatement_reproduces_scikit_learn_on_g20(case):
+    c = g20(case)
+    for matmul in (False, True):
+        labels, centres, inertia, n_iter, margin, max_empty = lloyd_restated(c.X, c.init, matmul=matmul)
+        assert np.array_equal(labels, c.labels) and n_iter == int(c.n_iter)
+        assert np.abs(centres - c.centers).max() <= 1e-12
+        assert abs(inertia - float(c.inertia)) <= 1e-9 * float(c.inertia)
+        assert max_empty == int(c.max_empty) and margin >= MARGIN_BAND
+    assert lloyd_restated(c.X, c.init)[4] == pytest.approx(float(c.margin), rel=1e-6)
+
+
+def _fake_tscode():
+    mods = {}
+    for name in SITES:
+        m = types.ModuleType(name)
+        m.align_structures = lambda *a, **k: "reference"
+        m.prune_conformers_rmsd = lambda *a, **k: "reference"
+        mods[name] = m
+    mods["tscode.torsion_module"].most_diverse_conformers = lambda *a, **k: "reference"
+    return mods
+
+
+def test_install_diverse_patches_exactly_the_nine_sites():
+    import tscode_amd
+    import importlib
+    inst = importlib.import_module("tscode_amd.install")
+    assert "align_structures" not in inst._PATCHES and "most_diverse_conformers" not in inst._PATCHES
+    assert "align_structures" not in inst._WHOLE_ENSEMBLE and "most_diverse_conformers" not in inst._WHOLE_ENSEMBLE
+    recorded = json.load(open(os.path.join(GOLDEN, "G20_diverse.json")))["sites"]
+    assert {k: sorted(v[1]) for k, v in inst._DIVERSE_PATCHES.items()} == recorded, "the table differs from the reference's import lines"
+    mods = _fake_tscode()
+    try:
+        done = inst.install(modules=mods)
+        assert not [d for d in done if d[1] in inst._DIVERSE_PATCHES], "install() alone must not patch the diverse functions"
+        assert all(m.align_structures() == "reference" for m in mods.values())
+        inst.uninstall(modules=mods)
+        done = inst.install(modules=mods, diverse=True)
+        got = sorted(d for d in done if d[1] in inst._DIVERSE_PATCHES)
+        assert got == sorted([(s, "align_structures") for s in SITES] + [("tscode.torsion_module", "most_diverse_conformers")]) and len(got) == 9
+        assert all(m.align_structures is tscode_amd.align_structures for m in mods.values())
+        assert mods["tscode.torsion_module"].most_diverse_conformers is tscode_amd.most_diverse_conformers
+    finally:
+        inst.uninstall(modules=mods)
+    assert all(m.align_structures() == "reference" for m in mods.values())
+    assert mods["tscode.torsion_module"].most_diverse_conformers() == "reference"
+
+
+def test_limits_raise_valueerror_before_the_library_is_entered(monkeypatch):
+    import tscode_amd
+    from tscode_amd import hypermolecule_class, kmeans, torsion_module
+
+    def no_device(*a, **k):
+        raise AssertionError("the library was entered")
+    for mod in (hypermolecule_class, kmeans, torsion_module):
+        monkeypatch.setattr(mod, "get_engine", no_device)
+    X = np.random.default_rng(0).normal(size=(10, 6))
+    with pytest.raises(ValueError):
+        tscode_amd.kmeans_lloyd(X, np.zeros((0, 6)))                      # k = 0
+    with pytest.raises(ValueError):
+        tscode_amd.kmeans_lloyd(np.zeros((400, 6)), np.zeros((301, 6)))   # k = 301
+    with pytest.raises(ValueError):
+        tscode_amd.kmeans_lloyd(X, np.zeros((11, 6)))                     # k > N
+    with pytest.raises(ValueError):
+        tscode_amd.kmeans_lloyd(X, np.zeros((3, 5)))                      # init of the wrong shape
+    with pytest.raises(ValueError):
+        tscode_amd.kmeans_lloyd(X, np.zeros(6))
+    with pytest.raises(ValueError):
+        tscode_amd.kmeans_plusplus_rows(X, 0, seed=1)
+    with pytest.raises(ValueError):
+        tscode_amd.kmeans_plusplus_rows(X, 11, seed=1)
+    with pytest.raises(ValueError):
+        tscode_amd.kmeans_lloyd(np.zeros((4, 3 * 513)), np.zeros((2, 3 * 513)))
+    with pytest.raises(ValueError):
+        tscode_amd.align_structures(np.zeros((3, 513, 3)))                # 513 atoms
+    with pytest.raises(ValueError):
+        tscode_amd.align_structures(np.zeros((3, 5, 3)), indices=[0, 5])
+    big = np.zeros((4, 513, 3))
+    for k in (0, 301, 5):
+        with pytest.raises(ValueError):
+            tscode_amd.diverse_select(np.zeros((4, 5, 3)), k, init_rows=np.zeros(max(k, 1), dtype=np.int32))
+    with pytest.raises(ValueError):
+        tscode_amd.diverse_select(big, 2, init_rows=[0, 1])
+    with pytest.raises(ValueError):
+        tscode_amd.diverse_select(np.zeros((4, 5, 3)), 2, init_rows=[0, 4])
+
+
+def test_non_finite_input_raises_valueerror_before_the_library_is_entered(monkeypatch):
+    """One NaN in X makes every expanded distance NaN: scikit-learn refuses such input with a ValueError, and so does this package
+    (and the library, with TSC_ERR_INVALID) before any launch."""
+    import tscode_amd
+    from tscode_amd import hypermolecule_class, kmeans, torsion_module
+
+    def no_device(*a, **k):
+        raise AssertionError("the library was entered")
+    for mod in (hypermolecule_class, kmeans, torsion_module):
+        monkeypatch.setattr(mod, "get_engine", no_device)
+    rng = np.random.default_rng(1)
+    for bad in (np.nan, np.inf, -np.inf):
+        X = rng.normal(size=(12, 6))
+        init = X[:3].copy()
+        Xb = X.copy()
+        Xb[7, 2] = bad
+        with pytest.raises(ValueError):
+            tscode_amd.kmeans_lloyd(Xb, init)
+        initb = init.copy()
+        initb[1, 5] = bad
+        with pytest.raises(ValueError):
+            tscode_amd.kmeans_lloyd(X, initb)
+        with pytest.raises(ValueError):
+            tscode_amd.kmeans_plusplus_rows(Xb, 3, seed=0)
+        s = rng.normal(size=(8, 5, 3))
+        sb = s.copy()
+        sb[3, 4, 1] = bad
+        with pytest.raises(ValueError):
+            tscode_amd.align_structures(sb)
+        with pytest.raises(ValueError):
+            tscode_amd.diverse_select(sb, 2, init_rows=[0, 1])
+        with pytest.raises(ValueError):
+            tscode_amd.diverse_select(sb, 2, seed=0)
+    e = np.zeros(8)
+    e[2] = np.nan
+    with pytest.raises(ValueError):
+        tscode_amd.diverse_select(rng.normal(size=(8, 5, 3)), 2, init_rows=[0, 1], energies=e)
+
+
+def test_the_five_symbols_are_in_the_header_and_the_prototype_table():
+    from tscode_amd import _lib
+    header = open(os.path.join(ROOT, "include", "tscode_hip.h")).read()
+    for s in SYMBOLS:
+        assert re.search(r"^int " + s + r"\(", header, re.M), f"{s} is not declared in include/tscode_hip.h"
+        assert s in _lib.EXPORTED_SYMBOLS
+    from tscode_amd import build
+    assert "diverse.hip" in build.SOURCES and "diverse.hpp" in build.HEADERS
+
+
+# ------------------------------------------------------------------------------------------------------- GPU
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ("small", "subset", "pair", "empty"))
+def test_align_structures_matches_the_reference(case):
+    import tscode_amd
+    c = g20(case)
+    work = c.structures.copy()
+    indices = list(c.indices) if hasattr(c, "indices") else None
+    out = tscode_amd.align_structures(work, indices)
+    print(f"{case}: |out - reference| = {np.abs(out - c.aligned).max():.3e}, |centred input - reference| = {np.abs(work - c.centred_input).max():.3e}")
+    assert out is not work and out.shape == c.aligned.shape
+    assert np.abs(out - c.aligned).max() <= COORD_TOL
+    assert np.abs(work - c.centred_input).max() <= COORD_TOL, "the caller's array is left centred by the reference (:53-55)"
+
+
+@pytest.mark.gpu
+def test_align_structures_on_a_collinear_index_set_is_finite_and_proper():
+    import tscode_amd
+    rng = np.random.default_rng(5)
+    s = rng.normal(size=(6, 9, 3))
+    s[:, :3] = np.array([[0.0, 0, 0], [1.0, 0, 0], [2.5, 0, 0]]) @ np.eye(3) + rng.normal(size=(6, 1, 3))     # three atoms on a line
+    out = tscode_amd.align_structures(s.copy(), [0, 1, 2])
+    assert np.isfinite(out).all()
+    cen = s - s[:, :3].mean(axis=1, keepdims=True)
+    for t in range(1, 6):     # a proper rotation keeps every distance and the handedness
+        R, *_ = np.linalg.lstsq(cen[t], out[t], rcond=None)
+        assert np.abs(R.T @ R - np.eye(3)).max() < 1e-9 and np.linalg.det(R) > 0.0
+    one = tscode_amd.align_structures(s.copy(), [4])          # a single atom: S = 0
+    assert np.isfinite(one).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", KMEANS_CASES)
+def test_kmeans_lloyd_matches_scikit_learn_on_g20(case):
+    import tscode_amd
+    c = g20(case)
+    labels, centres, inertia, n_iter = tscode_amd.kmeans_lloyd(c.X, c.init)
+    print(f"{case}: n_iter {n_iter} (recorded {int(c.n_iter)}), labels differing {int((labels != c.labels).sum())}, "
+          f"|centres - recorded| = {np.abs(centres - c.centers).max():.3e}, inertia rel. {abs(inertia - float(c.inertia)) / float(c.inertia):.3e}")
+    assert np.array_equal(labels, c.labels) and n_iter == int(c.n_iter)
+    assert np.abs(centres - c.centers).max() <= COORD_TOL
+    assert abs(inertia - float(c.inertia)) <= 1e-9 * float(c.inertia)
+
+
+@pytest.mark.gpu
+def test_most_diverse_conformers_matches_the_reference_in_both_modes():
+    import tscode_amd
+    c = g20("mdc")
+    n = int(c.n)
+    assert np.array_equal(tscode_amd.prune_conformers_tfd(c.structures.copy(), c.quadruplets)[1], c.tfd_mask), "the TFD prune in front differs"
+    out_e = tscode_amd.most_diverse_conformers(n, c.structures.copy(), c.quadruplets, energies=c.energies, init_rows=c.init_rows)
+    out_d = tscode_amd.most_diverse_conformers(n, c.structures.copy(), c.quadruplets, init_rows=c.init_rows)
+    for name, got, want in (("energies", out_e, c.out_energies), ("diverse", out_d, c.out_diverse)):
+        assert got.shape == want.shape, name
+        print(f"most_diverse_conformers ({name}): |out - reference| = {np.abs(got - want).max():.3e}")
+        assert np.abs(got - want).max() <= COORD_TOL, name
+    # the default path: seeds drawn on the aligned features, reproducible for a seed
+    a = tscode_amd.most_diverse_conformers(n, c.structures.copy(), c.quadruplets, seed=11)
+    b = tscode_amd.most_diverse_conformers(n, c.structures.copy(), c.quadruplets, seed=11)
+    assert a.shape == (n, 24, 3) and np.array_equal(a, b)
+
+
+@pytest.mark.gpu
+def test_most_diverse_conformers_early_returns():
+    import tscode_amd
+    c = g20("mdc")
+    few = c.structures[:15]
+    assert tscode_amd.most_diverse_conformers(20, few, c.quadruplets) is few                          # :859
+    base = c.structures[c.tfd_mask][:100]
+    twice = np.concatenate([base, base])                                                              # every structure and an exact copy of it
+    pruned = tscode_amd.most_diverse_conformers(150, twice.copy(), c.quadruplets)                    # :875: len <= n after the TFD prune
+    assert len(pruned) <= 150 < len(twice)
+    assert np.array_equal(pruned, tscode_amd.prune_conformers_tfd(twice.copy(), c.quadruplets)[0]), "returned as pruned: not aligned, not clustered"
+    s = np.random.default_rng(3).normal(size=(900, 4, 3))
+    np.random.seed(77)
+    want = s[np.sort(np.random.choice(900, size=301))]                                                # :863-865
+    np.random.seed(77)
+    assert np.array_equal(tscode_amd.most_diverse_conformers(301, s, c.quadruplets[:0]), want)
+
+
+def _scale_case():
+    from tscode_amd.synthetic import make_ensemble
+    s = moved(make_ensemble(20000, (25, 25), seed=2020, children=10).poses(), 2020)
+    rows = np.random.default_rng(2020).choice(len(s), 100, replace=False).astype(np.int32)
+    return s, rows
+
+
+@pytest.mark.gpu
+def test_scale_20000_structures_k100_against_the_restatement():
+    import tscode_amd
+    s, rows = _scale_case()
+    want_aligned = kabsch_align_numpy(s)
+    X = want_aligned.reshape(len(s), -1)
+    labels, centres, inertia, n_iter, margin, max_empty = lloyd_restated(X, X[rows], matmul=True)
+    print(f"scale: restatement n_iter {n_iter}, margin {margin:.3e}, max_empty {max_empty}")
+    assert margin >= MARGIN_BAND, "the yardstick's own labels are not settled on this input"
+    aligned, got_labels, picked, got_rows, got_iter = tscode_amd.diverse_select(s, 100, init_rows=rows)
+    print(f"scale: |aligned - numpy Kabsch| = {np.abs(aligned - want_aligned).max():.3e}, n_iter {got_iter}, "
+          f"labels differing {int((got_labels != labels).sum())}")
+    assert np.abs(aligned - want_aligned).max() <= COORD_TOL
+    assert np.array_equal(got_labels, labels) and got_iter == n_iter
+    assert np.array_equal(got_rows, rows)
+    assert ((picked >= 0) == (np.bincount(labels, minlength=100) > 0)).all() and np.array_equal(labels[picked[picked >= 0]], np.flatnonzero(picked >= 0))
+    l2, c2, i2, n2 = tscode_amd.kmeans_lloyd(X, X[rows])
+    assert np.array_equal(l2, labels) and n2 == n_iter and np.abs(c2 - centres).max() <= COORD_TOL and abs(i2 - inertia) <= 1e-9 * inertia
+
+
+@pytest.mark.gpu
+def test_diverse_select_is_deterministic_to_the_bit():
+    import tscode_amd
+    c = g20("mdc")
+    s = np.ascontiguousarray(c.structures[c.tfd_mask])
+    for kw in (dict(init_rows=c.init_rows), dict(seed=4), dict(init_rows=c.init_rows, energies=c.energies[:len(s)])):
+        a = tscode_amd.diverse_select(s, 20, **kw)
+        b = tscode_amd.diverse_select(s, 20, **kw)
+        for x, y in zip(a[:4], b[:4]):
+            assert x.tobytes() == y.tobytes()
+        assert a[4] == b[4]
+
+
+@pytest.mark.gpu
+def test_tsc_diverse_pick_follows_the_reference_rules():
+    from tscode_amd import _lib
+    from tscode_amd.engine import get_engine
+    c = g20("mdc")
+    n_kept, k = len(c.X), 20
+    aligned = np.ascontiguousarray(c.X.reshape(n_kept, -1, 3))
+    cen = c.centers.reshape(k, -1, 3)
+    r = np.arange(k)
+    want_d, want_e = [], []
+    for cl in range(k):
+        members = np.flatnonzero(c.labels == cl)
+        cum = [np.sum(np.linalg.norm(cen[r != p] - aligned[m], axis=2)) for p, m in enumerate(members)]     # :919 as written
+        want_d.append(members[int(np.argmax(cum))])
+        want_e.append(members[int(np.argmin(c.energies[members]))])
+    eng = get_engine()
+    for energies, want in ((None, want_d), (np.ascontiguousarray(c.energies[:n_kept]), want_e)):
+        picked = np.empty(k, dtype=np.int32)
+        _lib.check(eng.lib.tsc_diverse_pick(eng._h, _lib.ptr(aligned), C.c_int64(n_kept), C.c_int(aligned.shape[1]), _lib.ptr(np.ascontiguousarray(c.labels)),
+                                            _lib.ptr(np.ascontiguousarray(c.centers)), C.c_int(k), _lib.ptr(energies), _lib.ptr(picked)))
+        assert picked.tolist() == [int(w) for w in want]
+    labels = np.where(c.labels == 7, 8, c.labels).astype(np.int32)             # cluster 7 emptied
+    picked = np.empty(k, dtype=np.int32)
+    _lib.check(eng.lib.tsc_diverse_pick(eng._h, _lib.ptr(aligned), C.c_int64(n_kept), C.c_int(aligned.shape[1]), _lib.ptr(labels),
+                                        _lib.ptr(np.ascontiguousarray(c.centers)), C.c_int(k), None, _lib.ptr(picked)))
+    assert picked[7] == -1 and (np.delete(picked, 7) >= 0).all()
+
+
+@pytest.mark.gpu
+def test_library_refuses_the_limits_with_an_error_code():
+    from tscode_amd import _lib
+    from tscode_amd.engine import get_engine
+    eng = get_engine()
+    X = np.zeros((8, 6))
+    out_l, out_c, inertia, n_iter = np.empty(8, np.int32), np.empty((301, 6)), C.c_double(), C.c_int()
+    for k in (0, 301, 9):
+        rc = eng.lib.tsc_kmeans_lloyd(eng._h, _lib.ptr(X), C.c_int64(8), C.c_int64(6), _lib.ptr(np.zeros((max(k, 1), 6))), C.c_int(k), C.c_int(300),
+                                      C.c_double(1e-4), _lib.ptr(out_l), _lib.ptr(out_c), C.byref(inertia), C.byref(n_iter), None)
+        assert rc == -1
+    big = np.zeros((2, 513, 3))
+    assert eng.lib.tsc_align_structures(eng._h, _lib.ptr(big), C.c_int64(2), C.c_int(513), None, C.c_int(0), _lib.ptr(np.empty_like(big))) == -1
+    # non-finite input: refused before any launch, on every entry that takes coordinates
+    Xb = np.random.default_rng(2).normal(size=(8, 6))
+    init = Xb[:2].copy()
+    Xb[5, 1] = np.nan
+    args = lambda X, ini: (eng._h, _lib.ptr(X), C.c_int64(8), C.c_int64(6), _lib.ptr(ini), C.c_int(2), C.c_int(300), C.c_double(1e-4),   # noqa: E731
+                           _lib.ptr(out_l), _lib.ptr(out_c), C.byref(inertia), C.byref(n_iter), None)
+    assert eng.lib.tsc_kmeans_lloyd(*args(Xb, init)) == -1
+    assert eng.lib.tsc_kmeans_lloyd(*args(np.zeros((8, 6)), np.full((2, 6), np.inf))) == -1
+    rows = np.empty(2, np.int32)
+    assert eng.lib.tsc_kmeans_seed(eng._h, _lib.ptr(Xb), C.c_int64(8), C.c_int64(6), C.c_int(2), _lib.ptr(np.array([0.5, 0.5])), _lib.ptr(rows)) == -1
+    assert eng.lib.tsc_kmeans_seed(eng._h, _lib.ptr(np.zeros((8, 6))), C.c_int64(8), C.c_int64(6), C.c_int(2), _lib.ptr(np.array([0.5, 1.0])),
+                                   _lib.ptr(rows)) == -1
+    sb = np.zeros((8, 2, 3))
+    sb[1, 1, 1] = np.inf
+    assert eng.lib.tsc_align_structures(eng._h, _lib.ptr(sb), C.c_int64(8), C.c_int(2), None, C.c_int(0), _lib.ptr(np.empty_like(sb))) == -1
+    lab, picked, it = np.empty(8, np.int32), np.empty(2, np.int32), C.c_int()
+    assert eng.lib.tsc_diverse_select(eng._h, _lib.ptr(sb), C.c_int64(8), C.c_int(2), _lib.ptr(np.array([0, 1], np.int32)), None, C.c_int(2), None,
+                                      C.c_int(300), C.c_double(1e-4), _lib.ptr(np.empty_like(sb)), _lib.ptr(lab), _lib.ptr(picked), C.byref(it)) == -1
+    assert eng.lib.tsc_diverse_select(eng._h, _lib.ptr(np.zeros((8, 2, 3))), C.c_int64(8), C.c_int(2), _lib.ptr(np.zeros(2, np.int32)),
+                                      _lib.ptr(np.array([0.5, 1.5])), C.c_int(2), None, C.c_int(300), C.c_double(1e-4), _lib.ptr(np.empty_like(sb)),
+                                      _lib.ptr(lab), _lib.ptr(picked), C.byref(it)) == -1
+
+
+@pytest.mark.gpu
+def test_kmeans_plusplus_rows_follows_the_stated_rule():
+    import tscode_amd
+    from tscode_amd.kmeans import seed_uniforms
+    c = g20("wide")
+    for seed in (1, 2, 3):
+        u = seed_uniforms(40, seed)
+        want, clear = seed_restated(c.X, u)
+        assert clear >= 1e-9, "a target lies on a running-sum boundary: the parallel scan may round to either side"
+        rows = tscode_amd.kmeans_plusplus_rows(c.X, 40, seed)
+        assert np.array_equal(rows, tscode_amd.kmeans_plusplus_rows(c.X, 40, seed))
+        assert len(set(rows.tolist())) == 40
+        assert np.array_equal(rows, want)

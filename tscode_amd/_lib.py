@@ -141,6 +141,14 @@ _SIGNATURES = {
     "tsc_rot_corr_end": (C.c_int, [_vp, _vp]),
     "tsc_rot_corr_destroy": (C.c_int, [_vp]),
     "tsc_rot_corr_pairs": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
+    "tsc_align_structures": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, _vp]),
+    "tsc_kmeans_lloyd": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, c_f64p, C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int)]),
+    "tsc_kmeans_seed": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp]),
+    "tsc_diverse_pick": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
+    "tsc_diverse_select": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp,
+                                     C.POINTER(C.c_int)]),
+    "tsc_diverse_timings": (C.c_int, [_vp, c_f32p]),
     "tsc_pipeline_dev": (C.c_int, [_vp, _vp, c_i64p, c_i32p, c_i32p, C.c_int, _vp, _vp, _vp, C.c_int64, c_i32p, C.c_int,
                                    C.c_double, C.c_int64, C.c_double, C.c_int, _vp, _vp, _vp, _vp, c_i64p, c_i64p,
                                    C.POINTER(PassStats), C.POINTER(C.c_int), c_f32p]),

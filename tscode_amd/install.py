@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import sys
 
-from . import algebra, embeds, numba_functions, optimization_methods, rmsd_pruning, rot_corr, torsion_module
+from . import algebra, embeds, hypermolecule_class, numba_functions, optimization_methods, rmsd_pruning, rot_corr, torsion_module
 
 # attribute -> (replacement, modules that bind it)
 _PATCHES = {
@@ -53,22 +53,34 @@ _ROT_CORR_PATCHES = {
                                        ("tscode.torsion_module", "tscode.embedder", "tscode.operators")),
 }
 
+# Opt-in (install(diverse=True)): the end of a conformational search (tscode/torsion_module.py:817, :837) and the alignment that
+# embedder.py runs on the whole ensemble at every checkpoint (:1195, 1405, 1515, 1581, 1749, 1818, 2045).  align_structures is bound
+# by name in eight modules, most_diverse_conformers only where it is defined.
+_DIVERSE_PATCHES = {
+    "align_structures": (hypermolecule_class.align_structures,
+                         ("tscode.hypermolecule_class", "tscode.embedder", "tscode.operators", "tscode.torsion_module",
+                          "tscode.ase_manipulations", "tscode.mep_relaxer", "tscode.atropisomer_module", "tscode.automep")),
+    "most_diverse_conformers": (torsion_module.most_diverse_conformers, ("tscode.torsion_module",)),
+}
+
 _saved = {}
 
 
-def install(modules=None, per_item=False, rot_corr=False):
+def install(modules=None, per_item=False, rot_corr=False, diverse=False):
     """Replace the hot-path functions in every already-imported tscode module: by default those that work on a whole ensemble
     per call (prune_conformers_rmsd, prune_conformers_tfd, get_moi_similarity_matches, _score_embed_poses) and the two embed
     loops (string_embed, cyclical_embed: one GPU call each instead of one Python iteration per pose); with
     ``per_item=True`` also the per-pose / per-pair ones (compenetration_check, get_embed, rmsd_and_max_numba, ...), which are
     equivalent but slower than the reference's jitted code when called one item at a time; with ``rot_corr=True`` also
-    prune_conformers_rmsd_rot_corr (_ROT_CORR_PATCHES).
+    prune_conformers_rmsd_rot_corr (_ROT_CORR_PATCHES); with ``diverse=True`` also align_structures and most_diverse_conformers
+    (_DIVERSE_PATCHES).
     Returns the list of (module, attribute) pairs that were patched."""
     mods = sys.modules if modules is None else modules
     done = []
-    table = list(_PATCHES.items()) + (list(_ROT_CORR_PATCHES.items()) if rot_corr else [])
+    table = (list(_PATCHES.items()) + (list(_ROT_CORR_PATCHES.items()) if rot_corr else []) +
+             (list(_DIVERSE_PATCHES.items()) if diverse else []))
     for attr, (fn, names) in table:
-        if not per_item and attr not in _WHOLE_ENSEMBLE and attr not in _ROT_CORR_PATCHES:
+        if not per_item and attr not in _WHOLE_ENSEMBLE and attr not in _ROT_CORR_PATCHES and attr not in _DIVERSE_PATCHES:
             continue
         for name in names:
             mod = mods.get(name)
