@@ -606,6 +606,43 @@ int tsc_diverse_select(tsc_ctx *ctx, const double *structures, int64_t N, int n_
                        int *n_iter);
 int tsc_diverse_timings(tsc_ctx *ctx, float *ms4);
 
+/* Bond graphs from distances and their difference to an expected graph, for a whole ensemble per call (csrc/topology.hpp): the
+ * topology test the reference applies to every structure that survives the embed and prune steps.
+ *   replaces   graphize                 tscode/graph_manipulations.py:33-55 (d_min_bond :28-29)
+ *              molecule_check           tscode/utils.py:341-353
+ *              scramble_check           tscode/utils.py:355-387
+ *              get_double_bonds_indices tscode/utils.py:293-314 (the same scan with another threshold table)
+ * Atoms i < j of a structure are BONDED iff both are active and sqrt(dx dx + dy dy + dz dz) < thr[class_i][class_j], in fp64 with the
+ * reference's roundings (the kernel compares dx dx + dy dy + dz dz, formed without fused multiply-add, with the smallest double whose
+ * square root reaches the threshold: the same verdict).  A threshold of 0 means "never bonded".  The self loops graphize puts on the
+ * diagonal are not formed here: only the strict upper triangle is, and every consumer of the reference drops a == b.
+ *   coords      f64[n_structs, n_atoms, 3]; n_atoms 1 .. 512.  Non-finite coordinates are not refused: such an atom is bonded to nothing.
+ *   atom_class  u8[n_atoms], each < n_classes (1 .. 16): the ensemble shares its elements, so a threshold depends on the class pair only.
+ *   thr         f64[n_classes, n_classes], finite and >= 0; read as given (the caller makes it symmetric).
+ *   active      u8[n_atoms] or NULL (all): graphize's mask.
+ *   ref_bits    u64[n_atoms, W], W = ceil(n_atoms / 64), or NULL (no bonds): the expected bonds, bit (j & 63) of word j >> 6 of row i for
+ *               i < j; bits outside the strict upper triangle are refused.  Expected bonds that touch an inactive atom count as broken.
+ *   excluded    atoms whose pairs are not counted: i32[n_excl] shared by all structures (excl_per_struct == 0) or
+ *               i32[n_structs, n_excl] (excl_per_struct != 0); -1 = unused slot; n_excl 0 .. 16.
+ *   care(i, j)  = i < j and neither atom excluded.  formed = #{care & bonded & ~ref}, broken = #{care & ~bonded & ref},
+ *   mask[s]     = formed + broken <= max_newbonds.  mask u8[n_structs] is always written; formed i32[n_structs], broken i32[n_structs]
+ *               and adj u64[n_structs, n_atoms, W] (the bonds found, laid out as ref_bits, excluded atoms included) where given.
+ * tsc_bond_delta takes host arrays.  tsc_bond_delta_dev: coords, excluded (when per structure), mask, formed, broken and adj are device
+ * pointers, the small tables host pointers; a per-structure excluded index outside 0 .. n_atoms-1 cannot be refused there and is an unused
+ * slot; the call is enqueued on the context's stream and, when ref_bits is given, waits for it.
+ * Refused with TSC_ERR_INVALID before any launch: null required pointers, n_atoms outside 1 .. 512, n_classes outside 1 .. 16, a class
+ * >= n_classes, a negative or non-finite threshold, n_excl > 16, an excluded index >= n_atoms or < -1 (host arrays).  n_structs == 0
+ * succeeds and writes nothing.
+ *   tsc_topology_timings  under the context option "pass_timing" >= 1 the two calls time their kernel with events (and synchronise for
+ *                         it): *ms = that time for the calling thread's latest call, -1 where it took none. */
+int tsc_bond_delta(tsc_ctx *ctx, const double *coords, int64_t n_structs, int n_atoms, const uint8_t *atom_class, const double *thr,
+                   int n_classes, const uint8_t *active, const uint64_t *ref_bits, const int32_t *excluded, int n_excl,
+                   int excl_per_struct, int64_t max_newbonds, uint8_t *mask, int32_t *formed, int32_t *broken, uint64_t *adj);
+int tsc_bond_delta_dev(tsc_ctx *ctx, const double *coords, int64_t n_structs, int n_atoms, const uint8_t *atom_class, const double *thr,
+                       int n_classes, const uint8_t *active, const uint64_t *ref_bits, const int32_t *excluded, int n_excl,
+                       int excl_per_struct, int64_t max_newbonds, uint8_t *mask, int32_t *formed, int32_t *broken, uint64_t *adj);
+int tsc_topology_timings(tsc_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,10 @@ from .algebra import (align_vec_pair, all_dists, norm, norm_of, quaternion_to_ro
                       rot_mat_from_pointer, rotation_matrix_from_vectors, transform_coords, vec_angle)
 from .embeds import (EmbedTrace, cyclical_embed_batch, cyclical_embed_params, embed_batch, filter_angular_groups, get_embed,  # noqa: F401
                      string_embed_batch, string_embed_params, string_embed_poses)
-from .utils import TriangleError, cartesian_product, polygonize  # noqa: F401
+from .utils import (TriangleError, cartesian_product, get_double_bonds_indices, molecule_check, polygonize,  # noqa: F401
+                    scramble_check)
+from .graph_manipulations import (bond_graph_batch, bond_tables, covalent_radii, d_min_bond, double_bonds_batch,  # noqa: F401
+                                  edges_from_bits, graphize, molecule_check_mask, pack_edges, scramble_mask)
 from .engine import Engine, FragmentSet, device_count, get_engine  # noqa: F401
 from .install import install, uninstall  # noqa: F401
 from .numba_functions import (_get_tf_mat, compenetration_check, compenetration_mask, count_clashes, get_torsion_fingerprint,  # noqa: F401

@@ -431,6 +431,56 @@ class Engine:
                                               C.c_double(thresh), C.c_int64(int(max_clashes)), ptr(ok)))
         return ok
 
+    # ---- topology ---------------------------------------------------------------------------
+    def bond_delta(self, coords, classes, thr, active=None, ref_bits=None, excluded=None, max_newbonds=0, want_counts=False, want_adj=False,
+                   checked=False):
+        """tsc_bond_delta on host arrays (include/tscode_hip.h): the bonds of every structure of coords f64[N, n, 3] from the class
+        table thr f64[T, T], compared with the expected bonds ref_bits u64[n, W].  excluded: i32[E] shared or i32[N, E] per structure.
+        Returns {"mask": bool[N]} plus "formed" / "broken" i32[N] (want_counts) and "adj" u64[N, n, W] (want_adj)."""
+        if not checked:
+            from .graph_manipulations import check_bond_delta_args
+            coords, classes, thr, active, ref_bits, excluded = check_bond_delta_args(coords, classes, thr, active, ref_bits, excluded)
+        n_structs, n = coords.shape[0], coords.shape[1]
+        mask = np.zeros(n_structs, dtype=np.uint8)
+        formed = np.zeros(n_structs, dtype=np.int32) if want_counts else None
+        broken = np.zeros(n_structs, dtype=np.int32) if want_counts else None
+        adj = np.zeros((n_structs, n, (n + 63) // 64), dtype=np.uint64) if want_adj else None
+        n_excl = 0 if excluded is None else excluded.shape[-1]
+        check(self.lib.tsc_bond_delta(self._h, ptr(coords), C.c_int64(n_structs), C.c_int(n), ptr(classes), ptr(thr), C.c_int(len(thr)), ptr(active),
+                                      ptr(ref_bits), ptr(excluded), C.c_int(n_excl), C.c_int(int(excluded is not None and excluded.ndim == 2)),
+                                      C.c_int64(int(max_newbonds)), ptr(mask), ptr(formed), ptr(broken), ptr(adj)))
+        out = {"mask": mask.astype(bool)}
+        if want_counts:
+            out["formed"], out["broken"] = formed, broken
+        if want_adj:
+            out["adj"] = adj
+        return out
+
+    def bond_delta_dev(self, coords, n_structs, n_atoms, classes, thr, active, ref_bits, excluded, excl_per_struct, max_newbonds, mask,
+                       formed=None, broken=None, adj=None):
+        """tsc_bond_delta_dev: coords, mask, formed, broken, adj (and excluded i32[N, E] when excl_per_struct) on the device; classes
+        u8[n], thr f64[T, T], active u8[n] | None, ref_bits u64[n, W] | None (and excluded i32[E] otherwise) NumPy arrays."""
+        classes = np.ascontiguousarray(classes, dtype=np.uint8)
+        thr = np.ascontiguousarray(thr, dtype=np.float64)
+        active = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
+        ref_bits = None if ref_bits is None else np.ascontiguousarray(ref_bits, dtype=np.uint64)
+        if excluded is None:
+            n_excl = 0
+        elif excl_per_struct:
+            n_excl = int(excluded.shape[-1])
+        else:
+            excluded = np.ascontiguousarray(excluded, dtype=np.int32).ravel()
+            n_excl = len(excluded)
+        check(self.lib.tsc_bond_delta_dev(self._h, ptr(coords), C.c_int64(n_structs), C.c_int(n_atoms), ptr(classes), ptr(thr), C.c_int(len(thr)),
+                                          ptr(active), ptr(ref_bits), ptr(excluded), C.c_int(n_excl), C.c_int(int(bool(excl_per_struct))),
+                                          C.c_int64(int(max_newbonds)), ptr(mask), ptr(formed), ptr(broken), ptr(adj)))
+
+    def topology_kernel_ms(self) -> float:
+        """tsc_topology_timings: the kernel time of this thread's latest bond_delta / bond_delta_dev under set_option("pass_timing", 1)."""
+        ms = C.c_float()
+        check(self.lib.tsc_topology_timings(self._h, C.byref(ms)))
+        return ms.value
+
     def prune_heavy(self, heavy, rmsd_thr=0.5, mode=0):
         """prune_conformers_rmsd on the heavy-atom array f64[N, h, 3]. Returns (mask bool[N], per-pass stats)."""
         heavy = np.ascontiguousarray(heavy, dtype=np.float64)

@@ -11,7 +11,8 @@ from __future__ import annotations
 
 import sys
 
-from . import algebra, embeds, hypermolecule_class, numba_functions, optimization_methods, rmsd_pruning, rot_corr, torsion_module
+from . import algebra, embeds, graph_manipulations, hypermolecule_class, numba_functions, optimization_methods, rmsd_pruning, rot_corr, torsion_module
+from . import utils
 
 # attribute -> (replacement, modules that bind it)
 _PATCHES = {
@@ -63,24 +64,44 @@ _DIVERSE_PATCHES = {
     "most_diverse_conformers": (torsion_module.most_diverse_conformers, ("tscode.torsion_module",)),
 }
 
+# Opt-in (install(topology=True)): the topology checks the reference applies to every structure that survives the embed and prune steps
+# (tscode/embedder.py:1489, 1725, tscode/optimization_methods.py:115-117, tscode/ase_manipulations.py:286, 342-344, 830, ...).  The sites
+# are the ones tests/golden/gen_topology.py records from the reference's import lines (G21_topology_sites.json).  Off by default until
+# the per-call latency has a number from hardware (tools/dropin_latency.py).
+_TOPOLOGY_PATCHES = {
+    "graphize": (graph_manipulations.graphize,
+                 ("tscode.ase_manipulations", "tscode.atropisomer_module", "tscode.embedder", "tscode.graph_manipulations",
+                  "tscode.hypermolecule_class", "tscode.operators", "tscode.pka", "tscode.torsion_module", "tscode.utils")),
+    "molecule_check": (utils.molecule_check,
+                       ("tscode.ase_manipulations", "tscode.atropisomer_module", "tscode.operators", "tscode.optimization_methods",
+                        "tscode.utils")),
+    "scramble_check": (utils.scramble_check,
+                       ("tscode.ase_manipulations", "tscode.calculators._openbabel", "tscode.embedder", "tscode.optimization_methods",
+                        "tscode.utils")),
+    "get_double_bonds_indices": (utils.get_double_bonds_indices, ("tscode.ase_manipulations", "tscode.torsion_module", "tscode.utils")),
+}
+
+_OPT_IN = (_ROT_CORR_PATCHES, _DIVERSE_PATCHES, _TOPOLOGY_PATCHES)
+
 _saved = {}
 
 
-def install(modules=None, per_item=False, rot_corr=False, diverse=False):
+def install(modules=None, per_item=False, rot_corr=False, diverse=False, topology=False):
     """Replace the hot-path functions in every already-imported tscode module: by default those that work on a whole ensemble
     per call (prune_conformers_rmsd, prune_conformers_tfd, get_moi_similarity_matches, _score_embed_poses) and the two embed
     loops (string_embed, cyclical_embed: one GPU call each instead of one Python iteration per pose); with
     ``per_item=True`` also the per-pose / per-pair ones (compenetration_check, get_embed, rmsd_and_max_numba, ...), which are
     equivalent but slower than the reference's jitted code when called one item at a time; with ``rot_corr=True`` also
     prune_conformers_rmsd_rot_corr (_ROT_CORR_PATCHES); with ``diverse=True`` also align_structures and most_diverse_conformers
-    (_DIVERSE_PATCHES).
+    (_DIVERSE_PATCHES); with ``topology=True`` also graphize, molecule_check, scramble_check and get_double_bonds_indices
+    (_TOPOLOGY_PATCHES).
     Returns the list of (module, attribute) pairs that were patched."""
     mods = sys.modules if modules is None else modules
     done = []
     table = (list(_PATCHES.items()) + (list(_ROT_CORR_PATCHES.items()) if rot_corr else []) +
-             (list(_DIVERSE_PATCHES.items()) if diverse else []))
+             (list(_DIVERSE_PATCHES.items()) if diverse else []) + (list(_TOPOLOGY_PATCHES.items()) if topology else []))
     for attr, (fn, names) in table:
-        if not per_item and attr not in _WHOLE_ENSEMBLE and attr not in _ROT_CORR_PATCHES and attr not in _DIVERSE_PATCHES:
+        if not per_item and attr not in _WHOLE_ENSEMBLE and not any(attr in t for t in _OPT_IN):
             continue
         for name in names:
             mod = mods.get(name)

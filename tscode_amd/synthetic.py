@@ -23,7 +23,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-__all__ = ["Ensemble", "make_fragment", "make_ensemble", "make_unscreenable", "CONFIGS", "make_config", "quat_to_mat", "make_rot_corr_ensemble"]
+__all__ = ["Ensemble", "make_fragment", "make_ensemble", "make_unscreenable", "CONFIGS", "make_config", "quat_to_mat", "make_rot_corr_ensemble", "make_chain_ensemble",
+           "CHAIN_ELEMENTS", "CHAIN_SIGMAS"]
 
 
 def make_fragment(rng: np.random.Generator, n_atoms: int, step: float = 1.5, min_dist: float = 1.2) -> np.ndarray:
@@ -250,3 +251,36 @@ def make_rot_corr_ensemble(base, torsions, angles, move_masks, n_clusters, per_c
             labels.append(c)
     perm = rng.permutation(len(out))
     return np.array(out)[perm], np.array(labels)[perm]
+
+
+# ---- chains for the topology checks (tscode_amd.graph_manipulations; fixtures G21) ---------------------------------------------
+CHAIN_ELEMENTS = (6, 6, 8, 7, 6)                 # C, C, O, N, C, repeating
+CHAIN_SIGMAS = (0.02, 0.05, 0.08, 0.12)          # A: from "every bond survives" to "hardly any structure keeps its graph"
+
+
+def make_chain(rng: np.random.Generator, n_atoms: int, step: float = 1.5, min_dist: float = 2.0) -> np.ndarray:
+    """A self-avoiding walk: consecutive atoms ``step`` apart (bonded for every pair of CHAIN_ELEMENTS), all others at least
+    ``min_dist`` (not bonded).  Returns f64[n_atoms, 3]."""
+    pts = np.zeros((n_atoms, 3))
+    i, tries = 1, 0
+    while i < n_atoms:
+        v = rng.normal(size=3)
+        cand = pts[i - 1] + v * (step / np.sqrt(v @ v))
+        tries += 1
+        if i == 1 or np.sqrt(((pts[:i - 1] - cand) ** 2).sum(axis=1)).min() >= min_dist:
+            pts[i] = cand
+            i += 1
+        if tries > 1000000:
+            raise RuntimeError("random walk stuck")
+    return pts
+
+
+def make_chain_ensemble(n_structs: int, n_atoms: int, seed: int):
+    """(base f64[n, 3], structures f64[N, n, 3], atomnos int[n], sigma f64[N]): the chain plus Gaussian noise whose sigma is drawn
+    per structure from CHAIN_SIGMAS."""
+    rng = np.random.default_rng(seed)
+    base = make_chain(rng, n_atoms)
+    atomnos = np.array([CHAIN_ELEMENTS[i % len(CHAIN_ELEMENTS)] for i in range(n_atoms)])
+    sigma = np.array(CHAIN_SIGMAS)[rng.integers(0, len(CHAIN_SIGMAS), size=n_structs)]
+    structures = base[None] + rng.normal(size=(n_structs, n_atoms, 3)) * sigma[:, None, None]
+    return base, np.ascontiguousarray(structures), atomnos, sigma
