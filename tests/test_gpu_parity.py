@@ -1424,6 +1424,25 @@ def test_string_embed_params_vs_oracle(eng, oracle):
 
 
 # ----------------------------------------------------------------------------- N2: torsion-fingerprint pruning
+def _assert_float32_of_the_same_angle(oracle, got, recorded, structures, quadruplets):
+    """Element by element: bit-equal to the recorded float32 where the fp64 angle lies 1e-9 degrees or more from a float32 rounding tie (device
+    and host differ in atan2 and sqrt only: about 1e-13 degrees at 180), at most one float32 ulp apart elsewhere."""
+    import ctypes as C
+    s = np.ascontiguousarray(structures, dtype=np.float64)
+    q = np.ascontiguousarray(quadruplets, dtype=np.int32).reshape(-1, 4)
+    ang = np.empty((len(s), len(q)))
+    fn = oracle.lib().orc_torsion_angles_f64
+    fn.restype = None
+    fn(s.ctypes.data_as(C.c_void_p), C.c_int64(len(s)), C.c_int(s.shape[1]), q.ctypes.data_as(C.c_void_p), C.c_int(len(q)), ang.ctypes.data_as(C.c_void_p))
+    f = ang.astype(np.float32)
+    f64 = f.astype(np.float64)
+    lo, hi = np.nextafter(f, np.float32(-np.inf)).astype(np.float64), np.nextafter(f, np.float32(np.inf)).astype(np.float64)
+    decidable = np.minimum(np.abs((lo + f64) / 2 - ang), np.abs((hi + f64) / 2 - ang)) >= 1e-9
+    assert decidable.mean() > 0.99
+    assert np.array_equal(got[decidable], recorded[decidable]), int((got != recorded)[decidable].sum())
+    assert ((got == recorded) | (got == np.nextafter(recorded, np.float32(np.inf))) | (got == np.nextafter(recorded, np.float32(-np.inf)))).all()
+
+
 def test_tfd_pruning_golden(eng, oracle):
     """prune_conformers_tfd on the GPU against the reference's own results (G8: its function, networkx and all), plus the
     fingerprints and tfd_similarity against G6."""
@@ -1433,6 +1452,7 @@ def test_tfd_pruning_golden(eng, oracle):
     fp = tscode_amd._get_tf_mat(g6["coords"], g6["quadruplets"])
     assert fp.dtype == np.float32 and fp.shape == g6["fingerprints"].shape
     assert np.abs(fp - g6["fingerprints"]).max() < 2e-5 and (fp != g6["fingerprints"]).mean() < 0.01     # float32 of an fp64 angle
+    _assert_float32_of_the_same_angle(oracle, fp, g6["fingerprints"], g6["coords"], g6["quadruplets"])
     assert np.array_equal(tscode_amd.get_torsion_fingerprint(g6["coords"][3], g6["quadruplets"]), fp[3])
     sims = [[tscode_amd.tfd_similarity(g6["fingerprints"][i], g6["fingerprints"][j], thresh=t) for j in range(10)] for i in range(4) for t in (10, 90, 300)]
     assert np.array_equal(np.array(sims), g6["similarity"][:12].astype(bool))
@@ -1441,6 +1461,7 @@ def test_tfd_pruning_golden(eng, oracle):
         structures, thresh = g[f"structures{c}"], float(g[f"thresh{c}"])
         tf = eng.torsion_fingerprints(structures, g["quadruplets"])
         assert np.abs(tf - g[f"tf_mat{c}"]).max() < 2e-5
+        _assert_float32_of_the_same_angle(oracle, tf, g[f"tf_mat{c}"], structures, g["quadruplets"])
         # every pass of the pair search against the oracle on the reference's fingerprints
         n = len(structures)
         for k in (1, 2, 5, 10):

@@ -64,14 +64,19 @@ def csrc_digest():
 
 
 def _unit_deps(src):
-    """The files a unit was last compiled from (hipcc -MD): its source and the project headers it includes, transitively."""
+    """The files a unit was last compiled from (hipcc -MD): its source and the project headers it includes, transitively.
+    The units are compiled from the repository root under relative names, so the list still holds after the tree has been moved or copied;
+    a list that does not name the unit's own source inside this tree (written by a build of another tree under absolute names) counts as
+    never built here."""
     dep = os.path.join(OBJ, src + ".d")
     try:
         words = open(dep).read().replace("\\\n", " ").split()
     except OSError:
         return None
     root = os.path.dirname(HERE)
-    return sorted({os.path.normpath(w) for w in words[1:] if os.path.normpath(w).startswith(root)})
+    paths = {os.path.normpath(os.path.join(root, w)) for w in words[1:]}          # (an absolute name stays what it is)
+    deps = sorted(p for p in paths if p.startswith(root + os.sep))
+    return deps if os.path.join(CSRC, src) in deps else None
 
 
 def _unit_stale(src, digest):
@@ -91,16 +96,18 @@ def build(force=False, verbose=False):
         return OUT
     os.makedirs(OBJ, exist_ok=True)
     digest = csrc_digest()
+    root = os.path.dirname(HERE)
     stale = [s for s in SOURCES if force or _unit_stale(s, digest)]
     procs = []
     for src in stale:
-        cmd = [_hipcc()] + CFLAGS + ["-c", "-MD", "-MF", os.path.join(OBJ, src + ".d"), "-o", os.path.join(OBJ, src + ".o"), os.path.join(CSRC, src)]
+        cmd = [_hipcc()] + CFLAGS + ["-c", "-MD", "-MF", os.path.join(OBJ, src + ".d"), "-o", os.path.join(OBJ, src + ".o"),
+                                     os.path.relpath(os.path.join(CSRC, src), root)]
         if src == DIGEST_UNIT:
             cmd.insert(1, f'-DTSC_CSRC_DIGEST="{digest}"')
         if verbose:
             cmd.append("-Rpass-analysis=kernel-resource-usage")
             print(" ".join(cmd))
-        procs.append((src, subprocess.Popen(cmd)))     # (nine units: side by side)
+        procs.append((src, subprocess.Popen(cmd, cwd=root)))     # (the units side by side)
     failed = [src for src, pr in procs if pr.wait() != 0]
     if failed:
         raise subprocess.CalledProcessError(1, "hipcc -c " + " ".join(failed))
