@@ -643,6 +643,60 @@ int tsc_bond_delta_dev(tsc_ctx *ctx, const double *coords, int64_t n_structs, in
                        int excl_per_struct, int64_t max_newbonds, uint8_t *mask, int32_t *formed, int32_t *broken, uint64_t *adj);
 int tsc_topology_timings(tsc_ctx *ctx, float *ms);
 
+/* Non-covalent interactions of a whole ensemble per call (csrc/nci.hpp), one wavefront per structure.
+ *   replaces   get_nci                  tscode/nci.py:28-52, called once per structure from print_nci (tscode/embedder.py:2053-2096)
+ *              _get_nci_atomic_pairs    tscode/nci.py:54-89
+ *              _get_nci_aromatic_rings  tscode/nci.py:91-139
+ *              _get_aromatic_centers    tscode/nci.py:141-181, with is_phenyl (tscode/graph_manipulations.py:152-174) and dihedral
+ *                                       (tscode/algebra.py:24-56): the walk over every combination of 6 of a molecule's C/N atoms is
+ *                                       replaced by the enumeration of the 6-cliques of the graph "distance not above 3 A"
+ * The result equals the reference's, quirks included.  All distances in fp64 with the reference's roundings (dx dx + dy dy + dz dz without
+ * fused multiply-add, compared with the squared bound that gives the verdict of sqrt-then-compare); a threshold of 0 means "never".
+ *   1 pairs      i1 ascending, i2 ascending over the atoms of every LATER molecule; neither atom constrained; hit iff
+ *                dist < thr[class_i1][class_i2], strictly.
+ *   2 rings      per molecule in order, every 6-combination of its ring candidates in lexicographic order of atom index: a ring iff no
+ *                pair distance is above 3 A and the dihedral of its four LOWEST atoms has 1 - |cos| < 1 - cos(10 deg); atan2(0, 0) = 0 is
+ *                flat, a NaN dihedral is not a ring.  Centre = the mean of the six atoms, owner = the molecule.
+ *   3 ring-atom  every ring in list order against every atom of the WHOLE system: hit iff dist(centre, atom) < ring_thr[class_atom] and the
+ *                owner rule lets the pair through.  owner_rule 0 (the reference as written, nci.py:100-105, where the atom's owner is always
+ *                0): the ring's molecule is not molecule 0 -- a ring's own atoms included, rings of molecule 0 never.  owner_rule 1 (what
+ *                the comment at :105-106 intends): the atom's molecule is not the ring's.  Constrained atoms are NOT excluded here.
+ *   4 ring-ring  rings r < s in list order with different owners: hit iff dist(centre_r, centre_s) < ring_ring_thr.
+ *   coords          f64[n_structs, n_atoms, 3]; n_atoms 1 .. 512.  DEVIATION: non-finite coordinates are not refused here (the Python
+ *                   layer refuses them); such an atom takes part in no pair and no ring, where the reference's is_phenyl would let a NaN
+ *                   distance pass (np.max(...) > 3 is False for NaN).
+ *   atom_class      u8[n_atoms], each < n_classes (1 .. 8); thr f64[n_classes, n_classes] and ring_thr f64[n_classes], finite and >= 0.
+ *   atom_mol        u8[n_atoms]: the molecule of every atom; non-decreasing from 0 to n_mols - 1 in steps of at most 1 (n_mols 1 .. 8).
+ *   ring_candidate  u8[n_atoms]: non-zero for the C / N atoms; at most 64 per molecule.  Molecules with fewer than 6 are not scanned.
+ *   constrained     i32[n_con] shared by all structures (con_per_struct == 0) or i32[n_structs, n_con]; -1 = unused slot; n_con 0 .. 16.
+ *   counts          i32[n_structs, 4]: pairs, rings, ring-atom hits, ring-ring hits.  Always written, as is
+ *   overflow        u8[n_structs]: 1 where a structure has more than 64 rings.  The ring count stays exact; the lists below hold the first
+ *                   64 rings in order, and the ring-atom / ring-ring counts cover those.
+ *   optional (NULL: not wanted), slots behind the last ring zero:
+ *   pair_bits       u64[n_structs, n_atoms, W], W = ceil(n_atoms / 64): bit (i2 & 63) of word i2 >> 6 of row i1, laid out as adj of tsc_bond_delta
+ *   ring_atoms      u16[n_structs, 64, 6] ascending atom indices;  ring_owner u8[n_structs, 64];  ring_center f64[n_structs, 64, 3]
+ *   ring_atom_bits  u64[n_structs, 64, W]: the atoms hit by ring r;  ring_ring_bits u64[n_structs, 64]: bit s of word r for a hit r < s
+ * tsc_nci takes host arrays.  tsc_nci_dev: coords, constrained (when per structure) and every output are device pointers, the small tables
+ * host pointers; a per-structure constrained index outside 0 .. n_atoms-1 cannot be refused there and is an unused slot; the call is
+ * enqueued on the context's stream and does not wait for it.
+ * Refused with TSC_ERR_INVALID before any launch: null required pointers, n_atoms outside 1 .. 512, n_classes outside 1 .. 8, n_mols
+ * outside 1 .. 8, a class >= n_classes, molecule indices that are not contiguous blocks in order, more than 64 candidates in a molecule,
+ * a negative or non-finite threshold, n_con > 16, a constrained index >= n_atoms or < -1 (host arrays), an owner rule other than 0 / 1.
+ * n_structs == 0 succeeds and writes nothing.
+ *   tsc_nci_timings  under the context option "pass_timing" >= 1 the two calls time their kernel with events (and synchronise for it):
+ *                    *ms = that time for the calling thread's latest call, -1 where it took none. */
+int tsc_nci(tsc_ctx *ctx, const double *coords, int64_t n_structs, int n_atoms, const uint8_t *atom_class, const double *thr, int n_classes,
+            const uint8_t *atom_mol, int n_mols, const uint8_t *ring_candidate, const double *ring_thr, double ring_ring_thr,
+            const int32_t *constrained, int n_con, int con_per_struct, int owner_rule, int32_t *counts, uint8_t *overflow,
+            uint64_t *pair_bits, uint16_t *ring_atoms, uint8_t *ring_owner, double *ring_center, uint64_t *ring_atom_bits,
+            uint64_t *ring_ring_bits);
+int tsc_nci_dev(tsc_ctx *ctx, const double *coords, int64_t n_structs, int n_atoms, const uint8_t *atom_class, const double *thr,
+                int n_classes, const uint8_t *atom_mol, int n_mols, const uint8_t *ring_candidate, const double *ring_thr,
+                double ring_ring_thr, const int32_t *constrained, int n_con, int con_per_struct, int owner_rule, int32_t *counts,
+                uint8_t *overflow, uint64_t *pair_bits, uint16_t *ring_atoms, uint8_t *ring_owner, double *ring_center,
+                uint64_t *ring_atom_bits, uint64_t *ring_ring_bits);
+int tsc_nci_timings(tsc_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

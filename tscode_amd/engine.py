@@ -481,6 +481,61 @@ class Engine:
         check(self.lib.tsc_topology_timings(self._h, C.byref(ms)))
         return ms.value
 
+    # ---- non-covalent interactions -----------------------------------------------------------
+    def nci(self, coords, classes, thr, atom_mol, n_mols, candidate, ring_thr, ring_ring_thr, constrained=None, owner_rule=0, want=()):
+        """tsc_nci on host arrays (include/tscode_hip.h), already checked (tscode_amd.nci.check_nci_args): coords f64[N, n, 3], classes
+        u8[n], thr f64[T, T], atom_mol u8[n], candidate u8[n], ring_thr f64[T], constrained i32[E] shared or i32[N, E] per structure.
+        Returns {"counts": i32[N, 4], "overflow": bool[N]} plus the arrays named in ``want``."""
+        n_structs, n = coords.shape[0], coords.shape[1]
+        w = (n + 63) // 64
+        shapes = {"pair_bits": ((n_structs, n, w), np.uint64), "ring_atoms": ((n_structs, 64, 6), np.uint16),
+                  "ring_owner": ((n_structs, 64), np.uint8), "ring_center": ((n_structs, 64, 3), np.float64),
+                  "ring_atom_bits": ((n_structs, 64, w), np.uint64), "ring_ring_bits": ((n_structs, 64), np.uint64)}
+        out = {name: (np.zeros(*shapes[name]) if name in want else None) for name in shapes}
+        counts = np.zeros((n_structs, 4), dtype=np.int32)
+        overflow = np.zeros(n_structs, dtype=np.uint8)
+        thr = np.ascontiguousarray(thr, dtype=np.float64)
+        ring_thr = np.ascontiguousarray(ring_thr, dtype=np.float64)
+        n_con = 0 if constrained is None else constrained.shape[-1]
+        check(self.lib.tsc_nci(self._h, ptr(coords), C.c_int64(n_structs), C.c_int(n), ptr(np.ascontiguousarray(classes, dtype=np.uint8)), ptr(thr),
+                               C.c_int(len(thr)), ptr(np.ascontiguousarray(atom_mol, dtype=np.uint8)), C.c_int(int(n_mols)),
+                               ptr(np.ascontiguousarray(candidate, dtype=np.uint8)), ptr(ring_thr), C.c_double(float(ring_ring_thr)),
+                               ptr(constrained), C.c_int(n_con), C.c_int(int(constrained is not None and constrained.ndim == 2)),
+                               C.c_int(int(owner_rule)), ptr(counts), ptr(overflow), *[ptr(out[name]) for name in shapes]))
+        res = {"counts": counts, "overflow": overflow.astype(bool)}
+        res.update({name: arr for name, arr in out.items() if arr is not None})
+        return res
+
+    def nci_dev(self, coords, n_structs, n_atoms, classes, thr, atom_mol, n_mols, candidate, ring_thr, ring_ring_thr, constrained, con_per_struct,
+                owner_rule, counts, overflow, pair_bits=None, ring_atoms=None, ring_owner=None, ring_center=None, ring_atom_bits=None,
+                ring_ring_bits=None):
+        """tsc_nci_dev: coords, counts, overflow and the optional outputs (and constrained i32[N, E] when con_per_struct) on the device;
+        classes u8[n], thr f64[T, T], atom_mol u8[n], candidate u8[n], ring_thr f64[T] (and constrained i32[E] otherwise) NumPy arrays.
+        Enqueued on the context's stream."""
+        classes = np.ascontiguousarray(classes, dtype=np.uint8)
+        thr = np.ascontiguousarray(thr, dtype=np.float64)
+        atom_mol = np.ascontiguousarray(atom_mol, dtype=np.uint8)
+        candidate = np.ascontiguousarray(candidate, dtype=np.uint8)
+        ring_thr = np.ascontiguousarray(ring_thr, dtype=np.float64)
+        if constrained is None:
+            n_con = 0
+        elif con_per_struct:
+            n_con = int(constrained.shape[-1])
+        else:
+            constrained = np.ascontiguousarray(constrained, dtype=np.int32).ravel()
+            n_con = len(constrained)
+        check(self.lib.tsc_nci_dev(self._h, ptr(coords), C.c_int64(n_structs), C.c_int(n_atoms), ptr(classes), ptr(thr), C.c_int(len(thr)),
+                                   ptr(atom_mol), C.c_int(int(n_mols)), ptr(candidate), ptr(ring_thr), C.c_double(float(ring_ring_thr)),
+                                   ptr(constrained), C.c_int(n_con), C.c_int(int(bool(con_per_struct))), C.c_int(int(owner_rule)), ptr(counts),
+                                   ptr(overflow), ptr(pair_bits), ptr(ring_atoms), ptr(ring_owner), ptr(ring_center), ptr(ring_atom_bits),
+                                   ptr(ring_ring_bits)))
+
+    def nci_kernel_ms(self) -> float:
+        """tsc_nci_timings: the kernel time of this thread's latest nci / nci_dev under set_option("pass_timing", 1)."""
+        ms = C.c_float()
+        check(self.lib.tsc_nci_timings(self._h, C.byref(ms)))
+        return ms.value
+
     def prune_heavy(self, heavy, rmsd_thr=0.5, mode=0):
         """prune_conformers_rmsd on the heavy-atom array f64[N, h, 3]. Returns (mask bool[N], per-pass stats)."""
         heavy = np.ascontiguousarray(heavy, dtype=np.float64)

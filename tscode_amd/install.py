@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import sys
 
-from . import algebra, embeds, graph_manipulations, hypermolecule_class, numba_functions, optimization_methods, rmsd_pruning, rot_corr, torsion_module
+from . import algebra, embeds, graph_manipulations, hypermolecule_class, nci, numba_functions, optimization_methods, rmsd_pruning, rot_corr, torsion_module
 from . import utils
 
 # attribute -> (replacement, modules that bind it)
@@ -81,12 +81,19 @@ _TOPOLOGY_PATCHES = {
     "get_double_bonds_indices": (utils.get_double_bonds_indices, ("tscode.ase_manipulations", "tscode.torsion_module", "tscode.utils")),
 }
 
-_OPT_IN = (_ROT_CORR_PATCHES, _DIVERSE_PATCHES, _TOPOLOGY_PATCHES)
+# Opt-in (install(nci=True)): the non-covalent-interaction finder that print_nci calls once per structure (tscode/embedder.py:2063; bound
+# by name at :47).  The sites are the ones tests/golden/gen_nci.py records from the reference's import lines (G22_nci_sites.json).  Off by
+# default like the other per-structure drop-ins; a caller with an ensemble wants tscode_amd.nci_batch and differential_nci.
+_NCI_PATCHES = {
+    "get_nci": (nci.get_nci, ("tscode.embedder", "tscode.nci")),
+}
+
+_OPT_IN = (_ROT_CORR_PATCHES, _DIVERSE_PATCHES, _TOPOLOGY_PATCHES, _NCI_PATCHES)
 
 _saved = {}
 
 
-def install(modules=None, per_item=False, rot_corr=False, diverse=False, topology=False):
+def install(modules=None, per_item=False, rot_corr=False, diverse=False, topology=False, nci=False):
     """Replace the hot-path functions in every already-imported tscode module: by default those that work on a whole ensemble
     per call (prune_conformers_rmsd, prune_conformers_tfd, get_moi_similarity_matches, _score_embed_poses) and the two embed
     loops (string_embed, cyclical_embed: one GPU call each instead of one Python iteration per pose); with
@@ -94,12 +101,13 @@ def install(modules=None, per_item=False, rot_corr=False, diverse=False, topolog
     equivalent but slower than the reference's jitted code when called one item at a time; with ``rot_corr=True`` also
     prune_conformers_rmsd_rot_corr (_ROT_CORR_PATCHES); with ``diverse=True`` also align_structures and most_diverse_conformers
     (_DIVERSE_PATCHES); with ``topology=True`` also graphize, molecule_check, scramble_check and get_double_bonds_indices
-    (_TOPOLOGY_PATCHES).
+    (_TOPOLOGY_PATCHES); with ``nci=True`` also get_nci (_NCI_PATCHES).
     Returns the list of (module, attribute) pairs that were patched."""
     mods = sys.modules if modules is None else modules
     done = []
     table = (list(_PATCHES.items()) + (list(_ROT_CORR_PATCHES.items()) if rot_corr else []) +
-             (list(_DIVERSE_PATCHES.items()) if diverse else []) + (list(_TOPOLOGY_PATCHES.items()) if topology else []))
+             (list(_DIVERSE_PATCHES.items()) if diverse else []) + (list(_TOPOLOGY_PATCHES.items()) if topology else []) +
+             (list(_NCI_PATCHES.items()) if nci else []))
     for attr, (fn, names) in table:
         if not per_item and attr not in _WHOLE_ENSEMBLE and not any(attr in t for t in _OPT_IN):
             continue

@@ -24,7 +24,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 __all__ = ["Ensemble", "make_fragment", "make_ensemble", "make_unscreenable", "CONFIGS", "make_config", "quat_to_mat", "make_rot_corr_ensemble", "make_chain_ensemble",
-           "CHAIN_ELEMENTS", "CHAIN_SIGMAS"]
+           "CHAIN_ELEMENTS", "CHAIN_SIGMAS", "aromatic_block", "make_aromatic_ensemble", "AROMATIC_SIGMAS"]
 
 
 def make_fragment(rng: np.random.Generator, n_atoms: int, step: float = 1.5, min_dist: float = 1.2) -> np.ndarray:
@@ -284,3 +284,75 @@ def make_chain_ensemble(n_structs: int, n_atoms: int, seed: int):
     sigma = np.array(CHAIN_SIGMAS)[rng.integers(0, len(CHAIN_SIGMAS), size=n_structs)]
     structures = base[None] + rng.normal(size=(n_structs, n_atoms, 3)) * sigma[:, None, None]
     return base, np.ascontiguousarray(structures), atomnos, sigma
+
+
+# ---- aromatic building blocks for the non-covalent-interaction finder (tscode_amd.nci; fixtures G22) ----------------------------
+AROMATIC_SIGMAS = (0.0, 0.03, 0.08, 0.15)        # A: from "every ring is flat" to "hardly any ring passes is_phenyl's 10 degrees"
+
+
+def _hexagon(radius, z_alt=0.0, start=0.0):
+    ang = start + np.arange(6) * (np.pi / 3)
+    return np.stack([radius * np.cos(ang), radius * np.sin(ang), z_alt * (-1.0) ** np.arange(6)], axis=1)
+
+
+def aromatic_block(name: str):
+    """(atomnos int[k], coords f64[k, 3]) of a building block, its ring(s) in the xy plane about the origin, heavy atoms first:
+      benzene      6 C on a hexagon of 1.39 A, 6 H at 2.48 A
+      hexagon      the 6 C of benzene alone
+      pyridine     N + 5 C on the same hexagon, 5 H
+      pyranyl      O + 5 C on the same hexagon, 5 H: exactly 5 ring candidates, never scanned
+      naphthalene  10 C (two hexagons sharing an edge), 8 H
+      chair        cyclohexane: 6 C on a hexagon of 1.45 A at z = +-0.25 A (all within 3 A of one another, not flat), 12 H
+      rod          6 C on the x axis, 0.5 A apart: axis-aligned collinear atoms, the dihedral's atan2(0, 0)
+      H O N F C    one atom at the origin (probes)"""
+    ring, outer = _hexagon(1.39), _hexagon(2.48)
+    if name == "hexagon":
+        return np.array([6] * 6), ring
+    if name == "benzene":
+        return np.array([6] * 6 + [1] * 6), np.concatenate([ring, outer])
+    if name in ("pyridine", "pyranyl"):
+        return np.array([7 if name == "pyridine" else 8] + [6] * 5 + [1] * 5), np.concatenate([ring, outer[1:]])
+    if name == "naphthalene":
+        shift = np.array([1.39 * np.sqrt(3.0) / 2, 0.0, 0.0])
+        a, b = _hexagon(1.39, start=np.pi / 6) - shift, _hexagon(1.39, start=np.pi / 6) + shift
+        carbons = np.concatenate([a, [p for p in b if np.sqrt(((a - p) ** 2).sum(1)).min() > 0.1]])    # (two of b's vertices are the shared edge)
+        ha, hb = _hexagon(2.48, start=np.pi / 6) - shift, _hexagon(2.48, start=np.pi / 6) + shift
+        hyd = [p for p in np.concatenate([ha, hb]) if np.sqrt(((carbons - p) ** 2).sum(1)).min() > 1.0]
+        return np.array([6] * len(carbons) + [1] * len(hyd)), np.concatenate([carbons, hyd])
+    if name == "chair":
+        c = _hexagon(1.45, z_alt=0.25)
+        axial = c + np.array([0.0, 0.0, 1.1]) * np.sign(c[:, 2:3])
+        equatorial = c + np.concatenate([c[:, :2] / 1.45 * 1.0, -0.35 * np.sign(c[:, 2:3])], axis=1)
+        return np.array([6] * 6 + [1] * 12), np.concatenate([c, axial, equatorial])
+    if name == "rod":
+        return np.array([6] * 6), np.stack([0.5 * np.arange(6), np.zeros(6), np.zeros(6)], axis=1)
+    if name in ("H", "O", "N", "F", "C"):
+        return np.array([{"H": 1, "C": 6, "N": 7, "O": 8, "F": 9}[name]]), np.zeros((1, 3))
+    raise ValueError(f"no building block {name!r}")
+
+
+def make_aromatic_ensemble(molecules, n_structs: int, seed: int, sigmas=AROMATIC_SIGMAS, rigid: float = 0.0):
+    """An ensemble for the non-covalent-interaction finder.  ``molecules`` is a list of molecules, each a list of placed building
+    blocks ``(name, position)`` or ``(name, position, quaternion)`` (aromatic_block; the block is turned by the quaternion, then
+    moved to the position).  Every structure is the base with Gaussian noise on every coordinate, sigma drawn per structure from
+    ``sigmas``, after each molecule but the first was moved as a whole by N(0, rigid) per axis (so contacts between molecules open
+    and close from structure to structure even at sigma = 0, and axis-aligned atoms stay axis-aligned there).
+    Returns (base f64[n, 3], structures f64[N, n, 3], atomnos int[n], ids int[n_mols], sigma f64[N])."""
+    rng = np.random.default_rng(seed)
+    zs, xs, ids = [], [], []
+    for mol in molecules:
+        count = 0
+        for placed in mol:
+            z, x = aromatic_block(placed[0])
+            if len(placed) > 2 and placed[2] is not None:
+                x = x @ quat_to_mat(np.asarray(placed[2], dtype=np.float64)[None])[0].T
+            zs.append(z)
+            xs.append(x + np.asarray(placed[1], dtype=np.float64))
+            count += len(z)
+        ids.append(count)
+    atomnos, base, ids = np.concatenate(zs), np.concatenate(xs), np.array(ids)
+    sigma = np.asarray(sigmas, dtype=np.float64)[rng.integers(0, len(sigmas), size=n_structs)]
+    shift = rng.normal(size=(n_structs, len(ids), 3)) * rigid
+    shift[:, 0] = 0.0
+    structures = base[None] + np.repeat(shift, ids, axis=1) + rng.normal(size=(n_structs, len(base), 3)) * sigma[:, None, None]
+    return base, np.ascontiguousarray(structures), atomnos, ids, sigma
