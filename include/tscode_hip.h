@@ -697,6 +697,82 @@ int tsc_nci_dev(tsc_ctx *ctx, const double *coords, int64_t n_structs, int n_ato
                 uint64_t *ring_atom_bits, uint64_t *ring_ring_bits);
 int tsc_nci_timings(tsc_ctx *ctx, float *ms);
 
+/* Reactive-atom orbitals and pivots of every conformer of one molecule per call (csrc/orbitals.hpp), one lane per conformer: what the embed
+ * drivers take as input (tsc_string_embed: centres and orbital vectors; tsc_cyclical_embed: pivots), from coordinates.
+ *   replaces   Hypermolecule.compute_orbitals   tscode/hypermolecule_class.py:195-217 (the loop over conformers and reactive atoms, :212-214)
+ *              Single / Sp2 / Sp3 / Ether / Ketone / Imine / Sp_or_carbene / Metal .init(update=True)
+ *                                               tscode/reactive_atoms_classes.py:34-80, :88-119, :127-207, :253-284, :293-375, :383-416,
+ *                                               :425-538, :546-576, with rot_mat_from_pointer, norm, norm_of, vec_angle (tscode/algebra.py)
+ *              is_sigmatropic                   tscode/graph_manipulations.py:231-273 -- its test per conformer (:256); the rest comes in as a mode
+ *              Embedder._get_pivots             tscode/embedder.py:575-621, with Pivot (tscode/hypermolecule_class.py:388-402)
+ *              Embedder._set_pivots             tscode/embedder.py:542-573 (the suprafacial and sigma-star filters)
+ * Everything the reference reads from the bond graph (of conformer 0: hypermolecule_class.py:185) comes in a RECIPE per reactive atom, built
+ * on the host once (tscode_amd/reactive_atoms.py: orbital_recipes).  tsc_orbital_recipe, field by field:
+ *   cls           TSC_ORB_SINGLE .. TSC_ORB_METAL: the class get_atom_type picked (reactive_atoms_classes.py:645-660)
+ *   flags         TSC_ORB_F_SIGMASTAR    mol.sp3_sigmastar (is_vicinal, graph_manipulations.py:275-298): the same in every recipe of a call
+ *                 TSC_ORB_F_BOND_LENGTH  Single without a parameter: orb_dim is this conformer's |atom - nb[0]| (:77) and the field orb_dim is not read
+ *                 TSC_ORB_F_ALLENE / TSC_ORB_F_KETENE   Sp_or_carbene (:448-482): where a conformer is 'sp', pivot1 comes from ex[0], ex[1]
+ *                 TSC_ORB_F_KETONE_KETENE / _TWO / _TRILOBE   Ketone: its neighbour has 1 / 2 / 3 other neighbours (:322, :342, :360); one of them is required
+ *   atom          the reactive atom
+ *   nb[4]         its neighbours in ascending index, as many as the class reads: Single 1 (`other`), Sp2 3, Ether 2, Ketone 1, Imine 2,
+ *                 Sp_or_carbene 2, Metal 1, Sp3 0; -1 = unused
+ *   ex[4]         Single / Sp3 under sigmastar: {the bonded reactive partner, Single: the first neighbour of the partner that is not `atom` (:60-62);
+ *                                 Sp3: the first neighbour of `atom` that is not the partner (:187-189)}
+ *                 Sp3 otherwise: {the leaving group (:141-170)}
+ *                 Ketone KETENE: {the neighbour's other neighbour, that atom's first other neighbour (:325-329)};  TWO: {a1, a2 (:346-347)};
+ *                 TRILOBE: {the three (:363)}
+ *                 Sp_or_carbene ALLENE: {the first other neighbour of nb[0], nb[0] (:507-508)};  KETENE: {substituent, ketene atom (:471-479)}
+ *                 Metal: {neighbors(graph, nb[0])[0] (:561) -- the metal itself where it has the lowest index there: NaN, as in the reference}
+ *   reserved      0
+ *   orb_dim       the lobe distance (orb_dim_dict, the DIST keyword, _scale_orbs); for Sp_or_carbene that of 'sp'
+ *   orb_dim_bent  Sp_or_carbene: that of 'bent carbene' (the key depends on the conformer, :486)
+ *   seed[3]       Sp_or_carbene: stands for np.random.rand(3) of :495, read where a conformer is 'sp' and neither flag is set
+ * Per conformer c:
+ *   sigmatropic[c]  sigmatropic_mode 0: 0;  1 (two reactive atoms): |atom_0 - atom_1| < 3 A (:256);  2: 1 (an explicit override; the only way to
+ *                   the Ketone 'p' lobes of :350-353, which compute_orbitals cannot reach: str() of a Ketone is never in sp2_types)
+ *   centers, orb_vecs f64[n_conf, n_reactive, 4, 3]   the class's .center and .orb_vecs, unused lobes zero;  n_lobes u8[n_conf, n_reactive]
+ *   kind u8[n_conf, n_reactive]   TSC_ORB_KIND_*: what str(r_atom) names -- 'sp' iff abs(vec_angle - 180) < 5 (:439-446), the Ketone subtype
+ *   pivots (one or two reactive atoms; all four arrays or none), in the order of cartesian_product (first lobe index fastest; one reactive atom:
+ *   the lobe pairs i < j), after the suprafacial filter (only where a conformer has exactly 4 pivots, embedder.py:552-563) and the sigma-star
+ *   filter (lengths within 1e-5 of the shortest, :569-573):
+ *   pivot, meanpoint f64[n_conf, 16, 3];  lobe_index i8[n_conf, 16, 2];  n_pivots u8[n_conf];  slots behind the last: 0 and -1
+ * Coordinates are used as given (the reference has subtracted the ensemble's centroid, hypermolecule_class.py:179-184).  fp64 throughout; the
+ * three decisions per conformer (angle, distance, pivot lengths) are taken on values that may differ from the reference's in the last bits.
+ * tsc_orbitals takes host arrays.  tsc_orbitals_dev: coords and every output are device pointers, the recipes a host pointer; the call is
+ * enqueued on the context's stream and does not wait for it.
+ * Refused with TSC_ERR_INVALID before any launch: null required pointers, n_atoms outside 1 .. 65536, n_reactive outside 1 .. 8, an unknown class
+ * or flag bit, a Ketone without subtype, an atom / neighbour / extra index the class reads outside 0 .. n_atoms-1, a non-finite orb_dim or seed,
+ * recipes that disagree on TSC_ORB_F_SIGMASTAR, sigmatropic_mode outside 0 .. 2 or 1 without exactly two reactive atoms, some but not all of the
+ * four pivot arrays, pivot arrays with more than two reactive atoms.  n_conf == 0 succeeds and writes nothing.
+ *   tsc_orbitals_timings  under the context option "pass_timing" >= 1 the two calls time their kernel with events (and synchronise for it):
+ *                         *ms = that time for the calling thread's latest call, -1 where it took none. */
+#define TSC_ORB_MAX_REACTIVE 8
+#define TSC_ORB_MAX_LOBES 4
+#define TSC_ORB_MAX_PIVOTS 16
+#define TSC_ORB_MAX_ATOMS 65536
+enum { TSC_ORB_SINGLE = 0, TSC_ORB_SP2 = 1, TSC_ORB_SP3 = 2, TSC_ORB_ETHER = 3, TSC_ORB_KETONE = 4, TSC_ORB_IMINE = 5, TSC_ORB_SP_OR_CARBENE = 6,
+       TSC_ORB_METAL = 7 };
+enum { TSC_ORB_F_SIGMASTAR = 1, TSC_ORB_F_BOND_LENGTH = 2, TSC_ORB_F_ALLENE = 4, TSC_ORB_F_KETENE = 8, TSC_ORB_F_KETONE_KETENE = 16,
+       TSC_ORB_F_KETONE_TWO = 32, TSC_ORB_F_KETONE_TRILOBE = 48, TSC_ORB_F_KETONE_MASK = 48, TSC_ORB_F_ALL = 63 };
+enum { TSC_ORB_KIND_SINGLE = 0, TSC_ORB_KIND_SP2 = 1, TSC_ORB_KIND_SP3 = 2, TSC_ORB_KIND_ETHER = 3, TSC_ORB_KIND_KETONE_PP = 4,
+       TSC_ORB_KIND_KETONE_SP2 = 5, TSC_ORB_KIND_KETONE_P = 6, TSC_ORB_KIND_KETONE_TRILOBE = 7, TSC_ORB_KIND_IMINE = 8, TSC_ORB_KIND_SP = 9,
+       TSC_ORB_KIND_BENT_CARBENE = 10, TSC_ORB_KIND_METAL = 11 };
+typedef struct tsc_orbital_recipe {
+    int32_t cls, flags, atom;
+    int32_t nb[4];
+    int32_t ex[4];
+    int32_t reserved;
+    double orb_dim, orb_dim_bent;
+    double seed[3];
+} tsc_orbital_recipe;
+int tsc_orbitals(tsc_ctx *ctx, const double *coords, int64_t n_conf, int n_atoms, const tsc_orbital_recipe *recipes, int n_reactive,
+                 int sigmatropic_mode, int suprafacial, double *centers, double *orb_vecs, uint8_t *n_lobes, uint8_t *kind, uint8_t *sigmatropic,
+                 double *pivot, double *meanpoint, int8_t *lobe_index, uint8_t *n_pivots);
+int tsc_orbitals_dev(tsc_ctx *ctx, const double *coords, int64_t n_conf, int n_atoms, const tsc_orbital_recipe *recipes, int n_reactive,
+                     int sigmatropic_mode, int suprafacial, double *centers, double *orb_vecs, uint8_t *n_lobes, uint8_t *kind,
+                     uint8_t *sigmatropic, double *pivot, double *meanpoint, int8_t *lobe_index, uint8_t *n_pivots);
+int tsc_orbitals_timings(tsc_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

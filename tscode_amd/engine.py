@@ -536,6 +536,38 @@ class Engine:
         check(self.lib.tsc_nci_timings(self._h, C.byref(ms)))
         return ms.value
 
+    # ---- reactive-atom orbitals and pivots ----------------------------------------------------
+    def orbitals(self, coords, recipes, sigmatropic_mode=0, suprafacial=False, want_pivots=True):
+        """tsc_orbitals on host arrays (include/tscode_hip.h), already checked (tscode_amd.reactive_atoms): coords f64[C, n, 3], recipes a
+        record array of reactive_atoms.RECIPE_DTYPE.  Returns the arrays of the header by name; the four pivot arrays with want_pivots."""
+        n_conf, n = coords.shape[0], coords.shape[1]
+        recipes = np.ascontiguousarray(recipes)
+        r = len(recipes)
+        out = {"centers": np.zeros((n_conf, r, 4, 3)), "orb_vecs": np.zeros((n_conf, r, 4, 3)), "n_lobes": np.zeros((n_conf, r), dtype=np.uint8),
+               "kind": np.zeros((n_conf, r), dtype=np.uint8), "sigmatropic": np.zeros(n_conf, dtype=np.uint8)}
+        piv = {"pivot": np.zeros((n_conf, 16, 3)), "meanpoint": np.zeros((n_conf, 16, 3)), "lobe_index": np.full((n_conf, 16, 2), -1, dtype=np.int8),
+               "n_pivots": np.zeros(n_conf, dtype=np.uint8)} if want_pivots else dict.fromkeys(("pivot", "meanpoint", "lobe_index", "n_pivots"))
+        check(self.lib.tsc_orbitals(self._h, ptr(coords), C.c_int64(n_conf), C.c_int(n), ptr(recipes), C.c_int(r), C.c_int(int(sigmatropic_mode)),
+                                    C.c_int(int(bool(suprafacial))), *[ptr(v) for v in out.values()], *[ptr(v) for v in piv.values()]))
+        out["sigmatropic"] = out["sigmatropic"].astype(bool)
+        if want_pivots:
+            out.update(piv)
+        return out
+
+    def orbitals_dev(self, coords, n_conf, n_atoms, recipes, sigmatropic_mode, suprafacial, centers, orb_vecs, n_lobes, kind, sigmatropic,
+                     pivot=None, meanpoint=None, lobe_index=None, n_pivots=None):
+        """tsc_orbitals_dev: coords and every output on the device, recipes a NumPy record array.  Enqueued on the context's stream."""
+        recipes = np.ascontiguousarray(recipes)
+        check(self.lib.tsc_orbitals_dev(self._h, ptr(coords), C.c_int64(n_conf), C.c_int(n_atoms), ptr(recipes), C.c_int(len(recipes)),
+                                        C.c_int(int(sigmatropic_mode)), C.c_int(int(bool(suprafacial))), ptr(centers), ptr(orb_vecs), ptr(n_lobes),
+                                        ptr(kind), ptr(sigmatropic), ptr(pivot), ptr(meanpoint), ptr(lobe_index), ptr(n_pivots)))
+
+    def orbitals_kernel_ms(self) -> float:
+        """tsc_orbitals_timings: the kernel time of this thread's latest orbitals / orbitals_dev under set_option("pass_timing", 1)."""
+        ms = C.c_float()
+        check(self.lib.tsc_orbitals_timings(self._h, C.byref(ms)))
+        return ms.value
+
     def prune_heavy(self, heavy, rmsd_thr=0.5, mode=0):
         """prune_conformers_rmsd on the heavy-atom array f64[N, h, 3]. Returns (mask bool[N], per-pass stats)."""
         heavy = np.ascontiguousarray(heavy, dtype=np.float64)
