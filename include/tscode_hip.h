@@ -278,6 +278,39 @@ int tsc_csearch_rotate(tsc_ctx *ctx, const double *coords, int n_atoms, const in
 int tsc_csearch_rotate_dev(tsc_ctx *ctx, const double *coords, int n_atoms, const int32_t *torsions, const uint8_t *masks, int n_tors,
                            const int32_t *angles, int64_t n_cand, double thresh, int64_t max_clashes, double *out,
                            int32_t *rotated_bonds);
+/* The same candidates from MANY start structures and torsion sets in one launch: the loop over starting_points of
+ * clustered_csearch (tscode/torsion_module.py:736-780, every start x the group's whole angle table) and the one random_csearch
+ * per TS candidate of Embedder.csearch_augmentation (tscode/embedder.py:1907-1939, each with its own torsions, masks and
+ * shuffled table).  starts f64[n_starts, n_atoms, 3].  The n_sets torsion sets lie back to back: torsions i32[set_off[n_sets], 4],
+ * masks u8[set_off[n_sets], n_atoms], set k owning rows set_off[k] .. set_off[k + 1]; start s uses set start_set[s].  One angle
+ * table angles i32[n_rows, t_max]: a set's rows are zero-padded to t_max (a zero angle is skipped by the loop itself, :480 / :754).
+ * Candidate m = (start cand_start[m], row cand_row[m]); the candidates of one start are contiguous and cand_start ascends.
+ * out f64[n_cand, n_atoms, 3], rotated_bonds i32[n_cand].  The LDS bound of tsc_csearch_rotate holds per set.
+ * tsc_csearch_multi_plan (host arrays, no device work) cuts the candidates into the kernel's work items, which never straddle two
+ * sets: items i32[n_items, 4]; items == NULL only counts them.  The _dev form takes every array on the device except set_off (a
+ * host array: it sizes the launch) and the items of the plan, uploaded by the caller; the host form plans by itself. */
+int tsc_csearch_multi_plan(const int32_t *cand_start, int64_t n_cand, const int32_t *start_set, int n_starts, const int32_t *set_off,
+                           int n_sets, int n_atoms, int32_t *items, int64_t items_cap, int64_t *n_items);
+int tsc_csearch_rotate_multi(tsc_ctx *ctx, const double *starts, int n_starts, int n_atoms, const int32_t *torsions,
+                             const uint8_t *masks, const int32_t *set_off, int n_sets, const int32_t *start_set, const int32_t *angles,
+                             int64_t n_rows, int t_max, const int32_t *cand_start, const int32_t *cand_row, int64_t n_cand, double thresh,
+                             int64_t max_clashes, double *out, int32_t *rotated_bonds);
+int tsc_csearch_rotate_multi_dev(tsc_ctx *ctx, const double *starts, int n_atoms, const int32_t *torsions, const uint8_t *masks,
+                                 const int32_t *set_off, int n_sets, const int32_t *angles, int t_max, const int32_t *cand_start,
+                                 const int32_t *cand_row, int64_t n_cand, const int32_t *items, int64_t n_items, double thresh,
+                                 int64_t max_clashes, double *out, int32_t *rotated_bonds);
+/* Which candidates the reference appends, decided and compacted on the device (tscode/torsion_module.py:505-511; :779 for
+ * n_out < 0).  One round of a search hands in, for each start still walking its table, ONE segment g = candidates
+ * [seg_off[g], seg_off[g + 1]) of start seg_start[g] in table order, the first of them row seg_a0[g] of that start's table.  A row
+ * is kept iff rotated_bonds != 0; only just after a row was kept is `len(new_structures) == n_out or a == max_tries` tested, so a
+ * dropped row max_tries does not end the walk; n_out < 0 never stops on the count.  Carried per start from round to round:
+ * kept_count i32[n_starts] and done i32[n_starts] (in / out; zero them before the first round; a start that is done takes
+ * nothing); rows_consumed i32[n_starts] (out) = rows of the segment the loop walked.  kept_rows f64[capacity, n_atoms, 3] receives
+ * the rows taken, in order, the segments back to back (segment g holds kept_count's increase of its start); *n_kept_host their
+ * number (the call synchronises for it).  All arrays on the device. */
+int tsc_csearch_select_dev(tsc_ctx *ctx, const double *cand, const int32_t *rotated_bonds, int n_atoms, const int32_t *seg_off,
+                           const int32_t *seg_start, const int32_t *seg_a0, int n_seg, int n_out, int64_t max_tries, int32_t *kept_count,
+                           int32_t *done, int32_t *rows_consumed, double *kept_rows, int64_t capacity, int64_t *n_kept_host);
 /* tsc_rotate_dihedral: rotate_dihedral (tscode/utils.py:389-414) for n_structs structures f64[n_structs, n_atoms, 3] that share the
  * torsion (i1, i2, i3, i4) and the mask u8[n_atoms] of the atoms that move: structure s turns them by angles[s] degrees -- any real
  * number, tscode/torsion_module.py:984-1005 searches fractional corrections -- about its own i2 - i3 bond (centre i3).  No clash

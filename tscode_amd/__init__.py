@@ -26,8 +26,9 @@ from .numba_functions import (_get_tf_mat, compenetration_check, compenetration_
                               prune_conformers_tfd, tfd_similarity)
 from .optimization_methods import (_score_embed_poses, fitness_check, fitness_mask, get_inertia_moments,  # noqa: F401
                                    get_moi_similarity_matches, prune_by_moment_of_inertia)
-from .torsion_module import (csearch_candidates, csearch_rotate, diverse_select, most_diverse_conformers, rotate_dihedral,  # noqa: F401
-                             rotate_dihedral_batch, torsion_comp_check)
+from .torsion_module import (clustered_csearch_step, csearch_candidates, csearch_candidates_multi, csearch_rotate,  # noqa: F401
+                             csearch_rotate_multi, diverse_select, most_diverse_conformers, rotate_dihedral, rotate_dihedral_batch,
+                             torsion_comp_check)
 from .hypermolecule_class import align_structures  # noqa: F401
 from .kmeans import kmeans_lloyd, kmeans_plusplus_rows  # noqa: F401
 from .rot_corr import last_rot_corr_stats, prune_conformers_rmsd_rot_corr, prune_rmsd_rot_corr_arrays, rot_corr_pairs  # noqa: F401

@@ -93,6 +93,12 @@ _SIGNATURES = {
     "tsc_cyclical_embed_params": (C.c_int, [_vp] * 10 + [C.c_int64, _vp, _vp]),
     "tsc_csearch_rotate": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int64, C.c_double, C.c_int64, _vp, _vp]),
     "tsc_csearch_rotate_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int64, C.c_double, C.c_int64, _vp, _vp]),
+    "tsc_csearch_multi_plan": (C.c_int, [_vp, C.c_int64, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int64, c_i64p]),
+    "tsc_csearch_rotate_multi": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int64,
+                                           C.c_double, C.c_int64, _vp, _vp]),
+    "tsc_csearch_rotate_multi_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int64, _vp, C.c_int64,
+                                               C.c_double, C.c_int64, _vp, _vp]),
+    "tsc_csearch_select_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int64, _vp, _vp, _vp, _vp, C.c_int64, c_i64p]),
     "tsc_torsion_comp_check": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_double, C.c_int64, _vp]),
     "tsc_rotate_dihedral": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "tsc_greedy_group_filter": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp]),

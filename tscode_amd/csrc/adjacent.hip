@@ -129,6 +129,159 @@ extern "C" __attribute__((visibility("default"))) int tsc_csearch_rotate(tsc_ctx
     TSC_API_GUARD_END
 }
 
+// The per-set checks of the multi kernel and the widest set's torsion count: csearch_args' LDS bound holds for every set
+static int csearch_multi_sets(int n_atoms, const int32_t *set_off, int n_sets, int *t_widest) {
+    TSC_REQUIRE(n_atoms > 0 && n_sets > 0 && set_off && set_off[0] == 0, "bad sizes (%d atoms, %d torsion sets; set_off must start at 0)", n_atoms, n_sets);
+    int widest = 0;
+    for (int k = 0; k < n_sets; ++k) {
+        const int t = set_off[k + 1] - set_off[k];
+        TSC_REQUIRE(t >= 0, "torsion set %d: set_off must not decrease", k);
+        TSC_REQUIRE(n_atoms <= 65535 && torsion_lists_bytes(t, n_atoms) + csearch_wave_bytes(n_atoms) <= 150 * 1024,
+                    "torsion set %d: %d atoms x %d torsions exceed the LDS staging of the csearch kernels", k, n_atoms, t);
+        widest = std::max(widest, t);
+    }
+    *t_widest = widest;
+    return 0;
+}
+
+// Host arrays.  Cuts the candidates (cand_start ascending: the candidates of one start are contiguous) into the work items of
+// k_csearch_rotate_multi: (lo, hi, first torsion of the set, torsions of the set), at most one candidate per wavefront of a
+// workgroup, never across two starts of different sets.  items == NULL only counts.
+extern "C" __attribute__((visibility("default"))) int tsc_csearch_multi_plan(const int32_t *cand_start, int64_t n_cand, const int32_t *start_set, int n_starts,
+                                                                             const int32_t *set_off, int n_sets, int n_atoms, int32_t *items,
+                                                                             int64_t items_cap, int64_t *n_items) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(n_items && (n_cand == 0 || cand_start) && (n_starts == 0 || start_set), "tsc_csearch_multi_plan: null argument");
+    TSC_REQUIRE(n_cand >= 0 && n_cand < INT32_MAX && n_starts >= 0, "bad sizes (%lld candidates, %d starts)", (long long)n_cand, n_starts);
+    int widest;
+    TSC_TRY(csearch_multi_sets(n_atoms, set_off, n_sets, &widest));
+    for (int s = 0; s < n_starts; ++s) TSC_REQUIRE(start_set[s] >= 0 && start_set[s] < n_sets, "start %d: torsion set %d out of range", s, start_set[s]);
+    size_t lds;
+    const int waves = csearch_waves(n_atoms, widest, &lds);
+    int64_t count = 0;
+    for (int64_t lo = 0; lo < n_cand;) {
+        const int s = cand_start[lo];
+        TSC_REQUIRE(s >= 0 && s < n_starts && (lo == 0 || s >= cand_start[lo - 1]), "candidate %lld: start %d out of range or out of order", (long long)lo, s);
+        const int k = start_set[s];
+        int64_t hi = lo + 1;
+        while (hi < n_cand && hi - lo < waves && cand_start[hi] >= 0 && cand_start[hi] < n_starts && cand_start[hi] >= cand_start[hi - 1] &&
+               start_set[cand_start[hi]] == k)
+            ++hi;
+        if (items) {
+            TSC_REQUIRE(count < items_cap, "tsc_csearch_multi_plan: more than %lld work items", (long long)items_cap);
+            items[4 * count] = int32_t(lo), items[4 * count + 1] = int32_t(hi), items[4 * count + 2] = set_off[k], items[4 * count + 3] = set_off[k + 1] - set_off[k];
+        }
+        ++count, lo = hi;
+    }
+    *n_items = count;
+    return 0;
+    TSC_API_GUARD_END
+}
+
+// set_off is a HOST array (it sizes the launch); everything else lives on the device
+extern "C" __attribute__((visibility("default"))) int tsc_csearch_rotate_multi_dev(tsc_ctx *c, const double *starts, int n_atoms, const int32_t *torsions,
+                                                                                   const uint8_t *masks, const int32_t *set_off, int n_sets,
+                                                                                   const int32_t *angles, int t_max, const int32_t *cand_start,
+                                                                                   const int32_t *cand_row, int64_t n_cand, const int32_t *items,
+                                                                                   int64_t n_items, double thresh, int64_t max_clashes, double *out,
+                                                                                   int32_t *rotated_bonds) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(c && set_off, "tsc_csearch_rotate_multi_dev: null argument");
+    int widest;
+    TSC_TRY(csearch_multi_sets(n_atoms, set_off, n_sets, &widest));
+    TSC_REQUIRE(t_max >= widest && n_items >= 0 && n_items <= n_cand, "bad sizes (table %d wide, widest set %d; %lld work items, %lld candidates)", t_max,
+                widest, (long long)n_items, (long long)n_cand);
+    CsearchMultiArgs ma;
+    TSC_TRY(csearch_args(n_atoms, widest, n_items, thresh, max_clashes, &ma.a));
+    TSC_REQUIRE(n_cand < INT32_MAX, "too many candidates");
+    if (n_cand == 0) return 0;
+    TSC_REQUIRE(starts && out && rotated_bonds && cand_start && cand_row && items && (widest == 0 || (torsions && masks && angles)),
+                "tsc_csearch_rotate_multi_dev: null argument");
+    DeviceGuard guard(c->device);
+    size_t lds;
+    const int waves = csearch_waves(n_atoms, widest, &lds);
+    ma.t_max = t_max, ma.lists_bytes = torsion_lists_bytes(widest, n_atoms);
+    if (lds > 64 * 1024)
+        TSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_csearch_rotate_multi), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+    hipLaunchKernelGGL(k_csearch_rotate_multi, dim3(grid_for(n_items, 1, 256 * 8)), dim3(64 * waves), lds, c->stream, ma, starts, torsions, masks, angles,
+                       cand_start, cand_row, items, out, rotated_bonds);
+    TSC_HIP(hipGetLastError());
+    return 0;
+    TSC_API_GUARD_END
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_csearch_rotate_multi(tsc_ctx *c, const double *starts, int n_starts, int n_atoms, const int32_t *torsions,
+                                                                               const uint8_t *masks, const int32_t *set_off, int n_sets,
+                                                                               const int32_t *start_set, const int32_t *angles, int64_t n_rows, int t_max,
+                                                                               const int32_t *cand_start, const int32_t *cand_row, int64_t n_cand,
+                                                                               double thresh, int64_t max_clashes, double *out, int32_t *rotated_bonds) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(c && set_off && (n_cand == 0 || (starts && start_set && cand_start && cand_row && out && rotated_bonds)),
+                "tsc_csearch_rotate_multi: null argument");
+    TSC_REQUIRE(n_starts >= 0 && n_rows >= 0 && n_rows < INT32_MAX && n_cand >= 0 && t_max >= 0, "bad sizes");
+    int64_t n_items = 0;
+    TSC_TRY(tsc_csearch_multi_plan(cand_start, n_cand, start_set, n_starts, set_off, n_sets, n_atoms, nullptr, 0, &n_items));
+    const int n_tors = set_off[n_sets];
+    TSC_REQUIRE(n_tors == 0 || (torsions && masks), "tsc_csearch_rotate_multi: null argument");
+    TSC_TRY(check_torsions(torsions, n_tors, n_atoms));
+    for (int64_t m = 0; m < n_cand; ++m) TSC_REQUIRE(cand_row[m] >= 0 && cand_row[m] < n_rows, "candidate %lld: angle row %d out of range", (long long)m, cand_row[m]);
+    if (n_cand == 0) return 0;
+    TSC_REQUIRE(n_rows * t_max == 0 || angles, "tsc_csearch_rotate_multi: null argument");
+    std::vector<int32_t> items(size_t(n_items) * 4);
+    TSC_TRY(tsc_csearch_multi_plan(cand_start, n_cand, start_set, n_starts, set_off, n_sets, n_atoms, items.data(), n_items, &n_items));
+    DeviceGuard guard(c->device);
+    Scratch s(c);
+    double *d_starts, *d_out;
+    int32_t *d_tors, *d_angles, *d_cs, *d_cr, *d_items, *d_rb;
+    uint8_t *d_masks;
+    TSC_TRY(upload(c, s, starts, size_t(n_starts) * n_atoms * 3, &d_starts));
+    TSC_TRY(upload(c, s, torsions, size_t(n_tors) * 4, &d_tors));
+    TSC_TRY(upload(c, s, masks, size_t(n_tors) * n_atoms, &d_masks));
+    TSC_TRY(upload(c, s, angles, size_t(n_rows) * t_max, &d_angles));
+    TSC_TRY(upload(c, s, cand_start, size_t(n_cand), &d_cs));
+    TSC_TRY(upload(c, s, cand_row, size_t(n_cand), &d_cr));
+    TSC_TRY(upload(c, s, items.data(), items.size(), &d_items));
+    TSC_TRY(s.get(size_t(n_cand) * n_atoms * 3, &d_out));
+    TSC_TRY(s.get(size_t(n_cand), &d_rb));
+    TSC_TRY(tsc_csearch_rotate_multi_dev(c, d_starts, n_atoms, d_tors, d_masks, set_off, n_sets, d_angles, t_max, d_cs, d_cr, n_cand, d_items, n_items, thresh,
+                                         max_clashes, d_out, d_rb));
+    TSC_HIP(hipMemcpyAsync(out, d_out, size_t(n_cand) * n_atoms * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TSC_HIP(hipMemcpyAsync(rotated_bonds, d_rb, size_t(n_cand) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TSC_HIP(hipStreamSynchronize(c->stream));   // (items, a host vector, is read by its upload until here)
+    return 0;
+    TSC_API_GUARD_END
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_csearch_select_dev(tsc_ctx *c, const double *cand, const int32_t *rotated_bonds, int n_atoms,
+                                                                             const int32_t *seg_off, const int32_t *seg_start, const int32_t *seg_a0, int n_seg,
+                                                                             int n_out, int64_t max_tries, int32_t *kept_count, int32_t *done,
+                                                                             int32_t *rows_consumed, double *kept_rows, int64_t capacity,
+                                                                             int64_t *n_kept_host) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(c && n_kept_host, "tsc_csearch_select_dev: null argument");
+    TSC_REQUIRE(n_atoms > 0 && n_seg >= 0 && capacity >= 0, "bad sizes (%d atoms, %d segments, room for %lld rows)", n_atoms, n_seg, (long long)capacity);
+    *n_kept_host = 0;
+    if (n_seg == 0) return 0;
+    TSC_REQUIRE(cand && rotated_bonds && seg_off && seg_start && seg_a0 && kept_count && done && rows_consumed && (capacity == 0 || kept_rows),
+                "tsc_csearch_select_dev: null argument");
+    DeviceGuard guard(c->device);
+    Scratch s(c);
+    int32_t *seg_kept, *total;
+    TSC_TRY(s.get(size_t(n_seg), &seg_kept));
+    TSC_TRY(s.get(1, &total));
+    hipLaunchKernelGGL(k_csearch_select, dim3(grid_for(n_seg, 4, INT32_MAX)), dim3(256), 0, c->stream, rotated_bonds, seg_off, seg_start, seg_a0, n_seg, n_out,
+                       (long long)max_tries, kept_count, done, rows_consumed, seg_kept);
+    hipLaunchKernelGGL(k_csearch_compact, dim3(grid_for(n_seg, 4, INT32_MAX)), dim3(256), 0, c->stream, cand, rotated_bonds, seg_off, (const int32_t *)seg_kept,
+                       n_seg, n_atoms * 3, (long long)capacity, kept_rows, total);
+    TSC_HIP(hipGetLastError());
+    int32_t kept = 0;
+    TSC_TRY(read_i32(c, total, &kept));
+    TSC_REQUIRE(kept <= capacity, "tsc_csearch_select_dev: %d rows kept, room for %lld (the rows past it were not written)", kept, (long long)capacity);
+    *n_kept_host = kept;
+    return 0;
+    TSC_API_GUARD_END
+}
+
 extern "C" __attribute__((visibility("default"))) int tsc_rotate_dihedral(tsc_ctx *c, const double *coords, int64_t n_structs, int n_atoms, const int32_t *torsion,
                                                                           const uint8_t *mask, const double *angles, double *out) {
     TSC_API_GUARD_BEGIN

@@ -252,6 +252,61 @@ inline __global__ __launch_bounds__(256) void k_rotate_dihedral(const double *__
     }
 }
 
+// One candidate of torsion_module.py:463-500 (and :745-780, the same loop) on the calling wavefront: copy the start into LDS, the
+// torsions in order, each rotated by its angle and walked back in 5-degree steps while it clashes, then the structure and the number
+// of bonds that really rotated written out.  `L` are the torsion lists of `tors` (n_tors torsions), `angle_row` the candidate's row of
+// the angle table; c / F / step_rot the wavefront's LDS area (csearch_wave_bytes).  Both candidate kernels below call this.
+__device__ __forceinline__ void csearch_candidate(const CsearchArgs &a, const double *__restrict__ base, const int32_t *__restrict__ tors, int n_tors,
+                                                  const int32_t *__restrict__ angle_row, const TorsionLists &L, double *c, float *F, double *step_rot,
+                                                  double *__restrict__ o, int32_t *__restrict__ rotated_out, int lane) {
+    const int n = a.n, npad = (n + 2) & ~1;
+    for (int e = lane; e < n * 3; e += 64) c[e] = base[e];  // new_coords = np.copy(coords), :473
+    __builtin_amdgcn_wave_barrier();
+    int rotated = 0;
+    for (int t = 0; t < n_tors; ++t) {
+        const int angle = angle_row[t];
+        if (angle == 0) continue;  // :482
+        const int i2 = tors[4 * t + 1], i3 = tors[4 * t + 2];
+        const uint16_t *moved = L.moved + size_t(t) * n, *fixed = L.fixed + size_t(t) * n;
+        const int nm = L.count[4 * t], nf = L.count[4 * t + 1];
+        const double cmax_fixed = a.max_clashes == 0 ? stage_fixed_f32(c, fixed, nf, F, npad, lane) : 0.0;
+        // :484-501 as one loop with a single check site: step -1 is the rotation by `angle`, steps 0 .. angle // 5 - 1 the walk-back
+        const int steps = angle >= 0 ? angle / 5 : 0;  // range(angle // 5): a negative angle is never walked back
+        // every step of the walk-back is the same rotation: the axis atoms do not move (i3 is the centre; i2 unless the mask turns
+        // it, in which case the matrix is formed anew each step as the reference does)
+        const bool same_matrix = L.count[4 * t + 2] == 0;
+        int hint = -1;
+        bool hint_ok = false;
+        float lo_h = 0.0f;
+        for (int rep = -1; rep < steps; ++rep) {
+            if (rep <= 0 || !same_matrix) {  // the matrix of this step -> LDS (the one place the trigonometry is done)
+                double R[9], cen[3];
+                dihedral_rotation(c, i2, i3, rep < 0 ? double(angle) : -5.0, R, cen);
+                if (rep == 0) {  // the walk-back begins: the band its hints are decided with
+                    float hi_h;
+                    hint_ok = a.max_clashes == 0 && fp32_min_band(a.sq_bound, fmax(cmax_fixed, moved_side_bound(c, cen, moved, nm, lane)), &lo_h, &hi_h);
+                }
+                __builtin_amdgcn_wave_barrier();
+                if (lane == 0) {
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) step_rot[i] = R[i];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) step_rot[9 + i] = cen[i];
+                }
+            }
+            apply_rotation_lds(c, step_rot, step_rot + 9, moved, nm, lane);  // :484, :491
+            if (rep >= 0 && hint_ok && hint >= 0 && hint_still_clashes(c, moved, nm, nf, F, npad, lo_h, hint, lane)) continue;  // still clashing
+            if (torsion_comp_check_lds(c, moved, nm, fixed, nf, F, npad, cmax_fixed, a.sq_bound, a.max_clashes, lane, &hint)) {  // :487, :492
+                ++rotated;  // :494, :501
+                break;
+            }
+        }
+    }
+    for (int e = lane; e < n * 3; e += 64) o[e] = c[e];
+    if (lane == 0) *rotated_out = rotated;
+    __builtin_amdgcn_wave_barrier();
+}
+
 // out [n_cand][n][3], rotated_bonds [n_cand]; angles [n_cand][n_tors] int32 degrees; masks [n_tors][n]; torsions [n_tors][4]
 // dynamic LDS: torsion lists, then one csearch_wave_bytes(n) area per wavefront of the block
 inline __global__ __launch_bounds__(256) void k_csearch_rotate(CsearchArgs a, const double *__restrict__ base, const int32_t *__restrict__ tors,
@@ -264,53 +319,120 @@ inline __global__ __launch_bounds__(256) void k_csearch_rotate(CsearchArgs a, co
     double *c = reinterpret_cast<double *>(s_raw + torsion_lists_bytes(a.n_tors, n) + size_t(wid) * csearch_wave_bytes(n));
     float *F = reinterpret_cast<float *>(c + size_t(n) * 3);
     double *step_rot = reinterpret_cast<double *>(F + size_t(3) * npad);
-    for (int64_t m = int64_t(blockIdx.x) * nw + wid; m < a.n_cand; m += int64_t(gridDim.x) * nw) {
-        for (int e = lane; e < n * 3; e += 64) c[e] = base[e];  // new_coords = np.copy(coords), :473
-        __builtin_amdgcn_wave_barrier();
-        int rotated = 0;
-        for (int t = 0; t < a.n_tors; ++t) {
-            const int angle = angles[m * a.n_tors + t];
-            if (angle == 0) continue;  // :482
-            const int i2 = tors[4 * t + 1], i3 = tors[4 * t + 2];
-            const uint16_t *moved = L.moved + size_t(t) * n, *fixed = L.fixed + size_t(t) * n;
-            const int nm = L.count[4 * t], nf = L.count[4 * t + 1];
-            const double cmax_fixed = a.max_clashes == 0 ? stage_fixed_f32(c, fixed, nf, F, npad, lane) : 0.0;
-            // :484-501 as one loop with a single check site: step -1 is the rotation by `angle`, steps 0 .. angle // 5 - 1 the walk-back
-            const int steps = angle >= 0 ? angle / 5 : 0;  // range(angle // 5): a negative angle is never walked back
-            // every step of the walk-back is the same rotation: the axis atoms do not move (i3 is the centre; i2 unless the mask turns
-            // it, in which case the matrix is formed anew each step as the reference does)
-            const bool same_matrix = L.count[4 * t + 2] == 0;
-            int hint = -1;
-            bool hint_ok = false;
-            float lo_h = 0.0f;
-            for (int rep = -1; rep < steps; ++rep) {
-                if (rep <= 0 || !same_matrix) {  // the matrix of this step -> LDS (the one place the trigonometry is done)
-                    double R[9], cen[3];
-                    dihedral_rotation(c, i2, i3, rep < 0 ? double(angle) : -5.0, R, cen);
-                    if (rep == 0) {  // the walk-back begins: the band its hints are decided with
-                        float hi_h;
-                        hint_ok = a.max_clashes == 0 && fp32_min_band(a.sq_bound, fmax(cmax_fixed, moved_side_bound(c, cen, moved, nm, lane)), &lo_h, &hi_h);
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    if (lane == 0) {
-#pragma unroll
-                        for (int i = 0; i < 9; ++i) step_rot[i] = R[i];
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) step_rot[9 + i] = cen[i];
-                    }
-                }
-                apply_rotation_lds(c, step_rot, step_rot + 9, moved, nm, lane);  // :484, :491
-                if (rep >= 0 && hint_ok && hint >= 0 && hint_still_clashes(c, moved, nm, nf, F, npad, lo_h, hint, lane)) continue;  // still clashing
-                if (torsion_comp_check_lds(c, moved, nm, fixed, nf, F, npad, cmax_fixed, a.sq_bound, a.max_clashes, lane, &hint)) {  // :487, :492
-                    ++rotated;  // :494, :501
-                    break;
-                }
-            }
+    for (int64_t m = int64_t(blockIdx.x) * nw + wid; m < a.n_cand; m += int64_t(gridDim.x) * nw)
+        csearch_candidate(a, base, tors, a.n_tors, angles + m * a.n_tors, L, c, F, step_rot, out + m * n * 3, rotated_bonds + m, lane);
+}
+
+// The same candidates for many start structures and torsion sets in one launch (tscode/torsion_module.py:736-780: the loop over
+// starting_points of clustered_csearch; tscode/embedder.py:1907-1939: one random_csearch per TS candidate).  Candidate m is
+// (start cand_start[m], row cand_row[m] of the shared angle table, whose rows are t_max wide and zero-padded).  The host cuts the
+// candidates into work items (lo, hi, first torsion of the set, torsions of the set) of at most one candidate per wavefront
+// that never straddle a torsion set; a workgroup walks items with a grid stride and rebuilds its LDS torsion lists only when the
+// set of its next item is not the one it holds.  dynamic LDS: the lists of the widest set, then one area per wavefront.
+struct CsearchMultiArgs {
+    CsearchArgs a;           // n_tors: unused (each item carries its own); n_cand: the number of work items
+    int t_max;               // row stride of angles
+    size_t lists_bytes;      // torsion_lists_bytes of the widest set
+};
+
+inline __global__ __launch_bounds__(256) void k_csearch_rotate_multi(CsearchMultiArgs ma, const double *__restrict__ starts, const int32_t *__restrict__ tors,
+                                                               const uint8_t *__restrict__ masks, const int32_t *__restrict__ angles,
+                                                               const int32_t *__restrict__ cand_start, const int32_t *__restrict__ cand_row,
+                                                               const int32_t *__restrict__ items, double *__restrict__ out,
+                                                               int32_t *__restrict__ rotated_bonds) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, n = ma.a.n, npad = (n + 2) & ~1;
+    double *c = reinterpret_cast<double *>(s_raw + ma.lists_bytes + size_t(wid) * csearch_wave_bytes(n));
+    float *F = reinterpret_cast<float *>(c + size_t(n) * 3);
+    double *step_rot = reinterpret_cast<double *>(F + size_t(3) * npad);
+    int held_off = -1, held_n = -1;  // the set whose lists are in LDS
+    TorsionLists L = torsion_lists_at(s_raw, 0, n);
+    for (int64_t it = blockIdx.x; it < ma.a.n_cand; it += gridDim.x) {  // (block-uniform: every wavefront sees the same items)
+        const int lo = items[4 * it], hi = items[4 * it + 1], t_off = items[4 * it + 2], n_tors = items[4 * it + 3];
+        const int32_t *set_tors = tors + size_t(t_off) * 4;
+        if (t_off != held_off || n_tors != held_n) {
+            __syncthreads();  // nobody still walks the lists of the previous set
+            L = torsion_lists_at(s_raw, n_tors, n);
+            build_torsion_lists(L, masks + size_t(t_off) * n, set_tors, n_tors, n);
+            held_off = t_off, held_n = n_tors;
         }
-        double *o = out + m * n * 3;
-        for (int e = lane; e < n * 3; e += 64) o[e] = c[e];
-        if (lane == 0) rotated_bonds[m] = rotated;
-        __builtin_amdgcn_wave_barrier();
+        const int64_t m = int64_t(lo) + wid;
+        if (m < hi)
+            csearch_candidate(ma.a, starts + size_t(cand_start[m]) * n * 3, set_tors, n_tors, angles + size_t(cand_row[m]) * ma.t_max, L, c, F, step_rot,
+                              out + m * n * 3, rotated_bonds + m, lane);
+    }
+}
+
+// The stop rule of tscode/torsion_module.py:505-511 for one start's segment [lo, hi) of a round, on one wavefront: a row is kept iff
+// rotated_bonds != 0, and only just after a row was kept is `len(new_structures) == n_out or a == max_tries` tested (a: the row's
+// index in that start's table, a0 + its position in the segment).  n_out < 0: no stop on the count (:779 keeps every rotated row).
+// Returns the number of rows taken (wave-uniform); *consumed = rows walked, *stopped = whether the walk ended inside the segment.
+__device__ inline int csearch_select_segment(const int32_t *__restrict__ rotated_bonds, int lo, int hi, int a0, int kept_before, int n_out,
+                                             long long max_tries, int lane, int *consumed, int *stopped) {
+    int taken = 0;
+    *stopped = 0, *consumed = hi - lo;
+    for (int b = lo; b < hi; b += 64) {
+        const int m = b + lane;
+        const bool kept = m < hi && rotated_bonds[m] != 0;
+        const unsigned long long bk = __ballot(kept), upto = lane == 63 ? ~0ull : (1ull << (lane + 1)) - 1ull;
+        const int rank = kept_before + taken + __popcll(bk & upto);  // len(new_structures) just after this row was appended
+        const bool stop = kept && ((n_out >= 0 && rank == n_out) || (long long)(a0 + (m - lo)) == max_tries);
+        const unsigned long long bs = __ballot(stop);
+        if (bs) {
+            const int j = __ffsll((long long)bs) - 1;
+            taken += __popcll(bk & (j == 63 ? ~0ull : (1ull << (j + 1)) - 1ull));
+            *consumed = b + j + 1 - lo, *stopped = 1;
+            return taken;
+        }
+        taken += __popcll(bk);
+    }
+    return taken;
+}
+
+// One wavefront per segment g = candidates [seg_off[g], seg_off[g + 1]) of start seg_start[g], whose first row has index seg_a0[g]
+// in its start's table.  State per start, carried from round to round: kept_count (in / out), done (in / out); rows_consumed (out)
+// = rows of this segment the reference's loop would have walked.  seg_kept[g] = rows taken this round.
+inline __global__ __launch_bounds__(256) void k_csearch_select(const int32_t *__restrict__ rotated_bonds, const int32_t *__restrict__ seg_off,
+                                                         const int32_t *__restrict__ seg_start, const int32_t *__restrict__ seg_a0, int n_seg, int n_out,
+                                                         long long max_tries, int32_t *__restrict__ kept_count, int32_t *__restrict__ done,
+                                                         int32_t *__restrict__ rows_consumed, int32_t *__restrict__ seg_kept) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_seg) return;
+    const int s = seg_start[g];
+    int taken = 0, consumed = 0, stopped = 0;
+    if (!done[s]) taken = csearch_select_segment(rotated_bonds, seg_off[g], seg_off[g + 1], seg_a0[g], kept_count[s], n_out, max_tries, lane, &consumed, &stopped);
+    if (lane == 0) {
+        kept_count[s] += taken, rows_consumed[s] = consumed, seg_kept[g] = taken;
+        if (stopped) done[s] = 1;
+    }
+}
+
+// The rows k_csearch_select took, compacted in order into the output: segment g's slice begins at the sum of seg_kept over the
+// segments before it and holds the first seg_kept[g] rows of the segment with rotated_bonds != 0 (the rows taken are a prefix of
+// the rows kept).  One wavefront per segment; rows past `capacity` are not written; total[0] = rows taken by all segments.
+inline __global__ __launch_bounds__(256) void k_csearch_compact(const double *__restrict__ cand, const int32_t *__restrict__ rotated_bonds,
+                                                          const int32_t *__restrict__ seg_off, const int32_t *__restrict__ seg_kept, int n_seg,
+                                                          int row_doubles, long long capacity, double *__restrict__ kept_rows,
+                                                          int32_t *__restrict__ total) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_seg) return;
+    long long off = 0;
+    for (int h = lane; h < g; h += 64) off += seg_kept[h];
+    for (int d = 32; d > 0; d >>= 1) off += __shfl_xor(off, d);
+    const int want = seg_kept[g], lo = seg_off[g], hi = seg_off[g + 1];
+    if (g == n_seg - 1 && lane == 0) total[0] = int32_t(off + want);
+    int taken = 0;
+    for (int b = lo; b < hi && taken < want; b += 64) {
+        const int m = b + lane;
+        const unsigned long long bk = __ballot(m < hi && rotated_bonds[m] != 0);
+        for (unsigned long long rest = bk; rest && taken < want; rest &= rest - 1, ++taken) {
+            const int j = __ffsll((long long)rest) - 1;
+            const long long dst = off + taken;
+            if (dst >= capacity) continue;
+            const double *src = cand + size_t(b + j) * row_doubles;
+            double *o = kept_rows + size_t(dst) * row_doubles;
+            for (int e = lane; e < row_doubles; e += 64) o[e] = src[e];
+        }
     }
 }
 

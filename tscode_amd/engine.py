@@ -405,6 +405,66 @@ class Engine:
         check(self.lib.tsc_csearch_rotate_dev(self._h, ptr(coords), C.c_int(n_atoms), ptr(torsions), ptr(masks), C.c_int(n_tors), ptr(angles),
                                               C.c_int64(n_cand), C.c_double(thresh), C.c_int64(int(max_clashes)), ptr(out), ptr(rotated_bonds)))
 
+    def csearch_multi_plan(self, cand_start, start_set, set_off, n_atoms):
+        """The work items i32[n_items, 4] of tsc_csearch_rotate_multi_dev for candidates in start order (host arrays, no device work)."""
+        n_items = C.c_int64()
+        args = (ptr(cand_start), C.c_int64(len(cand_start)), ptr(start_set), C.c_int(len(start_set)), ptr(set_off), C.c_int(len(set_off) - 1),
+                C.c_int(n_atoms))
+        check(self.lib.tsc_csearch_multi_plan(*args, None, C.c_int64(0), C.byref(n_items)))
+        items = np.empty((n_items.value, 4), dtype=np.int32)
+        check(self.lib.tsc_csearch_multi_plan(*args, ptr(items), C.c_int64(len(items)), C.byref(n_items)))
+        return items
+
+    def csearch_rotate_multi(self, starts, torsions, masks, set_off, start_set, angles, cand_start, cand_row, thresh=1.5, max_clashes=0):
+        """tsc_csearch_rotate_multi on host arrays (include/tscode_hip.h): candidate m = start cand_start[m] turned by row cand_row[m]
+        of angles i32[R, t_max] with the torsion set start_set[cand_start[m]].  Returns (new_coords f64[K, n, 3], rotated_bonds i32[K])."""
+        S, n = starts.shape[:2]
+        out = np.empty((len(cand_start), n, 3))
+        rb = np.zeros(len(cand_start), dtype=np.int32)
+        check(self.lib.tsc_csearch_rotate_multi(self._h, ptr(starts), C.c_int(S), C.c_int(n), ptr(torsions), ptr(masks), ptr(set_off),
+                                                C.c_int(len(set_off) - 1), ptr(start_set), ptr(angles), C.c_int64(angles.shape[0]),
+                                                C.c_int(angles.shape[1]), ptr(cand_start), ptr(cand_row), C.c_int64(len(cand_start)),
+                                                C.c_double(thresh), C.c_int64(int(max_clashes)), ptr(out), ptr(rb)))
+        return out, rb
+
+    def csearch_rotate_multi_dev(self, starts, n_atoms, torsions, masks, set_off, angles, t_max, cand_start, cand_row, n_cand, items, n_items,
+                                 thresh, max_clashes, out, rotated_bonds):
+        """The same on device buffers, asynchronous on the engine's stream; set_off is a host array, items come from csearch_multi_plan."""
+        check(self.lib.tsc_csearch_rotate_multi_dev(self._h, ptr(starts), C.c_int(n_atoms), ptr(torsions), ptr(masks), ptr(set_off),
+                                                    C.c_int(len(set_off) - 1), ptr(angles), C.c_int(t_max), ptr(cand_start), ptr(cand_row),
+                                                    C.c_int64(n_cand), ptr(items), C.c_int64(n_items), C.c_double(thresh),
+                                                    C.c_int64(int(max_clashes)), ptr(out), ptr(rotated_bonds)))
+
+    def csearch_select_dev(self, cand, rotated_bonds, n_atoms, seg_off, seg_start, seg_a0, n_seg, n_out, max_tries, kept_count, done,
+                           rows_consumed, kept_rows, capacity):
+        """tsc_csearch_select_dev: the stop rule of tscode/torsion_module.py:505-511 and the ordered compaction, on device buffers.
+        n_out None = keep every rotated row.  Returns the number of rows written to kept_rows."""
+        n_kept = C.c_int64()
+        check(self.lib.tsc_csearch_select_dev(self._h, ptr(cand), ptr(rotated_bonds), C.c_int(n_atoms), ptr(seg_off), ptr(seg_start), ptr(seg_a0),
+                                              C.c_int(n_seg), C.c_int(-1 if n_out is None else int(n_out)), C.c_int64(int(max_tries)),
+                                              ptr(kept_count), ptr(done), ptr(rows_consumed), ptr(kept_rows), C.c_int64(capacity),
+                                              C.byref(n_kept)))
+        return n_kept.value
+
+    # device memory of the context for the callers that keep buffers resident between calls (raw addresses: ptr() takes them)
+    def dev_alloc(self, nbytes) -> int:
+        p = C.c_void_p()
+        check(self.lib.tsc_malloc(self._h, C.c_size_t(int(nbytes)), C.byref(p)))
+        return p.value
+
+    def dev_free(self, addr):
+        check(self.lib.tsc_free(self._h, C.c_void_p(addr)))
+
+    def dev_upload(self, host: np.ndarray) -> int:
+        host = np.ascontiguousarray(host)
+        addr = self.dev_alloc(host.nbytes)
+        check(self.lib.tsc_memcpy_h2d(self._h, C.c_void_p(addr), ptr(host), C.c_size_t(host.nbytes)))
+        return addr
+
+    def dev_download(self, addr, host: np.ndarray):
+        check(self.lib.tsc_memcpy_d2h(self._h, ptr(host), C.c_void_p(addr), C.c_size_t(host.nbytes)))
+        return host
+
     def rotate_dihedral_batch(self, coords, torsion, mask, angles):
         """rotate_dihedral (tscode/utils.py:389-414) on structures f64[M, n, 3] sharing torsion and mask: structure s by angles[s]
         degrees (floats).  Returns the rotated copies."""
