@@ -23,7 +23,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-__all__ = ["Ensemble", "make_fragment", "make_ensemble", "make_unscreenable", "CONFIGS", "make_config", "quat_to_mat", "make_rot_corr_ensemble", "make_chain_ensemble",
+__all__ = ["Ensemble", "make_fragment", "make_ensemble", "make_unscreenable", "CONFIGS", "make_config", "quat_to_mat", "make_rot_corr_ensemble",
+           "RotorMolecule", "make_rotor_molecule", "make_chain_ensemble",
            "CHAIN_ELEMENTS", "CHAIN_SIGMAS", "aromatic_block", "make_aromatic_ensemble", "AROMATIC_SIGMAS"]
 
 
@@ -251,6 +252,158 @@ def make_rot_corr_ensemble(base, torsions, angles, move_masks, n_clusters, per_c
             labels.append(c)
     perm = rng.permutation(len(out))
     return np.array(out)[perm], np.array(labels)[perm]
+
+
+@dataclass
+class RotorMolecule:
+    """What make_rotor_molecule returns: the molecule and the set-up arrays of tscode_amd.prune_rmsd_rot_corr_arrays."""
+
+    coords: np.ndarray          # f64[n, 3]
+    atomnos: np.ndarray         # int[n]: 6 (tree and hubs), 9 (rotor atoms), 1
+    bonds: list                 # [(a, b)], a < b: a tree
+    torsions: np.ndarray        # i32[T, 4]: (a neighbour of i2, i2, i3 = the rotor's hub, one of its k atoms)
+    angles: list                # T tuples of degrees, 0 first
+    folds: list                 # T ints
+    move_masks: np.ndarray      # bool[T, n]
+    sub_nodes: list             # T sorted index lists
+
+    def setup(self):
+        return dict(torsions=self.torsions, angles=self.angles, move_masks=self.move_masks, sub_nodes=self.sub_nodes)
+
+
+def _unit(v):
+    return v / np.sqrt(v @ v)
+
+
+def _cone(rng, p, back, length, k):
+    """k positions bonded to p, 109.47 degrees from the bond p - back, at exact 360 / k steps about it (random phase)."""
+    w = _unit(back - p)
+    e1 = _unit(np.cross(w, [1.0, 0.0, 0.0] if abs(w[0]) < 0.9 else [0.0, 1.0, 0.0]))
+    e2 = np.cross(w, e1)
+    th, phi0 = np.radians(109.47), rng.uniform(0.0, 2 * np.pi)
+    return [p + length * (np.cos(th) * w + np.sin(th) * (np.cos(phi0 + 2 * np.pi * s / k) * e1 + np.sin(phi0 + 2 * np.pi * s / k) * e2))
+            for s in range(k)]
+
+
+def _component(n, bonds, cut, start):
+    """The atoms reachable from ``start`` over ``bonds`` without the bonds of ``cut``."""
+    cut = {tuple(sorted(b)) for b in cut}
+    nb = [[] for _ in range(n)]
+    for a, b in bonds:
+        if tuple(sorted((a, b))) not in cut:
+            nb[a].append(b)
+            nb[b].append(a)
+    seen, todo = {start}, [start]
+    while todo:
+        for b in nb[todo.pop()]:
+            if b not in seen:
+                seen.add(b)
+                todo.append(b)
+    return seen
+
+
+def make_rotor_molecule(n_atoms, groups, seed=0, heavy_share=0.6, order=None, table=None):
+    """A tree-shaped molecule with symmetric heavy-atom rotors, and the set-up of the symmetry-corrected prune on it.
+
+    The tree is a branched self-avoiding walk of carbons (1.5 A steps).  Each entry of ``groups`` hangs one rotor group on a tree
+    atom and is ``k``, ``(k, kc)`` or either with the string "far" appended:
+      k        a hub carbon with k identical atoms (Z = 9) at exact 360 / k steps about the hub's bond: one k-fold torsion;
+      (k, kc)  the k atoms are hub carbons themselves, images of one another under the 360 / k turn, each with kc identical atoms
+               about its own bond (C(CF3)3 is (3, 3)): one k-fold torsion, then k torsions of fold kc;
+      "far"    the group's first torsion turns the OTHER side of its bond (the rest of the molecule), so its moved list is long.
+    Hydrogens on tree atoms fill the molecule up to ``n_atoms``; ``heavy_share`` of the atoms outside the groups are tree carbons.
+
+    Per torsion (i1, i2, i3, i4), i3 is the rotor's hub.  ``angles`` are 0, 360 / k, ... (``table`` = {torsion: angles} replaces
+    single entries); ``move_masks`` hold one side of the i2 - i3 bond without i2 and i3 (the rotor's side unless "far");
+    ``sub_nodes`` are the sorted heavy atoms of the component of i2 once every other torsion's bond is cut.
+
+    ``order``: None leaves heavy atoms first and hydrogens last; "shuffle" draws a permutation from the seed, an array gives one
+    (new atom q is old atom order[q]).  Returns a RotorMolecule."""
+    rng = np.random.default_rng(seed)
+    specs = []
+    for g in groups:
+        g = (g,) if isinstance(g, int) else tuple(g)
+        far = g[-1] == "far"
+        g = g[:-1] if far else g
+        if len(g) not in (1, 2) or any(k not in (2, 3, 4, 6) for k in g):
+            raise ValueError(f"rotor group {g!r}: k or (k, kc) with folds of 2, 3, 4 or 6")
+        specs.append((g[0], g[1] if len(g) == 2 else 0, far))
+    in_groups = sum(1 + k + k * kc for k, kc, _ in specs)
+    n_tree = int(np.ceil((n_atoms - in_groups) * heavy_share))
+    n_h = n_atoms - in_groups - n_tree
+    if n_tree < 2 or n_h < 0:
+        raise ValueError(f"{n_atoms} atoms do not hold these rotor groups and a tree")
+
+    z, x, bonds = [6], [np.zeros(3)], []
+
+    def add(zz, pos, to):
+        z.append(zz)
+        x.append(np.asarray(pos, dtype=np.float64))
+        bonds.append((to, len(z) - 1))
+        return len(z) - 1
+
+    tries = 0
+    while len(z) < n_tree:                                                          # the tree
+        base = len(z) - 1 if rng.random() < 0.7 else int(rng.integers(0, len(z)))
+        cand = x[base] + 1.5 * _unit(rng.normal(size=3))
+        d = np.sqrt(((np.array(x) - cand) ** 2).sum(axis=1))
+        d[base] = np.inf
+        tries += 1
+        if d.min() >= 1.2:
+            add(6, cand, base)
+        if tries > 100000:
+            raise RuntimeError("random walk stuck")
+    tors, folds, far_flags = [], [], []
+    anchors = rng.permutation(np.arange(1, n_tree))[:len(specs)] if n_tree > len(specs) else rng.integers(1, n_tree, size=len(specs))
+    for (k, kc, far), a in zip(specs, anchors.tolist()):
+        back = next(p for p, q in bonds if q == a)                                  # the tree atom that a grew from
+        hub = add(6, x[a] + 1.52 * _unit(x[a] - x[back] + 0.5 * rng.normal(size=3)), a)
+        first = _cone(rng, x[hub], x[a], 1.54 if kc else 1.35, k)
+        ring = [add(6 if kc else 9, p, hub) for p in first]
+        tors.append((back, a, hub, ring[0]))
+        folds.append(k)
+        far_flags.append(far)
+        if kc:
+            # the first sub-rotor, then its images under the group's 360 / k turn about the hub's bond
+            axis = _unit(x[a] - x[hub])                                             # (the sense in which _cone steps)
+            leaves = np.array(_cone(rng, x[ring[0]], x[hub], 1.35, kc))
+            for s, c in enumerate(ring):
+                R = quat_to_mat(np.array([[np.cos(np.pi * s / k), *(np.sin(np.pi * s / k) * axis)]]))[0]
+                img = (leaves - x[hub]) @ R.T + x[hub]
+                ids = [add(9, p, c) for p in img]
+                tors.append((a, hub, c, ids[0]))
+                folds.append(kc)
+                far_flags.append(False)
+    for q in range(n_h):                                                            # hydrogens, round the tree
+        a = q % n_tree
+        add(1, x[a] + 1.09 * _unit(rng.normal(size=3)), a)
+    z, x = np.array(z), np.array(x)
+    n = len(z)
+    assert n == n_atoms
+
+    masks, subs = np.zeros((len(tors), n), dtype=bool), []
+    for t, (i1, i2, i3, i4) in enumerate(tors):
+        side = _component(n, bonds, [(i2, i3)], i2 if far_flags[t] else i3)
+        masks[t, list(side)] = True
+        masks[t, [i2, i3]] = False
+        comp = _component(n, bonds, [(o[1], o[2]) for q, o in enumerate(tors) if q != t], i2)
+        subs.append(sorted(i for i in comp if z[i] != 1))
+    angles = [tuple(360.0 / k * s for s in range(k)) for k in folds]
+    for t, a in (table or {}).items():
+        angles[t] = tuple(float(v) for v in a)
+    if order is None:
+        order = np.array(sorted(range(n), key=lambda i: (z[i] == 1, i)))
+    elif isinstance(order, str):
+        if order != "shuffle":
+            raise ValueError(f"order = {order!r}")
+        order = rng.permutation(n)
+    order = np.asarray(order)
+    new = np.empty(n, dtype=np.int64)
+    new[order] = np.arange(n)
+    return RotorMolecule(coords=np.ascontiguousarray(x[order]), atomnos=z[order],
+                         bonds=sorted(tuple(sorted((int(new[a]), int(new[b])))) for a, b in bonds),
+                         torsions=new[np.array(tors)].astype(np.int32), angles=angles, folds=list(folds),
+                         move_masks=np.ascontiguousarray(masks[:, order]), sub_nodes=[sorted(new[s].tolist()) for s in subs])
 
 
 # ---- chains for the topology checks (tscode_amd.graph_manipulations; fixtures G21) ---------------------------------------------
