@@ -505,3 +505,75 @@ def test_kmeans_plusplus_rows_follows_the_stated_rule():
         assert np.array_equal(rows, tscode_amd.kmeans_plusplus_rows(c.X, 40, seed))
         assert len(set(rows.tolist())) == 40
         assert np.array_equal(rows, want)
+
+
+@pytest.mark.gpu
+def test_stage_times_are_taken_only_under_pass_timing_and_per_thread():
+    """tsc_diverse_timings on 8 structures of 4 atoms, k = 2: four slots of -1 without the option; with it the select fills all four
+    with positive times and the alignment alone its own slot; -1 again once the option is off, -1 in a thread that never called."""
+    import threading
+    import tscode_amd
+    from tscode_amd import _lib
+    eng = tscode_amd.get_engine()
+    s = np.random.default_rng(8).normal(size=(8, 4, 3))
+
+    def times():
+        ms = (C.c_float * 4)()
+        _lib.check(eng.lib.tsc_diverse_timings(eng._h, ms))
+        return list(ms)
+
+    def in_a_fresh_thread():
+        got = []
+        t = threading.Thread(target=lambda: got.append(times()))
+        t.start()
+        t.join()
+        return got[0]
+
+    eng.set_option("pass_timing", 0)
+    want = tscode_amd.diverse_select(s, 2, init_rows=[0, 1])
+    assert times() == [-1.0] * 4
+    eng.set_option("pass_timing", 1)
+    try:
+        got = tscode_amd.diverse_select(s, 2, init_rows=[0, 1])
+        assert all(np.isfinite(t) and t > 0.0 for t in times()), times()
+        assert all(np.asarray(a).tobytes() == np.asarray(b).tobytes() for a, b in zip(got, want))
+        assert in_a_fresh_thread() == [-1.0] * 4
+        tscode_amd.align_structures(s.copy())
+        align = times()
+        assert np.isfinite(align[0]) and align[0] > 0.0 and align[1:] == [-1.0] * 3, align
+        tscode_amd.kmeans_lloyd(s.reshape(8, -1), s.reshape(8, -1)[:2])
+        lloyd = times()
+        assert lloyd[0] == -1.0 and lloyd[3] == -1.0 and lloyd[1] > 0.0 and lloyd[2] > 0.0, lloyd
+    finally:
+        eng.set_option("pass_timing", 0)
+    tscode_amd.diverse_select(s, 2, init_rows=[0, 1])
+    assert times() == [-1.0] * 4
+
+
+@pytest.mark.parametrize("k", (16, 17, 128))
+def test_template_width_inputs_are_settled(k):
+    X, init = _width_case(k)
+    labels, centres, inertia, n_iter, margin, max_empty = lloyd_restated(X, init)
+    assert margin >= MARGIN_BAND and max_empty == 0 and n_iter >= 2
+
+
+def _width_case(k):
+    """k centres among k + 40 rows of 9 columns: 16 and 17 clusters are one and two centre tiles of the assign kernel (its template
+    widths 1 and 2, at their boundary), 128 are eight tiles in one block (width 8, which neither the fixtures -- widths 1, 2 and 3 -- nor
+    the scale case -- width 7 -- reach)."""
+    rng = np.random.default_rng(500 + k)
+    X = rng.normal(size=(k + 40, 9))
+    return X, X[rng.choice(len(X), k, replace=False)].copy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", (16, 17, 128))
+def test_kmeans_lloyd_at_the_template_widths_of_the_assign_kernel(k):
+    import tscode_amd
+    X, init = _width_case(k)
+    want_labels, want_centres, want_inertia, want_iter, margin, _ = lloyd_restated(X, init)
+    assert margin >= MARGIN_BAND
+    labels, centres, inertia, n_iter = tscode_amd.kmeans_lloyd(X, init)
+    assert np.array_equal(labels, want_labels) and n_iter == want_iter
+    assert np.abs(centres - want_centres).max() <= COORD_TOL
+    assert abs(inertia - want_inertia) <= 1e-9 * want_inertia

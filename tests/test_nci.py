@@ -635,3 +635,62 @@ def test_device_entry_equals_the_host_entry():
         assert (got.view(host[k].dtype if k != "overflow" else np.uint8) == host[k]).all(), k
     empty = eng.nci(np.zeros((0, n, 3)), classes, thr, atom_mol, len(ids), cand, ring_thr, 3.8, None, 0, ("pair_bits",))
     assert empty["counts"].shape == (0, 4) and empty["pair_bits"].shape == (0, n, w)
+
+
+@pytest.mark.gpu
+def test_kernel_time_is_taken_only_under_pass_timing_and_per_thread():
+    """tsc_nci_timings on 3 structures of the smallest fixture molecule: -1 without the option, a positive time with it through both
+    entries, -1 after zero structures, -1 again once the option is off, -1 in a thread that never called."""
+    import math
+    import threading
+    import torch
+    import tscode_amd
+    from tscode_amd.nci import NCI_DICT, check_nci_args, nci_tables
+    g = g22(min(CASES, key=lambda case: len(g22(case).atomnos)))
+    x, z, ids, atom_mol, con, rule, _ = check_nci_args(g.structures[:3], g.atomnos, g.constrained[:3], g.ids)
+    classes, thr, ring_thr, cand = nci_tables(z)
+    eng = tscode_amd.get_engine()
+    N, n = x.shape[:2]
+    assert N == 3
+    dev = torch.device("cuda", eng.device)
+    counts = torch.zeros((N, 4), dtype=torch.int32, device=dev)
+    overflow = torch.zeros((N,), dtype=torch.uint8, device=dev)
+    d_x, d_con = torch.from_numpy(x).to(dev), torch.from_numpy(con).to(dev)
+    torch.cuda.synchronize()
+
+    def host(rows=N):
+        return eng.nci(x[:rows], classes, thr, atom_mol, len(ids), cand, ring_thr, NCI_DICT["PhPh"][0], con[:rows], rule, ())
+
+    def device():
+        eng.nci_dev(d_x, N, n, classes, thr, atom_mol, len(ids), cand, ring_thr, NCI_DICT["PhPh"][0], d_con, True, rule, counts, overflow)
+        eng.synchronize()
+
+    def in_a_fresh_thread():
+        got = []
+        t = threading.Thread(target=lambda: got.append(eng.nci_kernel_ms()))
+        t.start()
+        t.join()
+        return got[0]
+
+    eng.set_option("pass_timing", 0)
+    want = host()
+    assert eng.nci_kernel_ms() == -1.0
+    device()
+    assert eng.nci_kernel_ms() == -1.0
+    eng.set_option("pass_timing", 1)
+    try:
+        timed = host()
+        assert math.isfinite(eng.nci_kernel_ms()) and eng.nci_kernel_ms() > 0.0
+        assert (timed["counts"] == want["counts"]).all()
+        assert in_a_fresh_thread() == -1.0
+        device()
+        assert math.isfinite(eng.nci_kernel_ms()) and eng.nci_kernel_ms() > 0.0
+        assert (counts.cpu().numpy() == want["counts"]).all()
+        host(0)
+        assert eng.nci_kernel_ms() == -1.0
+        host()
+        assert eng.nci_kernel_ms() > 0.0
+    finally:
+        eng.set_option("pass_timing", 0)
+    host()
+    assert eng.nci_kernel_ms() == -1.0

@@ -861,3 +861,64 @@ def test_string_inputs_feed_string_embed_to_the_recorded_poses():
                                               clash_thresh=float(g[f"clash_thresh_{k}"]), quadruplets=g[f"quadruplets_{k}"])
         assert poses.shape == g[f"poses_{k}"].shape and np.abs(poses - g[f"poses_{k}"]).max() < VAL_TOL
     assert neighbor_lists(edges[5][17], 5)[0] == [1, 2, 3, 4]
+
+
+@pytest.mark.gpu
+def test_kernel_time_is_taken_only_under_pass_timing_and_per_thread():
+    """tsc_orbitals_timings on 2 conformers of the smallest fixture: -1 without the option, a positive time with it through both
+    entries, -1 after zero conformers, -1 again once the option is off, -1 in a thread that never called."""
+    import math
+    import threading
+    import torch
+    import tscode_amd
+    from tscode_amd.reactive_atoms import orbital_recipes
+    g = g23(min(CASES, key=lambda case: g23(case).coords.shape[1]))
+    opts = case_options(g)
+    rec = orbital_recipes(g.atomnos, g.reactive, g.edges, orb_dim=opts["orb_dim"], leaving_group=opts["leaving_group"], sp_seed=g.seed)
+    x = np.ascontiguousarray(g.coords[:2], dtype=np.float64)
+    C, n, R = x.shape[0], x.shape[1], len(g.reactive)
+    assert C == 2
+    eng = tscode_amd.get_engine()
+    dev = torch.device("cuda", eng.device)
+    shapes = {"centers": ((C, R, 4, 3), torch.float64), "orb_vecs": ((C, R, 4, 3), torch.float64), "n_lobes": ((C, R), torch.uint8),
+              "kind": ((C, R), torch.uint8), "sigmatropic": ((C,), torch.uint8)}
+    out = {k: torch.zeros(s, dtype=t, device=dev) for k, (s, t) in shapes.items()}
+    d_x = torch.from_numpy(x).to(dev)
+    torch.cuda.synchronize()
+
+    def host(rows=C):
+        return eng.orbitals(x[:rows], rec["recipes"], rec["sigmatropic_mode"], False, want_pivots=False)
+
+    def device():
+        eng.orbitals_dev(d_x, C, n, rec["recipes"], rec["sigmatropic_mode"], False, *out.values())
+        eng.synchronize()
+
+    def in_a_fresh_thread():
+        got = []
+        t = threading.Thread(target=lambda: got.append(eng.orbitals_kernel_ms()))
+        t.start()
+        t.join()
+        return got[0]
+
+    eng.set_option("pass_timing", 0)
+    want = host()
+    assert eng.orbitals_kernel_ms() == -1.0
+    device()
+    assert eng.orbitals_kernel_ms() == -1.0
+    eng.set_option("pass_timing", 1)
+    try:
+        timed = host()
+        assert math.isfinite(eng.orbitals_kernel_ms()) and eng.orbitals_kernel_ms() > 0.0
+        assert timed["centers"].tobytes() == want["centers"].tobytes()
+        assert in_a_fresh_thread() == -1.0
+        device()
+        assert math.isfinite(eng.orbitals_kernel_ms()) and eng.orbitals_kernel_ms() > 0.0
+        assert out["centers"].cpu().numpy().tobytes() == want["centers"].tobytes()
+        host(0)
+        assert eng.orbitals_kernel_ms() == -1.0
+        host()
+        assert eng.orbitals_kernel_ms() > 0.0
+    finally:
+        eng.set_option("pass_timing", 0)
+    host()
+    assert eng.orbitals_kernel_ms() == -1.0

@@ -499,3 +499,46 @@ def test_graphize_drop_in():
         assert [graph.nodes[i]["atomnos"] for i in range(50)] == g.atomnos.tolist()
     full = ta.graphize(g.base, g.atomnos)
     assert sorted(a for a, b in full.edges if a == b) == list(range(50))
+
+
+def read_from_a_fresh_thread(read):
+    import threading
+    got = []
+    t = threading.Thread(target=lambda: got.append(read()))
+    t.start()
+    t.join()
+    return got[0]
+
+
+@pytest.mark.gpu
+def test_kernel_time_is_taken_only_under_pass_timing_and_per_thread():
+    """tsc_topology_timings on 3 structures of 5 atoms: -1 without the option, a positive time with it through both entries, -1
+    after zero structures, -1 again once the option is off, -1 in a thread that never called."""
+    import math
+    from tscode_amd.graph_manipulations import bond_tables
+    from tscode_amd.synthetic import make_chain_ensemble
+    _, structures, atomnos, _ = make_chain_ensemble(3, 5, 7100)
+    classes, thr = bond_tables(atomnos)
+    eng = engine()
+    eng.set_option("pass_timing", 0)
+    eng.bond_delta(structures, classes, thr)
+    assert eng.topology_kernel_ms() == -1.0
+    run_dev(eng, structures, classes, thr, None, None, None, 0, False)
+    assert eng.topology_kernel_ms() == -1.0
+    eng.set_option("pass_timing", 1)
+    try:
+        eng.bond_delta(structures, classes, thr)
+        host_ms = eng.topology_kernel_ms()
+        assert math.isfinite(host_ms) and host_ms > 0.0
+        assert read_from_a_fresh_thread(eng.topology_kernel_ms) == -1.0
+        run_dev(eng, structures, classes, thr, None, None, None, 0, False)
+        dev_ms = eng.topology_kernel_ms()
+        assert math.isfinite(dev_ms) and dev_ms > 0.0
+        eng.bond_delta(structures[:0], classes, thr)
+        assert eng.topology_kernel_ms() == -1.0
+        eng.bond_delta(structures, classes, thr)
+        assert eng.topology_kernel_ms() > 0.0
+    finally:
+        eng.set_option("pass_timing", 0)
+    eng.bond_delta(structures, classes, thr)
+    assert eng.topology_kernel_ms() == -1.0

@@ -1,6 +1,7 @@
 // adjacent.hip -- the adjacent rows: greedy filters, csearch rotations, TFD, moments of inertia, the embed drivers
 // gfx950 only.  There is deliberately no CPU implementation behind these entry points.
 #include "host.hpp"
+#include "call.hpp"
 #include "scan.hpp"
 #include "group_filter.hpp"
 #include "csearch.hpp"
@@ -40,18 +41,15 @@ extern "C" __attribute__((visibility("default"))) int tsc_greedy_group_filter(ts
                     "group %d: sizes must be in [0, %d]", g, GF_MAX_GROUP);
     const int64_t n_poses = group_off[n_groups];
     if (n_poses == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_poses;
     int32_t *d_off;
     uint8_t *d_acc;
-    TSC_TRY(upload(c, s, poses, size_t(n_poses) * n_atoms * 3, &d_poses));
-    TSC_TRY(upload(c, s, group_off, size_t(n_groups) + 1, &d_off));
-    TSC_TRY(s.get(size_t(n_poses), &d_acc));
+    TSC_TRY(h.in(poses, size_t(n_poses) * n_atoms * 3, &d_poses));
+    TSC_TRY(h.in(group_off, size_t(n_groups) + 1, &d_off));
+    TSC_TRY(h.out(accepted, size_t(n_poses), &d_acc));
     TSC_TRY(tsc_greedy_group_filter_dev(c, d_poses, d_off, n_groups, n_poses, n_atoms, rmsd_thr, d_acc));
-    TSC_HIP(hipMemcpyAsync(accepted, d_acc, size_t(n_poses), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -93,8 +91,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_csearch_rotate_dev(tsc
     DeviceGuard guard(c->device);
     size_t lds;
     const int waves = csearch_waves(n_atoms, n_tors, &lds);
-    if (lds > 64 * 1024)
-        TSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_csearch_rotate), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+    TSC_TRY(lds_attribute(&k_csearch_rotate, lds));
     hipLaunchKernelGGL(k_csearch_rotate, dim3(grid_for(n_cand, waves, 256 * 8)), dim3(64 * waves), lds, c->stream, a, coords, torsions, masks, angles, out,
                        rotated_bonds);
     TSC_HIP(hipGetLastError());
@@ -110,22 +107,18 @@ extern "C" __attribute__((visibility("default"))) int tsc_csearch_rotate(tsc_ctx
     TSC_REQUIRE(n_atoms > 0 && n_tors >= 0 && n_cand >= 0, "bad sizes");
     TSC_TRY(check_torsions(torsions, n_tors, n_atoms));
     if (n_cand == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_coords, *d_out;
     int32_t *d_tors, *d_angles, *d_rb;
     uint8_t *d_masks;
-    TSC_TRY(upload(c, s, coords, size_t(n_atoms) * 3, &d_coords));
-    TSC_TRY(upload(c, s, torsions, size_t(n_tors) * 4, &d_tors));
-    TSC_TRY(upload(c, s, masks, size_t(n_tors) * n_atoms, &d_masks));
-    TSC_TRY(upload(c, s, angles, size_t(n_cand) * n_tors, &d_angles));
-    TSC_TRY(s.get(size_t(n_cand) * n_atoms * 3, &d_out));
-    TSC_TRY(s.get(size_t(n_cand), &d_rb));
+    TSC_TRY(h.in(coords, size_t(n_atoms) * 3, &d_coords));
+    TSC_TRY(h.in(torsions, size_t(n_tors) * 4, &d_tors));
+    TSC_TRY(h.in(masks, size_t(n_tors) * n_atoms, &d_masks));
+    TSC_TRY(h.in(angles, size_t(n_cand) * n_tors, &d_angles));
+    TSC_TRY(h.out(out, size_t(n_cand) * n_atoms * 3, &d_out));
+    TSC_TRY(h.out(rotated_bonds, size_t(n_cand), &d_rb));
     TSC_TRY(tsc_csearch_rotate_dev(c, d_coords, n_atoms, d_tors, d_masks, n_tors, d_angles, n_cand, thresh, max_clashes, d_out, d_rb));
-    TSC_HIP(hipMemcpyAsync(out, d_out, size_t(n_cand) * n_atoms * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(rotated_bonds, d_rb, size_t(n_cand) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -201,8 +194,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_csearch_rotate_multi_d
     size_t lds;
     const int waves = csearch_waves(n_atoms, widest, &lds);
     ma.t_max = t_max, ma.lists_bytes = torsion_lists_bytes(widest, n_atoms);
-    if (lds > 64 * 1024)
-        TSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_csearch_rotate_multi), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+    TSC_TRY(lds_attribute(&k_csearch_rotate_multi, lds));
     hipLaunchKernelGGL(k_csearch_rotate_multi, dim3(grid_for(n_items, 1, 256 * 8)), dim3(64 * waves), lds, c->stream, ma, starts, torsions, masks, angles,
                        cand_start, cand_row, items, out, rotated_bonds);
     TSC_HIP(hipGetLastError());
@@ -227,28 +219,24 @@ extern "C" __attribute__((visibility("default"))) int tsc_csearch_rotate_multi(t
     for (int64_t m = 0; m < n_cand; ++m) TSC_REQUIRE(cand_row[m] >= 0 && cand_row[m] < n_rows, "candidate %lld: angle row %d out of range", (long long)m, cand_row[m]);
     if (n_cand == 0) return 0;
     TSC_REQUIRE(n_rows * t_max == 0 || angles, "tsc_csearch_rotate_multi: null argument");
-    std::vector<int32_t> items(size_t(n_items) * 4);
+    std::vector<int32_t> items(size_t(n_items) * 4);   // (declared in front of the HostCall that uploads it)
     TSC_TRY(tsc_csearch_multi_plan(cand_start, n_cand, start_set, n_starts, set_off, n_sets, n_atoms, items.data(), n_items, &n_items));
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_starts, *d_out;
     int32_t *d_tors, *d_angles, *d_cs, *d_cr, *d_items, *d_rb;
     uint8_t *d_masks;
-    TSC_TRY(upload(c, s, starts, size_t(n_starts) * n_atoms * 3, &d_starts));
-    TSC_TRY(upload(c, s, torsions, size_t(n_tors) * 4, &d_tors));
-    TSC_TRY(upload(c, s, masks, size_t(n_tors) * n_atoms, &d_masks));
-    TSC_TRY(upload(c, s, angles, size_t(n_rows) * t_max, &d_angles));
-    TSC_TRY(upload(c, s, cand_start, size_t(n_cand), &d_cs));
-    TSC_TRY(upload(c, s, cand_row, size_t(n_cand), &d_cr));
-    TSC_TRY(upload(c, s, items.data(), items.size(), &d_items));
-    TSC_TRY(s.get(size_t(n_cand) * n_atoms * 3, &d_out));
-    TSC_TRY(s.get(size_t(n_cand), &d_rb));
+    TSC_TRY(h.in(starts, size_t(n_starts) * n_atoms * 3, &d_starts));
+    TSC_TRY(h.in(torsions, size_t(n_tors) * 4, &d_tors));
+    TSC_TRY(h.in(masks, size_t(n_tors) * n_atoms, &d_masks));
+    TSC_TRY(h.in(angles, size_t(n_rows) * t_max, &d_angles));
+    TSC_TRY(h.in(cand_start, size_t(n_cand), &d_cs));
+    TSC_TRY(h.in(cand_row, size_t(n_cand), &d_cr));
+    TSC_TRY(h.in(items.data(), items.size(), &d_items));
+    TSC_TRY(h.out(out, size_t(n_cand) * n_atoms * 3, &d_out));
+    TSC_TRY(h.out(rotated_bonds, size_t(n_cand), &d_rb));
     TSC_TRY(tsc_csearch_rotate_multi_dev(c, d_starts, n_atoms, d_tors, d_masks, set_off, n_sets, d_angles, t_max, d_cs, d_cr, n_cand, d_items, n_items, thresh,
                                          max_clashes, d_out, d_rb));
-    TSC_HIP(hipMemcpyAsync(out, d_out, size_t(n_cand) * n_atoms * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(rotated_bonds, d_rb, size_t(n_cand) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));   // (items, a host vector, is read by its upload until here)
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -290,20 +278,17 @@ extern "C" __attribute__((visibility("default"))) int tsc_rotate_dihedral(tsc_ct
     TSC_REQUIRE(out != coords, "tsc_rotate_dihedral: out must not alias coords");
     for (int q = 1; q <= 2; ++q) TSC_REQUIRE(torsion[q] >= 0 && torsion[q] < n_atoms, "torsion index %d out of range", torsion[q]);
     if (n_structs == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_c, *d_o, *d_a;
     uint8_t *d_m;
-    TSC_TRY(upload(c, s, coords, size_t(n_structs) * n_atoms * 3, &d_c));
-    TSC_TRY(upload(c, s, angles, size_t(n_structs), &d_a));
-    TSC_TRY(upload(c, s, mask, size_t(n_atoms), &d_m));
-    TSC_TRY(s.get(size_t(n_structs) * n_atoms * 3, &d_o));
+    TSC_TRY(h.in(coords, size_t(n_structs) * n_atoms * 3, &d_c));
+    TSC_TRY(h.in(angles, size_t(n_structs), &d_a));
+    TSC_TRY(h.in(mask, size_t(n_atoms), &d_m));
+    TSC_TRY(h.out(out, size_t(n_structs) * n_atoms * 3, &d_o));
     hipLaunchKernelGGL(k_rotate_dihedral, dim3(grid_for(n_structs * n_atoms, 256)), dim3(256), 0, c->stream, (const double *)d_c, n_structs, n_atoms, int(torsion[1]),
                        int(torsion[2]), (const uint8_t *)d_m, (const double *)d_a, d_o);
     TSC_HIP(hipGetLastError());
-    TSC_HIP(hipMemcpyAsync(out, d_o, size_t(n_structs) * n_atoms * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -316,25 +301,21 @@ extern "C" __attribute__((visibility("default"))) int tsc_torsion_comp_check(tsc
     TSC_TRY(csearch_args(n_atoms, 1, n_structs, thresh, max_clashes, &a));
     TSC_TRY(check_torsions(torsion, 1, n_atoms));
     if (n_structs == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_coords;
     int32_t *d_tors, *d_ok;
     uint8_t *d_mask;
-    TSC_TRY(upload(c, s, coords, size_t(n_structs) * n_atoms * 3, &d_coords));
-    TSC_TRY(upload(c, s, torsion, size_t(4), &d_tors));
-    TSC_TRY(upload(c, s, mask, size_t(n_atoms), &d_mask));
-    TSC_TRY(s.get(size_t(n_structs), &d_ok));
+    TSC_TRY(h.in(coords, size_t(n_structs) * n_atoms * 3, &d_coords));
+    TSC_TRY(h.in(torsion, size_t(4), &d_tors));
+    TSC_TRY(h.in(mask, size_t(n_atoms), &d_mask));
+    TSC_TRY(h.out(ok, size_t(n_structs), &d_ok));
     size_t lds;
     const int waves = csearch_waves(n_atoms, 1, &lds);
-    if (lds > 64 * 1024)
-        TSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_torsion_comp_check), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+    TSC_TRY(lds_attribute(&k_torsion_comp_check, lds));
     hipLaunchKernelGGL(k_torsion_comp_check, dim3(grid_for(n_structs, waves, 256 * 8)), dim3(64 * waves), lds, c->stream, a, (const double *)d_coords,
                        (const int32_t *)d_tors, (const uint8_t *)d_mask, d_ok);
     TSC_HIP(hipGetLastError());
-    TSC_HIP(hipMemcpyAsync(ok, d_ok, size_t(n_structs) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -348,20 +329,17 @@ extern "C" __attribute__((visibility("default"))) int tsc_torsion_fingerprints(t
     TSC_REQUIRE(n_structs >= 0 && n_atoms > 0 && n_quads >= 0, "bad sizes");
     for (int q = 0; q < 4 * n_quads; ++q) TSC_REQUIRE(quads[q] >= 0 && quads[q] < n_atoms, "quadruplet atom index %d out of range", quads[q]);
     if (n_structs == 0 || n_quads == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_coords;
     int32_t *d_quads;
     float *d_out;
-    TSC_TRY(upload(c, s, coords, size_t(n_structs) * n_atoms * 3, &d_coords));
-    TSC_TRY(upload(c, s, quads, size_t(n_quads) * 4, &d_quads));
-    TSC_TRY(s.get(size_t(n_structs) * n_quads, &d_out));
+    TSC_TRY(h.in(coords, size_t(n_structs) * n_atoms * 3, &d_coords));
+    TSC_TRY(h.in(quads, size_t(n_quads) * 4, &d_quads));
+    TSC_TRY(h.out(out, size_t(n_structs) * n_quads, &d_out));
     hipLaunchKernelGGL(k_torsion_fingerprints, dim3(grid_for(n_structs * n_quads, 256, 256 * 8)), dim3(256), 0, c->stream, (const double *)d_coords,
                        n_structs, n_atoms, (const int32_t *)d_quads, n_quads, d_out);
     TSC_HIP(hipGetLastError());
-    TSC_HIP(hipMemcpyAsync(out, d_out, size_t(n_structs) * n_quads * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -374,18 +352,15 @@ extern "C" __attribute__((visibility("default"))) int tsc_tfd_first_similar(tsc_
                 "bad pass geometry (n = %lld, d = %lld, k = %lld, active = %lld)", (long long)n_structs, (long long)d, (long long)k, (long long)num_active);
     TSC_REQUIRE(n_structs < INT32_MAX, "too many structures");
     if (n_structs == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     float *d_tf;
     int32_t *d_first;
-    TSC_TRY(upload(c, s, tf, size_t(n_structs) * n_quads, &d_tf));
-    TSC_TRY(s.get(size_t(n_structs), &d_first));
+    TSC_TRY(h.in(tf, size_t(n_structs) * n_quads, &d_tf));
+    TSC_TRY(h.out(first, size_t(n_structs), &d_first));
     hipLaunchKernelGGL(k_tfd_first_similar, dim3(grid_for(n_structs, 4, 256 * 16)), dim3(256), 0, c->stream, (const float *)d_tf, n_structs, n_quads, d, k,
                        num_active, thresh, d_first);
     TSC_HIP(hipGetLastError());
-    TSC_HIP(hipMemcpyAsync(first, d_first, size_t(n_structs) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -419,18 +394,15 @@ extern "C" __attribute__((visibility("default"))) int tsc_inertia_moments(tsc_ct
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(c && structures && masses && out && n_structs >= 0 && n_atoms > 0, "tsc_inertia_moments: bad argument");
     if (n_structs == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_s, *d_m, *d_o;
-    TSC_TRY(upload(c, s, structures, size_t(n_structs) * n_atoms * 3, &d_s));
-    TSC_TRY(upload(c, s, masses, size_t(n_atoms), &d_m));
-    TSC_TRY(s.get(size_t(n_structs) * 3, &d_o));
+    TSC_TRY(h.in(structures, size_t(n_structs) * n_atoms * 3, &d_s));
+    TSC_TRY(h.in(masses, size_t(n_atoms), &d_m));
+    TSC_TRY(h.out(out, size_t(n_structs) * 3, &d_o));
     hipLaunchKernelGGL(k_inertia_moments, dim3(grid_for(n_structs, 256, 256 * 8)), dim3(256), 0, c->stream, (const double *)d_s, n_structs, n_atoms,
                        (const double *)d_m, d_o);
     TSC_HIP(hipGetLastError());
-    TSC_HIP(hipMemcpyAsync(out, d_o, size_t(n_structs) * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -439,17 +411,14 @@ extern "C" __attribute__((visibility("default"))) int tsc_moi_first_similar(tsc_
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(c && moments && first && n_structs >= 0 && n_structs < INT32_MAX, "tsc_moi_first_similar: bad argument");
     if (n_structs == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_m;
     int32_t *d_f;
-    TSC_TRY(upload(c, s, moments, size_t(n_structs) * 3, &d_m));
-    TSC_TRY(s.get(size_t(n_structs), &d_f));
+    TSC_TRY(h.in(moments, size_t(n_structs) * 3, &d_m));
+    TSC_TRY(h.out(first, size_t(n_structs), &d_f));
     hipLaunchKernelGGL(k_moi_first_similar, dim3(grid_for(n_structs, 4, 256 * 16)), dim3(256), 0, c->stream, (const double *)d_m, n_structs, max_deviation, d_f);
     TSC_HIP(hipGetLastError());
-    TSC_HIP(hipMemcpyAsync(first, d_f, size_t(n_structs) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -460,23 +429,19 @@ extern "C" __attribute__((visibility("default"))) int tsc_embed_scores(tsc_ctx *
     TSC_REQUIRE(c && structures && indices && distances && scores && fitness_error && n_structs >= 0 && n_atoms > 0 && n_c >= 0, "tsc_embed_scores: bad argument");
     for (int64_t q = 0; q < n_structs * n_c * 2; ++q) TSC_REQUIRE(indices[q] >= 0 && indices[q] < n_atoms, "constrained index %d out of range", indices[q]);
     if (n_structs == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_s, *d_d, *d_e;
     int32_t *d_i;
     float *d_sc;
-    TSC_TRY(upload(c, s, structures, size_t(n_structs) * n_atoms * 3, &d_s));
-    TSC_TRY(upload(c, s, indices, size_t(n_structs) * n_c * 2, &d_i));
-    TSC_TRY(upload(c, s, distances, size_t(n_structs) * n_c, &d_d));
-    TSC_TRY(s.get(size_t(n_structs), &d_sc));
-    TSC_TRY(s.get(size_t(n_structs), &d_e));
+    TSC_TRY(h.in(structures, size_t(n_structs) * n_atoms * 3, &d_s));
+    TSC_TRY(h.in(indices, size_t(n_structs) * n_c * 2, &d_i));
+    TSC_TRY(h.in(distances, size_t(n_structs) * n_c, &d_d));
+    TSC_TRY(h.out(scores, size_t(n_structs), &d_sc));
+    TSC_TRY(h.out(fitness_error, size_t(n_structs), &d_e));
     hipLaunchKernelGGL(k_embed_scores, dim3(grid_for(n_structs, 256, 256 * 8)), dim3(256), 0, c->stream, (const double *)d_s, n_structs, n_atoms,
                        (const int32_t *)d_i, (const double *)d_d, n_c, d_sc, d_e);
     TSC_HIP(hipGetLastError());
-    TSC_HIP(hipMemcpyAsync(scores, d_sc, size_t(n_structs) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(fitness_error, d_e, size_t(n_structs) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -507,26 +472,21 @@ extern "C" __attribute__((visibility("default"))) int tsc_string_embed_params(ts
     TSC_REQUIRE(c && p1 && p2 && ref_vec && mol_vec && conf_pair && angles && rot && pos && conf_idx, "tsc_string_embed_params: null argument");
     TSC_REQUIRE(n_sites >= 0 && n_angles >= 0, "bad sizes");
     if (n_sites == 0 || n_angles == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_p1, *d_p2, *d_rv, *d_mv, *d_ang, *d_rot, *d_pos;
     int32_t *d_cp, *d_ci;
     const size_t N = size_t(n_sites) * n_angles;
-    TSC_TRY(upload(c, s, p1, size_t(n_sites) * 3, &d_p1));
-    TSC_TRY(upload(c, s, p2, size_t(n_sites) * 3, &d_p2));
-    TSC_TRY(upload(c, s, ref_vec, size_t(n_sites) * 3, &d_rv));
-    TSC_TRY(upload(c, s, mol_vec, size_t(n_sites) * 3, &d_mv));
-    TSC_TRY(upload(c, s, conf_pair, size_t(n_sites) * 2, &d_cp));
-    TSC_TRY(upload(c, s, angles, size_t(n_angles), &d_ang));
-    TSC_TRY(s.get(N * 18, &d_rot));
-    TSC_TRY(s.get(N * 6, &d_pos));
-    TSC_TRY(s.get(N * 2, &d_ci));
+    TSC_TRY(h.in(p1, size_t(n_sites) * 3, &d_p1));
+    TSC_TRY(h.in(p2, size_t(n_sites) * 3, &d_p2));
+    TSC_TRY(h.in(ref_vec, size_t(n_sites) * 3, &d_rv));
+    TSC_TRY(h.in(mol_vec, size_t(n_sites) * 3, &d_mv));
+    TSC_TRY(h.in(conf_pair, size_t(n_sites) * 2, &d_cp));
+    TSC_TRY(h.in(angles, size_t(n_angles), &d_ang));
+    TSC_TRY(h.out(rot, N * 18, &d_rot));
+    TSC_TRY(h.out(pos, N * 6, &d_pos));
+    TSC_TRY(h.out(conf_idx, N * 2, &d_ci));
     TSC_TRY(tsc_string_embed_params_dev(c, d_p1, d_p2, d_rv, d_mv, d_cp, n_sites, d_ang, n_angles, d_rot, d_pos, d_ci));
-    TSC_HIP(hipMemcpyAsync(rot, d_rot, N * 18 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(pos, d_pos, N * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(conf_idx, d_ci, N * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -539,24 +499,20 @@ extern "C" __attribute__((visibility("default"))) int tsc_cyclical_embed_params(
     TSC_REQUIRE(n >= 0, "bad size");
     for (int64_t q = 0; q < n; ++q) TSC_REQUIRE(n_reactive[q] == 1 || n_reactive[q] == 2, "row %lld: n_reactive must be 1 or 2", (long long)q);
     if (n == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     const double *host[7] = {start, end, direction, pivot, meanpoint, r0, r1};
     double *dev[7], *d_angle, *d_rot, *d_pos;
     int32_t *d_nr;
-    for (int i = 0; i < 7; ++i) TSC_TRY(upload(c, s, host[i], size_t(n) * 3, &dev[i]));
-    TSC_TRY(upload(c, s, n_reactive, size_t(n), &d_nr));
-    TSC_TRY(upload(c, s, angle, size_t(n), &d_angle));
-    TSC_TRY(s.get(size_t(n) * 9, &d_rot));
-    TSC_TRY(s.get(size_t(n) * 3, &d_pos));
+    for (int i = 0; i < 7; ++i) TSC_TRY(h.in(host[i], size_t(n) * 3, &dev[i]));
+    TSC_TRY(h.in(n_reactive, size_t(n), &d_nr));
+    TSC_TRY(h.in(angle, size_t(n), &d_angle));
+    TSC_TRY(h.out(rot, size_t(n) * 9, &d_rot));
+    TSC_TRY(h.out(pos, size_t(n) * 3, &d_pos));
     hipLaunchKernelGGL(k_cyclical_embed_params, dim3(grid_for(n, 256, 256 * 8)), dim3(256), 0, c->stream, (const double *)dev[0], (const double *)dev[1],
                        (const double *)dev[2], (const double *)dev[3], (const double *)dev[4], (const double *)dev[5], (const double *)dev[6],
                        (const int32_t *)d_nr, (const double *)d_angle, n, d_rot, d_pos);
     TSC_HIP(hipGetLastError());
-    TSC_HIP(hipMemcpyAsync(rot, d_rot, size_t(n) * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(pos, d_pos, size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -603,19 +559,18 @@ extern "C" __attribute__((visibility("default"))) int tsc_tfd_greedy_filter(tsc_
     TSC_REQUIRE(n_structs >= 0 && n_structs < INT32_MAX && n_quads >= 0, "bad sizes");
     if (n_kept) *n_kept = 0;
     if (n_structs == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    int32_t nk = 0;
+    HostCall h(c);
     float *d_tf;
     uint8_t *d_acc;
     int32_t *d_list, *d_nk;
-    TSC_TRY(upload(c, s, tf, std::max<size_t>(size_t(n_structs) * n_quads, 1), &d_tf));
-    TSC_TRY(s.get(size_t(n_structs), &d_acc));
-    TSC_TRY(s.get(size_t(n_structs), &d_list));
-    TSC_TRY(s.get(1, &d_nk));
-    TSC_TRY(launch_tfd_greedy(c, s, d_tf, n_structs, n_quads, thresh, d_acc, d_list, d_nk));
-    TSC_HIP(hipMemcpyAsync(accepted, d_acc, size_t(n_structs), hipMemcpyDeviceToHost, c->stream));
-    int32_t nk = 0;
-    TSC_TRY(read_i32(c, d_nk, &nk));
+    TSC_TRY(h.in(tf, std::max<size_t>(size_t(n_structs) * n_quads, 1), &d_tf));
+    TSC_TRY(h.out(accepted, size_t(n_structs), &d_acc));
+    TSC_TRY(h.scratch().get(size_t(n_structs), &d_list));
+    TSC_TRY(h.scratch().get(1, &d_nk));
+    TSC_TRY(launch_tfd_greedy(c, h.scratch(), d_tf, n_structs, n_quads, thresh, d_acc, d_list, d_nk));
+    TSC_TRY(h.fetch(&nk, d_nk, 1));
+    TSC_TRY(h.finish());
     if (n_kept) *n_kept = nk;
     return 0;
     TSC_API_GUARD_END
@@ -625,22 +580,17 @@ extern "C" __attribute__((visibility("default"))) int tsc_tfd_greedy_filter(tsc_
 // embedded in candidate order, a filter over them (`filter(d_structs, n_pass, d_pos_scan, d_acc)`), the kept poses compacted
 // and copied out, both verdicts per candidate.
 template <typename Filter>
-static int embed_filter_run(tsc_ctx *c, Scratch &s, const double *d_frags, const FragTable &ft, const int64_t *frag_off, const int32_t *n_atoms,
+static int embed_filter_run(tsc_ctx *c, HostCall &h, const double *d_frags, const FragTable &ft, const int64_t *frag_off, const int32_t *n_atoms,
                             const int32_t *n_conf, const int32_t *d_ci, const double *d_rot, const double *d_pos, int64_t N, double clash_thresh,
                             int64_t max_clashes, uint8_t *clash_ok, uint8_t *kept, double *poses, int64_t poses_capacity, int64_t *n_pass_out,
                             int64_t *n_kept_out, Filter filter) {
     hipStream_t st = c->stream;
+    Scratch &s = h.scratch();
     const int n = ft.n_total;
-    // copies into the CALLER's host arrays are enqueued long before this function returns: whatever path leaves it -- an error
-    // included -- the stream is idle first, so that no copy lands in memory the caller has meanwhile freed
-    struct SyncOnExit {
-        hipStream_t st;
-        ~SyncOnExit() { (void)hipStreamSynchronize(st); }
-    } sync_on_exit{st};
     uint8_t *d_mask, *d_kept_full, *d_acc;
     int32_t *bsum, *act, *pos_scan, *total, *act2, *total2;
     TSC_TRY(s.get(size_t(N), &d_mask));
-    TSC_TRY(s.get(size_t(N), &d_kept_full));
+    TSC_TRY(h.out(kept, size_t(N), &d_kept_full));
     TSC_TRY(s.get(scan_bsum_count(N), &bsum));
     TSC_TRY(s.get(size_t(N), &act));
     TSC_TRY(s.get(size_t(N) + 1, &pos_scan));
@@ -649,7 +599,7 @@ static int embed_filter_run(tsc_ctx *c, Scratch &s, const double *d_frags, const
     TSC_TRY(s.get(1, &total2));
     TSC_TRY(tsc_embed_clash_mask_dev(c, d_frags, frag_off, n_atoms, n_conf, ft.n_mols, d_ci, d_rot, d_pos, N, clash_thresh, max_clashes, d_mask, nullptr));
     TSC_TRY(scan_mask(st, d_mask, N, bsum, pos_scan, act, nullptr, total));
-    TSC_HIP(hipMemcpyAsync(clash_ok, d_mask, size_t(N), hipMemcpyDeviceToHost, st));
+    TSC_TRY(h.fetch(clash_ok, d_mask, size_t(N)));   // (here, in front of the first wait)
     TSC_HIP(hipMemsetAsync(d_kept_full, 0, size_t(N), st));
     int32_t n_pass = 0, n_kept = 0;
     TSC_TRY(read_i32(c, total, &n_pass));
@@ -670,11 +620,10 @@ static int embed_filter_run(tsc_ctx *c, Scratch &s, const double *d_frags, const
             TSC_REQUIRE(n_kept <= poses_capacity, "poses holds %lld rows, %d poses were kept", (long long)poses_capacity, n_kept);
             TSC_TRY(s.get(size_t(n_kept) * n * 3, &d_out));
             TSC_TRY(launch_gather_rows(st, d_structs, act2, n_kept, n * 3, nullptr, n * 3, d_out));
-            TSC_HIP(hipMemcpyAsync(poses, d_out, size_t(n_kept) * n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+            TSC_TRY(h.fetch(poses, d_out, size_t(n_kept) * n * 3));
         }
     }
-    TSC_HIP(hipMemcpyAsync(kept, d_kept_full, size_t(N), hipMemcpyDeviceToHost, st));
-    TSC_HIP(hipStreamSynchronize(st));
+    TSC_TRY(h.finish());
     *n_kept_out = n_kept;
     return 0;
 }
@@ -699,18 +648,18 @@ extern "C" __attribute__((visibility("default"))) int tsc_string_embed(tsc_ctx *
         TSC_REQUIRE(conf_pair[2 * q] >= 0 && conf_pair[2 * q] < n_conf[0] && conf_pair[2 * q + 1] >= 0 && conf_pair[2 * q + 1] < n_conf[1],
                     "site %lld: conformer index out of range", (long long)q);
     for (int q = 0; q < 4 * n_quads; ++q) TSC_REQUIRE(quads[q] >= 0 && quads[q] < ft.n_total, "quadruplet atom index %d out of range", quads[q]);
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
+    Scratch &s = h.scratch();
     double *d_frags, *d_p1, *d_p2, *d_rv, *d_mv, *d_ang, *d_rot, *d_pos;
     int32_t *d_cp, *d_ci, *d_quads = nullptr;
-    TSC_TRY(upload(c, s, frags, size_t(frags_total_doubles(frag_off, n_atoms, n_conf, 2)), &d_frags));
-    TSC_TRY(upload(c, s, p1, size_t(n_sites) * 3, &d_p1));
-    TSC_TRY(upload(c, s, p2, size_t(n_sites) * 3, &d_p2));
-    TSC_TRY(upload(c, s, ref_vec, size_t(n_sites) * 3, &d_rv));
-    TSC_TRY(upload(c, s, mol_vec, size_t(n_sites) * 3, &d_mv));
-    TSC_TRY(upload(c, s, conf_pair, size_t(n_sites) * 2, &d_cp));
-    TSC_TRY(upload(c, s, angles, size_t(n_angles), &d_ang));
-    if (n_quads) TSC_TRY(upload(c, s, quads, size_t(n_quads) * 4, &d_quads));
+    TSC_TRY(h.in(frags, size_t(frags_total_doubles(frag_off, n_atoms, n_conf, 2)), &d_frags));
+    TSC_TRY(h.in(p1, size_t(n_sites) * 3, &d_p1));
+    TSC_TRY(h.in(p2, size_t(n_sites) * 3, &d_p2));
+    TSC_TRY(h.in(ref_vec, size_t(n_sites) * 3, &d_rv));
+    TSC_TRY(h.in(mol_vec, size_t(n_sites) * 3, &d_mv));
+    TSC_TRY(h.in(conf_pair, size_t(n_sites) * 2, &d_cp));
+    TSC_TRY(h.in(angles, size_t(n_angles), &d_ang));
+    if (n_quads) TSC_TRY(h.in(quads, size_t(n_quads) * 4, &d_quads));
     TSC_TRY(s.get(size_t(N) * 18, &d_rot));
     TSC_TRY(s.get(size_t(N) * 6, &d_pos));
     TSC_TRY(s.get(size_t(N) * 2, &d_ci));
@@ -729,7 +678,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_string_embed(tsc_ctx *
         TSC_HIP(hipGetLastError());
         return launch_tfd_greedy(c, s, d_tf, int64_t(np), n_quads, tfd_thresh, d_acc, d_list, d_nk);
     };
-    return embed_filter_run(c, s, d_frags, ft, frag_off, n_atoms, n_conf, d_ci, d_rot, d_pos, N, clash_thresh, max_clashes, clash_ok, kept, poses, poses_capacity,
+    return embed_filter_run(c, h, d_frags, ft, frag_off, n_atoms, n_conf, d_ci, d_rot, d_pos, N, clash_thresh, max_clashes, clash_ok, kept, poses, poses_capacity,
                             n_pass, n_kept, filter);
     TSC_API_GUARD_END
 }
@@ -758,17 +707,17 @@ extern "C" __attribute__((visibility("default"))) int tsc_cyclical_embed(tsc_ctx
     TSC_REQUIRE(n_groups > 0 && group_off[0] == 0 && group_off[n_groups] == n_poses, "group_off must run from 0 to n_poses");
     for (int g = 0; g < n_groups; ++g)
         TSC_REQUIRE(group_off[g + 1] >= group_off[g] && group_off[g + 1] - group_off[g] <= GF_MAX_GROUP, "group %d: sizes must be in [0, %d]", g, GF_MAX_GROUP);
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
+    Scratch &s = h.scratch();
     const double *host[7] = {start, end, direction, pivot, meanpoint, r0, r1};
     double *d_frags, *dev[7], *d_angle, *d_rot, *d_pos;
     int32_t *d_nr, *d_ci, *d_goff, *d_goff_pass;
-    TSC_TRY(upload(c, s, frags, size_t(frags_total_doubles(frag_off, n_atoms, n_conf, n_mols)), &d_frags));
-    for (int i = 0; i < 7; ++i) TSC_TRY(upload(c, s, host[i], size_t(rows) * 3, &dev[i]));
-    TSC_TRY(upload(c, s, n_reactive, size_t(rows), &d_nr));
-    TSC_TRY(upload(c, s, angle, size_t(rows), &d_angle));
-    TSC_TRY(upload(c, s, conf_idx, size_t(rows), &d_ci));
-    TSC_TRY(upload(c, s, group_off, size_t(n_groups) + 1, &d_goff));
+    TSC_TRY(h.in(frags, size_t(frags_total_doubles(frag_off, n_atoms, n_conf, n_mols)), &d_frags));
+    for (int i = 0; i < 7; ++i) TSC_TRY(h.in(host[i], size_t(rows) * 3, &dev[i]));
+    TSC_TRY(h.in(n_reactive, size_t(rows), &d_nr));
+    TSC_TRY(h.in(angle, size_t(rows), &d_angle));
+    TSC_TRY(h.in(conf_idx, size_t(rows), &d_ci));
+    TSC_TRY(h.in(group_off, size_t(n_groups) + 1, &d_goff));
     TSC_TRY(s.get(size_t(n_groups) + 1, &d_goff_pass));
     TSC_TRY(s.get(size_t(rows) * 9, &d_rot));
     TSC_TRY(s.get(size_t(rows) * 3, &d_pos));
@@ -784,7 +733,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_cyclical_embed(tsc_ctx
         TSC_HIP(hipGetLastError());
         return tsc_greedy_group_filter_dev(c, d_structs, d_goff_pass, n_groups, np, n, rmsd_thr, d_acc);
     };
-    return embed_filter_run(c, s, d_frags, ft, frag_off, n_atoms, n_conf, d_ci, d_rot, d_pos, n_poses, clash_thresh, max_clashes, clash_ok, kept, poses,
+    return embed_filter_run(c, h, d_frags, ft, frag_off, n_atoms, n_conf, d_ci, d_rot, d_pos, n_poses, clash_thresh, max_clashes, clash_ok, kept, poses,
                             poses_capacity, n_pass, n_kept, filter);
     TSC_API_GUARD_END
 }

@@ -2,6 +2,7 @@
 // tscode/hypermolecule_class.py:38-72, tscode/torsion_module.py:849-924).  gfx950 only.  There is deliberately no CPU implementation
 // behind these entry points.
 #include "host.hpp"
+#include "call.hpp"
 #include "diverse.hpp"
 
 #include <algorithm>
@@ -14,29 +15,6 @@ using namespace tsc;
 // stage times of the calling thread's latest call (every entry resets them), taken only under the context option "pass_timing" >= 1 (tools/diverse_profile.py):
 // align, the first k_kmeans_assign launch, the first k_kmeans_update launch, the whole device part of the call
 thread_local float g_times[4] = {-1.f, -1.f, -1.f, -1.f};
-
-struct StageTimer {
-    tsc_ctx *c;
-    bool on;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    explicit StageTimer(tsc_ctx *ctx) : c(ctx), on(ctx->pass_timing >= 1) {
-        if (on && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)) on = false;
-    }
-    ~StageTimer() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void begin() {
-        if (on) (void)hipEventRecord(ev[0], c->stream);
-    }
-    void end(int slot) {   // (synchronises: a timed call is a measurement, not the product's path)
-        if (!on) return;
-        (void)hipEventRecord(ev[1], c->stream);
-        (void)hipEventSynchronize(ev[1]);
-        float ms = -1.f;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) g_times[slot] = ms;
-    }
-};
 
 void reset_times() {
     for (float &t : g_times) t = -1.f;
@@ -66,11 +44,11 @@ int check_k(const char *who, int64_t N, int64_t D, int k) {
     return 0;
 }
 
-int align_dev(tsc_ctx *c, Scratch &s, const double *d_in, int64_t N, int n, const int32_t *idx_host, int n_idx, double *d_out) {
+int align_dev(tsc_ctx *c, HostCall &h, const double *d_in, int64_t N, int n, const int32_t *idx_host, int n_idx, double *d_out) {
     int32_t *d_idx = nullptr;
     if (idx_host && n_idx > 0) {
         for (int q = 0; q < n_idx; ++q) TSC_REQUIRE(idx_host[q] >= 0 && idx_host[q] < n, "align_structures: index %d out of range", idx_host[q]);
-        TSC_TRY(upload(c, s, idx_host, size_t(n_idx), &d_idx));
+        TSC_TRY(h.in(idx_host, size_t(n_idx), &d_idx));
     } else {
         n_idx = n;   // hypermolecule_class.py:51
     }
@@ -109,13 +87,6 @@ int centre_features(tsc_ctx *c, Scratch &s, double *X, int64_t N, int D, double 
     return 0;
 }
 
-template <int NT>
-void launch_assign(tsc_ctx *c, const double *X, int64_t N, int D, const double *C, int k, const double *xn, const double *cn, int32_t *labels,
-                   double *own_d2, int *changed) {
-    hipLaunchKernelGGL(k_kmeans_assign<NT>, dim3(unsigned(ceil_div<int64_t>(N, KA_ROWS))), dim3(256), 0, c->stream, X, N, D, C, k, xn, cn, labels, own_d2,
-                       changed);
-}
-
 struct Lloyd {   // device state of one clustering; every block belongs to the caller's Scratch
     double *X = nullptr, *C = nullptr, *xn = nullptr, *cn = nullptr, *own_d2 = nullptr, *shift_part = nullptr;
     int32_t *labels = nullptr, *counts = nullptr, *offs = nullptr, *members = nullptr;
@@ -146,17 +117,11 @@ int assign(tsc_ctx *c, Lloyd &L, StageTimer *tm = nullptr) {
     hipLaunchKernelGGL(k_row_norms, dim3(ceil_div(L.k, 4)), dim3(256), 0, c->stream, L.C, int64_t(L.k), L.D, L.cn);
     TSC_HIP(hipMemsetAsync(L.changed, 0, sizeof(int), c->stream));
     if (tm) tm->begin();   // (the k_kmeans_assign launch alone)
-    switch (nt) {
-        case 1: launch_assign<1>(c, L.X, L.N, L.D, L.C, L.k, L.xn, L.cn, L.labels, L.own_d2, L.changed); break;
-        case 2: launch_assign<2>(c, L.X, L.N, L.D, L.C, L.k, L.xn, L.cn, L.labels, L.own_d2, L.changed); break;
-        case 3: launch_assign<3>(c, L.X, L.N, L.D, L.C, L.k, L.xn, L.cn, L.labels, L.own_d2, L.changed); break;
-        case 4: launch_assign<4>(c, L.X, L.N, L.D, L.C, L.k, L.xn, L.cn, L.labels, L.own_d2, L.changed); break;
-        case 5: launch_assign<5>(c, L.X, L.N, L.D, L.C, L.k, L.xn, L.cn, L.labels, L.own_d2, L.changed); break;
-        case 6: launch_assign<6>(c, L.X, L.N, L.D, L.C, L.k, L.xn, L.cn, L.labels, L.own_d2, L.changed); break;
-        case 7: launch_assign<7>(c, L.X, L.N, L.D, L.C, L.k, L.xn, L.cn, L.labels, L.own_d2, L.changed); break;
-        default: launch_assign<8>(c, L.X, L.N, L.D, L.C, L.k, L.xn, L.cn, L.labels, L.own_d2, L.changed); break;
-    }
-    if (tm) tm->end(1);
+    with_width(nt, [&](auto w) {
+        hipLaunchKernelGGL(k_kmeans_assign<decltype(w)::value>, dim3(unsigned(ceil_div<int64_t>(L.N, KA_ROWS))), dim3(256), 0, c->stream, L.X, L.N, L.D,
+                           L.C, L.k, L.xn, L.cn, L.labels, L.own_d2, L.changed);
+    });
+    if (tm) tm->end(&g_times[1]);
     TSC_HIP(hipGetLastError());
     return 0;
 }
@@ -186,7 +151,7 @@ int lloyd_run(tsc_ctx *c, Lloyd &L, int max_iter, double tol_abs, int *n_iter, i
         if (timed) tm->begin();
         hipLaunchKernelGGL(k_kmeans_update, dim3(L.k, L.slices), dim3(256), 0, c->stream, L.X, L.D, L.members, L.offs, L.counts, L.ctl, L.C,
                            L.shift_part);
-        if (timed) tm->end(2);
+        if (timed) tm->end(&g_times[2]);
         hipLaunchKernelGGL(k_kmeans_control, dim3(1), dim3(64), 0, c->stream, L.shift_part, L.k * L.slices, L.changed, L.ctl);
         TSC_HIP(hipGetLastError());
         struct {
@@ -217,10 +182,10 @@ int lloyd_run(tsc_ctx *c, Lloyd &L, int max_iter, double tol_abs, int *n_iter, i
 }
 
 // k-means++ without local trials on X[N, D]: d_rows[k] on the device (tsc_kmeans_seed in the header); u_host checked by the caller
-int seed_dev(tsc_ctx *c, Scratch &s, const double *X, int64_t N, int D, int k, const double *u_host, int32_t *d_rows) {
+int seed_dev(tsc_ctx *c, HostCall &h, const double *X, int64_t N, int D, int k, const double *u_host, int32_t *d_rows) {
     double *d_u, *min_d2;
-    TSC_TRY(upload(c, s, u_host, size_t(k), &d_u));
-    TSC_TRY(s.get(size_t(N), &min_d2));
+    TSC_TRY(h.in(u_host, size_t(k), &d_u));
+    TSC_TRY(h.scratch().get(size_t(N), &min_d2));
     const int32_t first = int32_t(std::min<int64_t>(N - 1, int64_t(u_host[0] * double(N))));
     TSC_HIP(hipMemcpyAsync(d_rows, &first, sizeof(first), hipMemcpyHostToDevice, c->stream));
     for (int j = 1; j < k; ++j) {
@@ -257,19 +222,16 @@ extern "C" __attribute__((visibility("default"))) int tsc_align_structures(tsc_c
     TSC_REQUIRE(n_idx <= n_atoms, "tsc_align_structures: %d indices for %d atoms", n_idx, n_atoms);
     TSC_TRY(check_finite("tsc_align_structures", "structures", structures, size_t(n_structs) * n_atoms * 3));
     reset_times();
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     const size_t count = size_t(n_structs) * n_atoms * 3;
     double *d_in, *d_out;
-    TSC_TRY(upload(c, s, structures, count, &d_in));
-    TSC_TRY(s.get(count, &d_out));
+    TSC_TRY(h.in(structures, count, &d_in));
+    TSC_TRY(h.out(out, count, &d_out));
     StageTimer tm(c);
     tm.begin();
-    TSC_TRY(align_dev(c, s, d_in, n_structs, n_atoms, indices, n_idx, d_out));
-    tm.end(0);
-    TSC_HIP(hipMemcpyAsync(out, d_out, count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    TSC_TRY(align_dev(c, h, d_in, n_structs, n_atoms, indices, n_idx, d_out));
+    tm.end(&g_times[0]);
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -283,10 +245,10 @@ extern "C" __attribute__((visibility("default"))) int tsc_kmeans_lloyd(tsc_ctx *
     TSC_TRY(check_finite("tsc_kmeans_lloyd", "X", X, size_t(N) * D));
     TSC_TRY(check_finite("tsc_kmeans_lloyd", "init", init, size_t(k) * D));
     reset_times();
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
+    Scratch &s = h.scratch();
     double *d_X, *d_mean, *d_in;
-    TSC_TRY(upload(c, s, X, size_t(N) * D, &d_X));
+    TSC_TRY(h.in(X, size_t(N) * D, &d_X));
     TSC_TRY(s.get(size_t(D), &d_mean));
     double tol_abs = 0.0;
     TSC_TRY(centre_features(c, s, d_X, N, int(D), d_mean, tol, &tol_abs));
@@ -302,11 +264,10 @@ extern "C" __attribute__((visibility("default"))) int tsc_kmeans_lloyd(tsc_ctx *
     hipLaunchKernelGGL(k_sum_fixed, dim3(1), dim3(1024), 0, c->stream, L.own_d2, N, 1.0, d_in);
     hipLaunchKernelGGL(k_shift_cols, dim3(grid_for(int64_t(k) * D, 256)), dim3(256), 0, c->stream, L.C, int64_t(k), int(D), d_mean, 1.0);
     TSC_HIP(hipGetLastError());
-    TSC_HIP(hipMemcpyAsync(labels, L.labels, size_t(N) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(centers, L.C, size_t(k) * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(inertia, d_in, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    TSC_TRY(h.fetch(labels, L.labels, size_t(N)));
+    TSC_TRY(h.fetch(centers, L.C, size_t(k) * D));
+    TSC_TRY(h.fetch(inertia, d_in, 1));
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -318,16 +279,13 @@ extern "C" __attribute__((visibility("default"))) int tsc_kmeans_seed(tsc_ctx *c
     TSC_TRY(check_uniforms("tsc_kmeans_seed", u, k));
     TSC_TRY(check_finite("tsc_kmeans_seed", "X", X, size_t(N) * D));
     reset_times();
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_X;
     int32_t *d_rows;
-    TSC_TRY(upload(c, s, X, size_t(N) * D, &d_X));
-    TSC_TRY(s.get(size_t(k), &d_rows));
-    TSC_TRY(seed_dev(c, s, d_X, N, int(D), k, u, d_rows));
-    TSC_HIP(hipMemcpyAsync(rows, d_rows, size_t(k) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    TSC_TRY(h.in(X, size_t(N) * D, &d_X));
+    TSC_TRY(h.out(rows, size_t(k), &d_rows));
+    TSC_TRY(seed_dev(c, h, d_X, N, int(D), k, u, d_rows));
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -343,26 +301,24 @@ extern "C" __attribute__((visibility("default"))) int tsc_diverse_pick(tsc_ctx *
     if (energies)
         for (int64_t i = 0; i < N; ++i) TSC_REQUIRE(!std::isnan(energies[i]), "tsc_diverse_pick: energies[%lld] is NaN", (long long)i);
     reset_times();
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
+    Scratch &s = h.scratch();
     const int D = 3 * n_atoms;
     double *d_X, *d_C, *d_e = nullptr;
     int32_t *d_picked;
-    TSC_TRY(upload(c, s, aligned, size_t(N) * D, &d_X));
-    TSC_TRY(upload(c, s, centers, size_t(k) * D, &d_C));
-    if (energies) TSC_TRY(upload(c, s, energies, size_t(N), &d_e));
+    TSC_TRY(h.in(aligned, size_t(N) * D, &d_X));
+    TSC_TRY(h.in(centers, size_t(k) * D, &d_C));
+    if (energies) TSC_TRY(h.in(energies, size_t(N), &d_e));
     Lloyd L;
     L.N = N, L.D = D, L.k = k;
-    TSC_TRY(upload(c, s, labels, size_t(N), &L.labels));
+    TSC_TRY(h.in(labels, size_t(N), &L.labels));
     TSC_TRY(s.get(size_t(k), &L.counts));
     TSC_TRY(s.get(size_t(k) + 1, &L.offs));
     TSC_TRY(s.get(size_t(N), &L.members));
-    TSC_TRY(s.get(size_t(k), &d_picked));
+    TSC_TRY(h.out(picked, size_t(k), &d_picked));
     TSC_TRY(bucket(c, L));
     TSC_TRY(pick_dev(c, L, d_X, d_C, d_e, d_picked));
-    TSC_HIP(hipMemcpyAsync(picked, d_picked, size_t(k) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -384,28 +340,28 @@ extern "C" __attribute__((visibility("default"))) int tsc_diverse_select(tsc_ctx
     if (energies)
         for (int64_t i = 0; i < N; ++i) TSC_REQUIRE(!std::isnan(energies[i]), "tsc_diverse_select: energies[%lld] is NaN", (long long)i);
     reset_times();
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
+    Scratch &s = h.scratch();
     const size_t count = size_t(N) * D;
     double *d_in, *d_al, *d_X, *d_mean, *d_e = nullptr;
     int32_t *d_rows, *d_picked;
-    TSC_TRY(upload(c, s, structures, count, &d_in));
+    TSC_TRY(h.in(structures, count, &d_in));
     TSC_TRY(s.get(count, &d_al));
     TSC_TRY(s.get(count, &d_X));
     TSC_TRY(s.get(size_t(D), &d_mean));
     TSC_TRY(s.get(size_t(k), &d_rows));
-    TSC_TRY(s.get(size_t(k), &d_picked));
-    if (energies) TSC_TRY(upload(c, s, energies, size_t(N), &d_e));
+    TSC_TRY(h.out(picked, size_t(k), &d_picked));
+    if (energies) TSC_TRY(h.in(energies, size_t(N), &d_e));
     StageTimer whole(c), tm(c);
     whole.begin();
     tm.begin();
-    TSC_TRY(align_dev(c, s, d_in, N, n_atoms, nullptr, 0, d_al));
-    tm.end(0);
-    TSC_HIP(hipMemcpyAsync(aligned_out, d_al, count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TSC_TRY(align_dev(c, h, d_in, N, n_atoms, nullptr, 0, d_al));
+    tm.end(&g_times[0]);
+    TSC_TRY(h.fetch(aligned_out, d_al, count));
     TSC_HIP(hipMemcpyAsync(d_X, d_al, count * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     if (u) {   // seeds chosen here, on the aligned features, and handed back
-        TSC_TRY(seed_dev(c, s, d_al, N, D, k, u, d_rows));
-        TSC_HIP(hipMemcpyAsync(init_rows, d_rows, size_t(k) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        TSC_TRY(seed_dev(c, h, d_al, N, D, k, u, d_rows));
+        TSC_TRY(h.fetch(init_rows, d_rows, size_t(k)));
     } else {
         TSC_HIP(hipMemcpyAsync(d_rows, init_rows, size_t(k) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
@@ -417,10 +373,8 @@ extern "C" __attribute__((visibility("default"))) int tsc_diverse_select(tsc_ctx
     TSC_TRY(lloyd_run(c, L, max_iter, tol_abs, n_iter, nullptr, tm.on ? &tm : nullptr));
     // the pick sees differences centre - member only: the centred features and centres serve as they are
     TSC_TRY(pick_dev(c, L, d_X, L.C, d_e, d_picked));
-    whole.end(3);
-    TSC_HIP(hipMemcpyAsync(labels, L.labels, size_t(N) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(picked, d_picked, size_t(k) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    whole.end(&g_times[3]);
+    TSC_TRY(h.fetch(labels, L.labels, size_t(N)));
+    return h.finish();
     TSC_API_GUARD_END
 }

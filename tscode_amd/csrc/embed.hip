@@ -1,6 +1,7 @@
 // embed.hip -- K1 / K2: batched embed, clash masks, distances, ordered compaction
 // gfx950 only.  There is deliberately no CPU implementation behind these entry points.
 #include "host.hpp"
+#include "call.hpp"
 #include "scan.hpp"
 
 // --------------------------------------------------------------------------------------------------
@@ -35,19 +36,16 @@ extern "C" __attribute__((visibility("default"))) int tsc_transform_batch(tsc_ct
     for (int64_t i = 0; i < n_poses * n_mols; ++i)
         TSC_REQUIRE(conf_idx[i] >= 0 && conf_idx[i] < n_conf[i % n_mols], "conf_idx[%lld] out of range", (long long)i);
     if (n_poses == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_frags, *d_rot, *d_pos, *d_out;
     int32_t *d_ci;
-    TSC_TRY(upload(c, s, frags, size_t(frags_total_doubles(frag_off, n_atoms, n_conf, n_mols)), &d_frags));
-    TSC_TRY(upload(c, s, conf_idx, size_t(n_poses) * n_mols, &d_ci));
-    TSC_TRY(upload(c, s, rot, size_t(n_poses) * n_mols * 9, &d_rot));
-    TSC_TRY(upload(c, s, pos, size_t(n_poses) * n_mols * 3, &d_pos));
-    TSC_TRY(s.get(size_t(n_poses) * ft.n_total * 3, &d_out));
+    TSC_TRY(h.in(frags, size_t(frags_total_doubles(frag_off, n_atoms, n_conf, n_mols)), &d_frags));
+    TSC_TRY(h.in(conf_idx, size_t(n_poses) * n_mols, &d_ci));
+    TSC_TRY(h.in(rot, size_t(n_poses) * n_mols * 9, &d_rot));
+    TSC_TRY(h.in(pos, size_t(n_poses) * n_mols * 3, &d_pos));
+    TSC_TRY(h.out(out, size_t(n_poses) * ft.n_total * 3, &d_out));
     TSC_TRY(tsc_transform_batch_dev(c, d_frags, frag_off, n_atoms, n_conf, n_mols, d_ci, d_rot, d_pos, n_poses, d_out));
-    TSC_HIP(hipMemcpyAsync(out, d_out, size_t(n_poses) * ft.n_total * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -96,8 +94,7 @@ static int launch_clash_impl(tsc_ctx *c, const ClashArgs &a, const double *coord
     TSC_REQUIRE(lds <= 160 * 1024, "pose too large for the LDS staging of the clash kernel (%d atoms)", a.n);
     int64_t waves = ceil_div<int64_t>(a.n_poses, ppw);
     int blocks = grid_for(waves, 4, 256 * 32);  // (measured: 8192 workgroups beat 2048 by 15 % at 500k x 200 -- a wavefront that loops over poses is a chain of load latencies)
-    if (lds > 64 * 1024)
-        TSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_clash<FUSED, SELF, MINMODE>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+    TSC_TRY(lds_attribute(&k_clash<FUSED, SELF, MINMODE>, lds));
     hipLaunchKernelGGL((k_clash<FUSED, SELF, MINMODE>), dim3(blocks), dim3(256), lds, c->stream, a, coords, frags, ft, conf_idx, rot, pos, mask, counts);
     TSC_HIP(hipGetLastError());
     return 0;
@@ -178,19 +175,15 @@ extern "C" __attribute__((visibility("default"))) int tsc_clash_mask(tsc_ctx *c,
     ClashArgs a;
     TSC_TRY(make_clash_args(n_poses, n_atoms, ids, n_ids, thresh, max_clashes, &a));
     if (n_poses == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *d_coords;
     uint8_t *d_mask;
-    int32_t *d_counts = nullptr;
-    TSC_TRY(upload(c, s, coords, size_t(n_poses) * n_atoms * 3, &d_coords));
-    TSC_TRY(s.get(size_t(n_poses), &d_mask));
-    if (counts) TSC_TRY(s.get(size_t(n_poses), &d_counts));
+    int32_t *d_counts;
+    TSC_TRY(h.in(coords, size_t(n_poses) * n_atoms * 3, &d_coords));
+    TSC_TRY(h.out(mask, size_t(n_poses), &d_mask));
+    TSC_TRY(h.out(counts, size_t(n_poses), &d_counts));
     TSC_TRY(tsc_clash_mask_dev(c, d_coords, n_poses, n_atoms, ids, n_ids, thresh, max_clashes, d_mask, d_counts));
-    TSC_HIP(hipMemcpyAsync(mask, d_mask, size_t(n_poses), hipMemcpyDeviceToHost, c->stream));
-    if (counts) TSC_HIP(hipMemcpyAsync(counts, d_counts, size_t(n_poses) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -214,17 +207,14 @@ extern "C" __attribute__((visibility("default"))) int tsc_all_dists(tsc_ctx *c, 
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(c && A && B && out && na >= 0 && nb >= 0, "tsc_all_dists: bad argument");
     if (na == 0 || nb == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     double *dA, *dB, *dO;
-    TSC_TRY(upload(c, s, A, size_t(na) * 3, &dA));
-    TSC_TRY(upload(c, s, B, size_t(nb) * 3, &dB));
-    TSC_TRY(s.get(size_t(na) * nb, &dO));
+    TSC_TRY(h.in(A, size_t(na) * 3, &dA));
+    TSC_TRY(h.in(B, size_t(nb) * 3, &dB));
+    TSC_TRY(h.out(out, size_t(na) * nb, &dO));
     hipLaunchKernelGGL(k_all_dists, dim3(grid_for(int64_t(na) * nb, 256)), dim3(256), 0, c->stream, dA, na, dB, nb, dO);
     TSC_HIP(hipGetLastError());
-    TSC_HIP(hipMemcpyAsync(out, dO, size_t(na) * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }
 

@@ -1,6 +1,7 @@
 // host.hpp -- host-side helpers shared by the translation units of libtscode_hip (one .hip per kernel family: ctx, embed, prune,
-// pairs_*, adjacent, pipeline).  Functions declared here without a body are defined in exactly one of them; the library is built
-// with -fvisibility=hidden, so none of this is exported.
+// pairs_*, adjacent, pipeline, xchg, rot_corr, diverse, topology, nci, orbitals; what only the entry points on host arrays need
+// is in call.hpp).  Functions declared here without a body are defined in exactly one of them; the library is built with
+// -fvisibility=hidden, so none of this is exported.
 #pragma once
 
 #include <hip/hip_ext.h>
@@ -40,6 +41,13 @@ static inline int make_frag_table(const int64_t *frag_off, const int32_t *n_atom
 
 static inline int grid_for(int64_t work_items, int per_block, int cap = 256 * 16) {
     return int(std::max<int64_t>(1, std::min<int64_t>(ceil_div<int64_t>(work_items, per_block), cap)));
+}
+
+// a launch with more dynamic LDS than the 64 KB a kernel may use without asking
+template <typename K>
+static inline int lds_attribute(K kernel, size_t lds) {
+    if (lds > 64 * 1024) TSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+    return 0;
 }
 
 template <typename T>

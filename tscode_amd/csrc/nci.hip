@@ -1,6 +1,7 @@
 // nci.hip -- launches and C ABI of the batched non-covalent-interaction finder (nci.hpp; tscode/nci.py:28-181 with is_phenyl,
 // tscode/graph_manipulations.py:152-174).  gfx950 only.  There is deliberately no CPU implementation behind these entry points.
 #include "host.hpp"
+#include "call.hpp"
 #include "nci.hpp"
 
 namespace {
@@ -52,9 +53,9 @@ int make_args(const char *who, int64_t n_structs, int n_atoms, const uint8_t *at
     // the atoms of a molecule are contiguous and the molecules come in order, every one with an atom: what np.cumsum(ids) describes
     TSC_REQUIRE(atom_mol[0] == 0 && atom_mol[n_atoms - 1] == n_mols - 1, "%s: the atoms run from molecule %d to %d with %d molecules", who,
                 int(atom_mol[0]), int(atom_mol[n_atoms - 1]), n_mols);
+    TSC_TRY(check_class_table(who, atom_class, n_atoms, thr, n_classes, a.bound, T));  // (a bound of 0: never)
     int n_cand = 0;
     for (int i = 0; i < n_atoms; ++i) {
-        TSC_REQUIRE(atom_class[i] < n_classes, "%s: class %d of atom %d with %d classes", who, int(atom_class[i]), i, n_classes);
         const int m = atom_mol[i];
         TSC_REQUIRE(i == 0 || m == atom_mol[i - 1] || m == atom_mol[i - 1] + 1, "%s: atom %d of molecule %d follows one of molecule %d", who, i, m,
                     int(atom_mol[i - 1]));
@@ -68,69 +69,24 @@ int make_args(const char *who, int64_t n_structs, int n_atoms, const uint8_t *at
     }
     a.cand_off[n_mols] = n_cand;
     for (int p = 0; p < n_classes; ++p) {
-        for (int q = 0; q < n_classes; ++q) {
-            const double t = thr[p * n_classes + q];
-            TSC_REQUIRE(std::isfinite(t) && t >= 0.0, "%s: thr[%d][%d] = %g is negative or not finite", who, p, q, t);
-            a.bound[p * T + q] = clash_sq_bound(t);  // (0 for a threshold of 0: never)
-        }
         TSC_REQUIRE(std::isfinite(ring_thr[p]) && ring_thr[p] >= 0.0, "%s: ring_thr[%d] = %g is negative or not finite", who, p, ring_thr[p]);
         a.ring_bound[p] = clash_sq_bound(ring_thr[p]);
     }
-    const bool per_struct = n_con > 0 && con_per_struct != 0;
-    a.n_con = per_struct ? n_con : 0;
-    if (n_con > 0 && (!per_struct || constrained_on_host)) {
-        const int64_t count = per_struct ? n_structs * n_con : n_con;
-        for (int64_t q = 0; q < count; ++q) {
-            const int32_t e = constrained[q];
-            TSC_REQUIRE(e >= -1 && e < n_atoms, "%s: constrained atom %d with %d atoms", who, e, n_atoms);
-            if (!per_struct && e >= 0) a.con_words[e >> 6] |= 1ull << (e & 63);
-        }
-    }
-    return 0;
-}
-
-template <int W>
-void launch_w(tsc_ctx *c, const NciArgs &a, const double *coords, const int32_t *con, const Outputs &o) {
-    // (a grid-stride loop from 8192 structures on: eight blocks per CU is what the LDS of a small structure admits)
-    const int blocks = grid_for(a.n_structs, 4, 2048);
-    hipLaunchKernelGGL(k_nci<W>, dim3(blocks), dim3(256), nci_lds_bytes(a.n), c->stream, a, coords, con, o.counts, o.overflow, o.pair_bits,
-                       o.ring_atoms, o.ring_owner, o.ring_center, o.ring_atom_bits, o.ring_ring_bits);
+    return check_index_list(who, "constrained", constrained, n_con, con_per_struct, constrained_on_host, n_structs, n_atoms, a.con_words, &a.n_con);
 }
 
 // device pointers throughout, except the tables
 int run_dev(tsc_ctx *c, const NciArgs &a, const double *coords, const int32_t *con_dev, const Outputs &o) {
     static_assert(nci_lds_bytes(NC_MAX_ATOMS) <= 65536, "LDS of a block");
-    const bool timed = c->pass_timing >= 1;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EventPair {   // (a profiling path: the events live for this call only, whichever way it ends)
-        hipEvent_t *e;
-        ~EventPair() {
-            for (int q = 0; q < 2; ++q)
-                if (e[q]) (void)hipEventDestroy(e[q]);
-        }
-    } owner{ev};
-    if (timed) {
-        TSC_HIP(hipEventCreate(&ev[0]));
-        TSC_HIP(hipEventCreate(&ev[1]));
-        TSC_HIP(hipEventRecord(ev[0], c->stream));
-    }
-    switch (ceil_div(a.n, 64)) {
-        case 1: launch_w<1>(c, a, coords, con_dev, o); break;
-        case 2: launch_w<2>(c, a, coords, con_dev, o); break;
-        case 3: launch_w<3>(c, a, coords, con_dev, o); break;
-        case 4: launch_w<4>(c, a, coords, con_dev, o); break;
-        case 5: launch_w<5>(c, a, coords, con_dev, o); break;
-        case 6: launch_w<6>(c, a, coords, con_dev, o); break;
-        case 7: launch_w<7>(c, a, coords, con_dev, o); break;
-        default: launch_w<8>(c, a, coords, con_dev, o); break;
-    }
-    hipError_t launched = hipGetLastError();
-    if (timed) {
-        float ms = -1.f;
-        if (launched == hipSuccess && hipEventRecord(ev[1], c->stream) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
-            hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-            g_kernel_ms = ms;
-    }
+    StageTimer tm(c);
+    tm.begin();
+    with_words(a.n, [&](auto w) {
+        // (a grid-stride loop from 8192 structures on: eight blocks per CU is what the LDS of a small structure admits)
+        hipLaunchKernelGGL(k_nci<decltype(w)::value>, dim3(grid_for(a.n_structs, 4, 2048)), dim3(256), nci_lds_bytes(a.n), c->stream, a, coords, con_dev,
+                           o.counts, o.overflow, o.pair_bits, o.ring_atoms, o.ring_owner, o.ring_center, o.ring_atom_bits, o.ring_ring_bits);
+    });
+    const hipError_t launched = hipGetLastError();
+    if (launched == hipSuccess) tm.end(&g_kernel_ms);
     TSC_HIP(launched);
     return 0;
 }
@@ -180,32 +136,22 @@ extern "C" __attribute__((visibility("default"))) int tsc_nci(tsc_ctx *c, const 
                       constrained, n_con, con_per_struct, true, owner_rule, &a));
     g_kernel_ms = -1.f;
     if (n_structs == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall h(c);
     const size_t N = size_t(n_structs), W = size_t(ceil_div(n_atoms, 64)), R = NC_MAX_RINGS;
     double *d_coords;
     int32_t *d_con = nullptr;
     Outputs o{};
-    TSC_TRY(upload(c, s, coords, N * n_atoms * 3, &d_coords));
-    if (a.n_con) TSC_TRY(upload(c, s, constrained, N * n_con, &d_con));
-    TSC_TRY(s.get(N * 4, &o.counts));
-    TSC_TRY(s.get(N, &o.overflow));
-    if (pair_bits) TSC_TRY(s.get(N * n_atoms * W, &o.pair_bits));
-    if (ring_atoms) TSC_TRY(s.get(N * R * 6, &o.ring_atoms));
-    if (ring_owner) TSC_TRY(s.get(N * R, &o.ring_owner));
-    if (ring_center) TSC_TRY(s.get(N * R * 3, &o.ring_center));
-    if (ring_atom_bits) TSC_TRY(s.get(N * R * W, &o.ring_atom_bits));
-    if (ring_ring_bits) TSC_TRY(s.get(N * R, &o.ring_ring_bits));
+    TSC_TRY(h.in(coords, N * n_atoms * 3, &d_coords));
+    if (a.n_con) TSC_TRY(h.in(constrained, N * n_con, &d_con));
+    TSC_TRY(h.out(counts, N * 4, &o.counts));
+    TSC_TRY(h.out(overflow, N, &o.overflow));
+    TSC_TRY(h.out(pair_bits, N * n_atoms * W, &o.pair_bits));
+    TSC_TRY(h.out(ring_atoms, N * R * 6, &o.ring_atoms));
+    TSC_TRY(h.out(ring_owner, N * R, &o.ring_owner));
+    TSC_TRY(h.out(ring_center, N * R * 3, &o.ring_center));
+    TSC_TRY(h.out(ring_atom_bits, N * R * W, &o.ring_atom_bits));
+    TSC_TRY(h.out(ring_ring_bits, N * R, &o.ring_ring_bits));
     TSC_TRY(run_dev(c, a, d_coords, d_con, o));
-    TSC_HIP(hipMemcpyAsync(counts, o.counts, N * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(overflow, o.overflow, N, hipMemcpyDeviceToHost, c->stream));
-    if (pair_bits) TSC_HIP(hipMemcpyAsync(pair_bits, o.pair_bits, N * n_atoms * W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (ring_atoms) TSC_HIP(hipMemcpyAsync(ring_atoms, o.ring_atoms, N * R * 6 * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
-    if (ring_owner) TSC_HIP(hipMemcpyAsync(ring_owner, o.ring_owner, N * R, hipMemcpyDeviceToHost, c->stream));
-    if (ring_center) TSC_HIP(hipMemcpyAsync(ring_center, o.ring_center, N * R * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (ring_atom_bits) TSC_HIP(hipMemcpyAsync(ring_atom_bits, o.ring_atom_bits, N * R * W * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (ring_ring_bits) TSC_HIP(hipMemcpyAsync(ring_ring_bits, o.ring_ring_bits, N * R * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }

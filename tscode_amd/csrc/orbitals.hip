@@ -2,6 +2,7 @@
 // tscode/hypermolecule_class.py:195-217, tscode/reactive_atoms_classes.py, tscode/embedder.py:542-621).  gfx950 only.  No entry point
 // has a CPU path; the per-conformer code of orbitals.hpp is host-callable only so that tools/probe/orbitals_host_check.cpp can run it under sanitizers.
 #include "host.hpp"
+#include "call.hpp"
 #include "orbitals.hpp"
 
 namespace {
@@ -79,30 +80,13 @@ int make_args(const char *who, int64_t n_conf, int n_atoms, const tsc_orbital_re
 
 // device pointers throughout
 int run_dev(tsc_ctx *c, const OrbArgs &a, const double *coords, const Outputs &o) {
-    const bool timed = c->pass_timing >= 1;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EventPair {   // (a profiling path: the events live for this call only, whichever way it ends)
-        hipEvent_t *e;
-        ~EventPair() {
-            for (int q = 0; q < 2; ++q)
-                if (e[q]) (void)hipEventDestroy(e[q]);
-        }
-    } owner{ev};
-    if (timed) {
-        TSC_HIP(hipEventCreate(&ev[0]));
-        TSC_HIP(hipEventCreate(&ev[1]));
-        TSC_HIP(hipEventRecord(ev[0], c->stream));
-    }
+    StageTimer tm(c);
+    tm.begin();
     // (a grid-stride loop from a million conformers on)
     hipLaunchKernelGGL(k_orbitals, dim3(grid_for(a.n_conf, 256)), dim3(256), 0, c->stream, a, coords, o.centers, o.orb_vecs, o.n_lobes, o.kind,
                        o.sigmatropic, o.pivot, o.meanpoint, o.lobe_index, o.n_pivots);
-    hipError_t launched = hipGetLastError();
-    if (timed) {
-        float ms = -1.f;
-        if (launched == hipSuccess && hipEventRecord(ev[1], c->stream) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
-            hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-            g_kernel_ms = ms;
-    }
+    const hipError_t launched = hipGetLastError();
+    if (launched == hipSuccess) tm.end(&g_kernel_ms);
     TSC_HIP(launched);
     return 0;
 }
@@ -146,36 +130,21 @@ extern "C" __attribute__((visibility("default"))) int tsc_orbitals(tsc_ctx *c, c
     TSC_TRY(make_args("tsc_orbitals", n_conf, n_atoms, recipes, n_reactive, sigmatropic_mode, suprafacial, h, &a));
     g_kernel_ms = -1.f;
     if (n_conf == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall hc(c);
     const size_t C = size_t(n_conf), R = size_t(n_reactive), L = OB_LOBES, P = OB_PIVOTS;
     double *d_coords;
     Outputs o{};
-    TSC_TRY(upload(c, s, coords, C * n_atoms * 3, &d_coords));
-    TSC_TRY(s.get(C * R * L * 3, &o.centers));
-    TSC_TRY(s.get(C * R * L * 3, &o.orb_vecs));
-    TSC_TRY(s.get(C * R, &o.n_lobes));
-    TSC_TRY(s.get(C * R, &o.kind));
-    TSC_TRY(s.get(C, &o.sigmatropic));
-    if (a.want_pivots) {
-        TSC_TRY(s.get(C * P * 3, &o.pivot));
-        TSC_TRY(s.get(C * P * 3, &o.meanpoint));
-        TSC_TRY(s.get(C * P * 2, &o.lobe_index));
-        TSC_TRY(s.get(C, &o.n_pivots));
-    }
+    TSC_TRY(hc.in(coords, C * n_atoms * 3, &d_coords));
+    TSC_TRY(hc.out(centers, C * R * L * 3, &o.centers));
+    TSC_TRY(hc.out(orb_vecs, C * R * L * 3, &o.orb_vecs));
+    TSC_TRY(hc.out(n_lobes, C * R, &o.n_lobes));
+    TSC_TRY(hc.out(kind, C * R, &o.kind));
+    TSC_TRY(hc.out(sigmatropic, C, &o.sigmatropic));
+    TSC_TRY(hc.out(pivot, C * P * 3, &o.pivot));   // (the four pivot arrays together or none of them: make_args)
+    TSC_TRY(hc.out(meanpoint, C * P * 3, &o.meanpoint));
+    TSC_TRY(hc.out(lobe_index, C * P * 2, &o.lobe_index));
+    TSC_TRY(hc.out(n_pivots, C, &o.n_pivots));
     TSC_TRY(run_dev(c, a, d_coords, o));
-    TSC_HIP(hipMemcpyAsync(centers, o.centers, C * R * L * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(orb_vecs, o.orb_vecs, C * R * L * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(n_lobes, o.n_lobes, C * R, hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(kind, o.kind, C * R, hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(sigmatropic, o.sigmatropic, C, hipMemcpyDeviceToHost, c->stream));
-    if (a.want_pivots) {
-        TSC_HIP(hipMemcpyAsync(pivot, o.pivot, C * P * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        TSC_HIP(hipMemcpyAsync(meanpoint, o.meanpoint, C * P * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        TSC_HIP(hipMemcpyAsync(lobe_index, o.lobe_index, C * P * 2, hipMemcpyDeviceToHost, c->stream));
-        TSC_HIP(hipMemcpyAsync(n_pivots, o.n_pivots, C, hipMemcpyDeviceToHost, c->stream));
-    }
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return hc.finish();
     TSC_API_GUARD_END
 }

@@ -1,45 +1,30 @@
 // rot_corr.hip -- launches and C ABI of the symmetry-corrected RMSD prune (rot_corr.hpp; tscode/torsion_module.py:953-1161).
 // gfx950 only.  There is deliberately no CPU implementation behind these entry points.
 #include "host.hpp"
+#include "call.hpp"
 #include "rot_corr.hpp"
 
 #include <algorithm>
 #include <climits>
+#include <memory>
 
 // One run: the centred structures live on the device from tsc_rot_corr_begin to tsc_rot_corr_end and are turned in place by the
 // passes, as the reference turns its array; the cache bitmap of dissimilar pairs (:1121-1123) lives beside them.
 struct tsc_rot_corr {
-    tsc_ctx *ctx = nullptr;
+    tsc_ctx *ctx;
     int64_t N = 0, words = 0;
     tsc::RotCorrArgs a{};
     double *coords = nullptr;
     uint32_t *cache = nullptr;
     int32_t *first = nullptr;
     unsigned long long *evaluated = nullptr;
-    std::vector<void *> blocks;
+    tsc::Scratch scratch;   // every device block of the run, handed back when it is deleted
+    explicit tsc_rot_corr(tsc_ctx *c) : ctx(c), scratch(c) {}
 };
 
 namespace {
 
 using namespace tsc;
-
-template <typename T>
-int rc_get(tsc_rot_corr *r, size_t count, T **out) {
-    void *p = nullptr;
-    TSC_TRY(r->ctx->alloc((count ? count : 1) * sizeof(T), &p));
-    r->blocks.push_back(p);
-    *out = static_cast<T *>(p);
-    return 0;
-}
-
-template <typename T>
-int rc_put(tsc_rot_corr *r, const T *host, size_t count, const T **out) {
-    T *d;
-    TSC_TRY(rc_get(r, count, &d));
-    if (count) TSC_HIP(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, r->ctx->stream));
-    *out = d;
-    return 0;
-}
 
 // the limits of the ABI (include/tscode_hip.h), checked on the host arrays before anything touches the device
 int check_setup(int64_t N, int n, const int32_t *heavy, int h, const int32_t *tors, int T, const double *angles, const int32_t *n_angles,
@@ -62,29 +47,17 @@ int check_setup(int64_t N, int n, const int32_t *heavy, int h, const int32_t *to
     return 0;
 }
 
-int upload_setup(tsc_rot_corr *r, int n, const int32_t *heavy, int h, const int32_t *tors, int T, const double *angles,
+int upload_setup(HostCall &hc, RotCorrArgs &a, int n, const int32_t *heavy, int h, const int32_t *tors, int T, const double *angles,
                  const int32_t *n_angles, const uint8_t *mask, const int32_t *sub_ptr, const int32_t *sub_idx) {
-    RotCorrArgs &a = r->a;
     a.n = n, a.h = h, a.n_tors = T;
-    TSC_TRY(rc_put(r, heavy, size_t(h), &a.heavy));
-    TSC_TRY(rc_put(r, tors, size_t(T) * 4, &a.tors));
-    TSC_TRY(rc_put(r, angles, size_t(T) * RC_MAX_ANGLES, &a.angles));
-    TSC_TRY(rc_put(r, n_angles, size_t(T), &a.n_angles));
-    TSC_TRY(rc_put(r, mask, size_t(T) * n, &a.masks));
-    TSC_TRY(rc_put(r, sub_ptr, size_t(T) + 1, &a.sub_ptr));
-    TSC_TRY(rc_put(r, sub_idx, size_t(sub_ptr[T]), &a.sub_idx));
+    TSC_TRY(hc.in(heavy, size_t(h), &a.heavy));
+    TSC_TRY(hc.in(tors, size_t(T) * 4, &a.tors));
+    TSC_TRY(hc.in(angles, size_t(T) * RC_MAX_ANGLES, &a.angles));
+    TSC_TRY(hc.in(n_angles, size_t(T), &a.n_angles));
+    TSC_TRY(hc.in(mask, size_t(T) * n, &a.masks));
+    TSC_TRY(hc.in(sub_ptr, size_t(T) + 1, &a.sub_ptr));
+    TSC_TRY(hc.in(sub_idx, size_t(sub_ptr[T]), &a.sub_idx));
     return 0;
-}
-
-template <typename K>
-int lds_attribute(K kernel, size_t lds) {
-    if (lds > 64 * 1024) TSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    return 0;
-}
-
-void free_run(tsc_rot_corr *r) {
-    for (void *p : r->blocks) r->ctx->release(p);
-    delete r;
 }
 
 }  // namespace
@@ -99,7 +72,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_rot_corr_destroy(tsc_r
         auto &lr = r->ctx->live_rot_corr;
         lr.erase(std::remove(lr.begin(), lr.end(), r), lr.end());
     }
-    free_run(r);
+    delete r;   // (its blocks go back to the cache)
     return 0;
     TSC_API_GUARD_END
 }
@@ -112,27 +85,20 @@ extern "C" __attribute__((visibility("default"))) int tsc_rot_corr_begin(tsc_ctx
     TSC_REQUIRE(c && out && (coords || n_structs == 0), "tsc_rot_corr_begin: null argument");
     *out = nullptr;
     TSC_TRY(check_setup(n_structs, n_atoms, heavy, n_heavy, torsions, n_tors, angles, n_angles, move_mask, sub_ptr, sub_idx));
-    DeviceGuard guard(c->device);
-    tsc_rot_corr *r = new tsc_rot_corr;
-    r->ctx = c;
-    r->N = n_structs;
-    r->words = (n_structs + 31) / 32;
-    int rc = upload_setup(r, n_atoms, heavy, n_heavy, torsions, n_tors, angles, n_angles, move_mask, sub_ptr, sub_idx);
-    const double *d_coords = nullptr;
-    if (!rc) rc = rc_put(r, coords, size_t(n_structs) * n_atoms * 3, &d_coords);
-    if (!rc) rc = rc_get(r, size_t(n_structs) * r->words, &r->cache);
-    if (!rc) rc = rc_get(r, size_t(n_structs), &r->first);
-    if (!rc) rc = rc_get(r, 1, &r->evaluated);
-    if (!rc && n_structs) {
-        hipError_t e = hipMemsetAsync(r->cache, 0, size_t(n_structs) * r->words * sizeof(uint32_t), c->stream);
-        if (e != hipSuccess) rc = fail(TSC_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);
-        free_run(r);
-        return rc;
-    }
-    r->coords = const_cast<double *>(d_coords);
+    // the run's blocks are the call's until everything is in place: an error hands them back behind an idle stream
+    HostCall h(c);
+    std::unique_ptr<tsc_rot_corr> run(new tsc_rot_corr(c));
+    run->N = n_structs;
+    run->words = (n_structs + 31) / 32;
+    TSC_TRY(upload_setup(h, run->a, n_atoms, heavy, n_heavy, torsions, n_tors, angles, n_angles, move_mask, sub_ptr, sub_idx));
+    TSC_TRY(h.in(coords, size_t(n_structs) * n_atoms * 3, &run->coords));
+    TSC_TRY(h.scratch().get(size_t(n_structs) * run->words, &run->cache));
+    TSC_TRY(h.scratch().get(size_t(n_structs), &run->first));
+    TSC_TRY(h.scratch().get(1, &run->evaluated));
+    if (n_structs) TSC_HIP(hipMemsetAsync(run->cache, 0, size_t(n_structs) * run->words * sizeof(uint32_t), c->stream));
+    TSC_TRY(h.finish());
+    run->scratch.blocks.swap(h.scratch().blocks);
+    tsc_rot_corr *r = run.release();
     {
         std::lock_guard<std::mutex> lock(c->runs_mutex);
         c->live_rot_corr.push_back(r);
@@ -151,7 +117,8 @@ extern "C" __attribute__((visibility("default"))) int tsc_rot_corr_pass(tsc_rot_
                 "bad pass geometry (n = %lld, d = %lld, k = %lld, active = %lld)", (long long)N, (long long)d, (long long)k, (long long)num_active);
     TSC_REQUIRE(std::isfinite(max_rmsd), "tsc_rot_corr_pass: max_rmsd not finite");
     tsc_ctx *c = r->ctx;
-    DeviceGuard guard(c->device);
+    unsigned long long ev = 0;
+    HostCall h(c);
     TSC_HIP(hipMemsetAsync(r->first, 0xff, size_t(N) * sizeof(int32_t), c->stream));
     TSC_HIP(hipMemsetAsync(r->evaluated, 0, sizeof(unsigned long long), c->stream));
     const size_t lds = rot_corr_lds_bytes(r->a.n_tors, r->a.n, RC_WAVES);
@@ -159,10 +126,9 @@ extern "C" __attribute__((visibility("default"))) int tsc_rot_corr_pass(tsc_rot_
     hipLaunchKernelGGL(k_rot_corr_pass, dim3(unsigned(k)), dim3(64 * RC_WAVES), lds, c->stream, r->a, r->coords, d, k, num_active, max_rmsd, r->cache,
                        r->words, r->first, r->evaluated);
     TSC_HIP(hipGetLastError());
-    unsigned long long ev = 0;
-    TSC_HIP(hipMemcpyAsync(first, r->first, size_t(N) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(&ev, r->evaluated, sizeof(ev), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
+    TSC_TRY(h.fetch(first, r->first, size_t(N)));
+    TSC_TRY(h.fetch(&ev, r->evaluated, 1));
+    TSC_TRY(h.finish());
     *pairs_evaluated = int64_t(ev);
     return 0;
     TSC_API_GUARD_END
@@ -172,10 +138,9 @@ extern "C" __attribute__((visibility("default"))) int tsc_rot_corr_end(tsc_rot_c
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(r && (coords_out || r->N == 0), "tsc_rot_corr_end: null argument");
     tsc_ctx *c = r->ctx;
-    DeviceGuard guard(c->device);
-    TSC_HIP(hipMemcpyAsync(coords_out, r->coords, size_t(r->N) * r->a.n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    HostCall h(c);
+    TSC_TRY(h.fetch(coords_out, r->coords, size_t(r->N) * r->a.n * 3));
+    return h.finish();
     TSC_API_GUARD_END
 }
 
@@ -192,33 +157,21 @@ extern "C" __attribute__((visibility("default"))) int tsc_rot_corr_pairs(tsc_ctx
     for (int64_t p = 0; p < 2 * n_pairs; ++p)
         TSC_REQUIRE(pairs[p] >= 0 && pairs[p] < n_structs, "tsc_rot_corr_pairs: pair %lld: structure index out of range", (long long)(p / 2));
     if (n_pairs == 0) return 0;
-    DeviceGuard guard(c->device);
-    // a run object only as the owner of the uploaded set-up (never listed: it does not outlive this call)
-    tsc_rot_corr tmp;
-    tmp.ctx = c;
-    struct Release {
-        tsc_rot_corr *r;
-        ~Release() {
-            (void)hipStreamSynchronize(r->ctx->stream);
-            for (void *p : r->blocks) r->ctx->release(p);
-        }
-    } release{&tmp};
-    TSC_TRY(upload_setup(&tmp, n_atoms, heavy, n_heavy, torsions, n_tors, angles, n_angles, move_mask, sub_ptr, sub_idx));
+    HostCall h(c);
+    RotCorrArgs a{};
+    TSC_TRY(upload_setup(h, a, n_atoms, heavy, n_heavy, torsions, n_tors, angles, n_angles, move_mask, sub_ptr, sub_idx));
     const double *d_coords;
     const int32_t *d_pairs;
     double *d_rmsd, *d_best;
-    TSC_TRY(rc_put(&tmp, coords, size_t(n_structs) * n_atoms * 3, &d_coords));
-    TSC_TRY(rc_put(&tmp, pairs, size_t(n_pairs) * 2, &d_pairs));
-    TSC_TRY(rc_get(&tmp, size_t(n_pairs), &d_rmsd));
-    TSC_TRY(rc_get(&tmp, size_t(n_pairs) * n_tors, &d_best));
+    TSC_TRY(h.in(coords, size_t(n_structs) * n_atoms * 3, &d_coords));
+    TSC_TRY(h.in(pairs, size_t(n_pairs) * 2, &d_pairs));
+    TSC_TRY(h.out(rmsd, size_t(n_pairs), &d_rmsd));
+    TSC_TRY(h.out(best_angle, size_t(n_pairs) * n_tors, &d_best));   // (null is allowed without torsions: nothing is written then)
     const size_t lds = rot_corr_lds_bytes(n_tors, n_atoms, RC_WAVES);
     TSC_TRY(lds_attribute(&k_rot_corr_pairs, lds));
-    hipLaunchKernelGGL(k_rot_corr_pairs, dim3(grid_for(n_pairs, RC_WAVES, 256 * 4)), dim3(64 * RC_WAVES), lds, c->stream, tmp.a, d_coords, d_pairs,
+    hipLaunchKernelGGL(k_rot_corr_pairs, dim3(grid_for(n_pairs, RC_WAVES, 256 * 4)), dim3(64 * RC_WAVES), lds, c->stream, a, d_coords, d_pairs,
                        n_pairs, d_rmsd, d_best);
     TSC_HIP(hipGetLastError());
-    TSC_HIP(hipMemcpyAsync(rmsd, d_rmsd, size_t(n_pairs) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (n_tors) TSC_HIP(hipMemcpyAsync(best_angle, d_best, size_t(n_pairs) * n_tors * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h.finish();
     TSC_API_GUARD_END
 }

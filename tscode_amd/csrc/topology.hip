@@ -1,6 +1,7 @@
 // topology.hip -- launches and C ABI of the batched bond-graph / scramble check (topology.hpp; tscode/graph_manipulations.py:28-55,
 // tscode/utils.py:293-314, :341-387).  gfx950 only.  There is deliberately no CPU implementation behind these entry points.
 #include "host.hpp"
+#include "call.hpp"
 #include "topology.hpp"
 
 #include <vector>
@@ -32,26 +33,9 @@ int make_tables(const char *who, int64_t n_structs, int n_atoms, const uint8_t *
     TopoArgs &a = out->a;
     memset(&a, 0, sizeof(a));
     a.n_structs = n_structs, a.n = n_atoms, a.n_tab = T, a.max_newbonds = max_newbonds;
-    for (int i = 0; i < n_atoms; ++i) {
-        TSC_REQUIRE(atom_class[i] < n_classes, "%s: class %d of atom %d with %d classes", who, int(atom_class[i]), i, n_classes);
-        a.cls[i] = (!active || active[i]) ? atom_class[i] : uint8_t(n_classes);
-    }
-    for (int p = 0; p < n_classes; ++p)
-        for (int q = 0; q < n_classes; ++q) {
-            const double t = thr[p * n_classes + q];
-            TSC_REQUIRE(std::isfinite(t) && t >= 0.0, "%s: thr[%d][%d] = %g is negative or not finite", who, p, q, t);
-            a.bound[p * T + q] = clash_sq_bound(t);  // (0 for a threshold of 0: never bonded)
-        }
-    const bool per_struct = n_excl > 0 && excl_per_struct != 0;
-    a.n_excl = per_struct ? n_excl : 0;
-    if (n_excl > 0 && (!per_struct || excluded_on_host)) {
-        const int64_t count = per_struct ? n_structs * n_excl : n_excl;
-        for (int64_t q = 0; q < count; ++q) {
-            const int32_t e = excluded[q];
-            TSC_REQUIRE(e >= -1 && e < n_atoms, "%s: excluded atom %d with %d atoms", who, e, n_atoms);
-            if (!per_struct && e >= 0) a.excl_words[e >> 6] |= 1ull << (e & 63);
-        }
-    }
+    TSC_TRY(check_class_table(who, atom_class, n_atoms, thr, n_classes, a.bound, T));  // (a bound of 0: never bonded)
+    for (int i = 0; i < n_atoms; ++i) a.cls[i] = (!active || active[i]) ? atom_class[i] : uint8_t(n_classes);
+    TSC_TRY(check_index_list(who, "excluded", excluded, n_excl, excl_per_struct, excluded_on_host, n_structs, n_atoms, a.excl_words, &a.n_excl));
     if (ref_bits) {
         for (int i = 0; i < n_atoms; ++i)
             for (int w = 0; w < W; ++w) {
@@ -66,50 +50,20 @@ int make_tables(const char *who, int64_t n_structs, int n_atoms, const uint8_t *
     return 0;
 }
 
-template <int W>
-void launch_w(tsc_ctx *c, const TopoArgs &a, const double *coords, const uint64_t *ref, const int32_t *excl, uint8_t *mask, int32_t *formed,
-              int32_t *broken, uint64_t *adj) {
-    const int blocks = grid_for(a.n_structs, 4);
-    hipLaunchKernelGGL(k_bond_delta<W>, dim3(blocks), dim3(256), topo_lds_bytes(a.n), c->stream, a, coords, ref, excl, mask, formed, broken, adj);
-}
-
 // device pointers throughout, except the tables
 int run_dev(tsc_ctx *c, Scratch &s, const Tables &t, const double *coords, const int32_t *excl_dev, uint8_t *mask, int32_t *formed,
             int32_t *broken, uint64_t *adj) {
     const TopoArgs &a = t.a;
     uint64_t *d_ref = nullptr;
     if (!t.ref.empty()) TSC_TRY(upload(c, s, t.ref.data(), t.ref.size(), &d_ref));
-    const bool timed = c->pass_timing >= 1;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EventPair {   // (a profiling path: the events live for this call only, whichever way it ends)
-        hipEvent_t *e;
-        ~EventPair() {
-            for (int q = 0; q < 2; ++q)
-                if (e[q]) (void)hipEventDestroy(e[q]);
-        }
-    } owner{ev};
-    if (timed) {
-        TSC_HIP(hipEventCreate(&ev[0]));
-        TSC_HIP(hipEventCreate(&ev[1]));
-        TSC_HIP(hipEventRecord(ev[0], c->stream));
-    }
-    switch (ceil_div(a.n, 64)) {
-        case 1: launch_w<1>(c, a, coords, d_ref, excl_dev, mask, formed, broken, adj); break;
-        case 2: launch_w<2>(c, a, coords, d_ref, excl_dev, mask, formed, broken, adj); break;
-        case 3: launch_w<3>(c, a, coords, d_ref, excl_dev, mask, formed, broken, adj); break;
-        case 4: launch_w<4>(c, a, coords, d_ref, excl_dev, mask, formed, broken, adj); break;
-        case 5: launch_w<5>(c, a, coords, d_ref, excl_dev, mask, formed, broken, adj); break;
-        case 6: launch_w<6>(c, a, coords, d_ref, excl_dev, mask, formed, broken, adj); break;
-        case 7: launch_w<7>(c, a, coords, d_ref, excl_dev, mask, formed, broken, adj); break;
-        default: launch_w<8>(c, a, coords, d_ref, excl_dev, mask, formed, broken, adj); break;
-    }
-    hipError_t launched = hipGetLastError();
-    if (timed) {
-        float ms = -1.f;
-        if (launched == hipSuccess && hipEventRecord(ev[1], c->stream) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
-            hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-            g_kernel_ms = ms;
-    }
+    StageTimer tm(c);
+    tm.begin();
+    with_words(a.n, [&](auto w) {
+        hipLaunchKernelGGL(k_bond_delta<decltype(w)::value>, dim3(grid_for(a.n_structs, 4)), dim3(256), topo_lds_bytes(a.n), c->stream, a, coords, d_ref, excl_dev,
+                           mask, formed, broken, adj);
+    });
+    const hipError_t launched = hipGetLastError();
+    if (launched == hipSuccess) tm.end(&g_kernel_ms);
     TSC_HIP(launched);
     // the expected rows were uploaded from this call's own memory: they must have left it before it is freed
     if (d_ref) TSC_HIP(hipStreamSynchronize(c->stream));
@@ -156,25 +110,19 @@ extern "C" __attribute__((visibility("default"))) int tsc_bond_delta(tsc_ctx *c,
                         max_newbonds, &t));
     g_kernel_ms = -1.f;
     if (n_structs == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
-    const size_t N = size_t(n_structs), rows = N * n_atoms * ceil_div(n_atoms, 64);
+    HostCall h(c);
+    const size_t N = size_t(n_structs);
     double *d_coords;
-    int32_t *d_excl = nullptr, *d_formed = nullptr, *d_broken = nullptr;
+    int32_t *d_excl = nullptr, *d_formed, *d_broken;
     uint8_t *d_mask;
-    uint64_t *d_adj = nullptr;
-    TSC_TRY(upload(c, s, coords, N * n_atoms * 3, &d_coords));
-    if (t.a.n_excl) TSC_TRY(upload(c, s, excluded, N * n_excl, &d_excl));
-    TSC_TRY(s.get(N, &d_mask));
-    if (formed) TSC_TRY(s.get(N, &d_formed));
-    if (broken) TSC_TRY(s.get(N, &d_broken));
-    if (adj) TSC_TRY(s.get(rows, &d_adj));
-    TSC_TRY(run_dev(c, s, t, d_coords, d_excl, d_mask, d_formed, d_broken, d_adj));
-    TSC_HIP(hipMemcpyAsync(mask, d_mask, N, hipMemcpyDeviceToHost, c->stream));
-    if (formed) TSC_HIP(hipMemcpyAsync(formed, d_formed, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (broken) TSC_HIP(hipMemcpyAsync(broken, d_broken, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (adj) TSC_HIP(hipMemcpyAsync(adj, d_adj, rows * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    uint64_t *d_adj;
+    TSC_TRY(h.in(coords, N * n_atoms * 3, &d_coords));
+    if (t.a.n_excl) TSC_TRY(h.in(excluded, N * n_excl, &d_excl));
+    TSC_TRY(h.out(mask, N, &d_mask));
+    TSC_TRY(h.out(formed, N, &d_formed));
+    TSC_TRY(h.out(broken, N, &d_broken));
+    TSC_TRY(h.out(adj, N * n_atoms * ceil_div(n_atoms, 64), &d_adj));
+    TSC_TRY(run_dev(c, h.scratch(), t, d_coords, d_excl, d_mask, d_formed, d_broken, d_adj));
+    return h.finish();
     TSC_API_GUARD_END
 }

@@ -535,11 +535,14 @@ class Engine:
                                           ptr(active), ptr(ref_bits), ptr(excluded), C.c_int(n_excl), C.c_int(int(bool(excl_per_struct))),
                                           C.c_int64(int(max_newbonds)), ptr(mask), ptr(formed), ptr(broken), ptr(adj)))
 
+    def _kernel_ms(self, timings) -> float:
+        ms = C.c_float()
+        check(timings(self._h, C.byref(ms)))
+        return ms.value
+
     def topology_kernel_ms(self) -> float:
         """tsc_topology_timings: the kernel time of this thread's latest bond_delta / bond_delta_dev under set_option("pass_timing", 1)."""
-        ms = C.c_float()
-        check(self.lib.tsc_topology_timings(self._h, C.byref(ms)))
-        return ms.value
+        return self._kernel_ms(self.lib.tsc_topology_timings)
 
     # ---- non-covalent interactions -----------------------------------------------------------
     def nci(self, coords, classes, thr, atom_mol, n_mols, candidate, ring_thr, ring_ring_thr, constrained=None, owner_rule=0, want=()):
@@ -592,9 +595,7 @@ class Engine:
 
     def nci_kernel_ms(self) -> float:
         """tsc_nci_timings: the kernel time of this thread's latest nci / nci_dev under set_option("pass_timing", 1)."""
-        ms = C.c_float()
-        check(self.lib.tsc_nci_timings(self._h, C.byref(ms)))
-        return ms.value
+        return self._kernel_ms(self.lib.tsc_nci_timings)
 
     # ---- reactive-atom orbitals and pivots ----------------------------------------------------
     def orbitals(self, coords, recipes, sigmatropic_mode=0, suprafacial=False, want_pivots=True):
@@ -624,9 +625,7 @@ class Engine:
 
     def orbitals_kernel_ms(self) -> float:
         """tsc_orbitals_timings: the kernel time of this thread's latest orbitals / orbitals_dev under set_option("pass_timing", 1)."""
-        ms = C.c_float()
-        check(self.lib.tsc_orbitals_timings(self._h, C.byref(ms)))
-        return ms.value
+        return self._kernel_ms(self.lib.tsc_orbitals_timings)
 
     def prune_heavy(self, heavy, rmsd_thr=0.5, mode=0):
         """prune_conformers_rmsd on the heavy-atom array f64[N, h, 3]. Returns (mask bool[N], per-pass stats)."""
