@@ -231,7 +231,7 @@ def algo(request, eng):
     ensembles beyond 4 M structures), the sieve with every pass of fewer than 64 chunks culled (sorted layout + bounding boxes:
     what the large passes of C4 / C5 run by default), and the last two again with stage 1 of the pair kernels reading the float32 copy
     of the coordinates (what runs of 128 MB of heavy atoms and more do by default).  Since round 5 the walked passes of the sieve
-    screen on the matrix cores in runs of 150 000 structures and more (mm.hpp, option sieve_mm = 1, the default; 2 = always, what the
+    screen on the matrix cores in runs of 100 000 structures and more (mm.hpp, option sieve_mm = 1, the default; 2 = always, what the
     fixture sets): every sieve route above takes that kernel -- fused and with
     its own apply launch, walked and culled (cull_mm.hpp), with stage 1 in float64 and on the float32 copy; the two "16-row" routes leave the choice to the library, which gives
     ensembles of this size the matrix-core screen on 16-row items (k_rmsd_sieve_mm16: what C3 runs); "other-screen" and the three
@@ -557,6 +557,39 @@ def test_culled_row_tiles_dealt_to_emulated_ranks(eng, oracle, world, n_poses, t
         eng.set_option("cull_tile_block", 256)
         eng.set_option("deterministic_basis", 0)
         eng.set_option("sieve_mm", 1)
+
+
+def test_pass_timing_levels_change_nothing_but_the_times(eng, oracle):
+    """The events of the passes ("pass_timing" 0, 1, 2) on a run of 9 000 structures that takes all three pass shapes -- chunk-local at
+    k = 200, 100, 50 (algo 3), walked at 20 and 10, culled at 5, 2, 1 (cull = 2, cull_min_pairs = 5e6): masks and every pass's record
+    are the oracle's at every level; level 0 times nothing; level 1 times the pair kernel of the walked and culled passes only (the
+    chunk-local kernel carries events from level 2 on); level 2 times every pass and its kernel, the kernel inside the pass."""
+    from tscode_amd.synthetic import make_config
+    ens = make_config("C2", 9_000)
+    heavy = np.ascontiguousarray(ens.poses()[:, ens.atomnos != 1])
+    ref = oracle.prune_heavy(heavy, 0.5, mode=0, row_parallel=True)
+    eng.set_option("cull_min_pairs", 5e6)
+    eng.set_option("cull", 2)
+    runs = {}
+    try:
+        for level in (0, 1, 2):
+            eng.set_option("pass_timing", level)
+            runs[level] = eng.prune_heavy(heavy, 0.5, 0)
+    finally:
+        eng.set_option("pass_timing", 0)
+        eng.set_option("cull_min_pairs", 2.0e9)
+        eng.set_option("cull", 1)
+    for level, (mask, stats) in runs.items():
+        print(level, [(s["k"], s["algo"], round(s["gpu_ms"], 4), round(s["tile_ms"], 4)) for s in stats])
+    want = [(s["k"], s["n_active_after"], s["pairs_evaluated"]) for s in ref["stats"]]
+    for level, (mask, stats) in runs.items():
+        assert np.array_equal(mask, ref["mask"]), level
+        assert [(s["k"], s["n_active_after"], s["pairs_evaluated"]) for s in stats] == want, level
+        assert [s["k"] for s in stats] == [200, 100, 50, 20, 10, 5, 2, 1]
+        assert [s["algo"] for s in stats] == [3, 3, 3, 2, 2, 2, 2, 2], level
+    assert all(s["gpu_ms"] == 0 and s["tile_ms"] == 0 for s in runs[0][1])
+    assert all(s["gpu_ms"] == 0 and (s["tile_ms"] > 0) == (s["algo"] == 2) for s in runs[1][1])
+    assert all(s["gpu_ms"] >= s["tile_ms"] > 0 for s in runs[2][1])
 
 
 @pytest.mark.parametrize("world,min_chunks,n_poses,mode,cull", [(2, 4, 12_000, 0, 0), (3, 1, 12_000, 0, 0), (8, 4, 40_000, 0, 0), (3, 4, 9_000, 1, 0), (5, 2, 700, 0, 0),

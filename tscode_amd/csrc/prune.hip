@@ -1,5 +1,6 @@
 // prune.hip -- K3: prune_conformers_rmsd -- the run, its passes, the sharded protocol
 // gfx950 only.  There is deliberately no CPU implementation behind these entry points.
+#include "call.hpp"
 #include "prune_host.hpp"
 
 // --------------------------------------------------------------------------------------------------
@@ -26,19 +27,15 @@ extern "C" __attribute__((visibility("default"))) int tsc_rmsd_pairs(tsc_ctx *c,
     for (int64_t k = 0; k < 2 * n_pairs; ++k)
         TSC_REQUIRE(pairs[k] >= 0 && pairs[k] < n_structs, "pairs[%lld] = %d out of range", (long long)k, pairs[k]);
     if (n_pairs == 0) return 0;
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall call(c);
     double *d_heavy, *d_r, *d_m;
     int32_t *d_pairs;
-    TSC_TRY(upload(c, s, heavy, size_t(n_structs) * h * 3, &d_heavy));
-    TSC_TRY(upload(c, s, pairs, size_t(n_pairs) * 2, &d_pairs));
-    TSC_TRY(s.get(size_t(n_pairs), &d_r));
-    TSC_TRY(s.get(size_t(n_pairs), &d_m));
+    TSC_TRY(call.in(heavy, size_t(n_structs) * h * 3, &d_heavy));
+    TSC_TRY(call.in(pairs, size_t(n_pairs) * 2, &d_pairs));
+    TSC_TRY(call.out(rmsd, size_t(n_pairs), &d_r));
+    TSC_TRY(call.out(maxdev, size_t(n_pairs), &d_m));
     TSC_TRY(tsc_rmsd_pairs_dev(c, d_heavy, n_structs, h, d_pairs, n_pairs, d_r, d_m));
-    TSC_HIP(hipMemcpyAsync(rmsd, d_r, size_t(n_pairs) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(maxdev, d_m, size_t(n_pairs) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return call.finish();
     TSC_API_GUARD_END
 }
 
@@ -47,29 +44,26 @@ extern "C" __attribute__((visibility("default"))) int tsc_screen_mm_values(tsc_c
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(c && D && S && limit_bits && out_scale, "tsc_screen_mm_values: null argument");
     TSC_REQUIRE(n >= 1 && n <= (1 << 20), "n = %lld not supported", (long long)n);
-    DeviceGuard guard(c->device);
-    Scratch s(c);
     float dmax = 0.0f;
     for (int64_t e = 0; e < n * DW; ++e) dmax = std::fabs(D[e]) > dmax || std::isnan(D[e]) ? (std::isnan(D[e]) ? NAN : std::fabs(D[e])) : dmax;
-    unsigned bits;
+    unsigned bits;   // (uploaded from here: declared in front of the call, which waits for the stream before it goes)
     memcpy(&bits, &dmax, sizeof(bits));
     if (std::isnan(dmax)) bits = NONFINITE_BITS;
+    HostCall call(c);
     float *d_D, *d_S;
     unsigned *d_bits;
-    int *d_lim;
+    int32_t *d_lim;
     _Float16 *d_rec;
-    TSC_TRY(upload(c, s, D, size_t(n) * DW, &d_D));
-    TSC_TRY(upload(c, s, &bits, 1, &d_bits));
-    TSC_TRY(s.get(size_t(n) * MM_REC_HALVES, &d_rec));
-    TSC_TRY(s.get(size_t(NFAM) * MM_ROWS * n, &d_S));
-    TSC_TRY(s.get(1, &d_lim));
+    TSC_TRY(call.in(D, size_t(n) * DW, &d_D));
+    TSC_TRY(call.in(&bits, 1, &d_bits));
+    TSC_TRY(call.scratch().get(size_t(n) * MM_REC_HALVES, &d_rec));
+    TSC_TRY(call.out(S, size_t(NFAM) * MM_ROWS * n, &d_S));
+    TSC_TRY(call.out(limit_bits, 1, &d_lim));
     hipLaunchKernelGGL(k_mm_records, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const float *)d_D, n, (const unsigned *)d_bits, d_rec);
     hipLaunchKernelGGL(k_mm_screen_dump, dim3(unsigned(ceil_div<int64_t>(n, MM_STEP))), dim3(64), 0, c->stream, (const _Float16 *)d_rec, int(n), (const unsigned *)d_bits,
                        limit, d_S, d_lim);
     TSC_HIP(hipGetLastError());
-    TSC_HIP(hipMemcpyAsync(S, d_S, size_t(NFAM) * MM_ROWS * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipMemcpyAsync(limit_bits, d_lim, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
+    TSC_TRY(call.finish());
     *out_scale = mm_scale(bits);
     return 0;
     TSC_API_GUARD_END
@@ -244,10 +238,7 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
     if (!rc) rc = palloc(p, 2 * p->bit_words, &p->bits);
     p->dsum_words = p->bit_words / 1024 + 4;  // one summary bit per 1024 cache-view bits, kept right behind the view
     p->n_views = 0;
-    for (int slot = 0; slot < TSC_MAX_PASSES; ++slot) {
-        const bool can_run = int64_t(KS[slot]) == 1 || 20 * int64_t(KS[slot]) < n;  // (tsc_prune_next_pass)
-        p->view_of_slot[slot] = (can_run && mode == 0) ? p->n_views++ : -1;
-    }
+    for (int slot = 0; slot < TSC_MAX_PASSES; ++slot) p->view_of_slot[slot] = (pass_can_run(n, slot) && mode == 0) ? p->n_views++ : -1;
     if (!rc) rc = palloc(p, std::max<size_t>(1, size_t(p->n_views) * (p->bit_words + p->dsum_words)), &p->views);
     if (!rc) rc = palloc(p, TSC_MAX_PASSES, &p->view_pass);
     if (!rc) rc = palloc(p, 1, &p->counters);
@@ -291,7 +282,7 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
         hipStream_t st = c->stream;
         int first_slot = -1;  // the pass tsc_prune_next_pass will hand out first: opened by k_init_run itself
         for (int slot = 0; slot < TSC_MAX_PASSES && first_slot < 0; ++slot)
-            if (int64_t(KS[slot]) == 1 || 20 * int64_t(KS[slot]) < n) first_slot = slot;
+            if (pass_can_run(n, slot)) first_slot = slot;
         p->opened_slot = first_slot;
         InitArgs ia;
         memset(&ia, 0, sizeof(ia));
@@ -359,10 +350,8 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_next_pass(tsc_pr
     *k_out = 0;
     while (p->next_ks < TSC_MAX_PASSES) {
         const int slot = p->next_ks++;
-        const int64_t k = int64_t(KS[slot]);  // int(k): the reference itself fails for float k
-        // count_nonzero(mask) <= n, so a pass with 20 k >= n can never pass the gate of :192; the others are enqueued
-        // and gated on the device
-        if (k == 1 || 20 * k < p->n) {
+        if (pass_can_run(p->n, slot)) {
+            const int64_t k = int64_t(KS[slot]);
             p->cur_k = k;
             p->cur_slot = slot;
             p->local_done = false;
@@ -385,122 +374,301 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_estimate(ts
     TSC_API_GUARD_END
 }
 
-// The pair search of one rank's row tiles of the open pass (step 3 of a pass; steps 1-2 have run).
-// rows_ub: upper bound of the rows of the pass on this device (n; in a rank-partitioned pass the structures of this rank's chunks)
-// rows_now (optional, <= rows_ub): the rows the pass really has, where the host has learnt it (a pass that waited for k_cull_decide): the grid is
-// sized for them; everything the kernels COUNT arrivals by stays with rows_ub, which k_open_rows was launched with
-static int launch_pair_search(tsc_prune *p, int rank, int world, int64_t rows_ub, int64_t rows_now = -1) {
+// ---- what the launches of a pass share ----
+
+// the pair kernel's own start / stop events ride on its dispatch packet (no extra packets in the stream; a hipEventRecord before and
+// after it costs about 4 us each on MI355X).  level: the "pass_timing" from which this kernel is timed
+struct PairEvents {
+    hipEvent_t e0, e1;
+};
+static PairEvents pair_events(const tsc_prune *p, int level) {
+    const bool on = p->ctx->pass_timing >= level;
+    return PairEvents{on ? p->ev[p->cur_slot][1] : nullptr, on ? p->ev[p->cur_slot][2] : nullptr};
+}
+
+// the thresholds of the open run, the same in every argument block that has them (pass_plan.hpp: thresholds)
+template <typename Args>
+static void put_thresholds(const tsc_prune *p, Args &a) {
+    const Thresholds t = thresholds(p->h, p->thr);
+    a.thr = t.thr, a.maxdev_thr = t.maxdev_thr;  // :95
+    a.half_h_thr2 = t.half_h_thr2;
+}
+template <typename Args>
+static void put_screen_thresholds(const tsc_prune *p, Args &a) {
+    const Thresholds t = thresholds(p->h, p->thr);
+    put_thresholds(p, a);
+    a.two_thr2 = t.two_thr2, a.desc_limit = t.desc_limit;
+    a.dmax_bits = p->dmax_bits;
+}
+// rows: the bound the grid was sized for -- tiles of the last block beyond it must leave before they read a stale tile_cmax[] entry and
+// arrive at the pass's counter as a tile that does not exist.  tile_cmax: null in a culled pass, whose tiles lie in another order
+static SieveArgs sieve_args(const tsc_prune *p, int rows, int rank, int world, int seg_cols, const int32_t *tile_cmax) {
+    SieveArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = rows, a.h = p->h;
+    a.tile_begin = rank, a.tile_stride = world, a.seg_cols = seg_cols;
+    put_screen_thresholds(p, a);
+    a.heavy32 = p->heavy32;
+    a.tile_cmax = tile_cmax;
+    a.drain_min = p->ctx->drain_min;
+    return a;
+}
+
+#ifdef TSC_DBG_STAMPS
+// room for 8 time stamps of each of `waves` wavefronts (tools/stamps.py), cleared on the stream
+static int stamp_buffer(tsc_ctx *c, int64_t waves, unsigned long long **dbg) {
+    const size_t bytes = size_t(waves) * 8 * sizeof(unsigned long long);
+    if (c->dbg_bytes < bytes) {
+        if (c->dbg_buf) (void)hipFree(c->dbg_buf);
+        TSC_HIP(hipMalloc(&c->dbg_buf, bytes));
+        c->dbg_bytes = bytes;
+    }
+    TSC_HIP(hipMemsetAsync(c->dbg_buf, 0, bytes, c->stream));
+    c->dbg_waves = waves;
+    *dbg = static_cast<unsigned long long *>(c->dbg_buf);
+    return 0;
+}
+#endif
+
+// ---- the walked pass: the pair search of one rank's row tiles of the open pass, in index order (step 3 of a pass; steps 1-2 have run) ----
+// rows_ub, rows_now: pass_plan.hpp, plan_walked
+static int walked_pass(tsc_prune *p, int rank, int world, int64_t rows_ub, int64_t rows_now = -1) {
     tsc_ctx *c = p->ctx;
     hipStream_t st = c->stream;
-    const int64_t n = p->n, k = p->cur_k;
-    const int slot = p->cur_slot;
-    const int A = int(std::max<int64_t>(rows_ub, 1));
-    PassGeom g{int(n), int(k), int(n / k)};
-    const int64_t longest_chunk = n - (k - 1) * g.cs;
-    // 3. pairs: rows dealt round-robin over ranks in tiles of 16, columns cut into segments for load balance
-    const int n_tiles = ceil_div(A, TILE_ROWS);
-    const int max_range = int(std::min<int64_t>(A, longest_chunk));
-    // a wavefront walks its segment tile by tile: short segments keep the critical path short when a pass has little
-    // work (many small chunks), long ones amortise the per-item setup when it has a lot
-    // (measured on MI355X, tools/sweep.py: 512 columns at 57k structures, 1024 at 126k, 4096 at 483k; "seg_cols" overrides)
-    int seg_cols = c->seg_cols > 0 ? c->seg_cols : (n <= 100000 ? 512 : (n <= 400000 ? 1024 : 4096));
-    while (seg_cols > 256 && max_range < seg_cols * 4) seg_cols /= 2;
-    // the screen on the matrix cores (mm.hpp): one rank, 64 rows per work item and segments of their own length
-    const bool mm = p->algo == ALGO_SIEVE && p->Dh && p->mm64;
-    const bool mm16 = p->algo == ALGO_SIEVE && p->Dh && !p->mm64 && c->sieve_cpl == 2 && c->sieve_trim != 0;
-    if (mm) seg_cols = c->mm_seg_cols > 0 ? c->mm_seg_cols : (max_range >= 2048 ? 1024 : 512);
-    const int n_seg = ceil_div(max_range + 64, seg_cols);  // + 64: a segment starts at the 64-aligned column below r0 + 1
-    const int my_tiles = (n_tiles - rank + world - 1) / world;
-    // (mm: groups of 64 rows dealt round-robin to the ranks; the 16-row matrix-core kernel: two items per workgroup, four where most workgroups are empty)
-    const int mm16_waves = mm16 ? (n_seg <= MM16_LONG_SEGS ? 2 : 4) : 4;
-    const int A_grid = rows_now >= 0 ? int(std::min<int64_t>(std::max<int64_t>(rows_now, 1), A)) : A;
-    const int grid_tiles = (ceil_div(A_grid, TILE_ROWS) - rank + world - 1) / world;
-    dim3 grid(std::max(1, mm ? ceil_div((ceil_div(A_grid, MM_ROWS) - rank + world - 1) / world, MM_WAVES) : ceil_div(std::min(my_tiles, grid_tiles), mm16_waves)), n_seg);
-    // the pair kernel's own start / stop events ride on its dispatch packet (no extra packets in the stream; a
-    // hipEventRecord before and after it costs about 4 us each on MI355X)
-    hipEvent_t e0 = c->pass_timing >= 1 ? p->ev[slot][1] : nullptr, e1 = c->pass_timing >= 1 ? p->ev[slot][2] : nullptr;
+    const PairForm form = pair_form(*c, p->algo, p->Dh != nullptr, p->mm64);
+    const WalkedPlan w = plan_walked(*c, p->n, p->cur_k, rank, world, rows_ub, rows_now, form);
+    const PairEvents ev = pair_events(p, 1);
     if (p->algo == ALGO_TILE) {
         TileArgs a;
         a.ld = p->npad, a.h = p->h;
-        a.tile_begin = rank, a.tile_stride = world, a.seg_cols = seg_cols;
-        a.thr = p->thr, a.maxdev_thr = 2 * p->thr;  // :95
-        a.half_h_thr2 = 0.5 * double(p->h) * p->thr * p->thr;
-        TSC_TRY(launch_rmsd_tile(p->hp, st, grid, e0, e1, (const double *)p->Xr, (const double *)p->Xc, (const double *)p->G, (const int32_t *)p->cend, p->best,
-                                 p->counters, (const PruneState *)p->state, a));
-    } else {
-        SieveArgs a;
-        // (the bound the grid was sized for: tiles of the last block beyond it must leave before they read a stale tile_cmax[] entry
-        // and arrive at the pass's counter as a tile that does not exist)
-        a.n = A, a.h = p->h;
-        a.tile_begin = rank, a.tile_stride = world, a.seg_cols = seg_cols;
-        a.thr = p->thr, a.maxdev_thr = 2 * p->thr;  // :95
-        a.half_h_thr2 = 0.5 * double(p->h) * p->thr * p->thr;
-        a.two_thr2 = p->h >= 4 ? 2.0 * p->thr * p->thr : -1.0;
-        a.dmax_bits = p->dmax_bits, a.desc_limit = double(p->h) * p->thr * p->thr;
-        a.heavy32 = p->heavy32;
-        a.tile_cmax = p->tile_cmax;
-        a.drain_min = c->drain_min;
-        a.dbg = nullptr;
-#ifdef TSC_DBG_STAMPS
-        if (c->dbg_stamp_k == k) {
-            const size_t bytes = size_t(grid.x) * grid.y * 32 * sizeof(unsigned long long);
-            if (c->dbg_bytes < bytes) {
-                if (c->dbg_buf) (void)hipFree(c->dbg_buf);
-                TSC_HIP(hipMalloc(&c->dbg_buf, bytes));
-                c->dbg_bytes = bytes;
-            }
-            TSC_HIP(hipMemsetAsync(c->dbg_buf, 0, bytes, st));
-            c->dbg_waves = int64_t(grid.x) * grid.y * 4;
-            a.dbg = static_cast<unsigned long long *>(c->dbg_buf);
-        }
-#endif
-        FusedApply fa;
-        memset(&fa, 0, sizeof(fa));
-        if (p->cur_fused) {
-            fa.ap = apply_args(p);
-            fa.tile_done = p->tile_done, fa.tickets = &p->tickets->pass, fa.n_tiles = unsigned(ceil_div(A, TILE_ROWS));
-            fa.sc = step_ctx(p, p->cur_range);
-            int nxt = -1;
-            fa.next = next_step_args(p, &nxt);
-            if (!p->cur_range) {
-                p->opened_slot = nxt;
-                p->last_slot = -1;  // closed on the device, by the pair kernel's last tile
-            }
-        }
-        const bool trim = c->sieve_cpl == 2 && c->sieve_trim;
-        if (mm16) {
-            TSC_TRY(launch_rmsd_sieve_mm16(p->cur_fused, a.heavy32 != nullptr, mm16_waves, st, grid, e0, e1, p->heavy, (const int32_t *)p->act, (const double *)p->Gall,
-                                           (const _Float16 *)p->Dh, (const int32_t *)p->cend, p->best, p->counters,
-                                           (const PruneState *)p->state, a, fa));
-            return 0;
-        }
-        if (mm) {
-            TSC_TRY(launch_rmsd_sieve_mm(p->cur_fused, a.heavy32 != nullptr, st, grid, e0, e1, p->heavy, (const int32_t *)p->act, (const double *)p->Gall,
-                                         (const float *)p->Dc, (const _Float16 *)p->Dh, (const int32_t *)p->cend, p->best, p->counters, (const PruneState *)p->state, a, fa));
-            return 0;
-        }
-        // (stage 1 on the float32 copy exists for the default shape of the kernel only)
-        TSC_TRY((p->cur_fused ? launch_rmsd_sieve_fused : launch_rmsd_sieve_plain)(
-            c->sieve_cpl, trim, trim && a.heavy32 != nullptr, st, grid, e0, e1, p->heavy, (const int32_t *)p->act, (const double *)p->Gall, (const float *)p->Dc,
-            (const int32_t *)p->cend, p->best, p->counters, (const PruneState *)p->state, a, fa));
+        a.tile_begin = rank, a.tile_stride = world, a.seg_cols = w.seg_cols;
+        put_thresholds(p, a);
+        TSC_TRY(launch_rmsd_tile(p->hp, st, w.grid, ev.e0, ev.e1, (const double *)p->Xr, (const double *)p->Xc, (const double *)p->G, (const int32_t *)p->cend,
+                                 p->best, p->counters, (const PruneState *)p->state, a));
+        TSC_HIP(hipGetLastError());
+        return 0;
     }
+    SieveArgs a = sieve_args(p, w.rows, rank, world, w.seg_cols, p->tile_cmax);
+#ifdef TSC_DBG_STAMPS
+    if (c->dbg_stamp_k == p->cur_k) TSC_TRY(stamp_buffer(c, int64_t(w.grid.x) * w.grid.y * 4, &a.dbg));
+#endif
+    FusedApply fa;
+    memset(&fa, 0, sizeof(fa));
+    if (p->cur_fused) {
+        fa.ap = apply_args(p);
+        fa.tile_done = p->tile_done, fa.tickets = &p->tickets->pass, fa.n_tiles = unsigned(w.n_tiles);
+        fa.sc = step_ctx(p, p->cur_range);
+        int nxt = -1;
+        fa.next = next_step_args(p, &nxt);
+        if (!p->cur_range) {
+            p->opened_slot = nxt;
+            p->last_slot = -1;  // closed on the device, by the pair kernel's last tile
+        }
+    }
+    const bool trim = c->sieve_cpl == 2 && c->sieve_trim;
+    if (form.mm16) {
+        TSC_TRY(launch_rmsd_sieve_mm16(p->cur_fused, a.heavy32 != nullptr, w.mm16_waves, st, w.grid, ev.e0, ev.e1, p->heavy, (const int32_t *)p->act,
+                                       (const double *)p->Gall, (const _Float16 *)p->Dh, (const int32_t *)p->cend, p->best, p->counters,
+                                       (const PruneState *)p->state, a, fa));
+        return 0;
+    }
+    if (form.mm) {
+        TSC_TRY(launch_rmsd_sieve_mm(p->cur_fused, a.heavy32 != nullptr, st, w.grid, ev.e0, ev.e1, p->heavy, (const int32_t *)p->act, (const double *)p->Gall,
+                                     (const float *)p->Dc, (const _Float16 *)p->Dh, (const int32_t *)p->cend, p->best, p->counters, (const PruneState *)p->state, a,
+                                     fa));
+        return 0;
+    }
+    // (stage 1 on the float32 copy exists for the default shape of the kernel only)
+    TSC_TRY((p->cur_fused ? launch_rmsd_sieve_fused : launch_rmsd_sieve_plain)(
+        c->sieve_cpl, trim, trim && a.heavy32 != nullptr, st, w.grid, ev.e0, ev.e1, p->heavy, (const int32_t *)p->act, (const double *)p->Gall, (const float *)p->Dc,
+        (const int32_t *)p->cend, p->best, p->counters, (const PruneState *)p->state, a, fa));
     TSC_HIP(hipGetLastError());
     return 0;
 }
 
-// The launches of a pass on this device.  range = false: the rows dealt to (rank, world) by tiles, of all chunks (tsc_prune_pass_local).
-// range = true: every row of the chunks that belong to this rank (tsc_prune_pass_range); rank / world are then 0 / 1 for the
-// kernels -- they see an ensemble made of this rank's rows.
+// ---- the chunk-local pass: the whole pass in one launch, a workgroup (or a few) per chunk (local_pass.hpp) ----
+static int local_pass(tsc_prune *p, const PassGeom &g, const PassRows &r, bool range) {
+    const LocalPlan l = plan_local(p->n, p->cur_k, r);
+    LocalPassArgs a;
+    a.h = p->h, a.use_cache = (p->mode == 0);
+    a.nb_regular = l.nb_regular, a.nb_last = l.nb_last;
+    a.c_lo = int(r.c_lo), a.n_reg = l.n_reg;
+    a.exch = range ? p->exch : nullptr;
+    put_screen_thresholds(p, a);
+    int nxt = -1;
+    const StepArgs sa = next_step_args(p, &nxt);
+    // (its own events only at pass_timing 2: level 1 is what a timed region carries for the PAIR kernel's durations, and a pair of
+    // events costs a small pass about 6 us)
+    const PairEvents ev = pair_events(p, 2);
+    TSC_TRY(launch_pass_chunks(p->ctx->stream, unsigned(l.blocks), ev.e0, ev.e1, g, a, p->state, p->mask, p->bits, int(p->bit_words), view_of_open_pass(p), p->heavy,
+                               (const double *)p->Gall, (const float *)p->Dall, later_views(p), p->counters, p->bsum, SCAN_TILE, step_ctx(p, range), sa,
+                               &p->tickets->local));
+    if (!range) {
+        p->opened_slot = nxt;
+        p->last_slot = -1;  // closed on the device
+    }
+    return 0;
+}
+
+// ---- what the culled and the walked pass have in front of them ----
+// 1. per row: which structure it is, its stop column, best[] = none, its descriptor by position (k_open_rows, rmsd.hpp); the coordinates by
+// position for the register-tiled kernel
+static int open_rows(tsc_prune *p, const PassGeom &g, const PassShape &s, bool range) {
+    tsc_ctx *c = p->ctx;
+    hipStream_t st = c->stream;
+    const OpenPlan o = plan_open_rows(s.rows_ub);
+    OpenArgs oa;
+    oa.use_cache = (p->mode == 0), oa.fused = s.fused ? 1 : 0, oa.lds_cap = std::min(c->open_lds_blocks, OPEN_LDS_BLOCKS);
+    oa.view = view_of_open_pass(p), oa.bits = p->bits, oa.bit_words = int(p->bit_words);
+    oa.boff = p->boff, oa.n_blocks = p->n_blocks, oa.block_items = SCAN_TILE;
+    oa.n_tiles = o.n_tiles, oa.tickets = &p->tickets->pass;
+    oa.rank_of = s.culled ? p->rank_of : nullptr;
+    oa.Dh = p->Dh, oa.dmax_bits = p->dmax_bits;
+    oa.dbg = nullptr;
+#ifdef TSC_DBG_STAMPS
+    if (c->dbg_stamp_k == -p->cur_k) TSC_TRY(stamp_buffer(c, int64_t(o.stamp_blocks) * 4, &oa.dbg));  // (a negative k selects k_open_rows of pass k)
+#endif
+    int nxt = -1;
+    const StepArgs sa = s.fused ? next_step_args(p, &nxt) : StepArgs{-1, -1, 0ll, 0, -1};
+    static_assert(SCAN_TILE == 64 * SCAN_BLOCK_WORDS && DW == DESC_WORDS, "k_open_rows");
+    hipLaunchKernelGGL(k_open_rows, dim3(o.blocks), dim3(256), 0, st, g, oa, step_ctx(p, range), sa, p->act, p->cend, p->best, p->tile_cmax, (const float *)p->Dall,
+                       s.need_dc ? p->Dc : nullptr);
+    if (p->algo == ALGO_TILE) {
+        const int hp3 = p->hp * 3;
+        size_t lds = size_t(64) * (hp3 + 1) * sizeof(double);
+        hipLaunchKernelGGL(k_compact_coords, dim3(ceil_div(s.rows_ub, 64)), dim3(256), lds, st, p->heavy, p->h, hp3, p->act, (const PruneState *)p->state, p->Xr,
+                           p->Xc, p->npad, p->G);
+    }
+    return 0;
+}
+
+// ---- the culled pass: the structures laid out along a Morton curve, tile pairs skipped by bounding box (cull.hpp); the verdicts are
+// applied by k_apply_pass behind the pair kernel (tsc_prune_pass_finish), on one rank or several ----
+
+// its buffers, when the first candidate comes up (in front of k_open_rows, which fills rank_of)
+static int cull_buffers(tsc_prune *p) {
+    if (p->morton_order) return 0;
+    const size_t n = size_t(p->n);
+    TSC_TRY(palloc(p, n, &p->morton_order));
+    TSC_TRY(palloc(p, n, &p->rank_of));
+    TSC_TRY(palloc(p, n + 256, &p->crank));
+    TSC_TRY(palloc(p, size_t(CULL_MAX_CHUNKS) + 1, &p->cbase));
+    TSC_TRY(palloc(p, size_t(CULL_MAX_CHUNKS) + 1, &p->cfill));
+    TSC_TRY(palloc(p, (n / CULL_LAYOUT_ITEMS + 2) * CULL_MAX_CHUNKS, &p->blk_cnt));
+    TSC_TRY(palloc(p, (n + 256) * DW, &p->Ds));
+    if (p->Dh && p->mm64) TSC_TRY(palloc(p, (n + 256) * MM_REC_HALVES, &p->Dhs));
+    if (p->Dh && p->mm64) TSC_TRY(palloc(p, n + 256, &p->cstruct));
+    TSC_TRY(palloc(p, (n / CULL_COLS + 2) * CULL_BOX, &p->cbox));
+    TSC_TRY(palloc(p, (n / CULL_COLS + 2) * 8 * CULL_BOX, &p->rbox));
+    return 0;
+}
+
+// once per run: the structures in coarse Morton order of their descriptors -- a stable two-digit radix sort by cell, so that
+// every rank of a sharded run comes to the same order (cull.hpp)
+static int morton_sort(tsc_prune *p) {
+    tsc_ctx *c = p->ctx;
+    hipStream_t st = c->stream;
+    const int64_t n = p->n;
+    Scratch s(c);
+    int32_t *tmp, *blk, *tot;
+    const int n_rb = int(ceil_div<int64_t>(n, 2048));
+    TSC_TRY(s.get(size_t(n), &tmp));
+    TSC_TRY(s.get(size_t(n_rb) * RADIX_BUCKETS, &blk));
+    TSC_TRY(s.get(size_t(RADIX_BUCKETS), &tot));
+    static_assert(CULL_MORTON_BITS * CULL_MORTON_DIMS <= 16, "two 8-bit digits");
+    for (int pass = 0; pass < 2; ++pass) {
+        const int32_t *in = pass == 0 ? nullptr : tmp;
+        int32_t *out = pass == 0 ? tmp : p->morton_order;
+        hipLaunchKernelGGL(k_radix_count, dim3(unsigned(n_rb)), dim3(256), 0, st, (const float *)p->Dall, in, n, (const unsigned *)p->dmax_bits, 8 * pass, blk);
+        hipLaunchKernelGGL(k_radix_scan, dim3(RADIX_BUCKETS), dim3(64), 0, st, n_rb, blk, tot);
+        hipLaunchKernelGGL(k_radix_base, dim3(1), dim3(256), 0, st, tot);
+        hipLaunchKernelGGL(k_radix_scatter, dim3(unsigned(n_rb)), dim3(256), 0, st, (const float *)p->Dall, in, n, (const unsigned *)p->dmax_bits, 8 * pass,
+                           (const int32_t *)blk, (const int32_t *)tot, out);
+    }
+    TSC_HIP(hipGetLastError());
+    p->morton_sorted = true;
+    return 0;
+}
+
+// culled, or walked in index order?  The rows' ranges decide (k_cull_decide); the host waits for the verdict -- a pass this
+// large takes a millisecond or more, the round trip some 20 us.  *rows_now: the pass's rows, which the host learns with it
+static int cull_verdict(tsc_prune *p, const PassGeom &g, bool *run_culled, int64_t *rows_now) {
+    tsc_ctx *c = p->ctx;
+    hipStream_t st = c->stream;
+    volatile int *flag = reinterpret_cast<volatile int *>(static_cast<char *>(c->pinned) + PINNED_FLAG_OFFSET + 64 * size_t(p->flag_slot));
+    *flag = 0;
+    hipLaunchKernelGGL(k_chunk_bases, dim3(unsigned(g.k + 1)), dim3(64), 0, st, g, (const PruneState *)p->state, (const int32_t *)p->boff,
+                       (const unsigned long long *)p->bits, int(p->bit_words), p->n_blocks, p->cbase, p->cfill);
+    hipLaunchKernelGGL(k_cull_decide, dim3(1), dim3(64), 0, st, p->state, (const PassCounters *)p->counters, (const int32_t *)p->cbase, g.k, c->cull == 2 ? 1 : 0,
+                       const_cast<int *>(flag));
+    TSC_HIP(hipStreamSynchronize(st));
+    *run_culled = *flag != 0;
+    *rows_now = flag[1];
+    return 0;
+}
+
+// A candidate pass: *ran = false where the device's verdict is "walked" (nothing but the verdict's two kernels has been enqueued then)
+static int culled_pass(tsc_prune *p, int rank, int world, bool range, const PassGeom &g, const PassShape &s, const PassRows &r, bool *ran, int64_t *rows_now) {
+    tsc_ctx *c = p->ctx;
+    hipStream_t st = c->stream;
+    const int64_t n = p->n, k = p->cur_k;
+    TSC_TRY(cull_verdict(p, g, ran, rows_now));
+    if (!*ran) return 0;
+    if (!p->morton_sorted) TSC_TRY(morton_sort(p));
+    // (the culled pass with the screen on the matrix cores: groups of 64 rows of the layout, dealt to the ranks in runs of tile_block / 4)
+    const bool cull_mm = p->Dhs && p->mm64;
+    p->cur_fused = false;  // rows collect verdicts as columns of other tiles too: the pass is applied behind the pair kernel (k_apply_pass)
+    const int n_lb = int(ceil_div<int64_t>(n, CULL_LAYOUT_ITEMS));
+    const LayoutRange lr{int(r.s_lo), int(r.s_hi)};
+    hipLaunchKernelGGL(k_layout_count, dim3(unsigned(n_lb)), dim3(256), 0, st, g, lr, (const PruneState *)p->state, (const int32_t *)p->morton_order,
+                       (const unsigned long long *)p->bits, int(p->bit_words), p->blk_cnt);
+    hipLaunchKernelGGL(k_layout_scan, dim3(unsigned(k)), dim3(64), 0, st, (const PruneState *)p->state, n_lb, (const int32_t *)p->cbase, p->blk_cnt);
+    hipLaunchKernelGGL(k_layout_scatter, dim3(unsigned(n_lb)), dim3(256), 0, st, g, lr, (const PruneState *)p->state, (const int32_t *)p->morton_order,
+                       (const unsigned long long *)p->bits, int(p->bit_words), (const int32_t *)p->rank_of, (const float *)p->Dc, (const int32_t *)p->blk_cnt, p->Ds,
+                       p->crank, (const _Float16 *)(cull_mm ? p->Dh : nullptr), cull_mm ? p->Dhs : nullptr, cull_mm ? p->cstruct : nullptr);
+    hipLaunchKernelGGL(k_tile_boxes, dim3(unsigned(ceil_div<int64_t>(n, CULL_COLS))), dim3(128), 0, st, (const PruneState *)p->state, (const float *)p->Ds, p->cbox,
+                       p->rbox);
+    const CulledPlan q = plan_culled(*c, s.rows_ub, s.longest_of_rank, rank, world, cull_mm);
+    SieveArgs a = sieve_args(p, s.rows_ub, rank, world, CULL_SEG_COLS, nullptr);
+    const CullArgs ca{p->Ds, p->crank, p->cbase, p->cbox, p->rbox, int(k), q.tile_block, c->cull_xcd};
+    const PairEvents ev = pair_events(p, 1);
+    if (cull_mm) {
+#ifdef TSC_DBG_STAMPS
+        if (c->dbg_stamp_k == k) TSC_TRY(stamp_buffer(c, q.grid_mm * 4, &a.dbg));  // (8 of every 32 words used: one wavefront per workgroup)
+#endif
+        const CullMmArgs cm{p->Dhs, p->cstruct};
+        TSC_TRY(launch_rmsd_sieve_sorted_mm(a.heavy32 != nullptr, st, dim3(unsigned(std::max<int64_t>(1, q.grid_mm))), ev.e0, ev.e1, p->heavy, (const int32_t *)p->act,
+                                            (const double *)p->Gall, (const int32_t *)p->cend, p->best, p->counters, (const PruneState *)p->state, a, ca, cm,
+                                            q.n_groups, q.n_seg_mm));
+    } else {
+        TSC_TRY(launch_rmsd_sieve_sorted(a.heavy32 != nullptr, st, dim3(q.sgrid), ev.e0, ev.e1, p->heavy, (const int32_t *)p->act, (const double *)p->Gall,
+                                         (const int32_t *)p->cend, p->best, p->counters, (const PruneState *)p->state, a, ca, q.my_tiles, q.n_seg));
+    }
+    if (range) {
+        // a partitioned pass is closed by tsc_prune_pass_merge after the exchange: this rank's verdicts go into the exchange buffer
+        // now (k_apply_pass in its noting form), its last block leaves the statistics there
+        int nxt = -1;
+        const StepArgs sa = next_step_args(p, &nxt);
+        const int blocks = int(std::min<int64_t>(ceil_div<int64_t>(s.rows_ub, 256), 512));
+        hipLaunchKernelGGL(k_apply_pass, dim3(blocks), dim3(256), 0, st, apply_args(p), step_ctx(p, true), sa);
+        TSC_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+// The launches of a pass on this device: what every pass has (events, opening the slot on the device where the pass before it has not,
+// the slot flags), then one of the three shapes (pass_plan.hpp: pass_shape).  range = false: the rows dealt to (rank, world) by tiles, of
+// all chunks (tsc_prune_pass_local).  range = true: every row of the chunks that belong to this rank (tsc_prune_pass_range); rank / world
+// are then 0 / 1 for the kernels -- they see an ensemble made of this rank's rows.
 static int pass_launch(tsc_prune *p, int rank, int world, bool range) {
     tsc_ctx *c = p->ctx;
     DeviceGuard guard(c->device);
     hipStream_t st = c->stream;
     const int64_t n = p->n, k = p->cur_k;
     const int slot = p->cur_slot;
-    int64_t c_lo = 0, c_hi = k, s_lo = 0, s_hi = n;
-    if (range) partition_bounds(n, k, p->part_rank, p->part_world, &c_lo, &c_hi, &s_lo, &s_hi);
-    const int A = int(std::max<int64_t>(s_hi - s_lo, 1));  // grids are sized for the upper bound; kernels read the true count from the state block
-    PassGeom g{int(n), int(k), int(n / k)};
+    const PassRows r = range ? partition_bounds(n, k, p->part_rank, p->part_world) : whole_pass(n, k);
+    const PassShape s = pass_shape(*c, n, k, p->algo, p->Dh != nullptr, p->mm64, p->det_desc, world, range, r);
+    const PassGeom g{int(n), int(k), int(n / k)};
     p->cur_range = range;
     for (int i = 0; i < 4; ++i)
         if (!p->ev[slot][i]) TSC_TRY(get_event(c, &p->ev[slot][i]));
@@ -513,232 +681,26 @@ static int pass_launch(tsc_prune *p, int rank, int world, bool range) {
     }
     if (range && p->range_ready_slot != slot)  // no k_pass_merge in front of this pass (the first of a run): which rows are this rank's
         hipLaunchKernelGGL(k_range_open, dim3(1), dim3(64), 0, st, p->state, (const int32_t *)p->boff, (const unsigned long long *)p->bits, int(p->bit_words),
-                           p->n_blocks, int(s_lo), int(s_hi));
+                           p->n_blocks, int(r.s_lo), int(r.s_hi));
     p->last_slot = slot;
     p->slot_used[slot] = true;
-    const int use_cache = (p->mode == 0);
-    // the last chunk takes the remainder (:141-142); of this rank's chunks, in a partitioned pass
-    const int64_t longest_chunk = c_hi == k ? n - (k - 1) * g.cs : g.cs;
-    // Short chunks: the whole pass in one launch, a workgroup (or a few) per chunk (local_pass.hpp)
-    // (measured on MI355X: a block of the chunk-local kernel is a chain of dependent memory round trips, so it wins where
-    // chunks are a few row tiles long -- at 57k structures the passes k = 1000, 500 and 200 take 37, 39 and 50 us instead of
-    // 52-58 -- and loses beyond: k = 100 takes 58 us there against 53 on the two-launch path; "local_max_chunk" moves the limit)
-    // (the longest chunk counts, i.e. the last one with its remainder: at 57 046 structures in 2 000 chunks -- 28 each, 1 074 in the last --
-    // the chunk-local kernel was tried with the long chunk on workgroups of its own: 97 us against 37 for the two launches)
-    p->cur_local = p->algo == ALGO_SIEVE && world == 1 && c->local_pass != 0 && std::max<int64_t>(longest_chunk, g.cs) <= std::min(LP_MAX_ROWS, c->local_max_chunk) &&
-                   c_hi > c_lo;
+    p->cur_local = s.local;
     p->cur_fused = false;
-    if (p->cur_local) {
-        LocalPassArgs a;
-        a.h = p->h, a.use_cache = use_cache;
-        a.nb_regular = std::max(1, ceil_div(ceil_div(g.cs, LP_TI), LP_TILES_PER_BLOCK));
-        a.nb_last = c_hi == k ? std::max(1, ceil_div(ceil_div(int(n - (k - 1) * g.cs), LP_TI), LP_TILES_PER_BLOCK)) : 0;
-        a.c_lo = int(c_lo), a.n_reg = int(std::min<int64_t>(c_hi, k - 1) - c_lo);
-        a.exch = range ? p->exch : nullptr;
-        a.thr = p->thr, a.maxdev_thr = 2 * p->thr;  // :95
-        a.half_h_thr2 = 0.5 * double(p->h) * p->thr * p->thr;
-        a.two_thr2 = p->h >= 4 ? 2.0 * p->thr * p->thr : -1.0;
-        a.desc_limit = double(p->h) * p->thr * p->thr;
-        a.dmax_bits = p->dmax_bits;
-        int nxt = -1;
-        const StepArgs sa = next_step_args(p, &nxt);
-        const int64_t blocks = int64_t(a.n_reg) * a.nb_regular + a.nb_last;
-        // (its own events only at pass_timing 2: level 1 is what a timed region carries for the PAIR kernel's durations, and a pair of
-        // events costs a small pass about 6 us)
-        hipEvent_t e0 = c->pass_timing >= 2 ? p->ev[slot][1] : nullptr, e1 = c->pass_timing >= 2 ? p->ev[slot][2] : nullptr;
-        TSC_TRY(launch_pass_chunks(st, unsigned(blocks), e0, e1, g, a, p->state, p->mask, p->bits, int(p->bit_words), view_of_open_pass(p), p->heavy,
-                                   (const double *)p->Gall, (const float *)p->Dall, later_views(p), p->counters, p->bsum, SCAN_TILE, step_ctx(p, range), sa,
-                                   &p->tickets->local));
-        if (!range) {
-            p->opened_slot = nxt;
-            p->last_slot = -1;  // closed on the device
-        }
+    if (s.local) {
+        TSC_TRY(local_pass(p, g, r, range));
         p->local_done = true;
         return 0;
     }
-    // Large passes: the structures laid out along a Morton curve, tile pairs skipped by bounding box (cull.hpp); the verdicts are
-    // applied by k_apply_pass behind the pair kernel (tsc_prune_pass_finish), on one rank or several
-    // (the pairs a rank gets to look at: its chunks in a partitioned pass, its row tiles in a pass dealt by tiles -- the layout and
-    // the boxes are made by every rank for itself and have to pay for themselves on that share)
-    const double my_pairs = range ? double(s_hi - s_lo) * double(n / k) * 0.5 : double(n) * double(n / k) * 0.5 / double(world);
-    // (row tiles dealt to several ranks: twice the threshold -- every rank lays the whole pass out for an eighth, say, of its tiles;
-    // measured at 1M x 50 and eight ranks the culled k = 2 pass costs a rank 0.82 ms against 0.77 for the walk)
-    // Row tiles of a pass dealt to several ranks (tsc_prune_pass_local / _rows with world > 1): the ranks deal the tiles of ONE sorted layout,
-    // so every rank must hold bit-identical descriptors -- only runs created under "deterministic_basis" may be culled that way; the others
-    // walk the pass in index order, every rank alike.  (Inside a pass partitioned by chunks a rank culls its own chunks with a layout of
-    // its own: no such condition.)
-    const bool shared_layout_ok = world == 1 || range || p->det_desc;
     if (world > 1 && p->auto_tile && !p->det_desc)
         return fail(TSC_ERR_STATE, "tsc_prune_pass_local: this run chose the all-pairs kernel from its own basis estimate; ranks of a sharded run could "
                                    "choose differently -- create the runs under deterministic_basis = 1, or force prune_algo 1 or 2 on every rank");
-    const bool culled = p->algo == ALGO_SIEVE && c->cull != 0 && c->sieve_cpl == 2 && k < CULL_MAX_CHUNKS && shared_layout_ok &&
-                        my_pairs >= c->cull_min_pairs * ((world > 1 && !range) ? 2.0 : 1.0);
-    if (culled && !p->morton_order) {
-        int rc = palloc(p, size_t(n), &p->morton_order);
-        if (!rc) rc = palloc(p, size_t(n), &p->rank_of);
-        if (!rc) rc = palloc(p, size_t(n) + 256, &p->crank);
-        if (!rc) rc = palloc(p, size_t(CULL_MAX_CHUNKS) + 1, &p->cbase);
-        if (!rc) rc = palloc(p, size_t(CULL_MAX_CHUNKS) + 1, &p->cfill);
-        if (!rc) rc = palloc(p, (size_t(n) / CULL_LAYOUT_ITEMS + 2) * CULL_MAX_CHUNKS, &p->blk_cnt);
-        if (!rc) rc = palloc(p, (size_t(n) + 256) * DW, &p->Ds);
-        if (!rc && p->Dh && p->mm64) rc = palloc(p, (size_t(n) + 256) * MM_REC_HALVES, &p->Dhs);
-        if (!rc && p->Dh && p->mm64) rc = palloc(p, size_t(n) + 256, &p->cstruct);
-        if (!rc) rc = palloc(p, (size_t(n) / CULL_COLS + 2) * CULL_BOX, &p->cbox);
-        if (!rc) rc = palloc(p, (size_t(n) / CULL_COLS + 2) * 8 * CULL_BOX, &p->rbox);
-        if (rc) return rc;
-    }
-    // 1. per row: which structure it is, its stop column, best[] = none, its descriptor by position (k_open_rows, rmsd.hpp)
-    p->cur_fused = p->algo == ALGO_SIEVE && world == 1 && (c->fused_apply != 0 || range);
-    {
-        // (the fp32 rows by position: read by the packed-fp32 kernels, by level 2 of the 64-row matrix-core kernels where it is built in, and by a
-        // culled pass's layout)
-        const bool need_dc = !(p->algo == ALGO_SIEVE && p->Dh && (p->mm64 ? !TSC_MM_LEVEL2 : (c->sieve_cpl == 2 && c->sieve_trim != 0)) && !culled);
-        OpenArgs oa;
-        oa.use_cache = use_cache, oa.fused = p->cur_fused ? 1 : 0, oa.lds_cap = std::min(c->open_lds_blocks, OPEN_LDS_BLOCKS);
-        oa.view = view_of_open_pass(p), oa.bits = p->bits, oa.bit_words = int(p->bit_words);
-        oa.boff = p->boff, oa.n_blocks = p->n_blocks, oa.block_items = SCAN_TILE;
-        oa.n_tiles = unsigned(ceil_div(A, 16)), oa.tickets = &p->tickets->pass;
-        oa.rank_of = culled ? p->rank_of : nullptr;
-        oa.Dh = p->Dh, oa.dmax_bits = p->dmax_bits;
-        oa.dbg = nullptr;
-#ifdef TSC_DBG_STAMPS
-        if (c->dbg_stamp_k == -k) {  // (a negative k selects k_open_rows of pass k)
-            const size_t bytes = size_t(ceil_div(ceil_div(A, 16), 4)) * 32 * sizeof(unsigned long long);
-            if (c->dbg_bytes < bytes) {
-                if (c->dbg_buf) (void)hipFree(c->dbg_buf);
-                TSC_HIP(hipMalloc(&c->dbg_buf, bytes));
-                c->dbg_bytes = bytes;
-            }
-            TSC_HIP(hipMemsetAsync(c->dbg_buf, 0, bytes, st));
-            c->dbg_waves = int64_t(ceil_div(ceil_div(A, 16), 4)) * 4;
-            oa.dbg = static_cast<unsigned long long *>(c->dbg_buf);
-        }
-#endif
-        int nxt = -1;
-        const StepArgs sa = p->cur_fused ? next_step_args(p, &nxt) : StepArgs{-1, -1, 0ll, 0, -1};
-        static_assert(SCAN_TILE == 64 * SCAN_BLOCK_WORDS && DW == DESC_WORDS, "k_open_rows");
-        hipLaunchKernelGGL(k_open_rows, dim3(ceil_div(ceil_div(A, 16), 16)), dim3(256), 0, st, g, oa, step_ctx(p, range), sa, p->act, p->cend, p->best, p->tile_cmax,
-                           (const float *)p->Dall, need_dc ? p->Dc : nullptr);
-    }
-    if (p->algo == ALGO_TILE) {
-        const int hp3 = p->hp * 3;
-        size_t lds = size_t(64) * (hp3 + 1) * sizeof(double);
-        hipLaunchKernelGGL(k_compact_coords, dim3(ceil_div(A, 64)), dim3(256), lds, st, p->heavy, p->h, hp3, p->act, (const PruneState *)p->state,
-                           p->Xr, p->Xc, p->npad, p->G);
-    }
-    bool run_culled = false;
+    if (s.culled) TSC_TRY(cull_buffers(p));
+    p->cur_fused = s.fused;
+    TSC_TRY(open_rows(p, g, s, range));
+    bool ran_culled = false;
     int64_t rows_now = -1;   // (the pass's rows, where the host has waited for the device anyway)
-    if (culled) {
-        // culled, or walked in index order?  The rows' ranges decide (k_cull_decide); the host waits for the verdict -- a pass this
-        // large takes a millisecond or more, the round trip some 20 us
-        volatile int *flag = reinterpret_cast<volatile int *>(static_cast<char *>(c->pinned) + PINNED_FLAG_OFFSET + 64 * size_t(p->flag_slot));
-        *flag = 0;
-        hipLaunchKernelGGL(k_chunk_bases, dim3(unsigned(k + 1)), dim3(64), 0, st, g, (const PruneState *)p->state, (const int32_t *)p->boff,
-                           (const unsigned long long *)p->bits, int(p->bit_words), p->n_blocks, p->cbase, p->cfill);
-        hipLaunchKernelGGL(k_cull_decide, dim3(1), dim3(64), 0, st, p->state, (const PassCounters *)p->counters, (const int32_t *)p->cbase, int(k),
-                           c->cull == 2 ? 1 : 0, const_cast<int *>(flag));
-        TSC_HIP(hipStreamSynchronize(st));
-        run_culled = *flag != 0;
-        rows_now = flag[1];
-    }
-    if (run_culled && !p->morton_sorted) {
-        // once per run: the structures in coarse Morton order of their descriptors -- a stable two-digit radix sort by cell, so that
-        // every rank of a sharded run comes to the same order (cull.hpp)
-        Scratch s(c);
-        int32_t *tmp, *blk, *tot;
-        const int n_rb = int(ceil_div<int64_t>(n, 2048));
-        TSC_TRY(s.get(size_t(n), &tmp));
-        TSC_TRY(s.get(size_t(n_rb) * RADIX_BUCKETS, &blk));
-        TSC_TRY(s.get(size_t(RADIX_BUCKETS), &tot));
-        static_assert(CULL_MORTON_BITS * CULL_MORTON_DIMS <= 16, "two 8-bit digits");
-        for (int pass = 0; pass < 2; ++pass) {
-            const int32_t *in = pass == 0 ? nullptr : tmp;
-            int32_t *out = pass == 0 ? tmp : p->morton_order;
-            hipLaunchKernelGGL(k_radix_count, dim3(unsigned(n_rb)), dim3(256), 0, st, (const float *)p->Dall, in, n, (const unsigned *)p->dmax_bits, 8 * pass, blk);
-            hipLaunchKernelGGL(k_radix_scan, dim3(RADIX_BUCKETS), dim3(64), 0, st, n_rb, blk, tot);
-            hipLaunchKernelGGL(k_radix_base, dim3(1), dim3(256), 0, st, tot);
-            hipLaunchKernelGGL(k_radix_scatter, dim3(unsigned(n_rb)), dim3(256), 0, st, (const float *)p->Dall, in, n, (const unsigned *)p->dmax_bits, 8 * pass,
-                               (const int32_t *)blk, (const int32_t *)tot, out);
-        }
-        TSC_HIP(hipGetLastError());
-        p->morton_sorted = true;
-    }
-    // (the culled pass with the screen on the matrix cores: one rank's own pass -- row tiles of a layout dealt to several ranks keep the
-    // kernel of cull.hpp, whose items are single row tiles)
-    const bool cull_mm = run_culled && p->Dhs && p->mm64;
-    if (run_culled) {
-        p->cur_fused = false;  // rows collect verdicts as columns of other tiles too: the pass is applied behind the pair kernel (k_apply_pass)
-        const int n_lb = int(ceil_div<int64_t>(n, CULL_LAYOUT_ITEMS));
-        const LayoutRange lr{int(s_lo), int(s_hi)};
-        hipLaunchKernelGGL(k_layout_count, dim3(unsigned(n_lb)), dim3(256), 0, st, g, lr, (const PruneState *)p->state, (const int32_t *)p->morton_order,
-                           (const unsigned long long *)p->bits, int(p->bit_words), p->blk_cnt);
-        hipLaunchKernelGGL(k_layout_scan, dim3(unsigned(k)), dim3(64), 0, st, (const PruneState *)p->state, n_lb, (const int32_t *)p->cbase, p->blk_cnt);
-        hipLaunchKernelGGL(k_layout_scatter, dim3(unsigned(n_lb)), dim3(256), 0, st, g, lr, (const PruneState *)p->state, (const int32_t *)p->morton_order,
-                           (const unsigned long long *)p->bits, int(p->bit_words), (const int32_t *)p->rank_of, (const float *)p->Dc,
-                           (const int32_t *)p->blk_cnt, p->Ds, p->crank, (const _Float16 *)(cull_mm ? p->Dh : nullptr), cull_mm ? p->Dhs : nullptr, cull_mm ? p->cstruct : nullptr);
-        hipLaunchKernelGGL(k_tile_boxes, dim3(unsigned(ceil_div<int64_t>(n, CULL_COLS))), dim3(128), 0, st, (const PruneState *)p->state, (const float *)p->Ds,
-                           p->cbox, p->rbox);
-        SieveArgs a;
-        memset(&a, 0, sizeof(a));
-        a.n = A, a.h = p->h;
-        a.tile_begin = rank, a.tile_stride = world, a.seg_cols = 4096;
-        a.thr = p->thr, a.maxdev_thr = 2 * p->thr;  // :95
-        a.half_h_thr2 = 0.5 * double(p->h) * p->thr * p->thr;
-        a.two_thr2 = p->h >= 4 ? 2.0 * p->thr * p->thr : -1.0;
-        a.dmax_bits = p->dmax_bits, a.desc_limit = double(p->h) * p->thr * p->thr;
-        a.heavy32 = p->heavy32;
-        a.drain_min = c->drain_min;
-        const int tb = world > 1 ? std::max(1, c->cull_tile_block) : 1;
-        CullArgs ca{p->Ds, p->crank, p->cbase, p->cbox, p->rbox, int(k), tb, c->cull_xcd};
-        const int n_tiles = ceil_div(A, TILE_ROWS);
-        // (slots of this rank: one by one, or whole runs of tb tiles -- an upper bound; slots beyond the last tile leave at once)
-        const int my_tiles = tb <= 1 ? (n_tiles - rank + world - 1) / world : (n_tiles / (tb * world) + 1) * tb;
-        // columns of a row tile: from its own 128-aligned position to the end of its (last row's) chunk -- a chunk and a tile more at most
-        const int n_seg = ceil_div(int(std::min<int64_t>(A, longest_chunk)) + 2 * CULL_COLS, a.seg_cols);
-        hipEvent_t e0 = c->pass_timing >= 1 ? p->ev[slot][1] : nullptr, e1 = c->pass_timing >= 1 ? p->ev[slot][2] : nullptr;
-        const int64_t items = int64_t(ceil_div(my_tiles, 4)) * n_seg;
-        // ("cull_xcd": one work item per workgroup, runs of row groups keyed to XCDs -- 8 XCDs x segments x the runs an XCD holds of a segment)
-        const int64_t xitems = int64_t(8) * n_seg * ceil_div(ceil_div(ceil_div(my_tiles, 4), CULL_XCD_RUN), 8) * CULL_XCD_RUN;
-        const dim3 sgrid(unsigned(std::max<int64_t>(1, c->cull_xcd ? xitems : std::min<int64_t>(items, c->cull_grid))));
-        if (cull_mm) {
-            // (one wavefront per workgroup; several ranks: this rank's share of the groups, in runs of tile_block / 4 -- an upper bound)
-            const int all_groups = ceil_div(A, MM_ROWS), tbg = std::max(1, tb / 4);
-            const int n_groups = world <= 1 ? all_groups : (all_groups / (tbg * world) + 1) * tbg, wgs = n_groups;
-            const int n_seg_mm = ceil_div(int(std::min<int64_t>(A, longest_chunk)) + 2 * CULL_COLS, CMM_SEG);
-            const int64_t grid_mm = c->cull_xcd ? int64_t(8) * n_seg_mm * ceil_div(ceil_div(wgs, CULL_XCD_RUN), 8) * CULL_XCD_RUN : int64_t(wgs) * n_seg_mm;
-#ifdef TSC_DBG_STAMPS
-            if (c->dbg_stamp_k == k) {
-                const size_t bytes = size_t(grid_mm) * 32 * sizeof(unsigned long long);
-                if (c->dbg_bytes < bytes) {
-                    if (c->dbg_buf) (void)hipFree(c->dbg_buf);
-                    TSC_HIP(hipMalloc(&c->dbg_buf, bytes));
-                    c->dbg_bytes = bytes;
-                }
-                TSC_HIP(hipMemsetAsync(c->dbg_buf, 0, bytes, st));
-                c->dbg_waves = grid_mm * 4;   // (8 of every 32 words used: one wavefront per workgroup)
-                a.dbg = static_cast<unsigned long long *>(c->dbg_buf);
-            }
-#endif
-            CullMmArgs cm{p->Dhs, p->cstruct};
-            TSC_TRY(launch_rmsd_sieve_sorted_mm(a.heavy32 != nullptr, st, dim3(unsigned(std::max<int64_t>(1, grid_mm))), e0, e1, p->heavy, (const int32_t *)p->act,
-                                                (const double *)p->Gall, (const int32_t *)p->cend, p->best, p->counters, (const PruneState *)p->state, a, ca, cm,
-                                                n_groups, n_seg_mm));
-        } else
-        TSC_TRY(launch_rmsd_sieve_sorted(a.heavy32 != nullptr, st, sgrid, e0, e1, p->heavy, (const int32_t *)p->act, (const double *)p->Gall, (const int32_t *)p->cend,
-                                         p->best, p->counters, (const PruneState *)p->state, a, ca, my_tiles, n_seg));
-        if (range) {
-            // a partitioned pass is closed by tsc_prune_pass_merge after the exchange: this rank's verdicts go into the exchange buffer
-            // now (k_apply_pass in its noting form), its last block leaves the statistics there
-            int nxt = -1;
-            const StepArgs sa2 = next_step_args(p, &nxt);
-            const int blocks = int(std::min<int64_t>(ceil_div<int64_t>(A, 256), 512));
-            hipLaunchKernelGGL(k_apply_pass, dim3(blocks), dim3(256), 0, st, apply_args(p), step_ctx(p, true), sa2);
-            TSC_HIP(hipGetLastError());
-        }
-        p->local_done = true;
-        return 0;
-    }
-    TSC_TRY(launch_pair_search(p, rank, world, A, rows_now));
+    if (s.culled) TSC_TRY(culled_pass(p, rank, world, range, g, s, r, &ran_culled, &rows_now));
+    if (!ran_culled) TSC_TRY(walked_pass(p, rank, world, s.rows_ub, rows_now));
     p->local_done = true;
     return 0;
 }
@@ -762,7 +724,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_local(tsc_p
 static int64_t views_words_of(int64_t n, int mode) {
     if (mode != 0) return 0;
     int n_views = 0;
-    for (int slot = 0; slot < TSC_MAX_PASSES; ++slot) n_views += (int64_t(KS[slot]) == 1 || 20 * int64_t(KS[slot]) < n) ? 1 : 0;
+    for (int slot = 0; slot < TSC_MAX_PASSES; ++slot) n_views += pass_can_run(n, slot) ? 1 : 0;
     const int64_t bit_words = n / 64 + 40;
     return int64_t(n_views) * (bit_words + bit_words / 1024 + 4);
 }
@@ -824,9 +786,8 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_merge(tsc_p
     ma.n = int(p->n), ma.bit_words = int(p->bit_words), ma.n_blocks = p->n_blocks, ma.bits = p->bits, ma.exch = p->exch, ma.mask = p->mask;
     ma.next_s_lo = ma.next_s_hi = -1;
     if (nxt >= 0 && pass_is_partitioned(p, int64_t(KS[nxt]))) {
-        int64_t c_lo, c_hi, s_lo, s_hi;
-        partition_bounds(p->n, int64_t(KS[nxt]), p->part_rank, p->part_world, &c_lo, &c_hi, &s_lo, &s_hi);
-        ma.next_s_lo = int(s_lo), ma.next_s_hi = int(s_hi);
+        const PassRows next = partition_bounds(p->n, int64_t(KS[nxt]), p->part_rank, p->part_world);
+        ma.next_s_lo = int(next.s_lo), ma.next_s_hi = int(next.s_hi);
         p->range_ready_slot = nxt;
     }
     hipLaunchKernelGGL(k_pass_merge, dim3(1), dim3(1024), 0, c->stream, ma, step_ctx(p), sa);
@@ -883,7 +844,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_rows(tsc_pr
     if (p->cur_k == 0 || !p->local_done || p->cur_local || p->cur_fused)
         return fail(TSC_ERR_STATE, "tsc_prune_pass_rows: needs an open pass whose tsc_prune_pass_local ran with world_size > 1");
     DeviceGuard guard(p->ctx->device);
-    return launch_pair_search(p, rank, world, p->n);
+    return walked_pass(p, rank, world, p->n);
     TSC_API_GUARD_END
 }
 
@@ -1140,16 +1101,13 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_rmsd(tsc_ctx *c,
         if (n_passes) *n_passes = 0;
         return 0;
     }
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall call(c);
     double *d_heavy;
     uint8_t *d_mask;
-    TSC_TRY(upload(c, s, heavy, size_t(n) * h * 3, &d_heavy));
-    TSC_TRY(s.get(size_t(n), &d_mask));
+    TSC_TRY(call.in(heavy, size_t(n) * h * 3, &d_heavy));
+    TSC_TRY(call.out(mask, size_t(n), &d_mask));
     TSC_TRY(tsc_prune_rmsd_dev(c, d_heavy, n, h, rmsd_thr, mode, d_mask, stats, n_passes));
-    TSC_HIP(hipMemcpyAsync(mask, d_mask, size_t(n), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return call.finish();
     TSC_API_GUARD_END
 }
 
@@ -1166,18 +1124,15 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_structures(tsc_c
         if (n_passes) *n_passes = 0;
         return 0;
     }
-    DeviceGuard guard(c->device);
-    Scratch s(c);
+    HostCall call(c);
     double *d_all, *d_heavy;
     uint8_t *d_mask;
-    TSC_TRY(upload(c, s, structures, size_t(n) * n_atoms * 3, &d_all));
-    TSC_TRY(s.get(size_t(n) * n_heavy * 3, &d_heavy));
-    TSC_TRY(s.get(size_t(n), &d_mask));
+    TSC_TRY(call.in(structures, size_t(n) * n_atoms * 3, &d_all));
+    TSC_TRY(call.scratch().get(size_t(n) * n_heavy * 3, &d_heavy));
+    TSC_TRY(call.out(mask, size_t(n), &d_mask));
     TSC_TRY(tsc_gather_heavy_dev(c, d_all, nullptr, n, n_atoms, heavy_idx, n_heavy, d_heavy, nullptr));
     TSC_TRY(tsc_prune_rmsd_dev(c, d_heavy, n, n_heavy, rmsd_thr, mode, d_mask, stats, n_passes));
-    TSC_HIP(hipMemcpyAsync(mask, d_mask, size_t(n), hipMemcpyDeviceToHost, c->stream));
-    TSC_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return call.finish();
     TSC_API_GUARD_END
 }
 

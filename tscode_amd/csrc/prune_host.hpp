@@ -2,13 +2,8 @@
 // units of their own (pairs_tile.hip, pairs_sieve.hip, pairs_sorted.hip: the template instantiations are most of the library's build time).
 #pragma once
 
-#include "host.hpp"
-#include "rmsd.hpp"
+#include "pass_plan.hpp"
 #include "scan.hpp"
-#include "local_pass.hpp"
-#include "cull.hpp"
-#include "mm.hpp"
-#include "cull_mm.hpp"
 
 // --------------------------------------------------------------------------------------------------
 // K3: prune_conformers_rmsd
@@ -21,6 +16,13 @@
 static const double KS[TSC_MAX_PASSES] = {5e5, 2e5, 1e5, 5e4, 2e4, 1e4, 5000, 2000, 1000, 500, 200, 100, 50, 20, 10, 5, 2, 1};  // :186-188
 
 static_assert(MAX_SLOTS == TSC_MAX_PASSES, "one cache view per schedule slot");
+
+// Can the pass of schedule slot `slot` ever run on n structures?  count_nonzero(mask) <= n, so a pass with 20 k >= n can never pass the
+// gate of :192; the others are enqueued and gated on the device.
+static inline bool pass_can_run(int64_t n, int slot) {
+    const int64_t k = int64_t(KS[slot]);  // int(k): the reference itself fails for float k
+    return k == 1 || 20 * k < n;
+}
 
 struct tsc_prune {
     tsc_ctx *ctx = nullptr;
@@ -105,13 +107,8 @@ static int palloc(tsc_prune *p, size_t count, T **out) {
 // finishes a pass also closes it and opens this one on the device.
 static inline StepArgs next_step_args(const tsc_prune *p, int *next_slot) {
     int nxt = -1;
-    for (int s = p->next_ks; s < TSC_MAX_PASSES; ++s) {
-        const int64_t k = int64_t(KS[s]);
-        if (k == 1 || 20 * k < p->n) {
-            nxt = s;
-            break;
-        }
-    }
+    for (int s = p->next_ks; s < TSC_MAX_PASSES && nxt < 0; ++s)
+        if (pass_can_run(p->n, s)) nxt = s;
     *next_slot = nxt;
     return StepArgs{p->cur_slot, nxt, nxt >= 0 ? (long long)KS[nxt] : 0ll, p->algo, p->cur_local ? ALGO_LOCAL : -1};
 }
@@ -123,14 +120,6 @@ static inline StepCtx step_ctx(const tsc_prune *p, bool range_close = false) {
                    int(sizeof(*p->tickets) / 128), range_close ? p->exch + p->bit_words : nullptr};
 }
 
-// Chunks [c_lo, c_hi) of a pass of k chunks that START inside rank's block [n rank / world, n (rank + 1) / world) of the
-// structure axis, and the structures [s_lo, s_hi) they cover (the last chunk of the pass runs to n, rmsd_pruning.py:141-144).
-static inline void partition_bounds(int64_t n, int64_t k, int rank, int world, int64_t *c_lo, int64_t *c_hi, int64_t *s_lo, int64_t *s_hi) {
-    const int64_t cs = n / k;
-    auto first_chunk = [&](int r) { return r <= 0 ? int64_t(0) : (r >= world ? k : std::min<int64_t>(ceil_div<int64_t>(n * r / world, cs), k)); };
-    *c_lo = first_chunk(rank), *c_hi = first_chunk(rank + 1);
-    *s_lo = *c_lo < k ? *c_lo * cs : n, *s_hi = *c_hi < k ? *c_hi * cs : n;
-}
 static inline bool pass_is_partitioned(const tsc_prune *p, int64_t k) {
     return p->part_world > 1 && p->exch && p->algo == ALGO_SIEVE && k >= int64_t(p->part_min_chunks) * p->part_world;
 }
