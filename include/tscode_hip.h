@@ -806,6 +806,77 @@ int tsc_orbitals_dev(tsc_ctx *ctx, const double *coords, int64_t n_conf, int n_a
                      uint8_t *sigmatropic, double *pivot, double *meanpoint, int8_t *lobe_index, uint8_t *n_pivots);
 int tsc_orbitals_timings(tsc_ctx *ctx, float *ms);
 
+/* Hydrogen bonds and the search graph of a conformational search, for a whole ensemble per call (csrc/torsions.hpp), one wavefront
+ * per structure.
+ *   replaces   _get_hydrogen_bonds      tscode/torsion_module.py:233-299 (fragments=None, or the connected components of the graph)
+ *              the graph set-up and the segmentation verdict of csearch, tscode/torsion_module.py:559-606
+ * The search graph starts as bonds U extra.  The NEIGHBOUR LIST of an atom is its bonded atoms in ascending index, then its partners
+ * from `extra` in the order of `extra`; an edge that already exists keeps its first position.
+ * Hetero pairs (i1 < i2, in index order) QUALIFY iff d_min < sqrt(dx dx + dy dy + dz dz) < d_max, both strictly, in fp64 with the
+ * reference's roundings (dx dx + dy dy + dz dz formed without fused multiply-add and compared with the squared bounds that give the
+ * verdicts of sqrt-then-compare).  The candidate hydrogens of a pair are the hydrogen neighbours of i1 in list order, then those of i2.
+ * With u = (r_i2 - r_i1) / |r_i2 - r_i1|, v1 = r_H - r_i1, v2 = r_H - r_i2: alfa is the angle between v1 and u when v1.u < v2.(-u), else
+ * the angle between v2 and -u (degrees, arccos of the clipped dot product of the two normalised vectors).  The FIRST hydrogen with
+ * alfa < max_angle ends the pair's search and appends the sorted pair (H, i2) when |v1| < |v2|, else (H, i1).  Output order: by hetero
+ * pair, i1 then i2.
+ *   mode 0 (keep_hb=True)   every hetero pair is searched.
+ *   mode 1 (keep_hb=False)  a search only where bonds U extra has more than one connected component, and then only of the pairs whose two
+ *                           hetero atoms lie in different components (:593).
+ * The pairs found are then added as edges.  status[s] = 1 (segmented: the reference raises SegmentedGraphError) iff the graph still has
+ * more than one component -- which covers mode 1 with a segmented graph and no pair found -- else 0.
+ *   coords      f64[n_structs, n_atoms, 3]; n_atoms 1 .. 512.  Non-finite coordinates are not refused: such an atom is in no pair.
+ *   hetero      u8[n_atoms]: non-zero for N and O.  hydrogen u8[n_atoms]: non-zero for H.  No atom may carry both.
+ *   bonds       u64[n_structs, n_atoms, W], W = ceil(n_atoms / 64): the strict upper triangle as tsc_bond_delta writes adj; bits at or
+ *               left of the diagonal and behind the last atom are ignored.
+ *   extra       i32[n_structs, n_extra, 2] or NULL with n_extra == 0 (0 .. 64): the constraint pairs; a pair that holds -1, or twice the
+ *               same atom, is an unused slot.
+ *   hb          i32[n_structs, max_hb, 2]: the pairs, lower index first.  n_hb i32[n_structs]: the TRUE count; where it exceeds max_hb the
+ *               first max_hb pairs were written and the caller calls again with more slots.  Nothing is written behind slot max_hb - 1;
+ *               the host-array form returns -1 in the slots behind a structure's pairs, the _dev form leaves them as they were.
+ *   status      u8[n_structs].  Optional (NULL: not wanted): n_components_before i32[n_structs] (of bonds U extra) and graph
+ *               u64[n_structs, n_atoms, W], the strict upper triangle of bonds U extra U hb (all pairs found, also those behind max_hb).
+ * tsc_hbonds takes host arrays.  tsc_hbonds_dev: coords, bonds, extra and every output are device pointers, hetero and hydrogen host
+ * pointers; an extra index outside -1 .. n_atoms-1 cannot be refused there and makes its pair an unused slot; the call is enqueued on the
+ * context's stream.
+ * Refused with TSC_ERR_INVALID before any launch: null required pointers, n_atoms outside 1 .. 512, n_extra outside 0 .. 64,
+ * max_hb < 0, a mode other than 0 and 1, an atom flagged both ways, an extra index >= n_atoms or < -1 (host arrays), a non-finite
+ * threshold, d_min >= d_max.  n_structs == 0 succeeds and writes nothing.
+ *
+ * Three reachability answers per (search graph, candidate torsion) (csrc/torsions.hpp), TOR_CHUNK torsions of one graph per wavefront.
+ *   replaces   Torsion.in_cycle         tscode/torsion_module.py:54-61   (nx.has_path)
+ *              Torsion.sort_torsion     tscode/torsion_module.py:120-132 (one nx.has_path per constrained atom)
+ *              _get_rotation_mask       tscode/torsion_module.py:301-325 (nx.shortest_path)
+ * Per graph g and torsion (i1, i2, i3, i4) of torsions[set_off[g] .. set_off[g+1]), every search in the graph WITHOUT the edge i2 - i3:
+ *   in_cycle  = i4 is reachable from i1.
+ *   reversed  = an ODD number of entries of constrained[g] (duplicates counted) are reachable from i2: the reference reverses the tuple
+ *               once per reachable entry and always tests from the original i2.
+ *   mask      with (a, b, c, _) the tuple after that reversal: the atoms reachable from a; inverted over the n_atoms atoms when more than
+ *               n_atoms / 2 (integer division) are; then mask[b] = 0.
+ *   graph        u64[n_graphs, n_atoms, W], laid out as above.
+ *   torsions     i32[T_total, 4]; set_off i32[n_graphs + 1] ascending from 0 -- a HOST pointer in both forms.
+ *   constrained  i32[n_graphs, n_con] or NULL with n_con == 0; -1 = unused slot.
+ *   flags        u8[T_total]: bit 0 in_cycle, bit 1 reversed.  masks u8[T_total, n_atoms], zero where in_cycle.
+ * tsc_torsion_reach takes host arrays.  tsc_torsion_reach_dev: graph, torsions, constrained, flags and masks are device pointers; a
+ * torsion that the host form would refuse gets flags 0x80 and a zero mask there, a constrained entry outside 0 .. n_atoms-1 is an unused
+ * slot; the call waits for the stream.
+ * Refused with TSC_ERR_INVALID before any launch: null required pointers, n_atoms outside 1 .. 512, n_graphs < 0, n_con < 0, a set_off
+ * that does not start at 0 or decreases, and (host arrays) a torsion index outside 0 .. n_atoms-1, i2 == i3, a constrained entry
+ * >= n_atoms or < -1.  n_graphs == 0 or T_total == 0 succeeds and writes nothing.
+ *   tsc_torsions_timings  under the context option "pass_timing" >= 1 the calls time their kernel with events (and synchronise for it):
+ *                         ms2[0] = the hydrogen-bond kernel, ms2[1] = the reachability kernel of the calling thread's latest calls, -1
+ *                         where none was taken. */
+int tsc_hbonds(tsc_ctx *ctx, const double *coords, int64_t n_structs, int n_atoms, const uint8_t *hetero, const uint8_t *hydrogen,
+               const uint64_t *bonds, const int32_t *extra, int n_extra, double d_min, double d_max, double max_angle, int mode, int max_hb,
+               int32_t *hb, int32_t *n_hb, uint8_t *status, int32_t *n_components_before, uint64_t *graph);
+int tsc_hbonds_dev(tsc_ctx *ctx, const double *coords, int64_t n_structs, int n_atoms, const uint8_t *hetero, const uint8_t *hydrogen,
+                   const uint64_t *bonds, const int32_t *extra, int n_extra, double d_min, double d_max, double max_angle, int mode,
+                   int max_hb, int32_t *hb, int32_t *n_hb, uint8_t *status, int32_t *n_components_before, uint64_t *graph);
+int tsc_torsion_reach(tsc_ctx *ctx, const uint64_t *graph, int n_graphs, int n_atoms, const int32_t *torsions, const int32_t *set_off,
+                      const int32_t *constrained, int n_con, uint8_t *flags, uint8_t *masks);
+int tsc_torsion_reach_dev(tsc_ctx *ctx, const uint64_t *graph, int n_graphs, int n_atoms, const int32_t *torsions, const int32_t *set_off,
+                          const int32_t *constrained, int n_con, uint8_t *flags, uint8_t *masks);
+int tsc_torsions_timings(tsc_ctx *ctx, float *ms2);
+
 #ifdef __cplusplus
 }
 #endif

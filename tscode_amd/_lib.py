@@ -167,6 +167,13 @@ _SIGNATURES = {
     "tsc_orbitals": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, C.c_int] + [_vp] * 9),
     "tsc_orbitals_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, C.c_int] + [_vp] * 9),
     "tsc_orbitals_timings": (C.c_int, [_vp, c_f32p]),
+    "tsc_hbonds": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int]
+                   + [_vp] * 5),
+    "tsc_hbonds_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int]
+                       + [_vp] * 5),
+    "tsc_torsion_reach": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]),
+    "tsc_torsion_reach_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]),
+    "tsc_torsions_timings": (C.c_int, [_vp, c_f32p]),
     "tsc_pipeline_dev": (C.c_int, [_vp, _vp, c_i64p, c_i32p, c_i32p, C.c_int, _vp, _vp, _vp, C.c_int64, c_i32p, C.c_int,
                                    C.c_double, C.c_int64, C.c_double, C.c_int, _vp, _vp, _vp, _vp, c_i64p, c_i64p,
                                    C.POINTER(PassStats), C.POINTER(C.c_int), c_f32p]),

@@ -544,6 +544,65 @@ class Engine:
         """tsc_topology_timings: the kernel time of this thread's latest bond_delta / bond_delta_dev under set_option("pass_timing", 1)."""
         return self._kernel_ms(self.lib.tsc_topology_timings)
 
+    # ---- hydrogen bonds and torsion reachability ------------------------------------------------
+    def hbonds(self, coords, hetero, hydrogen, bonds, extra=None, d_min=2.5, d_max=3.3, max_angle=45.0, mode=0, max_hb=8, want_graph=False):
+        """tsc_hbonds on host arrays (include/tscode_hip.h): coords f64[S, n, 3], hetero / hydrogen u8[n], bonds u64[S, n, W], extra
+        i32[S, E, 2] | None.  Returns {"hb": i32[S, max_hb, 2] (-1 behind a structure's pairs), "n_hb": i32[S], "status": u8[S],
+        "n_components_before": i32[S]} plus "graph" u64[S, n, W] (want_graph)."""
+        coords = np.ascontiguousarray(coords, dtype=np.float64)
+        S, n = coords.shape[0], coords.shape[1]
+        hetero, hydrogen = np.ascontiguousarray(hetero, dtype=np.uint8), np.ascontiguousarray(hydrogen, dtype=np.uint8)
+        bonds = np.ascontiguousarray(bonds, dtype=np.uint64)
+        extra = None if extra is None else np.ascontiguousarray(extra, dtype=np.int32)
+        n_extra = 0 if extra is None else int(extra.shape[1])
+        hb = np.full((S, max(int(max_hb), 0), 2), -1, dtype=np.int32)
+        n_hb, status, before = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.uint8), np.zeros(S, dtype=np.int32)
+        graph = np.zeros((S, n, (n + 63) // 64), dtype=np.uint64) if want_graph else None
+        check(self.lib.tsc_hbonds(self._h, ptr(coords), C.c_int64(S), C.c_int(n), ptr(hetero), ptr(hydrogen), ptr(bonds),
+                                  ptr(extra if n_extra else None), C.c_int(n_extra), C.c_double(d_min), C.c_double(d_max), C.c_double(max_angle),
+                                  C.c_int(int(mode)), C.c_int(int(max_hb)), ptr(hb if hb.size else None), ptr(n_hb), ptr(status), ptr(before),
+                                  ptr(graph)))
+        out = {"hb": hb, "n_hb": n_hb, "status": status, "n_components_before": before}
+        if want_graph:
+            out["graph"] = graph
+        return out
+
+    def hbonds_dev(self, coords, n_structs, n_atoms, hetero, hydrogen, bonds, extra, n_extra, d_min, d_max, max_angle, mode, max_hb, hb, n_hb,
+                   status, n_components_before=None, graph=None):
+        """tsc_hbonds_dev: coords, bonds, extra and the outputs on the device, asynchronous on the engine's stream; hetero and hydrogen
+        u8[n] NumPy arrays."""
+        hetero, hydrogen = np.ascontiguousarray(hetero, dtype=np.uint8), np.ascontiguousarray(hydrogen, dtype=np.uint8)
+        check(self.lib.tsc_hbonds_dev(self._h, ptr(coords), C.c_int64(n_structs), C.c_int(n_atoms), ptr(hetero), ptr(hydrogen), ptr(bonds),
+                                      ptr(extra), C.c_int(n_extra), C.c_double(d_min), C.c_double(d_max), C.c_double(max_angle), C.c_int(int(mode)),
+                                      C.c_int(int(max_hb)), ptr(hb), ptr(n_hb), ptr(status), ptr(n_components_before), ptr(graph)))
+
+    def torsion_reach(self, graph, torsions, set_off, constrained=None):
+        """tsc_torsion_reach on host arrays: graph u64[G, n, W], torsions i32[T, 4], set_off i32[G + 1], constrained i32[G, n_con] | None.
+        Returns (flags u8[T]: bit 0 in_cycle, bit 1 reversed; masks u8[T, n])."""
+        graph = np.ascontiguousarray(graph, dtype=np.uint64)
+        G, n = graph.shape[0], graph.shape[1]
+        torsions = np.ascontiguousarray(torsions, dtype=np.int32).reshape(-1, 4)
+        set_off = np.ascontiguousarray(set_off, dtype=np.int32)
+        constrained = None if constrained is None else np.ascontiguousarray(constrained, dtype=np.int32).reshape(G, -1)
+        n_con = 0 if constrained is None else int(constrained.shape[1])
+        flags, masks = np.zeros(len(torsions), dtype=np.uint8), np.zeros((len(torsions), n), dtype=np.uint8)
+        check(self.lib.tsc_torsion_reach(self._h, ptr(graph), C.c_int(G), C.c_int(n), ptr(torsions), ptr(set_off),
+                                         ptr(constrained if n_con else None), C.c_int(n_con), ptr(flags), ptr(masks)))
+        return flags, masks
+
+    def torsion_reach_dev(self, graph, n_graphs, n_atoms, torsions, set_off, constrained, n_con, flags, masks):
+        """tsc_torsion_reach_dev: graph, torsions, constrained, flags and masks on the device; set_off a NumPy array."""
+        set_off = np.ascontiguousarray(set_off, dtype=np.int32)
+        check(self.lib.tsc_torsion_reach_dev(self._h, ptr(graph), C.c_int(n_graphs), C.c_int(n_atoms), ptr(torsions), ptr(set_off), ptr(constrained),
+                                             C.c_int(n_con), ptr(flags), ptr(masks)))
+
+    def torsions_kernel_ms(self):
+        """tsc_torsions_timings: (hydrogen-bond kernel ms, reachability kernel ms) of this thread's latest calls under
+        set_option("pass_timing", 1); -1 where none was taken."""
+        ms = (C.c_float * 2)()
+        check(self.lib.tsc_torsions_timings(self._h, ms))
+        return float(ms[0]), float(ms[1])
+
     # ---- non-covalent interactions -----------------------------------------------------------
     def nci(self, coords, classes, thr, atom_mol, n_mols, candidate, ring_thr, ring_ring_thr, constrained=None, owner_rule=0, want=()):
         """tsc_nci on host arrays (include/tscode_hip.h), already checked (tscode_amd.nci.check_nci_args): coords f64[N, n, 3], classes

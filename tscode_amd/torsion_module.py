@@ -1,9 +1,11 @@
 """Drop-in names of the conformational-search rotations and their batched form.
 
 Reference: ``tscode/utils.py:389-414`` (rotate_dihedral), ``tscode/numba_functions.py:26-47`` (torsion_comp_check),
-``tscode/torsion_module.py:463-509`` (the loop over angle sets of random_csearch / csearch).  The rotation masks
-(``_get_rotation_mask``, a graph walk) and the shuffled angle table stay with the caller; everything per candidate
-runs on the GPU, one wavefront per candidate.
+``tscode/torsion_module.py:463-509`` (the loop over angle sets of random_csearch / csearch).  The candidate entry points take
+torsions, rotation masks and the shuffled angle table from the caller; everything per candidate runs on the GPU, one wavefront
+per candidate.  ``torsion_sets_batch`` makes torsions, folds and masks from coordinates for a whole ensemble (csearch's set-up,
+``:559-615``: hydrogen bonds and graph searches on the GPU, the rotatability rules per topology class on the host), and
+``csearch_augmentation_batch`` joins the two.
 """
 
 from __future__ import annotations
@@ -14,7 +16,9 @@ from .algebra import rot_mat_from_pointer
 from .engine import get_engine
 
 __all__ = ["rotate_dihedral", "rotate_dihedral_batch", "torsion_comp_check", "csearch_rotate", "csearch_candidates",
-           "csearch_rotate_multi", "csearch_candidates_multi", "clustered_csearch_step", "most_diverse_conformers", "diverse_select"]
+           "csearch_rotate_multi", "csearch_candidates_multi", "clustered_csearch_step", "most_diverse_conformers", "diverse_select",
+           "hydrogen_bonds_batch", "torsion_sets_batch", "csearch_augmentation_batch", "class_graph", "candidate_quadruplets",
+           "rotatable_torsions", "class_torsion_set"]
 
 
 def csearch_rotate(coords, torsions, masks, angles, thresh=1.5, max_clashes=0):
@@ -369,3 +373,460 @@ def most_diverse_conformers(n, structures, torsion_array, energies=None, interac
             raise ValueError(f"{len(energies)} energies for {len(structures)} structures")
     aligned, _, picked, _, _ = diverse_select(structures, n, init_rows=init_rows, seed=seed, energies=energies)
     return aligned[picked[picked >= 0]]
+
+
+# ---- from coordinates to torsion sets (tscode/torsion_module.py:559-615, per TS candidate there; per ensemble here) -------------------
+MAX_CONSTRAINT_PAIRS = 64               # TOR_MAX_EXTRA (csrc/torsions.hpp)
+HB_MODE_ALL, HB_MODE_LINK = 0, 1        # keep_hb=True / keep_hb=False (include/tscode_hip.h, tsc_hbonds)
+AUGMENTATION_TABLE_BYTES = 1 << 30      # angle tables one csearch_candidates_multi call of csearch_augmentation_batch may hold
+_CLASS_CACHE, _CLASS_CACHE_MAX = {}, 4096
+
+
+def _constraint_pairs(constrained_indices, S, n):
+    """i32[S, E, 2], -1 for an unused slot, from None, one (E, 2) list shared by all structures, an (S, E, 2) array or a list of S
+    lists of pairs of different lengths (Embedder.constrained_indices).  ValueError on anything else."""
+    if constrained_indices is None:
+        return np.full((S, 0, 2), -1, dtype=np.int32)
+    try:
+        arr = np.asarray(constrained_indices)
+        ragged = arr.dtype == object
+    except ValueError:
+        ragged = True
+    if ragged:
+        rows = [np.asarray(c).reshape(-1, 2) for c in constrained_indices]
+        if len(rows) != S:
+            raise ValueError(f"constraint pairs for {len(rows)} structures, {S} structures")
+        arr = np.full((S, max((len(r) for r in rows), default=0), 2), -1, dtype=np.int64)
+        for s, r in enumerate(rows):
+            if r.size and not np.issubdtype(r.dtype, np.integer):
+                raise ValueError("constraint pairs must be integers")
+            arr[s, :len(r)] = r
+    elif arr.size == 0:
+        return np.full((S, 0, 2), -1, dtype=np.int32)
+    elif not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("constraint pairs must be integers")
+    elif arr.ndim == 2 and arr.shape[1] == 2:
+        arr = np.broadcast_to(arr, (S,) + arr.shape)
+    elif arr.ndim != 3 or arr.shape[0] != S or arr.shape[2] != 2:
+        raise ValueError(f"constraint pairs of shape {arr.shape}: expected (E, 2) or ({S}, E, 2)")
+    if arr.shape[1] > MAX_CONSTRAINT_PAIRS:
+        raise ValueError(f"{arr.shape[1]} constraint pairs per structure: the engine takes at most {MAX_CONSTRAINT_PAIRS}")
+    if arr.size and (arr.min() < -1 or arr.max() >= n):
+        raise ValueError(f"constraint atom index outside -1 .. {n - 1}")
+    return np.ascontiguousarray(arr, dtype=np.int32)
+
+
+def _check_search_args(structures, atomnos, constrained_indices, d_min, d_max, max_angle):
+    from .graph_manipulations import _atomnos_array, _structures_array
+    z = _atomnos_array(atomnos)
+    x = _structures_array(structures, len(z))
+    extra = _constraint_pairs(constrained_indices, len(x), len(z))
+    d_min, d_max, max_angle = float(d_min), float(d_max), float(max_angle)
+    if not (np.isfinite(d_min) and np.isfinite(d_max) and np.isfinite(max_angle)):
+        raise ValueError("d_min, d_max and max_angle must be finite")
+    if not d_min < d_max:
+        raise ValueError(f"d_min {d_min} is not below d_max {d_max}")
+    return x, z, extra, d_min, d_max, max_angle
+
+
+def _search_graphs(x, z, extra, keep_hb, d_min, d_max, max_angle, want_double=False, timings=None):
+    """Bonds (tsc_bond_delta_dev), hydrogen bonds and the search graph (tsc_hbonds_dev) of every structure, the coordinates and the
+    bond bits resident on the device in between.  Returns a namespace: hb (list of i32[K, 2]), segmented bool[S], bonds / graph
+    u64[S, n, W] and, with want_double, double u64[S, n, W]."""
+    import types
+
+    from .graph_manipulations import bond_tables, double_bond_tables
+    S, n = x.shape[:2]
+    W = (n + 63) // 64
+    out = types.SimpleNamespace(hb=[np.zeros((0, 2), np.int32)] * S, segmented=np.zeros(S, bool), bonds=np.zeros((S, n, W), np.uint64),
+                                graph=np.zeros((S, n, W), np.uint64), double=np.zeros((S, n, W), np.uint64) if want_double else None)
+    if S == 0:
+        return out
+    classes, thr = bond_tables(z)
+    hetero, hydrogen = ((z == 7) | (z == 8)).astype(np.uint8), (z == 1).astype(np.uint8)
+    n_extra = extra.shape[1]
+    eng = get_engine()
+    held = []
+
+    def room(nbytes):
+        held.append(eng.dev_alloc(max(int(nbytes), 1)))
+        return held[-1]
+
+    try:
+        held.append(eng.dev_upload(x))
+        d_x = held[-1]
+        d_extra = None
+        if n_extra:
+            held.append(eng.dev_upload(extra))
+            d_extra = held[-1]
+        d_mask, d_bonds, d_graph = room(S), room(S * n * W * 8), room(S * n * W * 8)
+        d_nhb, d_status = room(S * 4), room(S)
+        eng.bond_delta_dev(d_x, S, n, classes, thr, None, None, None, False, 0, d_mask, adj=d_bonds)
+        if timings is not None:
+            timings["bond_delta_ms"] = eng.topology_kernel_ms()
+        n_hb, max_hb = np.zeros(S, np.int32), 8
+        while True:                                                          # (again with more slots where a structure overflowed)
+            d_hb = room(S * max_hb * 8)
+            eng.hbonds_dev(d_x, S, n, hetero, hydrogen, d_bonds, d_extra, n_extra, d_min, d_max, max_angle,
+                           HB_MODE_ALL if keep_hb else HB_MODE_LINK, max_hb, d_hb, d_nhb, d_status, None, d_graph)
+            if timings is not None:
+                timings["hbonds_ms"] = eng.torsions_kernel_ms()[0]
+            eng.dev_download(d_nhb, n_hb)
+            if n_hb.max() <= max_hb:
+                break
+            max_hb = int(n_hb.max())
+        hb = eng.dev_download(d_hb, np.empty((S, max_hb, 2), np.int32))
+        status = eng.dev_download(d_status, np.empty(S, np.uint8))
+        eng.dev_download(d_bonds, out.bonds), eng.dev_download(d_graph, out.graph)
+        if want_double:
+            dcl, dthr, heavy = double_bond_tables(z)
+            eng.bond_delta_dev(d_x, S, n, dcl, dthr, heavy.astype(np.uint8), None, None, False, 0, d_mask, adj=d_bonds)
+            eng.dev_download(d_bonds, out.double)
+        if timings is not None:
+            timings["bytes_up"] = x.nbytes + extra.nbytes
+            timings["bytes_down"] = n_hb.nbytes + hb.nbytes + status.nbytes + out.bonds.nbytes + out.graph.nbytes + (out.double.nbytes if want_double else 0)
+    finally:
+        for a in held:
+            eng.dev_free(a)
+    out.hb = [np.ascontiguousarray(hb[s, :n_hb[s]]) for s in range(S)]
+    out.segmented = status != 0
+    return out
+
+
+def hydrogen_bonds_batch(structures, atomnos, constrained_indices=None, keep_hb=True, d_min=2.5, d_max=3.3, max_angle=45):
+    """_get_hydrogen_bonds (tscode/torsion_module.py:233-299) as csearch calls it (:559-606), for every structure at once:
+    ``(hydrogen_bonds, segmented)`` -- per structure an ``int32[K, 2]`` array of sorted pairs in the reference's list order, and
+    ``bool[S]``, True where the reference raises SegmentedGraphError.  ``constrained_indices``: None, one (E, 2) list shared by
+    all structures, or one list per structure; the pairs are edges of the graph the neighbour lists are read from.
+    ``keep_hb=False`` looks for pairs only where that graph is segmented, and only across its pieces (:593)."""
+    x, z, extra, d_min, d_max, max_angle = _check_search_args(structures, atomnos, constrained_indices, d_min, d_max, max_angle)
+    r = _search_graphs(x, z, extra, bool(keep_hb), d_min, d_max, max_angle)
+    return r.hb, r.segmented
+
+
+# -- the class graph and its candidate torsions: host code, once per topology class
+def _nb(graph, i):
+    """neighbors (tscode/graph_manipulations.py:57-62): the adjacency of i in the graph's own order, the self loop left out."""
+    return [j for j in graph[i] if j != i]
+
+
+def class_graph(atomnos, bonds, constraint_pairs=(), hydrogen_bonds=()):
+    """The search graph of csearch (:559-569) for one topology class: graphize's graph -- nodes 0 .. n-1, a self loop per atom,
+    the bonds by i then j (tscode/graph_manipulations.py:33-55) -- then the constraint pairs, then the hydrogen bonds.  The order
+    matters: it is the order of every neighbour list, hence of the candidate quadruplets."""
+    import networkx as nx
+    graph = nx.Graph()
+    graph.add_nodes_from(range(len(atomnos)))
+    for i in range(len(atomnos)):
+        graph.add_edge(i, i)
+    for a, b in sorted((int(min(a, b)), int(max(a, b))) for a, b in bonds):
+        graph.add_edge(a, b)
+    for a, b in constraint_pairs:
+        if a >= 0 and b >= 0:
+            graph.add_edge(int(a), int(b))
+    for a, b in hydrogen_bonds:
+        graph.add_edge(int(a), int(b))
+    nx.set_node_attributes(graph, {i: int(z) for i, z in enumerate(atomnos)}, "atomnos")
+    return graph
+
+
+def candidate_quadruplets(graph, double_bonds=()):
+    """_get_quadruplets (:327-350) without the central bonds that are double bonds (:362): start atoms ascending, the depth-3
+    walk in adjacency order, the first path per unordered central bond.  The walk is findPaths' as written
+    (tscode/graph_manipulations.py:212-229): the atoms of the path so far are excluded, and so is every atom a path of this start
+    atom has already ENDED on -- the reference adds the last atom of a path to its exclusion set and never takes it out again, so
+    later paths from the same start neither pass through nor end on it.  Reproduced as it is."""
+    double = {(int(min(a, b)), int(max(a, b))) for a, b in double_bonds}
+    adj = {i: list(graph[i]) for i in graph}
+    seen, out = set(), []
+    for a in graph:
+        excluded = {a}
+        for b in adj[a]:
+            if b in excluded:
+                continue
+            excluded.add(b)
+            for c in adj[b]:
+                if c in excluded:
+                    continue
+                excluded.add(c)
+                for d in adj[c]:
+                    if d in excluded:
+                        continue
+                    excluded.add(d)
+                    key = (min(b, c), max(b, c))
+                    if key not in seen:
+                        seen.add(key)
+                        if key not in double:
+                            out.append((a, b, c, d))
+                excluded.remove(c)
+            excluded.remove(b)
+    return np.array(out, dtype=np.int32).reshape(-1, 4)
+
+
+def _sp_n(graph, i):
+    """get_sp_n (tscode/graph_manipulations.py:73-94).  As in the reference a nitrogen with three neighbours has none."""
+    table = {6: {2: 1, 3: 2, 4: 3}, 7: {2: 2, 3: None, 4: 3}, 8: {1: 2, 2: 3, 3: 3, 4: 3}, 15: {2: 2, 3: 3, 4: 3}, 16: {2: 2, 3: 3, 4: 3}}
+    z = graph.nodes[i]["atomnos"]
+    return table[z].get(len(_nb(graph, i))) if z in table else None
+
+
+def _amide_n(graph, i, n_hydrogens):
+    """is_amide_n (:96-131) with mode 1 (n_hydrogens=1, CONHR) or mode 2 (n_hydrogens=0, CONR2): a nitrogen with that many
+    hydrogens next to it and a carbon neighbour that has three neighbours, one of them an oxygen."""
+    z = lambda j: graph.nodes[j]["atomnos"]
+    if z(i) != 7:
+        return False
+    nb = _nb(graph, i)
+    if sum(z(j) == 1 for j in nb) != n_hydrogens:
+        return False
+    for c in nb:
+        if z(c) == 6:
+            around = _nb(graph, c)
+            if len(around) == 3 and any(z(j) == 8 for j in around):
+                return True
+    return False
+
+
+def _ester_o(graph, i):
+    """is_ester_o (:133-150), with its quirk: the test that is meant to rule carboxylic acids out asks whether atom INDEX 1 is a
+    neighbour (``1 not in nb``), not whether a hydrogen is.  Reproduced as it is."""
+    z = lambda j: graph.nodes[j]["atomnos"]
+    if z(i) != 8:
+        return False
+    nb = _nb(graph, i)
+    if 1 in nb:
+        return False
+    for c in nb:
+        if z(c) == 6:
+            around = _nb(graph, c)
+            if len(around) == 3 and sum(z(j) == 8 for j in around) > 1:
+                return True
+    return False
+
+
+def _free(graph, i):
+    """_is_free (:134-156): not an sp2 carbon next to an oxygen, not the nitrogen of a secondary amide, not an ester oxygen."""
+    z = lambda j: graph.nodes[j]["atomnos"]
+    if z(i) == 6 and _sp_n(graph, i) == 2 and any(z(j) == 8 for j in _nb(graph, i)):
+        return False
+    return not _amide_n(graph, i, 1) and not _ester_o(graph, i)
+
+
+def _phenyl_ids(graph, i):
+    """_get_phenyl_ids (tscode/graph_manipulations.py:197-210): the first simple path of six heavy atoms with three neighbours
+    each from i to one of its neighbours."""
+    import networkx as nx
+    for nbr in _nb(graph, i):
+        for path in nx.all_simple_paths(graph, source=i, target=nbr, cutoff=6):
+            if len(path) == 6 and all(graph.nodes[j]["atomnos"] != 1 for j in path) and all(len(_nb(graph, j)) == 3 for j in path):
+                return path
+    return None
+
+
+def _nondummy(graph, i, root):
+    """_is_nondummy (:158-231): turning about root - i changes something, i.e. the substituents of i away from root are not all
+    alike (methyl, CF3, tBu, a symmetric phenyl: dummy).  Only carbon and nitrogen are looked at."""
+    import copy
+
+    import networkx as nx
+    if graph.nodes[i]["atomnos"] not in (6, 7):
+        return True
+    same = lambda p, q: p["atomnos"] == q["atomnos"]
+    g = copy.deepcopy(graph)
+    nb = _nb(g, i)
+    nb.remove(root)
+    if len(nb) == 1 and len(_nb(g, nb[0])) == 2:
+        return False
+    if len(nb) == 2:
+        ring = _phenyl_ids(g, i)
+        if ring is not None:
+            r1, r2, r3, r4, r5, r6 = ring
+            for a, b in ((r3, r4), (r4, r5), (r1, r2), (r1, r6)):
+                g.remove_edge(a, b)
+            halves = [nx.subgraph(g, c) for c in nx.connected_components(g) if r2 in c or r6 in c]
+            if len(halves) == 2:
+                return not nx.is_isomorphic(halves[0], halves[1], node_match=same)
+            return True
+    for j in nb:
+        g.remove_edge(i, j)
+    parts = [c for c in nx.connected_components(g) if root not in c]
+    if len(parts) == 1:
+        return True
+    subs = [nx.subgraph(g, c) for c in parts]
+    return any(not nx.is_isomorphic(subs[0], other, node_match=same) for other in subs[1:])
+
+
+def _n_fold(graph, i2, i3):
+    """Torsion.get_n_fold (:86-110)."""
+    nums = (graph.nodes[i2]["atomnos"], graph.nodes[i3]["atomnos"])
+    if 1 in nums:
+        return 6
+    if _amide_n(graph, i2, 0) or _amide_n(graph, i3, 0):
+        return 2
+    if 6 in nums or 7 in nums or 16 in nums:
+        sp = (_sp_n(graph, i2), _sp_n(graph, i3))
+        if 3 in sp:
+            return 3
+        if 2 in sp:
+            return 2
+    return 4
+
+
+def rotatable_torsions(graph, candidates, in_cycle, hydrogen_bonds=()):
+    """Which candidates _get_torsions keeps (:352-371, keepdummy=False) and their fold: ``(rows, n_folds)``.  ``in_cycle`` bool[T]
+    comes from the reachability kernel.  The rules are Torsion.is_rotable's (:63-84): a central bond that is listed as a hydrogen
+    bond is never rotatable (the reference's own choice, :68-72); one end must be free and both ends non-dummy.
+    Like the reference's in_cycle, every candidate takes its central bond out of the graph and puts it back, which moves the two
+    atoms to the end of each other's neighbour list: the lists the later rules read are the reference's."""
+    hb = {(int(min(a, b)), int(max(a, b))) for a, b in hydrogen_bonds}
+    rows, folds = [], []
+    for k, (i1, i2, i3, i4) in enumerate(np.asarray(candidates).reshape(-1, 4).tolist()):
+        graph.remove_edge(i2, i3)
+        graph.add_edge(i2, i3)
+        if in_cycle[k] or (min(i2, i3), max(i2, i3)) in hb:
+            continue
+        if (_free(graph, i2) or _free(graph, i3)) and _nondummy(graph, i2, i3) and _nondummy(graph, i3, i2):
+            rows.append(k)
+            folds.append(_n_fold(graph, i2, i3))
+    return np.array(rows, dtype=np.int64), np.array(folds, dtype=np.int32)
+
+
+def _oriented_set(candidates, flags, masks, rows, folds):
+    tors = candidates[rows].copy()
+    flip = (flags[rows] & 2) != 0
+    tors[flip] = tors[flip][:, ::-1]
+    return np.ascontiguousarray(tors), np.ascontiguousarray(masks.reshape(len(candidates), -1)[rows]), folds
+
+
+def class_torsion_set(graph, candidates, flags, masks, hydrogen_bonds=()):
+    """One class's ``(torsions i32[T, 4] oriented, masks u8[T, n], n_folds i32[T])`` from its candidates and the answers of
+    tsc_torsion_reach: flags bit 0 in_cycle, bit 1 reversed (Torsion.sort_torsion, :120-132), masks as _get_rotation_mask
+    (:301-325) of the oriented tuple.  ``graph`` is a fresh class_graph: the rules reorder its neighbour lists as they go."""
+    candidates = np.asarray(candidates, dtype=np.int32).reshape(-1, 4)
+    flags = np.asarray(flags, dtype=np.uint8)
+    rows, folds = rotatable_torsions(graph, candidates, (flags & 1) != 0, hydrogen_bonds)
+    return _oriented_set(candidates, flags, np.asarray(masks, dtype=np.uint8), rows, folds)
+
+
+def torsion_sets_batch(structures, atomnos, constrained_indices=None, keep_hb=True, timings=None):
+    """What csearch sets up per TS candidate (tscode/torsion_module.py:559-615) for a whole ensemble: bonds, hydrogen bonds and the
+    segmentation verdict per structure on the GPU, then one torsion set per TOPOLOGY CLASS -- the structures that share bond bits,
+    double-bond bits, the ordered constraint list and the ordered hydrogen-bond list.  Returns a namespace with
+
+    * ``set_of_structure`` i32[S]: the structure's set, -1 where ``segmented``;
+    * ``segmented`` bool[S]; ``hydrogen_bonds``: per structure int32[K, 2];
+    * ``sets[k] = (torsions i32[T_k, 4], masks u8[T_k, n], n_folds i32[T_k])``: _get_torsions after sort_torsion, the
+      _get_rotation_mask of each, and Torsion.n_fold -- ready for csearch_candidates_multi once an angle table is added.
+
+    No TSCoDe import: the rotatability rules are restated here on the class graph (networkx does the isomorphism tests)."""
+    import time
+    import types
+
+    from .graph_manipulations import edges_from_bits
+    x, z, extra, d_min, d_max, max_angle = _check_search_args(structures, atomnos, constrained_indices, 2.5, 3.3, 45)
+    S, n = x.shape[:2]
+    r = _search_graphs(x, z, extra, bool(keep_hb), d_min, d_max, max_angle, want_double=True, timings=timings)
+    t0 = time.perf_counter()
+    set_of = np.full(S, -1, dtype=np.int32)
+    keys, members = {}, []
+    for s in np.flatnonzero(~r.segmented):
+        key = (z.tobytes(), r.bonds[s].tobytes(), r.double[s].tobytes(), extra[s].tobytes(), r.hb[s].tobytes())
+        k = keys.setdefault(key, len(members))
+        if k == len(members):
+            members.append(int(s))
+        set_of[s] = k
+    t1 = time.perf_counter()
+    # per class, cached: the candidates, and the rows and folds the rules gave for these in_cycle answers
+    key_list, graphs, cands = list(keys), [], []
+    for key, s in zip(key_list, members):
+        hit = _CLASS_CACHE.get(key)
+        if hit is None:
+            graphs.append(class_graph(z, edges_from_bits(r.bonds[s]), extra[s], r.hb[s]))
+            cands.append(candidate_quadruplets(graphs[-1], edges_from_bits(r.double[s])))
+        else:
+            graphs.append(None), cands.append(hit[0])
+    t2 = time.perf_counter()
+    sets = []
+    t2b = t2
+    if members:
+        set_off = np.concatenate([[0], np.cumsum([len(c) for c in cands])]).astype(np.int32)
+        flags, masks = get_engine().torsion_reach(r.graph[members], np.concatenate(cands), set_off, extra[members].reshape(len(members), -1))
+        if timings is not None:
+            timings["reach_ms"] = get_engine().torsions_kernel_ms()[1]
+            timings["bytes_up"] += r.graph[members].nbytes + 16 * int(set_off[-1])
+            timings["bytes_down"] += flags.nbytes + masks.nbytes
+        t2b = time.perf_counter()
+        for k, (key, s) in enumerate(zip(key_list, members)):
+            f, m = flags[set_off[k]:set_off[k + 1]], masks[set_off[k]:set_off[k + 1]]
+            cyc = ((f & 1) != 0).tobytes()
+            hit = _CLASS_CACHE.get(key)
+            if hit is None or hit[1] != cyc:
+                g = graphs[k] if graphs[k] is not None else class_graph(z, edges_from_bits(r.bonds[s]), extra[s], r.hb[s])
+                hit = (cands[k], cyc) + rotatable_torsions(g, cands[k], (f & 1) != 0, r.hb[s])
+                if len(_CLASS_CACHE) >= _CLASS_CACHE_MAX:
+                    _CLASS_CACHE.clear()
+                _CLASS_CACHE[key] = hit
+            sets.append(_oriented_set(cands[k], f, m, hit[2], hit[3]))
+    t3 = time.perf_counter()
+    if timings is not None:
+        timings.update(n_classes=len(members), grouping_ms=1e3 * (t1 - t0), quadruplets_ms=1e3 * (t2 - t1), chemistry_ms=1e3 * (t3 - t2b))
+    return types.SimpleNamespace(set_of_structure=set_of, segmented=r.segmented, hydrogen_bonds=r.hb, sets=sets, constraint_pairs=extra)
+
+
+def csearch_augmentation_batch(structures, atomnos, constrained_indices, n_out=100, max_tries=10000, keep_hb=True, max_structs=None,
+                               timings=None):
+    """The loop of Embedder.csearch_augmentation (tscode/embedder.py:1907-1939) without the energy bookkeeping:
+    ``(new_structures [K, n, 3], start_index [K])``, structure after structure what ``csearch(structure, atomnos,
+    constrained_indices[s], keep_hb=True, mode=2, n_out=n_out)`` returns -- nothing for a segmented structure (:1930), the
+    structure itself where no bond is rotatable (tscode/torsion_module.py:619-621), else the candidates of random_csearch.  With
+    ``max_structs``, ``n_out`` follows :1904-1905.  The angle table of a structure with torsions is ``cartesian_product`` of its
+    n-fold angles shuffled with ``np.random.shuffle`` -- exactly one shuffle per such structure, in order, so a caller who seeds
+    ``np.random`` gets the reference's tables.  The rotations are csearch_candidates_multi calls with one set per structure, as
+    many structures per call as keep its tables under ``AUGMENTATION_TABLE_BYTES``."""
+    import time
+
+    from .utils import cartesian_product
+    ts = torsion_sets_batch(structures, atomnos, constrained_indices, keep_hb, timings=timings)
+    x = np.ascontiguousarray(structures, dtype=np.float64)
+    if x.ndim == 2:
+        x = x[None]
+    S, n = x.shape[:2]
+    if max_structs is not None:
+        n_out = 100 if S * 100 < max_structs else round(max_structs / S)            # embedder.py:1904-1905
+        n_out = max((1, n_out))
+    t0 = time.perf_counter()
+    pieces = [None] * S
+    batch, batch_bytes = [], 0
+
+    def flush():
+        nonlocal batch, batch_bytes
+        if batch:
+            rows, start = csearch_candidates_multi(x[[s for s, _ in batch]], [st for _, st in batch], None, n_out=n_out, max_tries=max_tries)
+            for local, (s, _) in enumerate(batch):
+                pieces[s] = rows[start == local]
+        batch, batch_bytes = [], 0
+
+    tables_s = 0.0
+    for s in range(S):
+        if ts.segmented[s]:
+            pieces[s] = np.zeros((0, n, 3))
+            continue
+        tors, masks, folds = ts.sets[ts.set_of_structure[s]]
+        if not len(tors):
+            pieces[s] = x[s][None]
+            continue
+        t1 = time.perf_counter()
+        table = cartesian_product(*[N_FOLD_ANGLES[int(f)] for f in folds])            # tscode/torsion_module.py:453
+        np.random.shuffle(table)                                                      # :460
+        tables_s += time.perf_counter() - t1
+        if batch and batch_bytes + table.nbytes > AUGMENTATION_TABLE_BYTES:
+            flush()
+        batch.append((s, (tors, masks, table)))
+        batch_bytes += table.nbytes
+    flush()
+    if timings is not None:
+        timings["tables_ms"] = 1e3 * tables_s
+        timings["augmentation_host_ms"] = 1e3 * (time.perf_counter() - t0)
+    counts = [len(p) for p in pieces]
+    out = np.concatenate(pieces) if pieces else np.zeros((0, n, 3))
+    return out, np.repeat(np.arange(S, dtype=np.int32), counts)
