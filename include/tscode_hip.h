@@ -109,10 +109,13 @@ int tsc_ctx_synchronize(tsc_ctx *ctx);
  * "stage1_f32": the pair kernels' first look at a pair that passed the screen (H = p^T q and the quartic tests) reads a float32 copy
  * of the coordinates with the rounding bound that goes with it, the float64 coordinates only for what that leaves undecided: 0 = never,
  * 1 (default) = in runs with 128 MB of heavy-atom coordinates or more (where the gathers come from HBM), 2 = always;
+ * "prune_batch_max_n": structures per segment that tsc_prune_rmsd_batch takes at most (1 .. 8192, default 2048; see there);
  * "pass_timing": HIP events for tsc_pass_stats.gpu_ms / tile_ms and the pipeline's stage timings: 0 = none (default; an
  * event record in the stream costs about 4 us on MI355X), 1 = the pair kernel's own start/stop events (tile_ms; passes run by the
  * chunk-local kernel carry theirs at level 2 only), 2 = also around every whole pass (gpu_ms) and the stages of tsc_pipeline_dev. */
 int tsc_ctx_set_option(tsc_ctx *ctx, const char *name, double value);
+/* The current value of a tunable the host side routes by: "prune_batch_max_n" (the Python layer sends longer ensembles to tsc_prune_rmsd). */
+int tsc_ctx_get_option(tsc_ctx *ctx, const char *name, double *value);
 /* Device memory helpers for hosts that do not bring their own allocator (tests, C callers). */
 int tsc_malloc(tsc_ctx *ctx, size_t bytes, void **dptr);
 int tsc_free(tsc_ctx *ctx, void *dptr);
@@ -411,6 +414,40 @@ int tsc_prune_structures(tsc_ctx *ctx, const double *structures, int64_t n, int 
                          double rmsd_thr, int mode, uint8_t *mask, tsc_pass_stats *stats, int *n_passes);
 int tsc_prune_rmsd_dev(tsc_ctx *ctx, const double *heavy, int64_t n, int h, double rmsd_thr, int mode, uint8_t *mask,
                        tsc_pass_stats *stats, int *n_passes); /* synchronises (the schedule gate reads counts) */
+
+/* Per-pass statistics of one segment of tsc_prune_rmsd_batch (one entry per executed k of that segment's schedule). */
+typedef struct {
+    int64_t k;               /* number of chunks (tscode/rmsd_pruning.py:186-188) */
+    int64_t n_active_before; /* count_nonzero(mask) entering the pass (:192) */
+    int64_t n_active_after;
+    int64_t pairs_evaluated; /* pair evaluations the reference's sequential scan performs in this pass (:70): the columns a row visits up
+                                to and including the one it stops at; columns the kernel computed beyond a row's stop are not counted */
+    int64_t new_keys;        /* cache keys appended (:76, :204): one per removed row */
+} tsc_batch_pass_stats;
+
+#define TSC_PRUNE_BATCH_MAX_N 8192 /* the largest "prune_batch_max_n" */
+
+/* prune_conformers_rmsd (tscode/rmsd_pruning.py:164-206) on MANY ensembles in one launch: one run of :164-206 per segment, each with
+ * its own schedule (:186-192), chunks (:136-144), cache (:183, :65-67, :204) and threshold, every one as tsc_prune_rmsd computes it.
+ * One workgroup owns one segment for all its passes; the workgroups share nothing.
+ *   heavy     f64: the segments' [n[s], h[s], 3] heavy-atom arrays (structures[:, atomnos != 1], :178-179) back to back;
+ *   offsets   i64[n_segments + 1]: segment s starts at heavy + offsets[s] (in doubles); offsets[0] = 0 and
+ *             offsets[s + 1] - offsets[s] = n[s] * h[s] * 3;
+ *   n, h      i32[n_segments]: structures (>= 0, at most the context option "prune_batch_max_n") and heavy atoms (>= 1) per segment;
+ *   thr       f64[n_segments]: rmsd_thr per segment (the max deviation threshold is 2 * thr, :95);  mode as in tsc_prune_rmsd;
+ *   mask      u8[sum n] out (1 = kept), the segments back to back;
+ *   stats     (optional) [n_segments][TSC_MAX_PASSES] out, zero beyond a segment's passes;  n_passes (optional) i32[n_segments] out;
+ *   nonfinite (optional) u8[n_segments] out: 1 = the segment holds a structure with a NaN or infinite coordinate.  Such a structure
+ *             is similar to nothing and is kept; the reference raises LinAlgError there (np.linalg.svd, :19), and so does the Python layer.
+ * "prune_batch_max_n" (tsc_ctx_set_option; 1 .. 8192, default 2048): a longer segment is refused -- a workgroup is one compute unit, a long
+ * ensemble belongs to tsc_prune_rmsd, which spreads a pass over the device (the Python layer routes it there).
+ * The _dev form takes heavy, mask, stats, n_passes and nonfinite on the device and the four tables in host memory; it synchronises
+ * (the tables are sorted into launch order and uploaded from the call's own memory). */
+int tsc_prune_rmsd_batch(tsc_ctx *ctx, const double *heavy, const int64_t *offsets, const int32_t *n, const int32_t *h, const double *thr,
+                         int64_t n_segments, int mode, uint8_t *mask, tsc_batch_pass_stats *stats, int32_t *n_passes, uint8_t *nonfinite);
+int tsc_prune_rmsd_batch_dev(tsc_ctx *ctx, const double *heavy, const int64_t *offsets_host, const int32_t *n_host, const int32_t *h_host,
+                             const double *thr_host, int64_t n_segments, int mode, uint8_t *mask, tsc_batch_pass_stats *stats,
+                             int32_t *n_passes, uint8_t *nonfinite);
 
 /* Stepping form of the same run, for one-process-per-GPU sharding of a pass (rows of a pass are
  * independent: tscode/rmsd_pruning.py:92,101-113).  Every rank holds the full `heavy` array and calls

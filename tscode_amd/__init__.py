@@ -32,6 +32,7 @@ from .torsion_module import (clustered_csearch_step, csearch_augmentation_batch,
 from .hypermolecule_class import align_structures  # noqa: F401
 from .kmeans import kmeans_lloyd, kmeans_plusplus_rows  # noqa: F401
 from .rot_corr import last_rot_corr_stats, prune_conformers_rmsd_rot_corr, prune_rmsd_rot_corr_arrays, rot_corr_pairs  # noqa: F401
-from .rmsd_pruning import _rmsd_similarity, last_prune_stats, prune_conformers_rmsd, rmsd_and_max_numba  # noqa: F401
+from .rmsd_pruning import (_rmsd_similarity, last_prune_batch_stats, last_prune_stats, pack_heavy_batch, prune_conformers_rmsd,  # noqa: F401
+                           prune_conformers_rmsd_batch, rmsd_and_max_numba)
 
 __version__ = "0.1.0"

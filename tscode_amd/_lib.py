@@ -40,6 +40,15 @@ class PassStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class BatchPassStats(C.Structure):
+    """tsc_batch_pass_stats: one pass of one segment of tsc_prune_rmsd_batch."""
+    _fields_ = [("k", C.c_int64), ("n_active_before", C.c_int64), ("n_active_after", C.c_int64), ("pairs_evaluated", C.c_int64),
+                ("new_keys", C.c_int64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class ExchangeRecord(C.Structure):
     """tsc_exchange_record: one collective of tsc_prune_run_sharded (k < 0: the cache views in front of pass -k)."""
     _fields_ = [("k", C.c_int64), ("kind", C.c_int32), ("count", C.c_int64)]
@@ -61,6 +70,7 @@ _SIGNATURES = {
     "tsc_ctx_set_stream": (C.c_int, [_vp, _vp]),
     "tsc_ctx_synchronize": (C.c_int, [_vp]),
     "tsc_ctx_set_option": (C.c_int, [_vp, C.c_char_p, C.c_double]),
+    "tsc_ctx_get_option": (C.c_int, [_vp, C.c_char_p, c_f64p]),
     "tsc_malloc": (C.c_int, [_vp, C.c_size_t, C.POINTER(_vp)]),
     "tsc_free": (C.c_int, [_vp, _vp]),
     "tsc_memcpy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
@@ -113,6 +123,8 @@ _SIGNATURES = {
     "tsc_prune_structures": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, c_i32p, C.c_int, C.c_double, C.c_int, _vp, C.POINTER(PassStats),
                                        C.POINTER(C.c_int)]),
     "tsc_prune_rmsd_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_double, C.c_int, _vp, C.POINTER(PassStats), C.POINTER(C.c_int)]),
+    "tsc_prune_rmsd_batch": (C.c_int, [_vp, _vp, c_i64p, c_i32p, c_i32p, c_f64p, C.c_int64, C.c_int, _vp, C.POINTER(BatchPassStats), c_i32p, c_u8p]),
+    "tsc_prune_rmsd_batch_dev": (C.c_int, [_vp, _vp, c_i64p, c_i32p, c_i32p, c_f64p, C.c_int64, C.c_int, _vp, C.POINTER(BatchPassStats), _vp, _vp]),
     "tsc_prune_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_double, C.c_int, C.POINTER(_vp)]),
     "tsc_prune_next_pass": (C.c_int, [_vp, c_i64p]),
     "tsc_prune_pass_estimate": (C.c_int, [_vp, c_i64p]),

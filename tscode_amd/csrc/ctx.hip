@@ -337,12 +337,28 @@ extern "C" __attribute__((visibility("default"))) int tsc_ctx_set_option(tsc_ctx
         c->clash_fp32 = int(value);
         return 0;
     }
+    if (strcmp(name, "prune_batch_max_n") == 0) {
+        TSC_REQUIRE(value >= 1 && value <= TSC_PRUNE_BATCH_MAX_N && value == double(int(value)), "prune_batch_max_n must be a whole number in [1, %d]", TSC_PRUNE_BATCH_MAX_N);
+        c->prune_batch_max_n = int(value);
+        return 0;
+    }
     if (strcmp(name, "seg_cols") == 0) {
         TSC_REQUIRE(value == 0 || (value >= 256 && value <= 4096 && int(value) % 256 == 0), "seg_cols must be 0 (automatic) or a multiple of 256 in [256, 4096]");
         c->seg_cols = int(value);
         return 0;
     }
     return fail(TSC_ERR_INVALID, "unknown option '%s'", name);
+    TSC_API_GUARD_END
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_ctx_get_option(tsc_ctx *c, const char *name, double *value) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(c && name && value, "null argument");
+    if (strcmp(name, "prune_batch_max_n") == 0) {
+        *value = double(c->prune_batch_max_n);
+        return 0;
+    }
+    return fail(TSC_ERR_INVALID, "tsc_ctx_get_option: option '%s' cannot be read", name);
     TSC_API_GUARD_END
 }
 

@@ -14,7 +14,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import PassStats, TSC_MAX_PASSES, check, ptr
+from ._lib import BatchPassStats, PassStats, TSC_MAX_PASSES, check, ptr
 
 __all__ = ["Engine", "FragmentSet", "get_engine", "device_count"]
 
@@ -61,6 +61,26 @@ def _ids_arg(ids):
 
 def _stats_list(stats, n):
     return [stats[i].as_dict() for i in range(n)]
+
+
+_BATCH_STAT_FIELDS = tuple(f for f, _ in BatchPassStats._fields_)
+
+
+def pack_heavy_batch(heavies):
+    """The arrays tsc_prune_rmsd_batch takes for a sequence of heavy-atom arrays f64[N_s, h_s, 3]: (flat, offsets, n, h) -- the arrays
+    back to back, offsets i64[S + 1] in doubles, n i32[S] structures and h i32[S] heavy atoms per ensemble.  No device is touched."""
+    arrays = []
+    for s, a in enumerate(heavies):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"ensemble {s}: heavy must be (N, h, 3), got {a.shape}")
+        arrays.append(a)
+    n = np.array([a.shape[0] for a in arrays], dtype=np.int32)
+    h = np.array([a.shape[1] for a in arrays], dtype=np.int32)
+    offsets = np.zeros(len(arrays) + 1, dtype=np.int64)
+    np.cumsum(n.astype(np.int64) * h * 3, out=offsets[1:])
+    flat = np.concatenate([a.ravel() for a in arrays]) if arrays else np.zeros(0)
+    return flat, offsets, n, h
 
 
 class PipelineResult:
@@ -132,8 +152,20 @@ class Engine:
         check(self.lib.tsc_ctx_synchronize(self._h))
 
     def set_option(self, name: str, value: float):
-        """Tunables of the library: "prune_algo" (0 auto, 1 register-tiled, 2 sieve), "seg_cols"."""
+        """Tunables of the library, as include/tscode_hip.h lists them at tsc_ctx_set_option: "prune_algo" (0 auto, 1 register-tiled,
+        2 sieve), "seg_cols", "prune_batch_max_n" (structures per ensemble that the batch kernel takes), ..."""
         check(self.lib.tsc_ctx_set_option(self._h, name.encode(), C.c_double(value)))
+
+    def get_option(self, name: str) -> float:
+        """tsc_ctx_get_option: the current value of a tunable the host side routes by ("prune_batch_max_n")."""
+        v = C.c_double()
+        check(self.lib.tsc_ctx_get_option(self._h, name.encode(), C.byref(v)))
+        return v.value
+
+    @property
+    def prune_batch_max_n(self) -> int:
+        """Structures per ensemble that tsc_prune_rmsd_batch takes (the context's option, read from the library: one copy of the default)."""
+        return int(self.get_option("prune_batch_max_n"))
 
     def timer_begin(self):
         check(self.lib.tsc_timer_begin(self._h))
@@ -698,6 +730,60 @@ class Engine:
         check(self.lib.tsc_prune_rmsd(self._h, ptr(heavy), C.c_int64(n), C.c_int(h), C.c_double(rmsd_thr), C.c_int(mode), ptr(mask),
                                       stats, C.byref(np_)))
         return mask.astype(bool), _stats_list(stats, np_.value)
+
+    def prune_heavy_batch(self, heavies, rmsd_thr=0.5, mode=0):
+        """prune_conformers_rmsd on many heavy-atom arrays f64[N_s, h_s, 3] (rmsd_thr a scalar or one per ensemble).  Ensembles of at
+        most "prune_batch_max_n" structures go through tsc_prune_rmsd_batch in ONE launch, a workgroup each; a longer one takes
+        prune_heavy on its own, which spreads a pass over the device.  Returns (masks, stats, nonfinite): per ensemble the mask bool[N_s],
+        the list of its passes (k, n_active_before, n_active_after, pairs_evaluated, new_keys) and whether it holds a NaN or infinite
+        coordinate (bool[S])."""
+        heavies = [np.ascontiguousarray(a, dtype=np.float64) for a in heavies]
+        S = len(heavies)
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(rmsd_thr, dtype=np.float64), (S,)))
+        masks, stats, nonfinite = [None] * S, [None] * S, np.zeros(S, dtype=bool)
+        for s, a in enumerate(heavies):
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"ensemble {s}: heavy must be (N, h, 3), got {a.shape}")
+            if a.shape[1] < 1:
+                raise ValueError(f"ensemble {s}: no heavy atoms")
+        max_n = self.prune_batch_max_n
+        small = [s for s in range(S) if heavies[s].shape[0] <= max_n]
+        if small:
+            flat, offsets, n, h = pack_heavy_batch([heavies[s] for s in small])
+            B = len(small)
+            mask = np.zeros(int(n.sum()), dtype=np.uint8)
+            st = (BatchPassStats * (B * TSC_MAX_PASSES))()
+            np_ = np.zeros(B, dtype=np.int32)
+            nf = np.zeros(B, dtype=np.uint8)
+            t = np.ascontiguousarray(thr[small])
+            check(self.lib.tsc_prune_rmsd_batch(self._h, ptr(flat), offsets.ctypes.data_as(_lib.c_i64p), n.ctypes.data_as(_lib.c_i32p),
+                                                h.ctypes.data_as(_lib.c_i32p), t.ctypes.data_as(_lib.c_f64p), C.c_int64(B), C.c_int(int(mode)),
+                                                ptr(mask), st, np_.ctypes.data_as(_lib.c_i32p), nf.ctypes.data_as(_lib.c_u8p)))
+            table = np.frombuffer(st, dtype=np.int64).reshape(B, TSC_MAX_PASSES, len(_BATCH_STAT_FIELDS))
+            ends = np.cumsum(n, dtype=np.int64)
+            for b, s in enumerate(small):
+                masks[s] = mask[ends[b] - n[b]:ends[b]].astype(bool)
+                stats[s] = [dict(zip(_BATCH_STAT_FIELDS, map(int, row))) for row in table[b, :np_[b]]]
+                nonfinite[s] = bool(nf[b])
+        for s in range(S):
+            if masks[s] is None:
+                masks[s], full = self.prune_heavy(heavies[s], float(thr[s]), mode)
+                stats[s] = [{f: int(p[f]) for f in _BATCH_STAT_FIELDS} for p in full]
+                nonfinite[s] = bool(full and full[0].get("nonfinite_input"))
+        return masks, stats, nonfinite
+
+    def prune_heavy_batch_dev(self, heavy, offsets, n, h, rmsd_thr, mode, mask, stats=None, n_passes=None, nonfinite=None):
+        """tsc_prune_rmsd_batch_dev: heavy f64 and the outputs mask u8[sum n], stats (i64[S, TSC_MAX_PASSES, 5]), n_passes i32[S] and
+        nonfinite u8[S] on the device (torch tensors or raw pointers; the last three optional), the tables offsets / n / h / rmsd_thr
+        NumPy arrays (pack_heavy_batch).  Every ensemble must have at most "prune_batch_max_n" structures.  Synchronises."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = np.ascontiguousarray(n, dtype=np.int32)
+        h = np.ascontiguousarray(h, dtype=np.int32)
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(rmsd_thr, dtype=np.float64), n.shape))
+        st = C.cast(ptr(stats), C.POINTER(BatchPassStats)) if stats is not None else None
+        check(self.lib.tsc_prune_rmsd_batch_dev(self._h, ptr(heavy), offsets.ctypes.data_as(_lib.c_i64p), n.ctypes.data_as(_lib.c_i32p),
+                                                h.ctypes.data_as(_lib.c_i32p), thr.ctypes.data_as(_lib.c_f64p), C.c_int64(len(n)), C.c_int(int(mode)),
+                                                ptr(mask), st, ptr(n_passes), ptr(nonfinite)))
 
     def prune_structures(self, structures, heavy_idx, rmsd_thr=0.5, mode=0):
         """The same from all-atom structures f64[N, n_atoms, 3] (C-contiguous) and the indices of the heavy atoms: the gather of

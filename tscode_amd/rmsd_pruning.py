@@ -8,11 +8,13 @@ from __future__ import annotations
 
 import numpy as np
 
-from .engine import get_engine
+from .engine import get_engine, pack_heavy_batch  # noqa: F401  (pack_heavy_batch: the arrays tsc_prune_rmsd_batch takes)
 
-__all__ = ["prune_conformers_rmsd", "rmsd_and_max_numba", "_rmsd_similarity", "last_prune_stats"]
+__all__ = ["prune_conformers_rmsd", "prune_conformers_rmsd_batch", "rmsd_and_max_numba", "_rmsd_similarity", "last_prune_stats",
+           "last_prune_batch_stats", "pack_heavy_batch"]
 
 _last_stats = []
+_last_batch_stats = []
 
 
 def last_prune_stats():
@@ -49,6 +51,63 @@ def prune_conformers_rmsd(structures, atomnos, rmsd_thr=0.5, mode=0, **_ignored)
         # library itself defines the verdict (similar to nothing, kept) and only reports that it met one
         raise np.linalg.LinAlgError("Array must not contain infs or NaNs")
     return structures[mask], mask                                                   # :206
+
+
+def last_prune_batch_stats():
+    """Per ensemble, the per-pass statistics (k, active before/after, pair evaluations, new keys) of the latest batch call."""
+    return [list(passes) for passes in _last_batch_stats]
+
+
+def _check_batch(ensembles, atomnos, rmsd_thr):
+    """The arguments of prune_conformers_rmsd_batch as (structures, heavy indices, thresholds) per ensemble; raises before anything
+    is uploaded."""
+    ensembles = [np.asarray(e) for e in ensembles]
+    S = len(ensembles)
+    try:
+        one = np.asarray(atomnos)
+        shared = one.ndim == 1 and one.dtype != object       # one array of atomic numbers (a list of arrays has two axes, or is ragged)
+    except ValueError:
+        shared = False
+    if shared:
+        atomnos = [np.asarray(atomnos)] * S
+    else:
+        atomnos = [np.asarray(a) for a in atomnos]
+        if len(atomnos) != S:
+            raise ValueError(f"{len(atomnos)} atomnos arrays for {S} ensembles")
+    thr = np.asarray(rmsd_thr, dtype=np.float64)
+    if thr.ndim == 0:
+        thr = np.full(S, float(thr))
+    elif thr.shape != (S,):
+        raise ValueError(f"{thr.size} thresholds for {S} ensembles")
+    heavy_idx = []
+    for s, (e, a) in enumerate(zip(ensembles, atomnos)):
+        if e.ndim != 3 or e.shape[2] != 3 or a.ndim != 1 or e.shape[1] != a.shape[0]:
+            raise ValueError(f"ensemble {s}: structures must be (N, n_atoms, 3) with len(atomnos) == n_atoms, got {e.shape} and {a.shape}")
+        heavy_idx.append(np.flatnonzero(a != 1))                                     # :178
+    for s, idx in enumerate(heavy_idx):
+        if len(idx) == 0:
+            raise ZeroDivisionError(f"ensemble {s}: no non-hydrogen atoms: the reference divides by zero (rmsd_pruning.py:35)")
+    return ensembles, heavy_idx, thr
+
+
+def prune_conformers_rmsd_batch(ensembles, atomnos, rmsd_thr=0.5, mode=0):
+    """tscode/rmsd_pruning.py:164-206 on many ensembles at once: [prune_conformers_rmsd(e, a, thr, mode) for every ensemble], in one
+    launch for the ensembles of at most "prune_batch_max_n" structures (Engine.prune_heavy_batch).
+
+    ``ensembles``: a sequence of (N_s, n_s, 3) arrays; ``atomnos``: one array shared by all, or a list with one per ensemble;
+    ``rmsd_thr``: a scalar or one per ensemble.  Returns the list of (structures_s[mask_s], mask_s)."""
+    global _last_batch_stats
+    ensembles, heavy_idx, thr = _check_batch(ensembles, atomnos, rmsd_thr)
+    if not ensembles:
+        _last_batch_stats = []
+        return []
+    heavies = [np.ascontiguousarray(e[:, idx], dtype=np.float64) for e, idx in zip(ensembles, heavy_idx)]    # :179
+    masks, _last_batch_stats, nonfinite = get_engine().prune_heavy_batch(heavies, thr, int(mode))
+    for s, e in enumerate(ensembles):
+        if nonfinite[s] and len(e) > 1:
+            # (as prune_conformers_rmsd: the reference's np.linalg.svd raises on such a structure, rmsd_pruning.py:19)
+            raise np.linalg.LinAlgError(f"ensemble {s}: Array must not contain infs or NaNs")
+    return [(e[m], m) for e, m in zip(ensembles, masks)]                            # :206
 
 
 def rmsd_and_max_numba(p, q):
