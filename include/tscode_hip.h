@@ -914,6 +914,41 @@ int tsc_torsion_reach_dev(tsc_ctx *ctx, const uint64_t *graph, int n_graphs, int
                           const int32_t *constrained, int n_con, uint8_t *flags, uint8_t *masks);
 int tsc_torsions_timings(tsc_ctx *ctx, float *ms2);
 
+/* Which torsions of a structure turn together in a clustered conformational search, for a whole ensemble per call (csrc/torsions.hpp),
+ * one wavefront per structure.
+ *   replaces   _group_torsions_dbscan   tscode/torsion_module.py:373-397 (scikit-learn's dbscan with min_samples=1, level after level)
+ *              the T < 9 branch of clustered_csearch, tscode/torsion_module.py:689-695
+ * Per structure s with T = set_off[s+1] - set_off[s] torsions (i1, i2, i3, i4):
+ *   T < min_torsions (9 in the reference): one group -- group_of 0 for every torsion, n_groups 1 (0 where T == 0), eps_index -1,
+ *   oversize 0.  Otherwise:
+ *   centre    of torsion t = (r_i2 + r_i3) / 2 in fp64 (:379).
+ *   linked    at a level eps: two torsions whose centres have dx dx + dy dy + dz dz <= eps eps, inclusive, in fp64 without fused
+ *             multiply-add (every level is a multiple of 0.5: its square is exact).
+ *   clusters  the connected components of that relation; a cluster's label is the rank of its smallest member among the clusters'
+ *             smallest members (dbscan with min_samples=1: every point is a core point, clusters are numbered as they are met).
+ *   levels    10.0, 9.5, ..., 2.0 (np.arange(10, 1.5, -0.5), seventeen), in that order: the first whose largest cluster has at most
+ *             max_size members (5 in the reference, 3 with ff_opt) is kept and eps_index is its position.  No level qualifies (the
+ *             reference's loop has no else): the clusters of the last level stand, eps_index = 16, oversize = 1.
+ *   order     the groups are the clusters by size ascending, ties by label (sorted(output, key=len), :394, a stable sort);
+ *             group_of[t] is the position of t's cluster in that order.  Inside a group the torsions keep ascending index.
+ *   coords      f64[n_structs, n_atoms, 3]; n_atoms 1 .. 512.  A torsion with a non-finite centre is linked to nothing.
+ *   torsions    i32[T_total, 4]; set_off i32[n_structs + 1] ascending from 0 -- a HOST pointer in both forms; at most 512 torsions per
+ *               structure.
+ *   group_of    i32[T_total].  n_groups, eps_index i32[n_structs].  oversize u8[n_structs].
+ * tsc_torsion_groups takes host arrays.  tsc_torsion_groups_dev: coords, torsions and the four outputs are device pointers; a torsion
+ * with i2 or i3 outside 0 .. n_atoms-1, which the host form refuses, has no centre there and is linked to nothing; the call waits for
+ * the stream.
+ * Refused with TSC_ERR_INVALID before any launch: null required pointers, n_atoms outside 1 .. 512, n_structs < 0, max_size < 1, a
+ * set_off that does not start at 0 or decreases, more than 512 torsions in a structure, and (host arrays) a torsion index outside
+ * 0 .. n_atoms-1.  n_structs == 0 or T_total == 0 succeeds and writes nothing.
+ *   tsc_torsion_groups_timings  under the context option "pass_timing" >= 1: *ms = the kernel of the calling thread's latest call, -1
+ *                               where none was taken. */
+int tsc_torsion_groups(tsc_ctx *ctx, const double *coords, int n_structs, int n_atoms, const int32_t *torsions, const int32_t *set_off,
+                       int max_size, int min_torsions, int32_t *group_of, int32_t *n_groups, int32_t *eps_index, uint8_t *oversize);
+int tsc_torsion_groups_dev(tsc_ctx *ctx, const double *coords, int n_structs, int n_atoms, const int32_t *torsions, const int32_t *set_off,
+                           int max_size, int min_torsions, int32_t *group_of, int32_t *n_groups, int32_t *eps_index, uint8_t *oversize);
+int tsc_torsion_groups_timings(tsc_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,9 @@ _SIGNATURES = {
     "tsc_torsion_reach": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]),
     "tsc_torsion_reach_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]),
     "tsc_torsions_timings": (C.c_int, [_vp, c_f32p]),
+    "tsc_torsion_groups": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "tsc_torsion_groups_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "tsc_torsion_groups_timings": (C.c_int, [_vp, c_f32p]),
     "tsc_pipeline_dev": (C.c_int, [_vp, _vp, c_i64p, c_i32p, c_i32p, C.c_int, _vp, _vp, _vp, C.c_int64, c_i32p, C.c_int,
                                    C.c_double, C.c_int64, C.c_double, C.c_int, _vp, _vp, _vp, _vp, c_i64p, c_i64p,
                                    C.POINTER(PassStats), C.POINTER(C.c_int), c_f32p]),

@@ -1,5 +1,5 @@
-// torsions.hip -- launches and C ABI of the hydrogen-bond finder and the torsion reachability kernels (torsions.hpp;
-// tscode/torsion_module.py:54-61, :120-132, :233-325, :559-606).  gfx950 only.  There is deliberately no CPU implementation behind
+// torsions.hip -- launches and C ABI of the hydrogen-bond finder, the torsion reachability and the torsion grouping kernels
+// (torsions.hpp; tscode/torsion_module.py:54-61, :120-132, :233-325, :373-397, :559-606).  gfx950 only.  There is deliberately no CPU implementation behind
 // these entry points.
 #include "host.hpp"
 #include "call.hpp"
@@ -14,6 +14,8 @@ using namespace tsc;
 // HIP-event times of the kernels of the calling thread's latest tsc_hbonds[_dev] ([0]) and tsc_torsion_reach[_dev] ([1]), taken
 // only under the context option "pass_timing" >= 1 (tools/torsion_sets_profile.py); -1 otherwise
 thread_local float g_kernel_ms[2] = {-1.f, -1.f};
+// ... and of its latest tsc_torsion_groups[_dev] (tsc_torsion_groups_timings; tools/clustered_csearch_profile.py)
+thread_local float g_groups_ms = -1.f;
 
 // Largest double x with sqrt(x) <= thresh, so that (thresh < sqrt(d2)) == (d2 > x) for every d2 >= 0: the strict lower bound of
 // _get_hydrogen_bonds on squared distances, the counterpart of clash_sq_bound.  A negative threshold lets every distance pass.
@@ -116,7 +118,102 @@ int run_reach(tsc_ctx *c, Scratch &s, int n_atoms, const std::vector<int32_t> &i
     return 0;
 }
 
+// What both forms of tsc_torsion_groups refuse; *t_max = the most torsions of one structure.
+int check_groups(const char *who, int n_structs, int n_atoms, const int32_t *set_off, int max_size, int *t_max) {
+    TSC_REQUIRE(n_structs >= 0, "%s: %d structures", who, n_structs);
+    TSC_REQUIRE(n_atoms >= 1 && n_atoms <= TOR_MAX_ATOMS, "%s: %d atoms per structure (1 .. %d)", who, n_atoms, TOR_MAX_ATOMS);
+    TSC_REQUIRE(max_size >= 1, "%s: max_size = %d", who, max_size);
+    TSC_REQUIRE(n_structs == 0 || set_off, "%s: null argument", who);
+    *t_max = 0;
+    if (n_structs == 0) return 0;
+    TSC_REQUIRE(set_off[0] == 0, "%s: set_off[0] = %d", who, set_off[0]);
+    for (int s = 0; s < n_structs; ++s) {
+        TSC_REQUIRE(set_off[s + 1] >= set_off[s], "%s: set_off decreases at structure %d", who, s);
+        const int T = set_off[s + 1] - set_off[s];
+        TSC_REQUIRE(T <= GRP_MAX_TORSIONS, "%s: %d torsions in structure %d (at most %d)", who, T, s, GRP_MAX_TORSIONS);
+        *t_max = std::max(*t_max, T);
+    }
+    return 0;
+}
+
+// device pointers throughout
+int run_groups(tsc_ctx *c, int n_structs, int n_atoms, int t_max, const double *coords, const int32_t *torsions, const int32_t *set_off,
+               int max_size, int min_torsions, int32_t *group_of, int32_t *n_groups, int32_t *eps_index, uint8_t *oversize) {
+    StageTimer tm(c);
+    tm.begin();
+    with_width(ceil_div(t_max, 64), [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        hipLaunchKernelGGL(k_torsion_groups<K>, dim3(grid_for(n_structs, 1)), dim3(64), groups_lds_bytes(t_max), c->stream, n_structs, n_atoms,
+                           t_max, coords, torsions, set_off, max_size, min_torsions, group_of, n_groups, eps_index, oversize);
+    });
+    const hipError_t launched = hipGetLastError();
+    if (launched == hipSuccess) tm.end(&g_groups_ms);
+    TSC_HIP(launched);
+    return 0;
+}
+
 }  // namespace
+
+extern "C" __attribute__((visibility("default"))) int tsc_torsion_groups_timings(tsc_ctx *c, float *ms) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(c && ms, "tsc_torsion_groups_timings: null argument");
+    *ms = g_groups_ms;
+    return 0;
+    TSC_API_GUARD_END
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_torsion_groups_dev(tsc_ctx *c, const double *coords, int n_structs, int n_atoms,
+                                                                             const int32_t *torsions, const int32_t *set_off, int max_size,
+                                                                             int min_torsions, int32_t *group_of, int32_t *n_groups,
+                                                                             int32_t *eps_index, uint8_t *oversize) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(c, "tsc_torsion_groups_dev: null argument");
+    int t_max;
+    TSC_TRY(check_groups("tsc_torsion_groups_dev", n_structs, n_atoms, set_off, max_size, &t_max));
+    g_groups_ms = -1.f;
+    if (n_structs == 0 || set_off[n_structs] == 0) return 0;   // (nothing to read or write: the array pointers may be anything)
+    TSC_REQUIRE(coords && torsions && group_of && n_groups && eps_index && oversize, "tsc_torsion_groups_dev: null argument");
+    DeviceGuard guard(c->device);
+    Scratch s(c);
+    int32_t *d_off = nullptr;
+    TSC_TRY(upload(c, s, set_off, size_t(n_structs) + 1, &d_off));
+    const int rc = run_groups(c, n_structs, n_atoms, t_max, coords, torsions, d_off, max_size, min_torsions, group_of, n_groups, eps_index, oversize);
+    // set_off was uploaded from the caller's memory: it must have left it before the call returns
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+    TSC_API_GUARD_END
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_torsion_groups(tsc_ctx *c, const double *coords, int n_structs, int n_atoms,
+                                                                         const int32_t *torsions, const int32_t *set_off, int max_size,
+                                                                         int min_torsions, int32_t *group_of, int32_t *n_groups,
+                                                                         int32_t *eps_index, uint8_t *oversize) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(c, "tsc_torsion_groups: null argument");
+    int t_max;
+    TSC_TRY(check_groups("tsc_torsion_groups", n_structs, n_atoms, set_off, max_size, &t_max));
+    g_groups_ms = -1.f;
+    if (n_structs == 0 || set_off[n_structs] == 0) return 0;   // (nothing to read or write: the array pointers may be anything)
+    TSC_REQUIRE(coords && torsions && group_of && n_groups && eps_index && oversize, "tsc_torsion_groups: null argument");
+    const size_t S = size_t(n_structs), T = size_t(set_off[n_structs]);
+    for (size_t q = 0; q < 4 * T; ++q)
+        TSC_REQUIRE(torsions[q] >= 0 && torsions[q] < n_atoms, "tsc_torsion_groups: torsion %zu holds atom %d with %d atoms", q / 4, torsions[q], n_atoms);
+    HostCall h(c);
+    const double *d_coords;
+    const int32_t *d_tors, *d_off;
+    int32_t *d_group, *d_ng, *d_eps;
+    uint8_t *d_over;
+    TSC_TRY(h.in(coords, S * n_atoms * 3, &d_coords));
+    TSC_TRY(h.in(torsions, T * 4, &d_tors));
+    TSC_TRY(h.in(set_off, S + 1, &d_off));
+    TSC_TRY(h.out(group_of, T, &d_group));
+    TSC_TRY(h.out(n_groups, S, &d_ng));
+    TSC_TRY(h.out(eps_index, S, &d_eps));
+    TSC_TRY(h.out(oversize, S, &d_over));
+    TSC_TRY(run_groups(c, n_structs, n_atoms, t_max, d_coords, d_tors, d_off, max_size, min_torsions, d_group, d_ng, d_eps, d_over));
+    return h.finish();
+    TSC_API_GUARD_END
+}
 
 extern "C" __attribute__((visibility("default"))) int tsc_torsions_timings(tsc_ctx *c, float *ms2) {
     TSC_API_GUARD_BEGIN

@@ -443,4 +443,129 @@ inline __global__ __launch_bounds__(64 * WPB) void k_torsion_reach(int n, int64_
     }
 }
 
+// ---- which torsions turn together ------------------------------------------------------------------------------------------------
+// tscode/torsion_module.py:373-397 (_group_torsions_dbscan) and the T < 9 branch of :689; the semantics are spelled out at
+// tsc_torsion_groups in include/tscode_hip.h.  One wavefront per structure, one wavefront per block; lane l owns torsions l, l + 64, ...
+// (K = ceil(T_max / 64) of them, centres and labels in registers).  LDS: the centres as three f64[T_max] and label, count and position
+// as three i32[T_max] -- 36 T_max bytes, 18 KiB at 512 torsions.
+//
+// The clusters of one level are the connected components of "centres at most eps apart".  Every torsion starts as its own label; a
+// sweep gives it the smallest label among the torsions it is linked to (every lane walks all T centres, which all lanes read at the
+// same address: a broadcast), then follows the labels down to one that points at itself.  A label is always the index of a member of
+// the torsion's own component and never grows, so the sweeps end -- when one changes nothing -- with every torsion carrying the
+// smallest index of its component.  Thanks to the second step a line of T centres closes in a few sweeps, not in T.
+constexpr int GRP_MAX_TORSIONS = 512;
+constexpr int GRP_LEVELS = 17;   // 10.0, 9.5, ..., 2.0 (np.arange(10, 1.5, -0.5))
+
+__host__ __device__ inline size_t groups_lds_bytes(int t_max) { return size_t(36) * t_max; }
+
+template <int K>
+inline __global__ __launch_bounds__(64) void k_torsion_groups(int n_structs, int n, int t_max, const double *__restrict__ coords,
+                                                              const int32_t *__restrict__ torsions, const int32_t *__restrict__ set_off,
+                                                              int max_size, int min_torsions, int32_t *__restrict__ group_of,
+                                                              int32_t *__restrict__ n_groups, int32_t *__restrict__ eps_index,
+                                                              uint8_t *__restrict__ oversize) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    double *cx = reinterpret_cast<double *>(s_raw), *cy = cx + t_max, *cz = cy + t_max;
+    int *label = reinterpret_cast<int *>(cz + t_max), *count = label + t_max, *pos = count + t_max;
+    const int lane = threadIdx.x;
+    for (int s = blockIdx.x; s < n_structs; s += gridDim.x) {
+        const int t0 = __builtin_amdgcn_readfirstlane(set_off[s]);
+        const int T = min(__builtin_amdgcn_readfirstlane(set_off[s + 1]) - t0, 64 * K);   // (the host refused more than t_max)
+        if (T < min_torsions || T <= 0) {
+            for (int t = lane; t < T; t += 64) group_of[t0 + t] = 0;
+            if (lane == 0) n_groups[s] = T > 0 ? 1 : 0, eps_index[s] = -1, oversize[s] = 0;
+            continue;
+        }
+        // ---- centres (:379); a torsion with an atom outside 0 .. n-1 (only the _dev form can meet one) gets NaN: linked to nothing
+        const double *xyz = coords + size_t(s) * n * 3;
+        double x[K], y[K], z[K];
+        int my[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int t = lane + 64 * k;
+            x[k] = y[k] = z[k] = __builtin_nan("");
+            if (t < T) {
+                const int i2 = torsions[4 * size_t(t0 + t) + 1], i3 = torsions[4 * size_t(t0 + t) + 2];
+                if (i2 >= 0 && i2 < n && i3 >= 0 && i3 < n) {
+                    x[k] = (xyz[3 * i2] + xyz[3 * i3]) / 2.0, y[k] = (xyz[3 * i2 + 1] + xyz[3 * i3 + 1]) / 2.0;
+                    z[k] = (xyz[3 * i2 + 2] + xyz[3 * i3 + 2]) / 2.0;
+                }
+                cx[t] = x[k], cy[t] = y[k], cz[t] = z[k];
+            }
+        }
+        int level = 0, biggest = 0;
+        for (;; ++level) {
+            const double eps = 10.0 - 0.5 * level, eps_sq = eps * eps;   // (a multiple of 0.5: the square is exact)
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                my[k] = lane + 64 * k;
+                if (my[k] < T) label[my[k]] = my[k];
+            }
+            __builtin_amdgcn_wave_barrier();
+            for (;;) {
+                bool changed = false;
+                for (int u = 0; u < T; ++u) {
+                    const double ux = cx[u], uy = cy[u], uz = cz[u];
+                    const int lu = label[u];
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+#pragma clang fp contract(off)
+                        const double dx = x[k] - ux, dy = y[k] - uy, dz = z[k] - uz;
+                        if (dx * dx + dy * dy + dz * dz <= eps_sq && lu < my[k]) my[k] = lu, changed = true;   // (NaN: never)
+                    }
+                }
+                if (!__ballot(changed)) break;
+                // the sweep read the labels of the sweep before; now they move, and then every torsion follows them down
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+                    if (lane + 64 * k < T) label[lane + 64 * k] = my[k];
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+                    if (lane + 64 * k < T) {
+                        int l = my[k];
+                        for (int up = label[l]; up < l; up = label[l]) l = up;
+                        my[k] = l;
+                    }
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+                    if (lane + 64 * k < T) label[lane + 64 * k] = my[k];
+                __builtin_amdgcn_wave_barrier();
+            }
+            // ---- members per cluster, kept at the cluster's smallest member, and the largest cluster (:385)
+            for (int t = lane; t < T; t += 64) count[t] = 0;
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                if (lane + 64 * k < T) atomicAdd(&count[my[k]], 1);
+            __builtin_amdgcn_wave_barrier();
+            biggest = 0;
+            for (int t = lane; t < T; t += 64) biggest = max(biggest, count[t]);
+            for (int off = 32; off > 0; off >>= 1) biggest = max(biggest, __shfl_xor(biggest, off));
+            if (biggest <= max_size || level == GRP_LEVELS - 1) break;   // (:387; no level qualifies: the last one stands)
+        }
+        // ---- sorted(output, key=len) (:394): a cluster's place is the number of clusters that are smaller, or as large with a smaller
+        // first member -- dbscan numbers its clusters by first member, and the sort is stable
+        int n_clusters = 0;
+        for (int t = lane; t < T; t += 64) {
+            if (label[t] != t) continue;
+            const int mine = count[t];
+            int before = 0;
+            for (int u = 0; u < T; ++u)
+                if (label[u] == u && (count[u] < mine || (count[u] == mine && u < t))) ++before;
+            pos[t] = before;
+            ++n_clusters;
+        }
+        for (int off = 32; off > 0; off >>= 1) n_clusters += __shfl_xor(n_clusters, off);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            if (lane + 64 * k < T) group_of[t0 + lane + 64 * k] = pos[my[k]];
+        if (lane == 0) n_groups[s] = n_clusters, eps_index[s] = level, oversize[s] = uint8_t(biggest > max_size ? 1 : 0);
+        __builtin_amdgcn_wave_barrier();   // the next structure overwrites this wavefront's LDS
+    }
+}
+
 }  // namespace tsc

@@ -635,6 +635,30 @@ class Engine:
         check(self.lib.tsc_torsions_timings(self._h, ms))
         return float(ms[0]), float(ms[1])
 
+    def torsion_groups(self, coords, torsions, set_off, max_size=5, min_torsions=9):
+        """tsc_torsion_groups on host arrays: coords f64[S, n, 3], torsions i32[T, 4], set_off i32[S + 1].  Returns (group_of i32[T],
+        n_groups i32[S], eps_index i32[S], oversize u8[S])."""
+        coords = np.ascontiguousarray(coords, dtype=np.float64)
+        S, n = coords.shape[0], coords.shape[1]
+        torsions = np.ascontiguousarray(torsions, dtype=np.int32).reshape(-1, 4)
+        set_off = np.ascontiguousarray(set_off, dtype=np.int32)
+        group_of = np.zeros(len(torsions), dtype=np.int32)
+        n_groups, eps_index, oversize = np.zeros(S, dtype=np.int32), np.full(S, -1, dtype=np.int32), np.zeros(S, dtype=np.uint8)
+        check(self.lib.tsc_torsion_groups(self._h, ptr(coords), C.c_int(S), C.c_int(n), ptr(torsions), ptr(set_off), C.c_int(int(max_size)),
+                                          C.c_int(int(min_torsions)), ptr(group_of), ptr(n_groups), ptr(eps_index), ptr(oversize)))
+        return group_of, n_groups, eps_index, oversize
+
+    def torsion_groups_dev(self, coords, n_structs, n_atoms, torsions, set_off, max_size, min_torsions, group_of, n_groups, eps_index, oversize):
+        """tsc_torsion_groups_dev: coords, torsions and the four outputs on the device; set_off a NumPy array."""
+        set_off = np.ascontiguousarray(set_off, dtype=np.int32)
+        check(self.lib.tsc_torsion_groups_dev(self._h, ptr(coords), C.c_int(n_structs), C.c_int(n_atoms), ptr(torsions), ptr(set_off),
+                                              C.c_int(int(max_size)), C.c_int(int(min_torsions)), ptr(group_of), ptr(n_groups), ptr(eps_index),
+                                              ptr(oversize)))
+
+    def torsion_groups_kernel_ms(self) -> float:
+        """tsc_torsion_groups_timings: the kernel time of this thread's latest torsion_groups[_dev] under set_option("pass_timing", 1)."""
+        return self._kernel_ms(self.lib.tsc_torsion_groups_timings)
+
     # ---- non-covalent interactions -----------------------------------------------------------
     def nci(self, coords, classes, thr, atom_mol, n_mols, candidate, ring_thr, ring_ring_thr, constrained=None, owner_rule=0, want=()):
         """tsc_nci on host arrays (include/tscode_hip.h), already checked (tscode_amd.nci.check_nci_args): coords f64[N, n, 3], classes

@@ -88,12 +88,21 @@ _NCI_PATCHES = {
     "get_nci": (nci.get_nci, ("tscode.embedder", "tscode.nci")),
 }
 
-_OPT_IN = (_ROT_CORR_PATCHES, _DIVERSE_PATCHES, _TOPOLOGY_PATCHES, _NCI_PATCHES)
+# Opt-in (install(csearch=True)): the clustered conformational search, which csearch reaches with its default mode
+# (tscode/torsion_module.py:623-640), and the grouping it starts with (:693).  Both names are bound only where they are defined; the
+# sites are the ones tests/golden/gen_clustered_csearch.py records from the reference's import lines (G26_clustered_csearch_sites.json).
+# The drop-in hands ff_opt, mode 0 and write_torsions to the function it replaced (torsion_module._csearch_originals).
+_CSEARCH_PATCHES = {
+    "clustered_csearch": (torsion_module.clustered_csearch, ("tscode.torsion_module",)),
+    "_group_torsions_dbscan": (torsion_module._group_torsions_dbscan, ("tscode.torsion_module",)),
+}
+
+_OPT_IN = (_ROT_CORR_PATCHES, _DIVERSE_PATCHES, _TOPOLOGY_PATCHES, _NCI_PATCHES, _CSEARCH_PATCHES)
 
 _saved = {}
 
 
-def install(modules=None, per_item=False, rot_corr=False, diverse=False, topology=False, nci=False):
+def install(modules=None, per_item=False, rot_corr=False, diverse=False, topology=False, nci=False, csearch=False):
     """Replace the hot-path functions in every already-imported tscode module: by default those that work on a whole ensemble
     per call (prune_conformers_rmsd, prune_conformers_tfd, get_moi_similarity_matches, _score_embed_poses) and the two embed
     loops (string_embed, cyclical_embed: one GPU call each instead of one Python iteration per pose); with
@@ -101,13 +110,14 @@ def install(modules=None, per_item=False, rot_corr=False, diverse=False, topolog
     equivalent but slower than the reference's jitted code when called one item at a time; with ``rot_corr=True`` also
     prune_conformers_rmsd_rot_corr (_ROT_CORR_PATCHES); with ``diverse=True`` also align_structures and most_diverse_conformers
     (_DIVERSE_PATCHES); with ``topology=True`` also graphize, molecule_check, scramble_check and get_double_bonds_indices
-    (_TOPOLOGY_PATCHES); with ``nci=True`` also get_nci (_NCI_PATCHES).
+    (_TOPOLOGY_PATCHES); with ``nci=True`` also get_nci (_NCI_PATCHES); with ``csearch=True`` also clustered_csearch and
+    _group_torsions_dbscan (_CSEARCH_PATCHES).
     Returns the list of (module, attribute) pairs that were patched."""
     mods = sys.modules if modules is None else modules
     done = []
     table = (list(_PATCHES.items()) + (list(_ROT_CORR_PATCHES.items()) if rot_corr else []) +
              (list(_DIVERSE_PATCHES.items()) if diverse else []) + (list(_TOPOLOGY_PATCHES.items()) if topology else []) +
-             (list(_NCI_PATCHES.items()) if nci else []))
+             (list(_NCI_PATCHES.items()) if nci else []) + (list(_CSEARCH_PATCHES.items()) if csearch else []))
     for attr, (fn, names) in table:
         if not per_item and attr not in _WHOLE_ENSEMBLE and not any(attr in t for t in _OPT_IN):
             continue
@@ -117,6 +127,8 @@ def install(modules=None, per_item=False, rot_corr=False, diverse=False, topolog
                 _saved.setdefault((name, attr), getattr(mod, attr))
                 if attr in ("string_embed", "cyclical_embed") and name == "tscode.embeds":
                     embeds._originals[attr] = _saved[(name, attr)]      # what the drop-in hands the cases it does not cover to
+                if attr in _CSEARCH_PATCHES and name == "tscode.torsion_module":
+                    torsion_module._csearch_originals[attr] = _saved[(name, attr)]
                 setattr(mod, attr, fn)
                 done.append((name, attr))
     return done
@@ -130,3 +142,4 @@ def uninstall(modules=None):
             setattr(mod, attr, fn)
         del _saved[(name, attr)]
     embeds._originals.clear()
+    torsion_module._csearch_originals.clear()

@@ -5,7 +5,9 @@ Reference: ``tscode/utils.py:389-414`` (rotate_dihedral), ``tscode/numba_functio
 torsions, rotation masks and the shuffled angle table from the caller; everything per candidate runs on the GPU, one wavefront
 per candidate.  ``torsion_sets_batch`` makes torsions, folds and masks from coordinates for a whole ensemble (csearch's set-up,
 ``:559-615``: hydrogen bonds and graph searches on the GPU, the rotatability rules per topology class on the host), and
-``csearch_augmentation_batch`` joins the two.
+``csearch_augmentation_batch`` joins the two.  ``group_torsions_batch`` decides per pose which torsions turn together
+(``_group_torsions_dbscan``, ``:373-397``, one wavefront per pose), ``clustered_csearch_batch`` drives the pieces round after round
+(``clustered_csearch`` mode 1, ``:655-847``) and ``csearch_batch`` is the front door (``csearch``, ``:523-653``).
 """
 
 from __future__ import annotations
@@ -18,7 +20,8 @@ from .engine import get_engine
 __all__ = ["rotate_dihedral", "rotate_dihedral_batch", "torsion_comp_check", "csearch_rotate", "csearch_candidates",
            "csearch_rotate_multi", "csearch_candidates_multi", "clustered_csearch_step", "most_diverse_conformers", "diverse_select",
            "hydrogen_bonds_batch", "torsion_sets_batch", "csearch_augmentation_batch", "class_graph", "candidate_quadruplets",
-           "rotatable_torsions", "class_torsion_set"]
+           "rotatable_torsions", "class_torsion_set", "group_torsions_batch", "clustered_csearch_batch", "csearch_batch",
+           "clustered_csearch", "_group_torsions_dbscan"]
 
 
 def csearch_rotate(coords, torsions, masks, angles, thresh=1.5, max_clashes=0):
@@ -830,3 +833,311 @@ def csearch_augmentation_batch(structures, atomnos, constrained_indices, n_out=1
     counts = [len(p) for p in pieces]
     out = np.concatenate(pieces) if pieces else np.zeros((0, n, 3))
     return out, np.repeat(np.arange(S, dtype=np.int32), counts)
+
+
+# ---- the clustered search (tscode/torsion_module.py:373-397, :655-847, per TS candidate there; per ensemble here) ----------------------
+MAX_GROUP_TORSIONS = 512                # GRP_MAX_TORSIONS (csrc/torsions.hpp)
+MIN_TORSIONS_TO_GROUP = 9               # :689
+_csearch_originals = {}                 # what install(csearch=True) replaced: the drop-ins hand over what they do not cover
+
+
+def _set_torsions(st):
+    """The [T, 4] indices of a torsion set given as ``(torsions, masks, n_folds)`` (torsion_sets_batch) or as the indices alone."""
+    t = st[0] if isinstance(st, tuple) else st
+    return np.asarray(t, dtype=np.int32).reshape(-1, 4)
+
+
+def group_torsions_batch(structures, torsion_sets, set_of_structure=None, max_size=5):
+    """_group_torsions_dbscan (tscode/torsion_module.py:373-397) with the ``len(torsions) < 9`` branch of clustered_csearch (:689) for
+    every structure at once (tsc_torsion_groups): ``(groups, eps_index i32[S], oversize bool[S])``.  ``groups[s]`` is a list of index
+    arrays into structure s's torsion set, in the reference's group order (size ascending, ties by first member) and ascending
+    inside a group.  ``torsion_sets``: ``(torsions, masks, n_folds)`` tuples as torsion_sets_batch returns them, or ``[T, 4]`` index
+    arrays; structure s uses set ``set_of_structure[s]`` (default: the only set, or set s when there are S of them; -1: no
+    torsions, no groups).  ``eps_index``: the position of the level kept in 10.0, 9.5, ..., 2.0, -1 where the set was not
+    clustered; ``oversize``: no level gave groups of at most ``max_size``, and the groups of the last one stand."""
+    x = np.ascontiguousarray(structures, dtype=np.float64)
+    if x.ndim == 2:
+        x = x[None]
+    if x.ndim != 3 or x.shape[2] != 3 or not 1 <= x.shape[1] <= 512:
+        raise ValueError(f"structures of shape {x.shape}: expected (n_structures, 1 .. 512 atoms, 3)")
+    if not np.isfinite(x).all():
+        raise ValueError("structures contain NaN or infinity")
+    S, n = x.shape[:2]
+    if int(max_size) != max_size or max_size < 1:
+        raise ValueError("max_size must be a positive integer")
+    tors = [_set_torsions(st) for st in torsion_sets]
+    if set_of_structure is None:
+        if len(tors) == 1:
+            set_of_structure = np.zeros(S, dtype=np.int64)
+        elif len(tors) == S:
+            set_of_structure = np.arange(S)
+        else:
+            raise ValueError(f"{len(tors)} torsion sets for {S} structures: set_of_structure is needed")
+    set_of = np.asarray(set_of_structure, dtype=np.int64).ravel()
+    if len(set_of) != S or (S and (set_of.min() < -1 or set_of.max() >= len(tors))):
+        raise ValueError(f"set_of_structure: expected {S} set indices in [-1, {len(tors)})")
+    for k, t in enumerate(tors):
+        if len(t) > MAX_GROUP_TORSIONS:
+            raise ValueError(f"torsion set {k}: {len(t)} torsions, the engine groups at most {MAX_GROUP_TORSIONS}")
+        if len(t) and (t.min() < 0 or t.max() >= n):
+            raise ValueError(f"torsion set {k}: atom index out of range")
+    counts = np.array([len(tors[k]) if k >= 0 else 0 for k in set_of], dtype=np.int64)
+    if counts.sum() >= 2**31:
+        raise ValueError("2^31 torsions or more in one call")
+    set_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    eps_index, oversize = np.full(S, -1, dtype=np.int32), np.zeros(S, dtype=bool)
+    if counts.sum() == 0:
+        return [[] for _ in range(S)], eps_index, oversize
+    flat = np.concatenate([tors[k] for k in set_of if k >= 0])
+    group_of, n_groups, eps_index, over = get_engine().torsion_groups(x, flat, set_off, int(max_size), MIN_TORSIONS_TO_GROUP)
+    groups = []
+    for s in range(S):
+        g = group_of[set_off[s]:set_off[s + 1]]
+        groups.append([np.flatnonzero(g == k) for k in range(n_groups[s])] if counts[s] else [])
+    return groups, eps_index, over != 0
+
+
+def _trim_seed(seed, coords, call):
+    """The k-means seed of most_diverse_conformers call ``call`` of the search that starts from ``coords``: drawn from
+    ``np.random.default_rng`` seeded with the caller's seed, the call's number and a checksum of the start structure's own bytes --
+    not its position -- so that a structure gets the same rows alone, inside an ensemble, and however the ensemble is sliced."""
+    import zlib
+    return int(np.random.default_rng([int(seed), zlib.crc32(np.ascontiguousarray(coords).tobytes()), int(call)]).integers(2**31 - 1))
+
+
+def _clustered_rounds(x, search, n, n_out, seed, init_rows, log=None, timings=None):
+    """Rounds :722-840 for the structures ``search = {s: (torsions i32[T, 4], masks u8[T, n_atoms], n_folds i32[T], groups)}`` of
+    ``x``.  Returns ({s: output structures}, {s: [(generated, kept) per round]})."""
+    import time
+
+    from .numba_functions import prune_conformers_tfd
+    from .utils import cartesian_product
+    init_rows = {} if init_rows is None else init_rows
+    n_atoms = x.shape[1]
+    starts = {s: x[s][None] for s in search}
+    output = {s: [] for s in search}
+    calls = {s: 0 for s in search}
+    sizes = {s: [] for s in search}
+    final = {}
+    rot_ms, trim_ms, final_ms = [], [], 0.0
+
+    def pick(s, k, structures, torsion_array):
+        c = calls[s]
+        calls[s] += 1
+        rows = init_rows.get((s, c))
+        sd = None if rows is not None or seed is None else _trim_seed(seed, x[s], c)
+        return most_diverse_conformers(k, structures, torsion_array, seed=sd, init_rows=rows)
+
+    def close_round(s, g, new):
+        """What follows the candidate loop of group g of structure s (:783-840), as soon as its rows are complete."""
+        nonlocal final_ms
+        tors, _, _, groups = search[s]
+        t0 = time.perf_counter()
+        generated = len(new)
+        last = g + 1 == len(groups)
+        if not last and n is not None and generated > n:                                   # :809-819
+            new = pick(s, n, new, tors)
+        sizes[s].append((generated, len(new)))
+        if log and not last:
+            log(s, f"  Group {g + 1}/{len(groups)}: {generated} structures built, kept the most diverse {len(new)} as starting points for the next group")
+        if not last:
+            new = np.array(new)                                                            # (its own memory: not a window into the call's rows)
+            output[s].append(new)                                                           # :823
+            starts[s] = new
+        t1 = time.perf_counter()
+        trim_ms[-1] += 1e3 * (t1 - t0)
+        if last:
+            out = np.concatenate(output.pop(s) + [new])                                     # :823, :826
+            out, _ = prune_conformers_tfd(out, tors)                                        # :827
+            if generated > n_out:                                                           # :829: the LAST ROUND's count, not the output's
+                out = pick(s, n_out, out, tors)
+            final[s] = np.asarray(out)
+            del starts[s]
+            final_ms += 1e3 * (time.perf_counter() - t1)
+
+    g = 0
+    while starts:
+        live = [s for s in search if s in starts]
+        rot_ms.append(0.0), trim_ms.append(0.0)
+        # a round is ONE candidate call, unless its candidates would exceed a launch slice: then one call per slice of structures
+        at = 0
+        while at < len(live):
+            part, part_bytes = [], 0
+            sets, set_index, set_of_start = [], {}, []
+            while at < len(live):
+                s = live[at]
+                tors, masks, folds, groups = search[s]
+                idx = groups[g]
+                key = (tors[idx].tobytes(), masks[idx].tobytes(), folds[idx].tobytes())
+                table_rows = int(np.prod([len(N_FOLD_ANGLES[int(f)]) for f in folds[idx]]))
+                need = len(starts[s]) * (table_rows + 1) * n_atoms * 24
+                if part and part_bytes + need > MULTI_SCRATCH_BYTES:
+                    break
+                if key not in set_index:
+                    set_index[key] = len(sets)
+                    sets.append((tors[idx], masks[idx], cartesian_product(*[N_FOLD_ANGLES[int(f)] for f in folds[idx]])))   # :726
+                if log:
+                    log(s, f"\n> Group {g + 1}/{len(groups)}: {len(idx)} bonds, n-folds {folds[idx].tolist()}, {len(starts[s])} "
+                           f"starting point{'s' if len(starts[s]) > 1 else ''} = {table_rows * len(starts[s])} conformers")
+                set_of_start += [set_index[key]] * len(starts[s])
+                part.append(s)
+                at += 1
+                part_bytes += need
+            t0 = time.perf_counter()
+            rows, start_index = csearch_candidates_multi(np.concatenate([starts[s] for s in part]), sets, set_of_start, n_out=None,
+                                                         include_start=True)
+            rot_ms[-1] += 1e3 * (time.perf_counter() - t0)
+            bounds = np.searchsorted(start_index, np.cumsum([0] + [len(starts[s]) for s in part]))
+            for k, s in enumerate(part):
+                close_round(s, g, rows[bounds[k]:bounds[k + 1]])
+            del rows
+        g += 1
+    if timings is not None:
+        timings.update(rotation_ms=rot_ms, trim_ms=trim_ms, final_ms=final_ms)
+    return final, sizes
+
+
+def clustered_csearch_batch(structures, atomnos, constrained_indices=None, keep_hb=False, n=100, n_out=100, max_size=5, seed=None,
+                            init_rows=None, info=None, timings=None):
+    """clustered_csearch mode 1 (tscode/torsion_module.py:655-847) as csearch reaches it (:523-640), for every structure of an
+    ensemble: ``(new_structures [K, n_atoms, 3], start_index [K])``, shaped like csearch_augmentation_batch's.
+
+    * Set-up: torsion_sets_batch.  A segmented structure contributes no rows (``info["segmented"]``), one without rotatable bonds
+      contributes itself (:619-621).
+    * Groups: group_torsions_batch on each structure's own coordinates -- two poses of one topology class may group differently.
+    * Round g: ONE csearch_candidates_multi(..., n_out=None, include_start=True) call with the current starting points of every
+      structure that still has a group g, each start carrying its structure's set for that group; the table is cartesian_product
+      of the group's n-fold angles, not shuffled (:726).  Where the candidates of a round would take more than MULTI_SCRATCH_BYTES
+      the round is split into one call per slice of structures, so the host never holds more than one slice of candidates plus
+      the kept rows: a structure's round is closed as soon as its rows are there.
+    * Between groups, per structure: ``most_diverse_conformers(n, new_structures, torsion_array)`` iff this is not the last group
+      and there are more than ``n`` (:809-819); the next round starts from the ALIGNED coordinates it returns, as in the reference.
+      Every round's (trimmed) structures go to the output, the repeated starting points too (:823).
+    * After the last group: prune_conformers_tfd on the output, then ``most_diverse_conformers(n_out, ...)`` iff the LAST ROUND
+      built more than ``n_out`` structures -- not the output (:829, reproduced as it is).
+    * The k-means initialisation, which the reference leaves to chance: ``init_rows`` maps ``(structure, call)`` -- the call's
+      number among that structure's most_diverse_conformers calls -- to the rows to start from; otherwise, with ``seed``, each
+      such call gets a seed of its own (_trim_seed) that depends on the structure's coordinates and the call, not on its place in
+      the ensemble; with neither, most_diverse_conformers draws one from ``np.random``.
+
+    ``info`` (a dict) receives ``segmented``, ``torsions``, ``n_folds``, ``groups``, ``eps_index``, ``oversize`` and ``round_sizes``
+    (per structure and round: structures built, structures kept); ``timings`` the stages' milliseconds."""
+    import time
+    if n is not None and (int(n) != n or n < 1):
+        raise ValueError("n must be a positive integer or None")
+    if int(n_out) != n_out or n_out < 1:
+        raise ValueError("n_out must be a positive integer")
+    if int(max_size) != max_size or max_size < 1:
+        raise ValueError("max_size must be a positive integer")
+    if init_rows is not None and not hasattr(init_rows, "get"):
+        raise ValueError("init_rows must map (structure, call) to row indices")
+    t0 = time.perf_counter()
+    ts = torsion_sets_batch(structures, atomnos, constrained_indices, keep_hb, timings=timings)
+    if timings is not None:
+        timings["setup_ms"] = 1e3 * (time.perf_counter() - t0)
+    x = np.ascontiguousarray(structures, dtype=np.float64)
+    if x.ndim == 2:
+        x = x[None]
+    S, n_atoms = x.shape[:2]
+    t0 = time.perf_counter()
+    groups, eps_index, oversize = group_torsions_batch(x, ts.sets, ts.set_of_structure, max_size)
+    if timings is not None:
+        timings["groups_ms"] = 1e3 * (time.perf_counter() - t0)
+        timings["groups_kernel_ms"] = get_engine().torsion_groups_kernel_ms() if any(groups) else -1.0
+    search = {}
+    for s in range(S):
+        if not ts.segmented[s] and groups[s]:
+            tors, masks, folds = ts.sets[ts.set_of_structure[s]]
+            search[s] = (tors, masks, np.asarray(folds), groups[s])
+    final, sizes = _clustered_rounds(x, search, n, int(n_out), seed, init_rows, timings=timings)
+    pieces = []
+    for s in range(S):
+        if ts.segmented[s]:
+            pieces.append(np.zeros((0, n_atoms, 3)))
+        else:
+            pieces.append(final[s] if s in final else x[s][None])                           # :619-621
+    if info is not None:
+        own = [ts.sets[k] if k >= 0 else None for k in ts.set_of_structure]
+        info.update(segmented=ts.segmented, groups=groups, eps_index=eps_index, oversize=oversize,
+                    torsions=[None if st is None else st[0] for st in own], n_folds=[None if st is None else st[2] for st in own],
+                    round_sizes=[sizes.get(s, []) for s in range(S)])
+    out = np.concatenate(pieces) if pieces else np.zeros((0, n_atoms, 3))
+    return out, np.repeat(np.arange(S, dtype=np.int32), [len(p) for p in pieces])
+
+
+def csearch_batch(structures, atomnos, constrained_indices=None, keep_hb=False, mode=1, n=100, n_out=100, **kw):
+    """csearch (tscode/torsion_module.py:523-653) for an ensemble: ``(new_structures [K, n_atoms, 3], start_index [K])``.  Mode 1,
+    the reference's default: clustered_csearch_batch.  Mode 2: csearch_augmentation_batch with the caller's ``n_out`` (``n`` has no
+    part in it).  Mode 0 keeps the structures of lowest energy and needs an external optimiser (ff_opt): ValueError."""
+    if mode == 1:
+        return clustered_csearch_batch(structures, atomnos, constrained_indices, keep_hb=keep_hb, n=n, n_out=n_out, **kw)
+    if mode == 2:
+        return csearch_augmentation_batch(structures, atomnos, constrained_indices, n_out=n_out, keep_hb=keep_hb, **kw)
+    if mode == 0:
+        raise ValueError("mode 0 ranks the conformers by the energies of an external optimiser (ff_opt=True), which this package does not run")
+    raise ValueError(f"mode {mode!r}: 1 (clustered, most diverse) or 2 (random rotations)")
+
+
+# -- drop-ins with the reference's signatures (install(csearch=True))
+def _reach_masks(graph, torsions, n_atoms):
+    """_get_rotation_mask (:301-325) of every torsion, already oriented, in the caller's graph (tsc_torsion_reach, nothing constrained)."""
+    from .graph_manipulations import pack_edges
+    bits = pack_edges([(int(a), int(b)) for a, b in graph.edges], n_atoms)[None]
+    return get_engine().torsion_reach(bits, torsions, np.array([0, len(torsions)], dtype=np.int32), None)[1]
+
+
+def _group_torsions_dbscan(coords, torsions, max_size=5):
+    """Drop-in for tscode.torsion_module._group_torsions_dbscan (:373-397): the torsion objects in groups, smallest group first.
+    Always clusters, like the reference's function (the ``< 9`` branch is its caller's)."""
+    torsions = list(torsions)
+    quads = np.array([t.torsion for t in torsions], dtype=np.int32).reshape(-1, 4)
+    x = np.ascontiguousarray(coords, dtype=np.float64)[None]
+    if len(quads) > MAX_GROUP_TORSIONS:
+        raise ValueError(f"{len(quads)} torsions, the engine groups at most {MAX_GROUP_TORSIONS}")
+    if not len(quads):
+        return []
+    group_of, n_groups, _, _ = get_engine().torsion_groups(x, quads, np.array([0, len(quads)], dtype=np.int32), int(max_size), 0)
+    return [[torsions[t] for t in np.flatnonzero(group_of == k)] for k in range(n_groups[0])]
+
+
+def clustered_csearch(coords, atomnos, torsions, graph, constrained_indices=None, ff_opt=False, n=100, n_out=100, mode=1, calc=None,
+                      method=None, title='test', logfunction=print, interactive_print=True, write_torsions=False, *, seed=None,
+                      init_rows=None):
+    """Drop-in for tscode.torsion_module.clustered_csearch (:655-847), mode 1: one structure through the rounds of
+    clustered_csearch_batch.  ``torsions``: objects with ``.torsion`` (already oriented by sort_torsion) and ``.n_fold``; the
+    rotation masks are read off ``graph`` on the GPU.  ``ff_opt``, ``mode == 0`` and ``write_torsions`` go to the function that
+    install(csearch=True) replaced; without one that is a RuntimeError.  ``seed`` / ``init_rows`` (keys ``(0, call)``) are this
+    package's additions: see clustered_csearch_batch."""
+    import time
+    if ff_opt or mode == 0 or write_torsions:
+        original = _csearch_originals.get("clustered_csearch")
+        if original is None:
+            raise RuntimeError("clustered_csearch with ff_opt, mode 0 or write_torsions needs the reference's function: "
+                               "tscode_amd.install(csearch=True) records it")
+        return original(coords, atomnos, torsions, graph, constrained_indices=constrained_indices, ff_opt=ff_opt, n=n, n_out=n_out, mode=mode,
+                        calc=calc, method=method, title=title, logfunction=logfunction, interactive_print=interactive_print,
+                        write_torsions=write_torsions)
+    if mode != 1:
+        raise ValueError("The mode keyword can only be 0 or 1")
+    t_start = time.perf_counter()
+    torsions = list(torsions)
+    x = np.ascontiguousarray(coords, dtype=np.float64)[None]
+    n_atoms = x.shape[1]
+    quads = np.array([t.torsion for t in torsions], dtype=np.int32).reshape(-1, 4)
+    folds = np.array([t.n_fold for t in torsions], dtype=np.int32)
+    if not len(quads):
+        raise ValueError("clustered_csearch needs at least one torsion")
+    groups, _, _ = group_torsions_batch(x, [quads], None, max_size=5)
+    logfunction('\n> Torsion list: (indices: n-fold)')
+    for i, t in enumerate(torsions):
+        logfunction(f' {i} - {str(t.torsion):21s} : {t.n_fold}-fold')
+    logfunction('\n> Rotable bonds ids: ' + ' '.join(str(i) for i in sorted({int(i) for q in quads for i in q[1:3]})))
+    logfunction(f'\n--> Clustered CSearch on {title}\n    mode 1 (diversity) - {len(torsions)} torsions in {len(groups[0])} '
+                f'group{"s" if len(groups[0]) != 1 else ""} - {[len(g) for g in groups[0]]}')
+    search = {0: (quads, _reach_masks(graph, quads, n_atoms), folds, groups[0])}
+    final, _ = _clustered_rounds(x, search, n, n_out, seed, init_rows, log=lambda s, text: logfunction(text))
+    out = final[0]
+    share = round(100 * len(out) / float(np.prod(folds.astype(np.float64))), 2)
+    logfunction(f'  Selected the most diverse {len(out)} conformers, about {share} % of the total conformational space - '
+                f'CSearch time {time.perf_counter() - t_start:.1f} s')
+    return out
