@@ -229,6 +229,25 @@ int tsc_torsion_fingerprints(tsc_ctx *ctx, const double *coords, int64_t n_struc
 int tsc_tfd_first_similar(tsc_ctx *ctx, const float *tf, int64_t n_structs, int n_quads, int64_t d, int64_t k, int64_t num_active,
                           double thresh, int32_t *first);
 
+/* The same for many small ensembles per call (tscode/numba_functions.py:142-231, one run of the schedule :160-226 per segment).
+ * tsc_tfd_batch_fingerprints_dev: _get_tf_mat (:233-240) of n_segments ensembles in one launch.  Segment s has n_structs[s]
+ * structures of n_atoms[s] atoms at coords + offsets[s] (offsets i64[n_segments + 1] in doubles, offsets[0] = 0) and n_quads[s]
+ * quadruplets, its own, back to back in quads i32[sum n_quads, 4]; n_structs[s] = 0 and n_quads[s] = 0 are allowed.  coords, quads
+ * and the tables are host arrays; tf f32[tf_count] is DEVICE memory (tsc_malloc) and receives the segments' fingerprints back to
+ * back, tf_count = sum n_structs[s] * n_quads[s], where they stay for every schedule slot.
+ * tsc_tfd_batch_pass_dev: the pair search of one schedule slot (:171-199) in one launch, for the n_open segments whose gate (:166)
+ * is open in it.  Entry q: n_structs[q] >= 1 fingerprints of n_quads[q] angles at tf + elem0[q], pass geometry d[q], k[q],
+ * num_active[q] and thresh[q] as tsc_tfd_first_similar takes them, rows [row0[q], row0[q] + n_structs[q]) of first, ascending and
+ * disjoint.  first i32[total_rows] (host): first[row0[q] + i] is what tsc_tfd_first_similar gives row i of that segment alone --
+ * an index inside the segment -- and -1 for every row of no open segment.  A row never looks at a column of another segment.
+ * An invalid entry refuses the whole call before any launch; tsc_last_error() names it. */
+int tsc_tfd_batch_fingerprints_dev(tsc_ctx *ctx, const double *coords, const int64_t *offsets, const int32_t *n_structs,
+                                   const int32_t *n_atoms, const int32_t *quads, const int32_t *n_quads, int64_t n_segments, float *tf,
+                                   int64_t tf_count);
+int tsc_tfd_batch_pass_dev(tsc_ctx *ctx, const float *tf, int64_t tf_count, const int64_t *elem0, const int64_t *row0,
+                           const int32_t *n_structs, const int32_t *n_quads, const int64_t *d, const int64_t *k, const int64_t *num_active,
+                           const double *thresh, int64_t n_open, int64_t total_rows, int32_t *first);
+
 /* Moments of inertia and embed scores.
  * tsc_inertia_moments: tscode/algebra.py:165-186 get_inertia_moments for every structure -- out f64[n_structs, 3], the
  * eigenvalues of the inertia tensor about the centre of mass ordered by absolute value; masses f64[n_atoms].
@@ -675,6 +694,24 @@ int tsc_diverse_select(tsc_ctx *ctx, const double *structures, int64_t N, int n_
                        const double *energies, int max_iter, double tol, double *aligned_out, int32_t *labels, int32_t *picked,
                        int *n_iter);
 int tsc_diverse_timings(tsc_ctx *ctx, float *ms4);
+
+/* tsc_diverse_select for many small ensembles per call (csrc/diverse_batch.hpp; tscode/torsion_module.py:882-922 per segment).
+ * Segment s has n_structs[s] structures of n_atoms[s] atoms at structures + offsets[s] (offsets i64[n_segments + 1] in doubles,
+ * offsets[0] = 0) and k[s] clusters; the limits per segment are tsc_diverse_select's.  flags u8[n_segments]: bit 0 = the segment
+ * has energies, at energies + (the sum of n_structs before it) in energies f64[sum n_structs] (may be NULL when no segment has
+ * any); bit 1 = its initial centres are k-means++ seeds from u + (the sum of k before it) in u f64[sum k] (may be NULL when no
+ * segment is seeded), and its part of init_rows i32[sum k] RECEIVES them; otherwise that part is read.  max_iter and tol hold
+ * for every segment.  Outputs, segment after segment: aligned_out f64 like structures, labels i32[sum n_structs], picked i32[sum
+ * k] (-1 for an empty cluster), n_iter i32[n_segments].
+ * Each segment's results are those of tsc_diverse_select on it alone, bit for bit: the segmented kernels call the same device
+ * functions on the segment's own grid, so every sum keeps its fixed order.  Each segment stops by the single call's rule (:889-890
+ * as tsc_kmeans_lloyd states it), decided on the device; the host reads one 8-byte record per iteration for the whole batch, and
+ * the workgroups of a finished segment return at once.  Seeding takes one pair of launches per seed index for all segments that
+ * still need it.  An invalid segment refuses the whole call before any launch; tsc_last_error() names the segment. */
+int tsc_diverse_select_batch(tsc_ctx *ctx, const double *structures, const int64_t *offsets, const int32_t *n_structs,
+                             const int32_t *n_atoms, const int32_t *k, int64_t n_segments, int32_t *init_rows, const double *u,
+                             const double *energies, const uint8_t *flags, int max_iter, double tol, double *aligned_out,
+                             int32_t *labels, int32_t *picked, int32_t *n_iter);
 
 /* Bond graphs from distances and their difference to an expected graph, for a whole ensemble per call (csrc/topology.hpp): the
  * topology test the reference applies to every structure that survives the embed and prune steps.

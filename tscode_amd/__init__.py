@@ -23,11 +23,11 @@ from .reactive_atoms import (ORB_DIM_DICT, ReactiveMolecule, atom_type, orbital_
 from .engine import Engine, FragmentSet, device_count, get_engine  # noqa: F401
 from .install import install, uninstall  # noqa: F401
 from .numba_functions import (_get_tf_mat, compenetration_check, compenetration_mask, count_clashes, get_torsion_fingerprint,  # noqa: F401
-                              prune_conformers_tfd, tfd_similarity)
+                              prune_conformers_tfd, prune_conformers_tfd_batch, tfd_similarity)
 from .optimization_methods import (_score_embed_poses, fitness_check, fitness_mask, get_inertia_moments,  # noqa: F401
                                    get_moi_similarity_matches, prune_by_moment_of_inertia)
 from .torsion_module import (clustered_csearch_batch, clustered_csearch_step, csearch_augmentation_batch, csearch_batch, csearch_candidates, csearch_candidates_multi,  # noqa: F401
-                             csearch_rotate, csearch_rotate_multi, diverse_select, group_torsions_batch, hydrogen_bonds_batch, torsion_sets_batch, most_diverse_conformers, rotate_dihedral, rotate_dihedral_batch,
+                             csearch_rotate, csearch_rotate_multi, diverse_select, diverse_select_batch, group_torsions_batch, hydrogen_bonds_batch, torsion_sets_batch, most_diverse_conformers, most_diverse_conformers_batch, rotate_dihedral, rotate_dihedral_batch,
                              torsion_comp_check)
 from .hypermolecule_class import align_structures  # noqa: F401
 from .kmeans import kmeans_lloyd, kmeans_plusplus_rows  # noqa: F401

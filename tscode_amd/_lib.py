@@ -98,6 +98,8 @@ _SIGNATURES = {
     "tsc_embed_scores": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
     "tsc_torsion_fingerprints": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, _vp]),
     "tsc_tfd_first_similar": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, _vp]),
+    "tsc_tfd_batch_fingerprints_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64]),
+    "tsc_tfd_batch_pass_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp]),
     "tsc_string_embed_params": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int, _vp, _vp, _vp]),
     "tsc_string_embed_params_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int, _vp, _vp, _vp]),
     "tsc_cyclical_embed_params": (C.c_int, [_vp] * 10 + [C.c_int64, _vp, _vp]),
@@ -167,6 +169,7 @@ _SIGNATURES = {
     "tsc_diverse_select": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp,
                                      C.POINTER(C.c_int)]),
     "tsc_diverse_timings": (C.c_int, [_vp, c_f32p]),
+    "tsc_diverse_select_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp]),
     "tsc_bond_delta": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int64, _vp, _vp, _vp, _vp]),
     "tsc_bond_delta_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int64, _vp, _vp, _vp,
                                      _vp]),

@@ -20,30 +20,6 @@ void reset_times() {
     for (float &t : g_times) t = -1.f;
 }
 
-// scikit-learn refuses NaN / infinity with a ValueError; here they would turn every distance into NaN (no row ever nearer to any
-// centre) -- refused on the host arrays before anything touches the device
-int check_finite(const char *who, const char *what, const double *v, size_t count) {
-    for (size_t q = 0; q < count; ++q) TSC_REQUIRE(std::isfinite(v[q]), "%s: %s[%zu] is not finite", who, what, q);
-    return 0;
-}
-int check_uniforms(const char *who, const double *u, int k) {
-    for (int j = 0; j < k; ++j) TSC_REQUIRE(u[j] >= 0.0 && u[j] < 1.0, "%s: u[%d] not in [0, 1)", who, j);
-    return 0;
-}
-
-int check_shape(const char *who, int64_t N, int n_atoms) {
-    TSC_REQUIRE(N >= 1 && N < INT32_MAX, "%s: %lld structures (1 .. %d)", who, (long long)N, INT32_MAX - 1);
-    TSC_REQUIRE(n_atoms >= 1 && n_atoms <= DV_MAX_ATOMS, "%s: %d atoms per structure (1 .. %d)", who, n_atoms, DV_MAX_ATOMS);
-    return 0;
-}
-int check_k(const char *who, int64_t N, int64_t D, int k) {
-    TSC_REQUIRE(N >= 1 && N < INT32_MAX, "%s: %lld rows (1 .. %d)", who, (long long)N, INT32_MAX - 1);
-    TSC_REQUIRE(D >= 1 && D <= 3 * DV_MAX_ATOMS, "%s: %lld columns (1 .. %d)", who, (long long)D, 3 * DV_MAX_ATOMS);
-    TSC_REQUIRE(k >= 1 && k <= DV_MAX_K, "%s: %d clusters (1 .. %d)", who, k, DV_MAX_K);
-    TSC_REQUIRE(k <= N, "%s: %d clusters for %lld rows", who, k, (long long)N);
-    return 0;
-}
-
 int align_dev(tsc_ctx *c, HostCall &h, const double *d_in, int64_t N, int n, const int32_t *idx_host, int n_idx, double *d_out) {
     int32_t *d_idx = nullptr;
     if (idx_host && n_idx > 0) {

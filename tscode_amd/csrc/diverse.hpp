@@ -16,6 +16,11 @@
 //                         clusters (scikit-learn's _relocate_empty_clusters_dense), the new centre and its squared shift.
 //   k_diverse_pick        one workgroup per cluster: the member to keep (torsion_module.py:894-922).
 //   k_kmeans_seed_update / k_kmeans_seed_pick   k-means++ without local trials, the uniforms given by the caller.
+//
+// Every kernel's body is a __device__ function (dv_*) of the problem's own pointers and sizes and of the workgroup's place in the
+// problem's own grid; the __global__ kernel here is its one-line wrapper.  The kernels of diverse_batch.hpp, which serve many ensembles
+// per launch, look up (segment, local workgroup) and call the same function: a segment's sums are taken in the order the single call
+// takes them, and its results are the single call's bit for bit.
 #pragma once
 #include "common.hpp"
 #include "rmsd.hpp"
@@ -48,10 +53,10 @@ __device__ inline void dv_centroid(const double *__restrict__ s, const int32_t *
 
 // idx == null: every atom (n_idx == n).  Structure 0 is only centred (:53, :58); structure t >= 1 is centred on the mean of its indexed
 // atoms (:55) and turned by the proper rotation that takes its indexed atoms onto the reference's (:63, :70).
-inline __global__ __launch_bounds__(256) void k_align_structures(const double *__restrict__ in, int64_t N, int n, const int32_t *__restrict__ idx,
-                                                                 int n_idx, double *__restrict__ out) {
+__device__ inline void dv_align_structures(const double *__restrict__ in, int64_t N, int n, const int32_t *__restrict__ idx, int n_idx,
+                                           double *__restrict__ out, int64_t block) {
     const int lane = threadIdx.x & 63;
-    const int64_t t = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    const int64_t t = block * 4 + (threadIdx.x >> 6);
     if (t >= N) return;
     const double *ref = in, *tgt = in + t * n * 3;
     double *o = out + t * n * 3;
@@ -92,14 +97,19 @@ inline __global__ __launch_bounds__(256) void k_align_structures(const double *_
         o[3 * a + 2] = R20 * px + R21 * py + R22 * pz;
     }
 }
+inline __global__ __launch_bounds__(256) void k_align_structures(const double *__restrict__ in, int64_t N, int n, const int32_t *__restrict__ idx,
+                                                                 int n_idx, double *__restrict__ out) {
+    dv_align_structures(in, N, n, idx, n_idx, out, blockIdx.x);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // column statistics of X[N, D] in a fixed order: grid (ceil(D / 64), chunks), 256 threads = 64 columns x 4 row lanes
 
-inline __global__ __launch_bounds__(256) void k_col_partial(const double *__restrict__ X, int64_t N, int D, int squares, double *__restrict__ part) {
+// (workgroup (bx, by) of a grid (ceil(D / 64), chunks))
+__device__ inline void dv_col_partial(const double *__restrict__ X, int64_t N, int D, int squares, double *__restrict__ part, int bx, int by, int chunks) {
     __shared__ double s[4][64];
-    const int col = threadIdx.x & 63, g = threadIdx.x >> 6, d = blockIdx.x * 64 + col;
-    const int64_t per = ceil_div<int64_t>(N, gridDim.y), lo = per * blockIdx.y, hi = lo + per < N ? lo + per : N;
+    const int col = threadIdx.x & 63, g = threadIdx.x >> 6, d = bx * 64 + col;
+    const int64_t per = ceil_div<int64_t>(N, chunks), lo = per * by, hi = lo + per < N ? lo + per : N;
     double acc = 0.0;
     if (d < D)
         for (int64_t i = lo + g; i < hi; i += 4) {
@@ -108,15 +118,21 @@ inline __global__ __launch_bounds__(256) void k_col_partial(const double *__rest
         }
     s[g][col] = acc;
     __syncthreads();
-    if (g == 0 && d < D) part[size_t(blockIdx.y) * D + d] = ((s[0][col] + s[1][col]) + s[2][col]) + s[3][col];
+    if (g == 0 && d < D) part[size_t(by) * D + d] = ((s[0][col] + s[1][col]) + s[2][col]) + s[3][col];
+}
+inline __global__ __launch_bounds__(256) void k_col_partial(const double *__restrict__ X, int64_t N, int D, int squares, double *__restrict__ part) {
+    dv_col_partial(X, N, D, squares, part, blockIdx.x, blockIdx.y, gridDim.y);
 }
 // out[d] = scale * sum over the chunks, in chunk order
-inline __global__ __launch_bounds__(256) void k_col_finish(const double *__restrict__ part, int chunks, int D, double scale, double *__restrict__ out) {
-    const int d = blockIdx.x * 256 + threadIdx.x;
+__device__ inline void dv_col_finish(const double *__restrict__ part, int chunks, int D, double scale, double *__restrict__ out, int block) {
+    const int d = block * 256 + threadIdx.x;
     if (d >= D) return;
     double acc = 0.0;
     for (int q = 0; q < chunks; ++q) acc += part[size_t(q) * D + d];
     out[d] = acc * scale;
+}
+inline __global__ __launch_bounds__(256) void k_col_finish(const double *__restrict__ part, int chunks, int D, double scale, double *__restrict__ out) {
+    dv_col_finish(part, chunks, D, scale, out, blockIdx.x);
 }
 // X[i, d] += sign * v[d]
 inline __global__ __launch_bounds__(256) void k_shift_cols(double *__restrict__ X, int64_t rows, int D, const double *__restrict__ v, double sign) {
@@ -128,7 +144,7 @@ inline __global__ __launch_bounds__(256) void k_gather_rows(const double *__rest
     for (int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x; e < total; e += int64_t(gridDim.x) * 256) out[e] = X[int64_t(rows[e / D]) * D + e % D];
 }
 // out[0] = scale * sum v[0 .. n) in a fixed order: one workgroup of 1024, a contiguous piece per thread, then a tree
-inline __global__ __launch_bounds__(1024) void k_sum_fixed(const double *__restrict__ v, int64_t n, double scale, double *__restrict__ out) {
+__device__ inline void dv_sum_fixed(const double *__restrict__ v, int64_t n, double scale, double *__restrict__ out) {
     __shared__ double s[1024];
     const int64_t per = ceil_div<int64_t>(n, 1024), lo = per * threadIdx.x, hi = lo + per < n ? lo + per : n;
     double acc = 0.0;
@@ -141,10 +157,13 @@ inline __global__ __launch_bounds__(1024) void k_sum_fixed(const double *__restr
     }
     if (threadIdx.x == 0) out[0] = s[0] * scale;
 }
+inline __global__ __launch_bounds__(1024) void k_sum_fixed(const double *__restrict__ v, int64_t n, double scale, double *__restrict__ out) {
+    dv_sum_fixed(v, n, scale, out);
+}
 // out[r] = |X[r]|^2, one wavefront per row
-inline __global__ __launch_bounds__(256) void k_row_norms(const double *__restrict__ X, int64_t rows, int D, double *__restrict__ out) {
+__device__ inline void dv_row_norms(const double *__restrict__ X, int64_t rows, int D, double *__restrict__ out, int64_t block) {
     const int lane = threadIdx.x & 63;
-    const int64_t r = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    const int64_t r = block * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
     double acc = 0.0;
     for (int d = lane; d < D; d += 64) {
@@ -154,6 +173,9 @@ inline __global__ __launch_bounds__(256) void k_row_norms(const double *__restri
     acc = dv_wave_sum(acc);
     if (lane == 0) out[r] = acc;
 }
+inline __global__ __launch_bounds__(256) void k_row_norms(const double *__restrict__ X, int64_t rows, int D, double *__restrict__ out) {
+    dv_row_norms(X, rows, D, out, blockIdx.x);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // the assignment step
@@ -161,13 +183,13 @@ inline __global__ __launch_bounds__(256) void k_row_norms(const double *__restri
 constexpr int KA_ROWS = 64, KA_DS = 32, KA_LD = KA_DS + 4;   // (row stride 36 doubles: the 16 rows x 4 columns a wavefront reads fall on 64 distinct 8-byte slots)
 
 template <int NT>
-__global__ __launch_bounds__(256) void k_kmeans_assign(const double *__restrict__ X, int64_t N, int D, const double *__restrict__ C, int k,
-                                                       const double *__restrict__ xn, const double *__restrict__ cn, int32_t *__restrict__ labels,
-                                                       double *__restrict__ own_d2, int *__restrict__ changed) {
+__device__ inline void dv_kmeans_assign(const double *__restrict__ X, int64_t N, int D, const double *__restrict__ C, int k,
+                                        const double *__restrict__ xn, const double *__restrict__ cn, int32_t *__restrict__ labels,
+                                        double *__restrict__ own_d2, int *__restrict__ changed, int64_t block) {
     __shared__ double sX[KA_ROWS * KA_LD];
     __shared__ double sC[NT * 16 * KA_LD];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, rc = lane & 15, g = lane >> 4;
-    const int64_t row0 = int64_t(blockIdx.x) * KA_ROWS;
+    const int64_t row0 = block * KA_ROWS;
     double bd[4];
     int bc[4];
 #pragma unroll
@@ -226,6 +248,12 @@ __global__ __launch_bounds__(256) void k_kmeans_assign(const double *__restrict_
     }
     if (diff) atomicAdd(changed, diff);
 }
+template <int NT>
+__global__ __launch_bounds__(256) void k_kmeans_assign(const double *__restrict__ X, int64_t N, int D, const double *__restrict__ C, int k,
+                                                       const double *__restrict__ xn, const double *__restrict__ cn, int32_t *__restrict__ labels,
+                                                       double *__restrict__ own_d2, int *__restrict__ changed) {
+    dv_kmeans_assign<NT>(X, N, D, C, k, xn, cn, labels, own_d2, changed, blockIdx.x);
+}
 
 // own_d2[i] = |x_i - C[labels[i]]|^2 by direct differences, one wavefront per row.  only_if_empty: nothing to do unless a cluster is
 // empty (the relocation is what needs the exact values; the assignment's come from the expanded form)
@@ -234,11 +262,10 @@ __device__ inline bool dv_any_empty(const int32_t *__restrict__ counts, int k, i
     for (int c = lane; c < k; c += 64) any |= counts[c] == 0;
     return __ballot(any) != 0;
 }
-inline __global__ __launch_bounds__(256) void k_own_d2(const double *__restrict__ X, int64_t N, int D, const double *__restrict__ C,
-                                                       const int32_t *__restrict__ labels, const int32_t *__restrict__ counts, int k, int only_if_empty,
-                                                       double *__restrict__ own_d2) {
+__device__ inline void dv_own_d2(const double *__restrict__ X, int64_t N, int D, const double *__restrict__ C, const int32_t *__restrict__ labels,
+                                 const int32_t *__restrict__ counts, int k, int only_if_empty, double *__restrict__ own_d2, int64_t block) {
     const int lane = threadIdx.x & 63;
-    const int64_t i = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    const int64_t i = block * 4 + (threadIdx.x >> 6);
     if (i >= N) return;
     if (only_if_empty && !dv_any_empty(counts, k, lane)) return;
     const double *c = C + int64_t(labels[i]) * D;
@@ -249,6 +276,11 @@ inline __global__ __launch_bounds__(256) void k_own_d2(const double *__restrict_
     }
     acc = dv_wave_sum(acc);
     if (lane == 0) own_d2[i] = acc;
+}
+inline __global__ __launch_bounds__(256) void k_own_d2(const double *__restrict__ X, int64_t N, int D, const double *__restrict__ C,
+                                                       const int32_t *__restrict__ labels, const int32_t *__restrict__ counts, int k, int only_if_empty,
+                                                       double *__restrict__ own_d2) {
+    dv_own_d2(X, N, D, C, labels, counts, k, only_if_empty, own_d2, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -263,20 +295,22 @@ __device__ inline int dv_block_sum_int(int v, int *s) {   // 256 threads; every 
     __syncthreads();
     return s[0] + s[1] + s[2] + s[3];
 }
-inline __global__ __launch_bounds__(256) void k_label_count(const int32_t *__restrict__ labels, int64_t N, int32_t *__restrict__ counts) {
+__device__ inline void dv_label_count(const int32_t *__restrict__ labels, int64_t N, int32_t *__restrict__ counts, int c) {
     __shared__ int s[4];
-    const int c = blockIdx.x;
     int mine = 0;
     for (int64_t i = threadIdx.x; i < N; i += 256) mine += labels[i] == c;
     const int total = dv_block_sum_int(mine, s);
     if (threadIdx.x == 0) counts[c] = total;
 }
+inline __global__ __launch_bounds__(256) void k_label_count(const int32_t *__restrict__ labels, int64_t N, int32_t *__restrict__ counts) {
+    dv_label_count(labels, N, counts, blockIdx.x);
+}
 // members[offs[c] .. offs[c] + counts[c]) = the rows of cluster c, ascending
-inline __global__ __launch_bounds__(256) void k_label_bucket(const int32_t *__restrict__ labels, int64_t N, const int32_t *__restrict__ counts, int k,
-                                                             int32_t *__restrict__ offs, int32_t *__restrict__ members) {
+__device__ inline void dv_label_bucket(const int32_t *__restrict__ labels, int64_t N, const int32_t *__restrict__ counts, int k, int32_t *__restrict__ offs,
+                                       int32_t *__restrict__ members, int c) {
     __shared__ int s[4];
     __shared__ int s_wave[4];
-    const int c = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     int before = 0;
     for (int q = threadIdx.x; q < c; q += 256) before += counts[q];
     int base = dv_block_sum_int(before, s);
@@ -297,6 +331,10 @@ inline __global__ __launch_bounds__(256) void k_label_bucket(const int32_t *__re
         base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
     }
 }
+inline __global__ __launch_bounds__(256) void k_label_bucket(const int32_t *__restrict__ labels, int64_t N, const int32_t *__restrict__ counts, int k,
+                                                             int32_t *__restrict__ offs, int32_t *__restrict__ members) {
+    dv_label_bucket(labels, N, counts, k, offs, members, blockIdx.x);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // the update step
@@ -311,8 +349,8 @@ struct KmControl {
     int rel_e[DV_MAX_K], rel_f[DV_MAX_K], rel_from[DV_MAX_K];
 };
 
-inline __global__ __launch_bounds__(256) void k_kmeans_relocate(const double *__restrict__ own_d2, int64_t N, const int32_t *__restrict__ labels,
-                                                                const int32_t *__restrict__ counts, int k, KmControl *__restrict__ ctl) {
+__device__ inline void dv_kmeans_relocate(const double *__restrict__ own_d2, int64_t N, const int32_t *__restrict__ labels,
+                                          const int32_t *__restrict__ counts, int k, KmControl *__restrict__ ctl) {
     __shared__ int s_empty[DV_MAX_K], s_chosen[DV_MAX_K], s_n;
     __shared__ double s_d[256];
     __shared__ int s_i[256];
@@ -359,14 +397,19 @@ inline __global__ __launch_bounds__(256) void k_kmeans_relocate(const double *__
         __syncthreads();
     }
 }
+inline __global__ __launch_bounds__(256) void k_kmeans_relocate(const double *__restrict__ own_d2, int64_t N, const int32_t *__restrict__ labels,
+                                                                const int32_t *__restrict__ counts, int k, KmControl *__restrict__ ctl) {
+    dv_kmeans_relocate(own_d2, N, labels, counts, k, ctl);
+}
 
 // grid (k, ceil(D / 64)); 256 threads = 64 columns x 4 member lanes.  C is updated in place; shift_part[c * slices + slice] = the
 // slice's share of |C_new[c] - C[c]|^2
-inline __global__ __launch_bounds__(256) void k_kmeans_update(const double *__restrict__ X, int D, const int32_t *__restrict__ members,
-                                                              const int32_t *__restrict__ offs, const int32_t *__restrict__ counts,
-                                                              const KmControl *__restrict__ ctl, double *__restrict__ C, double *__restrict__ shift_part) {
+// (workgroup (c, slice) of a grid (k, slices))
+__device__ inline void dv_kmeans_update(const double *__restrict__ X, int D, const int32_t *__restrict__ members, const int32_t *__restrict__ offs,
+                                        const int32_t *__restrict__ counts, const KmControl *__restrict__ ctl, double *__restrict__ C,
+                                        double *__restrict__ shift_part, int c, int slice, int slices) {
     __shared__ double s[4][64];
-    const int c = blockIdx.x, col = threadIdx.x & 63, g = threadIdx.x >> 6, d = blockIdx.y * 64 + col;
+    const int col = threadIdx.x & 63, g = threadIdx.x >> 6, d = slice * 64 + col;
     const int m0 = offs[c], cnt = counts[c];
     double acc = 0.0;
     if (d < D)
@@ -391,15 +434,23 @@ inline __global__ __launch_bounds__(256) void k_kmeans_update(const double *__re
         sh = (nw - old) * (nw - old);
     }
     sh = dv_wave_sum(sh);
-    if (col == 0) shift_part[size_t(c) * gridDim.y + blockIdx.y] = sh;
+    if (col == 0) shift_part[size_t(c) * slices + slice] = sh;
+}
+inline __global__ __launch_bounds__(256) void k_kmeans_update(const double *__restrict__ X, int D, const int32_t *__restrict__ members,
+                                                              const int32_t *__restrict__ offs, const int32_t *__restrict__ counts,
+                                                              const KmControl *__restrict__ ctl, double *__restrict__ C, double *__restrict__ shift_part) {
+    dv_kmeans_update(X, D, members, offs, counts, ctl, C, shift_part, blockIdx.x, blockIdx.y, gridDim.y);
 }
 // one wavefront: the iteration's shift, in a fixed order
-inline __global__ __launch_bounds__(64) void k_kmeans_control(const double *__restrict__ shift_part, int n_part, const int *__restrict__ changed,
-                                                              KmControl *__restrict__ ctl) {
+__device__ inline void dv_kmeans_control(const double *__restrict__ shift_part, int n_part, const int *__restrict__ changed, KmControl *__restrict__ ctl) {
     double acc = 0.0;
     for (int q = threadIdx.x; q < n_part; q += 64) acc += shift_part[q];
     acc = dv_wave_sum(acc);
     if (threadIdx.x == 0) ctl->shift = acc, ctl->changed = *changed;
+}
+inline __global__ __launch_bounds__(64) void k_kmeans_control(const double *__restrict__ shift_part, int n_part, const int *__restrict__ changed,
+                                                              KmControl *__restrict__ ctl) {
+    dv_kmeans_control(shift_part, n_part, changed, ctl);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -408,13 +459,12 @@ inline __global__ __launch_bounds__(64) void k_kmeans_control(const double *__re
 //  no energies: the member of largest cumdist, the first on a tie (:919-921), where for the member at POSITION p of its cluster's
 //  list  cumdist = sum over the centres c != p, over the atoms, of |centre_c[a] - member[a]|  -- the reference's `c` at :919 is the
 //  loop variable of enumerate(cluster), the member's position, not its cluster; with p >= k no centre is left out.
-inline __global__ __launch_bounds__(256) void k_diverse_pick(const double *__restrict__ X, int n, const int32_t *__restrict__ members,
-                                                             const int32_t *__restrict__ offs, const int32_t *__restrict__ counts,
-                                                             const double *__restrict__ C, int k, const double *__restrict__ energies,
-                                                             int32_t *__restrict__ picked) {
+__device__ inline void dv_diverse_pick(const double *__restrict__ X, int n, const int32_t *__restrict__ members, const int32_t *__restrict__ offs,
+                                       const int32_t *__restrict__ counts, const double *__restrict__ C, int k, const double *__restrict__ energies,
+                                       int32_t *__restrict__ picked, int c) {
     __shared__ double s_v[4];
     __shared__ int s_p[4];
-    const int c = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int m0 = offs[c], cnt = counts[c], D = 3 * n;
     if (cnt == 0) {
         if (threadIdx.x == 0) picked[c] = -1;
@@ -456,13 +506,19 @@ inline __global__ __launch_bounds__(256) void k_diverse_pick(const double *__res
         picked[c] = members[m0 + bp];
     }
 }
+inline __global__ __launch_bounds__(256) void k_diverse_pick(const double *__restrict__ X, int n, const int32_t *__restrict__ members,
+                                                             const int32_t *__restrict__ offs, const int32_t *__restrict__ counts,
+                                                             const double *__restrict__ C, int k, const double *__restrict__ energies,
+                                                             int32_t *__restrict__ picked) {
+    dv_diverse_pick(X, n, members, offs, counts, C, k, energies, picked, blockIdx.x);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // k-means++ seeding without local trials.  rows[j] is the seed chosen last; min_d2[i] = min(min_d2[i], |x_i - x_rows[j]|^2)
-inline __global__ __launch_bounds__(256) void k_kmeans_seed_update(const double *__restrict__ X, int64_t N, int D, const int32_t *__restrict__ rows, int j,
-                                                                   double *__restrict__ min_d2) {
+__device__ inline void dv_kmeans_seed_update(const double *__restrict__ X, int64_t N, int D, const int32_t *__restrict__ rows, int j,
+                                             double *__restrict__ min_d2, int64_t block) {
     const int lane = threadIdx.x & 63;
-    const int64_t i = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    const int64_t i = block * 4 + (threadIdx.x >> 6);
     if (i >= N) return;
     const double *y = X + int64_t(rows[j]) * D;
     double acc = 0.0;
@@ -473,10 +529,13 @@ inline __global__ __launch_bounds__(256) void k_kmeans_seed_update(const double 
     acc = dv_wave_sum(acc);
     if (lane == 0) min_d2[i] = (j == 0 || acc < min_d2[i]) ? acc : min_d2[i];
 }
+inline __global__ __launch_bounds__(256) void k_kmeans_seed_update(const double *__restrict__ X, int64_t N, int D, const int32_t *__restrict__ rows, int j,
+                                                                   double *__restrict__ min_d2) {
+    dv_kmeans_seed_update(X, N, D, rows, j, min_d2, blockIdx.x);
+}
 // rows[j] = the first row whose running sum of min_d2 (row order) exceeds u[j] * total.  One workgroup of 1024: a contiguous piece
 // per thread, a scan of the pieces' sums, then the piece that crosses the target is walked again.
-inline __global__ __launch_bounds__(1024) void k_kmeans_seed_pick(const double *__restrict__ min_d2, int64_t N, const double *__restrict__ u, int j,
-                                                                  int32_t *__restrict__ rows) {
+__device__ inline void dv_kmeans_seed_pick(const double *__restrict__ min_d2, int64_t N, const double *__restrict__ u, int j, int32_t *__restrict__ rows) {
     __shared__ double s[1024];
     __shared__ int s_first;
     const int t = threadIdx.x;
@@ -512,6 +571,37 @@ inline __global__ __launch_bounds__(1024) void k_kmeans_seed_pick(const double *
         }
         rows[j] = int32_t(pick);
     }
+}
+inline __global__ __launch_bounds__(1024) void k_kmeans_seed_pick(const double *__restrict__ min_d2, int64_t N, const double *__restrict__ u, int j,
+                                                                  int32_t *__restrict__ rows) {
+    dv_kmeans_seed_pick(min_d2, N, u, j, rows);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the limits of the entry points (diverse.hip, select_batch.hip), checked on the host arrays
+
+// scikit-learn refuses NaN / infinity with a ValueError; here they would turn every distance into NaN (no row ever nearer to any
+// centre) -- refused on the host arrays before anything touches the device
+inline int check_finite(const char *who, const char *what, const double *v, size_t count) {
+    for (size_t q = 0; q < count; ++q) TSC_REQUIRE(std::isfinite(v[q]), "%s: %s[%zu] is not finite", who, what, q);
+    return 0;
+}
+inline int check_uniforms(const char *who, const double *u, int k) {
+    for (int j = 0; j < k; ++j) TSC_REQUIRE(u[j] >= 0.0 && u[j] < 1.0, "%s: u[%d] not in [0, 1)", who, j);
+    return 0;
+}
+
+inline int check_shape(const char *who, int64_t N, int n_atoms) {
+    TSC_REQUIRE(N >= 1 && N < INT32_MAX, "%s: %lld structures (1 .. %d)", who, (long long)N, INT32_MAX - 1);
+    TSC_REQUIRE(n_atoms >= 1 && n_atoms <= DV_MAX_ATOMS, "%s: %d atoms per structure (1 .. %d)", who, n_atoms, DV_MAX_ATOMS);
+    return 0;
+}
+inline int check_k(const char *who, int64_t N, int64_t D, int k) {
+    TSC_REQUIRE(N >= 1 && N < INT32_MAX, "%s: %lld rows (1 .. %d)", who, (long long)N, INT32_MAX - 1);
+    TSC_REQUIRE(D >= 1 && D <= 3 * DV_MAX_ATOMS, "%s: %lld columns (1 .. %d)", who, (long long)D, 3 * DV_MAX_ATOMS);
+    TSC_REQUIRE(k >= 1 && k <= DV_MAX_K, "%s: %d clusters (1 .. %d)", who, k, DV_MAX_K);
+    TSC_REQUIRE(k <= N, "%s: %d clusters for %lld rows", who, k, (long long)N);
+    return 0;
 }
 
 }  // namespace tsc

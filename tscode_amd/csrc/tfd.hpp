@@ -33,53 +33,113 @@ __device__ inline double dihedral_deg_dev(const double *__restrict__ p0, const d
     return atan2(y, x) * (180.0 / 3.14159265358979323846);
 }
 
+// One element of _get_tf_mat (:233-240): torsion t of the structure c[n][3].  The plain and the segmented kernel both call this, so a
+// fingerprint cannot differ between the two routes.
+__device__ inline float tfd_fingerprint_element(const double *__restrict__ c, const int32_t *__restrict__ quads, int t) {
+    const int32_t *q = quads + 4 * t;
+    return float(dihedral_deg_dev(c + 3 * q[0], c + 3 * q[1], c + 3 * q[2], c + 3 * q[3]));
+}
+
 // _get_tf_mat (:233-240): out f32[N][T]
 inline __global__ __launch_bounds__(256) void k_torsion_fingerprints(const double *__restrict__ coords, int64_t N, int n, const int32_t *__restrict__ quads,
                                                                int T, float *__restrict__ out) {
     const int64_t total = N * T;
     for (int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; e < total; e += int64_t(gridDim.x) * blockDim.x) {
         const int64_t s = e / T;
-        const int t = int(e - s * T);
-        const double *c = coords + s * n * 3;
-        const int32_t *q = quads + 4 * t;
-        out[e] = float(dihedral_deg_dev(c + 3 * q[0], c + 3 * q[1], c + 3 * q[2], c + 3 * q[3]));
+        out[e] = tfd_fingerprint_element(coords + s * n * 3, quads, int(e - s * T));
     }
 }
 
-// One pass of the pair search (:171-199).  first[i] = absolute index of the first similar j > i inside i's chunk, -1 if
-// none or if i lies in no chunk (the last chunk ends at num_active, :175-178).
+// Row i of one pass of the pair search (:171-199), by one wavefront: the absolute index of the first similar j > i inside i's chunk,
+// -1 if none or if i lies in no chunk (the last chunk ends at num_active, :175-178).  The same value in every lane.  The plain and
+// the segmented kernel both call this, so a verdict cannot differ between the two routes.
+__device__ inline int32_t tfd_first_similar_row(const float *__restrict__ tf, int T, int64_t i, int64_t d, int64_t k, int64_t num_active, double thresh,
+                                                int lane) {
+    int64_t step = i / d;
+    if (step > k - 1) step = k - 1;
+    const int64_t start = d * step;
+    int64_t len = (step == k - 1) ? num_active - start : d;
+    if (len < 0) len = 0;
+    const int64_t i_rel = i - start;
+    int32_t found = -1;
+    if (i_rel < len) {
+        const float *a = tf + i * T;
+        for (int64_t j0 = i_rel + 1; j0 < len && found < 0; j0 += 64) {
+            const int64_t j = j0 + lane;
+            bool sim = false;
+            if (j < len) {
+                const float *b = tf + (start + j) * T;
+                double sum = 0.0;
+                for (int t = 0; t < T; ++t) {
+                    const float d32 = fabsf(a[t] - b[t]);          // float32, like the reference's arrays
+                    double dd = double(d32);
+                    if (d32 > 180.0f) dd -= 360.0;                  // the integer term makes the rest float64
+                    sum += fabs(dd);
+                }
+                sim = sum < thresh;
+            }
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(sim);
+            if (m) found = int32_t(start + j0 + (__ffsll((long long)m) - 1));
+        }
+    }
+    return found;
+}
+
+// One pass of the pair search (:171-199): first[i] = tfd_first_similar_row of row i
 inline __global__ __launch_bounds__(256) void k_tfd_first_similar(const float *__restrict__ tf, int64_t N, int T, int64_t d, int64_t k, int64_t num_active,
                                                             double thresh, int32_t *__restrict__ first) {
     const int lane = threadIdx.x & 63;
     for (int64_t i = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); i < N; i += int64_t(gridDim.x) * 4) {
-        int64_t step = i / d;
-        if (step > k - 1) step = k - 1;
-        const int64_t start = d * step;
-        int64_t len = (step == k - 1) ? num_active - start : d;
-        if (len < 0) len = 0;
-        const int64_t i_rel = i - start;
-        int32_t found = -1;
-        if (i_rel < len) {
-            const float *a = tf + i * T;
-            for (int64_t j0 = i_rel + 1; j0 < len && found < 0; j0 += 64) {
-                const int64_t j = j0 + lane;
-                bool sim = false;
-                if (j < len) {
-                    const float *b = tf + (start + j) * T;
-                    double sum = 0.0;
-                    for (int t = 0; t < T; ++t) {
-                        const float d32 = fabsf(a[t] - b[t]);          // float32, like the reference's arrays
-                        double dd = double(d32);
-                        if (d32 > 180.0f) dd -= 360.0;                  // the integer term makes the rest float64
-                        sum += fabs(dd);
-                    }
-                    sim = sum < thresh;
-                }
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(sim);
-                if (m) found = int32_t(start + j0 + (__ffsll((long long)m) - 1));
-            }
-        }
+        const int32_t found = tfd_first_similar_row(tf, T, i, d, k, num_active, thresh, lane);
         if (lane == 0) first[i] = found;
+    }
+}
+
+// ---- many ensembles per launch (tfd_batch.hip) ---------------------------------------------------------------------------------
+// Segment s of a batch is an ensemble of its own: N structures of n atoms at coords + coord0, T quadruplets at quads + 4 * quad0.  Its
+// fingerprints are f32[N][T] at tf + elem0: elem0 is the running sum of N * T, and an element finds its segment by that table.
+struct TfdSegment {
+    int64_t coord0, quad0, elem0;
+    int32_t N, n, T, pad;
+};
+// the last entry q of table[0 .. count) with key(q) <= v; table[0]'s key is <= v.  Entries of equal key: the last one, which is the
+// one that is not empty.
+template <typename Entry, typename Key>
+__device__ inline int tfd_last_not_above(const Entry *__restrict__ table, int count, int64_t v, Key key) {
+    int lo = 0, hi = count - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (key(table[mid]) <= v) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// _get_tf_mat of every segment: out f32[total], total = the sum of N * T
+inline __global__ __launch_bounds__(256) void k_torsion_fingerprints_seg(const double *__restrict__ coords, const int32_t *__restrict__ quads,
+                                                                   const TfdSegment *__restrict__ segs, int n_segs, int64_t total,
+                                                                   float *__restrict__ out) {
+    for (int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; e < total; e += int64_t(gridDim.x) * blockDim.x) {
+        const TfdSegment g = segs[tfd_last_not_above(segs, n_segs, e, [](const TfdSegment &q) { return q.elem0; })];
+        const int64_t el = e - g.elem0, s = el / g.T;   // (a segment that holds an element has T >= 1)
+        out[e] = tfd_fingerprint_element(coords + g.coord0 + s * g.n * 3, quads + 4 * g.quad0, int(el - s * g.T));
+    }
+}
+
+// One schedule slot for the segments whose gate is open in it (:166), each with its own pass geometry.  The rows of these segments are
+// numbered through: wave0 is a segment's first number, and a wavefront finds its row's segment by that table.  first[row0 + i] = what
+// k_tfd_first_similar gives row i of the segment alone, an index INSIDE the segment; rows of other segments are neither read nor written.
+struct TfdPassSegment {
+    int64_t wave0, row0, elem0, d, k, num_active;
+    double thresh;
+    int32_t N, T;
+};
+inline __global__ __launch_bounds__(256) void k_tfd_first_similar_seg(const float *__restrict__ tf, const TfdPassSegment *__restrict__ segs, int n_segs,
+                                                                int64_t total_rows, int32_t *__restrict__ first) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t r = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); r < total_rows; r += int64_t(gridDim.x) * 4) {
+        const TfdPassSegment g = segs[tfd_last_not_above(segs, n_segs, r, [](const TfdPassSegment &q) { return q.wave0; })];
+        const int64_t i = r - g.wave0;
+        const int32_t found = tfd_first_similar_row(tf + g.elem0, g.T, i, g.d, g.k, g.num_active, g.thresh, lane);
+        if (lane == 0) first[g.row0 + i] = found;
     }
 }
 

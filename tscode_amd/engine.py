@@ -308,6 +308,32 @@ class Engine:
                                              C.c_int64(int(num_active)), C.c_double(float(thresh)), ptr(first)))
         return first
 
+    def tfd_batch_fingerprints_dev(self, coords, offsets, n_structs, n_atoms, quads, n_quads):
+        """tsc_tfd_batch_fingerprints_dev (include/tscode_hip.h): the fingerprints of every segment, computed once and left on the
+        device.  coords f64[sum N n 3] with offsets i64[S + 1], quads i32[sum T, 4]; n_structs, n_atoms, n_quads i32[S].  Returns
+        (address, element count); the caller hands the address back with dev_free."""
+        count = int(np.dot(n_structs.astype(np.int64), n_quads.astype(np.int64)))
+        tf = self.dev_alloc(4 * count)
+        try:
+            check(self.lib.tsc_tfd_batch_fingerprints_dev(self._h, ptr(coords), ptr(offsets), ptr(n_structs), ptr(n_atoms), ptr(quads), ptr(n_quads),
+                                                          C.c_int64(len(n_structs)), C.c_void_p(tf), C.c_int64(count)))
+        except BaseException:
+            self.dev_free(tf)
+            raise
+        return tf, count
+
+    def tfd_batch_pass_dev(self, tf, tf_count, elem0, row0, n_structs, n_quads, d, k, num_active, thresh, total_rows):
+        """tsc_tfd_batch_pass_dev: one schedule slot of prune_conformers_tfd for every open segment in one launch: i32[total_rows],
+        indices inside each segment, -1 = none or a row of no open segment."""
+        first = np.full(int(total_rows), -1, dtype=np.int32)
+        elem0, row0, d, k, num_active = (np.ascontiguousarray(a, dtype=np.int64) for a in (elem0, row0, d, k, num_active))
+        n_structs, n_quads = (np.ascontiguousarray(a, dtype=np.int32) for a in (n_structs, n_quads))
+        thresh = np.ascontiguousarray(thresh, dtype=np.float64)
+        check(self.lib.tsc_tfd_batch_pass_dev(self._h, C.c_void_p(tf), C.c_int64(int(tf_count)), ptr(elem0), ptr(row0), ptr(n_structs), ptr(n_quads),
+                                              ptr(d), ptr(k), ptr(num_active), ptr(thresh), C.c_int64(len(elem0)), C.c_int64(int(total_rows)),
+                                              ptr(first)))
+        return first
+
     # ---- N4: moments of inertia, embed scores -------------------------------------------------------
     def inertia_moments(self, structures, masses):
         structures = np.ascontiguousarray(structures, dtype=np.float64)

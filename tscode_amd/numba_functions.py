@@ -6,8 +6,8 @@ import numpy as np
 
 from .engine import get_engine
 
-__all__ = ["compenetration_check", "count_clashes", "compenetration_mask", "prune_conformers_tfd", "_get_tf_mat",
-           "get_torsion_fingerprint", "tfd_similarity"]
+__all__ = ["compenetration_check", "count_clashes", "compenetration_mask", "prune_conformers_tfd", "prune_conformers_tfd_batch",
+           "_get_tf_mat", "get_torsion_fingerprint", "tfd_similarity"]
 
 TFD_KS = (5e5, 2e5, 1e5, 5e4, 2e4, 1e4, 5000, 2000, 1000, 500, 200, 100, 50, 20, 10, 5, 2, 1)      # numba_functions.py:160-162
 
@@ -255,3 +255,147 @@ def prune_conformers_tfd(structures, quadruplets, thresh=10, verbose=False):
     eng = get_engine()
     tf_mat = eng.torsion_fingerprints(structures, quadruplets)
     return _tfd_schedule(structures, tf_mat, thresh, verbose, eng.tfd_first_similar)
+
+
+# ---- the same for many small ensembles per call -------------------------------------------------------------------------------
+TFD_BATCH_BYTES = 1 << 30               # coordinates one prune_conformers_tfd_batch upload may hold; a longer list goes in slices
+
+
+def _tfd_reject_matches_batch(first, off, sizes, d, k, keep):
+    """_tfd_reject_matches for every segment of one schedule slot at once.  ``first`` i32[sum sizes]: per row the index INSIDE its
+    segment of its first similar j, -1 for none and for every row of a segment whose gate is closed; ``off`` i64[S + 1] the segments'
+    first rows, ``d`` i64[S] their chunk lengths (read only where a segment has matches), ``keep`` bool[sum sizes] the concatenated
+    masks, cleared in place.  The single-match shortcut runs over the concatenated rows, the graph step of all other chunks of all
+    segments is ONE tsc_host_graph_step call (its chunk_off indexes the concatenated mask)."""
+    rows = np.flatnonzero(first >= 0)
+    if len(rows) == 0:
+        return
+    seg = np.searchsorted(off, rows, side="right") - 1
+    base = off[seg]
+    steps = np.minimum((rows - base) // d[seg], int(k) - 1)
+    bounds = np.flatnonzero((np.diff(seg) != 0) | (np.diff(steps) != 0)) + 1
+    starts = np.concatenate(([0], bounds))
+    n_match = np.diff(np.concatenate((starts, [len(rows)])))
+    single = starts[n_match == 1]
+    keep[base[single] + first[rows[single]]] = False
+    if len(single) == len(starts):
+        return
+    multi = n_match > 1
+    at, count = starts[multi], n_match[multi]
+    if _host_graph_step_ok(big=int(count.max()) > 40000):
+        sel = np.concatenate([np.arange(a, a + c) for a, c in zip(at.tolist(), count.tolist())])
+        chunk_seg, chunk_step = seg[at], steps[at].astype(np.int64)
+        local_off = chunk_step * d[chunk_seg]
+        chunk_len = np.where(chunk_step == int(k) - 1, sizes[chunk_seg] - local_off, d[chunk_seg]).astype(np.int64)
+        local_per_match = np.repeat(local_off, count)
+        _host_graph_step(rows[sel] - base[sel] - local_per_match, first[rows[sel]].astype(np.int64) - local_per_match,
+                         np.concatenate(([0], np.cumsum(count))), off[chunk_seg] + local_off, chunk_len, keep)
+        return
+    for a, c in zip(at.tolist(), count.tolist()):                       # the Python path, chunk by chunk on the segment's own rows
+        s = int(seg[a])
+        lo, hi = int(off[s]), int(off[s + 1])
+        _tfd_reject_graph(first[lo:hi], int(d[s]), int(k), keep[lo:hi], [rows[a:a + c] - lo])
+
+
+def _tfd_schedule_batch(sizes, pair_search, verbose=False):
+    """_pass_schedule for S segments of ``sizes`` structures in lockstep over TFD_KS: each segment keeps its own gate
+    ``k == 1 or 5 k < active_s`` (:166), its own ``d_s = N_s // k`` (:173) and the skip at ``d_s == 0``; a slot in which no
+    segment's gate is open costs nothing.  ``pair_search(open, d, k, num_active) -> i32[sum sizes]`` is the pair search of one slot
+    for the segments ``open`` (ascending) with their ``d`` and ``num_active``: per row the index inside its own segment of the
+    first similar j, -1 for none and for the rows of every other segment (the engine's launch in the product; the tests also
+    drive it with the CPU oracle).  Returns (keep bool[sum sizes], off i64[S + 1])."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    S = len(sizes)
+    off = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    keep = np.ones(int(off[-1]), dtype=bool)
+    seg_of_row = np.repeat(np.arange(S), sizes)
+    d = np.zeros(S, dtype=np.int64)
+    for k in TFD_KS:
+        active = np.bincount(seg_of_row[keep], minlength=S).astype(np.int64)
+        d[:] = sizes // int(k)                                                                # :173
+        is_open = ((k == 1) | (5 * int(k) < active)) & (d > 0)                                # :166
+        open_segs = np.flatnonzero(is_open)
+        if len(open_segs) == 0:
+            continue
+        if verbose:
+            print(f"Working on subgroups with k={k} ({len(open_segs)} ensembles, {int(active[open_segs].sum())} candidates left) {' ' * 10}", end="\r")
+        first = pair_search(open_segs, d[open_segs], int(k), active[open_segs])
+        _tfd_reject_matches_batch(first, off, sizes, d, int(k), keep)
+    return keep, off
+
+
+def _tfd_batch_args(ensembles, quadruplets, thresh):
+    """The checked arguments of prune_conformers_tfd_batch: ([f64[N_s, n_s, 3]], [i32[T_s, 4]], f64[S])."""
+    if isinstance(ensembles, np.ndarray) and ensembles.ndim != 4:
+        raise ValueError("ensembles must be a list of (N, n_atoms, 3) arrays")
+    ens = [np.ascontiguousarray(e, dtype=np.float64) for e in ensembles]
+    S = len(ens)
+    for s, e in enumerate(ens):
+        if e.ndim != 3 or e.shape[2] != 3 or e.shape[1] < 1:
+            raise ValueError(f"ensemble {s}: structures must be (N, n_atoms, 3)")
+    # one array of quadruplets for all (an array, or a list of 4-tuples), or one per ensemble (a list, or a stacked array)
+    one_for_all = np.ndim(quadruplets) <= 2 if isinstance(quadruplets, np.ndarray) else (len(quadruplets) == 0 or np.ndim(quadruplets[0]) <= 1)
+    if one_for_all:
+        quadruplets = [quadruplets] * S
+    if len(quadruplets) != S:
+        raise ValueError(f"{len(quadruplets)} quadruplet arrays for {S} ensembles")
+    quads = [np.ascontiguousarray(q, dtype=np.int32).reshape(-1, 4) for q in quadruplets]
+    for s, (e, q) in enumerate(zip(ens, quads)):
+        if len(q) and (q.min() < 0 or q.max() >= e.shape[1]):
+            raise ValueError(f"ensemble {s}: quadruplet atom index out of range")
+    th = np.asarray(thresh, dtype=np.float64)
+    if th.ndim == 0:
+        th = np.full(S, float(th))
+    if th.shape != (S,):
+        raise ValueError(f"{th.size} thresholds for {S} ensembles")
+    return ens, quads, np.ascontiguousarray(th)
+
+
+def _tfd_batch_masks(ens, quads, th, verbose=False):
+    """The masks of one upload: fingerprints of all segments in one launch, left on the device for every schedule slot."""
+    eng = get_engine()
+    S = len(ens)
+    n_structs = np.array([len(e) for e in ens], dtype=np.int32)
+    n_atoms = np.array([e.shape[1] for e in ens], dtype=np.int32)
+    n_quads = np.array([len(q) for q in quads], dtype=np.int32)
+    sizes = n_structs.astype(np.int64)
+    offsets = np.concatenate(([0], np.cumsum(sizes * n_atoms * 3))).astype(np.int64)
+    coords = np.concatenate([e.ravel() for e in ens]) if S else np.zeros(0)
+    quads_all = np.ascontiguousarray(np.concatenate(quads)) if S else np.zeros((0, 4), dtype=np.int32)
+    elem0 = np.concatenate(([0], np.cumsum(sizes * n_quads)))[:-1].astype(np.int64)
+    row0 = np.concatenate(([0], np.cumsum(sizes)))[:-1].astype(np.int64)
+    tf, tf_count = eng.tfd_batch_fingerprints_dev(coords, offsets, n_structs, n_atoms, quads_all, n_quads)
+    try:
+        def pair_search(open_segs, d, k, num_active):
+            return eng.tfd_batch_pass_dev(tf, tf_count, elem0[open_segs], row0[open_segs], n_structs[open_segs], n_quads[open_segs], d,
+                                          np.full(len(open_segs), k, dtype=np.int64), num_active, th[open_segs], int(sizes.sum()))
+        keep, off = _tfd_schedule_batch(sizes, pair_search, verbose)
+    finally:
+        eng.dev_free(tf)
+    return [keep[off[s]:off[s + 1]] for s in range(S)]
+
+
+def prune_conformers_tfd_batch(ensembles, quadruplets, thresh=10, verbose=False):
+    """prune_conformers_tfd (tscode/numba_functions.py:142-231) for many ensembles per call: ``[(structures_s[mask_s], mask_s)]``,
+    each entry exactly what ``prune_conformers_tfd(ensembles[s], quadruplets_s, thresh_s)`` returns.
+
+    ``ensembles`` is a list of f64[N_s, n_s, 3]; ``quadruplets`` one i32[T, 4] for all or a list with one per ensemble (``T_s = 0``
+    allowed); ``thresh`` a scalar or one value per ensemble.  The fingerprints of all ensembles are computed in one launch and stay
+    on the device; the schedule's slots are walked in lockstep (_tfd_schedule_batch), one launch per slot for every ensemble whose
+    gate is open in it -- the same per-row device code as the single call's kernel (csrc/tfd.hpp) -- and one graph step per slot.
+    A list whose coordinates exceed ``TFD_BATCH_BYTES`` goes in slices; a list of one goes to prune_conformers_tfd."""
+    ens, quads, th = _tfd_batch_args(ensembles, quadruplets, thresh)
+    S = len(ens)
+    if S == 0:
+        return []
+    if S == 1:
+        return [prune_conformers_tfd(ens[0], quads[0], float(th[0]), verbose)]
+    masks, at = [], 0
+    while at < S:
+        end, nbytes = at, 0
+        while end < S and (end == at or nbytes + ens[end].nbytes <= TFD_BATCH_BYTES):
+            nbytes += ens[end].nbytes
+            end += 1
+        masks += _tfd_batch_masks(ens[at:end], quads[at:end], th[at:end], verbose)
+        at = end
+    return [(e[m], m) for e, m in zip(ens, masks)]

@@ -378,6 +378,159 @@ def most_diverse_conformers(n, structures, torsion_array, energies=None, interac
     return aligned[picked[picked >= 0]]
 
 
+# ---- the same for many small ensembles per call ------------------------------------------------------------------------------------------
+DIVERSE_BATCH_BYTES = 1 << 30           # device bytes one tsc_diverse_select_batch call may fill with structures (input, aligned, centred)
+
+
+def _per_segment(value, S, what):
+    """``value`` for every segment: a list of S entries as it is, None as S times None."""
+    if value is None:
+        return [None] * S
+    if len(value) != S:
+        raise ValueError(f"{len(value)} {what} for {S} ensembles")
+    return list(value)
+
+
+def _diverse_batch_args(ensembles, k, init_rows, seeds, energies):
+    """The checked arguments of diverse_select_batch, per segment: (structures, k, rows or None, uniforms or None, energies or None)."""
+    from .hypermolecule_class import _check_structures
+    from .kmeans import _check_k, seed_uniforms
+
+    ens = [np.ascontiguousarray(e, dtype=np.float64) for e in ensembles]
+    S = len(ens)
+    ks = [int(k)] * S if np.ndim(k) == 0 else [int(v) for v in _per_segment(k, S, "cluster counts")]
+    init_rows, seeds, energies = (_per_segment(v, S, w) for v, w in ((init_rows, "init_rows entries"), (seeds, "seeds"), (energies, "energies arrays")))
+    segs = []
+    for s in range(S):
+        _check_structures(ens[s])
+        N, n = ens[s].shape[:2]
+        _check_k(N, 3 * n, ks[s])
+        rows = u = e = None
+        if init_rows[s] is None:
+            u = seed_uniforms(ks[s], seeds[s])
+        else:
+            rows = np.ascontiguousarray(np.asarray(init_rows[s]).ravel(), dtype=np.int32)
+            if len(rows) != ks[s] or rows.min() < 0 or rows.max() >= N:
+                raise ValueError(f"ensemble {s}: init_rows: expected {ks[s]} row indices in [0, {N})")
+        if energies[s] is not None:
+            e = np.ascontiguousarray(energies[s], dtype=np.float64).ravel()
+            if len(e) != N:
+                raise ValueError(f"ensemble {s}: {len(e)} energies for {N} structures")
+            if np.isnan(e).any():
+                raise ValueError(f"ensemble {s}: energies contain NaN")
+        segs.append((ens[s], ks[s], rows, u, e))
+    return segs
+
+
+def _diverse_select_slice(segs, max_iter, tol):
+    """One tsc_diverse_select_batch call."""
+    import ctypes as C
+
+    from ._lib import check, ptr
+    S = len(segs)
+    n_structs = np.array([len(x) for x, *_ in segs], dtype=np.int32)
+    n_atoms = np.array([x.shape[1] for x, *_ in segs], dtype=np.int32)
+    ks = np.array([k for _, k, *_ in segs], dtype=np.int32)
+    offsets = np.concatenate(([0], np.cumsum(n_structs.astype(np.int64) * n_atoms * 3))).astype(np.int64)
+    row_off = np.concatenate(([0], np.cumsum(n_structs.astype(np.int64))))
+    k_off = np.concatenate(([0], np.cumsum(ks.astype(np.int64))))
+    structures = np.concatenate([x.ravel() for x, *_ in segs])
+    rows = np.zeros(int(k_off[-1]), dtype=np.int32)
+    u = np.zeros(int(k_off[-1]), dtype=np.float64)
+    energies = np.zeros(int(row_off[-1]), dtype=np.float64)
+    flags = np.zeros(S, dtype=np.uint8)
+    for s, (_, _, r, us, e) in enumerate(segs):
+        if r is None:
+            u[k_off[s]:k_off[s + 1]] = us
+            flags[s] |= 2
+        else:
+            rows[k_off[s]:k_off[s + 1]] = r
+        if e is not None:
+            energies[row_off[s]:row_off[s + 1]] = e
+            flags[s] |= 1
+    aligned = np.empty_like(structures)
+    labels = np.empty(int(row_off[-1]), dtype=np.int32)
+    picked = np.empty(int(k_off[-1]), dtype=np.int32)
+    n_iter = np.zeros(S, dtype=np.int32)
+    eng = get_engine()
+    check(eng.lib.tsc_diverse_select_batch(eng._h, ptr(structures), ptr(offsets), ptr(n_structs), ptr(n_atoms), ptr(ks), C.c_int64(S), ptr(rows),
+                                           ptr(u) if (flags & 2).any() else None, ptr(energies) if (flags & 1).any() else None, ptr(flags),
+                                           C.c_int(int(max_iter)), C.c_double(float(tol)), ptr(aligned), ptr(labels), ptr(picked), ptr(n_iter)))
+    return [(aligned[offsets[s]:offsets[s + 1]].reshape(segs[s][0].shape), labels[row_off[s]:row_off[s + 1]], picked[k_off[s]:k_off[s + 1]],
+             rows[k_off[s]:k_off[s + 1]], int(n_iter[s])) for s in range(S)]
+
+
+def diverse_select_batch(ensembles, k, init_rows=None, seeds=None, energies=None, max_iter=300, tol=1e-4):
+    """diverse_select for many ensembles per call (tsc_diverse_select_batch): ``[(aligned, labels, picked, init_rows, n_iter)]``, each
+    entry what ``diverse_select(ensembles[s], k_s, init_rows[s], seeds[s], energies[s], max_iter, tol)`` returns, bit for bit.
+
+    ``ensembles`` is a list of f64[N_s, n_s, 3]; ``k`` an int or one per ensemble; ``init_rows``, ``seeds`` and ``energies`` are
+    lists with None entries allowed (or None for all).  A list whose structures would fill more than ``DIVERSE_BATCH_BYTES`` on the
+    device goes in slices of ensembles; a list of one goes to diverse_select."""
+    segs = _diverse_batch_args(ensembles, k, init_rows, seeds, energies)
+    if len(segs) == 1:
+        x, ks, rows, _, e = segs[0]
+        sd = None if seeds is None else seeds[0]
+        return [diverse_select(x, ks, init_rows=rows, seed=sd, energies=e, max_iter=max_iter, tol=tol)]
+    out, at = [], 0
+    while at < len(segs):
+        end, nbytes = at, 0
+        while end < len(segs) and (end == at or nbytes + 3 * segs[end][0].nbytes <= DIVERSE_BATCH_BYTES):
+            nbytes += 3 * segs[end][0].nbytes
+            end += 1
+        out += _diverse_select_slice(segs[at:end], max_iter, tol) if end - at > 1 else \
+            [diverse_select(segs[at][0], segs[at][1], init_rows=segs[at][2], seed=None if seeds is None else seeds[at], energies=segs[at][4],
+                            max_iter=max_iter, tol=tol)]
+        at = end
+    return out
+
+
+def most_diverse_conformers_batch(n, ensembles, torsion_arrays, energies=None, *, seeds=None, init_rows=None):
+    """most_diverse_conformers for many ensembles per call: ``[array]``, each entry what
+    ``most_diverse_conformers(n_s, ensembles[s], torsion_array_s, energies[s], seed=seeds[s], init_rows=init_rows[s])`` returns.
+
+    ``n`` is an int or one per ensemble; ``torsion_arrays`` one i32[T, 4] for all or a list with one per ensemble; ``energies``,
+    ``seeds`` and ``init_rows`` are lists with None entries allowed.  Every rule of most_diverse_conformers holds per segment: the
+    early returns at ``len <= n`` before and after the TFD prune, ``n > 300`` with that very ``np.random.choice`` call, the
+    energies zip quirk, and a seed drawn from ``np.random`` when neither seed nor rows are given.  The ``np.random`` draws are made
+    in segment order, so a caller who seeds ``np.random`` gets what the loop over most_diverse_conformers gives.  The TFD prune in
+    front is ONE prune_conformers_tfd_batch call over the segments that reach it, the clustering ONE diverse_select_batch call."""
+    from . import numba_functions
+
+    S = len(ensembles)
+    ns = [int(n)] * S if np.ndim(n) == 0 else [int(v) for v in _per_segment(n, S, "n entries")]
+    energies, seeds, init_rows = (_per_segment(v, S, w) for v, w in ((energies, "energies arrays"), (seeds, "seeds"), (init_rows, "init_rows entries")))
+    one_for_all = np.ndim(torsion_arrays) <= 2 if isinstance(torsion_arrays, np.ndarray) else (len(torsion_arrays) == 0 or np.ndim(torsion_arrays[0]) <= 1)
+    torsion_arrays = [torsion_arrays] * S if one_for_all else _per_segment(torsion_arrays, S, "torsion arrays")
+    out = [None] * S
+    to_prune = [s for s in range(S) if len(ensembles[s]) > ns[s] and ns[s] <= 300]               # :859, :863
+    pruned = dict(zip(to_prune, (p for p, _ in numba_functions.prune_conformers_tfd_batch([ensembles[s] for s in to_prune],
+                                                                                          [torsion_arrays[s] for s in to_prune]))))   # :872
+    cluster = []
+    for s in range(S):                                                                           # (the draws, in segment order)
+        structures = ensembles[s]
+        if len(structures) <= ns[s]:                                                             # :859
+            out[s] = structures
+        elif ns[s] > 300:                                                                        # :863-865
+            out[s] = structures[np.sort(np.random.choice(len(structures), size=ns[s]))]
+        elif len(pruned[s]) <= ns[s]:                                                            # :875
+            out[s] = pruned[s]
+        else:
+            if init_rows[s] is None and seeds[s] is None:
+                seeds[s] = int(np.random.randint(0, 2**31 - 1))
+            if energies[s] is not None:
+                energies[s] = np.asarray(energies[s], dtype=np.float64).ravel()[:len(pruned[s])]   # :896 (zip stops at the shorter)
+                if len(energies[s]) < len(pruned[s]):
+                    raise ValueError(f"ensemble {s}: {len(energies[s])} energies for {len(pruned[s])} structures")
+            cluster.append(s)
+    if cluster:
+        res = diverse_select_batch([pruned[s] for s in cluster], [ns[s] for s in cluster], init_rows=[init_rows[s] for s in cluster],
+                                   seeds=[seeds[s] for s in cluster], energies=[energies[s] for s in cluster])
+        for s, (aligned, _, picked, _, _) in zip(cluster, res):
+            out[s] = aligned[picked[picked >= 0]]
+    return out
+
+
 # ---- from coordinates to torsion sets (tscode/torsion_module.py:559-615, per TS candidate there; per ensemble here) -------------------
 MAX_CONSTRAINT_PAIRS = 64               # TOR_MAX_EXTRA (csrc/torsions.hpp)
 HB_MODE_ALL, HB_MODE_LINK = 0, 1        # keep_hb=True / keep_hb=False (include/tscode_hip.h, tsc_hbonds)
@@ -897,6 +1050,12 @@ def group_torsions_batch(structures, torsion_sets, set_of_structure=None, max_si
     return groups, eps_index, over != 0
 
 
+# Structures in a slice of a round from which its trims and finals go through the batched calls (close_slice).  Measured (MEASURED.md
+# section 20): with one structure the batched calls hand over to the single ones and cost 3 % on top (7.40 against 7.21 ms); from two
+# structures on the batch route is ahead by more than the spread of the runs (14.4 against 17.0 ms at 2, 39.7 against 96.3 at 16).
+CLUSTERED_BATCH_MIN_POSES = 2
+
+
 def _trim_seed(seed, coords, call):
     """The k-means seed of most_diverse_conformers call ``call`` of the search that starts from ``coords``: drawn from
     ``np.random.default_rng`` seeded with the caller's seed, the call's number and a checksum of the start structure's own bytes --
@@ -910,7 +1069,7 @@ def _clustered_rounds(x, search, n, n_out, seed, init_rows, log=None, timings=No
     ``x``.  Returns ({s: output structures}, {s: [(generated, kept) per round]})."""
     import time
 
-    from .numba_functions import prune_conformers_tfd
+    from .numba_functions import prune_conformers_tfd, prune_conformers_tfd_batch
     from .utils import cartesian_product
     init_rows = {} if init_rows is None else init_rows
     n_atoms = x.shape[1]
@@ -921,12 +1080,21 @@ def _clustered_rounds(x, search, n, n_out, seed, init_rows, log=None, timings=No
     final = {}
     rot_ms, trim_ms, final_ms = [], [], 0.0
 
-    def pick(s, k, structures, torsion_array):
+    def next_call(s):
+        """(seed, rows) of the next most_diverse_conformers call of structure s."""
         c = calls[s]
         calls[s] += 1
         rows = init_rows.get((s, c))
-        sd = None if rows is not None or seed is None else _trim_seed(seed, x[s], c)
+        return (None if rows is not None or seed is None else _trim_seed(seed, x[s], c)), rows
+
+    def pick(s, k, structures, torsion_array):
+        sd, rows = next_call(s)
         return most_diverse_conformers(k, structures, torsion_array, seed=sd, init_rows=rows)
+
+    def pick_batch(members, k, structures, torsion_arrays):
+        """pick() for the structures ``members`` in ONE most_diverse_conformers_batch call, each with its own (structure, call) seed or rows."""
+        args = [next_call(s) for s in members]
+        return most_diverse_conformers_batch(k, structures, torsion_arrays, seeds=[a[0] for a in args], init_rows=[a[1] for a in args])
 
     def close_round(s, g, new):
         """What follows the candidate loop of group g of structure s (:783-840), as soon as its rows are complete."""
@@ -953,6 +1121,43 @@ def _clustered_rounds(x, search, n, n_out, seed, init_rows, log=None, timings=No
                 out = pick(s, n_out, out, tors)
             final[s] = np.asarray(out)
             del starts[s]
+            final_ms += 1e3 * (time.perf_counter() - t1)
+
+    def close_slice(part, g, news):
+        """close_round for all structures of a slice at once: the trims in one most_diverse_conformers_batch call, the finals that
+        close here in one prune_conformers_tfd_batch plus one most_diverse_conformers_batch call.  Every structure keeps the seeds and
+        rows pick() gives it; with neither seed nor rows the np.random draws of a slice's trims come before those of its finals."""
+        nonlocal final_ms
+        t0 = time.perf_counter()
+        generated = [len(new) for new in news]
+        lasts = [g + 1 == len(search[s][3]) for s in part]
+        trim = [i for i in range(len(part)) if not lasts[i] and n is not None and generated[i] > n]      # :809-819
+        if trim:
+            for i, new in zip(trim, pick_batch([part[i] for i in trim], n, [news[i] for i in trim], [search[part[i]][0] for i in trim])):
+                news[i] = new
+        for i, s in enumerate(part):
+            sizes[s].append((generated[i], len(news[i])))
+            if not lasts[i]:
+                if log:
+                    n_groups = len(search[s][3])
+                    log(s, f"  Group {g + 1}/{n_groups}: {generated[i]} structures built, kept the most diverse {len(news[i])} as starting points for the next group")
+                new = np.array(news[i])
+                output[s].append(new)                                                           # :823
+                starts[s] = new
+        t1 = time.perf_counter()
+        trim_ms[-1] += 1e3 * (t1 - t0)
+        fin = [i for i in range(len(part)) if lasts[i]]
+        if fin:
+            tors = [search[part[i]][0] for i in fin]
+            outs = [np.concatenate(output.pop(part[i]) + [news[i]]) for i in fin]               # :823, :826
+            outs = [kept for kept, _ in prune_conformers_tfd_batch(outs, tors)]                 # :827
+            again = [j for j, i in enumerate(fin) if generated[i] > n_out]                      # :829: the LAST ROUND's count, not the output's
+            if again:
+                for j, out in zip(again, pick_batch([part[fin[j]] for j in again], n_out, [outs[j] for j in again], [tors[j] for j in again])):
+                    outs[j] = out
+            for j, i in enumerate(fin):
+                final[part[i]] = np.asarray(outs[j])
+                del starts[part[i]]
             final_ms += 1e3 * (time.perf_counter() - t1)
 
     g = 0
@@ -988,8 +1193,11 @@ def _clustered_rounds(x, search, n, n_out, seed, init_rows, log=None, timings=No
                                                          include_start=True)
             rot_ms[-1] += 1e3 * (time.perf_counter() - t0)
             bounds = np.searchsorted(start_index, np.cumsum([0] + [len(starts[s]) for s in part]))
-            for k, s in enumerate(part):
-                close_round(s, g, rows[bounds[k]:bounds[k + 1]])
+            if len(part) >= CLUSTERED_BATCH_MIN_POSES:
+                close_slice(part, g, [rows[bounds[k]:bounds[k + 1]] for k in range(len(part))])
+            else:
+                for k, s in enumerate(part):
+                    close_round(s, g, rows[bounds[k]:bounds[k + 1]])
             del rows
         g += 1
     if timings is not None:
@@ -1015,6 +1223,11 @@ def clustered_csearch_batch(structures, atomnos, constrained_indices=None, keep_
       Every round's (trimmed) structures go to the output, the repeated starting points too (:823).
     * After the last group: prune_conformers_tfd on the output, then ``most_diverse_conformers(n_out, ...)`` iff the LAST ROUND
       built more than ``n_out`` structures -- not the output (:829, reproduced as it is).
+    * From ``CLUSTERED_BATCH_MIN_POSES`` structures in a slice on, the trims of the slice are ONE most_diverse_conformers_batch call
+      and the finals that close in it ONE prune_conformers_tfd_batch plus ONE most_diverse_conformers_batch call, each structure
+      with the seed or rows it would get alone: the same structures, bit for bit.  The batched calls copy what they are given
+      (concatenated input, pruned and aligned rows), in uploads of at most TFD_BATCH_BYTES / DIVERSE_BATCH_BYTES: on this route
+      the host holds one slice of candidates, the kept rows and those copies of the slice's trims.
     * The k-means initialisation, which the reference leaves to chance: ``init_rows`` maps ``(structure, call)`` -- the call's
       number among that structure's most_diverse_conformers calls -- to the rows to start from; otherwise, with ``seed``, each
       such call gets a seed of its own (_trim_seed) that depends on the structure's coordinates and the call, not on its place in
