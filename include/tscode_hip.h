@@ -74,48 +74,72 @@ int tsc_ctx_destroy(tsc_ctx *ctx);
  * torch.cuda.Stream current and pass its .cuda_stream here (tscode_amd/pipeline.py does). */
 int tsc_ctx_set_stream(tsc_ctx *ctx, void *hip_stream);
 int tsc_ctx_synchronize(tsc_ctx *ctx);
-/* Tunables.  "prune_algo": 0 = automatic (default), 1 = register-tiled all-pairs kernel (<= 32 heavy atoms),
- * 2 = descriptor sieve (any size);  "seg_cols": columns per pair-kernel work item (multiple of 256, at most 4096; 0 = automatic);
- * "drain_min": queued pairs that trigger an evaluation batch in the sieve kernel (1..64, default 32);
- * "sieve_cpl": columns per lane of the sieve kernel's screen, 1, 2 (default) or 4 -- register footprint against occupancy;
- * "early_basis": 1 (default) lets tsc_pipeline_dev estimate the descriptor basis of the prune from a sample of the unfiltered
- * poses on a side stream while the clash kernel runs (the choice of basis never changes a verdict); 0 = from the filtered
- * structures, on the main stream.  "fuse_descriptors": 1 (default) then lets the kernel that embeds the passing poses write their
- * descriptors as well (poses of up to about 80 heavy atoms; otherwise and with 0 a separate launch reads the coordinates back).
- * "pca_min_n": ensembles smaller than this (default 6000) take the identity basis for their descriptors instead of estimated
- * principal axes (three launches and about 45 us less per run; any basis gives the same verdicts).
- * "local_pass": 1 (default) lets passes whose longest chunk has at most "local_max_chunk" (default 384, up to 2048) structures
- * run in the one-launch chunk-local kernel; "sieve_trim": 1 (default) = the screen's shorter instruction sequence;
- * "sieve_mm": the pair kernels with the descriptor screen on the matrix cores and 64 rows per work item (csrc/mm.hpp, cull_mm.hpp):
- * 0 never, 1 (default) in runs of at least "mm_min_n" structures (default 100000), 2 always; "sieve_mm16": 1 (default) = smaller runs
- * take the matrix-core screen on 16-row work items (k_rmsd_sieve_mm16), 0 = the packed-fp32 screen; "mm_seg_cols": columns per work
- * item of the walked passes' 64-row kernel (a multiple of 64 up to 1024; 0 = automatic);
- * "fused_apply": 1 (default) lets the sieve kernel of a single-rank pass apply a row tile's verdicts itself when the tile's last
- * work item finishes and close the pass (two launches per pass); 0 = tsc_prune_pass_finish launches k_apply_pass (always so for the
- * register-tiled kernel and for passes searched by several ranks);  "open_lds_blocks": scan blocks (2048 structures each) up to which
- * the per-row kernel stages their prefix in LDS (default: its capacity, 2048; 0 = always read it from memory; tests);  "clash_fp32": 1 (default)
- * decides verdict-only clash masks by a packed-fp32 minimum with fp64 fallback;
- * "cull": 1 (default) lets the large passes of the sieve (at least "cull_min_pairs" = n (n / k) / 2 pairs, default 2e9, fewer than 64
- * chunks) lay their active structures out along a Morton curve of the descriptors and skip the tile pairs whose bounding boxes lie
- * beyond the screen's limit, where the rows' ranges are long enough for that to pay (decided per pass on the device, one
- * synchronisation); 0 = never, 2 = every such pass (tests).  "deterministic_basis": 1 = the descriptor basis from fixed-order sums, so
- * that every rank of a sharded run derives bit-identical descriptors and hence the same layout (default 0: atomics, 35 us faster).
- * A run remembers which of the two it was created under: only a run created under 1 culls a pass whose ROW TILES are dealt to several
- * ranks (tsc_prune_pass_local / tsc_prune_pass_rows with world_size > 1 -- the ranks deal the tiles of ONE sorted layout); a run created
- * under 0 walks such a pass in index order, and refuses it (TSC_ERR_STATE) when it had itself chosen the all-pairs kernel from its own
- * basis estimate ("prune_algo" 0), a choice that ranks with different estimates could make differently;
- * "cull_tile_block" (256): a culled pass dealt to several ranks by row tiles (tsc_prune_pass_local(rank, world)) gives a rank runs of this many
- * consecutive tiles of the sorted layout -- neighbours on the curve share their columns, and a row's early exit knows more of what was found;
- * "stage1_f32": the pair kernels' first look at a pair that passed the screen (H = p^T q and the quartic tests) reads a float32 copy
- * of the coordinates with the rounding bound that goes with it, the float64 coordinates only for what that leaves undecided: 0 = never,
- * 1 (default) = in runs with 128 MB of heavy-atom coordinates or more (where the gathers come from HBM), 2 = always;
- * "prune_batch_max_n": structures per segment that tsc_prune_rmsd_batch takes at most (1 .. 8192, default 2048; see there);
- * "pass_timing": HIP events for tsc_pass_stats.gpu_ms / tile_ms and the pipeline's stage timings: 0 = none (default; an
- * event record in the stream costs about 4 us on MI355X), 1 = the pair kernel's own start/stop events (tile_ms; passes run by the
- * chunk-local kernel carry theirs at level 2 only), 2 = also around every whole pass (gpu_ms) and the stages of tsc_pipeline_dev. */
+/* Tunables, one entry per option in the order of the table that defines them (csrc/options.hpp: name, default and what is accepted).
+ * A value outside what an option accepts is refused (TSC_ERR_INVALID; the message names the option, what it takes and the value given)
+ * and leaves the option as it was; fractions are cut off.
+ *   "prune_algo": 0 = automatic (default), 1 = register-tiled all-pairs kernel (<= 32 heavy atoms), 2 = descriptor sieve (any size);
+ *   "seg_cols": columns per pair-kernel work item (multiple of 256, at most 4096; 0 = automatic, the default);
+ *   "drain_min": queued pairs that trigger an evaluation batch in the sieve kernel (1..64, default 32);
+ *   "sieve_trim": 1 (default) = the screen's shorter instruction sequence, 0 = the other screen;
+ *   "sieve_mm": the pair kernels with the descriptor screen on the matrix cores and 64 rows per work item (csrc/mm.hpp, cull_mm.hpp):
+ *      0 never, 1 (default) in runs of at least mm_min_n structures, 2 always;
+ *   "mm_min_n": the number of structures from which sieve_mm 1 takes the 64-row kernels (0 .. 4e9, default 100000);
+ *   "sieve_mm16": 1 (default) = smaller runs take the matrix-core screen on 16-row work items (k_rmsd_sieve_mm16), 0 = the packed-fp32 screen;
+ *   "mm_seg_cols": columns per work item of the walked passes' 64-row kernel (a multiple of 64 up to 1024; 0 = automatic, the default);
+ *   "sieve_cpl": columns per lane of the sieve kernel's screen, 1, 2 (default) or 4 -- register footprint against occupancy;
+ *   "pca_min_n": ensembles smaller than this (0 .. 1e9, default 6000) take the identity basis for their descriptors instead of estimated
+ *      principal axes (three launches and about 45 us less per run; any basis gives the same verdicts);
+ *   "fuse_descriptors": 1 (default) lets the kernel that embeds the passing poses write their descriptors as well, under early_basis
+ *      (poses of up to about 80 heavy atoms; otherwise and with 0 a separate launch reads the coordinates back);
+ *   "early_basis": 1 (default) lets tsc_pipeline_dev estimate the descriptor basis of the prune from a sample of the unfiltered
+ *      poses on a side stream while the clash kernel runs (the choice of basis never changes a verdict); 0 = from the filtered
+ *      structures, on the main stream;
+ *   "clash_first": 0 (default) = tsc_pipeline_dev enqueues the chain that estimates the early basis in front of the clash launch,
+ *      1 = behind it;
+ *   "cull_tile_block" (1 .. 65536, default 256): a culled pass dealt to several ranks by row tiles (tsc_prune_pass_local(rank, world)) gives
+ *      a rank runs of this many consecutive tiles of the sorted layout -- neighbours on the curve share their columns, and a row's early
+ *      exit knows more of what was found;
+ *   "stage1_f32": the pair kernels' first look at a pair that passed the screen (H = p^T q and the quartic tests) reads a float32 copy
+ *      of the coordinates with the rounding bound that goes with it, the float64 coordinates only for what that leaves undecided:
+ *      0 = never, 1 (default) = in runs with 128 MB of heavy-atom coordinates or more (where the gathers come from HBM) -- with 8 MB
+ *      or more where the matrix-core kernels run --, 2 = always (the value is not checked: any other means never);
+ *   "local_max_chunk": see local_pass (16 .. 2048, default 384);
+ *   "local_pass": 1 (default) lets passes whose longest chunk has at most local_max_chunk structures run in the one-launch
+ *      chunk-local kernel;
+ *   "fused_apply": 1 (default) lets the sieve kernel of a single-rank pass apply a row tile's verdicts itself when the tile's last
+ *      work item finishes and close the pass (two launches per pass); 0 = tsc_prune_pass_finish launches k_apply_pass (always so for
+ *      the register-tiled kernel and for passes searched by several ranks);
+ *   "open_lds_blocks": scan blocks (2048 structures each) up to which the per-row kernel stages their prefix in LDS (default: its
+ *      capacity, 2048; 0 = always read it from memory; tests; not negative, and more than 2^30 is stored as 2^30);
+ *   "clash_fp32": 1 (default) decides verdict-only clash masks by a packed-fp32 minimum with fp64 fallback;
+ *   "clash_lanes": 1 (default) lets such a mask of two fragments, the smaller of at most 32 atoms, be decided by the kernel that embeds
+ *      the poses, one pose per lane (k_clash_lanes); 0 = by the clash kernel;
+ *   "deterministic_basis": 1 = the descriptor basis from fixed-order sums, so that every rank of a sharded run derives bit-identical
+ *      descriptors and hence the same layout (default 0: atomics, 35 us faster; any non-zero value counts as 1).  A run remembers which
+ *      of the two it was created under: only a run created under 1 culls a pass whose ROW TILES are dealt to several ranks
+ *      (tsc_prune_pass_local / tsc_prune_pass_rows with world_size > 1 -- the ranks deal the tiles of ONE sorted layout); a run created
+ *      under 0 walks such a pass in index order, and refuses it (TSC_ERR_STATE) when it had itself chosen the all-pairs kernel from its
+ *      own basis estimate (prune_algo 0), a choice that ranks with different estimates could make differently;
+ *   "cull": 1 (default) lets the large passes of the sieve (at least cull_min_pairs pairs, fewer than 64 chunks) lay their active
+ *      structures out along a Morton curve of the descriptors and skip the tile pairs whose bounding boxes lie beyond the screen's limit,
+ *      where the rows' ranges are long enough for that to pay (decided per pass on the device, one synchronisation); 0 = never,
+ *      2 = every such pass (tests);
+ *   "cull_min_pairs": the pairs n (n / k) / 2 from which a pass is large in the sense of cull (not negative, default 2e9);
+ *   "cull_grid": workgroups of the culled pair kernel at most, each walking work items with that stride, where cull_xcd is 0
+ *      (at least 1, default 2^30);
+ *   "cull_xcd": 1 (default) = the culled pair kernel keys runs of 32 row groups to XCDs (workgroup b runs on XCD b % 8), so that the
+ *      workgroups an XCD has in flight share their column windows in its L2; 0 = work items in plain order (any non-zero value counts as 1);
+ *   "prune_batch_max_n": structures per segment that tsc_prune_rmsd_batch takes at most (a whole number, 1 .. 8192, default 2048; see there);
+ *   "pass_timing": HIP events for tsc_pass_stats.gpu_ms / tile_ms and the pipeline's stage timings: 0 = none (default; an
+ *      event record in the stream costs about 4 us on MI355X), 1 = the pair kernel's own start/stop events (tile_ms; passes run by the
+ *      chunk-local kernel carry theirs at level 2 only), 2 = also around every whole pass (gpu_ms) and the stages of tsc_pipeline_dev.
+ * (A library built with -DTSC_DBG_STAMPS has one more, dbg_stamp_k: tools/stamps.py.) */
 int tsc_ctx_set_option(tsc_ctx *ctx, const char *name, double value);
-/* The current value of a tunable the host side routes by: "prune_batch_max_n" (the Python layer sends longer ensembles to tsc_prune_rmsd). */
+/* The current value of a tunable as it is stored: every option can be read ("deterministic_basis" set to 5 reads 1). */
 int tsc_ctx_get_option(tsc_ctx *ctx, const char *name, double *value);
+/* The options by index, without a context: the name and the default of option `index` (either pointer may be NULL), TSC_ERR_INVALID
+ * past the last one.  Lets a host or a test list the options without a list of its own. */
+int tsc_option_info(int index, const char **name, double *default_value);
 /* Device memory helpers for hosts that do not bring their own allocator (tests, C callers). */
 int tsc_malloc(tsc_ctx *ctx, size_t bytes, void **dptr);
 int tsc_free(tsc_ctx *ctx, void *dptr);

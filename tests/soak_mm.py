@@ -14,7 +14,6 @@ import numpy as np
 ROUTES = [("mm64-walked", 2, 1, 1, 2.0e9, 1, 0, 1), ("mm64-walked-f32-local", 2, 1, 1, 2.0e9, 2, 1, 1), ("mm64-culled", 2, 1, 2, 0.0, 1, 0, 1),
           ("mm64-culled-f32", 2, 1, 2, 0.0, 2, 1, 1), ("mm16", 1, 1, 1, 2.0e9, 1, 0, 1), ("mm16-f32-apply", 1, 1, 1, 2.0e9, 2, 1, 0),
           ("vector", 0, 0, 1, 2.0e9, 1, 1, 1)]
-DEFAULTS = (("prune_algo", 0), ("sieve_mm", 1), ("sieve_mm16", 1), ("cull", 1), ("cull_min_pairs", 2.0e9), ("stage1_f32", 1), ("local_pass", 1), ("fused_apply", 1))
 
 
 def make_case(rng, sizes=(1500, 2048, 3001, 6000, 8191, 12000, 20001, 40000)):
@@ -34,19 +33,13 @@ def make_case(rng, sizes=(1500, 2048, 3001, 6000, 8191, 12000, 20001, 40000)):
 
 
 def run_routes(eng, heavy, thr, mode, ref):
-    """{route: ok} of the prune through every route against the oracle's result `ref`; leaves the library's options at their defaults."""
+    """{route: ok} of the prune through every route against the oracle's result `ref`; leaves the library's options as it found them."""
     out = {}
-    try:
-        for name, smm, s16, cull, cmp_, f32, local, fused in ROUTES:
-            for k, v in (("prune_algo", 2), ("sieve_mm", smm), ("sieve_mm16", s16), ("cull", cull), ("cull_min_pairs", cmp_), ("stage1_f32", f32),
-                         ("local_pass", local), ("fused_apply", fused)):
-                eng.set_option(k, v)
+    for name, smm, s16, cull, cmp_, f32, local, fused in ROUTES:
+        with eng.options(prune_algo=2, sieve_mm=smm, sieve_mm16=s16, cull=cull, cull_min_pairs=cmp_, stage1_f32=f32, local_pass=local, fused_apply=fused):
             mask, stats = eng.prune_heavy(heavy, thr, mode)
-            out[name] = bool(np.array_equal(mask, ref["mask"]) and [s["k"] for s in stats] == [s["k"] for s in ref["stats"]]
-                             and [s["pairs_evaluated"] for s in stats] == [s["pairs_evaluated"] for s in ref["stats"]])
-    finally:
-        for k, v in DEFAULTS:
-            eng.set_option(k, v)
+        out[name] = bool(np.array_equal(mask, ref["mask"]) and [s["k"] for s in stats] == [s["k"] for s in ref["stats"]]
+                         and [s["pairs_evaluated"] for s in stats] == [s["pairs_evaluated"] for s in ref["stats"]])
     return out
 
 

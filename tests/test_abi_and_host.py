@@ -32,6 +32,25 @@ def test_library_exports_every_header_symbol():
     assert lib.tsc_version() == 100
 
 
+def test_option_table_checks_itself_and_the_header_documents_exactly_its_options(tmp_path):
+    """tools/probe/options_check.cpp (csrc/options.hpp alone, no HIP call; built here without the sanitizers of tools/options_check.py)
+    walks the option table: defaults, accepted and refused values of every row, unknown names, tsc_option_info.  The names it lists
+    are the quoted names of the comment above tsc_ctx_set_option in the header, in the same order."""
+    import subprocess
+
+    from tscode_amd.build import _hipcc
+    exe = str(tmp_path / "options_check")
+    subprocess.run([_hipcc(), "-O1", "-std=c++17", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function", "-Wno-cuda-compat", "-o", exe,
+                    os.path.join(ROOT, "tools", "probe", "options_check.cpp")], check=True, cwd=ROOT)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and re.search(r"options_check: \d+ checks passed", run.stdout), run.stdout + run.stderr
+    listed = [line.split()[0] for line in subprocess.run([exe, "--list"], capture_output=True, text=True, check=True).stdout.splitlines()]
+    assert len(listed) >= 28 and len(set(listed)) == len(listed)
+    text = open(os.path.join(ROOT, "include", "tscode_hip.h")).read()
+    block = text[text.index("/* Tunables"):text.index("int tsc_ctx_set_option(")]
+    assert re.findall(r'"([a-z_0-9]+)"', block) == listed
+
+
 def test_no_cpp_exception_can_cross_the_c_abi():
     """SURVEY.md 8b: "no C++ exception crosses the boundary".  The library's context holds std::map / std::vector and calls `new`:
     every `extern "C"` entry point that returns a status must run its body inside the try / catch of TSC_API_GUARD_BEGIN / _END

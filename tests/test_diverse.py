@@ -529,25 +529,22 @@ def test_stage_times_are_taken_only_under_pass_timing_and_per_thread():
         t.join()
         return got[0]
 
-    eng.set_option("pass_timing", 0)
-    want = tscode_amd.diverse_select(s, 2, init_rows=[0, 1])
-    assert times() == [-1.0] * 4
-    eng.set_option("pass_timing", 1)
-    try:
-        got = tscode_amd.diverse_select(s, 2, init_rows=[0, 1])
-        assert all(np.isfinite(t) and t > 0.0 for t in times()), times()
-        assert all(np.asarray(a).tobytes() == np.asarray(b).tobytes() for a, b in zip(got, want))
-        assert in_a_fresh_thread() == [-1.0] * 4
-        tscode_amd.align_structures(s.copy())
-        align = times()
-        assert np.isfinite(align[0]) and align[0] > 0.0 and align[1:] == [-1.0] * 3, align
-        tscode_amd.kmeans_lloyd(s.reshape(8, -1), s.reshape(8, -1)[:2])
-        lloyd = times()
-        assert lloyd[0] == -1.0 and lloyd[3] == -1.0 and lloyd[1] > 0.0 and lloyd[2] > 0.0, lloyd
-    finally:
-        eng.set_option("pass_timing", 0)
-    tscode_amd.diverse_select(s, 2, init_rows=[0, 1])
-    assert times() == [-1.0] * 4
+    with eng.options(pass_timing=0):
+        want = tscode_amd.diverse_select(s, 2, init_rows=[0, 1])
+        assert times() == [-1.0] * 4
+        with eng.options(pass_timing=1):
+            got = tscode_amd.diverse_select(s, 2, init_rows=[0, 1])
+            assert all(np.isfinite(t) and t > 0.0 for t in times()), times()
+            assert all(np.asarray(a).tobytes() == np.asarray(b).tobytes() for a, b in zip(got, want))
+            assert in_a_fresh_thread() == [-1.0] * 4
+            tscode_amd.align_structures(s.copy())
+            align = times()
+            assert np.isfinite(align[0]) and align[0] > 0.0 and align[1:] == [-1.0] * 3, align
+            tscode_amd.kmeans_lloyd(s.reshape(8, -1), s.reshape(8, -1)[:2])
+            lloyd = times()
+            assert lloyd[0] == -1.0 and lloyd[3] == -1.0 and lloyd[1] > 0.0 and lloyd[2] > 0.0, lloyd
+        tscode_amd.diverse_select(s, 2, init_rows=[0, 1])
+        assert times() == [-1.0] * 4
 
 
 @pytest.mark.parametrize("k", (16, 17, 128))

@@ -214,9 +214,6 @@ def test_prune_golden(eng, algo):
         assert np.cumsum([s["new_keys"] for s in stats]).tolist() == g[f"pass_nkeys{c}"].tolist()
 
 
-SIEVE_TRIM_DEFAULT = 1   # the library's default of option sieve_trim; the fixture `algo` also runs the other setting
-
-
 @pytest.fixture(params=[(0, 1, False, 1), (1, 1, False, 1), (2, 0, False, 1), (2, 0, True, 1), (2, 0, False, 0), (0, 1, False, 2), (2, 0, False, 3),
                         (2, 0, False, 4), (2, 0, False, 5), (2, 0, False, 6), (0, 1, False, 7), (2, 0, False, 8), (2, 0, False, 9), (2, 0, False, 10)],
                 ids=["algo-auto", "algo-tile", "algo-sieve-global", "algo-sieve-other-screen", "algo-sieve-separate-apply", "algo-auto-ranks-from-memory",
@@ -236,31 +233,19 @@ def algo(request, eng):
     its own apply launch, walked and culled (cull_mm.hpp), with stage 1 in float64 and on the float32 copy; the two "16-row" routes leave the choice to the library, which gives
     ensembles of this size the matrix-core screen on 16-row items (k_rmsd_sieve_mm16: what C3 runs); "other-screen" and the three
     "vector-screen" routes switch both off and run the packed-fp32 screen of sieve.hpp (what row tiles dealt to several ranks still use)."""
-    eng.set_option("prune_algo", request.param[0])
-    eng.set_option("sieve_mm", 0 if (request.param[2] or request.param[3] in (6, 7, 8)) else (1 if request.param[3] in (9, 10) else 2))
-    eng.set_option("sieve_mm16", 0 if (request.param[2] or request.param[3] in (6, 7, 8)) else 1)
-    eng.set_option("local_pass", request.param[1])
+    vector_screen = request.param[2] or request.param[3] in (6, 7, 8)
+    opts = dict(prune_algo=request.param[0], sieve_mm=0 if vector_screen else (1 if request.param[3] in (9, 10) else 2),
+                sieve_mm16=0 if vector_screen else 1, local_pass=request.param[1], fused_apply=1 if request.param[3] not in (0, 10) else 0)
     if request.param[2]:
-        eng.set_option("sieve_trim", 1 - SIEVE_TRIM_DEFAULT)
-    eng.set_option("fused_apply", 1 if request.param[3] not in (0, 10) else 0)
+        opts["sieve_trim"] = 1 - eng.get_option("sieve_trim")
     if request.param[3] == 2:
-        eng.set_option("open_lds_blocks", 0)
+        opts["open_lds_blocks"] = 0
     if request.param[3] in (3, 5, 8):      # every pass of fewer than 64 chunks laid out along the Morton curve, tile pairs skipped by bounding box (cull.hpp)
-        eng.set_option("cull_min_pairs", 0)
-        eng.set_option("cull", 2)
+        opts.update(cull_min_pairs=0, cull=2)
     if request.param[3] in (4, 5, 7):      # H of stage 1 from the float32 copy, its own rounding bound (sieve.hpp: pair_stage1)
-        eng.set_option("stage1_f32", 2)
-    yield request.param[0]
-    eng.set_option("sieve_mm", 1)
-    eng.set_option("sieve_mm16", 1)
-    eng.set_option("stage1_f32", 1)
-    eng.set_option("cull_min_pairs", 2.0e9)
-    eng.set_option("cull", 1)
-    eng.set_option("prune_algo", 0)
-    eng.set_option("local_pass", 1)
-    eng.set_option("sieve_trim", SIEVE_TRIM_DEFAULT)
-    eng.set_option("fused_apply", 1)
-    eng.set_option("open_lds_blocks", 2 ** 30)
+        opts["stage1_f32"] = 2
+    with eng.options(**opts):
+        yield request.param[0]
 
 
 @pytest.mark.parametrize("name", LARGE_PRUNE_CASES)
@@ -291,30 +276,29 @@ def test_prune_large_golden_every_pass_mask(eng, name, mm):
     import ctypes as C
 
     from tscode_amd import _lib
-    eng.set_option("sieve_mm", mm)
-    fx = load_large_prune(name)
-    g = fx.g
-    lib = eng.lib
-    d_heavy = C.c_void_p()
-    _lib.check(lib.tsc_malloc(eng._h, fx.heavy.nbytes, C.byref(d_heavy)))
-    _lib.check(lib.tsc_memcpy_h2d(eng._h, d_heavy, _lib.ptr(fx.heavy), fx.heavy.nbytes))
-    st = eng.prune_stepper(d_heavy.value, fx.n, fx.heavy.shape[1], fx.thr, 0)
-    after = {}
-    try:
-        while True:
-            k = st.next_pass()
-            if k == 0:
-                break
-            st.pass_local(0, 1)
-            st.pass_finish()
-            m = np.empty(fx.n, dtype=np.uint8)
-            _lib.check(lib.tsc_memcpy_d2h(eng._h, _lib.ptr(m), C.c_void_p(st.mask_ptr()), m.nbytes))
-            after[int(k)] = np.packbits(m.astype(bool))
-        ran = [s["k"] for s in st.stats()]
-    finally:
-        st.close()
-        _lib.check(lib.tsc_free(eng._h, d_heavy))
-        eng.set_option("sieve_mm", 1)
+    with eng.options(sieve_mm=mm):
+        fx = load_large_prune(name)
+        g = fx.g
+        lib = eng.lib
+        d_heavy = C.c_void_p()
+        _lib.check(lib.tsc_malloc(eng._h, fx.heavy.nbytes, C.byref(d_heavy)))
+        _lib.check(lib.tsc_memcpy_h2d(eng._h, d_heavy, _lib.ptr(fx.heavy), fx.heavy.nbytes))
+        st = eng.prune_stepper(d_heavy.value, fx.n, fx.heavy.shape[1], fx.thr, 0)
+        after = {}
+        try:
+            while True:
+                k = st.next_pass()
+                if k == 0:
+                    break
+                st.pass_local(0, 1)
+                st.pass_finish()
+                m = np.empty(fx.n, dtype=np.uint8)
+                _lib.check(lib.tsc_memcpy_d2h(eng._h, _lib.ptr(m), C.c_void_p(st.mask_ptr()), m.nbytes))
+                after[int(k)] = np.packbits(m.astype(bool))
+            ran = [s["k"] for s in st.stats()]
+        finally:
+            st.close()
+            _lib.check(lib.tsc_free(eng._h, d_heavy))
     assert ran == g["ks"].tolist()
     for k, bits in zip(ran, g["pass_mask_bits"]):
         assert np.array_equal(after[k], bits), f"{name}: the mask after the k = {k} pass differs from the reference's"
@@ -398,61 +382,59 @@ def test_prune_sharded_rows_equal_single(eng, oracle, mm):
     kernel, which deals groups of 64 rows (sieve_mm = 2)."""
     import ctypes as C
 
-    eng.set_option("sieve_mm", mm)
-
-    from tscode_amd import _lib
-    from tscode_amd.synthetic import make_config
-    ens = make_config("C2", 6000)
-    heavy = np.ascontiguousarray(ens.poses()[:, ens.atomnos != 1])
-    ref_mask, ref_stats = eng.prune_heavy(heavy, 0.5, 0)
-    lib = eng.lib
-    d_heavy = C.c_void_p()
-    _lib.check(lib.tsc_malloc(eng._h, heavy.nbytes, C.byref(d_heavy)))
-    _lib.check(lib.tsc_memcpy_h2d(eng._h, d_heavy, _lib.ptr(heavy), heavy.nbytes))
-    # three steppers (one per rank) over the same heavy array; after each pass the best[]
-    # arrays are min-merged on the host and written back, as the all-reduce(MIN) would do.
-    steppers = [eng.prune_stepper(d_heavy.value, len(heavy), heavy.shape[1], 0.5, 0) for _ in range(3)]
-    while True:
-        ks_now = [s.next_pass() for s in steppers]
-        assert len(set(ks_now)) == 1
-        if ks_now[0] == 0:
-            break
-        bests = []
-        for rank, s in enumerate(steppers):
-            s.pass_local(rank, 3)
-            p, n = s.best_ptr()
-            b = np.empty(n, dtype=np.int32)
-            _lib.check(lib.tsc_memcpy_d2h(eng._h, _lib.ptr(b), C.c_void_p(p), b.nbytes))
-            bests.append(b)
-        merged = np.minimum.reduce(bests)
+    with eng.options(sieve_mm=mm):
+        from tscode_amd import _lib
+        from tscode_amd.synthetic import make_config
+        ens = make_config("C2", 6000)
+        heavy = np.ascontiguousarray(ens.poses()[:, ens.atomnos != 1])
+        ref_mask, ref_stats = eng.prune_heavy(heavy, 0.5, 0)
+        lib = eng.lib
+        d_heavy = C.c_void_p()
+        _lib.check(lib.tsc_malloc(eng._h, heavy.nbytes, C.byref(d_heavy)))
+        _lib.check(lib.tsc_memcpy_h2d(eng._h, d_heavy, _lib.ptr(heavy), heavy.nbytes))
+        # three steppers (one per rank) over the same heavy array; after each pass the best[]
+        # arrays are min-merged on the host and written back, as the all-reduce(MIN) would do.
+        steppers = [eng.prune_stepper(d_heavy.value, len(heavy), heavy.shape[1], 0.5, 0) for _ in range(3)]
+        while True:
+            ks_now = [s.next_pass() for s in steppers]
+            assert len(set(ks_now)) == 1
+            if ks_now[0] == 0:
+                break
+            bests = []
+            for rank, s in enumerate(steppers):
+                s.pass_local(rank, 3)
+                p, n = s.best_ptr()
+                b = np.empty(n, dtype=np.int32)
+                _lib.check(lib.tsc_memcpy_d2h(eng._h, _lib.ptr(b), C.c_void_p(p), b.nbytes))
+                bests.append(b)
+            merged = np.minimum.reduce(bests)
+            for s in steppers:
+                p, n = s.best_ptr()
+                _lib.check(lib.tsc_memcpy_h2d(eng._h, C.c_void_p(p), _lib.ptr(merged), merged.nbytes))
+                s.pass_finish()
+        masks = []
         for s in steppers:
-            p, n = s.best_ptr()
-            _lib.check(lib.tsc_memcpy_h2d(eng._h, C.c_void_p(p), _lib.ptr(merged), merged.nbytes))
+            m = np.empty(len(heavy), dtype=np.uint8)
+            _lib.check(lib.tsc_memcpy_d2h(eng._h, _lib.ptr(m), C.c_void_p(s.mask_ptr()), m.nbytes))
+            masks.append(m.astype(bool))
+            assert [x["n_active_after"] for x in s.stats()] == [x["n_active_after"] for x in ref_stats]
+            s.close()
+        for m in masks:
+            assert np.array_equal(m, ref_mask)
+        # ONE stepper standing in for all three ranks: rank 0 opens the pass, the others' rows follow (tsc_prune_pass_rows)
+        s = eng.prune_stepper(d_heavy.value, len(heavy), heavy.shape[1], 0.5, 0)
+        while s.next_pass() != 0:
+            s.pass_local(0, 3)
+            s.pass_rows(2, 3)
+            s.pass_rows(1, 3)
+            s.pass_rows(2, 3)                                 # a share twice: the same minimum
             s.pass_finish()
-    masks = []
-    for s in steppers:
         m = np.empty(len(heavy), dtype=np.uint8)
         _lib.check(lib.tsc_memcpy_d2h(eng._h, _lib.ptr(m), C.c_void_p(s.mask_ptr()), m.nbytes))
-        masks.append(m.astype(bool))
-        assert [x["n_active_after"] for x in s.stats()] == [x["n_active_after"] for x in ref_stats]
+        assert np.array_equal(m.astype(bool), ref_mask)
+        assert [x["pairs_evaluated"] for x in s.stats()] == [x["pairs_evaluated"] for x in ref_stats]
         s.close()
-    for m in masks:
-        assert np.array_equal(m, ref_mask)
-    # ONE stepper standing in for all three ranks: rank 0 opens the pass, the others' rows follow (tsc_prune_pass_rows)
-    s = eng.prune_stepper(d_heavy.value, len(heavy), heavy.shape[1], 0.5, 0)
-    while s.next_pass() != 0:
-        s.pass_local(0, 3)
-        s.pass_rows(2, 3)
-        s.pass_rows(1, 3)
-        s.pass_rows(2, 3)                                 # a share twice: the same minimum
-        s.pass_finish()
-    m = np.empty(len(heavy), dtype=np.uint8)
-    _lib.check(lib.tsc_memcpy_d2h(eng._h, _lib.ptr(m), C.c_void_p(s.mask_ptr()), m.nbytes))
-    assert np.array_equal(m.astype(bool), ref_mask)
-    assert [x["pairs_evaluated"] for x in s.stats()] == [x["pairs_evaluated"] for x in ref_stats]
-    s.close()
-    _lib.check(lib.tsc_free(eng._h, d_heavy))
-    eng.set_option("sieve_mm", 1)
+        _lib.check(lib.tsc_free(eng._h, d_heavy))
 
 
 def test_non_finite_coordinates_have_a_defined_outcome(eng, oracle):
@@ -475,11 +457,8 @@ def test_non_finite_coordinates_have_a_defined_outcome(eng, oracle):
     for mode in (0, 1):
         ref = oracle.prune_heavy(bad, 0.5, mode=mode)
         for local_pass in (1, 0):
-            eng.set_option("local_pass", local_pass)
-            try:
+            with eng.options(local_pass=local_pass):
                 mask, stats = eng.prune_heavy(bad, 0.5, mode)
-            finally:
-                eng.set_option("local_pass", 1)
             assert mask[[17, 2500, 5999]].all() and np.array_equal(mask, ref["mask"]), (mode, local_pass)
             assert all(s["nonfinite_input"] == 1 for s in stats)
             assert [s["n_active_after"] for s in stats] == [s["n_active_after"] for s in ref["stats"]]
@@ -518,13 +497,8 @@ def test_culled_row_tiles_dealt_to_emulated_ranks(eng, oracle, world, n_poses, t
     ref = oracle.prune_heavy(heavy, 0.5, mode=0, row_parallel=True)
     dev = torch.device("cuda:0")
     d_heavy = torch.from_numpy(heavy).to(dev)
-    eng.set_option("cull_min_pairs", 0)
-    eng.set_option("cull", 2)
-    eng.set_option("local_pass", 0)
-    eng.set_option("cull_tile_block", tile_block)
-    eng.set_option("deterministic_basis", det)
-    eng.set_option("sieve_mm", mm)      # (2: the matrix-core kernels, which deal groups of 64 rows -- runs of tile_block / 4 of them)
-    try:
+    # (sieve_mm 2: the matrix-core kernels, which deal groups of 64 rows -- runs of tile_block / 4 of them)
+    with eng.options(cull_min_pairs=0, cull=2, local_pass=0, cull_tile_block=tile_block, deterministic_basis=det, sieve_mm=mm):
         sts = [eng.prune_stepper(d_heavy, len(heavy), heavy.shape[1], 0.5, 0) for _ in range(world)]
         bests = [torch.empty(len(heavy), dtype=torch.int32, device=dev) for _ in range(world)]
         for s, b in zip(sts, bests):
@@ -550,13 +524,6 @@ def test_culled_row_tiles_dealt_to_emulated_ranks(eng, oracle, world, n_poses, t
             assert np.array_equal(keep.cpu().numpy().astype(bool), ref["mask"])
             assert [x["n_active_after"] for x in s.stats()] == [x["n_active_after"] for x in ref["stats"]]
             s.close()
-    finally:
-        eng.set_option("cull_min_pairs", 2.0e9)
-        eng.set_option("cull", 1)
-        eng.set_option("local_pass", 1)
-        eng.set_option("cull_tile_block", 256)
-        eng.set_option("deterministic_basis", 0)
-        eng.set_option("sieve_mm", 1)
 
 
 def test_pass_timing_levels_change_nothing_but_the_times(eng, oracle):
@@ -568,17 +535,10 @@ def test_pass_timing_levels_change_nothing_but_the_times(eng, oracle):
     ens = make_config("C2", 9_000)
     heavy = np.ascontiguousarray(ens.poses()[:, ens.atomnos != 1])
     ref = oracle.prune_heavy(heavy, 0.5, mode=0, row_parallel=True)
-    eng.set_option("cull_min_pairs", 5e6)
-    eng.set_option("cull", 2)
     runs = {}
-    try:
-        for level in (0, 1, 2):
-            eng.set_option("pass_timing", level)
+    for level in (0, 1, 2):
+        with eng.options(cull_min_pairs=5e6, cull=2, pass_timing=level):
             runs[level] = eng.prune_heavy(heavy, 0.5, 0)
-    finally:
-        eng.set_option("pass_timing", 0)
-        eng.set_option("cull_min_pairs", 2.0e9)
-        eng.set_option("cull", 1)
     for level, (mask, stats) in runs.items():
         print(level, [(s["k"], s["algo"], round(s["gpu_ms"], 4), round(s["tile_ms"], 4)) for s in stats])
     want = [(s["k"], s["n_active_after"], s["pairs_evaluated"]) for s in ref["stats"]]
@@ -608,14 +568,9 @@ def test_partitioned_passes_emulated_ranks(eng, oracle, world, min_chunks, n_pos
     ref = oracle.prune_heavy(heavy, 0.5, mode=mode)
     one_mask, one_stats = eng.prune_heavy(heavy, 0.5, mode)
     assert np.array_equal(one_mask, ref["mask"])
-    if cull:        # every pass of fewer than 64 chunks that does not fit the chunk-local kernel: sorted layout + bounding boxes inside each rank's chunks
-        eng.set_option("cull", 2)
-        eng.set_option("cull_min_pairs", 0)
-    try:
+    # cull: every pass of fewer than 64 chunks that does not fit the chunk-local kernel: sorted layout + bounding boxes inside each rank's chunks
+    with eng.options(**(dict(cull=2, cull_min_pairs=0) if cull else {})):
         _partitioned_emulation(eng, torch, PruneStepper, heavy, ref, one_stats, world, min_chunks, mode)
-    finally:
-        eng.set_option("cull", 1)
-        eng.set_option("cull_min_pairs", 2.0e9)
 
 
 def _partitioned_emulation(eng, torch, PruneStepper, heavy, ref, one_stats, world, min_chunks, mode):
@@ -714,9 +669,8 @@ def test_pipeline_c2_vs_oracle(eng, oracle):
     # beside the clash kernel: a different basis, the same verdicts
     keep2 = torch.empty(n, dtype=torch.uint8, device=dev)
     for opt in ("early_basis", "fuse_descriptors"):     # (the latter: descriptors by k_descriptors instead of the embedding kernel)
-        eng.set_option(opt, 0)
-        res2 = eng.pipeline_dev(fs, d_frags, d_ci, d_rot, d_pos, n, heavy_idx, 1.5, 0, 0.5, 0, clash, structures, keep2)
-        eng.set_option(opt, 1)
+        with eng.options(**{opt: 0}):
+            res2 = eng.pipeline_dev(fs, d_frags, d_ci, d_rot, d_pos, n, heavy_idx, 1.5, 0, 0.5, 0, clash, structures, keep2)
         assert res2["n_keep"] == res["n_keep"] and torch.equal(keep2[:res["n_pass"]], keep[:res["n_pass"]]), opt
         assert np.abs(structures[:res["n_pass"]].cpu().numpy() - poses[cm]).max() < 1e-12
     # every pose clashes: the side stream's work is joined although no prune follows
@@ -994,8 +948,7 @@ def test_prune_beyond_256_scan_blocks(eng, oracle, lds_blocks):
     passes remove almost everything and the oracle finishes in seconds.  Masks, schedule and evaluation counts equal the
     oracle's, in both modes."""
     heavy = _blocks_of_near_duplicates(3200, 200, 6, seed=77)
-    eng.set_option("open_lds_blocks", lds_blocks)
-    try:
+    with eng.options(open_lds_blocks=lds_blocks):
         for mode in (0, 1):
             if mode not in _BIG_REF:              # (seconds of oracle time per mode: shared by the two parametrisations;
                 # chunk-parallel: the first pass has 20 000 chunks, one parallel region each if rows were spread instead)
@@ -1006,8 +959,6 @@ def test_prune_beyond_256_scan_blocks(eng, oracle, lds_blocks):
             assert [s["k"] for s in stats] == [s["k"] for s in ref["stats"]]
             assert [s["pairs_evaluated"] for s in stats] == [s["pairs_evaluated"] for s in ref["stats"]]
         assert int(mask.sum()) == 3200
-    finally:
-        eng.set_option("open_lds_blocks", 2 ** 30)
 
 
 def test_prune_children_spread_around_the_threshold(eng, oracle, algo):
@@ -1156,9 +1107,8 @@ def test_pairs_inside_the_guard_band(eng, oracle):
                     for algo_opt in (0, 1):
                         if algo_opt == 1 and h > 32:
                             continue
-                        eng.set_option("prune_algo", algo_opt)
-                        mask, _ = eng.prune_heavy(heavy, thr, 0)
-                        eng.set_option("prune_algo", 0)
+                        with eng.options(prune_algo=algo_opt):
+                            mask, _ = eng.prune_heavy(heavy, thr, 0)
                         if dist >= 1e-9:
                             assert np.array_equal(mask, ref), (h, which, delta, ro, mo)
                             n_checked += 1
@@ -1260,10 +1210,9 @@ def test_clash_fp32_band_falls_back_to_fp64(eng, oracle):
     ids = np.array([n_a, n_b], dtype=np.int32)
     ref = oracle.compenetration_mask(poses, ids, 1.5, 0)
     for fp32 in (1, 0):
-        eng.set_option("clash_fp32", fp32)
-        got = eng.clash_mask(poses, ids, 1.5, 0)
+        with eng.options(clash_fp32=fp32):
+            got = eng.clash_mask(poses, ids, 1.5, 0)
         assert np.array_equal(got.astype(bool), ref.astype(bool)), fp32
-    eng.set_option("clash_fp32", 1)
     assert 0 < ref.sum() < len(ref)
 
 
@@ -1281,11 +1230,11 @@ def test_fused_clash_one_pose_per_lane(eng, oracle):
 
     def run(frag_coords, ci, rot, pos, lanes):
         fs = FragmentSet(frag_coords)
-        eng.set_option("clash_lanes", lanes)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         d_mask = torch.zeros(len(ci), dtype=torch.uint8, device=dev)
-        eng.embed_clash_mask_dev(fs, t(fs.flat), t(ci.astype(np.int32)), t(rot), t(pos), len(ci), 1.5, 0, d_mask)
-        eng.synchronize()
+        with eng.options(clash_lanes=lanes):
+            eng.embed_clash_mask_dev(fs, t(fs.flat), t(ci.astype(np.int32)), t(rot), t(pos), len(ci), 1.5, 0, d_mask)
+            eng.synchronize()
         return d_mask.cpu().numpy().astype(bool)
 
     def rotations(n):
@@ -1293,50 +1242,47 @@ def test_fused_clash_one_pose_per_lane(eng, oracle):
         from tscode_amd.synthetic import quat_to_mat
         return quat_to_mat(q)
 
-    try:
-        for n_a, n_b, n_conf, n_poses, offset in ((1, 1, 1, 1, 0.0), (2, 9, 1, 63, 0.0), (8, 7, 3, 65, 0.0), (9, 16, 2, 1000, 0.0), (17, 40, 1, 700, 0.0),
-                                                  (24, 25, 1, 3000, 0.0), (25, 25, 4, 20000, 0.0), (26, 31, 1, 500, 0.0), (32, 33, 2, 1500, 0.0),
-                                                  (33, 33, 1, 300, 0.0), (25, 25, 1, 2000, 1.0e5), (25, 25, 1, 500, 1.0e16)):
-            fa = rng.normal(size=(n_conf, n_a, 3)) * 1.6
-            fb = rng.normal(size=(n_conf, n_b, 3)) * 1.6
-            ci = rng.integers(0, n_conf, size=(n_poses, 2))
-            rot = np.stack([rotations(n_poses), rotations(n_poses)], axis=1)
-            pos = np.stack([np.zeros((n_poses, 3)), rng.normal(size=(n_poses, 3)) * 3.5], axis=1) + offset
-            ref_poses = oracle.transform_batch([fa, fb], ci.astype(np.int32), rot, pos)
-            ref = oracle.compenetration_mask(ref_poses, np.array([n_a, n_b], np.int32), 1.5, 0).astype(bool)
-            for lanes in (1, 0):
-                got = run([fa, fb], ci, rot, pos, lanes)
-                assert np.array_equal(got, ref), (n_a, n_b, n_conf, n_poses, offset, lanes, got.sum(), ref.sum())
-            if offset == 0.0 and n_poses >= 500:
-                assert 0 < ref.sum() < n_poses
-        # inside the band: fragment b placed so that its atom 0 sits 1.5 + eps from atom 3 of a; everything else far away
-        n_a, n_b = 25, 25
-        fa = rng.normal(size=(1, n_a, 3)) * 2.0
-        fb = rng.normal(size=(1, n_b, 3)) * 0.4 + np.array([9.0, 0.0, 0.0])      # a tight clump 9 A from its own atom 0
-        fb[0, 0] = 0.0
-        rot_l, pos_l = [], []
-        for eps in (0.0, 1e-12, -1e-12, 1e-9, -1e-9, 1e-7, -1e-7, 1e-6, -1e-6, 1e-5, -1e-5, 1e-4, -1e-4, 1e-3, -1e-3):
-            for rep in range(9):
-                d = rng.normal(size=3)
-                d /= np.linalg.norm(d)
-                # rotate b so that its clump points AWAY from a (along d), then put its atom 0 at a[3] + d (1.5 + eps)
-                from tscode_amd.algebra import rotation_matrix_from_vectors
-                Rb = rotation_matrix_from_vectors(np.array([1.0, 0.0, 0.0]), d)
-                shift = rng.normal(size=3) * 15.0
-                rot_l.append(np.stack([np.eye(3), Rb]))
-                pos_l.append(np.stack([shift, fa[0, 3] + d * (1.5 + eps) + shift]))
-        rot, pos = np.array(rot_l), np.array(pos_l)
-        ci = np.zeros((len(rot), 2), np.int64)
+    for n_a, n_b, n_conf, n_poses, offset in ((1, 1, 1, 1, 0.0), (2, 9, 1, 63, 0.0), (8, 7, 3, 65, 0.0), (9, 16, 2, 1000, 0.0), (17, 40, 1, 700, 0.0),
+                                              (24, 25, 1, 3000, 0.0), (25, 25, 4, 20000, 0.0), (26, 31, 1, 500, 0.0), (32, 33, 2, 1500, 0.0),
+                                              (33, 33, 1, 300, 0.0), (25, 25, 1, 2000, 1.0e5), (25, 25, 1, 500, 1.0e16)):
+        fa = rng.normal(size=(n_conf, n_a, 3)) * 1.6
+        fb = rng.normal(size=(n_conf, n_b, 3)) * 1.6
+        ci = rng.integers(0, n_conf, size=(n_poses, 2))
+        rot = np.stack([rotations(n_poses), rotations(n_poses)], axis=1)
+        pos = np.stack([np.zeros((n_poses, 3)), rng.normal(size=(n_poses, 3)) * 3.5], axis=1) + offset
         ref_poses = oracle.transform_batch([fa, fb], ci.astype(np.int32), rot, pos)
-        assert oracle.clash_margin(ref_poses, np.array([n_a, n_b], np.int32), 1.5) < 1e-9            # (this set is MEANT to sit on the threshold)
         ref = oracle.compenetration_mask(ref_poses, np.array([n_a, n_b], np.int32), 1.5, 0).astype(bool)
         for lanes in (1, 0):
             got = run([fa, fb], ci, rot, pos, lanes)
-            # eps = 0 and +-1e-12 are decided by the last bits of the embedding (FMA contraction differs between compilers): compare from 1e-9 on
-            assert np.array_equal(got[27:], ref[27:]), lanes
-        assert 0 < ref[27:].sum() < len(ref) - 27
-    finally:
-        eng.set_option("clash_lanes", 1)
+            assert np.array_equal(got, ref), (n_a, n_b, n_conf, n_poses, offset, lanes, got.sum(), ref.sum())
+        if offset == 0.0 and n_poses >= 500:
+            assert 0 < ref.sum() < n_poses
+    # inside the band: fragment b placed so that its atom 0 sits 1.5 + eps from atom 3 of a; everything else far away
+    n_a, n_b = 25, 25
+    fa = rng.normal(size=(1, n_a, 3)) * 2.0
+    fb = rng.normal(size=(1, n_b, 3)) * 0.4 + np.array([9.0, 0.0, 0.0])      # a tight clump 9 A from its own atom 0
+    fb[0, 0] = 0.0
+    rot_l, pos_l = [], []
+    for eps in (0.0, 1e-12, -1e-12, 1e-9, -1e-9, 1e-7, -1e-7, 1e-6, -1e-6, 1e-5, -1e-5, 1e-4, -1e-4, 1e-3, -1e-3):
+        for rep in range(9):
+            d = rng.normal(size=3)
+            d /= np.linalg.norm(d)
+            # rotate b so that its clump points AWAY from a (along d), then put its atom 0 at a[3] + d (1.5 + eps)
+            from tscode_amd.algebra import rotation_matrix_from_vectors
+            Rb = rotation_matrix_from_vectors(np.array([1.0, 0.0, 0.0]), d)
+            shift = rng.normal(size=3) * 15.0
+            rot_l.append(np.stack([np.eye(3), Rb]))
+            pos_l.append(np.stack([shift, fa[0, 3] + d * (1.5 + eps) + shift]))
+    rot, pos = np.array(rot_l), np.array(pos_l)
+    ci = np.zeros((len(rot), 2), np.int64)
+    ref_poses = oracle.transform_batch([fa, fb], ci.astype(np.int32), rot, pos)
+    assert oracle.clash_margin(ref_poses, np.array([n_a, n_b], np.int32), 1.5) < 1e-9            # (this set is MEANT to sit on the threshold)
+    ref = oracle.compenetration_mask(ref_poses, np.array([n_a, n_b], np.int32), 1.5, 0).astype(bool)
+    for lanes in (1, 0):
+        got = run([fa, fb], ci, rot, pos, lanes)
+        # eps = 0 and +-1e-12 are decided by the last bits of the embedding (FMA contraction differs between compilers): compare from 1e-9 on
+        assert np.array_equal(got[27:], ref[27:]), lanes
+    assert 0 < ref[27:].sum() < len(ref) - 27
 
 
 # ----------------------------------------------------------------------------- N3: csearch rotations

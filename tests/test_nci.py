@@ -672,25 +672,22 @@ def test_kernel_time_is_taken_only_under_pass_timing_and_per_thread():
         t.join()
         return got[0]
 
-    eng.set_option("pass_timing", 0)
-    want = host()
-    assert eng.nci_kernel_ms() == -1.0
-    device()
-    assert eng.nci_kernel_ms() == -1.0
-    eng.set_option("pass_timing", 1)
-    try:
-        timed = host()
-        assert math.isfinite(eng.nci_kernel_ms()) and eng.nci_kernel_ms() > 0.0
-        assert (timed["counts"] == want["counts"]).all()
-        assert in_a_fresh_thread() == -1.0
-        device()
-        assert math.isfinite(eng.nci_kernel_ms()) and eng.nci_kernel_ms() > 0.0
-        assert (counts.cpu().numpy() == want["counts"]).all()
-        host(0)
+    with eng.options(pass_timing=0):
+        want = host()
         assert eng.nci_kernel_ms() == -1.0
+        device()
+        assert eng.nci_kernel_ms() == -1.0
+        with eng.options(pass_timing=1):
+            timed = host()
+            assert math.isfinite(eng.nci_kernel_ms()) and eng.nci_kernel_ms() > 0.0
+            assert (timed["counts"] == want["counts"]).all()
+            assert in_a_fresh_thread() == -1.0
+            device()
+            assert math.isfinite(eng.nci_kernel_ms()) and eng.nci_kernel_ms() > 0.0
+            assert (counts.cpu().numpy() == want["counts"]).all()
+            host(0)
+            assert eng.nci_kernel_ms() == -1.0
+            host()
+            assert eng.nci_kernel_ms() > 0.0
         host()
-        assert eng.nci_kernel_ms() > 0.0
-    finally:
-        eng.set_option("pass_timing", 0)
-    host()
-    assert eng.nci_kernel_ms() == -1.0
+        assert eng.nci_kernel_ms() == -1.0

@@ -900,25 +900,22 @@ def test_kernel_time_is_taken_only_under_pass_timing_and_per_thread():
         t.join()
         return got[0]
 
-    eng.set_option("pass_timing", 0)
-    want = host()
-    assert eng.orbitals_kernel_ms() == -1.0
-    device()
-    assert eng.orbitals_kernel_ms() == -1.0
-    eng.set_option("pass_timing", 1)
-    try:
-        timed = host()
-        assert math.isfinite(eng.orbitals_kernel_ms()) and eng.orbitals_kernel_ms() > 0.0
-        assert timed["centers"].tobytes() == want["centers"].tobytes()
-        assert in_a_fresh_thread() == -1.0
-        device()
-        assert math.isfinite(eng.orbitals_kernel_ms()) and eng.orbitals_kernel_ms() > 0.0
-        assert out["centers"].cpu().numpy().tobytes() == want["centers"].tobytes()
-        host(0)
+    with eng.options(pass_timing=0):
+        want = host()
         assert eng.orbitals_kernel_ms() == -1.0
+        device()
+        assert eng.orbitals_kernel_ms() == -1.0
+        with eng.options(pass_timing=1):
+            timed = host()
+            assert math.isfinite(eng.orbitals_kernel_ms()) and eng.orbitals_kernel_ms() > 0.0
+            assert timed["centers"].tobytes() == want["centers"].tobytes()
+            assert in_a_fresh_thread() == -1.0
+            device()
+            assert math.isfinite(eng.orbitals_kernel_ms()) and eng.orbitals_kernel_ms() > 0.0
+            assert out["centers"].cpu().numpy().tobytes() == want["centers"].tobytes()
+            host(0)
+            assert eng.orbitals_kernel_ms() == -1.0
+            host()
+            assert eng.orbitals_kernel_ms() > 0.0
         host()
-        assert eng.orbitals_kernel_ms() > 0.0
-    finally:
-        eng.set_option("pass_timing", 0)
-    host()
-    assert eng.orbitals_kernel_ms() == -1.0
+        assert eng.orbitals_kernel_ms() == -1.0

@@ -137,9 +137,8 @@ def test_reference_runs_in_one_call_under_every_routing(eng):
     assert sorted(len(s) for s in structures) == [40, 600, 600, 720, 1003, 2500]
     default = eng.prune_batch_max_n
     results = []
-    try:
-        for max_n in (default, 4096, 64):
-            eng.set_option("prune_batch_max_n", max_n)
+    for max_n in (default, 4096, 64):
+        with eng.options(prune_batch_max_n=max_n):
             out = tscode_amd.prune_conformers_rmsd_batch(structures, atomnos, thrs)
             stats = tscode_amd.last_prune_batch_stats()
             for c in cases:
@@ -149,8 +148,6 @@ def test_reference_runs_in_one_call_under_every_routing(eng):
                 assert [p["n_active_after"] for p in stats[c]] == g[f"pass_masks{c}"].sum(axis=1).tolist(), (max_n, c)
                 assert np.cumsum([p["new_keys"] for p in stats[c]]).tolist() == g[f"pass_nkeys{c}"].tolist(), (max_n, c)
             results.append(([m for _, m in out], stats))
-    finally:
-        eng.set_option("prune_batch_max_n", default)
     for masks, stats in results[1:]:
         assert all(np.array_equal(a, b) for a, b in zip(masks, results[0][0]))
         assert stats == results[0][1]
@@ -292,10 +289,7 @@ def test_device_array_form_equals_the_host_form(eng, mode):
     # a segment beyond the option is refused, with nothing written
     from tscode_amd._lib import TscodeHipError
     default = eng.prune_batch_max_n
-    try:
-        eng.set_option("prune_batch_max_n", 512)
+    with eng.options(prune_batch_max_n=512):
         with pytest.raises(TscodeHipError, match="prune_batch_max_n"):
             eng.prune_heavy_batch_dev(d_heavy, offsets, n, h, thrs, mode, d_mask)
-    finally:
-        eng.set_option("prune_batch_max_n", default)
     assert eng.prune_batch_max_n == default

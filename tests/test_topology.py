@@ -520,25 +520,22 @@ def test_kernel_time_is_taken_only_under_pass_timing_and_per_thread():
     _, structures, atomnos, _ = make_chain_ensemble(3, 5, 7100)
     classes, thr = bond_tables(atomnos)
     eng = engine()
-    eng.set_option("pass_timing", 0)
-    eng.bond_delta(structures, classes, thr)
-    assert eng.topology_kernel_ms() == -1.0
-    run_dev(eng, structures, classes, thr, None, None, None, 0, False)
-    assert eng.topology_kernel_ms() == -1.0
-    eng.set_option("pass_timing", 1)
-    try:
+    with eng.options(pass_timing=0):
         eng.bond_delta(structures, classes, thr)
-        host_ms = eng.topology_kernel_ms()
-        assert math.isfinite(host_ms) and host_ms > 0.0
-        assert read_from_a_fresh_thread(eng.topology_kernel_ms) == -1.0
-        run_dev(eng, structures, classes, thr, None, None, None, 0, False)
-        dev_ms = eng.topology_kernel_ms()
-        assert math.isfinite(dev_ms) and dev_ms > 0.0
-        eng.bond_delta(structures[:0], classes, thr)
         assert eng.topology_kernel_ms() == -1.0
+        run_dev(eng, structures, classes, thr, None, None, None, 0, False)
+        assert eng.topology_kernel_ms() == -1.0
+        with eng.options(pass_timing=1):
+            eng.bond_delta(structures, classes, thr)
+            host_ms = eng.topology_kernel_ms()
+            assert math.isfinite(host_ms) and host_ms > 0.0
+            assert read_from_a_fresh_thread(eng.topology_kernel_ms) == -1.0
+            run_dev(eng, structures, classes, thr, None, None, None, 0, False)
+            dev_ms = eng.topology_kernel_ms()
+            assert math.isfinite(dev_ms) and dev_ms > 0.0
+            eng.bond_delta(structures[:0], classes, thr)
+            assert eng.topology_kernel_ms() == -1.0
+            eng.bond_delta(structures, classes, thr)
+            assert eng.topology_kernel_ms() > 0.0
         eng.bond_delta(structures, classes, thr)
-        assert eng.topology_kernel_ms() > 0.0
-    finally:
-        eng.set_option("pass_timing", 0)
-    eng.bond_delta(structures, classes, thr)
-    assert eng.topology_kernel_ms() == -1.0
+        assert eng.topology_kernel_ms() == -1.0

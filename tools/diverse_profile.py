@@ -79,9 +79,8 @@ def main():
         D, k = 3 * n, 100
         rows = np.random.default_rng(2020).choice(N, k, replace=False).astype(np.int32)
         tscode_amd.diverse_select(s, k, init_rows=rows)                       # warm-up: allocations, code objects
-        eng.set_option("pass_timing", 1)
         best = None
-        try:
+        with eng.options(pass_timing=1):
             for _ in range(args.reps):
                 t = time.perf_counter()
                 aligned, labels, picked, _, n_iter = tscode_amd.diverse_select(s, k, init_rows=rows)
@@ -90,8 +89,6 @@ def main():
                 _lib.check(eng.lib.tsc_diverse_timings(eng._h, ms))
                 got = dict(align_ms=ms[0], assign_ms=ms[1], update_ms=ms[2], select_device_ms=ms[3], select_wall_ms=1e3 * wall)
                 best = got if best is None else {f: min(best[f], got[f]) for f in got}
-        finally:
-            eng.set_option("pass_timing", 0)
         t = time.perf_counter()
         tscode_amd.diverse_select(s, k, init_rows=rows)
         untimed_wall = time.perf_counter() - t

@@ -76,22 +76,21 @@ def main():
         torch.cuda.synchronize()
         row = {"n_structs": N, "n_atoms": n, "molecules": [int(v) for v in ids],
                "candidates_per_molecule": [int(cand[atom_mol == m].sum()) for m in range(len(ids))]}
-        eng.set_option("pass_timing", 1)
-        for name, kw in (("counts_only", {}), ("every_list", lists)):
+        with eng.options(pass_timing=1):
+            for name, kw in (("counts_only", {}), ("every_list", lists)):
+                times = []
+                for it in range(args.warmup + args.repeats):
+                    eng.nci_dev(coords, N, n, classes, thr, atom_mol, len(ids), cand, ring_thr, NCI_DICT["PhPh"][0], None, False, rule, counts, overflow, **kw)
+                    if it >= args.warmup:
+                        times.append(eng.nci_kernel_ms())
+                row[name + "_ms"] = float(np.median(times))
+                row[name + "_ms_min_max"] = [float(min(times)), float(max(times))]
+            b_classes, b_thr = bond_tables(atomnos)
             times = []
             for it in range(args.warmup + args.repeats):
-                eng.nci_dev(coords, N, n, classes, thr, atom_mol, len(ids), cand, ring_thr, NCI_DICT["PhPh"][0], None, False, rule, counts, overflow, **kw)
+                eng.bond_delta_dev(coords, N, n, b_classes, b_thr, None, None, None, False, 0, mask)
                 if it >= args.warmup:
-                    times.append(eng.nci_kernel_ms())
-            row[name + "_ms"] = float(np.median(times))
-            row[name + "_ms_min_max"] = [float(min(times)), float(max(times))]
-        b_classes, b_thr = bond_tables(atomnos)
-        times = []
-        for it in range(args.warmup + args.repeats):
-            eng.bond_delta_dev(coords, N, n, b_classes, b_thr, None, None, None, False, 0, mask)
-            if it >= args.warmup:
-                times.append(eng.topology_kernel_ms())
-        eng.set_option("pass_timing", 0)
+                    times.append(eng.topology_kernel_ms())
         row["bond_delta_ms"] = float(np.median(times))
         row["ratio_to_bond_delta"] = row["counts_only_ms"] / row["bond_delta_ms"]
         row["structures_per_s"] = N / (row["counts_only_ms"] * 1e-3)

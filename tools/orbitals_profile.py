@@ -71,13 +71,12 @@ def main():
                torch.zeros((C, 16, 3), dtype=torch.float64, device=dev), torch.zeros((C, 16, 2), dtype=torch.int8, device=dev),
                torch.zeros(C, dtype=torch.uint8, device=dev)]
         torch.cuda.synchronize()
-        eng.set_option("pass_timing", 1)
-        times = []
-        for it in range(args.warmup + args.repeats):
-            eng.orbitals_dev(coords, C, n, rec, mode, False, *out)
-            if it >= args.warmup:
-                times.append(eng.orbitals_kernel_ms())
-        eng.set_option("pass_timing", 0)
+        with eng.options(pass_timing=1):
+            times = []
+            for it in range(args.warmup + args.repeats):
+                eng.orbitals_dev(coords, C, n, rec, mode, False, *out)
+                if it >= args.warmup:
+                    times.append(eng.orbitals_kernel_ms())
         eng.synchronize()
         kernel_ms = float(np.median(times))
         x_host = coords.cpu().numpy()

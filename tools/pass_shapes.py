@@ -22,10 +22,6 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-DEFAULTS = {"cull": 1, "cull_min_pairs": 2.0e9, "sieve_mm": 1, "sieve_mm16": 1, "prune_algo": 0, "local_pass": 1, "cull_tile_block": 256,
-            "deterministic_basis": 0}
-
-
 def dispatches(out_dir):
     files = glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True)
     if len(files) != 1:
@@ -75,13 +71,8 @@ def main():
         print(f"{name}: {int(mask.sum())} kept, digest {hashlib.sha256(np.packbits(mask.astype(bool)).tobytes()).hexdigest()[:16]}", flush=True)
 
     def with_options(opts, f):
-        try:
-            for k, v in opts.items():
-                eng.set_option(k, v)
+        with eng.options(**opts):
             return f()
-        finally:
-            for k in opts:
-                eng.set_option(k, DEFAULTS[k])
 
     def mask_of(st, n):
         keep = torch.empty(n, dtype=torch.uint8, device=dev)

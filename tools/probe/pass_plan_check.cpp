@@ -1,7 +1,7 @@
 // pass_plan_check.cpp -- the sizing functions of csrc/pass_plan.hpp (which shape a prune pass takes, every grid of each shape) run by a
 // stand-alone program at shapes worked out by hand from the formulas, so that they can be checked without a GPU and built with
 // AddressSanitizer and UndefinedBehaviorSanitizer.  Not part of the library; tools/pass_plan_check.py builds and runs it.  No HIP runtime
-// call is made (a default-constructed tsc_ctx is a bag of options).  Grids marked [trace] were also seen in a kernel trace of
+// call is made (the functions take the options, a plain struct).  Grids marked [trace] were also seen in a kernel trace of
 // tools/pass_shapes.py (MEASURED.md 17).
 //
 //   pass_plan_check        (exit status 0 and a line "pass_plan_check: N checks passed", or the first failed check and status 1)
@@ -24,7 +24,7 @@ static bool is_grid(dim3 g, unsigned x, unsigned y) { return g.x == x && g.y == 
 static const PairForm PACKED{false, false}, MM16{false, true}, MM64{true, false};
 
 static int forms() {
-    tsc_ctx c;
+    tsc_options c;
     // a sieve run with float16 records: the 64-row kernels where the run chose them, else the 16-row form -- which exists for the default
     // screen (sieve_cpl 2, trimmed) only; no records, or the register-tiled kernel: neither
     CHECK(pair_form(c, ALGO_SIEVE, true, true).mm && !pair_form(c, ALGO_SIEVE, true, true).mm16);
@@ -38,7 +38,7 @@ static int forms() {
 }
 
 static int walked() {
-    tsc_ctx c;   // default options
+    tsc_options c;   // default options
     {   // 57 046 structures in 5 chunks: 57 046 / 5 = 11 409, the last chunk 57 046 - 4 x 11 409 = 11 410; ceil(57 046 / 16) = 3 566 row tiles;
         // n <= 100 000: 512 columns, and 11 410 >= 4 x 512 keeps them; ceil((11 410 + 64) / 512) = ceil(22.4) = 23 <= 64 segments: two items
         // per workgroup, 3 566 / 2 = 1 783
@@ -77,7 +77,7 @@ static int walked() {
         // 2 048 rows: ceil(2 112 / 1 024) = 3 segments, 32 groups again
         const WalkedPlan b = plan_walked(c, 2048, 1, 0, 1, 2048, -1, MM64);
         CHECK(b.seg_cols == 1024 && b.n_seg == 3 && is_grid(b.grid, 8, 3));
-        tsc_ctx o;
+        tsc_options o;
         o.mm_seg_cols = 2048, o.seg_cols = 128;   // the options override: "mm_seg_cols" the 64-row form, "seg_cols" the others (no halving below 256)
         CHECK(plan_walked(o, 2048, 1, 0, 1, 2048, -1, MM64).seg_cols == 2048 && plan_walked(o, 2048, 1, 0, 1, 2048, -1, MM16).seg_cols == 128);
     }
@@ -109,7 +109,7 @@ static int walked() {
 }
 
 static int chunk_local() {
-    tsc_ctx c;
+    tsc_options c;
     auto shape = [&](int64_t n, int64_t k, const PassRows &r, bool range) { return pass_shape(c, n, k, ALGO_SIEVE, true, false, false, 1, range, r); };
     {   // 9 000 in 200 chunks of 45 (the last: 9 000 - 199 x 45 = 45): three row tiles a chunk, one block of LP_TILES_PER_BLOCK = 4: 200 blocks  [trace]
         const LocalPlan l = plan_local(9000, 200, whole_pass(9000, 200));
@@ -125,7 +125,7 @@ static int chunk_local() {
         CHECK(!shape(9000, 20, whole_pass(9000, 20), false).local);
         CHECK(!pass_shape(c, 9000, 200, ALGO_SIEVE, true, false, false, 2, false, whole_pass(9000, 200)).local);
         CHECK(!pass_shape(c, 9000, 200, ALGO_TILE, false, false, false, 1, false, whole_pass(9000, 200)).local);
-        tsc_ctx off;
+        tsc_options off;
         off.local_pass = 0;
         CHECK(!pass_shape(off, 9000, 200, ALGO_SIEVE, true, false, false, 1, false, whole_pass(9000, 200)).local);
     }
@@ -154,7 +154,7 @@ static int chunk_local() {
 }
 
 static int culled() {
-    tsc_ctx c;
+    tsc_options c;
     c.cull = 2, c.cull_min_pairs = 5e6;
     {   // 9 000 in 5 chunks of 1 800: 9 000 x 1 800 / 2 = 8.1e6 pairs >= 5e6: a candidate; in 10 chunks 4.05e6: not
         CHECK(pass_shape(c, 9000, 5, ALGO_SIEVE, true, false, false, 1, false, whole_pass(9000, 5)).culled);
@@ -223,7 +223,7 @@ static int culled() {
 }
 
 static int decisions() {
-    tsc_ctx c;
+    tsc_options c;
     c.cull = 2, c.cull_min_pairs = 5e6;
     auto shape = [&](int64_t k, int algo, bool records, bool mm64, int world, bool range) {
         return pass_shape(c, 9000, k, algo, records, mm64, false, world, range, whole_pass(9000, k));

@@ -76,18 +76,14 @@ def main():
     for count, n in ((2000, 300), (200, 2000)):
         count = max(1, count // args.shrink)
         structures, atomnos = ensembles_of(count, n, SEED)
-        eng.set_option("prune_batch_max_n", max(default_max_n, n))      # (the kernel takes every ensemble of the workload)
-        try:
+        with eng.options(prune_batch_max_n=max(default_max_n, n)):      # (the kernel takes every ensemble of the workload)
             t_batch, t_loop, kept = both_routes(structures, atomnos, args.repeats)
-        finally:
-            eng.set_option("prune_batch_max_n", default_max_n)
         row = {"workload": f"{count}x{n}x50", "ensembles": count, "structures_per_ensemble": n, "atoms": 50, "heavy_atoms": int((atomnos != 1).sum()),
                "structures_kept": kept, "ms_batch_call": t_batch, "ms_loop_of_single_calls": t_loop, "loop_over_batch": t_loop["median"] / t_batch["median"]}
         rows.append(row)
         print(json.dumps(row), flush=True)
     single = []
-    eng.set_option("prune_batch_max_n", 8192)
-    try:
+    with eng.options(prune_batch_max_n=8192):
         for n in (256, 512, 1024, 2048, 4096, 8192):
             structures, atomnos = ensembles_of(1, n, SEED + 5000)
             t_batch, t_loop, kept = both_routes(structures, atomnos, args.repeats)
@@ -95,8 +91,6 @@ def main():
                    "single_over_batch": t_loop["median"] / t_batch["median"]}
             single.append(row)
             print(json.dumps(row), flush=True)
-    finally:
-        eng.set_option("prune_batch_max_n", default_max_n)
     import torch
     out = {"tool": "tools/prune_batch_profile.py", "device": torch.cuda.get_device_name(eng.device), "build_digest": eng.lib.tsc_build_digest().decode(),
            "sources_digest": build.csrc_digest(), "repeats": args.repeats, "threshold": THR, "mode": 0, "prune_batch_max_n_default": default_max_n,

@@ -59,16 +59,15 @@ def main():
         broken = torch.zeros(N, dtype=torch.int32, device=dev)
         torch.cuda.synchronize()
         row = {"n_structs": N, "n_atoms": n}
-        eng.set_option("pass_timing", 1)
-        for name, kw in (("verdict_only", {}), ("with_counts", {"formed": formed, "broken": broken})):
-            times = []
-            for it in range(args.warmup + args.repeats):
-                eng.bond_delta_dev(coords, N, n, classes, thr, None, ref, None, False, 0, mask, **kw)
-                if it >= args.warmup:
-                    times.append(eng.topology_kernel_ms())
-            row[name + "_ms"] = float(np.median(times))
-            row[name + "_ms_min_max"] = [float(min(times)), float(max(times))]
-        eng.set_option("pass_timing", 0)
+        with eng.options(pass_timing=1):
+            for name, kw in (("verdict_only", {}), ("with_counts", {"formed": formed, "broken": broken})):
+                times = []
+                for it in range(args.warmup + args.repeats):
+                    eng.bond_delta_dev(coords, N, n, classes, thr, None, ref, None, False, 0, mask, **kw)
+                    if it >= args.warmup:
+                        times.append(eng.topology_kernel_ms())
+                row[name + "_ms"] = float(np.median(times))
+                row[name + "_ms_min_max"] = [float(min(times)), float(max(times))]
         row["unchanged_share"] = float(mask.float().mean().item())
         times = []
         for it in range(args.warmup + args.repeats):

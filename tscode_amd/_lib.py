@@ -71,6 +71,7 @@ _SIGNATURES = {
     "tsc_ctx_synchronize": (C.c_int, [_vp]),
     "tsc_ctx_set_option": (C.c_int, [_vp, C.c_char_p, C.c_double]),
     "tsc_ctx_get_option": (C.c_int, [_vp, C.c_char_p, c_f64p]),
+    "tsc_option_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), c_f64p]),
     "tsc_malloc": (C.c_int, [_vp, C.c_size_t, C.POINTER(_vp)]),
     "tsc_free": (C.c_int, [_vp, _vp]),
     "tsc_memcpy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),

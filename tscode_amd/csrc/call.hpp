@@ -90,7 +90,7 @@ struct StageTimer {
     tsc_ctx *c;
     bool on;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    explicit StageTimer(tsc_ctx *ctx) : c(ctx), on(ctx->pass_timing >= 1) {
+    explicit StageTimer(tsc_ctx *ctx) : c(ctx), on(ctx->opt.pass_timing >= 1) {
         if (on && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)) on = false;
     }
     StageTimer(const StageTimer &) = delete;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/tscode_hip.h"
+#include "options.hpp"
 
 namespace tsc {
 
@@ -72,9 +73,6 @@ __host__ __device__ inline T ceil_div(T a, T b) {
 
 }  // namespace tsc
 
-struct tsc_ctx;
-static inline bool want_heavy32(const tsc_ctx *c, double heavy_bytes);
-
 // One per (process, device).  All work is enqueued on `stream`; scratch blocks are recycled in
 // stream order, so a block handed back by one call can be reused by the next without a sync.
 struct tsc_ctx {
@@ -90,44 +88,10 @@ struct tsc_ctx {
     std::map<void *, size_t> live;        // blocks handed out
     void *pinned = nullptr;               // small pinned host buffer for scalar read-backs
     size_t pinned_bytes = 0;
-    int prune_algo = 0;                   // tsc_ctx_set_option("prune_algo"): 0 auto, 1 register-tiled, 2 sieve
-    int seg_cols = 0;                     // columns per pair-kernel work item (0 = chosen from the problem size)
-    int drain_min = 32;                   // sieve: queued pairs that trigger an evaluation batch between column tiles (swept 16..64 after the row
-                                          // loop was trimmed: 32 is 1.3 % ahead of 64 at 1M structures, level elsewhere)
-    int sieve_trim = 1;                   // pair kernel: the screen with fewer vector instructions per (row, tile) (norms folded into the fma chain, per-family compares)
-    int sieve_mm = 1;                     // pair kernels of a one-rank run with the screen on the matrix cores, 64 rows per work item (mm.hpp, cull_mm.hpp): 0 never (the
-                                          // packed-fp32 screen of sieve.hpp / cull.hpp), 1 for runs of at least mm_min_n structures, 2 always
-    int64_t mm_min_n = 100000;            // (measured: at 57 000 structures a pass is a few thousand work items and bound by their chains of memory round trips, which
-                                          // the longer 64-row items lengthen -- C3 0.80 - 0.89 ms against 0.79; at 483 000 the passes are bound by issue: C4 9.05 -> 7.8 ms)
-    int sieve_mm16 = 1;                   // runs below mm_min_n: the walked passes' pair kernel with the matrix-core screen on 16-row items (mm.hpp: k_rmsd_sieve_mm16); 0: the packed-fp32 kernel
-    int mm_seg_cols = 0;                  // ... columns per work item of the walked passes' kernel (0: 1024 where rows' ranges reach 2048 columns, else 512)
-    int sieve_cpl = 2;                    // columns per lane of the pair kernel's screen: 2 = 128-column tiles at 5 waves/SIMD (default), 4 = 256-column tiles at 4, 1 = 64-column tiles at 6
-    int64_t pca_min_n = 6000;             // below this many structures the descriptors use the identity basis (no principal-axis estimate)
-    int fuse_descriptors = 1;             // ... and the descriptors by the kernel that embeds the passing poses (needs early_basis)
-    int early_basis = 1;                  // tsc_pipeline_dev: descriptor basis from a sample of unfiltered poses, on its own stream
-    int clash_first = 0;                  // ... whose chain is enqueued in front of the clash launch (0) or behind it (1: rounds 1 - 3)
-    int cull_tile_block = 256;             // culled passes dealt by row tiles: consecutive tiles of the sorted layout per rank and turn
-    int stage1_f32 = 1;                   // stage 1 of the pair kernels reads a float32 copy of the coordinates first (sieve.hpp: pair_stage1): 0 never, 2 always,
-                                          // 1: from 128 MB of heavy atoms on -- and from 8 MB on where the matrix-core kernels run (want_heavy32 below)
-    int local_max_chunk = 384;            // longest chunk (structures) of a pass that the chunk-local kernel takes
-    int local_pass = 1;                   // passes with short chunks run in one launch (local_pass.hpp)
+    tsc_options opt;                      // the tunables (options.hpp)
     void *dbg_buf = nullptr;              // -DTSC_DBG_STAMPS builds: time stamps of the pair kernel's wavefronts
     size_t dbg_bytes = 0;
-    int64_t dbg_waves = 0, dbg_stamp_k = -1;
-    int fused_apply = 1;                  // single-rank sieve passes: the pair kernel applies the verdicts tile by tile and closes the pass (sieve.hpp)
-    int open_lds_blocks = 1 << 30;        // k_open_rows stages the scan-block prefix in LDS up to this many blocks (tests lower it to take the other path)
-    int clash_fp32 = 1;                   // clash verdicts (max_clashes = 0, no counts): packed-fp32 minimum with fp64 fallback
-    int clash_lanes = 1;                  // ... of two fragments, the smaller of at most 32 atoms, fused with the embed: one pose per lane (k_clash_lanes)
-    int deterministic_basis = 0;          // the descriptor basis from fixed-order sums (sieve.hpp, k_feature_moments): a sharded run sets it -- its ranks
-                                          // must derive bit-identical descriptors (the culled passes deal the tiles of a layout sorted by them)
-    int cull = 1;                         // large passes of the sieve lay their structures out along a Morton curve and skip tile pairs by bounding box (cull.hpp)
-    double cull_min_pairs = 2.0e9;        // ... passes of at least this many pairs (n * (n / k) / 2)
-    int64_t cull_grid = 1 << 30;          // workgroups of the culled pair kernel at most (each walks work items with that stride)
-    int cull_xcd = 1;                     // 1 (default): the culled pair kernel keys runs of 32 row groups to XCDs (workgroup b runs on XCD b % 8): the workgroups an
-                                          // XCD has in flight share their column windows in its L2 (cull.hpp; an experiment of round 5)
-    int prune_batch_max_n = 2048;         // tsc_prune_rmsd_batch: structures per segment at most (prune_batch.hpp: one workgroup owns a segment); provisional,
-                                          // LP_MAX_ROWS -- the size up to which one workgroup already owns a chunk -- until the crossover is measured
-    int pass_timing = 0;                  // HIP events per pass: 0 none, 1 on the pair kernel's dispatch, 2 also around the whole pass
+    int64_t dbg_waves = 0;
     // basis estimated by tsc_embed_clash_compact_dev beside its clash kernel, for the tsc_prune_create that follows (consumed once)
     double *eb_block = nullptr;           // [sample coordinates | moment accumulators | basis]
     int eb_h = 0, eb_samples = 0;
@@ -197,16 +161,6 @@ struct tsc_ctx {
         cache.clear();
     }
 };
-
-// Does a run over `heavy_bytes` of heavy atoms (n * h * 24) keep the float32 copy that stage 1 of the pair kernels reads?  It pays where the
-// candidates' gathers come from HBM (128 MB and more: C4 12.1 -> 10.6 ms in round 4) and where the pair kernel is a chain of round trips rather
-// than VALU issue -- the matrix-core kernels: half the bytes and half the trips per evaluation batch (C3: 0.745 -> 0.704 ms); the packed-fp32
-// kernel at C3's size lost 2 % to the conversions.
-static inline bool want_heavy32(const tsc_ctx *c, double heavy_bytes) {
-    if (c->stage1_f32 != 1) return c->stage1_f32 == 2;
-    return heavy_bytes >= 128e6 || (heavy_bytes >= 8e6 && (c->sieve_mm != 0 || c->sieve_mm16 != 0));
-}
-
 
 namespace tsc {
 

@@ -199,166 +199,24 @@ extern "C" __attribute__((visibility("default"))) int tsc_debug_stamps(tsc_ctx *
 }
 #endif
 
-// Tunables: "prune_algo" 0 / 2 = descriptor sieve (any size), 1 = register-tiled all-pairs kernel (h <= 32);
-// "seg_cols" = columns per work item.
+// Tunables: the table of options.hpp holds each option's name, member and rule; the defaults are the initialisers of tsc_options.
 extern "C" __attribute__((visibility("default"))) int tsc_ctx_set_option(tsc_ctx *c, const char *name, double value) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(c && name, "null argument");
-    if (strcmp(name, "prune_algo") == 0) {
-        TSC_REQUIRE(value == 0 || value == 1 || value == 2, "prune_algo must be 0, 1 or 2");
-        c->prune_algo = int(value);
-        return 0;
-    }
-    if (strcmp(name, "drain_min") == 0) {
-        TSC_REQUIRE(value >= 1 && value <= 64, "drain_min must be in [1, 64]");
-        c->drain_min = int(value);
-        return 0;
-    }
-    if (strcmp(name, "pass_timing") == 0) {
-        TSC_REQUIRE(value == 0 || value == 1 || value == 2, "pass_timing must be 0, 1 or 2");
-        c->pass_timing = int(value);
-        return 0;
-    }
-    if (strcmp(name, "sieve_trim") == 0) {
-        TSC_REQUIRE(value == 0 || value == 1, "sieve_trim must be 0 or 1");
-        c->sieve_trim = int(value);
-        return 0;
-    }
-    if (strcmp(name, "sieve_mm") == 0) {
-        TSC_REQUIRE(value == 0 || value == 1 || value == 2, "sieve_mm must be 0 (never), 1 (large runs) or 2 (always)");
-        c->sieve_mm = int(value);
-        return 0;
-    }
-    if (strcmp(name, "sieve_mm16") == 0) {
-        TSC_REQUIRE(value == 0 || value == 1, "sieve_mm16 must be 0 or 1");
-        c->sieve_mm16 = int(value);
-        return 0;
-    }
-    if (strcmp(name, "mm_min_n") == 0) {
-        TSC_REQUIRE(value >= 0 && value <= 4e9, "mm_min_n must be in [0, 4e9]");
-        c->mm_min_n = int64_t(value);
-        return 0;
-    }
-    if (strcmp(name, "mm_seg_cols") == 0) {
-        TSC_REQUIRE(value == 0 || (value >= 64 && value <= 1024 && int(value) % 64 == 0), "mm_seg_cols must be 0 (automatic) or a multiple of 64 in [64, 1024]");
-        c->mm_seg_cols = int(value);
-        return 0;
-    }
-    if (strcmp(name, "sieve_cpl") == 0) {
-        TSC_REQUIRE(value == 1 || value == 2 || value == 4, "sieve_cpl must be 1, 2 or 4");
-        c->sieve_cpl = int(value);
-        return 0;
-    }
-    if (strcmp(name, "fuse_descriptors") == 0) {
-        TSC_REQUIRE(value == 0 || value == 1, "fuse_descriptors must be 0 or 1");
-        c->fuse_descriptors = int(value);
-        return 0;
-    }
-    if (strcmp(name, "pca_min_n") == 0) {
-        TSC_REQUIRE(value >= 0 && value <= 1e9, "pca_min_n must be in [0, 1e9]");
-        c->pca_min_n = int64_t(value);
-        return 0;
-    }
-    if (strcmp(name, "early_basis") == 0) {
-        TSC_REQUIRE(value == 0 || value == 1, "early_basis must be 0 or 1");
-        c->early_basis = int(value);
-        return 0;
-    }
-    if (strcmp(name, "local_max_chunk") == 0) {
-        TSC_REQUIRE(value >= 16 && value <= LP_MAX_ROWS, "local_max_chunk must be in [16, %d]", LP_MAX_ROWS);
-        c->local_max_chunk = int(value);
-        return 0;
-    }
-#ifdef TSC_DBG_STAMPS
-    if (strcmp(name, "dbg_stamp_k") == 0) {
-        c->dbg_stamp_k = int64_t(value);
-        return 0;
-    }
-#endif
-    if (strcmp(name, "cull") == 0) {
-        TSC_REQUIRE(value == 0.0 || value == 1.0 || value == 2.0, "cull must be 0 (off), 1 (the device decides per pass) or 2 (every candidate pass is culled)");
-        c->cull = int(value);
-        return 0;
-    }
-    if (strcmp(name, "deterministic_basis") == 0) {
-        c->deterministic_basis = value != 0.0 ? 1 : 0;
-        return 0;
-    }
-    if (strcmp(name, "cull_grid") == 0) {
-        TSC_REQUIRE(value >= 1.0, "cull_grid must be positive");
-        c->cull_grid = int64_t(value);
-        return 0;
-    }
-    if (strcmp(name, "cull_xcd") == 0) {
-        c->cull_xcd = value != 0.0 ? 1 : 0;
-        return 0;
-    }
-    if (strcmp(name, "cull_tile_block") == 0) {
-        TSC_REQUIRE(value >= 1 && value <= 65536, "cull_tile_block must be in [1, 65536]");
-        c->cull_tile_block = int(value);
-        return 0;
-    }
-    if (strcmp(name, "stage1_f32") == 0) {
-        c->stage1_f32 = int(value);
-        return 0;
-    }
-    if (strcmp(name, "cull_min_pairs") == 0) {
-        TSC_REQUIRE(value >= 0.0, "cull_min_pairs must not be negative");
-        c->cull_min_pairs = value;
-        return 0;
-    }
-    if (strcmp(name, "fused_apply") == 0) {
-        TSC_REQUIRE(value == 0 || value == 1, "fused_apply must be 0 or 1");
-        c->fused_apply = int(value);
-        return 0;
-    }
-    if (strcmp(name, "open_lds_blocks") == 0) {
-        TSC_REQUIRE(value >= 0, "open_lds_blocks must not be negative");
-        c->open_lds_blocks = int(std::min(value, 1073741824.0));
-        return 0;
-    }
-    if (strcmp(name, "local_pass") == 0) {
-        TSC_REQUIRE(value == 0 || value == 1, "local_pass must be 0 or 1");
-        c->local_pass = int(value);
-        return 0;
-    }
-    if (strcmp(name, "clash_first") == 0) {
-        TSC_REQUIRE(value == 0 || value == 1, "clash_first must be 0 or 1");
-        c->clash_first = int(value);
-        return 0;
-    }
-    if (strcmp(name, "clash_lanes") == 0) {
-        TSC_REQUIRE(value == 0 || value == 1, "clash_lanes must be 0 or 1");
-        c->clash_lanes = int(value);
-        return 0;
-    }
-    if (strcmp(name, "clash_fp32") == 0) {
-        TSC_REQUIRE(value == 0 || value == 1, "clash_fp32 must be 0 or 1");
-        c->clash_fp32 = int(value);
-        return 0;
-    }
-    if (strcmp(name, "prune_batch_max_n") == 0) {
-        TSC_REQUIRE(value >= 1 && value <= TSC_PRUNE_BATCH_MAX_N && value == double(int(value)), "prune_batch_max_n must be a whole number in [1, %d]", TSC_PRUNE_BATCH_MAX_N);
-        c->prune_batch_max_n = int(value);
-        return 0;
-    }
-    if (strcmp(name, "seg_cols") == 0) {
-        TSC_REQUIRE(value == 0 || (value >= 256 && value <= 4096 && int(value) % 256 == 0), "seg_cols must be 0 (automatic) or a multiple of 256 in [256, 4096]");
-        c->seg_cols = int(value);
-        return 0;
-    }
-    return fail(TSC_ERR_INVALID, "unknown option '%s'", name);
+    return option_set(c->opt, name, value, g_err, sizeof(g_err));
     TSC_API_GUARD_END
 }
 
 extern "C" __attribute__((visibility("default"))) int tsc_ctx_get_option(tsc_ctx *c, const char *name, double *value) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(c && name && value, "null argument");
-    if (strcmp(name, "prune_batch_max_n") == 0) {
-        *value = double(c->prune_batch_max_n);
-        return 0;
-    }
-    return fail(TSC_ERR_INVALID, "tsc_ctx_get_option: option '%s' cannot be read", name);
+    return option_get(c->opt, name, value, g_err, sizeof(g_err));
     TSC_API_GUARD_END
 }
 
+extern "C" __attribute__((visibility("default"))) int tsc_option_info(int index, const char **name, double *default_value) {
+    TSC_API_GUARD_BEGIN
+    if (option_info(index, name, default_value) != 0) return fail(TSC_ERR_INVALID, "tsc_option_info: no option %d", index);
+    return 0;
+    TSC_API_GUARD_END
+}

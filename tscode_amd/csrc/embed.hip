@@ -106,8 +106,8 @@ static int launch_clash(tsc_ctx *c, const ClashArgs &a, const double *coords, co
     if (a.n_poses == 0) return 0;
     if (a.self_mode) return launch_clash_impl<FUSED, true, false>(c, a, coords, frags, ft, conf_idx, rot, pos, mask, counts);
     // verdict only and no clash allowed: the packed-fp32 minimum with its fp64 fallback (embed_clash.hpp)
-    const bool minmode = !counts && a.max_clashes == 0 && c->clash_fp32 != 0 && 4 * clash_lds_per_wave(a.n, a.lp, true) <= 160 * 1024;
-    if (minmode && FUSED && c->clash_lanes != 0 && a.n_mols == 2 && ft.n_mols == 2 && a.atom_off[1] == ft.atom_off[1] && a.n == ft.n_total &&
+    const bool minmode = !counts && a.max_clashes == 0 && c->opt.clash_fp32 != 0 && 4 * clash_lds_per_wave(a.n, a.lp, true) <= 160 * 1024;
+    if (minmode && FUSED && c->opt.clash_lanes != 0 && a.n_mols == 2 && ft.n_mols == 2 && a.atom_off[1] == ft.atom_off[1] && a.n == ft.n_total &&
         std::min(ft.n_atoms[0], ft.n_atoms[1]) >= 1 && std::min(ft.n_atoms[0], ft.n_atoms[1]) <= 32) {
         // one pose per lane, the smaller fragment in registers (embed_clash.hpp, k_clash_lanes)
         const int mA = ft.n_atoms[0] <= ft.n_atoms[1] ? 0 : 1, mB = 1 - mA, na2 = (ft.n_atoms[mA] + 1) / 2;
@@ -123,7 +123,7 @@ static int launch_clash(tsc_ctx *c, const ClashArgs &a, const double *coords, co
         TSC_HIP(hipGetLastError());
         return 0;
     }
-    if (minmode && FUSED && c->clash_lanes != 0 && (a.n_mols == 2 || a.n_mols == 3) && ft.n_mols == a.n_mols && a.n == ft.n_total &&
+    if (minmode && FUSED && c->opt.clash_lanes != 0 && (a.n_mols == 2 || a.n_mols == 3) && ft.n_mols == a.n_mols && a.n == ft.n_total &&
         a.atom_off[1] == ft.atom_off[1] && (a.n_mols == 2 || a.atom_off[2] == ft.atom_off[2])) {
         // one pose per lane for fragments of any size and for three of them: the "A" fragment of every pair in register tiles, the poses
         // packed again between the fragment pairs (embed_clash.hpp, k_clash_lanes_multi).  The tile size that wastes the fewest padded

@@ -1,5 +1,5 @@
 // pass_plan.hpp -- what a pass of the prune launches, as numbers: which of the three shapes it takes (chunk-local, culled, walked) and
-// every grid of each.  Plain functions of (n, k, rows, rank, world, the context's options, the run's kernel form) that return structs
+// every grid of each.  Plain functions of (n, k, rows, rank, world, the context's options (options.hpp), the run's kernel form) that return structs
 // by value and make no HIP call: prune.hip launches what they say, tools/probe/pass_plan_check.cpp checks them without a GPU.
 #pragma once
 
@@ -9,6 +9,8 @@
 #include "cull.hpp"
 #include "mm.hpp"
 #include "cull_mm.hpp"
+
+static_assert(OPT_LOCAL_MAX_CHUNK_MAX == LP_MAX_ROWS, "the range of \"local_max_chunk\" (options.hpp) ends at the longest chunk the chunk-local kernel takes");
 
 // The chunks [c_lo, c_hi) and structures [s_lo, s_hi) a pass covers on this device: all of them, or a rank's share of a partitioned pass
 struct PassRows {
@@ -32,7 +34,7 @@ static inline PassRows partition_bounds(int64_t n, int64_t k, int rank, int worl
 struct PairForm {
     bool mm, mm16;
 };
-static inline PairForm pair_form(const tsc_ctx &c, int algo, bool records, bool mm64) {
+static inline PairForm pair_form(const tsc_options &c, int algo, bool records, bool mm64) {
     return PairForm{algo == ALGO_SIEVE && records && mm64, algo == ALGO_SIEVE && records && !mm64 && c.sieve_cpl == 2 && c.sieve_trim != 0};
 }
 
@@ -49,7 +51,7 @@ struct PassShape {
 };
 
 // range = false: the rows dealt to (rank, world) by tiles, of all chunks; range = true: every row of rank's chunks `r` (world is 1 then)
-static inline PassShape pass_shape(const tsc_ctx &c, int64_t n, int64_t k, int algo, bool records, bool mm64, bool det_desc, int world, bool range,
+static inline PassShape pass_shape(const tsc_options &c, int64_t n, int64_t k, int algo, bool records, bool mm64, bool det_desc, int world, bool range,
                                    const PassRows &r) {
     PassShape s;
     s.rows_ub = int(std::max<int64_t>(r.s_hi - r.s_lo, 1));
@@ -122,7 +124,7 @@ struct WalkedPlan {
 // rows_ub: upper bound of the rows of the pass on this device (n; in a rank-partitioned pass the structures of this rank's chunks)
 // rows_now (< 0: not known; else <= rows_ub is meant): the rows the pass really has, where the host has learnt it (a pass that waited for
 // k_cull_decide): the grid is sized for them; everything else stays with rows_ub
-static inline WalkedPlan plan_walked(const tsc_ctx &c, int64_t n, int64_t k, int rank, int world, int64_t rows_ub, int64_t rows_now, PairForm f) {
+static inline WalkedPlan plan_walked(const tsc_options &c, int64_t n, int64_t k, int rank, int world, int64_t rows_ub, int64_t rows_now, PairForm f) {
     WalkedPlan w;
     const int A = w.rows = int(std::max<int64_t>(rows_ub, 1));
     const int64_t longest_of_pass = n - (k - 1) * (n / k);
@@ -156,7 +158,7 @@ struct CulledPlan {
     int n_groups, n_seg_mm;   // cull_mm: this rank's groups of 64 rows, segments of CMM_SEG columns
     int64_t grid_mm;    // ... and the workgroups of k_rmsd_sieve_sorted_mm (one wavefront each; launched with at least 1)
 };
-static inline CulledPlan plan_culled(const tsc_ctx &c, int rows_ub, int64_t longest_of_rank, int rank, int world, bool cull_mm) {
+static inline CulledPlan plan_culled(const tsc_options &c, int rows_ub, int64_t longest_of_rank, int rank, int world, bool cull_mm) {
     CulledPlan p;
     const int A = rows_ub;
     const int tb = p.tile_block = world > 1 ? std::max(1, c.cull_tile_block) : 1;

@@ -55,7 +55,7 @@ struct BasisFork {
 };
 static int basis_fork_begin(tsc_ctx *c, int64_t n_poses, int n_heavy, BasisFork *bf) {
     *bf = BasisFork();
-    if (!(c->early_basis && c->prune_algo != ALGO_TILE)) return 0;
+    if (!(c->opt.early_basis && c->opt.prune_algo != ALGO_TILE)) return 0;
     TSC_TRY(basis_sample_table(c, n_poses, &bf->n_samples));
     const size_t need = size_t(bf->n_samples) * n_heavy * 3 + moment_doubles(n_heavy) + basis_doubles(n_heavy);
     if (!(c->eb_block && c->eb_h == n_heavy && c->eb_samples == bf->n_samples)) {
@@ -83,7 +83,7 @@ static int basis_fork_launch(tsc_ctx *c, const BasisFork &bf, Scratch &s, const 
     return 0;
 }
 const double *pending_basis(const tsc_ctx *c, int h) {
-    return (c->eb_valid && c->eb_h == h && c->prune_algo != ALGO_TILE) ? c->eb_block + size_t(c->eb_samples) * h * 3 + moment_doubles(h) : nullptr;
+    return (c->eb_valid && c->eb_h == h && c->opt.prune_algo != ALGO_TILE) ? c->eb_block + size_t(c->eb_samples) * h * 3 + moment_doubles(h) : nullptr;
 }
 
 // Fork the descriptor basis of the prune that will follow from a sample of these poses (all device pointers, as
@@ -137,7 +137,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_embed_masked_dev(tsc_c
     if (n_sel_host) TSC_TRY(read_i32_begin(c, total));
     const double *basis = heavy ? pending_basis(c, n_heavy) : nullptr;
     c->xd_valid = false;
-    if (basis && c->fuse_descriptors && transform_describe_lds_bytes(ft.n_mols, n_heavy) <= 64 * 1024) {
+    if (basis && c->opt.fuse_descriptors && transform_describe_lds_bytes(ft.n_mols, n_heavy) <= 64 * 1024) {
         if (!(c->xd_D && c->xd_cap >= n_poses)) {
             if (c->xd_borrowers > 0)
                 return fail(TSC_ERR_STATE, "tsc_embed_masked_dev: %d live prune run(s) still read the descriptor buffers of an earlier call, which %lld poses "
@@ -157,7 +157,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_embed_masked_dev(tsc_c
         const int nf0 = n_features(n_heavy, 0), nf1 = n_features(n_heavy, 1);
         // the float32 copy for stage 1 of the pair kernels, where the run can be large enough for it (the count is not known yet)
         float *h32 = nullptr;
-        if (want_heavy32(c, double(n_poses) * n_heavy * 24.0)) {
+        if (want_heavy32(c->opt, double(n_poses) * n_heavy * 24.0)) {
             const int64_t need = n_poses * heavy32_pitch(n_heavy);
             if (c->xd_h32_cap < need) {
                 if (c->xd_borrowers > 0)
@@ -247,7 +247,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_pipeline_dev(tsc_ctx *
     hipStream_t st = c->stream;
     Scratch s(c);
     // stage timings only on request ("pass_timing" = 2): four events in the stream cost about 4 us each
-    const bool timed = timings_ms && c->pass_timing >= 2;
+    const bool timed = timings_ms && c->opt.pass_timing >= 2;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     struct EvGuard {
         tsc_ctx *c;
@@ -281,21 +281,21 @@ extern "C" __attribute__((visibility("default"))) int tsc_pipeline_dev(tsc_ctx *
     int n_samples = 0;
     double *d_sample = nullptr, *d_moments = nullptr;
     bool fused_sample = false;
-    if (c->early_basis && c->prune_algo != ALGO_TILE) {
+    if (c->opt.early_basis && c->opt.prune_algo != ALGO_TILE) {
         TSC_TRY(basis_sample_table(c, n_poses, &n_samples));
         TSC_TRY(s.get(size_t(n_samples) * n_heavy * 3, &d_sample));
         TSC_TRY(s.get(basis_doubles(n_heavy), &d_basis));
-        if (c->fuse_descriptors && transform_describe_lds_bytes(ft.n_mols, n_heavy) <= 64 * 1024) {
+        if (c->opt.fuse_descriptors && transform_describe_lds_bytes(ft.n_mols, n_heavy) <= 64 * 1024) {
             TSC_TRY(s.get(size_t(n_poses) * DW, &ext.D));
             TSC_TRY(s.get(size_t(n_poses), &ext.G));
             TSC_TRY(s.get(4, &ext.dmax_bits));
             // (the float32 copy for stage 1 of the pair kernels, where the run can be large enough for it: the count is not known yet)
-            if (want_heavy32(c, double(n_poses) * n_heavy * 24.0))
+            if (want_heavy32(c->opt, double(n_poses) * n_heavy * 24.0))
                 TSC_TRY(s.get(size_t(n_poses) * heavy32_pitch(n_heavy), &ext.heavy32));
         }
         // one device: the sample is embedded and reduced by ONE kernel into accumulators the context keeps zero between runs (sieve.hpp,
         // k_sample_moments); a sharded run takes the fixed-order sums instead (k_transform + k_feature_moments, "deterministic_basis")
-        fused_sample = !c->deterministic_basis && sample_moments_lds_bytes(ft.n_mols, n_heavy) <= 64 * 1024;
+        fused_sample = !c->opt.deterministic_basis && sample_moments_lds_bytes(ft.n_mols, n_heavy) <= 64 * 1024;
         if (fused_sample) {
             const size_t a = size_t(n_features(n_heavy, 0) + 1), b = size_t(n_features(n_heavy, 1) + 1), need = a * a + b * b;
             if (c->mom_cap < need) {
@@ -341,12 +341,12 @@ extern "C" __attribute__((visibility("default"))) int tsc_pipeline_dev(tsc_ctx *
         TSC_HIP(hipEventRecord(c->ev_join, c->basis_stream));
         return 0;
     };
-    if (d_basis && !c->clash_first) TSC_TRY(enqueue_basis_chain());
+    if (d_basis && !c->opt.clash_first) TSC_TRY(enqueue_basis_chain());
     // K1+K2 fused verdicts
     TSC_TRY(tsc_embed_clash_mask_dev(c, frags, frag_off, n_atoms, n_conf, n_mols, conf_idx, rot, pos, n_poses, clash_thresh, max_clashes,
                                      clash_mask, nullptr));
     if (timed) TSC_HIP(hipEventRecord(ev[1], st));
-    if (d_basis && c->clash_first) TSC_TRY(enqueue_basis_chain());
+    if (d_basis && c->opt.clash_first) TSC_TRY(enqueue_basis_chain());
     // ordered compaction: embed only the passing poses, all atoms + heavy atoms
     // (the count goes to the host through pinned memory the scan kernel writes itself: an event record + a copy on a second stream in front
     // of the next launch cost the stream two packets, about 6 us each)
@@ -388,7 +388,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_pipeline_dev(tsc_ctx *
     // queues) is no shorter than the clash kernel + scan it runs beside: the count can be there before the spreads are.  A read of the
     // pre-set +inf would not change a verdict, only the kernel choice (sieve where the all-pairs kernel is 5x faster) -- from run to run.
     int force_algo = -1;
-    if (d_basis && c->prune_algo == ALGO_AUTO && mode == 1 && n_heavy <= MAX_HP) {
+    if (d_basis && c->opt.prune_algo == ALGO_AUTO && mode == 1 && n_heavy <= MAX_HP) {
         TSC_HIP(hipEventSynchronize(c->ev_join));
         const volatile double *sh = reinterpret_cast<const volatile double *>(static_cast<const char *>(c->pinned) + PINNED_SPREAD_OFFSET);
         const double spread[NFAM] = {sh[0], sh[1]};

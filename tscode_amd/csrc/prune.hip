@@ -103,7 +103,7 @@ int build_basis(tsc_ctx *c, hipStream_t st, Scratch &s, const double *heavy, int
     } else {
         TSC_TRY(s.get(m0 + m1 + 1, &d_zero));
         // (the arrival counters of the deterministic form -- its partial matrices are written whole --, or the matrices the fast form adds into)
-        if (c->deterministic_basis) TSC_HIP(hipMemsetAsync(d_zero + m0 + m1, 0, sizeof(double), st));
+        if (c->opt.deterministic_basis) TSC_HIP(hipMemsetAsync(d_zero + m0 + m1, 0, sizeof(double), st));
         else TSC_HIP(hipMemsetAsync(d_zero, 0, (m0 + m1 + 1) * sizeof(double), st));
     }
     d_M[0] = d_zero, d_M[1] = d_zero + m0;
@@ -111,7 +111,7 @@ int build_basis(tsc_ctx *c, hipStream_t st, Scratch &s, const double *heavy, int
         const size_t lds = size_t(32) * (std::max(nf[0], nf[1]) + 1) * sizeof(double);
         if (lds > 64 * 1024)
             TSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_feature_moments), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-        if (c->deterministic_basis)
+        if (c->opt.deterministic_basis)
             hipLaunchKernelGGL(k_feature_moments, dim3(MOM_BLOCKS, NFAM), dim3(256), lds, st, heavy, h, nf[0], nf[1], stride, n_samples, d_M[0], d_M[1],
                                reinterpret_cast<unsigned *>(d_zero + m0 + m1));
         else
@@ -140,7 +140,7 @@ static int build_descriptors(tsc_prune *p, const double *basis) {
         const int64_t stride = std::max<int64_t>(1, p->n / n_samples);
         double *q;
         TSC_TRY(s.get(basis_doubles(h), &q));
-        if (p->n < c->pca_min_n) {  // small ensemble: the identity basis, one tiny launch (sieve.hpp)
+        if (p->n < c->opt.pca_min_n) {  // small ensemble: the identity basis, one tiny launch (sieve.hpp)
             hipLaunchKernelGGL(k_identity_basis, dim3(1), dim3(256), 0, st, nf[0], nf[1], q, q + q_doubles);
             TSC_HIP(hipGetLastError());
         } else {
@@ -170,7 +170,7 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
     TSC_REQUIRE(h > 0, "no heavy atoms: the reference divides by zero here (rmsd_pruning.py:35)");
     TSC_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (reference-exact) or 1 (cache-free)");
     TSC_REQUIRE(rmsd_thr > 0, "rmsd_thr must be positive");
-    TSC_REQUIRE(c->prune_algo != ALGO_TILE || h <= MAX_HP, "prune_algo=1 (register-tiled kernel) supports at most %d heavy atoms, got %d", MAX_HP, h);
+    TSC_REQUIRE(c->opt.prune_algo != ALGO_TILE || h <= MAX_HP, "prune_algo=1 (register-tiled kernel) supports at most %d heavy atoms, got %d", MAX_HP, h);
     *out = nullptr;
     DeviceGuard guard(c->device);
     tsc_prune *p = new (std::nothrow) tsc_prune();
@@ -183,8 +183,8 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
     p->hp = (h + 3) / 4 * 4;
     p->thr = rmsd_thr;
     p->mode = mode;
-    p->algo = (c->prune_algo == ALGO_TILE) ? ALGO_TILE : ALGO_SIEVE;
-    p->det_desc = c->deterministic_basis != 0;
+    p->algo = (c->opt.prune_algo == ALGO_TILE) ? ALGO_TILE : ALGO_SIEVE;
+    p->det_desc = c->opt.deterministic_basis != 0;
     {   // this run's word of pinned memory (the culled-or-walked verdict of a candidate pass): its own for as long as it lives
         std::lock_guard<std::mutex> lock(c->runs_mutex);
         static_assert(PINNED_FLAG_SLOTS == 64, "one bit per flag word");
@@ -201,7 +201,7 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
     Scratch s_basis(c);
     if (force_algo >= 0) {
         p->algo = force_algo;
-    } else if (c->prune_algo == ALGO_AUTO && mode == 1 && h <= MAX_HP && n >= AUTO_TILE_MIN_N && !basis && !(ext && ext->D)) {
+    } else if (c->opt.prune_algo == ALGO_AUTO && mode == 1 && h <= MAX_HP && n >= AUTO_TILE_MIN_N && !basis && !(ext && ext->D)) {
         // automatic choice, no basis from a pipeline around this run: estimate it now and ask whether the screen can separate
         // anything (one synchronisation, some 20 us, on a run of at least 30 000 structures)
         const int n_samples = int(std::min<int64_t>(n, DESC_SAMPLE));
@@ -255,13 +255,13 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
         }
         if (!rc) rc = palloc(p, size_t(n) * DW, &p->Dc);
         // (mm.hpp; decided per run: the 64-row kernels for large runs, the 16-row form of the walked kernel -- "sieve_mm16" -- below that)
-        p->mm64 = c->sieve_mm == 2 || (c->sieve_mm == 1 && n >= c->mm_min_n);
-        const bool want_mm = p->mm64 || c->sieve_mm16 != 0;
+        p->mm64 = c->opt.sieve_mm == 2 || (c->opt.sieve_mm == 1 && n >= c->opt.mm_min_n);
+        const bool want_mm = p->mm64 || c->opt.sieve_mm16 != 0;
         if (!rc && want_mm) rc = palloc(p, size_t(n) * MM_REC_HALVES, &p->Dh);
         // the float32 copy stage 1 reads (sieve.hpp, pair_stage1): from the embedding kernel where there was one, else converted here
         // (it pays where the gathers come from HBM: 41 MB of heavy atoms at C3 sit in the 256 MB infinity cache and the conversions cost the
         // VALU-bound kernel 2 %; at C4's 348 MB a step goes from 12.1 to 10.6 ms.  "stage1_f32": 0 never, 1 from 128 MB on, 2 always)
-        if (!rc && want_heavy32(c, double(n) * h * 24.0)) {
+        if (!rc && want_heavy32(c->opt, double(n) * h * 24.0)) {
             if (ext && ext->heavy32) {  // written by the kernel that embedded the structures
                 p->heavy32 = ext->heavy32;
             } else {
@@ -320,7 +320,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_create(tsc_ctx *
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(c != nullptr, "tsc_prune_create: null argument");
     // descriptors that tsc_embed_masked_dev wrote with this very array are used once, by the run created next ...
-    if (c->xd_valid && c->xd_h == h && c->xd_heavy == heavy_dev && n <= c->xd_cap && c->prune_algo != ALGO_TILE) {
+    if (c->xd_valid && c->xd_h == h && c->xd_heavy == heavy_dev && n <= c->xd_cap && c->opt.prune_algo != ALGO_TILE) {
         ExternalDescriptors ext;
         ext.D = c->xd_D, ext.G = c->xd_G, ext.dmax_bits = c->xd_dmax;
         ext.heavy32 = c->xd_h32_valid ? c->xd_heavy32 : nullptr;
@@ -382,7 +382,7 @@ struct PairEvents {
     hipEvent_t e0, e1;
 };
 static PairEvents pair_events(const tsc_prune *p, int level) {
-    const bool on = p->ctx->pass_timing >= level;
+    const bool on = p->ctx->opt.pass_timing >= level;
     return PairEvents{on ? p->ev[p->cur_slot][1] : nullptr, on ? p->ev[p->cur_slot][2] : nullptr};
 }
 
@@ -410,7 +410,7 @@ static SieveArgs sieve_args(const tsc_prune *p, int rows, int rank, int world, i
     put_screen_thresholds(p, a);
     a.heavy32 = p->heavy32;
     a.tile_cmax = tile_cmax;
-    a.drain_min = p->ctx->drain_min;
+    a.drain_min = p->ctx->opt.drain_min;
     return a;
 }
 
@@ -435,8 +435,8 @@ static int stamp_buffer(tsc_ctx *c, int64_t waves, unsigned long long **dbg) {
 static int walked_pass(tsc_prune *p, int rank, int world, int64_t rows_ub, int64_t rows_now = -1) {
     tsc_ctx *c = p->ctx;
     hipStream_t st = c->stream;
-    const PairForm form = pair_form(*c, p->algo, p->Dh != nullptr, p->mm64);
-    const WalkedPlan w = plan_walked(*c, p->n, p->cur_k, rank, world, rows_ub, rows_now, form);
+    const PairForm form = pair_form(c->opt, p->algo, p->Dh != nullptr, p->mm64);
+    const WalkedPlan w = plan_walked(c->opt, p->n, p->cur_k, rank, world, rows_ub, rows_now, form);
     const PairEvents ev = pair_events(p, 1);
     if (p->algo == ALGO_TILE) {
         TileArgs a;
@@ -450,7 +450,7 @@ static int walked_pass(tsc_prune *p, int rank, int world, int64_t rows_ub, int64
     }
     SieveArgs a = sieve_args(p, w.rows, rank, world, w.seg_cols, p->tile_cmax);
 #ifdef TSC_DBG_STAMPS
-    if (c->dbg_stamp_k == p->cur_k) TSC_TRY(stamp_buffer(c, int64_t(w.grid.x) * w.grid.y * 4, &a.dbg));
+    if (c->opt.dbg_stamp_k == p->cur_k) TSC_TRY(stamp_buffer(c, int64_t(w.grid.x) * w.grid.y * 4, &a.dbg));
 #endif
     FusedApply fa;
     memset(&fa, 0, sizeof(fa));
@@ -465,7 +465,7 @@ static int walked_pass(tsc_prune *p, int rank, int world, int64_t rows_ub, int64
             p->last_slot = -1;  // closed on the device, by the pair kernel's last tile
         }
     }
-    const bool trim = c->sieve_cpl == 2 && c->sieve_trim;
+    const bool trim = c->opt.sieve_cpl == 2 && c->opt.sieve_trim;
     if (form.mm16) {
         TSC_TRY(launch_rmsd_sieve_mm16(p->cur_fused, a.heavy32 != nullptr, w.mm16_waves, st, w.grid, ev.e0, ev.e1, p->heavy, (const int32_t *)p->act,
                                        (const double *)p->Gall, (const _Float16 *)p->Dh, (const int32_t *)p->cend, p->best, p->counters,
@@ -480,7 +480,7 @@ static int walked_pass(tsc_prune *p, int rank, int world, int64_t rows_ub, int64
     }
     // (stage 1 on the float32 copy exists for the default shape of the kernel only)
     TSC_TRY((p->cur_fused ? launch_rmsd_sieve_fused : launch_rmsd_sieve_plain)(
-        c->sieve_cpl, trim, trim && a.heavy32 != nullptr, st, w.grid, ev.e0, ev.e1, p->heavy, (const int32_t *)p->act, (const double *)p->Gall, (const float *)p->Dc,
+        c->opt.sieve_cpl, trim, trim && a.heavy32 != nullptr, st, w.grid, ev.e0, ev.e1, p->heavy, (const int32_t *)p->act, (const double *)p->Gall, (const float *)p->Dc,
         (const int32_t *)p->cend, p->best, p->counters, (const PruneState *)p->state, a, fa));
     TSC_HIP(hipGetLastError());
     return 0;
@@ -518,7 +518,7 @@ static int open_rows(tsc_prune *p, const PassGeom &g, const PassShape &s, bool r
     hipStream_t st = c->stream;
     const OpenPlan o = plan_open_rows(s.rows_ub);
     OpenArgs oa;
-    oa.use_cache = (p->mode == 0), oa.fused = s.fused ? 1 : 0, oa.lds_cap = std::min(c->open_lds_blocks, OPEN_LDS_BLOCKS);
+    oa.use_cache = (p->mode == 0), oa.fused = s.fused ? 1 : 0, oa.lds_cap = std::min(c->opt.open_lds_blocks, OPEN_LDS_BLOCKS);
     oa.view = view_of_open_pass(p), oa.bits = p->bits, oa.bit_words = int(p->bit_words);
     oa.boff = p->boff, oa.n_blocks = p->n_blocks, oa.block_items = SCAN_TILE;
     oa.n_tiles = o.n_tiles, oa.tickets = &p->tickets->pass;
@@ -526,7 +526,7 @@ static int open_rows(tsc_prune *p, const PassGeom &g, const PassShape &s, bool r
     oa.Dh = p->Dh, oa.dmax_bits = p->dmax_bits;
     oa.dbg = nullptr;
 #ifdef TSC_DBG_STAMPS
-    if (c->dbg_stamp_k == -p->cur_k) TSC_TRY(stamp_buffer(c, int64_t(o.stamp_blocks) * 4, &oa.dbg));  // (a negative k selects k_open_rows of pass k)
+    if (c->opt.dbg_stamp_k == -p->cur_k) TSC_TRY(stamp_buffer(c, int64_t(o.stamp_blocks) * 4, &oa.dbg));  // (a negative k selects k_open_rows of pass k)
 #endif
     int nxt = -1;
     const StepArgs sa = s.fused ? next_step_args(p, &nxt) : StepArgs{-1, -1, 0ll, 0, -1};
@@ -599,7 +599,7 @@ static int cull_verdict(tsc_prune *p, const PassGeom &g, bool *run_culled, int64
     *flag = 0;
     hipLaunchKernelGGL(k_chunk_bases, dim3(unsigned(g.k + 1)), dim3(64), 0, st, g, (const PruneState *)p->state, (const int32_t *)p->boff,
                        (const unsigned long long *)p->bits, int(p->bit_words), p->n_blocks, p->cbase, p->cfill);
-    hipLaunchKernelGGL(k_cull_decide, dim3(1), dim3(64), 0, st, p->state, (const PassCounters *)p->counters, (const int32_t *)p->cbase, g.k, c->cull == 2 ? 1 : 0,
+    hipLaunchKernelGGL(k_cull_decide, dim3(1), dim3(64), 0, st, p->state, (const PassCounters *)p->counters, (const int32_t *)p->cbase, g.k, c->opt.cull == 2 ? 1 : 0,
                        const_cast<int *>(flag));
     TSC_HIP(hipStreamSynchronize(st));
     *run_culled = *flag != 0;
@@ -628,13 +628,13 @@ static int culled_pass(tsc_prune *p, int rank, int world, bool range, const Pass
                        p->crank, (const _Float16 *)(cull_mm ? p->Dh : nullptr), cull_mm ? p->Dhs : nullptr, cull_mm ? p->cstruct : nullptr);
     hipLaunchKernelGGL(k_tile_boxes, dim3(unsigned(ceil_div<int64_t>(n, CULL_COLS))), dim3(128), 0, st, (const PruneState *)p->state, (const float *)p->Ds, p->cbox,
                        p->rbox);
-    const CulledPlan q = plan_culled(*c, s.rows_ub, s.longest_of_rank, rank, world, cull_mm);
+    const CulledPlan q = plan_culled(c->opt, s.rows_ub, s.longest_of_rank, rank, world, cull_mm);
     SieveArgs a = sieve_args(p, s.rows_ub, rank, world, CULL_SEG_COLS, nullptr);
-    const CullArgs ca{p->Ds, p->crank, p->cbase, p->cbox, p->rbox, int(k), q.tile_block, c->cull_xcd};
+    const CullArgs ca{p->Ds, p->crank, p->cbase, p->cbox, p->rbox, int(k), q.tile_block, c->opt.cull_xcd};
     const PairEvents ev = pair_events(p, 1);
     if (cull_mm) {
 #ifdef TSC_DBG_STAMPS
-        if (c->dbg_stamp_k == k) TSC_TRY(stamp_buffer(c, q.grid_mm * 4, &a.dbg));  // (8 of every 32 words used: one wavefront per workgroup)
+        if (c->opt.dbg_stamp_k == k) TSC_TRY(stamp_buffer(c, q.grid_mm * 4, &a.dbg));  // (8 of every 32 words used: one wavefront per workgroup)
 #endif
         const CullMmArgs cm{p->Dhs, p->cstruct};
         TSC_TRY(launch_rmsd_sieve_sorted_mm(a.heavy32 != nullptr, st, dim3(unsigned(std::max<int64_t>(1, q.grid_mm))), ev.e0, ev.e1, p->heavy, (const int32_t *)p->act,
@@ -667,12 +667,12 @@ static int pass_launch(tsc_prune *p, int rank, int world, bool range) {
     const int64_t n = p->n, k = p->cur_k;
     const int slot = p->cur_slot;
     const PassRows r = range ? partition_bounds(n, k, p->part_rank, p->part_world) : whole_pass(n, k);
-    const PassShape s = pass_shape(*c, n, k, p->algo, p->Dh != nullptr, p->mm64, p->det_desc, world, range, r);
+    const PassShape s = pass_shape(c->opt, n, k, p->algo, p->Dh != nullptr, p->mm64, p->det_desc, world, range, r);
     const PassGeom g{int(n), int(k), int(n / k)};
     p->cur_range = range;
     for (int i = 0; i < 4; ++i)
         if (!p->ev[slot][i]) TSC_TRY(get_event(c, &p->ev[slot][i]));
-    if (c->pass_timing >= 2) TSC_HIP(hipEventRecord(p->ev[slot][0], st));
+    if (c->opt.pass_timing >= 2) TSC_HIP(hipEventRecord(p->ev[slot][0], st));
     // 0. open this pass: gate (:192), counters, cache-view bitmap -- already done by the apply kernel of the pass before
     //    it (its last block), by a one-block launch for the first pass of a run
     if (p->opened_slot != slot) {
@@ -794,7 +794,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_merge(tsc_p
     TSC_HIP(hipGetLastError());
     p->opened_slot = nxt;
     p->last_slot = -1;  // closed on the device
-    if (c->pass_timing >= 2) TSC_HIP(hipEventRecord(p->ev[p->cur_slot][3], c->stream));
+    if (c->opt.pass_timing >= 2) TSC_HIP(hipEventRecord(p->ev[p->cur_slot][3], c->stream));
     p->cur_k = 0;
     p->cur_slot = -1;
     p->cur_range = false;
@@ -883,7 +883,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_finish(tsc_
         p->last_slot = -1;  // closed on the device
         TSC_HIP(hipGetLastError());
     }
-    if (c->pass_timing >= 2) TSC_HIP(hipEventRecord(p->ev[p->cur_slot][3], c->stream));
+    if (c->opt.pass_timing >= 2) TSC_HIP(hipEventRecord(p->ev[p->cur_slot][3], c->stream));
     p->cur_k = 0;
     p->cur_slot = -1;
     p->collected = false;
@@ -1028,8 +1028,8 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_stats(tsc_prune 
             s.pairs_screened = rec[slot].screened, s.new_keys = rec[slot].removed, s.algo = rec[slot].algo;
             s.nonfinite_input = nonfinite ? 1 : 0;
             float ms = 0;
-            if (c->pass_timing >= 2 && hipEventElapsedTime(&ms, p->ev[slot][0], p->ev[slot][3]) == hipSuccess) s.gpu_ms = ms;
-            if (c->pass_timing >= (rec[slot].algo == ALGO_LOCAL ? 2 : 1) && hipEventElapsedTime(&ms, p->ev[slot][1], p->ev[slot][2]) == hipSuccess) s.tile_ms = ms;
+            if (c->opt.pass_timing >= 2 && hipEventElapsedTime(&ms, p->ev[slot][0], p->ev[slot][3]) == hipSuccess) s.gpu_ms = ms;
+            if (c->opt.pass_timing >= (rec[slot].algo == ALGO_LOCAL ? 2 : 1) && hipEventElapsedTime(&ms, p->ev[slot][1], p->ev[slot][2]) == hipSuccess) s.tile_ms = ms;
         }
         p->collected = true;
     }

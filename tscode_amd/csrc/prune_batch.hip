@@ -29,8 +29,8 @@ int make_segments(const char *who, const tsc_ctx *c, const int64_t *offsets, con
     for (int64_t s = 0; s < n_segments; ++s) {
         TSC_REQUIRE(h[s] >= 1, "%s: segment %lld has %d heavy atoms (at least 1)", who, (long long)s, h[s]);
         TSC_REQUIRE(n[s] >= 0, "%s: segment %lld has %d structures", who, (long long)s, n[s]);
-        TSC_REQUIRE(n[s] <= c->prune_batch_max_n, "%s: segment %lld has %d structures, more than \"prune_batch_max_n\" = %d", who, (long long)s, n[s],
-                    c->prune_batch_max_n);
+        TSC_REQUIRE(n[s] <= c->opt.prune_batch_max_n, "%s: segment %lld has %d structures, more than \"prune_batch_max_n\" = %d", who, (long long)s, n[s],
+                    c->opt.prune_batch_max_n);
         TSC_REQUIRE(offsets[s + 1] - offsets[s] == int64_t(n[s]) * h[s] * 3, "%s: offsets[%lld] .. offsets[%lld] span %lld doubles, segment is %d x %d x 3", who,
                     (long long)s, (long long)s + 1, (long long)(offsets[s + 1] - offsets[s]), n[s], h[s]);
         TSC_REQUIRE(std::isfinite(thr[s]), "%s: thr[%lld] is not finite", who, (long long)s);

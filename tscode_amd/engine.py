@@ -7,6 +7,7 @@ leave results on the device.  Every call goes through the C ABI of include/tscod
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import threading
 import weakref
@@ -152,15 +153,34 @@ class Engine:
         check(self.lib.tsc_ctx_synchronize(self._h))
 
     def set_option(self, name: str, value: float):
-        """Tunables of the library, as include/tscode_hip.h lists them at tsc_ctx_set_option: "prune_algo" (0 auto, 1 register-tiled,
-        2 sieve), "seg_cols", "prune_batch_max_n" (structures per ensemble that the batch kernel takes), ..."""
+        """tsc_ctx_set_option: set a tunable of the library.  include/tscode_hip.h lists them, with their values, above that function."""
         check(self.lib.tsc_ctx_set_option(self._h, name.encode(), C.c_double(value)))
 
     def get_option(self, name: str) -> float:
-        """tsc_ctx_get_option: the current value of a tunable the host side routes by ("prune_batch_max_n")."""
+        """tsc_ctx_get_option: the current value of a tunable (every one can be read)."""
         v = C.c_double()
         check(self.lib.tsc_ctx_get_option(self._h, name.encode(), C.byref(v)))
         return v.value
+
+    def option_defaults(self) -> dict:
+        """{name: default} of every tunable, in the library's order (tsc_option_info: the library holds the only list)."""
+        out, name, v = {}, C.c_char_p(), C.c_double()
+        while self.lib.tsc_option_info(len(out), C.byref(name), C.byref(v)) == 0:
+            out[name.value.decode()] = v.value
+        return out
+
+    @contextlib.contextmanager
+    def options(self, **values):
+        """Run a block under other values of some tunables: `with eng.options(cull=2, cull_min_pairs=0): ...` sets them and puts back
+        what was there before -- not the defaults -- in reverse order, however the block ends."""
+        old = [(name, self.get_option(name)) for name in values]
+        try:
+            for name, value in values.items():
+                self.set_option(name, value)
+            yield self
+        finally:
+            for name, value in reversed(old):
+                self.set_option(name, value)
 
     @property
     def prune_batch_max_n(self) -> int:
