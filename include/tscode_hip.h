@@ -59,6 +59,7 @@ typedef enum {
 typedef struct tsc_ctx tsc_ctx;     /* one per (process, device); owns a stream and scratch memory */
 typedef struct tsc_prune tsc_prune; /* state of one prune_conformers_rmsd run (stepping API) */
 typedef struct tsc_rot_corr tsc_rot_corr; /* state of one prune_conformers_rmsd_rot_corr run */
+typedef struct tsc_rot_corr_batch tsc_rot_corr_batch; /* ... of one run over many ensembles */
 
 /* ---- library / context ------------------------------------------------------------------ */
 int tsc_version(void);
@@ -283,6 +284,18 @@ int tsc_tfd_batch_pass_dev(tsc_ctx *ctx, const float *tf, int64_t tf_count, cons
  * n_c, 2], distances f64[n_structs, n_c] (NaN = no target).  Host pointers. */
 int tsc_inertia_moments(tsc_ctx *ctx, const double *structures, int64_t n_structs, int n_atoms, const double *masses, double *out);
 int tsc_moi_first_similar(tsc_ctx *ctx, const double *moments, int64_t n_structs, double max_deviation, int32_t *first);
+
+/* The same for many ensembles per call (tscode/optimization_methods.py:327-358, one prune_by_moment_of_inertia per segment).
+ * Segment s has n_structs[s] >= 0 structures of n_atoms[s] >= 1 atoms at structures + offsets[s] (offsets i64[n_segments + 1] in
+ * doubles, offsets[0] = 0) and its own masses, back to back in masses f64[sum n_atoms].  Host arrays.
+ * tsc_inertia_moments_batch: out f64[sum n_structs, 3], per segment what tsc_inertia_moments gives it alone, bit for bit.
+ * tsc_moi_first_similar_batch: moments f64[sum n_structs, 3] of the segments back to back; first i32[sum n_structs]: per row what
+ * tsc_moi_first_similar gives the segment alone with max_deviation[s] -- an index INSIDE the segment, or -1.  A row never looks at
+ * a column of another segment. */
+int tsc_inertia_moments_batch(tsc_ctx *ctx, const double *structures, const int64_t *offsets, const int32_t *n_structs,
+                              const int32_t *n_atoms, const double *masses, int64_t n_segments, double *out);
+int tsc_moi_first_similar_batch(tsc_ctx *ctx, const double *moments, const int32_t *n_structs, const double *max_deviation,
+                                int64_t n_segments, int32_t *first);
 int tsc_embed_scores(tsc_ctx *ctx, const double *structures, int64_t n_structs, int n_atoms, const int32_t *indices,
                      const double *distances, int n_c, float *scores, double *fitness_error);
 
@@ -673,6 +686,32 @@ int tsc_rot_corr_pairs(tsc_ctx *ctx, const double *coords, int64_t n_structs, in
                        const int32_t *torsions, int n_tors, const double *angles, const int32_t *n_angles, const uint8_t *move_mask,
                        const int32_t *sub_ptr, const int32_t *sub_idx, const int32_t *pairs, int64_t n_pairs, double *rmsd,
                        double *best_angle);
+
+/* The symmetry-corrected prune of many ensembles per run (tscode/torsion_module.py:1013-1161, one schedule :1076-1152 per segment,
+ * walked in lockstep by the caller).  Every segment is an ensemble of its own molecule: segment s has n_structs[s] structures of
+ * n_atoms[s] atoms at coords + offsets[s] (offsets i64[n_segments + 1] in doubles, offsets[0] = 0), centred as tsc_rot_corr_begin
+ * takes them, and its own set-up in the layout of tsc_rot_corr_begin, the segments' arrays back to back: heavy i32[sum n_heavy],
+ * torsions i32[sum n_tors, 4], angles f64[sum n_tors, 6], n_angles i32[sum n_tors], move_mask u8[sum n_tors[s] * n_atoms[s]],
+ * sub_ptr i32[sum (n_tors + 1)] (each segment's own, starting at 0), sub_idx i32[sum of the segments' sub_ptr[n_tors]].  The limits
+ * of tsc_rot_corr_begin hold per segment and are checked on the host arrays before anything touches the device; tsc_last_error()
+ * names the segment.  Host arrays throughout.
+ *   tsc_rot_corr_batch_begin    uploads every segment's set-up and structures and zeroes the caches of dissimilar pairs (:1121-1123).
+ *   tsc_rot_corr_batch_pass     one schedule slot in ONE launch for the n_open segments open[q] (ascending) whose gate (:1083) is
+ *                               open in it: chunk geometry d[q], num_active[q] and threshold max_rmsd[q] their own, k shared.  One
+ *                               workgroup per chunk of each open segment walks its rows as tsc_rot_corr_pass does.  first
+ *                               i32[sum n_structs]: per row of an open segment what tsc_rot_corr_pass gives the segment alone, as an
+ *                               index INSIDE the segment; -1 for every other row.  pairs_evaluated i64[n_open].  Synchronous.
+ *   tsc_rot_corr_batch_end      copies the structures as the passes left them to coords_out f64[offsets[n_segments]].
+ *   tsc_rot_corr_batch_destroy  frees the run.  A context lists its live runs and destroys them with itself: do not hand a run to
+ *                               tsc_rot_corr_batch_destroy after its context is destroyed. */
+int tsc_rot_corr_batch_begin(tsc_ctx *ctx, const double *coords, const int64_t *offsets, const int32_t *n_structs,
+                             const int32_t *n_atoms, const int32_t *heavy, const int32_t *n_heavy, const int32_t *torsions,
+                             const int32_t *n_tors, const double *angles, const int32_t *n_angles, const uint8_t *move_mask,
+                             const int32_t *sub_ptr, const int32_t *sub_idx, int64_t n_segments, tsc_rot_corr_batch **out);
+int tsc_rot_corr_batch_pass(tsc_rot_corr_batch *run, const int32_t *open, const int64_t *d, int64_t k, const int64_t *num_active,
+                            const double *max_rmsd, int64_t n_open, int32_t *first, int64_t *pairs_evaluated);
+int tsc_rot_corr_batch_end(tsc_rot_corr_batch *run, double *coords_out);
+int tsc_rot_corr_batch_destroy(tsc_rot_corr_batch *run);
 
 /* Ensemble alignment, k-means and the diverse-conformer pick: the end of a conformational search (tscode/torsion_module.py:849-924,
  * most_diverse_conformers; csrc/diverse.hpp).  Host arrays throughout; fp64; every sum in a fixed order, so two calls on the same

@@ -25,13 +25,15 @@ from .install import install, uninstall  # noqa: F401
 from .numba_functions import (_get_tf_mat, compenetration_check, compenetration_mask, count_clashes, get_torsion_fingerprint,  # noqa: F401
                               prune_conformers_tfd, prune_conformers_tfd_batch, tfd_similarity)
 from .optimization_methods import (_score_embed_poses, fitness_check, fitness_mask, get_inertia_moments,  # noqa: F401
-                                   get_moi_similarity_matches, prune_by_moment_of_inertia)
+                                   get_moi_similarity_matches, prune_by_moment_of_inertia, prune_by_moment_of_inertia_batch,
+                                   similarity_refining_batch)
 from .torsion_module import (clustered_csearch_batch, clustered_csearch_step, csearch_augmentation_batch, csearch_batch, csearch_candidates, csearch_candidates_multi,  # noqa: F401
                              csearch_rotate, csearch_rotate_multi, diverse_select, diverse_select_batch, group_torsions_batch, hydrogen_bonds_batch, torsion_sets_batch, most_diverse_conformers, most_diverse_conformers_batch, rotate_dihedral, rotate_dihedral_batch,
                              torsion_comp_check)
 from .hypermolecule_class import align_structures  # noqa: F401
 from .kmeans import kmeans_lloyd, kmeans_plusplus_rows  # noqa: F401
-from .rot_corr import last_rot_corr_stats, prune_conformers_rmsd_rot_corr, prune_rmsd_rot_corr_arrays, rot_corr_pairs  # noqa: F401
+from .rot_corr import (last_rot_corr_batch_stats, last_rot_corr_stats, prune_conformers_rmsd_rot_corr,  # noqa: F401
+                       prune_rmsd_rot_corr_arrays, prune_rmsd_rot_corr_arrays_batch, rot_corr_pairs)
 from .rmsd_pruning import (_rmsd_similarity, last_prune_batch_stats, last_prune_stats, pack_heavy_batch, prune_conformers_rmsd,  # noqa: F401
                            prune_conformers_rmsd_batch, rmsd_and_max_numba)
 

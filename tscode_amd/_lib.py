@@ -96,6 +96,8 @@ _SIGNATURES = {
     "tsc_embed_masked_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp, _vp, c_i64p]),
     "tsc_inertia_moments": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp]),
     "tsc_moi_first_similar": (C.c_int, [_vp, _vp, C.c_int64, C.c_double, _vp]),
+    "tsc_inertia_moments_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    "tsc_moi_first_similar_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "tsc_embed_scores": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
     "tsc_torsion_fingerprints": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, _vp]),
     "tsc_tfd_first_similar": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, _vp]),
@@ -162,6 +164,10 @@ _SIGNATURES = {
     "tsc_rot_corr_end": (C.c_int, [_vp, _vp]),
     "tsc_rot_corr_destroy": (C.c_int, [_vp]),
     "tsc_rot_corr_pairs": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
+    "tsc_rot_corr_batch_begin": (C.c_int, [_vp] * 14 + [C.c_int64, C.POINTER(_vp)]),
+    "tsc_rot_corr_batch_pass": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp]),
+    "tsc_rot_corr_batch_end": (C.c_int, [_vp, _vp]),
+    "tsc_rot_corr_batch_destroy": (C.c_int, [_vp]),
     "tsc_align_structures": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, _vp]),
     "tsc_kmeans_lloyd": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, c_f64p, C.POINTER(C.c_int),
                                    C.POINTER(C.c_int)]),

@@ -7,76 +7,118 @@
 // step of prune_by_moment_of_inertia stays on the host (tscode_amd/optimization_methods.py).
 #pragma once
 #include "common.hpp"
+#include "tfd.hpp"
 
 namespace tsc {
 
-inline __global__ __launch_bounds__(256) void k_inertia_moments(const double *__restrict__ structures, int64_t N, int n, const double *__restrict__ masses,
-                                                          double *__restrict__ out) {
-    for (int64_t s = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; s < N; s += int64_t(gridDim.x) * blockDim.x) {
-        const double *c = structures + s * n * 3;
-        double tot = 0, com0 = 0, com1 = 0, com2 = 0;
-        for (int a = 0; a < n; ++a) {  // algebra.py:215-223
-            const double m = masses[a];
-            tot += m, com0 += c[3 * a] * m, com1 += c[3 * a + 1] * m, com2 += c[3 * a + 2] * m;
-        }
-        com0 /= tot, com1 /= tot, com2 /= tot;
-        double A[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-        for (int a = 0; a < n; ++a) {  // :177-182
-            const double x = c[3 * a] - com0, y = c[3 * a + 1] - com1, z = c[3 * a + 2] - com2, m = masses[a];
-            const double r2 = x * x + y * y + z * z;
-            A[0][0] += m * (r2 - x * x), A[0][1] += m * (-x * y), A[0][2] += m * (-x * z);
-            A[1][1] += m * (r2 - y * y), A[1][2] += m * (-y * z), A[2][2] += m * (r2 - z * z);
-        }
-        A[1][0] = A[0][1], A[2][0] = A[0][2], A[2][1] = A[1][2];
-        for (int sweep = 0; sweep < 60; ++sweep) {  // cyclic Jacobi, constant indices only
-            const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-            const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-            if (!(off > 1e-32 * dia)) break;
+// get_inertia_moments (algebra.py:165-186, diagonalize :207-213) of the structure c[n][3]: centre of mass, tensor, cyclic Jacobi,
+// eigenvalues ordered by absolute value into out[3].  The plain and the segmented kernel both call this, so a moment cannot differ
+// between the two routes.
+__device__ inline void inertia_moments_of(const double *__restrict__ c, int n, const double *__restrict__ masses, double *__restrict__ out) {
+    double tot = 0, com0 = 0, com1 = 0, com2 = 0;
+    for (int a = 0; a < n; ++a) {  // algebra.py:215-223
+        const double m = masses[a];
+        tot += m, com0 += c[3 * a] * m, com1 += c[3 * a + 1] * m, com2 += c[3 * a + 2] * m;
+    }
+    com0 /= tot, com1 /= tot, com2 /= tot;
+    double A[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    for (int a = 0; a < n; ++a) {  // :177-182
+        const double x = c[3 * a] - com0, y = c[3 * a + 1] - com1, z = c[3 * a + 2] - com2, m = masses[a];
+        const double r2 = x * x + y * y + z * z;
+        A[0][0] += m * (r2 - x * x), A[0][1] += m * (-x * y), A[0][2] += m * (-x * z);
+        A[1][1] += m * (r2 - y * y), A[1][2] += m * (-y * z), A[2][2] += m * (r2 - z * z);
+    }
+    A[1][0] = A[0][1], A[2][0] = A[0][2], A[2][1] = A[1][2];
+    for (int sweep = 0; sweep < 60; ++sweep) {  // cyclic Jacobi, constant indices only
+        const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
+        const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
+        if (!(off > 1e-32 * dia)) break;
 #pragma unroll
-            for (int p = 0; p < 2; ++p)
+        for (int p = 0; p < 2; ++p)
 #pragma unroll
-                for (int q = p + 1; q < 3; ++q) {
-                    const double apq = A[p][q];
-                    if (apq != 0.0) {
-                        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-                        double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-                        t = theta < 0.0 ? -t : t;
-                        const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
+            for (int q = p + 1; q < 3; ++q) {
+                const double apq = A[p][q];
+                if (apq != 0.0) {
+                    const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+                    double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
+                    t = theta < 0.0 ? -t : t;
+                    const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
 #pragma unroll
-                        for (int k = 0; k < 3; ++k) {
-                            const double akp = A[k][p], akq = A[k][q];
-                            A[k][p] = cs * akp - sn * akq, A[k][q] = sn * akp + cs * akq;
-                        }
+                    for (int k = 0; k < 3; ++k) {
+                        const double akp = A[k][p], akq = A[k][q];
+                        A[k][p] = cs * akp - sn * akq, A[k][q] = sn * akp + cs * akq;
+                    }
 #pragma unroll
-                        for (int k = 0; k < 3; ++k) {
-                            const double apk = A[p][k], aqk = A[q][k];
-                            A[p][k] = cs * apk - sn * aqk, A[q][k] = sn * apk + cs * aqk;
-                        }
+                    for (int k = 0; k < 3; ++k) {
+                        const double apk = A[p][k], aqk = A[q][k];
+                        A[p][k] = cs * apk - sn * aqk, A[q][k] = sn * apk + cs * aqk;
                     }
                 }
-        }
-        double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2], t;  // order by |eigenvalue| (:209)
-        if (fabs(e0) > fabs(e1)) t = e0, e0 = e1, e1 = t;
-        if (fabs(e1) > fabs(e2)) t = e1, e1 = e2, e2 = t;
-        if (fabs(e0) > fabs(e1)) t = e0, e0 = e1, e1 = t;
-        out[3 * s] = e0, out[3 * s + 1] = e1, out[3 * s + 2] = e2;
+            }
     }
+    double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2], t;  // order by |eigenvalue| (:209)
+    if (fabs(e0) > fabs(e1)) t = e0, e0 = e1, e1 = t;
+    if (fabs(e1) > fabs(e2)) t = e1, e1 = e2, e2 = t;
+    if (fabs(e0) > fabs(e1)) t = e0, e0 = e1, e1 = t;
+    out[0] = e0, out[1] = e1, out[2] = e2;
 }
 
-// algebra.py:188-205: first[i] = first j > i with all(|im_i - im_j| / im_i < max_deviation), -1 if none
+inline __global__ __launch_bounds__(256) void k_inertia_moments(const double *__restrict__ structures, int64_t N, int n, const double *__restrict__ masses,
+                                                          double *__restrict__ out) {
+    for (int64_t s = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; s < N; s += int64_t(gridDim.x) * blockDim.x)
+        inertia_moments_of(structures + s * n * 3, n, masses, out + 3 * s);
+}
+
+// Row i of the pair search (algebra.py:188-205) over the moments mo[N][3], by one wavefront: the first j > i with
+// all(|im_i - im_j| / im_i < max_deviation), -1 if none.  The same value in every lane; both kernels below call this.
+__device__ inline int32_t moi_first_similar_row(const double *__restrict__ mo, int64_t N, int64_t i, double max_deviation, int lane) {
+    const double a0 = mo[3 * i], a1 = mo[3 * i + 1], a2 = mo[3 * i + 2];
+    int32_t found = -1;
+    for (int64_t j0 = i + 1; j0 < N && found < 0; j0 += 64) {
+        const int64_t j = j0 + lane;
+        bool sim = false;
+        if (j < N) sim = fabs(a0 - mo[3 * j]) / a0 < max_deviation && fabs(a1 - mo[3 * j + 1]) / a1 < max_deviation && fabs(a2 - mo[3 * j + 2]) / a2 < max_deviation;
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(sim);
+        if (m) found = int32_t(j0 + (__ffsll((long long)m) - 1));
+    }
+    return found;
+}
+
+// algebra.py:188-205: first[i] = moi_first_similar_row of row i
 inline __global__ __launch_bounds__(256) void k_moi_first_similar(const double *__restrict__ mo, int64_t N, double max_deviation, int32_t *__restrict__ first) {
     const int lane = threadIdx.x & 63;
     for (int64_t i = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); i < N; i += int64_t(gridDim.x) * 4) {
-        const double a0 = mo[3 * i], a1 = mo[3 * i + 1], a2 = mo[3 * i + 2];
-        int32_t found = -1;
-        for (int64_t j0 = i + 1; j0 < N && found < 0; j0 += 64) {
-            const int64_t j = j0 + lane;
-            bool sim = false;
-            if (j < N) sim = fabs(a0 - mo[3 * j]) / a0 < max_deviation && fabs(a1 - mo[3 * j + 1]) / a1 < max_deviation && fabs(a2 - mo[3 * j + 2]) / a2 < max_deviation;
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(sim);
-            if (m) found = int32_t(j0 + (__ffsll((long long)m) - 1));
-        }
+        const int32_t found = moi_first_similar_row(mo, N, i, max_deviation, lane);
         if (lane == 0) first[i] = found;
+    }
+}
+
+// ---- many ensembles per launch (refine_batch.hip) ------------------------------------------------------------------------------
+// Segment s is an ensemble of its own: N structures of n atoms at structures + coord0 with the masses at masses + mass0.  The rows of
+// all segments are numbered through (row0 is a segment's first number); a row finds its segment by that table, its moments lie at
+// out + 3 * (row0 + i), and row i searches j > i inside its own segment only: first[row0 + i] is an index INSIDE the segment.
+struct MoiSegment {
+    int64_t row0, coord0, mass0;
+    double max_deviation;
+    int32_t N, n;
+};
+
+inline __global__ __launch_bounds__(256) void k_inertia_moments_seg(const double *__restrict__ structures, const double *__restrict__ masses,
+                                                              const MoiSegment *__restrict__ segs, int n_segs, int64_t total_rows,
+                                                              double *__restrict__ out) {
+    for (int64_t r = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; r < total_rows; r += int64_t(gridDim.x) * blockDim.x) {
+        const MoiSegment g = segs[tfd_last_not_above(segs, n_segs, r, [](const MoiSegment &q) { return q.row0; })];
+        inertia_moments_of(structures + g.coord0 + (r - g.row0) * g.n * 3, g.n, masses + g.mass0, out + 3 * r);
+    }
+}
+
+inline __global__ __launch_bounds__(256) void k_moi_first_similar_seg(const double *__restrict__ mo, const MoiSegment *__restrict__ segs, int n_segs,
+                                                                int64_t total_rows, int32_t *__restrict__ first) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t r = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); r < total_rows; r += int64_t(gridDim.x) * 4) {
+        const MoiSegment g = segs[tfd_last_not_above(segs, n_segs, r, [](const MoiSegment &q) { return q.row0; })];
+        const int32_t found = moi_first_similar_row(mo + 3 * g.row0, g.N, r - g.row0, g.max_deviation, lane);
+        if (lane == 0) first[r] = found;
     }
 }
 

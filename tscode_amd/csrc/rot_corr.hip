@@ -26,27 +26,6 @@ namespace {
 
 using namespace tsc;
 
-// the limits of the ABI (include/tscode_hip.h), checked on the host arrays before anything touches the device
-int check_setup(int64_t N, int n, const int32_t *heavy, int h, const int32_t *tors, int T, const double *angles, const int32_t *n_angles,
-                const uint8_t *mask, const int32_t *sub_ptr, const int32_t *sub_idx) {
-    TSC_REQUIRE(heavy && (T == 0 || (tors && angles && n_angles && mask)) && sub_ptr && (T == 0 || sub_idx), "rot_corr: null argument");
-    TSC_REQUIRE(N >= 0 && N < INT32_MAX, "rot_corr: %lld structures (at most %d)", (long long)N, INT32_MAX - 1);
-    TSC_REQUIRE(n >= 1 && n <= RC_MAX_ATOMS, "rot_corr: %d atoms per structure (1 .. %d)", n, RC_MAX_ATOMS);
-    TSC_REQUIRE(T >= 0 && T <= RC_MAX_TORS, "rot_corr: %d torsions (0 .. %d)", T, RC_MAX_TORS);
-    TSC_REQUIRE(h >= 1 && h <= n, "rot_corr: %d heavy atoms of %d", h, n);
-    for (int q = 0; q < h; ++q) TSC_REQUIRE(heavy[q] >= 0 && heavy[q] < n, "rot_corr: heavy atom index %d out of range", heavy[q]);
-    TSC_REQUIRE(sub_ptr[0] == 0, "rot_corr: sub_ptr[0] must be 0");
-    for (int t = 0; t < T; ++t) {
-        for (int q = 0; q < 4; ++q) TSC_REQUIRE(tors[4 * t + q] >= 0 && tors[4 * t + q] < n, "rot_corr: torsion %d: atom index out of range", t);
-        TSC_REQUIRE(n_angles[t] >= 1 && n_angles[t] <= RC_MAX_ANGLES, "rot_corr: torsion %d: %d angles (1 .. %d)", t, n_angles[t], RC_MAX_ANGLES);
-        for (int q = 0; q < n_angles[t]; ++q) TSC_REQUIRE(std::isfinite(angles[RC_MAX_ANGLES * t + q]), "rot_corr: torsion %d: angle not finite", t);
-        TSC_REQUIRE(sub_ptr[t + 1] > sub_ptr[t] && sub_ptr[t + 1] - sub_ptr[t] <= n, "rot_corr: torsion %d: local subgraph of %d atoms", t,
-                    sub_ptr[t + 1] - sub_ptr[t]);
-        for (int q = sub_ptr[t]; q < sub_ptr[t + 1]; ++q) TSC_REQUIRE(sub_idx[q] >= 0 && sub_idx[q] < n, "rot_corr: subgraph index out of range");
-    }
-    return 0;
-}
-
 int upload_setup(HostCall &hc, RotCorrArgs &a, int n, const int32_t *heavy, int h, const int32_t *tors, int T, const double *angles,
                  const int32_t *n_angles, const uint8_t *mask, const int32_t *sub_ptr, const int32_t *sub_idx) {
     a.n = n, a.h = h, a.n_tors = T;
@@ -84,7 +63,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_rot_corr_begin(tsc_ctx
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(c && out && (coords || n_structs == 0), "tsc_rot_corr_begin: null argument");
     *out = nullptr;
-    TSC_TRY(check_setup(n_structs, n_atoms, heavy, n_heavy, torsions, n_tors, angles, n_angles, move_mask, sub_ptr, sub_idx));
+    TSC_TRY(rot_corr_check_setup(n_structs, n_atoms, heavy, n_heavy, torsions, n_tors, angles, n_angles, move_mask, sub_ptr, sub_idx));
     // the run's blocks are the call's until everything is in place: an error hands them back behind an idle stream
     HostCall h(c);
     std::unique_ptr<tsc_rot_corr> run(new tsc_rot_corr(c));
@@ -153,7 +132,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_rot_corr_pairs(tsc_ctx
     TSC_REQUIRE(c && (coords || n_structs == 0) && (n_pairs == 0 || (pairs && rmsd && (best_angle || n_tors == 0))),
                 "tsc_rot_corr_pairs: null argument");
     TSC_REQUIRE(n_pairs >= 0, "tsc_rot_corr_pairs: negative pair count");
-    TSC_TRY(check_setup(n_structs, n_atoms, heavy, n_heavy, torsions, n_tors, angles, n_angles, move_mask, sub_ptr, sub_idx));
+    TSC_TRY(rot_corr_check_setup(n_structs, n_atoms, heavy, n_heavy, torsions, n_tors, angles, n_angles, move_mask, sub_ptr, sub_idx));
     for (int64_t p = 0; p < 2 * n_pairs; ++p)
         TSC_REQUIRE(pairs[p] >= 0 && pairs[p] < n_structs, "tsc_rot_corr_pairs: pair %lld: structure index out of range", (long long)(p / 2));
     if (n_pairs == 0) return 0;

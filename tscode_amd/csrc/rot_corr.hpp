@@ -115,22 +115,20 @@ __device__ inline bool cache_bit(const uint32_t *cache, int64_t words, int64_t i
     return (cache[i * words + (j >> 5)] >> (j & 31)) & 1u;
 }
 
-// One pass (:1080-1152 without the graph step): chunk blockIdx.x is [d*step, d*(step+1)), the last one [d*(k-1), num_active).
-// first[i] = the first j of row i that is similar (rmsd < thr), or -1 (left as the caller set it for rows of empty chunks).
-inline __global__ __launch_bounds__(64 * RC_WAVES) void k_rot_corr_pass(RotCorrArgs a, double *__restrict__ coords, int64_t d, int64_t k,
-                                                                        int64_t num_active, double thr, uint32_t *__restrict__ cache,
-                                                                        int64_t words, int32_t *__restrict__ first,
-                                                                        unsigned long long *__restrict__ evaluated) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+// The rows of one chunk [lo, hi) of a pass (:1097-1125), in order, by one workgroup: coords, cache (rows of `words` 32-bit words) and
+// first are ONE ensemble's; lds is the workgroup's dynamic LDS, laid out here from a.n_tors and a.n (rot_corr_lds_bytes of them is the
+// least it may be).  first[i] = the first j of row i that is similar (rmsd < thr), or -1; *evaluated grows by the pairs evaluated.
+// k_rot_corr_pass and k_rot_corr_pass_seg both call this, so a turned structure cannot differ between the two routes.
+__device__ inline void rot_corr_chunk(const RotCorrArgs &a, double *__restrict__ coords, uint32_t *__restrict__ cache, int64_t words,
+                                      int32_t *__restrict__ first, int64_t lo, int64_t hi, double thr, unsigned char *lds,
+                                      unsigned long long *__restrict__ evaluated) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6, n = a.n;
-    const TorsionLists L = torsion_lists_at(s_raw, a.n_tors, n);
+    const TorsionLists L = torsion_lists_at(lds, a.n_tors, n);
     build_torsion_lists(L, a.masks, a.tors, a.n_tors, n);
-    double *c = reinterpret_cast<double *>(s_raw + torsion_lists_bytes(a.n_tors, n) + size_t(wid) * rot_corr_wave_bytes(n));
+    double *c = reinterpret_cast<double *>(lds + torsion_lists_bytes(a.n_tors, n) + size_t(wid) * rot_corr_wave_bytes(n));
     double *best = c + size_t(n) * 3;
-    int *s_first = reinterpret_cast<int *>(s_raw + torsion_lists_bytes(a.n_tors, n) + size_t(nw) * rot_corr_wave_bytes(n));
+    int *s_first = reinterpret_cast<int *>(lds + torsion_lists_bytes(a.n_tors, n) + size_t(nw) * rot_corr_wave_bytes(n));
     unsigned *s_count = reinterpret_cast<unsigned *>(s_first + 1);
-    const int64_t step = blockIdx.x;
-    const int64_t lo = d * step, hi = step == k - 1 ? num_active : d * (step + 1);   // :1093-1096
     if (threadIdx.x == 0) *s_count = 0;
     for (int64_t i = lo; i < hi; ++i) {
         if (threadIdx.x == 0) *s_first = INT_MAX;
@@ -167,6 +165,43 @@ inline __global__ __launch_bounds__(64 * RC_WAVES) void k_rot_corr_pass(RotCorrA
     if (threadIdx.x == 0 && *s_count) atomicAdd(evaluated, (unsigned long long)*s_count);
 }
 
+// One pass (:1080-1152 without the graph step): chunk blockIdx.x is [d*step, d*(step+1)), the last one [d*(k-1), num_active).
+// first[i] = the first j of row i that is similar (rmsd < thr), or -1 (left as the caller set it for rows of empty chunks).
+inline __global__ __launch_bounds__(64 * RC_WAVES) void k_rot_corr_pass(RotCorrArgs a, double *__restrict__ coords, int64_t d, int64_t k,
+                                                                        int64_t num_active, double thr, uint32_t *__restrict__ cache,
+                                                                        int64_t words, int32_t *__restrict__ first,
+                                                                        unsigned long long *__restrict__ evaluated) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    const int64_t step = blockIdx.x;
+    const int64_t lo = d * step, hi = step == k - 1 ? num_active : d * (step + 1);   // :1093-1096
+    rot_corr_chunk(a, coords, cache, words, first, lo, hi, thr, s_raw, evaluated);
+}
+
+// ---- many ensembles per launch (refine_batch.hip) ------------------------------------------------------------------------------
+// One schedule slot of prune_conformers_rmsd_rot_corr (:1080-1152 without the graph step) for the segments whose gate is open in it.
+// Every segment is an ensemble of its own -- its own molecule, set-up, threshold and pass geometry -- with its structures at
+// coords + coord0, its cache rows of `words` words at cache + cache0 and its rows at first + row0; all open segments share k (the
+// schedule is walked in lockstep), so workgroup b serves chunk b % k of segment b / k.  first holds indices INSIDE the segment.
+// dynamic LDS: rot_corr_lds_bytes of the largest open segment; a workgroup lays out its own segment's lists and wave blocks inside it.
+struct RotCorrSegment {
+    RotCorrArgs a;
+    int64_t coord0, cache0, row0;      // in doubles, 32-bit words and rows
+    int64_t words, d, num_active;
+    double thr;
+    unsigned long long *evaluated;     // the segment's pair counter
+};
+
+inline __global__ __launch_bounds__(64 * RC_WAVES) void k_rot_corr_pass_seg(const RotCorrSegment *__restrict__ segs, int64_t k,
+                                                                            double *__restrict__ coords, uint32_t *__restrict__ cache,
+                                                                            int32_t *__restrict__ first) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    const RotCorrSegment g = segs[blockIdx.x / k];
+    const int64_t step = blockIdx.x % k;
+    const int64_t lo = g.d * step, hi = step == k - 1 ? g.num_active : g.d * (step + 1);   // :1093-1096
+    if (lo >= hi) return;                                   // (block-uniform, in front of the first barrier)
+    rot_corr_chunk(g.a, coords + g.coord0, cache + g.cache0, g.words, first + g.row0, lo, hi, g.thr, s_raw, g.evaluated);
+}
+
 // The value-level form: one wavefront per pair, S[j] turned in LDS only (nothing is written back).
 inline __global__ __launch_bounds__(64 * RC_WAVES) void k_rot_corr_pairs(RotCorrArgs a, const double *__restrict__ coords,
                                                                          const int32_t *__restrict__ pairs, int64_t n_pairs,
@@ -187,6 +222,28 @@ inline __global__ __launch_bounds__(64 * RC_WAVES) void k_rot_corr_pairs(RotCorr
         for (int t = lane; t < a.n_tors; t += 64) best_angle[p * a.n_tors + t] = best[t];
         __builtin_amdgcn_wave_barrier();
     }
+}
+
+// the limits of the ABI (include/tscode_hip.h), checked on the host arrays before anything touches the device (rot_corr.hip, and per
+// segment in refine_batch.hip)
+inline int rot_corr_check_setup(int64_t N, int n, const int32_t *heavy, int h, const int32_t *tors, int T, const double *angles, const int32_t *n_angles,
+                                const uint8_t *mask, const int32_t *sub_ptr, const int32_t *sub_idx) {
+    TSC_REQUIRE(heavy && (T == 0 || (tors && angles && n_angles && mask)) && sub_ptr && (T == 0 || sub_idx), "rot_corr: null argument");
+    TSC_REQUIRE(N >= 0 && N < INT32_MAX, "rot_corr: %lld structures (at most %d)", (long long)N, INT32_MAX - 1);
+    TSC_REQUIRE(n >= 1 && n <= RC_MAX_ATOMS, "rot_corr: %d atoms per structure (1 .. %d)", n, RC_MAX_ATOMS);
+    TSC_REQUIRE(T >= 0 && T <= RC_MAX_TORS, "rot_corr: %d torsions (0 .. %d)", T, RC_MAX_TORS);
+    TSC_REQUIRE(h >= 1 && h <= n, "rot_corr: %d heavy atoms of %d", h, n);
+    for (int q = 0; q < h; ++q) TSC_REQUIRE(heavy[q] >= 0 && heavy[q] < n, "rot_corr: heavy atom index %d out of range", heavy[q]);
+    TSC_REQUIRE(sub_ptr[0] == 0, "rot_corr: sub_ptr[0] must be 0");
+    for (int t = 0; t < T; ++t) {
+        for (int q = 0; q < 4; ++q) TSC_REQUIRE(tors[4 * t + q] >= 0 && tors[4 * t + q] < n, "rot_corr: torsion %d: atom index out of range", t);
+        TSC_REQUIRE(n_angles[t] >= 1 && n_angles[t] <= RC_MAX_ANGLES, "rot_corr: torsion %d: %d angles (1 .. %d)", t, n_angles[t], RC_MAX_ANGLES);
+        for (int q = 0; q < n_angles[t]; ++q) TSC_REQUIRE(std::isfinite(angles[RC_MAX_ANGLES * t + q]), "rot_corr: torsion %d: angle not finite", t);
+        TSC_REQUIRE(sub_ptr[t + 1] > sub_ptr[t] && sub_ptr[t + 1] - sub_ptr[t] <= n, "rot_corr: torsion %d: local subgraph of %d atoms", t,
+                    sub_ptr[t + 1] - sub_ptr[t]);
+        for (int q = sub_ptr[t]; q < sub_ptr[t + 1]; ++q) TSC_REQUIRE(sub_idx[q] >= 0 && sub_idx[q] < n, "rot_corr: subgraph index out of range");
+    }
+    return 0;
 }
 
 }  // namespace tsc

@@ -370,6 +370,43 @@ class Engine:
         check(self.lib.tsc_moi_first_similar(self._h, ptr(moments), C.c_int64(len(moments)), C.c_double(float(max_deviation)), ptr(first)))
         return first
 
+    def inertia_moments_batch(self, ensembles, masses):
+        """inertia_moments of every ensemble ([f64[N_s, n_s, 3]], [f64[n_s]]) in one launch: [f64[N_s, 3]]."""
+        ensembles = [np.ascontiguousarray(e, dtype=np.float64) for e in ensembles]
+        masses = [np.ascontiguousarray(m, dtype=np.float64) for m in masses]
+        if len(masses) != len(ensembles):
+            raise ValueError(f"{len(masses)} mass arrays for {len(ensembles)} ensembles")
+        for e, m in zip(ensembles, masses):
+            if e.ndim != 3 or e.shape[2] != 3 or e.shape[1] < 1 or m.shape != (e.shape[1],):
+                raise ValueError("structures must be (N, n_atoms, 3) and masses (n_atoms,)")
+        if not ensembles:
+            return []
+        n_structs = np.array([len(e) for e in ensembles], dtype=np.int32)
+        n_atoms = np.array([e.shape[1] for e in ensembles], dtype=np.int32)
+        offsets = np.concatenate(([0], np.cumsum(n_structs.astype(np.int64) * n_atoms * 3))).astype(np.int64)
+        rows = np.concatenate(([0], np.cumsum(n_structs.astype(np.int64))))
+        coords = np.concatenate([e.ravel() for e in ensembles])
+        all_masses = np.concatenate(masses)
+        out = np.empty((int(rows[-1]), 3))
+        check(self.lib.tsc_inertia_moments_batch(self._h, ptr(coords), ptr(offsets), ptr(n_structs), ptr(n_atoms), ptr(all_masses),
+                                                 C.c_int64(len(ensembles)), ptr(out)))
+        return [out[rows[s]:rows[s + 1]] for s in range(len(ensembles))]
+
+    def moi_first_similar_batch(self, moments, max_deviation):
+        """moi_first_similar of every segment ([f64[N_s, 3]], one max_deviation each) in one launch: [i32[N_s]], indices inside the segment."""
+        moments = [np.ascontiguousarray(m, dtype=np.float64).reshape(-1, 3) for m in moments]
+        dev = np.ascontiguousarray(max_deviation, dtype=np.float64)
+        if dev.shape != (len(moments),):
+            raise ValueError(f"{dev.size} max_deviation values for {len(moments)} segments")
+        if not moments:
+            return []
+        n_structs = np.array([len(m) for m in moments], dtype=np.int32)
+        rows = np.concatenate(([0], np.cumsum(n_structs.astype(np.int64))))
+        all_moments = np.concatenate(moments)
+        first = np.full(int(rows[-1]), -1, dtype=np.int32)
+        check(self.lib.tsc_moi_first_similar_batch(self._h, ptr(all_moments), ptr(n_structs), ptr(dev), C.c_int64(len(moments)), ptr(first)))
+        return [first[rows[s]:rows[s + 1]] for s in range(len(moments))]
+
     def embed_scores(self, structures, indices, distances):
         structures = np.ascontiguousarray(structures, dtype=np.float64)
         indices = np.ascontiguousarray(indices, dtype=np.int32)

@@ -11,8 +11,8 @@ import numpy as np
 
 from .engine import get_engine
 
-__all__ = ["get_inertia_moments", "get_moi_similarity_matches", "prune_by_moment_of_inertia", "fitness_check", "fitness_mask",
-           "_score_embed_poses"]
+__all__ = ["get_inertia_moments", "get_moi_similarity_matches", "prune_by_moment_of_inertia", "prune_by_moment_of_inertia_batch",
+           "similarity_refining_batch", "fitness_check", "fitness_mask", "_score_embed_poses"]
 
 # Standard atomic weights as the `periodictable` package tabulates them (tscode/pt.py builds `pt` from it; the package is
 # not installed in the build image, so the table could not be checked against it) for the elements TSCoDe systems are
@@ -41,6 +41,25 @@ def get_moi_similarity_matches(structures, masses, max_deviation=1e-2):
     return [(int(i), int(first[i])) for i in np.flatnonzero(first >= 0)]
 
 
+def _heavy_masses(atomnos, heavy, masses):
+    """The masses of the heavy atoms: the caller's (per atom, hydrogens included) or the built-in table's, with its warning once.
+    Called from the body of the public function itself (no comprehension, no helper in between), so that the warning names that
+    function's caller."""
+    if masses is None:
+        global _WARNED_MASSES
+        if not _WARNED_MASSES:                                           # said once, loudly: the table is this package's, not periodictable's
+            import warnings
+            warnings.warn("prune_by_moment_of_inertia: masses= not given; using tscode_amd's built-in table of standard atomic weights, "
+                          "which has not been checked against the `periodictable` package the reference reads its masses from "
+                          "(tscode/pt.py).  Pass masses=[pt[z].mass for z in atomnos] to use the reference's own values.", stacklevel=3)
+            _WARNED_MASSES = True
+        try:
+            return np.array([_MASS[int(a)] for a in atomnos[heavy]])
+        except KeyError as exc:
+            raise ValueError(f"no built-in mass for element Z = {exc.args[0]}; pass masses=") from None
+    return np.asarray(masses, dtype=np.float64)[heavy]
+
+
 def prune_by_moment_of_inertia(structures, atomnos, max_deviation=1e-2, masses=None):
     """tscode/optimization_methods.py:327-358.  ``masses`` (per atom, hydrogens included) overrides the built-in table of
     periodictable values.  The member of a cluster that survives is ``tuple(graph.nodes)[0]`` of a networkx subgraph view,
@@ -49,20 +68,7 @@ def prune_by_moment_of_inertia(structures, atomnos, max_deviation=1e-2, masses=N
     structures = np.asarray(structures)
     atomnos = np.asarray(atomnos)
     heavy = atomnos != 1
-    if masses is None:
-        global _WARNED_MASSES
-        if not _WARNED_MASSES:                                           # said once, loudly: the table is this package's, not periodictable's
-            import warnings
-            warnings.warn("prune_by_moment_of_inertia: masses= not given; using tscode_amd's built-in table of standard atomic weights, "
-                          "which has not been checked against the `periodictable` package the reference reads its masses from "
-                          "(tscode/pt.py).  Pass masses=[pt[z].mass for z in atomnos] to use the reference's own values.", stacklevel=2)
-            _WARNED_MASSES = True
-        try:
-            heavy_masses = np.array([_MASS[int(a)] for a in atomnos[heavy]])
-        except KeyError as exc:
-            raise ValueError(f"no built-in mass for element Z = {exc.args[0]}; pass masses=") from None
-    else:
-        heavy_masses = np.asarray(masses, dtype=np.float64)[heavy]
+    heavy_masses = _heavy_masses(atomnos, heavy, masses)
     heavy_structures = np.ascontiguousarray(structures[:, heavy], dtype=np.float64)
     matches = get_moi_similarity_matches(heavy_structures, heavy_masses, max_deviation=max_deviation)
     G = nx.Graph(matches)                                                # :341
@@ -73,6 +79,147 @@ def prune_by_moment_of_inertia(structures, atomnos, max_deviation=1e-2, masses=N
             if i != head:
                 mask[i] = False
     return structures[mask], mask
+
+
+# ---- the same for many ensembles per call --------------------------------------------------------------------------------------
+def _per_ensemble(what, value, S, one_ndim):
+    """``value`` as a list of S entries: one array of ``one_ndim`` dimensions (or a flat sequence) stands for all ensembles."""
+    one_for_all = np.ndim(value) == one_ndim if isinstance(value, np.ndarray) else (len(value) == 0 or np.ndim(value[0]) == one_ndim - 1)
+    if one_for_all:
+        return [value] * S
+    if len(value) != S:
+        raise ValueError(f"{len(value)} {what} arrays for {S} ensembles")
+    return list(value)
+
+
+def _moi_batch_args(ensembles, atomnos, max_deviation, masses, need_heavy=True):
+    """The checked arguments of prune_by_moment_of_inertia_batch: ([structures_s], [atomnos_s], f64[S], [masses_s or None]).
+    ``need_heavy``: an ensemble without a heavy atom is refused (the moments are taken over the heavy atoms)."""
+    if isinstance(ensembles, np.ndarray) and ensembles.ndim != 4:
+        raise ValueError("ensembles must be a list of (N, n_atoms, 3) arrays")
+    ens = [np.asarray(e) for e in ensembles]
+    S = len(ens)
+    for s, e in enumerate(ens):
+        if e.ndim != 3 or e.shape[2] != 3 or e.shape[1] < 1:
+            raise ValueError(f"ensemble {s}: structures must be (N, n_atoms, 3)")
+    nos = [np.asarray(a).reshape(-1) for a in _per_ensemble("atomnos", atomnos, S, 1)]
+    ms = [None] * S if masses is None else [np.asarray(m, dtype=np.float64).reshape(-1) for m in _per_ensemble("masses", masses, S, 1)]
+    for s, (e, a, m) in enumerate(zip(ens, nos, ms)):
+        if len(a) != e.shape[1] or (m is not None and len(m) != e.shape[1]):
+            raise ValueError(f"ensemble {s}: atomnos and masses must have one entry per atom ({e.shape[1]})")
+        if need_heavy and not (a != 1).any():
+            raise ValueError(f"ensemble {s}: no heavy atom")
+    dev = np.asarray(max_deviation, dtype=np.float64)
+    if dev.ndim == 0:
+        dev = np.full(S, float(dev))
+    if dev.shape != (S,):
+        raise ValueError(f"{dev.size} max_deviation values for {S} ensembles")
+    return ens, nos, np.ascontiguousarray(dev), ms
+
+
+def prune_by_moment_of_inertia_batch(ensembles, atomnos, max_deviation=1e-2, masses=None):
+    """prune_by_moment_of_inertia (tscode/optimization_methods.py:327-358) for many ensembles per call:
+    ``[(structures_s[mask_s], mask_s)]``, each entry exactly what ``prune_by_moment_of_inertia(ensembles[s], atomnos_s,
+    max_deviation_s, masses_s)`` returns.
+
+    ``ensembles`` is a list of [N_s, n_s, 3] arrays; ``atomnos`` and ``masses`` one array for all or one per ensemble (``masses``
+    as the single call takes it; None: the built-in table, whose warning is given once per call at most); ``max_deviation`` a scalar
+    or one value per ensemble.  The moments of all ensembles are one launch and their pair searches another -- the same
+    per-structure and per-row device code as the single call's kernels (csrc/moi.hpp); a row only looks at columns of its own
+    ensemble.  The graph step (:341-358) stays on the host, per ensemble."""
+    import networkx as nx
+    from .numba_functions import _cluster_heads
+    ens, nos, dev, ms = _moi_batch_args(ensembles, atomnos, max_deviation, masses)
+    if not ens:
+        return []
+    heavy = [a != 1 for a in nos]
+    heavy_masses = []
+    for a, h, m in zip(nos, heavy, ms):                  # (a plain loop: _heavy_masses' warning counts frames)
+        heavy_masses.append(_heavy_masses(a, h, m))
+    eng = get_engine()
+    moments = eng.inertia_moments_batch([np.ascontiguousarray(e[:, h], dtype=np.float64) for e, h in zip(ens, heavy)], heavy_masses)
+    firsts = eng.moi_first_similar_batch(moments, dev)
+    out = []
+    for e, first in zip(ens, firsts):
+        G = nx.Graph([(int(i), int(first[i])) for i in np.flatnonzero(first >= 0)])      # :341
+        mask = np.ones(e.shape[0], dtype=bool)
+        for members, head in _cluster_heads(G):                                           # :342-346: tuple(subgraph.nodes)[0] survives
+            for i in members:
+                if i != head:
+                    mask[i] = False
+        out.append((e[mask], mask))
+    return out
+
+
+def similarity_refining_batch(ensembles, atomnos, quadruplets=None, rot_corr=None, rmsd_thr=0.5, tfd=True, moi=True, rmsd=True, masses=None):
+    """The similarity stages of Embedder.similarity_refining (tscode/embedder.py:1310-1388) on a list of ensembles, each stage ONE
+    batched call over the ensembles that take it: ``[(structures_s, mask_s)]`` with ``mask_s`` over the input rows of ensemble s.
+
+    Stages, order and size gates are the reference's (:1322-1382), each gate taken on the ensemble's current count:
+      TFD      (prune_conformers_tfd_batch) where ``tfd`` and ``quadruplets[s]`` is a non-empty array;
+      MOI      (prune_by_moment_of_inertia_batch) where ``moi`` and at most 500 structures are left (:1342);
+      RMSD     (prune_conformers_rmsd_batch, ``rmsd_thr``) where ``rmsd`` and at most 1e5 are left (:1356);
+      rot-corr (prune_rmsd_rot_corr_arrays_batch, ``max_rmsd = rmsd_thr`` as :1377 passes it) after the RMSD stage, where at most 500
+               are left (:1372) and ``rot_corr[s]`` -- a set-up dict with the keys ``torsions``, ``angles``, ``move_masks``,
+               ``sub_nodes`` -- is given.
+    ``atomnos`` and ``masses`` are one array for all or one per ensemble; ``quadruplets`` and ``rot_corr`` None, one (T, 4)
+    array / one set-up dict for all, or a list with one entry (or None) per ensemble; ``rmsd_thr`` a scalar or one value per
+    ensemble.  An ensemble that went through rot-corr comes back centred and turned, because the reference replaces
+    ``self.structures`` with that stage's result.  The reference's method leaves its TFD
+    ``mask`` undefined when the quadruplets are empty (:1333-1335); here an empty array simply skips the stage."""
+    from .numba_functions import prune_conformers_tfd_batch
+    from .rmsd_pruning import prune_conformers_rmsd_batch
+    from .rot_corr import _rot_corr_batch_args, prune_rmsd_rot_corr_arrays_batch
+    ens, nos, _, ms = _moi_batch_args(ensembles, atomnos, 0.0, masses, need_heavy=False)     # (each stage keeps its own rule on hydrogen-only ensembles)
+    S = len(ens)
+    thr = np.asarray(rmsd_thr, dtype=np.float64)
+    if thr.ndim == 0:
+        thr = np.full(S, float(thr))
+    if thr.shape != (S,):
+        raise ValueError(f"{thr.size} rmsd_thr values for {S} ensembles")
+    # one (T, 4) array of quadruplets (or a list of 4-tuples) and one set-up dict stand for all ensembles, as in the stages' own calls
+    if quadruplets is not None and (np.ndim(quadruplets) == 2 if isinstance(quadruplets, np.ndarray)
+                                    else len(quadruplets) > 0 and quadruplets[0] is not None and np.ndim(quadruplets[0]) == 1):
+        quadruplets = [quadruplets] * S
+    if isinstance(rot_corr, dict):
+        rot_corr = [rot_corr] * S
+    quads = [None] * S if quadruplets is None else list(quadruplets)
+    setups = [None] * S if rot_corr is None else list(rot_corr)
+    if len(quads) != S or len(setups) != S:
+        raise ValueError(f"{len(quads)} quadruplet arrays and {len(setups)} rot-corr set-ups for {S} ensembles")
+    quads = [None if q is None else np.asarray(q, dtype=np.int32).reshape(-1, 4) for q in quads]
+    for s, (e, q) in enumerate(zip(ens, quads)):
+        if q is not None and len(q) and (q.min() < 0 or q.max() >= e.shape[1]):
+            raise ValueError(f"ensemble {s}: quadruplet atom index out of range")
+    given = [s for s in range(S) if setups[s] is not None]
+    _rot_corr_batch_args([ens[s][:0] for s in given], [nos[s] for s in given], [setups[s] for s in given], 0.0)     # (ValueError here, not mid-way)
+    if S == 0:
+        return []
+    cur = list(ens)
+    rows = [np.arange(len(e)) for e in ens]             # the input rows still alive
+
+    def stage(which, call):
+        if which:
+            for s, (kept, mask) in zip(which, call(which)):
+                cur[s], rows[s] = kept, rows[s][mask]
+
+    if tfd:
+        stage([s for s in range(S) if quads[s] is not None and len(quads[s])],
+              lambda w: prune_conformers_tfd_batch([cur[s] for s in w], [quads[s] for s in w]))
+    if moi:
+        stage([s for s in range(S) if len(cur[s]) <= 500],
+              lambda w: prune_by_moment_of_inertia_batch([cur[s] for s in w], [nos[s] for s in w], masses=None if masses is None else [ms[s] for s in w]))
+    if rmsd:
+        stage([s for s in range(S) if len(cur[s]) <= 1e5],
+              lambda w: prune_conformers_rmsd_batch([cur[s] for s in w], [nos[s] for s in w], rmsd_thr=thr[w]))
+        stage([s for s in range(S) if len(cur[s]) <= 1e5 and len(cur[s]) <= 500 and setups[s] is not None],
+              lambda w: prune_rmsd_rot_corr_arrays_batch([cur[s] for s in w], [nos[s] for s in w], [setups[s] for s in w], max_rmsd=thr[w]))
+    out = []
+    for s in range(S):
+        mask = np.zeros(len(ens[s]), dtype=bool)
+        mask[rows[s]] = True
+        out.append((cur[s], mask))
+    return out
 
 
 def _score_embed_poses(structures, constrained_indices, constrained_distances):

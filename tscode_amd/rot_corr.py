@@ -16,13 +16,17 @@ import numpy as np
 from . import _lib
 from ._lib import check, ptr
 from .engine import get_engine
-from .numba_functions import TFD_KS, _pass_schedule
+from .numba_functions import TFD_KS, _pass_schedule, _tfd_schedule_batch
 
-__all__ = ["prune_rmsd_rot_corr_arrays", "prune_conformers_rmsd_rot_corr", "rot_corr_pairs", "last_rot_corr_stats"]
+__all__ = ["prune_rmsd_rot_corr_arrays", "prune_conformers_rmsd_rot_corr", "rot_corr_pairs", "last_rot_corr_stats",
+           "prune_rmsd_rot_corr_arrays_batch", "last_rot_corr_batch_stats"]
 
 MAX_TORSIONS, MAX_ATOMS, MAX_ANGLES = 16, 512, 6      # csrc/rot_corr.hpp: RC_MAX_TORS, RC_MAX_ATOMS, RC_MAX_ANGLES
 
+ROT_CORR_BATCH_BYTES = 1 << 30          # coordinates plus cache bitmaps (N_s^2 / 8 bytes) one batch upload may hold; a longer list goes in slices
+
 _last_stats = []
+_last_batch_stats = []
 
 
 def last_rot_corr_stats():
@@ -146,6 +150,195 @@ def prune_rmsd_rot_corr_arrays(structures, atomnos, torsions, angles, move_masks
         run.close()
     _last_stats[:] = [stats[int(k)] for k in TFD_KS]
     return structures[final_mask], final_mask
+
+
+# ---- the same for many ensembles per call --------------------------------------------------------------------------------------
+def last_rot_corr_batch_stats():
+    """Per ensemble of the latest prune_rmsd_rot_corr_arrays_batch call what last_rot_corr_stats() reports after the single call on
+    it: one dict per schedule slot.  An ensemble that took no part in the launch (no torsion, more than ``max_structures``
+    structures, fewer than two) has an empty list."""
+    return [list(s) for s in _last_batch_stats]
+
+
+class _BatchRun:
+    """One tsc_rot_corr_batch run: the structures of every segment live on the device, turned in place by the slots."""
+
+    def __init__(self, engine, ensembles, setups):
+        self.e = engine
+        S = len(ensembles)
+        self.n_structs = np.array([len(e) for e in ensembles], dtype=np.int32)
+        self.n_atoms = np.array([e.shape[1] for e in ensembles], dtype=np.int32)
+        self.offsets = np.concatenate(([0], np.cumsum(self.n_structs.astype(np.int64) * self.n_atoms * 3))).astype(np.int64)
+        self.total_rows = int(self.n_structs.sum())
+        self.coords = np.ascontiguousarray(np.concatenate([e.ravel() for e in ensembles]), dtype=np.float64)
+
+        def cat(name, dtype):
+            return np.ascontiguousarray(np.concatenate([np.asarray(getattr(st, name)).ravel() for st in setups]), dtype=dtype)
+        self.arrays = (cat("heavy", np.int32), np.array([len(st.heavy) for st in setups], dtype=np.int32), cat("tors", np.int32),
+                       np.array([st.T for st in setups], dtype=np.int32), cat("angles", np.float64), cat("n_angles", np.int32),
+                       cat("masks", np.uint8), cat("sub_ptr", np.int32), cat("sub_idx", np.int32))
+        h = C.c_void_p()
+        check(engine.lib.tsc_rot_corr_batch_begin(engine._h, ptr(self.coords), ptr(self.offsets), ptr(self.n_structs), ptr(self.n_atoms),
+                                                  *[ptr(a) for a in self.arrays], C.c_int64(S), C.byref(h)))
+        self._r = h
+        engine._runs.add(self)
+
+    def run_slot(self, open_segs, d, k, num_active, max_rmsd):
+        """(first i32[total rows]: indices inside each segment, pairs evaluated i64[open segments])"""
+        open_segs = np.ascontiguousarray(open_segs, dtype=np.int32)
+        d = np.ascontiguousarray(d, dtype=np.int64)
+        num_active = np.ascontiguousarray(num_active, dtype=np.int64)
+        max_rmsd = np.ascontiguousarray(max_rmsd, dtype=np.float64)
+        first = np.empty(self.total_rows, dtype=np.int32)
+        ev = np.zeros(len(open_segs), dtype=np.int64)
+        check(self.e.lib.tsc_rot_corr_batch_pass(self._r, ptr(open_segs), ptr(d), C.c_int64(int(k)), ptr(num_active), ptr(max_rmsd),
+                                                 C.c_int64(len(open_segs)), ptr(first), ptr(ev)))
+        return first, ev
+
+    def end(self):
+        out = np.empty_like(self.coords)
+        check(self.e.lib.tsc_rot_corr_batch_end(self._r, ptr(out)))
+        return [out[self.offsets[s]:self.offsets[s + 1]].reshape(int(self.n_structs[s]), int(self.n_atoms[s]), 3) for s in range(len(self.n_structs))]
+
+    def close(self):
+        if getattr(self, "_r", None):
+            if getattr(self.e, "_h", None):      # (a closed engine has destroyed its runs already)
+                self.e.lib.tsc_rot_corr_batch_destroy(self._r)
+            self._r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _batch_setup(s, n_atoms, atomnos, setup):
+    """The _Setup of ensemble s, with everything the library would refuse refused here."""
+    if not isinstance(setup, dict) or not {"torsions", "angles", "move_masks", "sub_nodes"} <= set(setup):
+        raise ValueError(f"ensemble {s}: a set-up is a dict with the keys torsions, angles, move_masks, sub_nodes")
+    try:
+        st = _Setup(n_atoms, atomnos, setup["torsions"], setup["angles"], setup["move_masks"], setup["sub_nodes"])
+    except ValueError as exc:
+        raise ValueError(f"ensemble {s}: {exc}") from None
+    if st.T == 0:
+        return st
+    if len(st.heavy) == 0:
+        raise ValueError(f"ensemble {s}: no heavy atom")
+    if st.tors.min() < 0 or st.tors.max() >= n_atoms:
+        raise ValueError(f"ensemble {s}: torsion atom index out of range")
+    if (np.diff(st.sub_ptr) <= 0).any() or (np.diff(st.sub_ptr) > n_atoms).any():
+        raise ValueError(f"ensemble {s}: a local subgraph is empty or has more than {n_atoms} atoms")
+    if st.sub_idx.min() < 0 or st.sub_idx.max() >= n_atoms:
+        raise ValueError(f"ensemble {s}: subgraph atom index out of range")
+    if not np.isfinite(st.angles).all():
+        raise ValueError(f"ensemble {s}: angle not finite")
+    return st
+
+
+def _rot_corr_batch_args(ensembles, atomnos, setups, max_rmsd):
+    """The checked arguments of prune_rmsd_rot_corr_arrays_batch: ([f64[N_s, n_s, 3]], [_Setup], f64[S], the atomnos and
+    the set-up dict of every ensemble as given); ValueError otherwise."""
+    if isinstance(ensembles, np.ndarray) and ensembles.ndim != 4:
+        raise ValueError("ensembles must be a list of (N, n_atoms, 3) arrays")
+    ens = [np.asarray(e, dtype=np.float64) for e in ensembles]
+    S = len(ens)
+    for s, e in enumerate(ens):
+        if e.ndim != 3 or e.shape[2] != 3 or e.shape[1] < 1:
+            raise ValueError(f"ensemble {s}: structures must be (N, n_atoms, 3)")
+    one_for_all = np.ndim(atomnos) == 1 if isinstance(atomnos, np.ndarray) else (len(atomnos) == 0 or np.ndim(atomnos[0]) == 0)
+    if one_for_all:
+        atomnos = [atomnos] * S
+    if len(atomnos) != S:
+        raise ValueError(f"{len(atomnos)} atomnos arrays for {S} ensembles")
+    if isinstance(setups, dict):
+        setups = [setups] * S
+    if len(setups) != S:
+        raise ValueError(f"{len(setups)} set-ups for {S} ensembles")
+    th = np.asarray(max_rmsd, dtype=np.float64)
+    if th.ndim == 0:
+        th = np.full(S, float(th))
+    if th.shape != (S,):
+        raise ValueError(f"{th.size} max_rmsd values for {S} ensembles")
+    if not np.isfinite(th).all():
+        raise ValueError("max_rmsd not finite")
+    return ens, [_batch_setup(s, e.shape[1], a, st) for s, (e, a, st) in enumerate(zip(ens, atomnos, setups))], np.ascontiguousarray(th), atomnos, setups
+
+
+def _rot_corr_batch_upload(ens, setups, th, verbose=False):
+    """One upload: the schedule of every segment in lockstep (_tfd_schedule_batch), one launch per slot.  Returns
+    ([turned structures], [mask], [stats])."""
+    sizes = np.array([len(e) for e in ens], dtype=np.int64)
+    stats = [{int(k): {"k": k, "n_active": None, "ran": False, "pairs_evaluated": 0} for k in TFD_KS} for _ in ens]
+    run = _BatchRun(get_engine(), ens, setups)
+    try:
+        def pair_search(open_segs, d, k, num_active):
+            first, ev = run.run_slot(open_segs, d, k, num_active, th[open_segs])
+            for s, na, e in zip(open_segs.tolist(), num_active.tolist(), ev.tolist()):
+                stats[s][k].update(n_active=na, ran=True, pairs_evaluated=e)
+            return first
+
+        keep, off = _tfd_schedule_batch(sizes, pair_search, verbose)
+        turned = run.end()
+    finally:
+        run.close()
+    for st in stats:                     # the gate's count of a slot that did not run: no pass lies between it and the next one that did
+        seen = None
+        for k in reversed(TFD_KS):
+            if st[int(k)]["ran"]:
+                seen = st[int(k)]["n_active"]
+            else:
+                st[int(k)]["n_active"] = seen
+    return turned, [keep[off[s]:off[s + 1]] for s in range(len(ens))], [[st[int(k)] for k in TFD_KS] for st in stats]
+
+
+def prune_rmsd_rot_corr_arrays_batch(ensembles, atomnos, setups, max_rmsd=0.25, max_structures=750, verbose=False):
+    """prune_rmsd_rot_corr_arrays (tscode/torsion_module.py:1013-1161) for many ensembles per call: ``[(centred_s[mask_s], mask_s)]``,
+    each entry exactly what ``prune_rmsd_rot_corr_arrays(ensembles[s], atomnos_s, **setups_s, max_rmsd=max_rmsd_s)`` returns.
+
+    ``ensembles`` is a list of f64[N_s, n_s, 3] (every ensemble may be another molecule); ``atomnos`` one array for all or one per
+    ensemble; ``setups`` one dict for all or one per ensemble with the keys ``torsions``, ``angles``, ``move_masks``, ``sub_nodes``
+    as prune_rmsd_rot_corr_arrays takes them; ``max_rmsd`` a scalar or one value per ensemble.  The schedule's slots are walked in
+    lockstep (_tfd_schedule_batch, the schedule :1076-1152 shares with the TFD prune): per slot ONE launch serves every chunk of
+    every ensemble whose gate is open in it, one workgroup per chunk -- the same per-chunk device code as the single call's kernel
+    (csrc/rot_corr.hpp) -- and one graph step.  An ensemble with no torsion, more than ``max_structures`` structures (:1056) or
+    fewer than two takes no part and comes back centred with a full mask.  A list whose coordinates and cache bitmaps exceed
+    ``ROT_CORR_BATCH_BYTES`` goes in slices; a list of one goes to prune_rmsd_rot_corr_arrays.  last_rot_corr_batch_stats() has
+    the slots of every ensemble."""
+    ens, sts, th, raw_atomnos, raw_setups = _rot_corr_batch_args(ensembles, atomnos, setups, max_rmsd)
+    S = len(ens)
+    if S == 0:
+        _last_batch_stats[:] = []
+        return []
+    takes_part = [st.T > 0 and len(e) >= 2 and (max_structures is None or len(e) <= max_structures) for e, st in zip(ens, sts)]
+    if S == 1 and not takes_part[0]:
+        _last_batch_stats[:] = [[]]
+        return [(_centred(ens[0]), np.ones(len(ens[0]), dtype=bool))]
+    if S == 1:
+        out = prune_rmsd_rot_corr_arrays(ens[0], raw_atomnos[0], **{key: raw_setups[0][key] for key in ("torsions", "angles", "move_masks", "sub_nodes")},
+                                         max_rmsd=float(th[0]), max_structures=max_structures, verbose=verbose)
+        _last_batch_stats[:] = [last_rot_corr_stats()]
+        return [out]
+    centred = [_centred(e) for e in ens]
+    masks = [np.ones(len(e), dtype=bool) for e in ens]
+    stats = [[] for _ in ens]
+    idx = [s for s in range(S) if takes_part[s]]
+    at = 0
+    while at < len(idx):
+        end, nbytes = at, 0
+        while end < len(idx):
+            cost = centred[idx[end]].nbytes + (len(centred[idx[end]]) ** 2 + 7) // 8
+            if end > at and nbytes + cost > ROT_CORR_BATCH_BYTES:
+                break
+            nbytes += cost
+            end += 1
+        part = idx[at:end]
+        turned, part_masks, part_stats = _rot_corr_batch_upload([centred[s] for s in part], [sts[s] for s in part], th[part], verbose)
+        for s, x, m, st in zip(part, turned, part_masks, part_stats):
+            centred[s], masks[s], stats[s] = x, m, st
+        at = end
+    _last_batch_stats[:] = stats
+    return [(x[m], m) for x, m in zip(centred, masks)]
 
 
 def rot_corr_pairs(structures, atomnos, torsions, angles, move_masks, sub_nodes, pairs):
