@@ -14,7 +14,7 @@ import weakref
 
 import numpy as np
 
-from . import _lib
+from . import _lib, segments
 from ._lib import BatchPassStats, PassStats, TSC_MAX_PASSES, check, ptr
 
 __all__ = ["Engine", "FragmentSet", "get_engine", "device_count"]
@@ -70,18 +70,11 @@ _BATCH_STAT_FIELDS = tuple(f for f, _ in BatchPassStats._fields_)
 def pack_heavy_batch(heavies):
     """The arrays tsc_prune_rmsd_batch takes for a sequence of heavy-atom arrays f64[N_s, h_s, 3]: (flat, offsets, n, h) -- the arrays
     back to back, offsets i64[S + 1] in doubles, n i32[S] structures and h i32[S] heavy atoms per ensemble.  No device is touched."""
-    arrays = []
-    for s, a in enumerate(heavies):
-        a = np.ascontiguousarray(a, dtype=np.float64)
+    arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in heavies]
+    for s, a in enumerate(arrays):
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError(f"ensemble {s}: heavy must be (N, h, 3), got {a.shape}")
-        arrays.append(a)
-    n = np.array([a.shape[0] for a in arrays], dtype=np.int32)
-    h = np.array([a.shape[1] for a in arrays], dtype=np.int32)
-    offsets = np.zeros(len(arrays) + 1, dtype=np.int64)
-    np.cumsum(n.astype(np.int64) * h * 3, out=offsets[1:])
-    flat = np.concatenate([a.ravel() for a in arrays]) if arrays else np.zeros(0)
-    return flat, offsets, n, h
+    return segments.pack(arrays)[:4]
 
 
 class PipelineResult:
@@ -381,16 +374,12 @@ class Engine:
                 raise ValueError("structures must be (N, n_atoms, 3) and masses (n_atoms,)")
         if not ensembles:
             return []
-        n_structs = np.array([len(e) for e in ensembles], dtype=np.int32)
-        n_atoms = np.array([e.shape[1] for e in ensembles], dtype=np.int32)
-        offsets = np.concatenate(([0], np.cumsum(n_structs.astype(np.int64) * n_atoms * 3))).astype(np.int64)
-        rows = np.concatenate(([0], np.cumsum(n_structs.astype(np.int64))))
-        coords = np.concatenate([e.ravel() for e in ensembles])
+        p = segments.pack(ensembles)
         all_masses = np.concatenate(masses)
-        out = np.empty((int(rows[-1]), 3))
-        check(self.lib.tsc_inertia_moments_batch(self._h, ptr(coords), ptr(offsets), ptr(n_structs), ptr(n_atoms), ptr(all_masses),
+        out = np.empty((int(p.row_off[-1]), 3))
+        check(self.lib.tsc_inertia_moments_batch(self._h, ptr(p.flat), ptr(p.offsets), ptr(p.n_structs), ptr(p.n_atoms), ptr(all_masses),
                                                  C.c_int64(len(ensembles)), ptr(out)))
-        return [out[rows[s]:rows[s + 1]] for s in range(len(ensembles))]
+        return p.cut(out)
 
     def moi_first_similar_batch(self, moments, max_deviation):
         """moi_first_similar of every segment ([f64[N_s, 3]], one max_deviation each) in one launch: [i32[N_s]], indices inside the segment."""
@@ -400,7 +389,7 @@ class Engine:
             raise ValueError(f"{dev.size} max_deviation values for {len(moments)} segments")
         if not moments:
             return []
-        n_structs = np.array([len(m) for m in moments], dtype=np.int32)
+        n_structs = np.array([len(m) for m in moments], dtype=np.int32)      # (rows only: nothing here is (N, n, 3), so no segments.pack)
         rows = np.concatenate(([0], np.cumsum(n_structs.astype(np.int64))))
         all_moments = np.concatenate(moments)
         first = np.full(int(rows[-1]), -1, dtype=np.int32)
@@ -856,20 +845,19 @@ class Engine:
         max_n = self.prune_batch_max_n
         small = [s for s in range(S) if heavies[s].shape[0] <= max_n]
         if small:
-            flat, offsets, n, h = pack_heavy_batch([heavies[s] for s in small])
+            packed = segments.pack([heavies[s] for s in small])
             B = len(small)
-            mask = np.zeros(int(n.sum()), dtype=np.uint8)
+            mask = np.zeros(int(packed.row_off[-1]), dtype=np.uint8)
             st = (BatchPassStats * (B * TSC_MAX_PASSES))()
             np_ = np.zeros(B, dtype=np.int32)
             nf = np.zeros(B, dtype=np.uint8)
             t = np.ascontiguousarray(thr[small])
-            check(self.lib.tsc_prune_rmsd_batch(self._h, ptr(flat), offsets.ctypes.data_as(_lib.c_i64p), n.ctypes.data_as(_lib.c_i32p),
-                                                h.ctypes.data_as(_lib.c_i32p), t.ctypes.data_as(_lib.c_f64p), C.c_int64(B), C.c_int(int(mode)),
+            check(self.lib.tsc_prune_rmsd_batch(self._h, ptr(packed.flat), packed.offsets.ctypes.data_as(_lib.c_i64p), packed.n_structs.ctypes.data_as(_lib.c_i32p),
+                                                packed.n_atoms.ctypes.data_as(_lib.c_i32p), t.ctypes.data_as(_lib.c_f64p), C.c_int64(B), C.c_int(int(mode)),
                                                 ptr(mask), st, np_.ctypes.data_as(_lib.c_i32p), nf.ctypes.data_as(_lib.c_u8p)))
             table = np.frombuffer(st, dtype=np.int64).reshape(B, TSC_MAX_PASSES, len(_BATCH_STAT_FIELDS))
-            ends = np.cumsum(n, dtype=np.int64)
-            for b, s in enumerate(small):
-                masks[s] = mask[ends[b] - n[b]:ends[b]].astype(bool)
+            for b, (s, m) in enumerate(zip(small, packed.cut(mask))):
+                masks[s] = m.astype(bool)
                 stats[s] = [dict(zip(_BATCH_STAT_FIELDS, map(int, row))) for row in table[b, :np_[b]]]
                 nonfinite[s] = bool(nf[b])
         for s in range(S):

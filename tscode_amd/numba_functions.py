@@ -5,6 +5,7 @@ from __future__ import annotations
 import numpy as np
 
 from .engine import get_engine
+from .segments import byte_slices, ensemble_list, one_or_each, pack, scalar_or_each
 
 __all__ = ["compenetration_check", "count_clashes", "compenetration_mask", "prune_conformers_tfd", "prune_conformers_tfd_batch",
            "_get_tf_mat", "get_torsion_fingerprint", "tfd_similarity"]
@@ -326,53 +327,33 @@ def _tfd_schedule_batch(sizes, pair_search, verbose=False):
 
 def _tfd_batch_args(ensembles, quadruplets, thresh):
     """The checked arguments of prune_conformers_tfd_batch: ([f64[N_s, n_s, 3]], [i32[T_s, 4]], f64[S])."""
-    if isinstance(ensembles, np.ndarray) and ensembles.ndim != 4:
-        raise ValueError("ensembles must be a list of (N, n_atoms, 3) arrays")
-    ens = [np.ascontiguousarray(e, dtype=np.float64) for e in ensembles]
-    S = len(ens)
-    for s, e in enumerate(ens):
-        if e.ndim != 3 or e.shape[2] != 3 or e.shape[1] < 1:
-            raise ValueError(f"ensemble {s}: structures must be (N, n_atoms, 3)")
+    ens = ensemble_list(ensembles, np.float64)
     # one array of quadruplets for all (an array, or a list of 4-tuples), or one per ensemble (a list, or a stacked array)
-    one_for_all = np.ndim(quadruplets) <= 2 if isinstance(quadruplets, np.ndarray) else (len(quadruplets) == 0 or np.ndim(quadruplets[0]) <= 1)
-    if one_for_all:
-        quadruplets = [quadruplets] * S
-    if len(quadruplets) != S:
-        raise ValueError(f"{len(quadruplets)} quadruplet arrays for {S} ensembles")
-    quads = [np.ascontiguousarray(q, dtype=np.int32).reshape(-1, 4) for q in quadruplets]
+    quads = [np.ascontiguousarray(q, dtype=np.int32).reshape(-1, 4) for q in one_or_each(quadruplets, len(ens), "quadruplet arrays", 2)]
     for s, (e, q) in enumerate(zip(ens, quads)):
         if len(q) and (q.min() < 0 or q.max() >= e.shape[1]):
             raise ValueError(f"ensemble {s}: quadruplet atom index out of range")
-    th = np.asarray(thresh, dtype=np.float64)
-    if th.ndim == 0:
-        th = np.full(S, float(th))
-    if th.shape != (S,):
-        raise ValueError(f"{th.size} thresholds for {S} ensembles")
-    return ens, quads, np.ascontiguousarray(th)
+    return ens, quads, scalar_or_each(thresh, len(ens), "thresholds")
 
 
 def _tfd_batch_masks(ens, quads, th, verbose=False):
     """The masks of one upload: fingerprints of all segments in one launch, left on the device for every schedule slot."""
     eng = get_engine()
-    S = len(ens)
-    n_structs = np.array([len(e) for e in ens], dtype=np.int32)
-    n_atoms = np.array([e.shape[1] for e in ens], dtype=np.int32)
+    p = pack(ens)
     n_quads = np.array([len(q) for q in quads], dtype=np.int32)
-    sizes = n_structs.astype(np.int64)
-    offsets = np.concatenate(([0], np.cumsum(sizes * n_atoms * 3))).astype(np.int64)
-    coords = np.concatenate([e.ravel() for e in ens]) if S else np.zeros(0)
-    quads_all = np.ascontiguousarray(np.concatenate(quads)) if S else np.zeros((0, 4), dtype=np.int32)
+    sizes = p.n_structs.astype(np.int64)
+    quads_all = np.ascontiguousarray(np.concatenate(quads)) if ens else np.zeros((0, 4), dtype=np.int32)
     elem0 = np.concatenate(([0], np.cumsum(sizes * n_quads)))[:-1].astype(np.int64)
-    row0 = np.concatenate(([0], np.cumsum(sizes)))[:-1].astype(np.int64)
-    tf, tf_count = eng.tfd_batch_fingerprints_dev(coords, offsets, n_structs, n_atoms, quads_all, n_quads)
+    row0 = p.row_off[:-1]
+    tf, tf_count = eng.tfd_batch_fingerprints_dev(p.flat, p.offsets, p.n_structs, p.n_atoms, quads_all, n_quads)
     try:
         def pair_search(open_segs, d, k, num_active):
-            return eng.tfd_batch_pass_dev(tf, tf_count, elem0[open_segs], row0[open_segs], n_structs[open_segs], n_quads[open_segs], d,
-                                          np.full(len(open_segs), k, dtype=np.int64), num_active, th[open_segs], int(sizes.sum()))
-        keep, off = _tfd_schedule_batch(sizes, pair_search, verbose)
+            return eng.tfd_batch_pass_dev(tf, tf_count, elem0[open_segs], row0[open_segs], p.n_structs[open_segs], n_quads[open_segs], d,
+                                          np.full(len(open_segs), k, dtype=np.int64), num_active, th[open_segs], int(p.row_off[-1]))
+        keep, _ = _tfd_schedule_batch(sizes, pair_search, verbose)
     finally:
         eng.dev_free(tf)
-    return [keep[off[s]:off[s + 1]] for s in range(S)]
+    return p.cut(keep)
 
 
 def prune_conformers_tfd_batch(ensembles, quadruplets, thresh=10, verbose=False):
@@ -390,12 +371,7 @@ def prune_conformers_tfd_batch(ensembles, quadruplets, thresh=10, verbose=False)
         return []
     if S == 1:
         return [prune_conformers_tfd(ens[0], quads[0], float(th[0]), verbose)]
-    masks, at = [], 0
-    while at < S:
-        end, nbytes = at, 0
-        while end < S and (end == at or nbytes + ens[end].nbytes <= TFD_BATCH_BYTES):
-            nbytes += ens[end].nbytes
-            end += 1
+    masks = []
+    for at, end in byte_slices([e.nbytes for e in ens], TFD_BATCH_BYTES):
         masks += _tfd_batch_masks(ens[at:end], quads[at:end], th[at:end], verbose)
-        at = end
     return [(e[m], m) for e, m in zip(ens, masks)]

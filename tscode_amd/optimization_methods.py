@@ -10,6 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from .engine import get_engine
+from .segments import ensemble_list, one_or_each, scalar_or_each
 
 __all__ = ["get_inertia_moments", "get_moi_similarity_matches", "prune_by_moment_of_inertia", "prune_by_moment_of_inertia_batch",
            "similarity_refining_batch", "fitness_check", "fitness_mask", "_score_embed_poses"]
@@ -82,39 +83,18 @@ def prune_by_moment_of_inertia(structures, atomnos, max_deviation=1e-2, masses=N
 
 
 # ---- the same for many ensembles per call --------------------------------------------------------------------------------------
-def _per_ensemble(what, value, S, one_ndim):
-    """``value`` as a list of S entries: one array of ``one_ndim`` dimensions (or a flat sequence) stands for all ensembles."""
-    one_for_all = np.ndim(value) == one_ndim if isinstance(value, np.ndarray) else (len(value) == 0 or np.ndim(value[0]) == one_ndim - 1)
-    if one_for_all:
-        return [value] * S
-    if len(value) != S:
-        raise ValueError(f"{len(value)} {what} arrays for {S} ensembles")
-    return list(value)
-
-
-def _moi_batch_args(ensembles, atomnos, max_deviation, masses, need_heavy=True):
-    """The checked arguments of prune_by_moment_of_inertia_batch: ([structures_s], [atomnos_s], f64[S], [masses_s or None]).
+def _atom_arrays(ens, atomnos, masses, need_heavy):
+    """([atomnos_s], [masses_s or None]) of the ensembles ``ens``, each one array for all or one per ensemble, one entry per atom.
     ``need_heavy``: an ensemble without a heavy atom is refused (the moments are taken over the heavy atoms)."""
-    if isinstance(ensembles, np.ndarray) and ensembles.ndim != 4:
-        raise ValueError("ensembles must be a list of (N, n_atoms, 3) arrays")
-    ens = [np.asarray(e) for e in ensembles]
     S = len(ens)
-    for s, e in enumerate(ens):
-        if e.ndim != 3 or e.shape[2] != 3 or e.shape[1] < 1:
-            raise ValueError(f"ensemble {s}: structures must be (N, n_atoms, 3)")
-    nos = [np.asarray(a).reshape(-1) for a in _per_ensemble("atomnos", atomnos, S, 1)]
-    ms = [None] * S if masses is None else [np.asarray(m, dtype=np.float64).reshape(-1) for m in _per_ensemble("masses", masses, S, 1)]
+    nos = [np.asarray(a).reshape(-1) for a in one_or_each(atomnos, S, "atomnos arrays", 1, exact=True)]
+    ms = [None] * S if masses is None else [np.asarray(m, dtype=np.float64).reshape(-1) for m in one_or_each(masses, S, "masses arrays", 1, exact=True)]
     for s, (e, a, m) in enumerate(zip(ens, nos, ms)):
         if len(a) != e.shape[1] or (m is not None and len(m) != e.shape[1]):
             raise ValueError(f"ensemble {s}: atomnos and masses must have one entry per atom ({e.shape[1]})")
         if need_heavy and not (a != 1).any():
             raise ValueError(f"ensemble {s}: no heavy atom")
-    dev = np.asarray(max_deviation, dtype=np.float64)
-    if dev.ndim == 0:
-        dev = np.full(S, float(dev))
-    if dev.shape != (S,):
-        raise ValueError(f"{dev.size} max_deviation values for {S} ensembles")
-    return ens, nos, np.ascontiguousarray(dev), ms
+    return nos, ms
 
 
 def prune_by_moment_of_inertia_batch(ensembles, atomnos, max_deviation=1e-2, masses=None):
@@ -129,7 +109,9 @@ def prune_by_moment_of_inertia_batch(ensembles, atomnos, max_deviation=1e-2, mas
     ensemble.  The graph step (:341-358) stays on the host, per ensemble."""
     import networkx as nx
     from .numba_functions import _cluster_heads
-    ens, nos, dev, ms = _moi_batch_args(ensembles, atomnos, max_deviation, masses)
+    ens = ensemble_list(ensembles)
+    nos, ms = _atom_arrays(ens, atomnos, masses, need_heavy=True)
+    dev = scalar_or_each(max_deviation, len(ens), "max_deviation values")
     if not ens:
         return []
     heavy = [a != 1 for a in nos]
@@ -169,30 +151,22 @@ def similarity_refining_batch(ensembles, atomnos, quadruplets=None, rot_corr=Non
     ``mask`` undefined when the quadruplets are empty (:1333-1335); here an empty array simply skips the stage."""
     from .numba_functions import prune_conformers_tfd_batch
     from .rmsd_pruning import prune_conformers_rmsd_batch
-    from .rot_corr import _rot_corr_batch_args, prune_rmsd_rot_corr_arrays_batch
-    ens, nos, _, ms = _moi_batch_args(ensembles, atomnos, 0.0, masses, need_heavy=False)     # (each stage keeps its own rule on hydrogen-only ensembles)
+    from .rot_corr import _batch_setup, prune_rmsd_rot_corr_arrays_batch
+    ens = ensemble_list(ensembles)
+    nos, ms = _atom_arrays(ens, atomnos, masses, need_heavy=False)       # (each stage keeps its own rule on hydrogen-only ensembles)
     S = len(ens)
-    thr = np.asarray(rmsd_thr, dtype=np.float64)
-    if thr.ndim == 0:
-        thr = np.full(S, float(thr))
-    if thr.shape != (S,):
-        raise ValueError(f"{thr.size} rmsd_thr values for {S} ensembles")
+    thr = scalar_or_each(rmsd_thr, S, "rmsd_thr values")
     # one (T, 4) array of quadruplets (or a list of 4-tuples) and one set-up dict stand for all ensembles, as in the stages' own calls
-    if quadruplets is not None and (np.ndim(quadruplets) == 2 if isinstance(quadruplets, np.ndarray)
-                                    else len(quadruplets) > 0 and quadruplets[0] is not None and np.ndim(quadruplets[0]) == 1):
-        quadruplets = [quadruplets] * S
-    if isinstance(rot_corr, dict):
-        rot_corr = [rot_corr] * S
-    quads = [None] * S if quadruplets is None else list(quadruplets)
-    setups = [None] * S if rot_corr is None else list(rot_corr)
+    quads = one_or_each(quadruplets, S, "quadruplet arrays", 2, allow_none=True, exact=True, count=False)
+    setups = one_or_each(rot_corr, S, "rot-corr set-ups", None, allow_none=True, count=False)
     if len(quads) != S or len(setups) != S:
         raise ValueError(f"{len(quads)} quadruplet arrays and {len(setups)} rot-corr set-ups for {S} ensembles")
     quads = [None if q is None else np.asarray(q, dtype=np.int32).reshape(-1, 4) for q in quads]
     for s, (e, q) in enumerate(zip(ens, quads)):
         if q is not None and len(q) and (q.min() < 0 or q.max() >= e.shape[1]):
             raise ValueError(f"ensemble {s}: quadruplet atom index out of range")
-    given = [s for s in range(S) if setups[s] is not None]
-    _rot_corr_batch_args([ens[s][:0] for s in given], [nos[s] for s in given], [setups[s] for s in given], 0.0)     # (ValueError here, not mid-way)
+    for at, s in enumerate(s for s in range(S) if setups[s] is not None):
+        _batch_setup(at, ens[s].shape[1], nos[s], setups[s])         # (ValueError here, not mid-way; it counts the ensembles that have a set-up)
     if S == 0:
         return []
     cur = list(ens)

@@ -9,6 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from .engine import get_engine, pack_heavy_batch  # noqa: F401  (pack_heavy_batch: the arrays tsc_prune_rmsd_batch takes)
+from .segments import one_or_each, scalar_or_each
 
 __all__ = ["prune_conformers_rmsd", "prune_conformers_rmsd_batch", "rmsd_and_max_numba", "_rmsd_similarity", "last_prune_stats",
            "last_prune_batch_stats", "pack_heavy_batch"]
@@ -61,24 +62,10 @@ def last_prune_batch_stats():
 def _check_batch(ensembles, atomnos, rmsd_thr):
     """The arguments of prune_conformers_rmsd_batch as (structures, heavy indices, thresholds) per ensemble; raises before anything
     is uploaded."""
-    ensembles = [np.asarray(e) for e in ensembles]
+    ensembles = [np.asarray(e) for e in ensembles]       # (no ensemble_list: the shapes are checked below, together with atomnos)
     S = len(ensembles)
-    try:
-        one = np.asarray(atomnos)
-        shared = one.ndim == 1 and one.dtype != object       # one array of atomic numbers (a list of arrays has two axes, or is ragged)
-    except ValueError:
-        shared = False
-    if shared:
-        atomnos = [np.asarray(atomnos)] * S
-    else:
-        atomnos = [np.asarray(a) for a in atomnos]
-        if len(atomnos) != S:
-            raise ValueError(f"{len(atomnos)} atomnos arrays for {S} ensembles")
-    thr = np.asarray(rmsd_thr, dtype=np.float64)
-    if thr.ndim == 0:
-        thr = np.full(S, float(thr))
-    elif thr.shape != (S,):
-        raise ValueError(f"{thr.size} thresholds for {S} ensembles")
+    atomnos = [np.asarray(a) for a in one_or_each(atomnos, S, "atomnos arrays", 1, exact=True, object_rows=True)]
+    thr = scalar_or_each(rmsd_thr, S, "thresholds")
     heavy_idx = []
     for s, (e, a) in enumerate(zip(ensembles, atomnos)):
         if e.ndim != 3 or e.shape[2] != 3 or a.ndim != 1 or e.shape[1] != a.shape[0]:

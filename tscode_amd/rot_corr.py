@@ -17,6 +17,7 @@ from . import _lib
 from ._lib import check, ptr
 from .engine import get_engine
 from .numba_functions import TFD_KS, _pass_schedule, _tfd_schedule_batch
+from .segments import byte_slices, ensemble_list, one_or_each, pack, scalar_or_each
 
 __all__ = ["prune_rmsd_rot_corr_arrays", "prune_conformers_rmsd_rot_corr", "rot_corr_pairs", "last_rot_corr_stats",
            "prune_rmsd_rot_corr_arrays_batch", "last_rot_corr_batch_stats"]
@@ -165,12 +166,8 @@ class _BatchRun:
 
     def __init__(self, engine, ensembles, setups):
         self.e = engine
-        S = len(ensembles)
-        self.n_structs = np.array([len(e) for e in ensembles], dtype=np.int32)
-        self.n_atoms = np.array([e.shape[1] for e in ensembles], dtype=np.int32)
-        self.offsets = np.concatenate(([0], np.cumsum(self.n_structs.astype(np.int64) * self.n_atoms * 3))).astype(np.int64)
-        self.total_rows = int(self.n_structs.sum())
-        self.coords = np.ascontiguousarray(np.concatenate([e.ravel() for e in ensembles]), dtype=np.float64)
+        self.packed = pack([np.ascontiguousarray(e, dtype=np.float64) for e in ensembles])
+        self.total_rows = int(self.packed.row_off[-1])
 
         def cat(name, dtype):
             return np.ascontiguousarray(np.concatenate([np.asarray(getattr(st, name)).ravel() for st in setups]), dtype=dtype)
@@ -178,8 +175,8 @@ class _BatchRun:
                        np.array([st.T for st in setups], dtype=np.int32), cat("angles", np.float64), cat("n_angles", np.int32),
                        cat("masks", np.uint8), cat("sub_ptr", np.int32), cat("sub_idx", np.int32))
         h = C.c_void_p()
-        check(engine.lib.tsc_rot_corr_batch_begin(engine._h, ptr(self.coords), ptr(self.offsets), ptr(self.n_structs), ptr(self.n_atoms),
-                                                  *[ptr(a) for a in self.arrays], C.c_int64(S), C.byref(h)))
+        check(engine.lib.tsc_rot_corr_batch_begin(engine._h, *[ptr(a) for a in self.packed[:4]], *[ptr(a) for a in self.arrays],
+                                                  C.c_int64(len(ensembles)), C.byref(h)))
         self._r = h
         engine._runs.add(self)
 
@@ -196,9 +193,9 @@ class _BatchRun:
         return first, ev
 
     def end(self):
-        out = np.empty_like(self.coords)
+        out = np.empty_like(self.packed.flat)
         check(self.e.lib.tsc_rot_corr_batch_end(self._r, ptr(out)))
-        return [out[self.offsets[s]:self.offsets[s + 1]].reshape(int(self.n_structs[s]), int(self.n_atoms[s]), 3) for s in range(len(self.n_structs))]
+        return self.packed.cut(out, doubles=True)
 
     def close(self):
         if getattr(self, "_r", None):
@@ -239,30 +236,14 @@ def _batch_setup(s, n_atoms, atomnos, setup):
 def _rot_corr_batch_args(ensembles, atomnos, setups, max_rmsd):
     """The checked arguments of prune_rmsd_rot_corr_arrays_batch: ([f64[N_s, n_s, 3]], [_Setup], f64[S], the atomnos and
     the set-up dict of every ensemble as given); ValueError otherwise."""
-    if isinstance(ensembles, np.ndarray) and ensembles.ndim != 4:
-        raise ValueError("ensembles must be a list of (N, n_atoms, 3) arrays")
-    ens = [np.asarray(e, dtype=np.float64) for e in ensembles]
+    ens = ensemble_list(ensembles, np.float64)
     S = len(ens)
-    for s, e in enumerate(ens):
-        if e.ndim != 3 or e.shape[2] != 3 or e.shape[1] < 1:
-            raise ValueError(f"ensemble {s}: structures must be (N, n_atoms, 3)")
-    one_for_all = np.ndim(atomnos) == 1 if isinstance(atomnos, np.ndarray) else (len(atomnos) == 0 or np.ndim(atomnos[0]) == 0)
-    if one_for_all:
-        atomnos = [atomnos] * S
-    if len(atomnos) != S:
-        raise ValueError(f"{len(atomnos)} atomnos arrays for {S} ensembles")
-    if isinstance(setups, dict):
-        setups = [setups] * S
-    if len(setups) != S:
-        raise ValueError(f"{len(setups)} set-ups for {S} ensembles")
-    th = np.asarray(max_rmsd, dtype=np.float64)
-    if th.ndim == 0:
-        th = np.full(S, float(th))
-    if th.shape != (S,):
-        raise ValueError(f"{th.size} max_rmsd values for {S} ensembles")
+    atomnos = one_or_each(atomnos, S, "atomnos arrays", 1, exact=True)
+    setups = one_or_each(setups, S, "set-ups", None)
+    th = scalar_or_each(max_rmsd, S, "max_rmsd values")
     if not np.isfinite(th).all():
         raise ValueError("max_rmsd not finite")
-    return ens, [_batch_setup(s, e.shape[1], a, st) for s, (e, a, st) in enumerate(zip(ens, atomnos, setups))], np.ascontiguousarray(th), atomnos, setups
+    return ens, [_batch_setup(s, e.shape[1], a, st) for s, (e, a, st) in enumerate(zip(ens, atomnos, setups))], th, atomnos, setups
 
 
 def _rot_corr_batch_upload(ens, setups, th, verbose=False):
@@ -323,20 +304,11 @@ def prune_rmsd_rot_corr_arrays_batch(ensembles, atomnos, setups, max_rmsd=0.25, 
     masks = [np.ones(len(e), dtype=bool) for e in ens]
     stats = [[] for _ in ens]
     idx = [s for s in range(S) if takes_part[s]]
-    at = 0
-    while at < len(idx):
-        end, nbytes = at, 0
-        while end < len(idx):
-            cost = centred[idx[end]].nbytes + (len(centred[idx[end]]) ** 2 + 7) // 8
-            if end > at and nbytes + cost > ROT_CORR_BATCH_BYTES:
-                break
-            nbytes += cost
-            end += 1
+    for at, end in byte_slices([centred[s].nbytes + (len(centred[s]) ** 2 + 7) // 8 for s in idx], ROT_CORR_BATCH_BYTES):
         part = idx[at:end]
         turned, part_masks, part_stats = _rot_corr_batch_upload([centred[s] for s in part], [sts[s] for s in part], th[part], verbose)
         for s, x, m, st in zip(part, turned, part_masks, part_stats):
             centred[s], masks[s], stats[s] = x, m, st
-        at = end
     _last_batch_stats[:] = stats
     return [(x[m], m) for x, m in zip(centred, masks)]
 

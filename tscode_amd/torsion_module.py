@@ -16,6 +16,7 @@ import numpy as np
 
 from .algebra import rot_mat_from_pointer
 from .engine import get_engine
+from .segments import byte_slices, one_or_each, pack
 
 __all__ = ["rotate_dihedral", "rotate_dihedral_batch", "torsion_comp_check", "csearch_rotate", "csearch_candidates",
            "csearch_rotate_multi", "csearch_candidates_multi", "clustered_csearch_step", "most_diverse_conformers", "diverse_select",
@@ -382,15 +383,6 @@ def most_diverse_conformers(n, structures, torsion_array, energies=None, interac
 DIVERSE_BATCH_BYTES = 1 << 30           # device bytes one tsc_diverse_select_batch call may fill with structures (input, aligned, centred)
 
 
-def _per_segment(value, S, what):
-    """``value`` for every segment: a list of S entries as it is, None as S times None."""
-    if value is None:
-        return [None] * S
-    if len(value) != S:
-        raise ValueError(f"{len(value)} {what} for {S} ensembles")
-    return list(value)
-
-
 def _diverse_batch_args(ensembles, k, init_rows, seeds, energies):
     """The checked arguments of diverse_select_batch, per segment: (structures, k, rows or None, uniforms or None, energies or None)."""
     from .hypermolecule_class import _check_structures
@@ -398,8 +390,9 @@ def _diverse_batch_args(ensembles, k, init_rows, seeds, energies):
 
     ens = [np.ascontiguousarray(e, dtype=np.float64) for e in ensembles]
     S = len(ens)
-    ks = [int(k)] * S if np.ndim(k) == 0 else [int(v) for v in _per_segment(k, S, "cluster counts")]
-    init_rows, seeds, energies = (_per_segment(v, S, w) for v, w in ((init_rows, "init_rows entries"), (seeds, "seeds"), (energies, "energies arrays")))
+    ks = [int(k)] * S if np.ndim(k) == 0 else [int(v) for v in one_or_each(k, S, "cluster counts", None)]
+    init_rows, seeds, energies = (one_or_each(v, S, w, None, allow_none=True)
+                                  for v, w in ((init_rows, "init_rows entries"), (seeds, "seeds"), (energies, "energies arrays")))
     segs = []
     for s in range(S):
         _check_structures(ens[s])
@@ -428,13 +421,9 @@ def _diverse_select_slice(segs, max_iter, tol):
 
     from ._lib import check, ptr
     S = len(segs)
-    n_structs = np.array([len(x) for x, *_ in segs], dtype=np.int32)
-    n_atoms = np.array([x.shape[1] for x, *_ in segs], dtype=np.int32)
+    p = pack([x for x, *_ in segs])
     ks = np.array([k for _, k, *_ in segs], dtype=np.int32)
-    offsets = np.concatenate(([0], np.cumsum(n_structs.astype(np.int64) * n_atoms * 3))).astype(np.int64)
-    row_off = np.concatenate(([0], np.cumsum(n_structs.astype(np.int64))))
-    k_off = np.concatenate(([0], np.cumsum(ks.astype(np.int64))))
-    structures = np.concatenate([x.ravel() for x, *_ in segs])
+    row_off, k_off = p.row_off, np.concatenate(([0], np.cumsum(ks.astype(np.int64))))
     rows = np.zeros(int(k_off[-1]), dtype=np.int32)
     u = np.zeros(int(k_off[-1]), dtype=np.float64)
     energies = np.zeros(int(row_off[-1]), dtype=np.float64)
@@ -448,16 +437,16 @@ def _diverse_select_slice(segs, max_iter, tol):
         if e is not None:
             energies[row_off[s]:row_off[s + 1]] = e
             flags[s] |= 1
-    aligned = np.empty_like(structures)
+    aligned = np.empty_like(p.flat)
     labels = np.empty(int(row_off[-1]), dtype=np.int32)
     picked = np.empty(int(k_off[-1]), dtype=np.int32)
     n_iter = np.zeros(S, dtype=np.int32)
     eng = get_engine()
-    check(eng.lib.tsc_diverse_select_batch(eng._h, ptr(structures), ptr(offsets), ptr(n_structs), ptr(n_atoms), ptr(ks), C.c_int64(S), ptr(rows),
+    check(eng.lib.tsc_diverse_select_batch(eng._h, ptr(p.flat), ptr(p.offsets), ptr(p.n_structs), ptr(p.n_atoms), ptr(ks), C.c_int64(S), ptr(rows),
                                            ptr(u) if (flags & 2).any() else None, ptr(energies) if (flags & 1).any() else None, ptr(flags),
                                            C.c_int(int(max_iter)), C.c_double(float(tol)), ptr(aligned), ptr(labels), ptr(picked), ptr(n_iter)))
-    return [(aligned[offsets[s]:offsets[s + 1]].reshape(segs[s][0].shape), labels[row_off[s]:row_off[s + 1]], picked[k_off[s]:k_off[s + 1]],
-             rows[k_off[s]:k_off[s + 1]], int(n_iter[s])) for s in range(S)]
+    return [(a, lab, picked[k_off[s]:k_off[s + 1]], rows[k_off[s]:k_off[s + 1]], int(n_iter[s]))
+            for s, (a, lab) in enumerate(zip(p.cut(aligned, doubles=True), p.cut(labels)))]
 
 
 def diverse_select_batch(ensembles, k, init_rows=None, seeds=None, energies=None, max_iter=300, tol=1e-4):
@@ -472,16 +461,11 @@ def diverse_select_batch(ensembles, k, init_rows=None, seeds=None, energies=None
         x, ks, rows, _, e = segs[0]
         sd = None if seeds is None else seeds[0]
         return [diverse_select(x, ks, init_rows=rows, seed=sd, energies=e, max_iter=max_iter, tol=tol)]
-    out, at = [], 0
-    while at < len(segs):
-        end, nbytes = at, 0
-        while end < len(segs) and (end == at or nbytes + 3 * segs[end][0].nbytes <= DIVERSE_BATCH_BYTES):
-            nbytes += 3 * segs[end][0].nbytes
-            end += 1
+    out = []
+    for at, end in byte_slices([3 * x.nbytes for x, *_ in segs], DIVERSE_BATCH_BYTES):
         out += _diverse_select_slice(segs[at:end], max_iter, tol) if end - at > 1 else \
             [diverse_select(segs[at][0], segs[at][1], init_rows=segs[at][2], seed=None if seeds is None else seeds[at], energies=segs[at][4],
                             max_iter=max_iter, tol=tol)]
-        at = end
     return out
 
 
@@ -498,10 +482,10 @@ def most_diverse_conformers_batch(n, ensembles, torsion_arrays, energies=None, *
     from . import numba_functions
 
     S = len(ensembles)
-    ns = [int(n)] * S if np.ndim(n) == 0 else [int(v) for v in _per_segment(n, S, "n entries")]
-    energies, seeds, init_rows = (_per_segment(v, S, w) for v, w in ((energies, "energies arrays"), (seeds, "seeds"), (init_rows, "init_rows entries")))
-    one_for_all = np.ndim(torsion_arrays) <= 2 if isinstance(torsion_arrays, np.ndarray) else (len(torsion_arrays) == 0 or np.ndim(torsion_arrays[0]) <= 1)
-    torsion_arrays = [torsion_arrays] * S if one_for_all else _per_segment(torsion_arrays, S, "torsion arrays")
+    ns = [int(n)] * S if np.ndim(n) == 0 else [int(v) for v in one_or_each(n, S, "n entries", None)]
+    energies, seeds, init_rows = (one_or_each(v, S, w, None, allow_none=True)
+                                  for v, w in ((energies, "energies arrays"), (seeds, "seeds"), (init_rows, "init_rows entries")))
+    torsion_arrays = one_or_each(torsion_arrays, S, "torsion arrays", 2)
     out = [None] * S
     to_prune = [s for s in range(S) if len(ensembles[s]) > ns[s] and ns[s] <= 300]               # :859, :863
     pruned = dict(zip(to_prune, (p for p, _ in numba_functions.prune_conformers_tfd_batch([ensembles[s] for s in to_prune],
