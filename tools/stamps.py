@@ -7,7 +7,8 @@ and run   TSCODE_AMD_LIB=$PWD/tscode_amd/libtscode_hip_stamps.so python tools/st
 (a negative k stamps k_open_rows of that pass instead of the pair kernel)
 The kernel stamps the 100 MHz wall clock (after draining its outstanding memory operations: the stamps perturb it a little) at:
 0 wavefront started, 1 prologue data arrived, 2 screen done, 3 candidates evaluated, 4 arrived at the tile's counter, 5 tile applied,
-6 arrived at the pass's counter, 7 pass closed.  Printed: percentiles of every phase over the wavefronts that went through it, in us.
+6 arrived at the pass's counter, 7 pass closed (6 and 7 only in a pass that closes itself; one that is left open ends at 5).  A pass that
+runs whole in k_pass_chunks stamps 0 started, 1 chunk ranked and stop columns found, 3 pairs evaluated, 5 rows applied, 6 and 7 as above.  Printed: percentiles of every phase over the wavefronts that went through it, in us.
 """
 import ctypes as C
 import sys

@@ -46,6 +46,7 @@ struct LocalPassArgs {
     unsigned long long *exch;  // rank-partitioned pass (else null): removed rows are noted here and applied by k_pass_merge
     double thr, maxdev_thr, half_h_thr2, two_thr2, desc_limit;
     const unsigned *dmax_bits;
+    unsigned long long *dbg;   // -DTSC_DBG_STAMPS builds only: 8 time stamps per wavefront of the launch (tools/stamps.py), else null
 };
 
 struct LocalTickets {  // zeroed by k_init_run and again by the wavefront that closes a pass
@@ -66,7 +67,7 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
                                                              const unsigned long long *__restrict__ dbit, const double *__restrict__ heavy,
                                                              const double *__restrict__ Gall, const float *__restrict__ D,
                                                              CacheViews cv, PassCounters *__restrict__ cnt, int32_t *__restrict__ bsum, int block_items,
-                                                             StepCtx sc, StepArgs next, LocalTickets *__restrict__ tickets) {
+                                                             StepCtx sc, StepArgs next, LocalTickets *__restrict__ tickets, DeriveArgs dv) {
     __shared__ unsigned long long s_mb[LP_WORDS + 2], s_db[LP_WORDS + 2];
     __shared__ unsigned short s_wpre[LP_WORDS + 2];
     __shared__ unsigned short s_act[LP_MAX_ROWS], s_cend[LP_MAX_ROWS];
@@ -74,16 +75,31 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
     __shared__ unsigned short s_queue[LP_WAVES][LP_QCAP], s_exq[LP_WAVES][128];
     __shared__ __attribute__((aligned(16))) float s_rowdesc[LP_WAVES][LP_TI * DW];
     __shared__ unsigned long long s_stat[8];  // block totals of the five statistics
-    __shared__ int s_A, s_anydb, s_last;
+    __shared__ int s_A, s_anydb, s_last, s_open[2];
     static_assert(DW == 16 && LP_TI * DW == 256, "row staging: 4 rows x 16 components per 64 lanes");
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool pass_on = st->pass_on != 0;
+    TSC_STAMP(0);  // the wavefront has started
+    // the state block of this pass: written by whoever closed the pass before it, or -- that pass was left open (rmsd.hpp,
+    // pass_derive) -- worked out here by every workgroup for itself.  The scan blocks' counts are being decremented by this very
+    // launch: no prefix is derived from them here, the next kernel that opens a pass makes its own
+    int open_on, open_sel;
+    if (dv.prev_st) {
+        if (wid == 0) {
+            const Derived d = pass_derive(dv, st, blockIdx.x == 0, nullptr, 0, nullptr, nullptr);
+            if (lane == 0) s_open[0] = d.pass_on, s_open[1] = d.bitsel;
+        }
+        __syncthreads();
+        open_on = s_open[0], open_sel = s_open[1];
+    } else {
+        open_on = st->pass_on, open_sel = st->bitsel;
+    }
+    const bool pass_on = open_on != 0;
     // the pass reads one bit copy of the mask and clears the rows it removes in the other (every row of a pass sees the mask
     // as it was when the pass began, rmsd_pruning.py:151-157, whatever order the workgroups run in)
-    const unsigned long long *mbit = bits + size_t(st->bitsel) * bit_words;
-    unsigned long long *mbit_next = bits + size_t(st->bitsel ^ 1) * bit_words;
+    const unsigned long long *mbit = bits + size_t(open_sel) * bit_words;
+    unsigned long long *mbit_next = bits + size_t(open_sel ^ 1) * bit_words;
     // which chunk, and which share of its row tiles
     int c, j, nb;
     {
@@ -158,6 +174,7 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
             s_best[r] = INT_MAX;
         }
         __syncthreads();
+        TSC_STAMP(1);  // ranked, stop columns found
 
         // ---- 3. pairs: one wavefront per (16 rows) x (all their columns), 64 columns at a time
         const int h3 = a.h * 3;
@@ -305,6 +322,7 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
         }
         for (int off = 8; off > 0; off >>= 1) my_screened += __shfl_xor(my_screened, off);
         n_screened = (unsigned long long)my_screened;
+        TSC_STAMP(3);  // this wavefront's pairs evaluated
         __syncthreads();
 
         // ---- 4. apply this block's rows: mask, one cache key per removed row (:69-73), scan counts, evaluation count
@@ -356,9 +374,15 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
         if (tid < 5) count_add(cnt, blockIdx.x, tid, s_stat[tid]);
     }
 
-    // ---- 6. the last block closes this pass and opens the next (as k_apply_pass does); two-level ticket
+    // ---- 6. the last block closes this pass and opens the next (as k_apply_pass does); two-level ticket.  tickets = null: the pass
+    // is left open, the first kernel of the next one closes it behind the kernel boundary (pass_derive)
+    if (!tickets) {
+        TSC_STAMP(5);
+        return;
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    TSC_STAMP(5);  // this block's rows applied, its statistics added
     if (tid == 0) {
         int last = 0;
         const unsigned grp = blockIdx.x % LP_TICKET_GROUPS;
@@ -370,7 +394,11 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
         s_last = last;
     }
     __syncthreads();
-    if (s_last && tid < 64) pass_step_wave(sc, next);  // (zeroes the tickets as well)
+    TSC_STAMP(6);  // arrived at the pass's counter
+    if (s_last && tid < 64) {
+        pass_step_wave(sc, next);  // (zeroes the tickets as well)
+        TSC_STAMP(7);  // pass closed
+    }
 }
 
 }  // namespace tsc

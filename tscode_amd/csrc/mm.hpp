@@ -444,6 +444,10 @@ inline __global__ __launch_bounds__(64 * MM_WAVES, TSC_MM_OCC) void k_rmsd_sieve
             count_add(counters, unsigned(slot), CNT_EVALUATED, ev_total);
             count_add(counters, unsigned(slot), CNT_REMOVED, rm_total);
         }
+        if (!fa.tickets) {  // the pass is left open: the first kernel of the next one closes it behind the kernel boundary (rmsd.hpp, pass_derive)
+            TSC_STAMP(5);
+            return;
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         TSC_STAMP(5);
         const bool fin = last && tickets_arrive(fa.tickets, unsigned(4 * grp + lane), fa.n_tiles, PT_GROUPS);
@@ -739,6 +743,10 @@ inline __global__ __launch_bounds__(64 * MM16_WAVES, TSC_MM16_OCC) void k_rmsd_s
         if (lane == 0) {
             count_add(counters, unsigned(tile), CNT_EVALUATED, ev_total);
             count_add(counters, unsigned(tile), CNT_REMOVED, rm_total);
+        }
+        if (!fa.tickets) {  // the pass is left open: the first kernel of the next one closes it behind the kernel boundary (rmsd.hpp, pass_derive)
+            TSC_STAMP(5);
+            return;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         TSC_STAMP(5);

@@ -241,8 +241,9 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
     for (int slot = 0; slot < TSC_MAX_PASSES; ++slot) p->view_of_slot[slot] = (pass_can_run(n, slot) && mode == 0) ? p->n_views++ : -1;
     if (!rc) rc = palloc(p, std::max<size_t>(1, size_t(p->n_views) * (p->bit_words + p->dsum_words)), &p->views);
     if (!rc) rc = palloc(p, TSC_MAX_PASSES, &p->view_pass);
-    if (!rc) rc = palloc(p, 1, &p->counters);
-    if (!rc) rc = palloc(p, 1, &p->state);
+    if (!rc) rc = palloc(p, TSC_MAX_PASSES, &p->counters_all);
+    if (!rc) rc = palloc(p, TSC_MAX_PASSES, &p->state_all);
+    p->counters = p->counters_all, p->state = p->state_all;  // (pass_launch moves them to the slot of the pass in flight)
     if (!rc) rc = palloc(p, TSC_MAX_PASSES, &p->records);
     const bool own_desc = !(ext && ext->D);  // (external descriptors: already enqueued on this stream, the caller owns the buffers)
     if (!rc && p->algo == ALGO_SIEVE) {
@@ -290,7 +291,7 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
         ia.views = p->views, ia.view_words = int64_t(p->n_views) * int64_t(p->bit_words + p->dsum_words), ia.view_pass = p->view_pass, ia.n_views = p->n_views;
         for (int slot = 0; slot < TSC_MAX_PASSES; ++slot)
             if (p->view_of_slot[slot] >= 0) ia.sched[p->view_of_slot[slot]] = view_pass(int(n), int(KS[slot]));
-        ia.st = p->state, ia.rec = p->records, ia.n_rec = TSC_MAX_PASSES, ia.cnt = p->counters;
+        ia.st = p->state_all, ia.rec = p->records, ia.n_rec = TSC_MAX_PASSES, ia.cnt = p->counters_all;  // (every slot's)
         ia.bsum = p->bsum, ia.boff = p->boff, ia.n_blocks = p->n_blocks, ia.block_items = SCAN_TILE;
         ia.dmax_bits = own_desc ? p->dmax_bits : nullptr;
         // the arrival counters and the per-tile ones lie in two blocks: the tickets are zeroed here, tile_done by its own loop below
@@ -456,14 +457,13 @@ static int walked_pass(tsc_prune *p, int rank, int world, int64_t rows_ub, int64
     memset(&fa, 0, sizeof(fa));
     if (p->cur_fused) {
         fa.ap = apply_args(p);
-        fa.tile_done = p->tile_done, fa.tickets = &p->tickets->pass, fa.n_tiles = unsigned(w.n_tiles);
+        // a rank-partitioned pass is closed by the pair kernel's last tile (its statistics go to the exchange buffer); any other is left
+        // open -- no arrivals, no closing wavefront -- and closed behind the kernel boundary by the first kernel of the next pass
+        fa.tile_done = p->tile_done, fa.tickets = p->cur_range ? &p->tickets->pass : nullptr, fa.n_tiles = unsigned(w.n_tiles);
         fa.sc = step_ctx(p, p->cur_range);
         int nxt = -1;
         fa.next = next_step_args(p, &nxt);
-        if (!p->cur_range) {
-            p->opened_slot = nxt;
-            p->last_slot = -1;  // closed on the device, by the pair kernel's last tile
-        }
+        if (!p->cur_range) p->last_local = false;  // (last_slot stays this pass's: left open)
     }
     const bool trim = c->opt.sieve_cpl == 2 && c->opt.sieve_trim;
     if (form.mm16) {
@@ -494,19 +494,21 @@ static int local_pass(tsc_prune *p, const PassGeom &g, const PassRows &r, bool r
     a.nb_regular = l.nb_regular, a.nb_last = l.nb_last;
     a.c_lo = int(r.c_lo), a.n_reg = l.n_reg;
     a.exch = range ? p->exch : nullptr;
+    a.dbg = nullptr;
+#ifdef TSC_DBG_STAMPS
+    if (p->ctx->opt.dbg_stamp_k == p->cur_k) TSC_TRY(stamp_buffer(p->ctx, int64_t(l.blocks) * 4, &a.dbg));
+#endif
     put_screen_thresholds(p, a);
     int nxt = -1;
     const StepArgs sa = next_step_args(p, &nxt);
     // (its own events only at pass_timing 2: level 1 is what a timed region carries for the PAIR kernel's durations, and a pair of
     // events costs a small pass about 6 us)
     const PairEvents ev = pair_events(p, 2);
+    // (range: the last block leaves the statistics in the exchange buffer; otherwise the pass is left open, as in walked_pass)
     TSC_TRY(launch_pass_chunks(p->ctx->stream, unsigned(l.blocks), ev.e0, ev.e1, g, a, p->state, p->mask, p->bits, int(p->bit_words), view_of_open_pass(p), p->heavy,
                                (const double *)p->Gall, (const float *)p->Dall, later_views(p), p->counters, p->bsum, SCAN_TILE, step_ctx(p, range), sa,
-                               &p->tickets->local));
-    if (!range) {
-        p->opened_slot = nxt;
-        p->last_slot = -1;  // closed on the device
-    }
+                               range ? &p->tickets->local : nullptr, derive_args(p)));
+    if (!range) p->last_local = true;  // (last_slot stays this pass's: left open)
     return 0;
 }
 
@@ -518,10 +520,12 @@ static int open_rows(tsc_prune *p, const PassGeom &g, const PassShape &s, bool r
     hipStream_t st = c->stream;
     const OpenPlan o = plan_open_rows(s.rows_ub);
     OpenArgs oa;
-    oa.use_cache = (p->mode == 0), oa.fused = s.fused ? 1 : 0, oa.lds_cap = std::min(c->opt.open_lds_blocks, OPEN_LDS_BLOCKS);
+    // (fused: tiles without columns arrive at the pass's counter here -- only where the pair kernel's last tile closes the pass, walked_pass)
+    oa.use_cache = (p->mode == 0), oa.fused = (s.fused && range) ? 1 : 0, oa.lds_cap = std::min(c->opt.open_lds_blocks, OPEN_LDS_BLOCKS);
     oa.view = view_of_open_pass(p), oa.bits = p->bits, oa.bit_words = int(p->bit_words);
     oa.boff = p->boff, oa.n_blocks = p->n_blocks, oa.block_items = SCAN_TILE;
     oa.n_tiles = o.n_tiles, oa.tickets = &p->tickets->pass;
+    oa.dv = derive_args(p), oa.bsum = p->bsum, oa.boff_out = p->boff;
     oa.rank_of = s.culled ? p->rank_of : nullptr;
     oa.Dh = p->Dh, oa.dmax_bits = p->dmax_bits;
     oa.dbg = nullptr;
@@ -673,16 +677,27 @@ static int pass_launch(tsc_prune *p, int rank, int world, bool range) {
     for (int i = 0; i < 4; ++i)
         if (!p->ev[slot][i]) TSC_TRY(get_event(c, &p->ev[slot][i]));
     if (c->opt.pass_timing >= 2) TSC_HIP(hipEventRecord(p->ev[slot][0], st));
-    // 0. open this pass: gate (:192), counters, cache-view bitmap -- already done by the apply kernel of the pass before
-    //    it (its last block), by a one-block launch for the first pass of a run
+    p->state = p->state_all + slot, p->counters = p->counters_all + slot;
+    // 0. open this pass: gate (:192), record, state block of its slot -- already done by the kernel that closed the pass before it (its
+    //    last block; k_init_run for the first pass of a run), or the pass before it was left open: then the first kernel of this pass
+    //    closes it and opens this one in its first round trip (pass_derive) -- k_pass_chunks, or k_open_rows where the prefix of the scan
+    //    blocks fits its LDS array; a one-block launch where neither is the first kernel
+    p->derive_prev = false;
     if (p->opened_slot != slot) {
-        StepArgs sa{p->last_slot, slot, (long long)k, p->algo, -1};
-        hipLaunchKernelGGL(k_pass_step, dim3(1), dim3(64), 0, st, step_ctx(p), sa);
+        if (p->last_slot < 0) return fail(TSC_ERR_STATE, "prune pass k = %lld: no pass in front of it was left open and nothing has opened its slot", (long long)k);
+        if (!range && (s.local || p->n_blocks <= std::min(c->opt.open_lds_blocks, OPEN_LDS_BLOCKS))) {
+            p->derive_prev = true, p->derive_slot = p->last_slot, p->derive_local = p->last_local;
+        } else {
+            StepArgs sa{p->last_slot, slot, (long long)k, p->algo, p->last_local ? ALGO_LOCAL : -1};
+            hipLaunchKernelGGL(k_pass_step, dim3(1), dim3(64), 0, st, step_ctx_of(p, p->last_slot, slot), sa);
+        }
+        p->opened_slot = slot;
     }
     if (range && p->range_ready_slot != slot)  // no k_pass_merge in front of this pass (the first of a run): which rows are this rank's
         hipLaunchKernelGGL(k_range_open, dim3(1), dim3(64), 0, st, p->state, (const int32_t *)p->boff, (const unsigned long long *)p->bits, int(p->bit_words),
                            p->n_blocks, int(r.s_lo), int(r.s_hi));
     p->last_slot = slot;
+    p->last_local = false;
     p->slot_used[slot] = true;
     p->cur_local = s.local;
     p->cur_fused = false;
@@ -999,10 +1014,14 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_stats(tsc_prune 
     DeviceGuard guard(c->device);
     if (!p->collected) {
         hipStream_t st = c->stream;
-        if (p->last_slot >= 0) {
-            StepArgs sa{p->last_slot, -1, 0ll, 0, -1};
-            hipLaunchKernelGGL(k_pass_step, dim3(1), dim3(64), 0, st, step_ctx(p), sa);
+        if (p->last_slot >= 0) {  // the last pass was left open: close it, and open the one that follows where the run goes on
+            int nxt = -1;
+            for (int s = p->next_ks; s < TSC_MAX_PASSES && nxt < 0; ++s)
+                if (pass_can_run(p->n, s)) nxt = s;
+            StepArgs sa{p->last_slot, nxt, nxt >= 0 ? (long long)KS[nxt] : 0ll, p->algo, p->last_local ? ALGO_LOCAL : -1};
+            hipLaunchKernelGGL(k_pass_step, dim3(1), dim3(64), 0, st, step_ctx_of(p, p->last_slot, nxt), sa);
             p->last_slot = -1;
+            p->opened_slot = nxt;
         }
         static_assert(sizeof(PassRecord) * TSC_MAX_PASSES <= 4096 && sizeof(PassRecord) % 8 == 0, "records fit the pinned staging buffer");
         {

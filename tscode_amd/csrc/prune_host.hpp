@@ -70,15 +70,21 @@ struct tsc_prune {
     bool views_split = false;            // partitioned passes have run: the cache views of the remaining passes hold this rank's keys only
     uint8_t *export_mask_host = nullptr;  // set by prune_run: pinned host buffer that receives the mask with the statistics
     unsigned *dmax_bits = nullptr;  // device scalar: largest |descriptor component| as float bits (zeroed by k_init_run)
-    PassCounters *counters = nullptr;
+    PassCounters *counters_all = nullptr;  // [TSC_MAX_PASSES]: a slot's counters are zeroed once, by k_init_run, and only ever added to
+    PruneState *state_all = nullptr;       // [TSC_MAX_PASSES]: a slot's state block is written by whoever opens the slot, read by its kernels
+    PassCounters *counters = nullptr;      // the entries of the pass in flight (pass_launch) -- what every kernel of a pass is handed
     PruneState *state = nullptr;
     PassRecord *records = nullptr;  // [TSC_MAX_PASSES]
     std::vector<void *> blocks;
     // host state
     int next_ks = 0;       // next index into KS to consider
     int cur_slot = -1;     // schedule slot of the pass in flight (-1 = none)
-    int last_slot = -1;    // slot of the last pass that was enqueued and not yet closed on the device
-    int opened_slot = -1;  // slot that the device has already opened (done by the apply kernel of the pass before it)
+    int last_slot = -1;    // slot of the last pass that was enqueued and LEFT OPEN on the device: its tails end after their rows are applied,
+                           // and the first kernel of the next pass (pass_derive), or a k_pass_step launch, closes it behind a kernel boundary
+    int opened_slot = -1;  // slot whose state block the device has already written (by the kernel that closed the pass before it)
+    bool derive_prev = false;  // the open pass's first kernel closes last pass's slot (set by pass_launch for open_rows / local_pass)
+    int derive_slot = -1;
+    bool last_local = false, derive_local = false;  // the pass left open in last_slot / derive_slot ran in k_pass_chunks (its record says so)
     int64_t cur_k = 0;
     bool local_done = false;
     bool slot_used[TSC_MAX_PASSES] = {false};
@@ -115,9 +121,30 @@ static inline StepArgs next_step_args(const tsc_prune *p, int *next_slot) {
 
 // range_close: the context of the kernels of a rank-partitioned pass -- their last unit leaves the statistics in the exchange buffer
 // instead of closing the pass (pass_step_wave)
+// prev / cur: the slots a step closes / opens (StepArgs), -1 for none
+static inline StepCtx step_ctx_of(const tsc_prune *p, int prev, int cur) {
+    const int of = prev >= 0 ? prev : cur;
+    return StepCtx{p->state_all + of, cur >= 0 ? p->state_all + cur : nullptr, p->counters_all + of, p->records, p->bsum, p->boff, p->n_blocks,
+                   reinterpret_cast<unsigned *>(p->tickets), int(sizeof(*p->tickets) / 128), nullptr};
+}
+// the step behind the open pass (next_step_args)
 static inline StepCtx step_ctx(const tsc_prune *p, bool range_close = false) {
-    return StepCtx{p->state, p->counters, p->records, p->bsum, p->boff, p->n_blocks, reinterpret_cast<unsigned *>(p->tickets),
-                   int(sizeof(*p->tickets) / 128), range_close ? p->exch + p->bit_words : nullptr};
+    int nxt = -1;
+    (void)next_step_args(p, &nxt);
+    StepCtx sc = step_ctx_of(p, p->cur_slot, nxt);
+    if (range_close) sc.exch_tail = p->exch + p->bit_words;
+    return sc;
+}
+// the first kernel of the open pass closes the pass that was left open in front of it (rmsd.hpp, pass_derive), or has nothing to close
+static inline DeriveArgs derive_args(const tsc_prune *p) {
+    DeriveArgs d;
+    memset(&d, 0, sizeof(d));
+    d.prev = d.cur = -1, d.prev_algo = -1;
+    if (!p->derive_prev) return d;
+    d.prev_st = p->state_all + p->derive_slot, d.prev_cnt = p->counters_all + p->derive_slot, d.rec = p->records;
+    d.prev = p->derive_slot, d.cur = p->cur_slot, d.k_cur = (long long)p->cur_k, d.algo_cur = p->algo;
+    d.prev_algo = p->derive_local ? ALGO_LOCAL : -1;
+    return d;
 }
 
 static inline bool pass_is_partitioned(const tsc_prune *p, int64_t k) {
@@ -177,4 +204,5 @@ int launch_rmsd_sieve_sorted_mm(bool f32, hipStream_t st, dim3 grid, hipEvent_t 
                                 const CullMmArgs &cm, int n_groups, int n_seg);
 int launch_pass_chunks(hipStream_t st, unsigned blocks, hipEvent_t e0, hipEvent_t e1, const PassGeom &g, const LocalPassArgs &a, PruneState *state, uint8_t *mask,
                        unsigned long long *bits, int bit_words, const unsigned long long *view, const double *heavy, const double *Gall, const float *Dall,
-                       const CacheViews &cv, PassCounters *counters, int32_t *bsum, int block_items, const StepCtx &sc, const StepArgs &sa, LocalTickets *tickets);
+                       const CacheViews &cv, PassCounters *counters, int32_t *bsum, int block_items, const StepCtx &sc, const StepArgs &sa, LocalTickets *tickets,
+                       const DeriveArgs &dv);

@@ -291,7 +291,7 @@ inline __global__ __launch_bounds__(256) void k_rmsd_pairs(const double *__restr
     }
 }
 
-// Statistics counters of a pass.  Thousands of wavefronts report at the end of a kernel; same-address atomics
+// Statistics counters of a pass (one set per schedule slot).  Thousands of wavefronts report at the end of a kernel; same-address atomics
 // serialise at ~12 ns each (MI355X_MICROARCH.md, "fanin"), which for 10^4 reports is longer than the kernels
 // themselves, so the counters are spread over 64 buckets on separate 128-byte lines and summed on the host.
 constexpr int CNT_BUCKETS = 64;
@@ -303,7 +303,8 @@ __device__ inline void count_add(PassCounters *c, unsigned bucket, int what, uns
     if (v) atomicAdd(&c->w[bucket & (CNT_BUCKETS - 1)][what], v);
 }
 
-// Device-resident control block of a prune run.  The host enqueues every pass that COULD run (20 k < N) without
+// Device-resident control block of a prune run, one per schedule slot: written by whoever opens the slot's pass, read by its kernels, so
+// that nothing a pass reads changes while it is in flight.  The host enqueues every pass that COULD run (20 k < N) without
 // waiting for counts; the kernel that closes a pass evaluates the reference's gate `k == 1 or 20*k < count_nonzero(mask)`
 // (rmsd_pruning.py:192) for the next one on the device, and the kernels of a pass that is gated off return immediately.
 struct PruneState {
@@ -448,8 +449,8 @@ inline __global__ __launch_bounds__(256) void k_init_run(InitArgs a) {
         a.bits[e] = w, a.bits[a.bit_words + e] = w;
     }
     for (int64_t e = tid; e < a.view_words; e += stride) a.views[e] = 0;
-    unsigned long long *c = &a.cnt->w[0][0];
-    for (int64_t e = tid; e < CNT_BUCKETS * CNT_WORDS; e += stride) c[e] = 0;
+    unsigned long long *c = &a.cnt->w[0][0];  // the counters of every slot: zeroed here, once per run, and by nothing else
+    for (int64_t e = tid; e < int64_t(MAX_SLOTS) * CNT_BUCKETS * CNT_WORDS; e += stride) c[e] = 0;
     for (int64_t e = tid; e < a.n_zero_words; e += stride) a.zero_words[e] = 0;
     for (int64_t e = tid; e < a.n_tile_done; e += stride) a.tile_done[e] = 0;
     char *r = reinterpret_cast<char *>(a.rec);
@@ -465,8 +466,12 @@ inline __global__ __launch_bounds__(256) void k_init_run(InitArgs a) {
     if (tid < a.n_views) a.view_pass[tid] = a.sched[tid];
     if (tid == 0) {
         if (a.dmax_bits) *a.dmax_bits = 0;  // running maximum of the descriptor build (sieve.hpp)
-        PruneState *st = a.st;
-        st->n_active = int(n), st->pass_on = 0, st->A = int(n), st->ticket = 0, st->bitsel = 0, st->row_lo = 0, st->cull_on = 0;
+        // the state block of every slot starts as that of the untouched ensemble, gated off; a slot's own is written by whoever opens it
+        for (int s = 0; s < MAX_SLOTS; ++s) {
+            PruneState *ss = a.st + s;
+            ss->n_active = int(n), ss->pass_on = 0, ss->A = int(n), ss->ticket = 0, ss->bitsel = 0, ss->row_lo = 0, ss->cull_on = 0;
+        }
+        PruneState *st = a.st + (a.first_slot >= 0 ? a.first_slot : 0);
         if (a.first_slot >= 0) {
             const int on = (a.first_k == 1 || 20 * a.first_k < (long long)n) ? 1 : 0;
             PassRecord &fr = a.rec[a.first_slot];
@@ -478,7 +483,7 @@ inline __global__ __launch_bounds__(256) void k_init_run(InitArgs a) {
 }
 
 // Closes the pass in slot `prev` (sums its counters, updates n_active, re-ranks the scan blocks, flips the bit copy) and
-// opens the pass in slot `cur` (gate, A, zeroed counters).  prev / cur = -1: nothing to close / open.  Runs in ONE
+// opens the pass in slot `cur` (gate, A: the state block of that slot; its counters were zeroed by k_init_run).  prev / cur = -1: nothing to close / open.  Runs in ONE
 // WAVEFRONT: of the last unit of the closing pass to finish -- a row tile of the pair kernel, a block of k_apply_pass or of
 // k_pass_chunks -- or, where no pass precedes, of k_pass_step.
 struct StepArgs {
@@ -488,8 +493,9 @@ struct StepArgs {
     int prev_algo;  // >= 0: the kernel that really ran the closing pass (recorded in its PassRecord), -1: as opened
 };
 struct StepCtx {
-    PruneState *st;
-    PassCounters *cnt;
+    PruneState *st;       // state block of the slot being closed (StepArgs::prev; of the slot being opened where there is none)
+    PruneState *st_next;  // state block of the slot being opened (StepArgs::cur), null where there is none
+    PassCounters *cnt;    // counters of the slot being closed
     PassRecord *rec;
     int32_t *bsum, *boff;
     int n_blocks;
@@ -515,7 +521,7 @@ __device__ inline void pass_step_wave(const StepCtx &sc, const StepArgs &sa) {
     int c_first = lane < sc.n_blocks ? __hip_atomic_load(&sc.bsum[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
     const bool closing = sa.prev >= 0 && pass_on != 0;
     unsigned long long sum[CNT_REMOVED + 1] = {v0, v1, v2, v3, v4};
-    if (sc.exch_tail) {  // this rank's share of a rank-partitioned pass is done: statistics into the exchange buffer, counters cleared
+    if (sc.exch_tail) {  // this rank's share of a rank-partitioned pass is done: statistics into the exchange buffer
 #pragma unroll
         for (int w = 0; w <= CNT_REMOVED; ++w)
             for (int off = 32; off > 0; off >>= 1) sum[w] += __shfl_xor(sum[w], off);
@@ -523,7 +529,6 @@ __device__ inline void pass_step_wave(const StepCtx &sc, const StepArgs &sa) {
 #pragma unroll
             for (int w = 0; w <= CNT_REMOVED; ++w) sc.exch_tail[w] = sum[w];
         }
-        for (int e = lane; e < CNT_BUCKETS * 8; e += 64) sc.cnt->w[e >> 3][e & 7] = 0;
         for (int e = lane; e < sc.ticket_lines; e += 64) sc.tickets[32 * e] = 0;
         return;
     }
@@ -531,6 +536,9 @@ __device__ inline void pass_step_wave(const StepCtx &sc, const StepArgs &sa) {
 #pragma unroll
         for (int w = 0; w <= CNT_REMOVED; ++w)
             for (int off = 32; off > 0; off >>= 1) sum[w] += __shfl_xor(sum[w], off);
+    }
+    if (sa.prev >= 0) {
+        // (also behind a pass that was gated off: a chunk-local pass further back that was left open removed rows and wrote no prefix)
         int run = 0;
         for (int b0 = 0; b0 < sc.n_blocks; b0 += 64) {
             const int b = b0 + lane;
@@ -546,16 +554,15 @@ __device__ inline void pass_step_wave(const StepCtx &sc, const StepArgs &sa) {
         if (lane == 0) sc.boff[sc.n_blocks] = run;
     }
     if (lane == 0) {
-        int n_active = n_before;
+        int n_active = n_before, sel = bitsel;
         if (closing) {
             PassRecord &r = sc.rec[sa.prev];
             r.formed = (long long)sum[CNT_FORMED], r.exact = (long long)sum[CNT_EXACT], r.screened = (long long)sum[CNT_SCREENED];
             r.evaluated = (long long)sum[CNT_EVALUATED], r.removed = (long long)sum[CNT_REMOVED];
             n_active -= int(sum[CNT_REMOVED]);
-            st->n_active = n_active;
             r.n_after = n_active;
             if (sa.prev_algo >= 0) r.algo = sa.prev_algo;
-            st->bitsel = bitsel ^ 1;  // the copy the closing pass cleared its removed rows in is the current one now
+            sel ^= 1;  // the copy the closing pass cleared its removed rows in is the current one now
         }
         int on = 0;
         if (sa.cur >= 0) {
@@ -564,14 +571,93 @@ __device__ inline void pass_step_wave(const StepCtx &sc, const StepArgs &sa) {
             r.k = sa.k_cur, r.n_before = n_active, r.n_after = n_active, r.on = on, r.algo = sa.algo_cur;
             r.formed = r.exact = r.screened = r.evaluated = r.removed = 0;
         }
-        st->A = n_active;
-        st->row_lo = 0;
-        st->pass_on = on;
-        st->ticket = 0;
+        // (the state block of the next slot is written whole: nothing of the closing slot's is touched, so a wavefront of the closing
+        // pass that is still on its way reads what its siblings read)
+        if (PruneState *sn = sc.st_next)
+            sn->n_active = n_active, sn->A = n_active, sn->bitsel = sel, sn->row_lo = 0, sn->pass_on = on, sn->ticket = 0, sn->cull_on = 0;
     }
-    // counters back to zero (only the words in use); the arrival counters: the first word of every 128-byte line
-    for (int e = lane; e < CNT_BUCKETS * 8; e += 64) sc.cnt->w[e >> 3][e & 7] = 0;
+    // the counters belong to their slot and stay; the arrival counters are shared: the first word of every 128-byte line back to zero
     for (int e = lane; e < sc.ticket_lines; e += 64) sc.tickets[32 * e] = 0;
+}
+
+// The same step without a closing wavefront: the pass in slot `prev` was LEFT OPEN by its last kernel (its tails end after they have
+// applied their rows and added to their counters), and the kernel boundary behind it makes its counters and the scan blocks' counts
+// final.  The first kernel of the pass in slot `cur` -- k_open_rows, k_pass_chunks -- derives what pass_step_wave would have written, in
+// every workgroup for itself, in the round trip it spends on the state block anyway; workgroup 0 also writes it down (state block of
+// `cur`, the records of both slots, the prefix of the scan blocks) for the kernels behind the next kernel boundary.  No workgroup reads
+// what workgroup 0 writes in the same launch.  prev_st = null: nothing to derive, the state block of `cur` has been written already.
+struct DeriveArgs {
+    const PruneState *prev_st;
+    const PassCounters *prev_cnt;
+    PassRecord *rec;
+    int prev, cur;
+    long long k_cur;
+    int algo_cur, prev_algo;  // (as in StepArgs)
+};
+struct Derived {
+    int n_active, pass_on, bitsel;
+};
+// One wavefront calls this.  bsum (optional): the scan blocks' counts, whose exclusive prefix goes to s_boff[0 .. n_blocks] (LDS) and,
+// from the writer, to boff.  st_cur: written by the writer only.
+__device__ inline Derived pass_derive(const DeriveArgs &d, PruneState *st_cur, bool writer, const int32_t *bsum, int n_blocks, int *s_boff, int32_t *boff) {
+    const int lane = threadIdx.x & 63;
+    const PruneState *sp = d.prev_st;
+    // one round trip: the state block, the removed-row buckets (all five statistics in the writer) and the first 64 block counts
+    const int prev_on = sp->pass_on, n_before = sp->n_active, sel_before = sp->bitsel;
+    unsigned long long sum[CNT_REMOVED + 1] = {0ull, 0ull, 0ull, 0ull, 0ull};
+    sum[CNT_REMOVED] = __hip_atomic_load(&d.prev_cnt->w[lane][CNT_REMOVED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (writer) {
+#pragma unroll
+        for (int w = 0; w < CNT_REMOVED; ++w) sum[w] = __hip_atomic_load(&d.prev_cnt->w[lane][w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const int c_first = (bsum && lane < n_blocks) ? __hip_atomic_load(&bsum[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+    for (int off = 32; off > 0; off >>= 1) sum[CNT_REMOVED] += __shfl_xor(sum[CNT_REMOVED], off);
+    if (writer) {
+#pragma unroll
+        for (int w = 0; w < CNT_REMOVED; ++w)
+            for (int off = 32; off > 0; off >>= 1) sum[w] += __shfl_xor(sum[w], off);
+    }
+    if (bsum) {
+        int run = 0;
+        for (int b0 = 0; b0 < n_blocks; b0 += 64) {
+            const int b = b0 + lane;
+            const int c = b0 == 0 ? c_first : (b < n_blocks ? __hip_atomic_load(&bsum[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0);
+            int incl = c;
+            for (int off = 1; off < 64; off <<= 1) {
+                const int t = __shfl_up(incl, off);
+                if (lane >= off) incl += t;
+            }
+            if (b < n_blocks) {
+                s_boff[b] = run + incl - c;
+                if (writer) boff[b] = run + incl - c;
+            }
+            run += __shfl(incl, 63);
+        }
+        if (lane == 0) {
+            s_boff[n_blocks] = run;
+            if (writer) boff[n_blocks] = run;
+        }
+    }
+    Derived out;
+    const bool closing = prev_on != 0;
+    out.n_active = closing ? n_before - int(sum[CNT_REMOVED]) : n_before;
+    out.bitsel = closing ? sel_before ^ 1 : sel_before;  // (a pass that was gated off hands both on unchanged)
+    out.pass_on = (d.k_cur == 1 || 20 * d.k_cur < (long long)out.n_active) ? 1 : 0;  // rmsd_pruning.py:192
+    if (writer && lane == 0) {
+        if (closing) {
+            PassRecord &r = d.rec[d.prev];
+            r.formed = (long long)sum[CNT_FORMED], r.exact = (long long)sum[CNT_EXACT], r.screened = (long long)sum[CNT_SCREENED];
+            r.evaluated = (long long)sum[CNT_EVALUATED], r.removed = (long long)sum[CNT_REMOVED];
+            r.n_after = out.n_active;
+            if (d.prev_algo >= 0) r.algo = d.prev_algo;
+        }
+        PassRecord &r = d.rec[d.cur];
+        r.k = d.k_cur, r.n_before = out.n_active, r.n_after = out.n_active, r.on = out.pass_on, r.algo = d.algo_cur;
+        r.formed = r.exact = r.screened = r.evaluated = r.removed = 0;
+        st_cur->n_active = out.n_active, st_cur->A = out.n_active, st_cur->bitsel = out.bitsel, st_cur->row_lo = 0, st_cur->pass_on = out.pass_on;
+        st_cur->ticket = 0, st_cur->cull_on = 0;
+    }
+    return out;
 }
 
 inline __global__ __launch_bounds__(64) void k_pass_step(StepCtx sc, StepArgs sa) { pass_step_wave(sc, sa); }
@@ -646,8 +732,11 @@ struct OpenArgs {
     int bit_words;
     const int32_t *boff;
     int n_blocks, block_items;
-    unsigned n_tiles;                // row tiles of the pass (arrival count of a fused pass)
+    unsigned n_tiles;                // row tiles of the pass (arrival count of a fused pass that closes itself)
     PassTickets *tickets;
+    DeriveArgs dv;                   // dv.prev_st != null: the pass before this one was left open and is closed here (pass_derive) ...
+    const int32_t *bsum;             // ... from the scan blocks' counts; the prefix goes to LDS (the host sees to n_blocks <= lds_cap) and,
+    int32_t *boff_out;               // from workgroup 0, to memory, for the kernels behind this one
     int32_t *rank_of;                // (optional) rank_of[structure] = its active rank: what a culled pass (cull.hpp) lays its sorted order out from
     _Float16 *Dh;                    // (optional) the float16 records of the matrix-core screen (mm.hpp), by position like Dc
     const unsigned *dmax_bits;       // ... and the largest |descriptor component| of the run that scales them
@@ -677,15 +766,22 @@ inline __global__ __launch_bounds__(256) void k_open_rows(PassGeom g, OpenArgs o
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // (the first 256 entries of the prefix are requested together with the state block: one round trip for both)
     const bool in_lds = oa.n_blocks <= oa.lds_cap;
-    const int boff_mine = (in_lds && int(threadIdx.x) <= oa.n_blocks) ? oa.boff[threadIdx.x] : 0;
+    const bool derive = oa.dv.prev_st != nullptr;   // (the prefix of a derived pass comes from bsum, below; memory holds the one before it)
+    const int boff_mine = (!derive && in_lds && int(threadIdx.x) <= oa.n_blocks) ? oa.boff[threadIdx.x] : 0;
     TSC_OPEN_STAMP(0);  // started (and the first loads have come back)
     // (row_lo / n_all differ from 0 / A only in a rank-partitioned pass: rows and ranks below are LOCAL except where the mask's
     // own ranking -- the prefix of the scan blocks -- is consulted)
-    // One read of the state per WORKGROUP: in a fused pass that is gated off the last tile to arrive -- possibly a wavefront of this
-    // very launch -- opens the NEXT pass and rewrites the state block, and a wavefront of this block that started late would then
-    // see the next pass's gate while its siblings saw this one's (a barrier below is conditional on it)
+    // One read of the state per WORKGROUP (a barrier below is conditional on it).  The pass before this one was either closed by its
+    // own last unit, which wrote this slot's state block, or left open: then the first wavefront works the block out (pass_derive)
     __shared__ int s_state[5];
-    if (threadIdx.x == 0) s_state[0] = st->pass_on, s_state[1] = st->A, s_state[2] = st->bitsel, s_state[3] = st->row_lo, s_state[4] = st->n_active;
+    if (derive) {
+        if (wid == 0) {
+            const Derived d = pass_derive(oa.dv, sc.st, blockIdx.x == 0, oa.bsum, oa.n_blocks, s_boff, oa.boff_out);
+            if (lane == 0) s_state[0] = d.pass_on, s_state[1] = d.n_active, s_state[2] = d.bitsel, s_state[3] = 0, s_state[4] = d.n_active;
+        }
+    } else if (threadIdx.x == 0) {
+        s_state[0] = st->pass_on, s_state[1] = st->A, s_state[2] = st->bitsel, s_state[3] = st->row_lo, s_state[4] = st->n_active;
+    }
     __syncthreads();
     const int pass_on = s_state[0], A = s_state[1], sel = s_state[2], row_lo = s_state[3], n_all = s_state[4];
     const unsigned long long *X = oa.bits + size_t(sel) * oa.bit_words;
@@ -696,7 +792,7 @@ inline __global__ __launch_bounds__(256) void k_open_rows(PassGeom g, OpenArgs o
         unsigned long long *Xo = oa.bits + size_t(sel ^ 1) * oa.bit_words;
         for (int w = blockIdx.x * 256 + threadIdx.x; w < oa.bit_words; w += gridDim.x * 256) Xo[w] = X[w];
     }
-    if (pass_on && in_lds && int(blockIdx.x) * 4 * OPEN_ROWS < A) {  // (block-uniform)
+    if (!derive && pass_on && in_lds && int(blockIdx.x) * 4 * OPEN_ROWS < A) {  // (block-uniform)
         if (int(threadIdx.x) <= oa.n_blocks) s_boff[threadIdx.x] = boff_mine;
         for (int e = threadIdx.x + 256; e <= oa.n_blocks; e += 256) s_boff[e] = oa.boff[e];
         __syncthreads();
@@ -1393,6 +1489,7 @@ inline __global__ __launch_bounds__(1024) void k_pass_merge(MergeArgs a, StepCtx
     __shared__ int s_cnt[MERGE_LDS_BLOCKS];
     __shared__ int s_part[16], s_run;
     PruneState *st = sc.st;
+    PruneState *sn = sc.st_next ? sc.st_next : st;  // the state block of the slot this merge opens (that of the closing slot where there is none)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int pass_on = st->pass_on, sel = st->bitsel, n_before = st->n_active;
     const bool closing = sa.prev >= 0 && pass_on != 0;
@@ -1455,9 +1552,10 @@ inline __global__ __launch_bounds__(1024) void k_pass_merge(MergeArgs a, StepCtx
             r.removed = (long long)(n_before - n_active);
             r.n_after = n_active;
             if (sa.prev_algo >= 0) r.algo = sa.prev_algo;
-            st->n_active = n_active;
-            st->bitsel = sel ^ 1;
         }
+        sn->n_active = n_active;
+        sn->bitsel = closing ? sel ^ 1 : sel;
+        sn->cull_on = 0;
         for (int w = 0; w < 8; ++w) a.exch[a.bit_words + w] = 0;
         int on = 0;
         if (sa.cur >= 0) {
@@ -1466,14 +1564,14 @@ inline __global__ __launch_bounds__(1024) void k_pass_merge(MergeArgs a, StepCtx
             r.k = sa.k_cur, r.n_before = n_active, r.n_after = n_active, r.on = on, r.algo = sa.algo_cur;
             r.formed = r.exact = r.screened = r.evaluated = r.removed = 0;
         }
-        st->pass_on = on;
-        st->ticket = 0;
-        if (a.next_s_lo < 0) st->A = n_active, st->row_lo = 0;
+        sn->pass_on = on;
+        sn->ticket = 0;
+        if (a.next_s_lo < 0) sn->A = n_active, sn->row_lo = 0;
     }
     if (a.next_s_lo >= 0 && wv == 0) {  // (boff and the new bit copy were written by this block, before the barriers above)
         const unsigned long long *Xn = closing ? Xo : X;
         const int lo = rank_below_wave(sc.boff, Xn, a.n_blocks, n_active, a.next_s_lo), hi = rank_below_wave(sc.boff, Xn, a.n_blocks, n_active, a.next_s_hi);
-        if (lane == 0) st->row_lo = lo, st->A = hi - lo;
+        if (lane == 0) sn->row_lo = lo, sn->A = hi - lo;
     }
 }
 

@@ -793,8 +793,9 @@ __device__ inline bool pair_is_similar(const double *__restrict__ p, const doubl
 #define TSC_SIEVE_OCC1 6
 #endif
 // What the pair kernel of a single-rank run does when the LAST work item of a row tile finishes: it applies the tile's
-// verdicts (apply_wave_rows, rmsd.hpp) and, if the tile was the last of the pass, closes the pass and opens the next one
-// (pass_step_wave) -- no k_apply_pass launch behind the pair kernel.  Work items of a tile = its column segments that start
+// verdicts (apply_wave_rows, rmsd.hpp) -- no k_apply_pass launch behind the pair kernel.  tickets = null: that is all, the pass is
+// left open and the first kernel of the next pass closes it (rmsd.hpp, pass_derive).  Otherwise (a rank-partitioned pass) the tile
+// that was the last of the pass closes it (pass_step_wave).  Work items of a tile = its column segments that start
 // below the tile's largest stop column (the others leave at their first test and do not count).
 struct FusedApply {
     ApplyArgs ap;
@@ -1235,6 +1236,10 @@ inline __global__ __launch_bounds__(256, CPL == 4 ? 4 : (CPL == 2 ? TSC_SIEVE_OC
         if (lane == 0) {
             count_add(counters, unsigned(slot), CNT_EVALUATED, ev_total);
             count_add(counters, unsigned(slot), CNT_REMOVED, rm_total);
+        }
+        if (!fa.tickets) {  // the pass is left open: the first kernel of the next one closes it behind the kernel boundary (rmsd.hpp, pass_derive)
+            TSC_STAMP(5);
+            return;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         TSC_STAMP(5);  // tile applied
