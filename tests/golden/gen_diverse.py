@@ -16,11 +16,14 @@ enforced here (a case is drawn again with the next seed, the seed recorded) so t
   * label margin: at every Lloyd iteration, every row's second-smallest minus smallest squared distance >= 1e-6 A^2;
   * at most one cluster empty at a time;
   * the pick: best and second-best cumdist of a cluster differ by >= 1e-6, energies inside a cluster are distinct;
-  * Horn's top eigenvalue separated from the next by >= 1e-3 relative for every aligned pair.
+  * Horn's top eigenvalue separated from the next by >= 1e-3 relative for every aligned pair;
+  * G20e only: two or more clusters empty at once, and the distances a relocation chooses between (the rows it takes and the first
+    it leaves) differ by >= 1e-9 relative, copies of a row apart.  Its label margin leaves out a centre that is a copy of a lower one.
 
 Files (each under 1 MiB): G20a (60 x 12 atoms k = 5; an index subset; two structures), G20b (400 x 30, k = 12, one init centre
 moved 50 A away: one cluster empty in iteration 1), G20c (600 x 24 through most_diverse_conformers, n = 20, both modes), G20d
-(1200 x 20, k = 40: the aligned features only), G20_diverse.json (the guard values, seeds, versions, and the modules that bind
+(1200 x 20, k = 40: the aligned features only), G20e (case_several_empty: features and init centres with 2 .. 5 clusters empty in
+iteration 1, k = 12 and 140, scikit-learn's result), G20_diverse.json (the guard values, seeds, versions, and the modules that bind
 align_structures / most_diverse_conformers by name, read off the reference's import lines).
 
 Usage:  python -B tests/golden/gen_diverse.py
@@ -64,7 +67,7 @@ import tscode.torsion_module as tm  # noqa: E402
 
 from tscode_amd.synthetic import make_ensemble  # noqa: E402  (NumPy only)
 
-MARGIN_BAND, PICK_BAND, HORN_BAND = 1e-6, 1e-6, 1e-3
+MARGIN_BAND, PICK_BAND, HORN_BAND, RELOC_BAND = 1e-6, 1e-6, 1e-3, 1e-9
 
 
 # ------------------------------------------------------------------------------------------------------- inputs
@@ -283,6 +286,57 @@ def case_mdc(n_structs, atoms, n, first_seed):
     return with_redraw(make, first_seed, f"most_diverse_conformers {n_structs} x {sum(atoms)}")
 
 
+# ------------------------------------------------------------------------------------------------------- several empty clusters
+COPIES = {(3, 12): (2, 5, 9), (5, 12): (0, 2, 5, 9, 11), (3, 140): (5, 77, 133), (5, 140): (5, 40, 77, 129, 139)}    # (on both sides of centre 128)
+FAR = {(2, 12): (3, 8), (4, 12): (1, 3, 8, 10), (2, 140): (3, 131), (4, 140): (3, 64, 131, 139)}
+
+
+def case_several_empty(kind, m, k, first_seed):
+    """Loose blobs, 4 k rows (k = 12: 20 k) of 9 columns (k = 140: 12), init centres taken from rows.
+    copies: the m centres COPIES[m, k] are copies of the first of them, so m - 1 clusters are empty in iteration 1.
+    far / twins: the m centres FAR[m, k] lie 50 A (and more) outside the data, and two rows placed 25 A out on the other side are the
+    two farthest rows and fall into one cluster (twins: the second is a copy of the first), so two relocations draw from one donor.
+    The guards are computed with the restatement of tests/test_diverse.py, the one the tests compare the library with."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_diverse import lloyd_restated as restated, relocation_gap
+
+    def make(seed):
+        rng = np.random.default_rng(seed)
+        N, D = (240, 9) if k == 12 else (4 * k, 12)
+        X = 2.0 * rng.normal(size=(k, D))[rng.integers(0, k, size=N)] + rng.normal(size=(N, D))
+        if kind != "copies":
+            i1, i2 = sorted(rng.choice(N, 2, replace=False).tolist())
+            X[i1] = -25.0 / np.sqrt(D) + 0.05 * rng.normal(size=D)
+            X[i2] = X[i1] if kind == "twins" else 1.05 * X[i1] + 0.05 * rng.normal(size=D)
+        pool = np.setdiff1d(np.arange(N), [i1, i2]) if kind != "copies" else np.arange(N)
+        init = X[np.sort(rng.choice(pool, k, replace=False))].copy()
+        if kind == "copies":
+            init[list(COPIES[m, k][1:])] = init[COPIES[m, k][0]]
+        else:
+            for j, c in enumerate(FAR[m, k]):
+                init[c] += (50.0 + 10.0 * j) / np.sqrt(D)
+        rel = []
+        r_labels, r_centres, r_inertia, r_iter, margin, max_empty = restated(X, init, ignore_copies=kind != "far", relocations=rel)
+        gap = relocation_gap(X, rel)
+        if margin < MARGIN_BAND or gap < RELOC_BAND or r_iter < 3:
+            return None
+        if kind == "copies":
+            if max_empty != m - 1 or len(rel[0][1]) != m - 1 or rel[0][1].tolist() != list(COPIES[m, k][1:]):
+                return None
+        else:
+            it0, empty0, far0, from0, _ = rel[0]
+            if max_empty != m or it0 != 0 or empty0.tolist() != list(FAR[m, k]) or far0[:2].tolist() != ([i1, i2] if kind == "twins" else [i2, i1]):
+                return None
+            if from0[0] != from0[1] or (m > 2 and from0[2] == from0[0]):
+                return None
+        labels, centres, inertia, n_iter = sklearn_lloyd(X, init)
+        assert np.array_equal(labels, r_labels) and n_iter == r_iter, "the restatement disagrees with scikit-learn"
+        assert np.abs(centres - r_centres).max() < 1e-10
+        return {"X": X, "init": init, "labels": labels, "centers": centres, "inertia": np.float64(inertia), "n_iter": np.int32(n_iter),
+                "margin": np.float64(margin), "max_empty": np.int32(max_empty), "reloc_gap": np.float64(gap), "m": np.int32(m)}
+    return with_redraw(make, first_seed, f"{kind}{m} k = {k}")
+
+
 # ------------------------------------------------------------------------------------------------------- binding sites
 def binding_sites(names):
     """The reference's modules that bind each name at import time (`from tscode.x import name`) or define it, as gen_install_sites.py
@@ -319,13 +373,14 @@ def save_npz(path, arrays):
 
 
 def main():
-    files = {"a": {}, "b": {}, "c": {}, "d": {}}
-    meta = {"sklearn": sklearn.__version__, "numpy": np.__version__, "bands": {"margin": MARGIN_BAND, "pick": PICK_BAND, "horn": HORN_BAND}, "cases": {}}
+    files = {"a": {}, "b": {}, "c": {}, "d": {}, "e": {}}
+    meta = {"sklearn": sklearn.__version__, "numpy": np.__version__,
+            "bands": {"margin": MARGIN_BAND, "pick": PICK_BAND, "horn": HORN_BAND, "relocation": RELOC_BAND}, "cases": {}}
 
     def put(key, case, got):
         meta["cases"][case] = {"file": f"G20{key}_diverse.npz",
                                **{f: (float(got[f]) if isinstance(got[f], np.floating) else int(got[f]))
-                                  for f in ("seed", "margin", "max_empty", "n_iter", "horn_gap", "pick_gap", "energy_gap", "inertia") if f in got}}
+                                  for f in ("seed", "margin", "max_empty", "n_iter", "horn_gap", "pick_gap", "energy_gap", "inertia", "reloc_gap") if f in got}}
         for f, v in got.items():
             files[key][f"{case}/{f}"] = v
 
@@ -335,6 +390,9 @@ def main():
     put("b", "empty", case_cluster(400, (15, 15), 12, 10, 2104, far_centre=True))
     put("c", "mdc", case_mdc(600, (12, 12), 20, 2105))
     put("d", "wide", case_cluster(1200, (10, 10), 40, 10, 2106, keep_input=False))
+    for at, (kind, m, k) in enumerate([("copies", 3, 12), ("copies", 5, 12), ("copies", 3, 140), ("copies", 5, 140), ("far", 2, 12), ("far", 4, 12),
+                                       ("far", 2, 140), ("far", 4, 140), ("twins", 2, 12)]):
+        put("e", f"{kind}{m if kind != 'twins' else ''}_k{k}", case_several_empty(kind, m, k, 2110 + at))
     meta["sites"] = binding_sites(["align_structures", "most_diverse_conformers"])
     for key, arrays in files.items():
         save_npz(os.path.join(HERE, f"G20{key}_diverse.npz"), arrays)

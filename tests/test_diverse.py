@@ -17,6 +17,10 @@ from conftest import GOLDEN, ROOT
 MARGIN_BAND, PICK_BAND, HORN_BAND = 1e-6, 1e-6, 1e-3          # the generator's guard bands
 COORD_TOL = 1e-9                                              # VAL_TOL of tests/test_gpu_parity.py: Kabsch values against the reference
 KMEANS_CASES = ("small", "empty", "mdc", "wide")
+RELOC_BAND = 1e-9                                             # the generator's band on the distances a relocation chooses between
+# G20e: several clusters empty at once.  copies<m>: m init centres are copies of one another to the bit; far<m>: m init centres
+# 50 A outside the data, with the two farthest rows in one cluster; twins: far2 with those two rows copies of one another
+EMPTY_CASES = ("copies3_k12", "copies5_k12", "copies3_k140", "copies5_k140", "far2_k12", "far4_k12", "far2_k140", "far4_k140", "twins_k12")
 SITES = ("tscode.hypermolecule_class", "tscode.embedder", "tscode.operators", "tscode.torsion_module", "tscode.ase_manipulations",
          "tscode.mep_relaxer", "tscode.atropisomer_module", "tscode.automep")
 SYMBOLS = ("tsc_align_structures", "tsc_kmeans_lloyd", "tsc_kmeans_seed", "tsc_diverse_pick", "tsc_diverse_select")
@@ -42,11 +46,14 @@ def g20(case):
 
 
 # ------------------------------------------------------------------------------------------------------- the restatement
-def lloyd_restated(X, init, max_iter=300, tol=1e-4, matmul=False):
+def lloyd_restated(X, init, max_iter=300, tol=1e-4, matmul=False, ignore_copies=False, relocations=None):
     """scikit-learn's dense Lloyd iteration as include/tscode_hip.h states it (tsc_kmeans_lloyd).  Returns labels, centres,
     inertia, n_iter, the smallest label margin (second-smallest minus smallest squared distance) over all iterations and rows,
     and the most clusters empty at once.  matmul: distances as |x|^2 - 2 x.c + |c|^2 (the large case), else by differences,
-    one centre at a time."""
+    one centre at a time.  ignore_copies: a centre that is a bit-for-bit copy of a lower centre is left out of the margin (its
+    distances are the lower one's to the bit in any implementation, and the rule sends the tie to the lower one); the labels are
+    taken over all centres as before.  relocations: a list that receives, per iteration with an empty cluster, (iteration, the
+    empty clusters, the rows they take in that order, the clusters those rows leave, every row's distance to its own centre)."""
     mean = X.mean(0)
     Xc, Cc = X - mean, init - mean
     tol_abs = np.mean(np.var(Xc, axis=0)) * tol
@@ -61,6 +68,9 @@ def lloyd_restated(X, init, max_iter=300, tol=1e-4, matmul=False):
             d2 = np.stack([((Xc - c) ** 2).sum(1) for c in Cc], axis=1)
         lab = d2.argmin(1)                                           # (the lowest centre on a tie)
         own = d2[rows, lab]
+        if ignore_copies:
+            first = np.unique(Cc, axis=0, return_index=True)[1]
+            d2[:, np.setdiff1d(np.arange(k), first)] = np.inf       # (np.unique keeps the lowest index of equal rows)
         if k > 1:
             d2[rows, lab] = np.inf
             gap = float((d2.min(1) - own).min())
@@ -83,6 +93,8 @@ def lloyd_restated(X, init, max_iter=300, tol=1e-4, matmul=False):
         if len(empty):
             own_exact = ((Xc - Cc[labels]) ** 2).sum(1)
             far = np.lexsort((rows, -own_exact))[:len(empty)]       # decreasing distance, the lower row on a tie
+            if relocations is not None:
+                relocations.append((it, empty.copy(), far.copy(), labels[far].copy(), own_exact))
             for e, f in zip(empty, far):
                 sums[labels[f]] -= Xc[f]
                 counts[labels[f]] -= 1
@@ -104,9 +116,23 @@ def lloyd_restated(X, init, max_iter=300, tol=1e-4, matmul=False):
     return labels.astype(np.int32), Cc + mean, inertia, it + 1, margin, max_empty
 
 
+def relocation_gap(X, relocations):
+    """Over what lloyd_restated(relocations=...) recorded: the smallest relative gap between consecutive distances to the own centre
+    among the rows a relocation takes and the first row it does not take.  Two rows that are copies to the bit are left out: their
+    distances are equal in any implementation, and the rule sends the lower row first."""
+    gap = np.inf
+    for _, _, far, _, own in relocations:
+        order = np.lexsort((np.arange(len(own)), -own))[:len(far) + 1]
+        for a, b in zip(order[:-1], order[1:]):
+            if not np.array_equal(X[a], X[b]):
+                gap = min(gap, float((own[a] - own[b]) / own[a]))
+    return gap
+
+
 def seed_restated(X, u):
     """k-means++ without local trials as include/tscode_hip.h states it (tsc_kmeans_seed).  Also returns the smallest relative
-    distance of a target u_j * total to the running-sum boundaries next to it."""
+    distance of a target u_j * total to the running-sum boundaries next to it.  A total of zero (every row a copy of a seed) or
+    a target that no running sum exceeds (u_j * total rounded up to the total) gives row N - 1, as csrc/diverse.hpp has it."""
     N, k = len(X), len(u)
     rows = [min(N - 1, int(u[0] * N))]
     min_d2 = ((X - X[rows[0]]) ** 2).sum(1)
@@ -117,6 +143,10 @@ def seed_restated(X, u):
         run = np.cumsum(min_d2)
         target = u[j] * run[-1]
         i = int(np.searchsorted(run, target, side="right"))        # the first row whose running sum exceeds the target
+        if i == N:
+            clear = 0.0
+            rows.append(N - 1)
+            continue
         clear = min(clear, abs(run[i] - target) / run[-1], abs(target - (run[i - 1] if i else 0.0)) / run[-1])
         rows.append(i)
     return np.array(rows, dtype=np.int32), clear
@@ -135,10 +165,12 @@ def moved(x, seed):
     return np.ascontiguousarray(np.einsum("nij,naj->nai", rot, x - cen) + cen + rng.uniform(-5, 5, size=(len(x), 1, 3)))
 
 
-def kabsch_align_numpy(structures):
-    """align_structures on all atoms, vectorised: centre, C = ref^T tgt, SVD with the rmsd-1.4 sign fix, out = tgt @ U^T."""
-    s = structures - structures.mean(axis=1, keepdims=True)
-    Cm = np.einsum("ai,naj->nij", s[0], s)
+def kabsch_align_numpy(structures, indices=None):
+    """align_structures, vectorised: centre on the indexed atoms (all when None; listed twice, an atom counts twice),
+    C = ref^T tgt over them, SVD with the rmsd-1.4 sign fix, out = tgt @ U^T for every atom."""
+    idx = np.arange(structures.shape[1]) if indices is None or len(indices) == 0 else np.asarray(indices).ravel()
+    s = structures - structures[:, idx].mean(axis=1, keepdims=True)
+    Cm = np.einsum("ai,naj->nij", s[0][idx], s[:, idx])
     V, S, W = np.linalg.svd(Cm)
     flip = np.linalg.det(V) * np.linalg.det(W) < 0.0
     V[flip, :, -1] *= -1.0
@@ -148,12 +180,48 @@ def kabsch_align_numpy(structures):
     return out
 
 
+def pick_restated(aligned, labels, centres, energies=None):
+    """tsc_diverse_pick as include/tscode_hip.h states it (torsion_module.py:894-922): per cluster the member of lowest energy, or
+    without energies of largest cumdist -- the member at POSITION p of its cluster's list sums |centre_c - member| over the atoms and
+    over the centres c != p (:919 as written) -- the first in row order on a tie, -1 for an empty cluster.  Also returns the smallest
+    relative gap between the best value of a cluster and the best value that is not the best one's bits again (inf when there is none)."""
+    k = len(centres)
+    cen = np.asarray(centres).reshape(k, -1, 3)
+    r = np.arange(k)
+    picked, gap = np.full(k, -1, dtype=np.int32), np.inf
+    for cl in range(k):
+        members = np.flatnonzero(labels == cl)
+        if not len(members):
+            continue
+        if energies is None:
+            v = np.array([np.sum(np.linalg.norm(cen[r != p] - aligned[m], axis=2)) for p, m in enumerate(members)])
+            best = int(np.argmax(v))                                     # (the first of equal values)
+        else:
+            v = -np.asarray(energies)[members]
+            best = int(np.argmin(energies[members]))
+        picked[cl] = members[best]
+        others = v[v != v[best]]
+        if len(others):
+            gap = min(gap, float((v[best] - others.max()) / max(abs(v[best]), 1e-300)))
+    return picked, gap
+
+
 # ------------------------------------------------------------------------------------------------------- CPU
 def test_g20_loads_and_its_guard_values_are_inside_the_bands():
     meta = json.load(open(os.path.join(GOLDEN, "G20_diverse.json")))
-    assert meta["bands"] == {"margin": MARGIN_BAND, "pick": PICK_BAND, "horn": HORN_BAND}
-    assert set(meta["cases"]) == {"small", "subset", "pair", "empty", "mdc", "wide"}
-    for name in meta["cases"]:
+    assert meta["bands"] == {"margin": MARGIN_BAND, "pick": PICK_BAND, "horn": HORN_BAND, "relocation": RELOC_BAND}
+    assert set(meta["cases"]) == {"small", "subset", "pair", "empty", "mdc", "wide"} | set(EMPTY_CASES)
+    for name in EMPTY_CASES:                                  # features and init centres only: nothing was aligned
+        c = g20(name)
+        m, k = int(c.m), int(name.split("_k")[1])
+        assert name.split("_k")[0] in (f"copies{m}", f"far{m}") or (name, m) == ("twins_k12", 2)
+        assert c.meta["file"] == "G20e_diverse.npz" and os.path.getsize(os.path.join(GOLDEN, c.meta["file"])) < 1 << 20
+        assert c.init.shape == c.centers.shape == (k, c.X.shape[1]) and c.labels.shape == (len(c.X),) and len(c.X) >= 4 * k
+        assert float(c.margin) >= MARGIN_BAND and float(c.reloc_gap) >= RELOC_BAND
+        assert int(c.max_empty) == (m - 1 if name[0] == "c" else m) >= 2
+        assert len(np.unique(c.init, axis=0)) == (k - m + 1 if name[0] == "c" else k)
+    assert len(np.unique(g20("twins_k12").X, axis=0)) == len(g20("twins_k12").X) - 1
+    for name in sorted(set(meta["cases"]) - set(EMPTY_CASES)):
         c = g20(name)
         assert os.path.getsize(os.path.join(GOLDEN, c.meta["file"])) < 1 << 20
         assert float(c.horn_gap) >= HORN_BAND
@@ -172,16 +240,20 @@ def test_g20_loads_and_its_guard_values_are_inside_the_bands():
     assert m.out_energies.shape == m.out_diverse.shape == (20, 24, 3) and len(m.X) == int(m.tfd_mask.sum()) > 20
 
 
-@pytest.mark.parametrize("case", KMEANS_CASES)
+@pytest.mark.parametrize("case", KMEANS_CASES + EMPTY_CASES)
 def test_restatement_reproduces_scikit_learn_on_g20(case):
+    """(The margin of the cases whose init centres are copies of one another leaves the copies out: there the tie is the case.)"""
     c = g20(case)
+    copies = case.startswith(("copies", "twins"))            # (twins: the two relocated centres are copies of one another)
     for matmul in (False, True):
-        labels, centres, inertia, n_iter, margin, max_empty = lloyd_restated(c.X, c.init, matmul=matmul)
+        labels, centres, inertia, n_iter, margin, max_empty = lloyd_restated(c.X, c.init, matmul=matmul, ignore_copies=copies)
         assert np.array_equal(labels, c.labels) and n_iter == int(c.n_iter)
         assert np.abs(centres - c.centers).max() <= 1e-12
         assert abs(inertia - float(c.inertia)) <= 1e-9 * float(c.inertia)
         assert max_empty == int(c.max_empty) and margin >= MARGIN_BAND
-    assert lloyd_restated(c.X, c.init)[4] == pytest.approx(float(c.margin), rel=1e-6)
+    assert lloyd_restated(c.X, c.init, ignore_copies=copies)[4] == pytest.approx(float(c.margin), rel=1e-6)
+    if copies:
+        assert lloyd_restated(c.X, c.init)[4] == 0.0, "without the parameter the tie between the copies is the smallest margin"
 
 
 def _fake_tscode():
@@ -435,14 +507,8 @@ def test_tsc_diverse_pick_follows_the_reference_rules():
     c = g20("mdc")
     n_kept, k = len(c.X), 20
     aligned = np.ascontiguousarray(c.X.reshape(n_kept, -1, 3))
-    cen = c.centers.reshape(k, -1, 3)
-    r = np.arange(k)
-    want_d, want_e = [], []
-    for cl in range(k):
-        members = np.flatnonzero(c.labels == cl)
-        cum = [np.sum(np.linalg.norm(cen[r != p] - aligned[m], axis=2)) for p, m in enumerate(members)]     # :919 as written
-        want_d.append(members[int(np.argmax(cum))])
-        want_e.append(members[int(np.argmin(c.energies[members]))])
+    want_d = pick_restated(aligned, c.labels, c.centers)[0]                                                     # :919 as written
+    want_e = pick_restated(aligned, c.labels, c.centers, c.energies[:n_kept])[0]
     eng = get_engine()
     for energies, want in ((None, want_d), (np.ascontiguousarray(c.energies[:n_kept]), want_e)):
         picked = np.empty(k, dtype=np.int32)
