@@ -424,6 +424,23 @@ int tsc_cyclical_embed(tsc_ctx *ctx, const double *frags, const int64_t *frag_of
                        int64_t max_clashes, double rmsd_thr, uint8_t *clash_ok, uint8_t *kept, double *poses, int64_t poses_capacity,
                        int64_t *n_pass, int64_t *n_kept);
 
+/* tsc_cyclical_embed_groups: tsc_cyclical_embed (tscode/embeds.py:657-717 / :785-847) from ONE record per (group, molecule) instead
+ *   of one per (pose, molecule) -- the form a multiembed (tscode/multiembed.py:26-82: one bimolecular cyclical embed per arrangement
+ *   of facing atoms, all over the same two coordinate stacks) needs, where the rows would run into the millions.  start, end,
+ *   direction, pivot, meanpoint, r0, r1 f64[n_groups * n_mols * 3] and n_reactive, conf_idx i32[n_groups * n_mols] at index
+ *   group * n_mols + m; angles f64[n_angles * n_mols] is the one table of angle sets every group walks (systematic_angles, :665).
+ *   Pose g * n_angles + a is record g under angle set a, and the groups are the records: exactly tsc_cyclical_embed on the rows
+ *   expanded from them, group_off[g] = g * n_angles.  Outputs as tsc_cyclical_embed with n_poses = n_groups * n_angles.
+ *   Checked before the device is touched, the message naming the group: 1 <= n_angles <= 8192, n_groups * n_angles < INT32_MAX,
+ *   n_mols 2 or 3, n_reactive 1 or 2, conf_idx in range.  The alignment (align_vec_pair, :691-692) is computed once per
+ *   (group, molecule) and not once per pose. */
+int tsc_cyclical_embed_groups(tsc_ctx *ctx, const double *frags, const int64_t *frag_off, const int32_t *n_atoms,
+                              const int32_t *n_conf, int n_mols, const double *start, const double *end, const double *direction,
+                              const double *pivot, const double *meanpoint, const double *r0, const double *r1,
+                              const int32_t *n_reactive, const int32_t *conf_idx, const double *angles, int64_t n_groups, int n_angles,
+                              double clash_thresh, int64_t max_clashes, double rmsd_thr, uint8_t *clash_ok, uint8_t *kept, double *poses,
+                              int64_t poses_capacity, int64_t *n_pass, int64_t *n_kept);
+
 /* HOST-side helper (no device, no context): the graph step of tscode/numba_functions.py:201-226 (prune_conformers_tfd) and
  * tscode/optimization_methods.py:341-358 (prune_by_moment_of_inertia) for any number of chunks: the matches (rel_i[q], rel_j[q]),
  * q in [chunk_ptr[c], chunk_ptr[c+1]), of chunk c are node indices relative to the chunk (0 <= index < chunk_len[c]), listed in the

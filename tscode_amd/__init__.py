@@ -20,6 +20,7 @@ from .graph_manipulations import (bond_graph_batch, bond_tables, covalent_radii,
 from .nci import NCI_DICT, differential_nci, get_nci, interactions_of, nci_batch, nci_tables  # noqa: F401
 from .reactive_atoms import (ORB_DIM_DICT, ReactiveMolecule, atom_type, orbital_recipes, orbitals_batch,  # noqa: F401
                              reactive_molecule)
+from .multiembed import MultiembedResult, multiembed_batch  # noqa: F401
 from .engine import Engine, FragmentSet, device_count, get_engine  # noqa: F401
 from .install import install, uninstall  # noqa: F401
 from .numba_functions import (_get_tf_mat, compenetration_check, compenetration_mask, count_clashes, get_torsion_fingerprint,  # noqa: F401

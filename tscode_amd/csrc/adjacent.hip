@@ -738,3 +738,67 @@ extern "C" __attribute__((visibility("default"))) int tsc_cyclical_embed(tsc_ctx
     TSC_API_GUARD_END
 }
 
+// The same embed from one record per (group, molecule) and one angle table shared by all groups: pose g * n_angles + a is record g under
+// angle set a, what tsc_cyclical_embed computes on the rows a caller would expand from them.  Per pose nothing is uploaded or checked.
+extern "C" __attribute__((visibility("default"))) int tsc_cyclical_embed_groups(tsc_ctx *c, const double *frags, const int64_t *frag_off, const int32_t *n_atoms,
+                                                                                const int32_t *n_conf, int n_mols, const double *start, const double *end,
+                                                                                const double *direction, const double *pivot, const double *meanpoint,
+                                                                                const double *r0, const double *r1, const int32_t *n_reactive,
+                                                                                const int32_t *conf_idx, const double *angles, int64_t n_groups, int n_angles,
+                                                                                double clash_thresh, int64_t max_clashes, double rmsd_thr, uint8_t *clash_ok,
+                                                                                uint8_t *kept, double *poses, int64_t poses_capacity, int64_t *n_pass,
+                                                                                int64_t *n_kept) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(c && frags && frag_off && n_atoms && n_conf && start && end && direction && pivot && meanpoint && r0 && r1 && n_reactive && conf_idx && angles &&
+                    clash_ok && kept && n_pass && n_kept,
+                "tsc_cyclical_embed_groups: null argument");
+    TSC_REQUIRE(n_mols == 2 || n_mols == 3, "tsc_cyclical_embed_groups: %d molecules, the cyclical embed takes 2 or 3", n_mols);
+    TSC_REQUIRE(n_angles >= 1 && n_angles <= GF_MAX_GROUP, "%d angle sets per group: must be in [1, %d]", n_angles, GF_MAX_GROUP);
+    TSC_REQUIRE(n_groups >= 0 && n_groups < INT32_MAX / n_angles, "%lld groups of %d poses: too many candidates", (long long)n_groups, n_angles);
+    TSC_REQUIRE(rmsd_thr > 0, "bad sizes");
+    *n_pass = *n_kept = 0;
+    if (n_groups == 0) return 0;
+    FragTable ft;
+    TSC_TRY(make_frag_table(frag_off, n_atoms, n_conf, n_mols, &ft));
+    const int64_t items = n_groups * n_mols, n_poses = n_groups * n_angles, rows = n_poses * n_mols;
+    for (int64_t q = 0; q < items; ++q) {
+        TSC_REQUIRE(n_reactive[q] == 1 || n_reactive[q] == 2, "group %lld, molecule %d: n_reactive must be 1 or 2", (long long)(q / n_mols), int(q % n_mols));
+        TSC_REQUIRE(conf_idx[q] >= 0 && conf_idx[q] < n_conf[q % n_mols], "group %lld, molecule %d: conformer index out of range", (long long)(q / n_mols),
+                    int(q % n_mols));
+    }
+    std::vector<int32_t> goff(size_t(n_groups) + 1);
+    for (int64_t g = 0; g <= n_groups; ++g) goff[size_t(g)] = int32_t(g * n_angles);
+    HostCall h(c);
+    Scratch &s = h.scratch();
+    const double *host[7] = {start, end, direction, pivot, meanpoint, r0, r1};
+    double *d_frags, *dev[7], *d_angles, *d_rot, *d_pos;
+    int32_t *d_nr, *d_cg, *d_ci, *d_goff, *d_goff_pass;
+    TSC_TRY(h.in(frags, size_t(frags_total_doubles(frag_off, n_atoms, n_conf, n_mols)), &d_frags));
+    for (int i = 0; i < 7; ++i) TSC_TRY(h.in(host[i], size_t(items) * 3, &dev[i]));
+    TSC_TRY(h.in(n_reactive, size_t(items), &d_nr));
+    TSC_TRY(h.in(conf_idx, size_t(items), &d_cg));
+    TSC_TRY(h.in(angles, size_t(n_angles) * n_mols, &d_angles));
+    TSC_TRY(h.in(goff.data(), size_t(n_groups) + 1, &d_goff));
+    TSC_TRY(s.get(size_t(n_groups) + 1, &d_goff_pass));
+    TSC_TRY(s.get(size_t(rows) * 9, &d_rot));
+    TSC_TRY(s.get(size_t(rows) * 3, &d_pos));
+    TSC_TRY(s.get(size_t(rows), &d_ci));
+    // a wavefront per chunk of 64 / n_mols groups, four per workgroup; 768 workgroups fill 256 CUs at the three waves per SIMD the kernel's
+    // registers allow, and more chunks than that are walked in further passes
+    hipLaunchKernelGGL(k_cyclical_embed_group_params, dim3(grid_for(ceil_div(n_groups, int64_t(64 / n_mols)), CGP_WAVES, 768)), dim3(64 * CGP_WAVES), 0, c->stream,
+                       (const double *)dev[0], (const double *)dev[1], (const double *)dev[2], (const double *)dev[3], (const double *)dev[4],
+                       (const double *)dev[5], (const double *)dev[6], (const int32_t *)d_nr, (const int32_t *)d_cg, (const double *)d_angles, n_groups, n_mols,
+                       n_angles, d_rot, d_pos, d_ci);
+    TSC_HIP(hipGetLastError());
+    const int n = ft.n_total;
+    const int ng = int(n_groups);
+    auto filter = [&](const double *d_structs, int32_t np, const int32_t *pos_scan, const int32_t *total, uint8_t *d_acc) -> int {
+        hipLaunchKernelGGL(k_group_offsets_after_filter, dim3(grid_for(ng + 1, 256, 1024)), dim3(256), 0, c->stream, (const int32_t *)d_goff, ng, pos_scan, n_poses,
+                           total, d_goff_pass);
+        TSC_HIP(hipGetLastError());
+        return tsc_greedy_group_filter_dev(c, d_structs, d_goff_pass, ng, np, n, rmsd_thr, d_acc);
+    };
+    return embed_filter_run(c, h, d_frags, ft, frag_off, n_atoms, n_conf, d_ci, d_rot, d_pos, n_poses, clash_thresh, max_clashes, clash_ok, kept, poses,
+                            poses_capacity, n_pass, n_kept, filter);
+    TSC_API_GUARD_END
+}

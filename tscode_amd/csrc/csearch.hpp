@@ -564,6 +564,59 @@ __device__ inline void align_vec_pair_dev(const double ref0[3], const double ref
     R[6] = 2 * (x * z - w * y), R[7] = 2 * (y * z + w * x), R[8] = w * w - x * x - y * y + z * z;
 }
 
+// The two halves of one (pose, molecule) row, shared by the row kernel and the group kernel below.  Everything a row computes before
+// its angle enters (:676-700, :708) depends on the group's record alone:
+struct CyclicalAlign {
+    double A[9];       // align_vec_pair of the polygon side and direction onto the pivot and the molecule's direction, :691-692
+    double axis[3];    // the step rotation's pointer, :697-700
+    double centre[3];  // A @ mean(reactive_coords), :708
+    double shift[3];   // polygon side's middle - A @ meanpoint, :713
+};
+
+__device__ inline void cyclical_align_dev(const double *__restrict__ start, const double *__restrict__ end, const double *__restrict__ direction,
+                                          const double *__restrict__ pivot, const double *__restrict__ meanpoint, const double *__restrict__ r0,
+                                          const double *__restrict__ r1, bool two, CyclicalAlign &o) {
+    double st[3], en[3], dir[3], pv[3], mp[3], a0[3], a1[3], apm[3], md[3], ref0[3];
+    bool zero = true;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        st[i] = start[i], en[i] = end[i], dir[i] = direction[i], pv[i] = pivot[i], mp[i] = meanpoint[i];
+        a0[i] = r0[i], a1[i] = r1[i];
+        apm[i] = two ? (a0[i] + a1[i]) / 2.0 : a0[i];  // np.mean(reactive_coords, axis=0), :673
+        md[i] = mp[i] - apm[i];                         // :676
+        zero = zero && md[i] == 0.0;
+        ref0[i] = en[i] - st[i];
+    }
+    if (zero) {  // :677-678
+#pragma unroll
+        for (int i = 0; i < 3; ++i) md[i] = mp[i];
+    }
+    align_vec_pair_dev(ref0, dir, pv, md, o.A);  // :691-692
+    const double *A = o.A;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double v0 = two ? a0[0] - a1[0] : pv[0], v1 = two ? a0[1] - a1[1] : pv[1], v2 = two ? a0[2] - a1[2] : pv[2];
+        o.axis[i] = A[3 * i] * v0 + A[3 * i + 1] * v1 + A[3 * i + 2] * v2;                  // :697-700
+        o.centre[i] = A[3 * i] * apm[0] + A[3 * i + 1] * apm[1] + A[3 * i + 2] * apm[2];    // :708
+        const double a_m = A[3 * i] * mp[0] + A[3 * i + 1] * mp[1] + A[3 * i + 2] * mp[2];
+        o.shift[i] = (st[i] + en[i]) / 2.0 - a_m;                                           // :713
+    }
+}
+
+// ... and the angle's half: rot = S(axis, angle) @ A, pos = centre - S @ centre + shift (:704, :711-714)
+__device__ inline void cyclical_step_dev(const CyclicalAlign &g, double angle, double *__restrict__ rot, double *__restrict__ pos) {
+    double S[9];
+    const double *A = g.A;
+    rot_mat_from_pointer_dev(g.axis, angle, S);  // :704
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) rot[3 * i + j] = S[3 * i] * A[j] + S[3 * i + 1] * A[3 + j] + S[3 * i + 2] * A[6 + j];  // :711
+        const double s_c = S[3 * i] * g.centre[0] + S[3 * i + 1] * g.centre[1] + S[3 * i + 2] * g.centre[2];
+        pos[i] = g.centre[i] - s_c + g.shift[i];  // :713-714
+    }
+}
+
 inline __global__ __launch_bounds__(256) void k_cyclical_embed_params(const double *__restrict__ start, const double *__restrict__ end,
                                                                 const double *__restrict__ direction, const double *__restrict__ pivot,
                                                                 const double *__restrict__ meanpoint, const double *__restrict__ r0,
@@ -571,39 +624,65 @@ inline __global__ __launch_bounds__(256) void k_cyclical_embed_params(const doub
                                                                 const double *__restrict__ angle, int64_t n, double *__restrict__ rot,
                                                                 double *__restrict__ pos) {
     for (int64_t q = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; q < n; q += int64_t(gridDim.x) * blockDim.x) {
-        double st[3], en[3], dir[3], pv[3], mp[3], a0[3], a1[3], apm[3], md[3], ref0[3];
-        const bool two = n_reactive[q] == 2;
-        bool zero = true;
+        CyclicalAlign g;
+        cyclical_align_dev(start + 3 * q, end + 3 * q, direction + 3 * q, pivot + 3 * q, meanpoint + 3 * q, r0 + 3 * q, r1 + 3 * q, n_reactive[q] == 2, g);
+        cyclical_step_dev(g, angle[q], rot + 9 * q, pos + 3 * q);
+    }
+}
+
+// The same rows from one record per (group, molecule) and one angle table for all groups (tsc_cyclical_embed_groups): pose g * A + a takes
+// record g and angle set a.  A wavefront takes a chunk of whole groups, 64 / n_mols of them, in two phases:
+//   1. one (group, molecule) record per lane: cyclical_align_dev -- the Jacobi sweep of align_vec_pair_dev -- once per record, all lanes
+//      busy, its 18 doubles parked in LDS (record-minor, so the 64 lanes write 64 consecutive doubles);
+//   2. the chunk's rows, which lie back to back in rot / pos, strided over the lanes: a lane fetches its row's record from LDS (neighbouring
+//      lanes mostly share one: a broadcast) and does the angle's half, cyclical_step_dev; consecutive lanes write consecutive rows.
+// So the sweep runs once per 64 records where the row kernel runs it once per 64 rows, and no lane idles while a group has fewer than 64
+// angle sets.  (One wavefront per record with the sweep in front of its angle loop was tried first: on 36 angle sets it keeps 36 of 64
+// lanes busy and took 1.8 times the row kernel's time -- lanes in lockstep make "once per wavefront" no cheaper than "once per 64 rows".)
+// The four wavefronts of a block walk their chunks in step, so the barriers between the phases are block barriers.  Also writes the rows'
+// conformer indices, which the embed reads per (pose, molecule).
+constexpr int CGP_WAVES = 4;
+
+inline __global__ __launch_bounds__(64 * CGP_WAVES) void k_cyclical_embed_group_params(
+    const double *__restrict__ start, const double *__restrict__ end, const double *__restrict__ direction, const double *__restrict__ pivot,
+    const double *__restrict__ meanpoint, const double *__restrict__ r0, const double *__restrict__ r1, const int32_t *__restrict__ n_reactive,
+    const int32_t *__restrict__ conf_idx, const double *__restrict__ angles, int64_t n_groups, int n_mols, int n_angles, double *__restrict__ rot,
+    double *__restrict__ pos, int32_t *__restrict__ conf_rows) {
+    __shared__ double s_align[CGP_WAVES][18][64];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int per_chunk = 64 / n_mols;  // groups per wavefront and pass
+    const int64_t n_chunks = (n_groups + per_chunk - 1) / per_chunk;
+    double(*sa)[64] = s_align[wid];
+    for (int64_t c0 = int64_t(blockIdx.x) * CGP_WAVES; c0 < n_chunks; c0 += int64_t(gridDim.x) * CGP_WAVES) {
+        const int64_t g0 = (c0 + wid) * per_chunk;  // (a wavefront past the last chunk has nothing to do in either phase)
+        const int groups_here = g0 < n_groups ? int(n_groups - g0 < per_chunk ? n_groups - g0 : per_chunk) : 0;
+        const int items_here = groups_here * n_mols;
+        if (lane < items_here) {
+            const int64_t w = g0 * n_mols + lane;
+            CyclicalAlign g;
+            cyclical_align_dev(start + 3 * w, end + 3 * w, direction + 3 * w, pivot + 3 * w, meanpoint + 3 * w, r0 + 3 * w, r1 + 3 * w, n_reactive[w] == 2, g);
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            st[i] = start[3 * q + i], en[i] = end[3 * q + i], dir[i] = direction[3 * q + i], pv[i] = pivot[3 * q + i], mp[i] = meanpoint[3 * q + i];
-            a0[i] = r0[3 * q + i], a1[i] = r1[3 * q + i];
-            apm[i] = two ? (a0[i] + a1[i]) / 2.0 : a0[i];  // np.mean(reactive_coords, axis=0), :673
-            md[i] = mp[i] - apm[i];                         // :676
-            zero = zero && md[i] == 0.0;
-            ref0[i] = en[i] - st[i];
+            for (int k = 0; k < 9; ++k) sa[k][lane] = g.A[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sa[9 + k][lane] = g.axis[k], sa[12 + k][lane] = g.centre[k], sa[15 + k][lane] = g.shift[k];
         }
-        if (zero) {  // :677-678
+        __syncthreads();
+        const int rows_here = items_here * n_angles;  // <= 64 * GF_MAX_GROUP
+        const int64_t row0 = g0 * n_angles * n_mols;
+        for (int r = lane; r < rows_here; r += 64) {
+            const int t = r / n_mols, m = r - t * n_mols;  // row = (group * n_angles + a) * n_mols + m
+            const int gl = t / n_angles, a = t - gl * n_angles;
+            const int item = gl * n_mols + m;
+            CyclicalAlign g;
 #pragma unroll
-            for (int i = 0; i < 3; ++i) md[i] = mp[i];
+            for (int k = 0; k < 9; ++k) g.A[k] = sa[k][item];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) g.axis[k] = sa[9 + k][item], g.centre[k] = sa[12 + k][item], g.shift[k] = sa[15 + k][item];
+            const int64_t row = row0 + r;
+            cyclical_step_dev(g, angles[a * n_mols + m], rot + 9 * row, pos + 3 * row);
+            conf_rows[row] = conf_idx[g0 * n_mols + item];
         }
-        double A[9], S[9], axis[3], centre[3];
-        align_vec_pair_dev(ref0, dir, pv, md, A);  // :691-692
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double v0 = two ? a0[0] - a1[0] : pv[0], v1 = two ? a0[1] - a1[1] : pv[1], v2 = two ? a0[2] - a1[2] : pv[2];
-            axis[i] = A[3 * i] * v0 + A[3 * i + 1] * v1 + A[3 * i + 2] * v2;                  // :697-700
-            centre[i] = A[3 * i] * apm[0] + A[3 * i + 1] * apm[1] + A[3 * i + 2] * apm[2];    // :708
-        }
-        rot_mat_from_pointer_dev(axis, angle[q], S);  // :704
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) rot[9 * q + 3 * i + j] = S[3 * i] * A[j] + S[3 * i + 1] * A[3 + j] + S[3 * i + 2] * A[6 + j];  // :711
-            const double s_c = S[3 * i] * centre[0] + S[3 * i + 1] * centre[1] + S[3 * i + 2] * centre[2];
-            const double a_m = A[3 * i] * mp[0] + A[3 * i + 1] * mp[1] + A[3 * i + 2] * mp[2];
-            pos[3 * q + i] = centre[i] - s_c + ((st[i] + en[i]) / 2.0 - a_m);  // :713-714
-        }
+        __syncthreads();
     }
 }
 

@@ -321,13 +321,23 @@ def cyclical_embed_batch(mols, systematic_angles, clash_thresh=1.5, max_clashes=
         blocks3, group_ids3, meta3 = _trimolecular_groups(coords, reactive, pivots, cumnums, pairings, internal_constraints)
         return _run_cyclical_groups(coords, blocks3, group_ids3, [(c, p, np.array([v])) for c, p, v in meta3], angles, clash_thresh, max_clashes, rmsd_thr,
                                     return_trace, flat_meta=True)
+    blocks, group_ids, group_meta = _bimolecular_groups(coords, reactive, pivots, rigid_shortcut, max_norm_delta, pairings, internal_constraints, return_trace)
+    return _run_cyclical_groups(coords, blocks, group_ids, group_meta, angles, clash_thresh, max_clashes, rmsd_thr, return_trace)
+
+
+def _bimolecular_groups(coords, reactive, pivots, rigid_shortcut=True, max_norm_delta=5, pairings=None, internal_constraints=(), want_meta=True):
+    """The (conformers, pivots, orientation) groups of a two-molecule cyclical embed in the reference's loop order (embeds.py:470-496, :636-655;
+    rigid shortcut :741-783): one 23-field record per (group, molecule) f64[G, 2, 23] -- start 0:3, end 3:6, direction 6:9, pivot 9:12,
+    meanpoint 12:15, the reactive atoms 15:18 and 18:21, their number 21, the conformer 22 --, the facing atoms of every group int[G, 2, 2]
+    and (conformers, pivot pairs, orientations) per conformer pair for the trace.  Host arithmetic only: what ``cyclical_embed_batch`` expands
+    into rows and ``multiembed_batch`` hands to the library as it is."""
     directions = np.array([[0.0, 1.0, 0.0], [0.0, -1.0, 0.0]])                                      # _get_directions for two, :252-253 / :768
     conf_indices = cartesian_product(*[np.arange(len(c)) for c in coords])                           # :470-471
     blocks, group_ids, group_meta = [], [], []
-    # Every conformer of a molecule has the same number of pivots (the usual case: pivots are a property of the reactive atoms) and no
-    # pairing filter: all conformer pairs at once.  The arrays below are the loop's, with one more leading axis; flattening them under
+    # Every conformer of a molecule has the same number of pivots (the usual case: pivots are a property of the reactive atoms): all
+    # conformer pairs at once.  The arrays below are the loop's, with one more leading axis; flattening them under
     # the mask in row-major order (conformer pair, pivot pair, orientation) is the order the loop appends in.
-    uniform = not pairings and len(conf_indices) > 0 and all(len({len(np.asarray(p[0]).reshape(-1, 3)) for p in pivots[m]}) == 1 for m in range(2))
+    uniform = len(conf_indices) > 0 and all(len({len(np.asarray(p[0]).reshape(-1, 3)) for p in pivots[m]}) == 1 for m in range(2))
     if uniform:
         vecs = [np.stack([np.asarray(p[0], dtype=np.float64).reshape(-1, 3) for p in pivots[m]]) for m in range(2)]      # [conformer, pivot, 3]
         means = [np.stack([np.asarray(p[1], dtype=np.float64).reshape(-1, 3) for p in pivots[m]]) for m in range(2)]
@@ -358,9 +368,12 @@ def cyclical_embed_batch(mols, systematic_angles, clash_thresh=1.5, max_clashes=
             ids[:, :, :, :, 0] = c0[:, :, None, :]
             ids[:, :, 0, :, 1], ids[:, :, 1, :, 1] = c1, c1[:, :, ::-1]
             take = np.repeat(ok[:, :, None], 2, axis=2)
+            for pair in pairings or ():                                                              # :642 / :777, every group at once
+                if not _in_constraints(pair, internal_constraints):
+                    take &= (ids == np.asarray(pair, dtype=np.int64)).all(axis=-1).any(axis=-1)
             blocks.append(rec[take])
             group_ids.append(ids[take])
-            if return_trace:
+            if want_meta:
                 for n in range(nc):
                     qs, vs = np.nonzero(take[n])
                     if len(qs):
@@ -415,7 +428,7 @@ def cyclical_embed_batch(mols, systematic_angles, clash_thresh=1.5, max_clashes=
     n_groups = sum(len(b) for b in blocks)
     blocks = np.concatenate(blocks) if n_groups else np.zeros((0, 2, 23))                            # [group, molecule, field]
     group_ids = np.concatenate(group_ids) if n_groups else np.zeros((0, 2, 2), dtype=np.int64)
-    return _run_cyclical_groups(coords, blocks, group_ids, group_meta, angles, clash_thresh, max_clashes, rmsd_thr, return_trace)
+    return blocks, group_ids, group_meta
 
 
 def _run_cyclical_groups(coords, blocks, group_ids, group_meta, angles, clash_thresh, max_clashes, rmsd_thr, return_trace, flat_meta=False):

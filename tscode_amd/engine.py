@@ -488,6 +488,27 @@ class Engine:
                                           C.byref(n_pass), C.byref(n_kept)))
         return ok.astype(bool), kept.astype(bool), (poses[:n_kept.value].copy() if want_poses else None)
 
+    def cyclical_embed_groups(self, frags: FragmentSet, start, end, direction, pivot, meanpoint, r0, r1, n_reactive, conf_idx, angles, clash_thresh,
+                              max_clashes, rmsd_thr=1.0, want_poses=True):
+        """``cyclical_embed`` from one record per (group, molecule), index = group * n_mols + molecule, and ONE angle table f64[A, n_mols] that every
+        group walks: pose g * A + a is record g under angle set a.  (clash_ok bool[G * A], kept bool[G * A], poses or None)."""
+        arrs = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3) for x in (start, end, direction, pivot, meanpoint, r0, r1)]
+        n_reactive = np.ascontiguousarray(n_reactive, dtype=np.int32).ravel()
+        conf_idx = np.ascontiguousarray(conf_idx, dtype=np.int32).ravel()
+        angles = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1, frags.n_mols)
+        items, A = len(n_reactive), len(angles)
+        if items % frags.n_mols or any(a.shape != (items, 3) for a in arrs) or conf_idx.shape != (items,):
+            raise ValueError("every per-group input must have n_groups * n_mols rows")
+        G = items // frags.n_mols
+        N = G * A
+        ok, kept = np.zeros(N, dtype=np.uint8), np.zeros(N, dtype=np.uint8)
+        poses = np.empty((N, frags.n_total, 3)) if want_poses else None        # rows beyond n_kept are never touched
+        n_pass, n_kept = C.c_int64(), C.c_int64()
+        check(self.lib.tsc_cyclical_embed_groups(self._h, ptr(frags.flat), *frags.table_args(), *[ptr(a) for a in arrs], ptr(n_reactive), ptr(conf_idx),
+                                                 ptr(angles), C.c_int64(G), C.c_int(A), C.c_double(float(clash_thresh)), C.c_int64(int(max_clashes)),
+                                                 C.c_double(float(rmsd_thr)), ptr(ok), ptr(kept), ptr(poses), C.c_int64(N), C.byref(n_pass), C.byref(n_kept)))
+        return ok.astype(bool), kept.astype(bool), (poses[:n_kept.value].copy() if want_poses else None)
+
     # ---- N3: conformational-search rotations ---------------------------------------------------
     def csearch_rotate(self, coords, torsions, masks, angles, thresh=1.5, max_clashes=0):
         """Every candidate of tscode/torsion_module.py:463-500: (new_coords f64[M, n, 3], rotated_bonds i32[M])."""

@@ -12,6 +12,7 @@ from __future__ import annotations
 import sys
 
 from . import algebra, embeds, graph_manipulations, hypermolecule_class, nci, numba_functions, optimization_methods, rmsd_pruning, rot_corr, torsion_module
+from . import multiembed as _multiembed      # (install() has a switch of the module's name)
 from . import utils
 
 # attribute -> (replacement, modules that bind it)
@@ -97,12 +98,22 @@ _CSEARCH_PATCHES = {
     "_group_torsions_dbscan": (torsion_module._group_torsions_dbscan, ("tscode.torsion_module",)),
 }
 
-_OPT_IN = (_ROT_CORR_PATCHES, _DIVERSE_PATCHES, _TOPOLOGY_PATCHES, _NCI_PATCHES, _CSEARCH_PATCHES)
+# Opt-in (install(multiembed=True)): the multiembed, the one embed of generate_candidates' table (tscode/embedder.py:1141-1147) that fans out
+# to child processes (tscode/multiembed.py:49-73).  The sites are the ones tests/golden/gen_multiembed.py records from the reference's
+# import lines (G27_multiembed.json): the dispatcher is bound by name in tscode.embedder, the bifunctional driver only where it is
+# defined (the reference's dispatcher looks it up there at call time).  The drop-ins hand shrink / simpleorbitals / debug children and
+# runs of more than two molecules to the functions they replaced (multiembed._originals).
+_MULTIEMBED_PATCHES = {
+    "multiembed_dispatcher": (_multiembed.multiembed_dispatcher, ("tscode.embedder", "tscode.multiembed")),
+    "multiembed_bifunctional": (_multiembed.multiembed_bifunctional, ("tscode.multiembed",)),
+}
+
+_OPT_IN = (_ROT_CORR_PATCHES, _DIVERSE_PATCHES, _TOPOLOGY_PATCHES, _NCI_PATCHES, _CSEARCH_PATCHES, _MULTIEMBED_PATCHES)
 
 _saved = {}
 
 
-def install(modules=None, per_item=False, rot_corr=False, diverse=False, topology=False, nci=False, csearch=False):
+def install(modules=None, per_item=False, rot_corr=False, diverse=False, topology=False, nci=False, csearch=False, multiembed=False):
     """Replace the hot-path functions in every already-imported tscode module: by default those that work on a whole ensemble
     per call (prune_conformers_rmsd, prune_conformers_tfd, get_moi_similarity_matches, _score_embed_poses) and the two embed
     loops (string_embed, cyclical_embed: one GPU call each instead of one Python iteration per pose); with
@@ -111,13 +122,15 @@ def install(modules=None, per_item=False, rot_corr=False, diverse=False, topolog
     prune_conformers_rmsd_rot_corr (_ROT_CORR_PATCHES); with ``diverse=True`` also align_structures and most_diverse_conformers
     (_DIVERSE_PATCHES); with ``topology=True`` also graphize, molecule_check, scramble_check and get_double_bonds_indices
     (_TOPOLOGY_PATCHES); with ``nci=True`` also get_nci (_NCI_PATCHES); with ``csearch=True`` also clustered_csearch and
-    _group_torsions_dbscan (_CSEARCH_PATCHES).
+    _group_torsions_dbscan (_CSEARCH_PATCHES); with ``multiembed=True`` also multiembed_dispatcher and multiembed_bifunctional
+    (_MULTIEMBED_PATCHES).
     Returns the list of (module, attribute) pairs that were patched."""
     mods = sys.modules if modules is None else modules
     done = []
     table = (list(_PATCHES.items()) + (list(_ROT_CORR_PATCHES.items()) if rot_corr else []) +
              (list(_DIVERSE_PATCHES.items()) if diverse else []) + (list(_TOPOLOGY_PATCHES.items()) if topology else []) +
-             (list(_NCI_PATCHES.items()) if nci else []) + (list(_CSEARCH_PATCHES.items()) if csearch else []))
+             (list(_NCI_PATCHES.items()) if nci else []) + (list(_CSEARCH_PATCHES.items()) if csearch else []) +
+             (list(_MULTIEMBED_PATCHES.items()) if multiembed else []))
     for attr, (fn, names) in table:
         if not per_item and attr not in _WHOLE_ENSEMBLE and not any(attr in t for t in _OPT_IN):
             continue
@@ -129,6 +142,8 @@ def install(modules=None, per_item=False, rot_corr=False, diverse=False, topolog
                     embeds._originals[attr] = _saved[(name, attr)]      # what the drop-in hands the cases it does not cover to
                 if attr in _CSEARCH_PATCHES and name == "tscode.torsion_module":
                     torsion_module._csearch_originals[attr] = _saved[(name, attr)]
+                if attr in _MULTIEMBED_PATCHES and name == "tscode.multiembed":
+                    _multiembed._originals[attr] = _saved[(name, attr)]
                 setattr(mod, attr, fn)
                 done.append((name, attr))
     return done
@@ -143,3 +158,4 @@ def uninstall(modules=None):
         del _saved[(name, attr)]
     embeds._originals.clear()
     torsion_module._csearch_originals.clear()
+    _multiembed._originals.clear()

@@ -133,13 +133,14 @@ def prune_by_moment_of_inertia_batch(ensembles, atomnos, max_deviation=1e-2, mas
     return out
 
 
-def similarity_refining_batch(ensembles, atomnos, quadruplets=None, rot_corr=None, rmsd_thr=0.5, tfd=True, moi=True, rmsd=True, masses=None):
+def similarity_refining_batch(ensembles, atomnos, quadruplets=None, rot_corr=None, rmsd_thr=0.5, tfd=True, moi=True, rmsd=True, masses=None,
+                              tfd_thresh=10, max_deviation=1e-2):
     """The similarity stages of Embedder.similarity_refining (tscode/embedder.py:1310-1388) on a list of ensembles, each stage ONE
     batched call over the ensembles that take it: ``[(structures_s, mask_s)]`` with ``mask_s`` over the input rows of ensemble s.
 
     Stages, order and size gates are the reference's (:1322-1382), each gate taken on the ensemble's current count:
-      TFD      (prune_conformers_tfd_batch) where ``tfd`` and ``quadruplets[s]`` is a non-empty array;
-      MOI      (prune_by_moment_of_inertia_batch) where ``moi`` and at most 500 structures are left (:1342);
+      TFD      (prune_conformers_tfd_batch, ``tfd_thresh``) where ``tfd`` and ``quadruplets[s]`` is a non-empty array;
+      MOI      (prune_by_moment_of_inertia_batch, ``max_deviation``) where ``moi`` and at most 500 structures are left (:1342);
       RMSD     (prune_conformers_rmsd_batch, ``rmsd_thr``) where ``rmsd`` and at most 1e5 are left (:1356);
       rot-corr (prune_rmsd_rot_corr_arrays_batch, ``max_rmsd = rmsd_thr`` as :1377 passes it) after the RMSD stage, where at most 500
                are left (:1372) and ``rot_corr[s]`` -- a set-up dict with the keys ``torsions``, ``angles``, ``move_masks``,
@@ -179,10 +180,11 @@ def similarity_refining_batch(ensembles, atomnos, quadruplets=None, rot_corr=Non
 
     if tfd:
         stage([s for s in range(S) if quads[s] is not None and len(quads[s])],
-              lambda w: prune_conformers_tfd_batch([cur[s] for s in w], [quads[s] for s in w]))
+              lambda w: prune_conformers_tfd_batch([cur[s] for s in w], [quads[s] for s in w], thresh=tfd_thresh))
     if moi:
         stage([s for s in range(S) if len(cur[s]) <= 500],
-              lambda w: prune_by_moment_of_inertia_batch([cur[s] for s in w], [nos[s] for s in w], masses=None if masses is None else [ms[s] for s in w]))
+              lambda w: prune_by_moment_of_inertia_batch([cur[s] for s in w], [nos[s] for s in w], max_deviation=max_deviation,
+                                                         masses=None if masses is None else [ms[s] for s in w]))
     if rmsd:
         stage([s for s in range(S) if len(cur[s]) <= 1e5],
               lambda w: prune_conformers_rmsd_batch([cur[s] for s in w], [nos[s] for s in w], rmsd_thr=thr[w]))
