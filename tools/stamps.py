@@ -8,7 +8,8 @@ and run   TSCODE_AMD_LIB=$PWD/tscode_amd/libtscode_hip_stamps.so python tools/st
 The kernel stamps the 100 MHz wall clock (after draining its outstanding memory operations: the stamps perturb it a little) at:
 0 wavefront started, 1 prologue data arrived, 2 screen done, 3 candidates evaluated, 4 arrived at the tile's counter, 5 tile applied,
 6 arrived at the pass's counter, 7 pass closed (6 and 7 only in a pass that closes itself; one that is left open ends at 5).  A pass that
-runs whole in k_pass_chunks stamps 0 started, 1 chunk ranked and stop columns found, 3 pairs evaluated, 5 rows applied, 6 and 7 as above.  Printed: percentiles of every phase over the wavefronts that went through it, in us.
+runs whole in k_pass_chunks stamps 0 started, 1 chunk ranked and stop columns found, 2 first evaluation stage entered, 4 last one left, 3 pairs evaluated,
+5 rows applied, 6 and 7 as above (tools/stamps_local.py prints those by class of wavefront).  Printed: percentiles of every phase over the wavefronts that went through it, in us.
 """
 import ctypes as C
 import sys
@@ -38,6 +39,7 @@ assert lib.tsc_debug_stamps(h, buf.ctypes.data, cap, C.byref(n)) == 0
 s = buf[: n.value].astype(np.int64)
 started = s[:, 0] > 0
 t_start = s[started, 0].min()
+s[s < t_start] = 0      # (k_pass_chunks of a pass left open keeps a batch count in slot 6, not a time: tools/stamps_local.py reads it)
 print(f"{cfg} pass k = {k}: {n.value} wavefronts launched, {int(started.sum())} stamped a start, {int((s[:, 1] > 0).sum())} had work, "
       f"{int((s[:, 5] > 0).sum())} applied a tile")
 

@@ -55,11 +55,74 @@ struct LocalTickets {  // zeroed by k_init_run and again by the wavefront that c
     unsigned pad[31];
 };
 
+// -DTSC_DBG_STAMPS builds: slot 2 = the wavefront enters its first evaluation stage, 4 = it has left its last one, 6 (a pass left open
+// does not use it) = how many sign batches it ran + 65536 * how many exact batches
+#ifdef TSC_DBG_STAMPS
+#define LP_STAGE_IN(exact)                                \
+    do {                                                  \
+        if (!n_stages) TSC_STAMP(2);                      \
+        n_stages += (exact) ? 65536 : 1;                  \
+    } while (0)
+#define LP_STAGE_OUT() TSC_STAMP(4)
+#define LP_STAGE_COUNT()                                                                                                             \
+    do {                                                                                                                             \
+        if (a.dbg && (threadIdx.x & 63) == 0) a.dbg[size_t(blockIdx.x) * 32 + (threadIdx.x >> 6) * 8 + 6] = (unsigned long long)n_stages; \
+    } while (0)
+#else
+#define LP_STAGE_IN(exact) do { } while (0)
+#define LP_STAGE_OUT() do { } while (0)
+#define LP_STAGE_COUNT() do { } while (0)
+#endif
+
 __device__ inline unsigned long long lds_extract64(const unsigned long long *bits, int start) {
     const int w = start >> 6, sh = start & 63;
     const unsigned long long lo = bits[w] >> sh;
     const unsigned long long hi = sh ? (bits[w + 1] << (64 - sh)) : 0ull;
     return lo | hi;
+}
+
+// views_insert_wave (rmsd.hpp) for this kernel, whose launch is as long as its slowest workgroup's chain: the same bits in the same words,
+// but ONE round trip for the summary words of all later views instead of one per view.  The bit of a key goes out as it is found (no
+// answer is waited for); the summary word of view j -- a load, and an or only where a bit is missing: thousands of rows would else or the
+// same word -- is left to lane j - cv.first, and the lanes go for their words together behind the loop.  Rows of one tile lie in one
+// chunk, so their keys share a summary word unless the chunk straddles a multiple of 65 536 structures: such a second word is dealt with
+// on the spot, as rmsd.hpp does.
+__device__ inline void lp_views_insert_wave(const CacheViews &cv, bool removed, int a, int b) {
+    if (__ballot(removed) == 0) return;
+    const int lane = threadIdx.x & 63;
+    static_assert(MAX_SLOTS <= 64, "a lane per later view");
+    long long my_word = -1;
+    unsigned long long my_sb = 0ull;
+    for (int j = cv.first; j < cv.count; ++j) {
+        const ViewPass vp = cv.pass[j];
+        bool ok = false;
+        if (removed) {
+            const int c = int(((unsigned long long)unsigned(a) * vp.magic) >> vp.shift);
+            if (c * vp.cs == a && c < vp.k) ok = b < ((c == vp.k - 1) ? cv.n : vp.cs * (c + 1));
+        }
+        unsigned long long left = __ballot(ok);
+        if (!left) continue;
+        unsigned long long *v = cv.views + int64_t(j) * cv.stride;
+        if (ok) atomicOr(&v[b >> 6], 1ull << (b & 63));
+        for (bool primary = true; left; primary = false) {
+            const int leader = __ffsll((long long)left) - 1;
+            const int word = __shfl(b >> 16, leader);
+            const bool same = ok && (b >> 16) == word;
+            unsigned long long sb = same ? 1ull << ((b >> 10) & 63) : 0ull;
+            for (int off = 32; off > 0; off >>= 1) sb |= __shfl_xor(sb, off);
+            if (primary) {
+                if (lane == j - cv.first) my_word = int64_t(j) * cv.stride + cv.bit_words + word, my_sb = sb;
+            } else if (lane == leader) {
+                unsigned long long *ds = v + cv.bit_words + word;
+                if ((__hip_atomic_load(ds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & sb) != sb) atomicOr(ds, sb);
+            }
+            left &= ~__ballot(same);
+        }
+    }
+    if (my_sb) {
+        unsigned long long *ds = cv.views + my_word;
+        if ((__hip_atomic_load(ds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & my_sb) != my_sb) atomicOr(ds, my_sb);
+    }
 }
 
 inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks(PassGeom g, LocalPassArgs a, PruneState *__restrict__ st, uint8_t *__restrict__ mask,
@@ -74,6 +137,7 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
     __shared__ int s_best[LP_MAX_ROWS];
     __shared__ unsigned short s_queue[LP_WAVES][LP_QCAP], s_exq[LP_WAVES][128];
     __shared__ __attribute__((aligned(16))) float s_rowdesc[LP_WAVES][LP_TI * DW];
+    __shared__ double s_jacobi[LP_WAVES][32];  // the Jacobi fallback of the exact stage (rmsd.hpp: top_eigvec4_mem), per wavefront
     __shared__ unsigned long long s_stat[8];  // block totals of the five statistics
     __shared__ int s_A, s_anydb, s_last, s_open[2];
     static_assert(DW == 16 && LP_TI * DW == 256, "row staging: 4 rows x 16 components per 64 lanes");
@@ -81,25 +145,6 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     TSC_STAMP(0);  // the wavefront has started
-    // the state block of this pass: written by whoever closed the pass before it, or -- that pass was left open (rmsd.hpp,
-    // pass_derive) -- worked out here by every workgroup for itself.  The scan blocks' counts are being decremented by this very
-    // launch: no prefix is derived from them here, the next kernel that opens a pass makes its own
-    int open_on, open_sel;
-    if (dv.prev_st) {
-        if (wid == 0) {
-            const Derived d = pass_derive(dv, st, blockIdx.x == 0, nullptr, 0, nullptr, nullptr);
-            if (lane == 0) s_open[0] = d.pass_on, s_open[1] = d.bitsel;
-        }
-        __syncthreads();
-        open_on = s_open[0], open_sel = s_open[1];
-    } else {
-        open_on = st->pass_on, open_sel = st->bitsel;
-    }
-    const bool pass_on = open_on != 0;
-    // the pass reads one bit copy of the mask and clears the rows it removes in the other (every row of a pass sees the mask
-    // as it was when the pass began, rmsd_pruning.py:151-157, whatever order the workgroups run in)
-    const unsigned long long *mbit = bits + size_t(open_sel) * bit_words;
-    unsigned long long *mbit_next = bits + size_t(open_sel ^ 1) * bit_words;
     // which chunk, and which share of its row tiles
     int c, j, nb;
     {
@@ -114,23 +159,64 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
     const int first = c * g.cs;                                  // :140
     const int L = ((c == g.k - 1) ? g.n : first + g.cs) - first;  // :141-144  (<= LP_MAX_ROWS, checked by the host)
     const int nw = (L + 63) >> 6;
+    // Requested in the round trip the state block takes, not behind it: the run's descriptor bound and this chunk's words of the cache
+    // view and of BOTH bit copies of the mask (which of the two the pass reads is what the state block says; the other one is being
+    // written by this launch and what was read of it is dropped).  All of it was final at the kernel boundary.
+    static_assert(LP_WORDS <= LP_THREADS, "a thread per 64 structures of the chunk");
+    const unsigned dmax_raw = *a.dmax_bits;
+    // (the two words a chunk's 64 structures straddle, as they are: put together behind the round trip.  Every bit copy and view has
+    // words to spare behind its last structure: prune.hip, bit_words)
+    unsigned long long w_copy0[2] = {0ull, 0ull}, w_copy1[2] = {0ull, 0ull}, w_view[2] = {0ull, 0ull};
+    if (tid < nw) {
+        const int64_t w0 = (int64_t(first) >> 6) + tid;
+        w_copy0[0] = bits[w0], w_copy0[1] = bits[w0 + 1];
+        w_copy1[0] = bits[bit_words + w0], w_copy1[1] = bits[bit_words + w0 + 1];
+        if (a.use_cache) w_view[0] = dbit[w0], w_view[1] = dbit[w0 + 1];
+    }
+    // the state block of this pass: written by whoever closed the pass before it, or -- that pass was left open (rmsd.hpp,
+    // pass_derive) -- worked out here by every workgroup for itself.  The scan blocks' counts are being decremented by this very
+    // launch: no prefix is derived from them here, the next kernel that opens a pass makes its own
+    int open_on, open_sel;
+    if (dv.prev_st) {
+        if (wid == 0) {
+            const Derived d = pass_derive(dv, st, blockIdx.x == 0, nullptr, 0, nullptr, nullptr);
+            if (lane == 0) s_open[0] = d.pass_on, s_open[1] = d.bitsel;
+        }
+        __syncthreads();
+        open_on = s_open[0], open_sel = s_open[1];
+    } else {
+        open_on = st->pass_on, open_sel = st->bitsel;
+    }
+    // (the same in every lane, and said so: what is worked out from them -- the bit copies' addresses, the tile counts -- stays scalar)
+    open_on = __builtin_amdgcn_readfirstlane(open_on), open_sel = __builtin_amdgcn_readfirstlane(open_sel);
+    const bool pass_on = open_on != 0;
+    // the pass reads one bit copy of the mask and clears the rows it removes in the other (every row of a pass sees the mask
+    // as it was when the pass began, rmsd_pruning.py:151-157, whatever order the workgroups run in)
+    unsigned long long *mbit_next = bits + size_t(open_sel ^ 1) * bit_words;
     if (tid < 8) s_stat[tid] = 0;
-    unsigned long long n_screened = 0, n_eval = 0, n_exact = 0, n_evaluated = 0, n_removed = 0;
+    int n_eval = 0, n_exact = 0;  // pairs this wavefront formed H for / sent to the exact stage (wave-uniform: kept scalar)
+    [[maybe_unused]] int n_stages = 0;
     int my_screened = 0;  // lanes 0..15 of a wavefront: pairs of its tiles' rows that went through the screen
 
     if (pass_on) {
         // ---- 1. the chunk's mask and cache view as bits; ranks of the active structures.  The other bit copy may lag one pass
         // behind (a superset of this one): and-ing this chunk's words into it brings it up to date, and commutes with the
         // bits other workgroups -- of this very chunk when it is shared -- clear there in step 4
-        if (j == 0 && !a.exch)
-            for (int w = (first >> 6) + tid; w <= ((first + L - 1) >> 6); w += LP_THREADS) atomicAnd(&mbit_next[w], mbit[w]);
-        for (int w = tid; w < nw; w += LP_THREADS) {
-            unsigned long long m = extract64(mbit, int64_t(first) + 64 * w);
-            unsigned long long v = a.use_cache ? extract64(dbit, int64_t(first) + 64 * w) : 0ull;
-            const int rem = L - 64 * w;
+        // (the words are here already: thread t holds word first / 64 + t and the one behind it, which the chunk's last thread adds
+        // where the chunk reaches into it)
+        if (j == 0 && !a.exch && tid < nw) {
+            const int w0 = (first >> 6) + tid;
+            atomicAnd(&mbit_next[w0], open_sel ? w_copy1[0] : w_copy0[0]);
+            if (tid == nw - 1 && w0 + 1 <= ((first + L - 1) >> 6)) atomicAnd(&mbit_next[w0 + 1], open_sel ? w_copy1[1] : w_copy0[1]);
+        }
+        if (tid < nw) {
+            const int sh = first & 63;  // (extract64 of rmsd.hpp on the words already here)
+            auto join = [sh](const unsigned long long (&w)[2]) { return (w[0] >> sh) | (sh ? (w[1] << (64 - sh)) : 0ull); };
+            unsigned long long m = open_sel ? join(w_copy1) : join(w_copy0), v = join(w_view);
+            const int rem = L - 64 * tid;
             if (rem < 64) m &= (1ull << rem) - 1ull, v &= (1ull << rem) - 1ull;
-            s_mb[w] = m;
-            s_db[w] = v;
+            s_mb[tid] = m;
+            s_db[tid] = v;
         }
         if (tid < 2) s_mb[nw + tid] = 0, s_db[nw + tid] = 0;
         __syncthreads();
@@ -145,7 +231,7 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
             s_A = run, s_anydb = any;
         }
         __syncthreads();
-        const int A = s_A;
+        const int A = __builtin_amdgcn_readfirstlane(s_A);
         auto rank_of = [&](int t) { return int(s_wpre[t >> 6]) + __popcll(s_mb[t >> 6] & ((t & 63) ? (~0ull >> (64 - (t & 63))) : 0ull)); };
         for (int t = tid; t < L; t += LP_THREADS)
             if ((s_mb[t >> 6] >> (t & 63)) & 1ull) s_act[rank_of(t)] = (unsigned short)t;
@@ -178,10 +264,14 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
 
         // ---- 3. pairs: one wavefront per (16 rows) x (all their columns), 64 columns at a time
         const int h3 = a.h * 3;
-        const float limit32 = screen_limit32(__uint_as_float(*a.dmax_bits), a.desc_limit);
-        const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+        const float limit32 = screen_limit32(__uint_as_float(dmax_raw), a.desc_limit);
+        // a lane's place among the set bits of a ballot: how many lanes below it are in
+        auto place_in = [](unsigned long long m) __attribute__((always_inline)) {
+            return int(__builtin_amdgcn_mbcnt_hi(unsigned(m >> 32), __builtin_amdgcn_mbcnt_lo(unsigned(m), 0u)));
+        };
         unsigned short *queue = s_queue[wid], *exq = s_exq[wid];
         float *rowdesc = s_rowdesc[wid];
+        double *jac = s_jacobi[wid];
         int tile_no = 0;
         for (int rt = j; rt < n_tiles; rt += nb, ++tile_no) {
             if ((tile_no % LP_WAVES) != wid) continue;  // this block's tiles are dealt round-robin to its wavefronts
@@ -195,21 +285,19 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) cmax = max(cmax, __shfl_xor(cmax, off));
             cmax = __builtin_amdgcn_readfirstlane(cmax);
+            float row_part[4];  // (the rows' descriptors and the first column tile are requested together, the LDS stores come behind both)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int rr = min(r0 + 4 * q + (lane >> 4), A - 1);
-                rowdesc[64 * q + lane] = D[int64_t(first + s_act[rr]) * DW + (lane & 15)];
+                row_part[q] = D[int64_t(first + s_act[rr]) * DW + (lane & 15)];
             }
-            __builtin_amdgcn_wave_barrier();
             int qn = 0, qe = 0;
 
-            auto decode = [&](unsigned e, int &t, int &col, const double *&pp, const double *&pq, double &Gi, double &Gj) __attribute__((always_inline)) {
-                t = int(e >> 12);
-                col = int(e & 0xfffu);
-                const int64_t i = first + s_act[r0 + t], jj = first + s_act[col];
-                pp = heavy + i * h3, pq = heavy + jj * h3;
-                Gi = Gall[i], Gj = Gall[jj];
-            };
+            // The two evaluation stages of the walked kernels (sieve.hpp), in this kernel's own form and with ONE call site each, in the
+            // drain loop behind the column step: a stage's body holds H, the quartic or the rotation in float64, and every further copy
+            // of it was another 5 - 10 KB of code and another set of values for the allocator to keep apart from the screen's.
+            // A queue entry is (row of the tile << 12 | column rank); the structures are held as 32-bit indices, the pointers formed
+            // where they are used.
             auto note_similar = [&](bool sim, int t, int col) __attribute__((always_inline)) {
                 if (sim) atomicMin(&s_best[r0 + t], col);
                 unsigned long long sm = __builtin_amdgcn_ballot_w64(sim);
@@ -220,23 +308,66 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
                 }
             };
             auto exact_stage = [&](int base, int cnt) __attribute__((always_inline)) {
+                LP_STAGE_IN(true);
                 int lpp = 64;
                 while (lpp > 1 && 64 / lpp < cnt) lpp >>= 1;
                 const int grp = lane / lpp, sub = lane - grp * lpp;
-                bool sim = false;
+                bool sim = false, degenerate = false;
                 int t = 0, col = 0;
+                unsigned ent = 0;
                 if (grp < cnt) {
-                    const double *pp, *pq;
-                    double Gi, Gj, H[9], rm, md;
-                    decode(exq[base + grp], t, col, pp, pq, Gi, Gj);
+                    ent = exq[base + grp];
+                    t = int(ent >> 12), col = int(ent & 0xfffu);
+                    const int i = first + s_act[r0 + t], jj = first + s_act[col];
+                    const double *pp = heavy + int64_t(i) * h3, *pq = heavy + int64_t(jj) * h3;
+                    const double Gi = Gall[i], Gj = Gall[jj];
+                    double H[9], e[4];
                     pair_H(pp, pq, a.h, sub, lpp, H);
-                    exact_rmsd_maxdev(pp, pq, a.h, H, Gi, Gj, rm, md, sub, lpp);
-                    sim = sub == 0 && rm < a.thr && md < a.maxdev_thr;  // rmsd_pruning.py:75
+                    if (rotation_quaternion_fast(H, Gi, Gj, e)) {  // (the lanes of a group hold the same H: they branch together)
+                        // (the entry is read and decoded AGAIN behind the quaternion -- a volatile read, so that it is: the two
+                        // pointers and the pair's indices need no registers while the cofactors of the 4x4 are worked out, which is
+                        // where this kernel runs out of them)
+                        const unsigned ent2 = reinterpret_cast<const volatile unsigned short *>(exq)[base + grp];
+                        t = int(ent2 >> 12), col = int(ent2 & 0xfffu);
+                        const int i2 = first + s_act[r0 + t], j2 = first + s_act[col];
+                        double rm, md;
+                        residual_rmsd_maxdev(heavy + int64_t(i2) * h3, heavy + int64_t(j2) * h3, a.h, e, rm, md, sub, lpp);
+                        sim = sub == 0 && rm < a.thr && md < a.maxdev_thr;  // rmsd_pruning.py:75
+                    } else {
+                        degenerate = sub == 0;
+                    }
                 }
                 note_similar(sim, t, col);
+                // A pair whose top eigenvalue is degenerate needs the Jacobi eigen-solver.  In registers its two 4x4 matrices are 64
+                // VGPRs in every lane of every batch (and were this kernel's scratch); as in the walked kernels the whole wavefront
+                // takes such a pair on instead, one at a time: H by all 64 lanes, the solver by lane 0 on an LDS area, the residual
+                // by all lanes again.
+                for (unsigned long long dm = __builtin_amdgcn_ballot_w64(degenerate); dm; dm &= dm - 1) {
+                    const unsigned e1 = unsigned(__builtin_amdgcn_readlane(int(ent), __ffsll((long long)dm) - 1));
+                    const int t2 = int(e1 >> 12), col2 = int(e1 & 0xfffu);
+                    const int i = first + s_act[r0 + t2], jj = first + s_act[col2];
+                    const double *pp = heavy + int64_t(i) * h3, *pq = heavy + int64_t(jj) * h3;
+                    double H[9], e[4], rm, md;
+                    pair_H(pp, pq, a.h, lane, 64, H);
+                    if (lane == 0) {
+                        horn_matrix(H, jac);
+                        top_eigvec4_mem(jac, jac + 16, e);
+                        jac[0] = e[0], jac[1] = e[1], jac[2] = e[2], jac[3] = e[3];
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    e[0] = jac[0], e[1] = jac[1], e[2] = jac[2], e[3] = jac[3];
+                    __builtin_amdgcn_wave_barrier();
+                    residual_rmsd_maxdev(pp, pq, a.h, e, rm, md, lane, 64);
+                    if (rm < a.thr && md < a.maxdev_thr) {  // wave-uniform
+                        if (lane == 0) atomicMin(&s_best[r0 + t2], col2);
+                        alive &= ~(1u << t2);
+                    }
+                }
                 __builtin_amdgcn_wave_barrier();
+                LP_STAGE_OUT();
             };
             auto sign_stage = [&](int base, int cnt) __attribute__((always_inline)) {
+                LP_STAGE_IN(false);
                 int lpp = 64;
                 while (lpp > 1 && 64 / lpp < cnt) lpp >>= 1;
                 const int grp = lane / lpp, sub = lane - grp * lpp;
@@ -245,27 +376,25 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
                 int t = 0, col = 0;
                 if (grp < cnt) {
                     e = queue[base + grp];
-                    const double *pp, *pq;
-                    double Gi, Gj, H[9];
-                    decode(e, t, col, pp, pq, Gi, Gj);
-                    pair_H(pp, pq, a.h, sub, lpp, H);
-                    const int verdict = pair_verdict(H, 0.5 * (Gi + Gj), a.half_h_thr2, a.two_thr2, a.h);
+                    t = int(e >> 12), col = int(e & 0xfffu);
+                    const int i = first + s_act[r0 + t], jj = first + s_act[col];
+                    const double half_sum = 0.5 * (Gall[i] + Gall[jj]);
+                    double H[9];
+                    pair_H(heavy + int64_t(i) * h3, heavy + int64_t(jj) * h3, a.h, sub, lpp, H);
+                    const int verdict = pair_verdict(H, half_sum, a.half_h_thr2, a.two_thr2, a.h);
                     cand = sub == 0 && verdict == PAIR_UNDECIDED;
                     sim = sub == 0 && verdict == PAIR_SIMILAR;
                 }
                 note_similar(sim, t, col);
                 const unsigned long long m = __builtin_amdgcn_ballot_w64(cand);
                 if (m) {
-                    if (cand) exq[qe + __popcll(m & lt_mask)] = (unsigned short)e;
+                    if (cand) exq[qe + place_in(m)] = (unsigned short)e;
                     qe += __popcll(m);
                 }
-                n_eval += cnt;
-                n_exact += __popcll(m);
+                n_eval = __builtin_amdgcn_readfirstlane(n_eval + cnt);
+                n_exact = __builtin_amdgcn_readfirstlane(n_exact + __popcll(m));
                 __builtin_amdgcn_wave_barrier();
-                if (qe >= 64) {
-                    exact_stage(qe - 64, 64);
-                    qe -= 64;
-                }
+                LP_STAGE_OUT();
             };
 
             // column tiles are double-buffered: the gather of the next tile is in flight while this one is screened
@@ -279,9 +408,13 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
                 }
             };
             f32x2 dq[KD], dq_next[KD];
-            load_cols((r0 + 1) & ~63, dq_next);
-            for (int c0 = (r0 + 1) & ~63; c0 < cmax && alive; c0 += 64) {
-                {
+            int c0 = (r0 + 1) & ~63;  // (< cmax: a live row's stop column lies beyond its own rank)
+            load_cols(c0, dq_next);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) rowdesc[64 * q + lane] = row_part[q];
+            __builtin_amdgcn_wave_barrier();
+            for (bool screening = true;;) {
+                if (screening) {
                     const int col = c0 + lane;
 #pragma unroll
                     for (int k = 0; k < KD; ++k) dq[k] = dq_next[k];
@@ -306,26 +439,45 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
                         const bool pass = col > r && col < ce && !(fmaxf(s2.x, s2.y) > limit32);
                         const unsigned long long m = __builtin_amdgcn_ballot_w64(pass);
                         if (m) {
-                            if (pass) queue[qn + __popcll(m & lt_mask)] = (unsigned short)((unsigned(t) << 12) | unsigned(col));
+                            if (pass) queue[qn + place_in(m)] = (unsigned short)((unsigned(t) << 12) | unsigned(col));
                             qn += __popcll(m);
                         }
                     }
+                    c0 += 64;
+                    __builtin_amdgcn_wave_barrier();
                 }
-                __builtin_amdgcn_wave_barrier();
-                while (qn >= 64) {
-                    sign_stage(qn - 64, 64);
-                    qn -= 64;
+                // The drain.  Between column steps: sign batches of 64 from the queue's top while it holds as many, and an exact batch
+                // of 64 as soon as one has gathered (qe < 64 before a sign batch adds at most 64: s_exq holds 128).  Behind the last
+                // column step (screening false): the sign queue's rest, a full exact batch if that made one, the exact queue's rest.
+                auto pending = [&]() __attribute__((always_inline)) { return qe >= 64 || qn >= 64 || (!screening && (qn | qe) != 0); };
+                if (pending()) {
+                    do {
+                        if (qe >= 64 || qn == 0) {
+                            const int cnt = min(qe, 64);
+                            exact_stage(qe - cnt, cnt);
+                            qe -= cnt;
+                        } else {
+                            const int cnt = min(qn, 64);
+                            sign_stage(qn - cnt, cnt);
+                            qn -= cnt;
+                        }
+                    } while (pending());
+                    if (!screening) break;
+                    // (the next tile is requested again behind a drain, clamped like any tile: its 32 registers are the stages' to use)
+                    load_cols(c0, dq_next);
+                } else if (!screening) {
+                    break;
                 }
+                screening = c0 < cmax && alive;
             }
-            if (qn > 0) sign_stage(0, qn);
-            if (qe > 0) exact_stage(0, qe);
         }
         for (int off = 8; off > 0; off >>= 1) my_screened += __shfl_xor(my_screened, off);
-        n_screened = (unsigned long long)my_screened;
+        const unsigned long long n_screened = (unsigned long long)my_screened;
         TSC_STAMP(3);  // this wavefront's pairs evaluated
         __syncthreads();
 
         // ---- 4. apply this block's rows: mask, one cache key per removed row (:69-73), scan counts, evaluation count
+        unsigned long long n_evaluated = 0, n_removed = 0;
         for (int rt = j; rt < n_tiles; rt += nb) {
             const int r = rt * LP_TI + lane;  // one wavefront per tile keeps the ballots simple; tiles dealt as above
             if (((rt - j) / nb) % LP_WAVES != wid) continue;
@@ -358,14 +510,14 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
                 left &= ~same;
             }
             const int n_rm = __popcll(__builtin_amdgcn_ballot_w64(removed));
-            views_insert_wave(cv, removed, first, first + delta);  // the cache keys (:69-73), where later passes will look for them
+            lp_views_insert_wave(cv, removed, first, first + delta);  // the cache keys (:69-73), where later passes will look for them
             for (int off = 32; off > 0; off >>= 1) ev += __shfl_down(ev, off);
             n_evaluated += ev, n_removed += (unsigned long long)n_rm;
         }
         // ---- 5. statistics: one set of atomics per block
         if (lane == 0) {
-            if (n_eval) atomicAdd(&s_stat[CNT_FORMED], n_eval);
-            if (n_exact) atomicAdd(&s_stat[CNT_EXACT], n_exact);
+            if (n_eval) atomicAdd(&s_stat[CNT_FORMED], (unsigned long long)n_eval);
+            if (n_exact) atomicAdd(&s_stat[CNT_EXACT], (unsigned long long)n_exact);
             if (n_screened) atomicAdd(&s_stat[CNT_SCREENED], n_screened);
             if (n_evaluated) atomicAdd(&s_stat[CNT_EVALUATED], n_evaluated);
             if (n_removed) atomicAdd(&s_stat[CNT_REMOVED], n_removed);
@@ -378,6 +530,7 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
     // is left open, the first kernel of the next one closes it behind the kernel boundary (pass_derive)
     if (!tickets) {
         TSC_STAMP(5);
+        LP_STAGE_COUNT();
         return;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
