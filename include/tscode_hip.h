@@ -441,6 +441,35 @@ int tsc_cyclical_embed_groups(tsc_ctx *ctx, const double *frags, const int64_t *
                               double clash_thresh, int64_t max_clashes, double rmsd_thr, uint8_t *clash_ok, uint8_t *kept, double *poses,
                               int64_t poses_capacity, int64_t *n_pass, int64_t *n_kept);
 
+/* tsc_trimolecular_groups: the records tsc_cyclical_embed_groups takes, for THREE molecules under RIGID, produced on the device.  Replaces
+ *   the host loop over (pivot triple, orientation) of tscode/embeds.py:636-655 with _adjust_directions (tscode/embeds.py:312-465) inside it:
+ *   per orientation three align_vec_pair, the 7 turns of -30 .. 30 degrees of six facing atoms, 343 candidates of three vec_angle each
+ *   and their argmin (the first of the smallest), whose displacement vectors are the `directions` of the group AND the input of the triple's
+ *   next orientation.  One wavefront per pivot triple; the orientations of a triple run in order.
+ *   Fragments as in tsc_cyclical_embed_groups (frags / frag_off / n_atoms / n_conf, three of them).  Per molecule: reactive i32[3, 2]
+ *   (n_reactive[m] = 1 or 2 of them used) and the rows (atom index, cumnum) of its reactive atoms, reactive_cumnums i64[sum n_rows, 2] with
+ *   n_rows i32[3], each at most 8.  Per pivot triple t, decided on the host (no comparison of a rounded value is left to the device): conf
+ *   i32[T, 3]; pivot, meanpoint f64[T, 3, 3]; cumnums i64[T, 3, 2] (start atom, end atom of the pivot); tri_poly f64[T, 3, 3] the
+ *   triangle's vertices the polygon's sides are taken from (side m runs from vertex m to vertex m + 1, backwards where the orientation
+ *   says so); tri_cost f64[T, 3, 3] the vertices the candidates are scored against (they differ from tri_poly where a right triangle was
+ *   nudged, :287-293); directions f64[T, 3, 3] of _get_directions; mask u8[T], bit v set where orientation v is embedded (:642); base
+ *   i64[T] the running count of mask bits in front of t.  The group of (t, v) is written at base[t] + (number of set bits of mask[t] below
+ *   v): blocks f64[G, 3, 23] (start, end, direction, pivot, meanpoint, the reactive atoms of conformer conf -- the second a copy of the
+ *   first where there is one --, their number, the conformer), group_ids i64[G, 3, 2] (the sorted cumnum pairs of the three contacts,
+ *   :895-897) and best i32[G], the chosen candidate's row in cartesian_product(range(7), range(7), range(7)).  An orientation left out
+ *   does not touch the directions.  A NaN cost is never chosen (all 343 NaN: candidate 0).
+ *   TSC_ERR_INVALID before anything is launched, the message naming the triple: a null pointer, a conformer or atom index out of range,
+ *   more than 8 table rows, a base that is not the running count or n_groups that is not its total, and -- for a triple with a
+ *   non-empty mask -- a pivot cumnum that no molecule's reactive_cumnums holds.  n_triples = 0 succeeds and writes nothing.
+ * tsc_trimolecular_groups_timings: under the context option "pass_timing" >= 1 the call times its kernel with events (and synchronises
+ *   for it); *ms = that time for the calling thread's latest call, -1 where none was taken. */
+int tsc_trimolecular_groups(tsc_ctx *ctx, const double *frags, const int64_t *frag_off, const int32_t *n_atoms, const int32_t *n_conf,
+                            const int32_t *reactive, const int32_t *n_reactive, const int64_t *reactive_cumnums, const int32_t *n_rows,
+                            const int32_t *conf, const double *pivot, const double *meanpoint, const int64_t *cumnums, const double *tri_poly,
+                            const double *tri_cost, const double *directions, const uint8_t *mask, const int64_t *base, int64_t n_triples,
+                            int64_t n_groups, double *blocks, int64_t *group_ids, int32_t *best);
+int tsc_trimolecular_groups_timings(tsc_ctx *ctx, float *ms);
+
 /* HOST-side helper (no device, no context): the graph step of tscode/numba_functions.py:201-226 (prune_conformers_tfd) and
  * tscode/optimization_methods.py:341-358 (prune_by_moment_of_inertia) for any number of chunks: the matches (rel_i[q], rel_j[q]),
  * q in [chunk_ptr[c], chunk_ptr[c+1]), of chunk c are node indices relative to the chunk (0 <= index < chunk_len[c]), listed in the

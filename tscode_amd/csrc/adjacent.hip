@@ -8,6 +8,7 @@
 #include "tfd.hpp"
 #include "moi.hpp"
 #include "host_order.hpp"
+#include "trimolecular.hpp"
 
 // --------------------------------------------------------------------------------------------------
 // greedy per-group filter
@@ -800,5 +801,113 @@ extern "C" __attribute__((visibility("default"))) int tsc_cyclical_embed_groups(
     };
     return embed_filter_run(c, h, d_frags, ft, frag_off, n_atoms, n_conf, d_ci, d_rot, d_pos, n_poses, clash_thresh, max_clashes, clash_ok, kept, poses,
                             poses_capacity, n_pass, n_kept, filter);
+    TSC_API_GUARD_END
+}
+
+// --------------------------------------------------------------------------------------------------
+// the groups of a three-molecule cyclical embed (trimolecular.hpp; tscode/embeds.py:312-465 inside the loop of :636-655)
+
+// HIP-event time of the kernel of the calling thread's latest tsc_trimolecular_groups, taken only under the context option "pass_timing" >= 1
+// (tools/trimolecular_profile.py); -1 otherwise
+static thread_local float g_trimolecular_ms = -1.f;
+
+extern "C" __attribute__((visibility("default"))) int tsc_trimolecular_groups_timings(tsc_ctx *c, float *ms) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(c && ms, "tsc_trimolecular_groups_timings: null argument");
+    *ms = g_trimolecular_ms;
+    return 0;
+    TSC_API_GUARD_END
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_trimolecular_groups(
+    tsc_ctx *c, const double *frags, const int64_t *frag_off, const int32_t *n_atoms, const int32_t *n_conf, const int32_t *reactive, const int32_t *n_reactive,
+    const int64_t *reactive_cumnums, const int32_t *n_rows, const int32_t *conf, const double *pivot, const double *meanpoint, const int64_t *cumnums,
+    const double *tri_poly, const double *tri_cost, const double *directions, const uint8_t *mask, const int64_t *base, int64_t n_triples, int64_t n_groups,
+    double *blocks, int64_t *group_ids, int32_t *best) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(c && frags && frag_off && n_atoms && n_conf && reactive && n_reactive && reactive_cumnums && n_rows, "tsc_trimolecular_groups: null argument");
+    TSC_REQUIRE(n_triples >= 0 && n_groups >= 0 && n_groups < INT32_MAX, "tsc_trimolecular_groups: %lld triples, %lld groups", (long long)n_triples,
+                (long long)n_groups);
+    FragTable ft;
+    TSC_TRY(make_frag_table(frag_off, n_atoms, n_conf, 3, &ft));
+    TriTables tb;
+    memset(&tb, 0, sizeof(tb));
+    const int64_t *row = reactive_cumnums;
+    for (int m = 0; m < 3; ++m) {
+        tb.frag_off[m] = frag_off[m], tb.n_atoms[m] = n_atoms[m], tb.n_reactive[m] = n_reactive[m], tb.n_rows[m] = n_rows[m];
+        TSC_REQUIRE(n_reactive[m] == 1 || n_reactive[m] == 2, "tsc_trimolecular_groups: molecule %d has %d reactive atoms, must be 1 or 2", m, n_reactive[m]);
+        for (int k = 0; k < n_reactive[m]; ++k) {
+            TSC_REQUIRE(reactive[2 * m + k] >= 0 && reactive[2 * m + k] < n_atoms[m], "tsc_trimolecular_groups: reactive atom %d of molecule %d with %d atoms",
+                        reactive[2 * m + k], m, n_atoms[m]);
+            tb.reactive[m][k] = reactive[2 * m + k];
+        }
+        TSC_REQUIRE(n_rows[m] >= 0 && n_rows[m] <= TG_MAX_ROWS, "tsc_trimolecular_groups: molecule %d has %d reactive_cumnums rows, at most %d are taken", m,
+                    n_rows[m], TG_MAX_ROWS);
+        for (int r = 0; r < n_rows[m]; ++r, row += 2) {
+            TSC_REQUIRE(row[0] >= 0 && row[0] < n_atoms[m], "tsc_trimolecular_groups: reactive_cumnums row %d of molecule %d names atom %lld of %d", r, m,
+                        (long long)row[0], n_atoms[m]);
+            tb.row_atom[m][r] = int(row[0]), tb.row_cum[m][r] = row[1];
+        }
+    }
+    g_trimolecular_ms = -1.f;
+    if (n_triples == 0) {
+        TSC_REQUIRE(n_groups == 0, "tsc_trimolecular_groups: %lld groups from no triple", (long long)n_groups);
+        return 0;
+    }
+    TSC_REQUIRE(conf && pivot && meanpoint && cumnums && tri_poly && tri_cost && directions && mask && base, "tsc_trimolecular_groups: null argument");
+    TSC_REQUIRE(n_groups == 0 || (blocks && group_ids && best), "tsc_trimolecular_groups: null output");
+    // a group's slot is base[triple] + the orientation's rank among the mask's bits: the bases must be the masks' running count, or a record
+    // would land outside the outputs
+    int64_t running = 0;
+    for (int64_t t = 0; t < n_triples; ++t) {
+        TSC_REQUIRE(base[t] == running, "tsc_trimolecular_groups: triple %lld: base %lld, the orientation masks in front of it count %lld", (long long)t,
+                    (long long)base[t], (long long)running);
+        running += __builtin_popcount(mask[t]);
+        for (int m = 0; m < 3; ++m)
+            TSC_REQUIRE(conf[3 * t + m] >= 0 && conf[3 * t + m] < n_conf[m], "tsc_trimolecular_groups: triple %lld, molecule %d: conformer %d of %d",
+                        (long long)t, m, conf[3 * t + m], n_conf[m]);
+        if (!mask[t]) continue;
+        // over the orientations every cumnum of the three pivots turns up in some pair of `ids`: each must be some molecule's reactive atom
+        for (int q = 0; q < 6; ++q) {
+            bool found = false;
+            for (int m = 0; m < 3 && !found; ++m)
+                for (int r = 0; r < tb.n_rows[m] && !found; ++r) found = tb.row_cum[m][r] == cumnums[6 * t + q];
+            TSC_REQUIRE(found, "tsc_trimolecular_groups: triple %lld: cumnum %lld of molecule %d's pivot is in no molecule's reactive_cumnums", (long long)t,
+                        (long long)cumnums[6 * t + q], q / 2);
+        }
+    }
+    TSC_REQUIRE(running == n_groups, "tsc_trimolecular_groups: the orientation masks count %lld groups, n_groups is %lld", (long long)running, (long long)n_groups);
+    if (n_groups == 0) return 0;
+    HostCall h(c);
+    const size_t T = size_t(n_triples), G = size_t(n_groups);
+    const double *d_frags, *d_pivot, *d_mean, *d_poly, *d_cost, *d_dir;
+    const int32_t *d_conf;
+    const int64_t *d_cum, *d_base;
+    const uint8_t *d_mask;
+    double *d_blocks;
+    int64_t *d_ids;
+    int32_t *d_best;
+    TSC_TRY(h.in(frags, size_t(frags_total_doubles(frag_off, n_atoms, n_conf, 3)), &d_frags));
+    TSC_TRY(h.in(conf, T * 3, &d_conf));
+    TSC_TRY(h.in(pivot, T * 9, &d_pivot));
+    TSC_TRY(h.in(meanpoint, T * 9, &d_mean));
+    TSC_TRY(h.in(cumnums, T * 6, &d_cum));
+    TSC_TRY(h.in(tri_poly, T * 9, &d_poly));
+    TSC_TRY(h.in(tri_cost, T * 9, &d_cost));
+    TSC_TRY(h.in(directions, T * 9, &d_dir));
+    TSC_TRY(h.in(mask, T, &d_mask));
+    TSC_TRY(h.in(base, T, &d_base));
+    TSC_TRY(h.out(blocks, G * 3 * TG_RECORD, &d_blocks));
+    TSC_TRY(h.out(group_ids, G * 6, &d_ids));
+    TSC_TRY(h.out(best, G, &d_best));
+    StageTimer tm(c);
+    tm.begin();
+    // a wavefront per triple, TG_WAVES per workgroup; 512 workgroups are two per CU, and more triples than that are walked in further passes
+    hipLaunchKernelGGL(k_trimolecular_groups, dim3(grid_for(n_triples, TG_WAVES, 512)), dim3(64 * TG_WAVES), 0, c->stream, d_frags, tb, d_conf, d_pivot, d_mean,
+                       d_cum, d_poly, d_cost, d_dir, d_mask, d_base, n_triples, d_blocks, d_ids, d_best);
+    const hipError_t launched = hipGetLastError();
+    if (launched == hipSuccess) tm.end(&g_trimolecular_ms);
+    TSC_HIP(launched);
+    return h.finish();
     TSC_API_GUARD_END
 }

@@ -7,6 +7,8 @@ get_embed per pose: all (R, t) of a run are built on the host, then K1 (+K2) run
 
 from __future__ import annotations
 
+import types
+
 import numpy as np
 
 from .algebra import align_vec_pair, norm, rot_mat_from_pointer, rotation_matrix_from_vectors, vec_angle  # noqa: F401  (host-side singles, re-exported)
@@ -14,7 +16,7 @@ from .engine import FragmentSet, get_engine
 from .utils import cartesian_product, polygonize
 
 __all__ = ["get_embed", "embed_batch", "string_embed_poses", "filter_angular_groups", "string_embed_batch", "cyclical_embed_batch",
-           "EmbedTrace", "string_embed", "cyclical_embed"]
+           "trimolecular_groups_batch", "EmbedTrace", "string_embed", "cyclical_embed"]
 
 
 def get_embed(mols, conf_ids):
@@ -127,6 +129,20 @@ def string_embed_batch(coords1, coords2, centers1, orb_vecs1, centers2, orb_vecs
 
 
 MAX_GROUP_POSES = 8192      # poses per (conformers, pivots, orientation) group that tsc_cyclical_embed takes (GF_MAX_GROUP, group_filter.hpp)
+
+# Poses per tsc_cyclical_embed_groups call.  On the device a candidate pose costs n_mols * 100 B of parameters (rotation 72 B, position 24 B,
+# conformer index 4 B per molecule) and about 20 B of masks and scans; a pose that passes the clash check costs n * 24 B of coordinates
+# (twice while the kept ones are gathered).  For two molecules of 40 atoms with a quarter of the poses passing that is 220 + 0.25 * 3840 B
+# = 1.2 kB per candidate: 2^20 candidates take about 1.2 GB of the device's 288 GB and leave the host's output array (n * 24 B per
+# candidate, touched only for the kept rows) at 2 GB of address space -- large enough that a 144-arrangement multiembed is a handful of calls,
+# small enough to sit beside whatever else the process keeps on the device.
+DEFAULT_MAX_POSES_PER_CALL = 1 << 20
+
+
+def _slabs(n_groups, A, max_poses):
+    """Whole groups of A poses in runs of at most max_poses poses (at least one group): [(first, end), ...]."""
+    per = max(1, int(max_poses) // max(A, 1))
+    return [(at, min(at + per, n_groups)) for at in range(0, n_groups, per)]
 
 
 def _in_constraints(pair, internal_constraints):
@@ -273,8 +289,179 @@ def _trimolecular_groups(coords, reactive, pivots, cumnums, pairings, internal_c
     return (np.array(blocks).reshape(-1, 3, 23), np.array(group_ids, dtype=np.int64).reshape(-1, 3, 2), group_meta)
 
 
+# ---- the same groups with the per-group part on the device.  What follows is per pivot TRIPLE, for all triples at once; the eight orientations
+# of a triple and _adjust_directions3 inside them are tsc_trimolecular_groups (csrc/trimolecular.hpp).
+#
+# The arrays must come out bit-equal to _triangle3 / _polygonize3 / _directions3, whose operands are NumPy SCALARS: a scalar's `x ** 2` and
+# `x ** 0.5` are the C library's pow(), while an array's `**` takes np.square / np.sqrt for those exponents and np.power may take a vector
+# library's pow -- neither agrees with pow() to the last bit.  np.float_power has the one plain loop around pow(): that is what stands for `**`
+# below.  vec_angle's np.dot and math.acos have no array twin that agrees to the last bit, and all that is read of them is `> 90`: the arrays
+# decide wherever the angle is further than _ANGLE_BAND from 90 degrees (rounding moves it by some 1e-14), the loop's own function elsewhere.
+_ANGLE_BAND = 1e-6
+MAX_CUMNUM_ROWS = 8        # rows of a molecule's reactive_cumnums that tsc_trimolecular_groups takes (TG_MAX_ROWS, trimolecular.hpp)
+
+
+def _pow(x, e):
+    return np.float_power(x, e)
+
+
+def _triangle3_all(norms):
+    """_triangle3 for norms f64[K, 3]: f64[K, 3, 3]."""
+    a, b, c = _pow(norms[:, 0], 2.0), _pow(norms[:, 1], 2.0), _pow(norms[:, 2], 2.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        x = (a - b + c) / (2 * _pow(a, 0.5))
+        y = _pow(c - _pow(x, 2.0), 0.5)
+    tri = np.zeros((len(norms), 3, 3))
+    tri[:, 1, 0], tri[:, 2, 0], tri[:, 2, 1] = norms[:, 0], x, y
+    return tri
+
+
+def _obtuse_all(p, q):
+    """_plane_angle(p[k], q[k]) > 90 for plane vectors f64[K, 2]: bool[K]."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        pn = p / np.sqrt(p[:, 0] * p[:, 0] + p[:, 1] * p[:, 1])[:, None]
+        qn = q / np.sqrt(q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1])[:, None]
+        angle = np.degrees(np.arccos(np.clip(pn[:, 0] * qn[:, 0] + pn[:, 1] * qn[:, 1], -1.0, 1.0)))
+        out = angle > 90
+        near = ~(np.abs(angle - 90) >= _ANGLE_BAND)                                                  # (a NaN is "near" too)
+    for k in np.nonzero(near)[0]:
+        out[k] = _plane_angle(p[k], q[k]) > 90
+    return out
+
+
+def _directions3_all(norms):
+    """_directions3 for norms f64[K, 3], nudged in place where it nudges: f64[K, 3, 3]."""
+    K = len(norms)
+    v = _triangle3_all(norms)[:, :, :2]
+    a, b, c = v[:, 1, 0], v[:, 2, 0], v[:, 2, 1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cc = np.stack([a / 2, (_pow(b, 2.0) + _pow(c, 2.0) - a * b) / (2 * c)], axis=1)
+    d = np.stack([cc - (v[:, 0] + v[:, 1]) / 2, cc - (v[:, 1] + v[:, 2]) / 2, cc - (v[:, 2] + v[:, 0]) / 2], axis=1)          # [K, 3, 2]
+    right = (d == 0).all(axis=2).any(axis=1)
+    if right.any():                                                                                  # :287-293, and again if the nudged one is right too
+        nudged = norms[right]
+        nudged[:, 0] += 1e-5
+        d[right] = _directions3_all(nudged)[:, :, :2]
+        norms[right] = nudged
+    obtuse = (_obtuse_all(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]), _obtuse_all(v[:, 0] - v[:, 1], v[:, 2] - v[:, 1]),
+              _obtuse_all(v[:, 0] - v[:, 2], v[:, 1] - v[:, 2]))
+    flip = (obtuse[2], obtuse[0], obtuse[1])                                                         # :299-301
+    out = np.zeros((K, 3, 3))
+    for i in range(3):
+        out[:, i, :2] = np.where(flip[i][:, None], -d[:, i], d[:, i])
+    x, y, z = out[:, :, 0], out[:, :, 1], out[:, :, 2]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return out / np.sqrt(x * x + y * y + z * z)[:, :, None]                                      # norm(out[i])
+
+
+def _trimolecular_prologue(coords, reactive, pivots, cumnums, pairings, internal_constraints):
+    """Everything _trimolecular_groups works out per pivot triple, for all triples that pass the triangle test at once, in its loop's order:
+    ``conf`` / ``pivot_index`` i32[T, 3]; ``pivot`` / ``meanpoint`` f64[T, 3, 3]; ``cumnums`` i64[T, 3, 2]; ``norms`` f64[T, 3] as :487 takes them
+    and ``norms_cost`` after _directions3's nudge; ``tri_poly`` / ``tri_cost`` f64[T, 3, 3] = _triangle3 of either; ``poly`` f64[T, 8, 3, 2, 3] =
+    _polygonize3(norms); ``directions`` f64[T, 3, 3] = _directions3; ``ids`` i64[T, 8, 3, 2] the facing cumnums of every orientation; ``take``
+    bool[T, 8] the orientations the pairings leave (:642) and ``mask`` u8[T] its bits, orientation 0 lowest.  No device work."""
+    conf_l, pi_l, pv_l, mp_l, cum_l, nrm_l = [], [], [], [], [], []
+    lengths = {}                                                                                     # np.linalg.norm per pivot, as the loop calls it (:487)
+    for conf_ids in cartesian_product(*[np.arange(len(c)) for c in coords]):
+        pv = [pivots[m][conf_ids[m]] for m in range(3)]
+        vec = [np.asarray(q[0], dtype=np.float64).reshape(-1, 3) for q in pv]
+        mean = [np.asarray(q[1], dtype=np.float64).reshape(-1, 3) for q in pv]
+        cum = [np.asarray(q[2]).reshape(-1, 2) for q in pv]
+        pi = cartesian_product(*[np.arange(len(v)) for v in vec])
+        if not len(pi):
+            continue
+        for m in range(3):
+            if (m, int(conf_ids[m])) not in lengths:
+                lengths[m, int(conf_ids[m])] = np.array([np.linalg.norm(q) for q in vec[m]])
+        conf_l.append(np.tile(np.asarray(conf_ids, dtype=np.int32), (len(pi), 1))), pi_l.append(pi.astype(np.int32))
+        pv_l.append(np.stack([vec[m][pi[:, m]] for m in range(3)], axis=1)), mp_l.append(np.stack([mean[m][pi[:, m]] for m in range(3)], axis=1))
+        cum_l.append(np.stack([cum[m][pi[:, m]] for m in range(3)], axis=1).astype(np.int64))
+        nrm_l.append(np.stack([lengths[m, int(conf_ids[m])][pi[:, m]] for m in range(3)], axis=1))
+    if conf_l:
+        conf, pidx, pivot, meanpoint, cum, norms = (np.concatenate(x) for x in (conf_l, pi_l, pv_l, mp_l, cum_l, nrm_l))
+        ok = (norms[:, 0] < norms[:, 2] + norms[:, 1]) & (norms[:, 1] < norms[:, 0] + norms[:, 2]) & (norms[:, 2] < norms[:, 1] + norms[:, 0])
+        conf, pidx, pivot, meanpoint, cum, norms = (np.ascontiguousarray(x[ok]) for x in (conf, pidx, pivot, meanpoint, cum, norms))
+    else:
+        conf, pidx, cum = np.zeros((0, 3), np.int32), np.zeros((0, 3), np.int32), np.zeros((0, 3, 2), np.int64)
+        pivot, meanpoint, norms = np.zeros((0, 3, 3)), np.zeros((0, 3, 3)), np.zeros((0, 3))
+    T = len(conf)
+    tri_poly = _triangle3_all(norms)                                                                 # (before the nudge: _polygonize3 comes first)
+    poly = np.zeros((T, 8, 3, 2, 3))
+    for m in range(3):
+        poly[:, :, m, 0], poly[:, :, m, 1] = tri_poly[:, None, m], tri_poly[:, None, (m + 1) % 3]
+    for t, m in _SWAPS3:
+        poly[:, t, m] = poly[:, t, m, ::-1].copy()
+    norms_cost = norms.copy()
+    directions = _directions3_all(norms_cost)
+    tri_cost = _triangle3_all(norms_cost)
+    c3 = np.where(_ORIENT3[None, :, :, None], cum[:, None, :, ::-1], cum[:, None, :, :])               # [T, 8, 3, 2]
+    ids = np.sort(np.stack([np.stack([c3[:, :, 0, 1], c3[:, :, 1, 0]], -1), np.stack([c3[:, :, 1, 1], c3[:, :, 2, 0]], -1),
+                            np.stack([c3[:, :, 2, 1], c3[:, :, 0, 0]], -1)], axis=2), axis=-1)                   # :895-897
+    take = np.ones((T, 8), dtype=bool)
+    for pair in pairings or ():                                                                      # :642, every group at once
+        if not _in_constraints(pair, internal_constraints):
+            take &= (ids == np.asarray(pair, dtype=np.int64)).all(axis=-1).any(axis=-1)
+    mask = np.packbits(take, axis=1, bitorder="little").reshape(-1)
+    return types.SimpleNamespace(conf=conf, pivot_index=pidx, pivot=pivot, meanpoint=meanpoint, cumnums=cum, norms=norms, norms_cost=norms_cost,
+                                 tri_poly=tri_poly, tri_cost=tri_cost, poly=poly, directions=directions, ids=ids, take=take, mask=mask)
+
+
+def _trimolecular_inputs(mols):
+    get = lambda m, k: m[k] if isinstance(m, dict) else getattr(m, k)
+    if len(mols) != 3:
+        raise ValueError("three molecules")
+    coords = [np.ascontiguousarray(get(m, "coords"), dtype=np.float64) for m in mols]
+    reactive = [np.atleast_1d(np.asarray(get(m, "reactive_indices"), dtype=np.int64)) for m in mols]
+    pivots = [get(m, "pivots") for m in mols]
+    cumnums = [np.asarray(get(m, "reactive_cumnums"), dtype=np.int64).reshape(-1, 2) for m in mols]
+    return coords, reactive, pivots, cumnums
+
+
+def trimolecular_groups_batch(mols, pairings=None, internal_constraints=()):
+    """The (conformers, pivots, orientation) groups of a three-molecule cyclical embed under RIGID (tscode/embeds.py:470-655 with
+    _adjust_directions, :312-465) in ONE library call: what ``_trimolecular_groups`` walks group by group on the host.
+
+    mols as ``cyclical_embed_batch`` takes three of them (coords, reactive_indices, pivots, reactive_cumnums).  Per pivot triple the host takes
+    the decisions (``_trimolecular_prologue``); per orientation the device aligns the molecules, scores the 343 turns and carries the chosen
+    ``directions`` over to the triple's next orientation (``tsc_trimolecular_groups``).
+
+    Returns a namespace of arrays over the G groups, in the loop's order: ``blocks`` f64[G, 3, 23] (the records ``Engine.cyclical_embed_groups``
+    takes: start 0:3, end 3:6, direction 6:9, pivot 9:12, meanpoint 12:15, the reactive atoms 15:18 and 18:21, their number 21, the conformer
+    22), ``group_ids`` i64[G, 3, 2], ``conf`` i32[G, 3], ``pivot_index`` i32[G, 3], ``orientation`` u8[G], ``best`` i32[G] (the chosen row of
+    _ADJUST_ANGLES).  ValueError before the library is asked: an atom index out of range, more than 8 rows in a ``reactive_cumnums``, a pivot
+    cumnum that no ``reactive_cumnums`` holds (where the host loop dies on ``None``)."""
+    coords, reactive, pivots, cumnums = _trimolecular_inputs(mols)
+    for m in range(3):
+        if coords[m].ndim != 3 or coords[m].shape[2] != 3 or not coords[m].shape[0] or not coords[m].shape[1]:
+            raise ValueError(f"molecule {m}: coords must be (n_conf, n_atoms, 3)")
+        n = coords[m].shape[1]
+        if len(reactive[m]) not in (1, 2) or reactive[m].min() < 0 or reactive[m].max() >= n:
+            raise ValueError(f"molecule {m}: 1 or 2 reactive atoms below {n}, not {reactive[m].tolist()}")
+        if len(cumnums[m]) > MAX_CUMNUM_ROWS:
+            raise ValueError(f"molecule {m}: {len(cumnums[m])} rows of reactive_cumnums, at most {MAX_CUMNUM_ROWS} are taken")
+        if len(cumnums[m]) and (cumnums[m][:, 0].min() < 0 or cumnums[m][:, 0].max() >= n):
+            raise ValueError(f"molecule {m}: reactive_cumnums names an atom that is not below {n}")
+        if len(pivots[m]) != len(coords[m]):
+            raise ValueError(f"molecule {m}: {len(pivots[m])} pivot lists for {len(coords[m])} conformers")
+    pro = _trimolecular_prologue(coords, reactive, pivots, cumnums, pairings, internal_constraints)
+    known = np.concatenate([c[:, 1] for c in cumnums])
+    lost = ~np.isin(pro.cumnums, known) & (pro.mask != 0)[:, None, None]
+    if lost.any():
+        t, m, k = (int(x[0]) for x in np.nonzero(lost))
+        raise ValueError(f"conformers {pro.conf[t].tolist()}, pivots {pro.pivot_index[t].tolist()}: cumnum {int(pro.cumnums[t, m, k])} of molecule {m}'s "
+                         "pivot is in no molecule's reactive_cumnums")
+    t_of, v_of = np.nonzero(pro.take)                                                                 # (row-major: the loop's order)
+    if not len(t_of):
+        blocks, ids, best = np.zeros((0, 3, 23)), np.zeros((0, 3, 2), dtype=np.int64), np.zeros(0, dtype=np.int32)
+    else:
+        blocks, ids, best, _ = get_engine().trimolecular_groups(FragmentSet(coords), reactive, cumnums, pro.conf, pro.pivot, pro.meanpoint, pro.cumnums,
+                                                                pro.tri_poly, pro.tri_cost, pro.directions, pro.mask)
+    return types.SimpleNamespace(blocks=blocks, group_ids=ids, conf=pro.conf[t_of], pivot_index=pro.pivot_index[t_of], orientation=v_of.astype(np.uint8),
+                                 best=best)
+
+
 def cyclical_embed_batch(mols, systematic_angles, clash_thresh=1.5, max_clashes=0, rigid_shortcut=True, max_norm_delta=5, pairings=None,
-                         internal_constraints=(), rmsd_thr=1, return_trace=False):
+                         internal_constraints=(), rmsd_thr=1, return_trace=False, groups_on="device", max_poses_per_call=DEFAULT_MAX_POSES_PER_CALL):
     """The loops of a BImolecular ``cyclical_embed`` (tscode/embeds.py:470-732, rigid shortcut :734-860) in one GPU call.
 
     Per (conformer pair, pivot pair) the reference takes the pivots' lengths, ``polygonize``s them into two orientations of two
@@ -303,7 +490,10 @@ def cyclical_embed_batch(mols, systematic_angles, clash_thresh=1.5, max_clashes=
     mol.reactive_atoms_classes_dict[0].items()]``).  UNPINNED WHERE THE REFERENCE IS UNDEFINED: its ``_get_directions`` calls ``vec_angle``
     on 2-vectors (:297-299) and ``algebra.norm`` reads ``vec[2]`` of them (tscode/algebra.py:87) -- an unchecked out-of-bounds read under
     Numba, an IndexError as plain NumPy.  This driver takes the intended reading (z = 0); fixture G18 is the reference's own code run with
-    that one change.  ``rigid_shortcut`` / ``max_norm_delta`` do not apply to three molecules.
+    that one change.  ``rigid_shortcut`` / ``max_norm_delta`` do not apply to three molecules.  Their groups come from
+    ``trimolecular_groups_batch`` (one call) and go to ``tsc_cyclical_embed_groups`` as one record per (group, molecule), in slabs of whole groups
+    of at most ``max_poses_per_call`` poses; ``groups_on="host"`` takes the host loop ``_trimolecular_groups`` and one row per (pose, molecule)
+    instead -- the same result, kept as the yardstick.
     """
     get = lambda m, k: m[k] if isinstance(m, dict) else getattr(m, k)
     if len(mols) not in (2, 3):
@@ -316,6 +506,13 @@ def cyclical_embed_batch(mols, systematic_angles, clash_thresh=1.5, max_clashes=
     A = len(angles)
     if A > MAX_GROUP_POSES:
         raise ValueError(f"{A} angle sets per group: tsc_cyclical_embed takes groups of up to {MAX_GROUP_POSES} poses (rotation steps up to 89)")
+    if groups_on not in ("device", "host"):
+        raise ValueError("groups_on is 'device' or 'host'")
+    if n_mols == 3 and groups_on == "device":
+        g = trimolecular_groups_batch(mols, pairings, internal_constraints)
+        return _run_group_records(coords, g.blocks, g.group_ids, angles, clash_thresh, max_clashes, rmsd_thr, max_poses_per_call,
+                                  (lambda: [(tuple(int(c) for c in g.conf[q]), tuple(int(i) for i in g.pivot_index[q]), int(g.orientation[q]),
+                                             g.group_ids[q].tolist()) for q in range(len(g.blocks))]) if return_trace else None)
     if n_mols == 3:
         cumnums = [np.asarray(get(m, "reactive_cumnums"), dtype=np.int64).reshape(-1, 2) for m in mols]
         blocks3, group_ids3, meta3 = _trimolecular_groups(coords, reactive, pivots, cumnums, pairings, internal_constraints)
@@ -429,6 +626,34 @@ def _bimolecular_groups(coords, reactive, pivots, rigid_shortcut=True, max_norm_
     blocks = np.concatenate(blocks) if n_groups else np.zeros((0, 2, 23))                            # [group, molecule, field]
     group_ids = np.concatenate(group_ids) if n_groups else np.zeros((0, 2, 2), dtype=np.int64)
     return blocks, group_ids, group_meta
+
+
+def _run_group_records(coords, blocks, group_ids, angles, clash_thresh, max_clashes, rmsd_thr, max_poses_per_call, trace_groups=None):
+    """The groups' records as they are -> tsc_cyclical_embed_groups, one record per (group, molecule) and ONE angle table, in slabs of whole
+    groups holding at most ``max_poses_per_call`` poses (groups are independent: the result does not depend on the slab size).  What
+    ``_run_cyclical_groups`` returns; the trace's per-group tuples come from ``trace_groups()`` and only where a trace is wanted."""
+    if int(max_poses_per_call) < 1:
+        raise ValueError("max_poses_per_call must be at least 1")
+    n_mols, A, G = len(coords), len(angles), len(blocks)
+    n_total = sum(c.shape[1] for c in coords)
+    frags = FragmentSet(coords)
+    eng = get_engine() if G else None
+    field = lambda lo, hi, dtype=np.float64: np.ascontiguousarray(blocks[:, :, lo:hi], dtype=dtype)
+    fields = [field(lo, lo + 3) for lo in range(0, 21, 3)]
+    n_reactive, conf_idx = field(21, 22, np.int32).reshape(G, n_mols), field(22, 23, np.int32).reshape(G, n_mols)
+    ok_parts, kept_parts, pose_parts = [], [], []
+    for at, end in _slabs(G, A, max_poses_per_call):
+        ok, kept, poses = eng.cyclical_embed_groups(frags, *[f[at:end] for f in fields], n_reactive[at:end], conf_idx[at:end], angles, clash_thresh, max_clashes,
+                                                    rmsd_thr)
+        ok_parts.append(ok), kept_parts.append(kept), pose_parts.append(poses)
+    ok = np.concatenate(ok_parts) if ok_parts else np.zeros(0, bool)
+    kept = np.concatenate(kept_parts) if kept_parts else np.zeros(0, bool)
+    poses = np.concatenate(pose_parts) if pose_parts else np.zeros((0, n_total, 3))
+    group_of = np.repeat(np.arange(G), A)
+    constrained = group_ids[group_of[kept]].reshape(-1, n_mols, 2)                                   # :718
+    if trace_groups is not None:
+        return poses, constrained, EmbedTrace(clash_ok=ok, kept=kept, group_of=group_of, groups=trace_groups())
+    return poses, constrained
 
 
 def _run_cyclical_groups(coords, blocks, group_ids, group_meta, angles, clash_thresh, max_clashes, rmsd_thr, return_trace, flat_meta=False):

@@ -509,6 +509,44 @@ class Engine:
                                                  C.c_double(float(rmsd_thr)), ptr(ok), ptr(kept), ptr(poses), C.c_int64(N), C.byref(n_pass), C.byref(n_kept)))
         return ok.astype(bool), kept.astype(bool), (poses[:n_kept.value].copy() if want_poses else None)
 
+    def trimolecular_groups(self, frags: FragmentSet, reactive, reactive_cumnums, conf, pivot, meanpoint, cumnums, tri_poly, tri_cost, directions, mask):
+        """tsc_trimolecular_groups: the 23-field records of a three-molecule cyclical embed from per-triple arrays (tscode/embeds.py:312-465 inside
+        :636-655).  ``reactive[m]`` 1 or 2 atom indices, ``reactive_cumnums[m]`` int[R <= 8, 2] = (atom, cumnum); per pivot triple ``conf`` i32[T, 3],
+        ``pivot`` / ``meanpoint`` f64[T, 3, 3], ``cumnums`` i64[T, 3, 2], ``tri_poly`` / ``tri_cost`` f64[T, 3, 3] (the triangle before / after a right
+        triangle's nudge), ``directions`` f64[T, 3, 3], ``mask`` u8[T] (bit v: orientation v is embedded).  Returns ``(blocks f64[G, 3, 23], group_ids
+        i64[G, 3, 2], best i32[G], base i64[T])``, the groups compacted in (triple, orientation) order, ``base`` the first group of every triple."""
+        if frags.n_mols != 3:
+            raise ValueError("trimolecular_groups takes three fragments")
+        react = np.zeros((3, 2), dtype=np.int32)
+        n_react = np.zeros(3, dtype=np.int32)
+        for m in range(3):
+            r = np.atleast_1d(np.asarray(reactive[m], dtype=np.int64))
+            if r.ndim != 1 or len(r) not in (1, 2):
+                raise ValueError(f"molecule {m}: 1 or 2 reactive atoms, not {r.shape}")
+            react[m, :len(r)], n_react[m] = r, len(r)
+        tables = [np.asarray(t, dtype=np.int64).reshape(-1, 2) for t in reactive_cumnums]
+        n_rows = np.array([len(t) for t in tables], dtype=np.int32)
+        rows = np.ascontiguousarray(np.concatenate(tables)) if n_rows.sum() else np.zeros((1, 2), np.int64)
+        conf = np.ascontiguousarray(conf, dtype=np.int32).reshape(-1, 3)
+        T = len(conf)
+        f9 = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3, 3) for x in (pivot, meanpoint, tri_poly, tri_cost, directions)]
+        cumnums = np.ascontiguousarray(cumnums, dtype=np.int64).reshape(-1, 3, 2)
+        mask = np.ascontiguousarray(mask, dtype=np.uint8).ravel()
+        if any(len(a) != T for a in f9) or len(cumnums) != T or len(mask) != T:
+            raise ValueError("every per-triple input must have one row per pivot triple")
+        per = np.unpackbits(mask[:, None], axis=1).sum(axis=1, dtype=np.int64)
+        base = np.ascontiguousarray(np.concatenate([[0], np.cumsum(per)[:-1]]) if T else np.zeros(0), dtype=np.int64)
+        G = int(per.sum())
+        blocks, ids, best = np.zeros((G, 3, 23)), np.zeros((G, 3, 2), dtype=np.int64), np.zeros(G, dtype=np.int32)
+        check(self.lib.tsc_trimolecular_groups(self._h, ptr(frags.flat), *frags.table_args()[:3], ptr(react), ptr(n_react), ptr(rows), ptr(n_rows), ptr(conf),
+                                               ptr(f9[0]), ptr(f9[1]), ptr(cumnums), ptr(f9[2]), ptr(f9[3]), ptr(f9[4]), ptr(mask), ptr(base),
+                                               C.c_int64(T), C.c_int64(G), ptr(blocks), ptr(ids), ptr(best)))
+        return blocks, ids, best, base
+
+    def trimolecular_groups_kernel_ms(self) -> float:
+        """tsc_trimolecular_groups_timings: the kernel time of this thread's latest trimolecular_groups under set_option("pass_timing", 1)."""
+        return self._kernel_ms(self.lib.tsc_trimolecular_groups_timings)
+
     # ---- N3: conformational-search rotations ---------------------------------------------------
     def csearch_rotate(self, coords, torsions, masks, angles, thresh=1.5, max_clashes=0):
         """Every candidate of tscode/torsion_module.py:463-500: (new_coords f64[M, n, 3], rotated_bonds i32[M])."""

@@ -14,20 +14,12 @@ from itertools import permutations
 
 import numpy as np
 
-from .embeds import MAX_GROUP_POSES, _bimolecular_groups
+from .embeds import DEFAULT_MAX_POSES_PER_CALL, MAX_GROUP_POSES, _bimolecular_groups, _slabs   # (the pose budget per call: see there)
 from .engine import FragmentSet, get_engine
 from .reactive_atoms import MAX_ATOMS, check_orbital_args, reactive_molecule
 from .utils import cartesian_product
 
 __all__ = ["multiembed_batch", "MultiembedResult", "arrangements", "multiembed_bifunctional", "multiembed_dispatcher", "DEFAULT_MAX_POSES_PER_CALL"]
-
-# Poses per tsc_cyclical_embed_groups call.  On the device a candidate pose costs n_mols * 100 B of parameters (rotation 72 B, position 24 B,
-# conformer index 4 B per molecule) and about 20 B of masks and scans; a pose that passes the clash check costs n * 24 B of coordinates
-# (twice while the kept ones are gathered).  For two molecules of 40 atoms with a quarter of the poses passing that is 220 + 0.25 * 3840 B
-# = 1.2 kB per candidate: 2^20 candidates take about 1.2 GB of the device's 288 GB and leave the host's output array (n * 24 B per
-# candidate, touched only for the kept rows) at 2 GB of address space -- large enough that a 144-arrangement multiembed is a handful of calls,
-# small enough to sit beside whatever else the process keeps on the device.
-DEFAULT_MAX_POSES_PER_CALL = 1 << 20
 
 _ORBITAL_KEYS = ("overrides", "orb_dim", "leaving_group", "sp_seed", "suprafacial", "sigmatropic")
 _CHILD_MAX_NORM_DELTA = 5          # a child calls cyclical_embed(embedder): its default reaches the rigid shortcut (tscode/embeds.py:234-241)
@@ -163,11 +155,6 @@ def arrangement_quadruplets(bonds1, bonds2, n1, n2, arrs):
     for (ix_1, ix_2), (iy_1, iy_2) in np.asarray(arrs).tolist():
         out.append(candidate_quadruplets(sum_graph(bonds1, bonds2, n1, n2, [(ix_1, ix_2 + n1), (iy_1, iy_2 + n1)])))
     return out
-
-
-def _slabs(n_groups, A, max_poses):
-    per = max(1, int(max_poses) // A)
-    return [(at, min(at + per, n_groups)) for at in range(0, n_groups, per)]
 
 
 def multiembed_batch(mol1, mol2, systematic_angles=None, clash_thresh=1.5, max_clashes=0, fitness_threshold=5, max_deviation=1e-2, tfd_thresh=10,
