@@ -86,6 +86,9 @@ int tsc_ctx_synchronize(tsc_ctx *ctx);
  *      0 never, 1 (default) in runs of at least mm_min_n structures, 2 always;
  *   "mm_min_n": the number of structures from which sieve_mm 1 takes the 64-row kernels (0 .. 4e9, default 100000);
  *   "sieve_mm16": 1 (default) = smaller runs take the matrix-core screen on 16-row work items (k_rmsd_sieve_mm16), 0 = the packed-fp32 screen;
+ *      the one-launch chunk-local kernel (see local_pass below; 16-row tiles too) follows it in runs of any size: at 1 a run whose schedule can hold such a
+ *      pass keeps a second set of float16 records, by structure index, written once when the run is created (64 bytes per structure);
+ *      verdicts, masks and pairs_evaluated are the same either way;
  *   "mm_seg_cols": columns per work item of the walked passes' 64-row kernel (a multiple of 64 up to 1024; 0 = automatic, the default);
  *   "sieve_cpl": columns per lane of the sieve kernel's screen, 1, 2 (default) or 4 -- register footprint against occupancy;
  *   "pca_min_n": ensembles smaller than this (0 .. 1e9, default 6000) take the identity basis for their descriptors instead of estimated

@@ -10,10 +10,26 @@
 //
 // Long chunks are shared: block j of the NB blocks of a chunk takes the row tiles j, j + NB, ... (rows of a pass are
 // independent, :92,101-113); every block of a chunk repeats the cheap ranking, only its own rows go further.
-// Same verdict functions as the big kernel (sieve.hpp): fp32 descriptor screen -> H -> quartic tests -> explicit rotation.
+// Same verdict functions as the big kernel (sieve.hpp): descriptor screen -> H -> quartic tests -> explicit rotation.
+//
+// Two forms of the screen, two kernels (template <bool MM>, a register allocation each; the host picks by "sieve_mm16", options.hpp: the option of the 16-row matrix-core screen):
+//   MM = false  the packed-fp32 screen of sieve.hpp, one live row after the other against 64 columns (the rows' descriptors in LDS, the
+//               columns' double-buffered in registers): about 30 vector instructions per row and step.
+//   MM = true   the matrix-core screen of mm.hpp (level 1: v_mfma_f32_16x16x16_f16 on float16 records, screen_limit_mm): a step of 64
+//               columns is four blocks of 16 against the tile's 16 rows -- 8 MFMAs, 32 v_alignbit_b32 that gather the sign bits, and an
+//               extraction loop that takes one candidate per lane and turn.  The records are read BY STRUCTURE INDEX from a buffer of the
+//               run's own (LocalPassArgs::rec), written once per run: by k_init_run where the descriptors are final before the run is set
+//               up (the fused pipeline, descriptors of tsc_embed_masked_dev), by k_mm_records behind the descriptor build otherwise
+//               (prune.hip).  k_open_rows' records by POSITION are not this kernel's: it has no opener.  The rows' operands wait in
+//               the LDS area the other form keeps its rows in, ONE column step is in registers, requested where it is used: anything
+//               more that lives around the evaluation stages is spilled (MEASURED.md section 28 has the forms that were tried).
+//               The float16 rounding lets a per cent or so more pairs through than the fp32 screen and queues a step's candidates in
+//               another order: pairs_computed, pairs_screened and the batch counts differ between the forms; verdicts, masks, cache
+//               keys and pairs_evaluated do not (tests/test_local_pass_mm.py).
 #pragma once
 #include "rmsd.hpp"
 #include "sieve.hpp"
+#include "mm.hpp"
 
 namespace tsc {
 
@@ -46,6 +62,7 @@ struct LocalPassArgs {
     unsigned long long *exch;  // rank-partitioned pass (else null): removed rows are noted here and applied by k_pass_merge
     double thr, maxdev_thr, half_h_thr2, two_thr2, desc_limit;
     const unsigned *dmax_bits;
+    const _Float16 *rec;       // the MM form: the float16 records of the matrix-core screen (mm_record.hpp) by STRUCTURE index, written once per run
     unsigned long long *dbg;   // -DTSC_DBG_STAMPS builds only: 8 time stamps per wavefront of the launch (tools/stamps.py), else null
 };
 
@@ -125,6 +142,9 @@ __device__ inline void lp_views_insert_wave(const CacheViews &cv, bool removed, 
     }
 }
 
+constexpr int LP_MM_BLOCKS = 64 / MM_STEP;  // the MM form: 16-column blocks of a column step
+
+template <bool MM>
 inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks(PassGeom g, LocalPassArgs a, PruneState *__restrict__ st, uint8_t *__restrict__ mask,
                                                              unsigned long long *__restrict__ bits, int bit_words,
                                                              const unsigned long long *__restrict__ dbit, const double *__restrict__ heavy,
@@ -136,7 +156,7 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
     __shared__ unsigned short s_act[LP_MAX_ROWS], s_cend[LP_MAX_ROWS];
     __shared__ int s_best[LP_MAX_ROWS];
     __shared__ unsigned short s_queue[LP_WAVES][LP_QCAP], s_exq[LP_WAVES][128];
-    __shared__ __attribute__((aligned(16))) float s_rowdesc[LP_WAVES][LP_TI * DW];
+    __shared__ __attribute__((aligned(16))) float s_rowdesc[LP_WAVES][LP_TI * DW];  // (the MM form: a tile's row operands, 16 bytes per lane)
     __shared__ double s_jacobi[LP_WAVES][32];  // the Jacobi fallback of the exact stage (rmsd.hpp: top_eigvec4_mem), per wavefront
     __shared__ unsigned long long s_stat[8];  // block totals of the five statistics
     __shared__ int s_A, s_anydb, s_last, s_open[2];
@@ -264,7 +284,10 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
 
         // ---- 3. pairs: one wavefront per (16 rows) x (all their columns), 64 columns at a time
         const int h3 = a.h * 3;
-        const float limit32 = screen_limit32(__uint_as_float(dmax_raw), a.desc_limit);
+        [[maybe_unused]] const float limit32 = MM ? 0.0f : screen_limit32(__uint_as_float(dmax_raw), a.desc_limit);
+        // (the same in every lane, and said so: a scalar register, not a vector one held through the evaluation stages)
+        [[maybe_unused]] const float limit_mm = MM ? __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(screen_limit_mm(dmax_raw, a.desc_limit)))) : 0.0f;
+        [[maybe_unused]] const int g4 = lane >> 4, rc = lane & 15;  // the MM form's lane: k group (slots 4 g4 .. 4 g4 + 3), row or column of a block
         // a lane's place among the set bits of a ballot: how many lanes below it are in
         auto place_in = [](unsigned long long m) __attribute__((always_inline)) {
             return int(__builtin_amdgcn_mbcnt_hi(unsigned(m >> 32), __builtin_amdgcn_mbcnt_lo(unsigned(m), 0u)));
@@ -285,11 +308,18 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) cmax = max(cmax, __shfl_xor(cmax, off));
             cmax = __builtin_amdgcn_readfirstlane(cmax);
-            float row_part[4];  // (the rows' descriptors and the first column tile are requested together, the LDS stores come behind both)
+            [[maybe_unused]] float row_part[4];  // (the rows' descriptors and the first column tile are requested together, the LDS stores come behind both)
+            [[maybe_unused]] f16x4 Ar[NFAM];     // the MM form: the rows' operands, lane (g4, rc) holds row rc's slots
+            if constexpr (MM) {
+                const _Float16 *rr = a.rec + int64_t(first + s_act[min(r0 + rc, A - 1)]) * MM_REC_HALVES;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int rr = min(r0 + 4 * q + (lane >> 4), A - 1);
-                row_part[q] = D[int64_t(first + s_act[rr]) * DW + (lane & 15)];
+                for (int fam = 0; fam < NFAM; ++fam) Ar[fam] = mm_load_A(rr, fam, g4);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int rr = min(r0 + 4 * q + (lane >> 4), A - 1);
+                    row_part[q] = D[int64_t(first + s_act[rr]) * DW + (lane & 15)];
+                }
             }
             int qn = 0, qe = 0;
 
@@ -407,14 +437,87 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
                     dst[2 * k + 1] = f32x2{v.z, v.w};
                 }
             };
-            f32x2 dq[KD], dq_next[KD];
-            int c0 = (r0 + 1) & ~63;  // (< cmax: a live row's stop column lies beyond its own rank)
-            load_cols(c0, dq_next);
+            // the MM form: a step's 64 columns as four blocks of 16, lane (g4, rc) holds column rc of every block -- four 16-byte loads per
+            // lane, the bytes of load_cols
+            auto load_recs = [&](int c0, f16x4 (&dst)[LP_MM_BLOCKS][NFAM]) __attribute__((always_inline)) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) rowdesc[64 * q + lane] = row_part[q];
+                for (int b = 0; b < LP_MM_BLOCKS; ++b)
+                    mm_load_B2(a.rec + int64_t(first + s_act[min(c0 + MM_STEP * b + rc, A - 1)]) * MM_REC_HALVES, g4, dst[b]);
+            };
+            // ... the rows' operands wait in LDS (where the other form keeps its rows), NOT in registers: whatever lives through the
+            // evaluation stages costs this kernel a spill.  A step reads them back with one 16-byte read; rows that are not (or no longer)
+            // looking then get +inf in the n0 slot of family 0 (mm.hpp: mark_rows of sieve_item_mm16), from `alive` as it is at that step
+            static_assert(NFAM == 2 && LP_TI * DW == 64 * 4, "a lane's two operands are the 16 bytes at its place in the row area");
+            auto put_rows = [&]() __attribute__((always_inline)) {
+                const f32x2 lo = __builtin_bit_cast(f32x2, Ar[0]), hi = __builtin_bit_cast(f32x2, Ar[1]);
+                *reinterpret_cast<f32x4 *>(rowdesc + 4 * lane) = f32x4{lo.x, lo.y, hi.x, hi.y};
+            };
+            auto get_rows = [&]() __attribute__((always_inline)) {
+                const f32x4 v = *reinterpret_cast<const f32x4 *>(rowdesc + 4 * lane);
+                const f32x2 lo = {v.x, v.y}, hi = {v.z, v.w};
+                Ar[0] = __builtin_bit_cast(f16x4, lo), Ar[1] = __builtin_bit_cast(f16x4, hi);
+                if (g4 == 2 && !((alive >> rc) & 1u)) Ar[0][0] = _Float16(__builtin_inff());
+            };
+            [[maybe_unused]] f32x2 dq[KD], dq_next[KD];
+            [[maybe_unused]] f16x4 Bq[LP_MM_BLOCKS][NFAM];
+            int c0 = (r0 + 1) & ~63;  // (< cmax: a live row's stop column lies beyond its own rank)
+            if constexpr (MM) {
+                put_rows();
+            } else {
+                load_cols(c0, dq_next);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) rowdesc[64 * q + lane] = row_part[q];
+            }
             __builtin_amdgcn_wave_barrier();
             for (bool screening = true;;) {
-                if (screening) {
+                if constexpr (MM) {
+                    if (screening) {
+                        // ONE column step, requested where it is used.  A second buffer in flight during the step (as dq / dq_next), or this
+                        // one requested at the bottom of the loop, lives -- for the register allocator -- around the stages: 29 to 70 spilled
+                        // registers and 72 to 128 bytes of scratch, the loads among them.  The step itself is 8 MFMAs and an extraction that
+                        // rarely iterates: next to the gather's round trip there is little to hide it behind, the SIMD's other wavefronts do.
+                        load_recs(c0, Bq);
+                        const bool here = lane < nrows && ((alive >> lane) & 1u) && my_cend > c0 && r0 + lane < c0 + 63;
+                        my_screened += here ? max(0, min(my_cend, c0 + 64) - max(r0 + lane + 1, c0)) : 0;
+                        get_rows();
+                        // 16 rows x 64 columns x two families: 8 MFMAs.  Every accumulator starts at -limit, a pair is kept iff BOTH families
+                        // come out negative; the sign bits go into a mask per family, value j = 4 b + i of the step -- row 4 g4 + i, column
+                        // 16 b + rc -- at bit 15 - j (mm.hpp)
+                        unsigned m0 = 0, m1 = 0;
+#pragma unroll
+                        for (int b = 0; b < LP_MM_BLOCKS; ++b) {
+                            const f32x4 z = {-limit_mm, -limit_mm, -limit_mm, -limit_mm};
+                            const f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x16f16(Ar[0], Bq[b][0], z, 0, 0, 0);
+                            const f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x16f16(Ar[1], Bq[b][1], z, 0, 0, 0);
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                m0 = __builtin_amdgcn_alignbit(m0, __float_as_uint(s0[i]), 31);
+                                m1 = __builtin_amdgcn_alignbit(m1, __float_as_uint(s1[i]), 31);
+                            }
+                        }
+                        static_assert(4 * LP_MM_BLOCKS == 16, "16 values per lane and family: moved to the top half for the count of leading zeros");
+                        unsigned hits = (m0 & m1) << 16;
+                        while (__builtin_amdgcn_ballot_w64(hits != 0u)) {
+                            // one pair per lane and turn (a lane rarely holds two); kept if it lies right of the diagonal, before its row's stop
+                            // column, and its row is still looking (clamped columns beyond the active count fail the second test)
+                            bool keep = false;
+                            unsigned ent = 0;
+                            if (hits) {
+                                const int jv = __builtin_clz(hits);
+                                hits &= ~(0x80000000u >> jv);
+                                const int row = 4 * g4 + (jv & 3), col = c0 + MM_STEP * (jv >> 2) + rc;
+                                keep = col > r0 + row && ((alive >> row) & 1u) && col < int(s_cend[r0 + row]);
+                                ent = (unsigned(row) << 12) | unsigned(col);
+                            }
+                            const unsigned long long km = __builtin_amdgcn_ballot_w64(keep);
+                            if (keep) queue[qn + place_in(km)] = (unsigned short)ent;
+                            qn += __popcll(km);
+                        }
+                        c0 += 64;
+                        alive &= ~unsigned(__builtin_amdgcn_ballot_w64(lane < nrows && ((alive >> lane) & 1u) && my_cend <= c0));  // rows whose range ends here
+                        __builtin_amdgcn_wave_barrier();
+                    }
+                } else if (screening) {
                     const int col = c0 + lane;
 #pragma unroll
                     for (int k = 0; k < KD; ++k) dq[k] = dq_next[k];
@@ -461,13 +564,18 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
                             sign_stage(qn - cnt, cnt);
                             qn -= cnt;
                         }
+                        if constexpr (MM) alive = unsigned(__builtin_amdgcn_readfirstlane(int(alive)));  // (see below)
                     } while (pending());
                     if (!screening) break;
                     // (the next tile is requested again behind a drain, clamped like any tile: its 32 registers are the stages' to use)
-                    load_cols(c0, dq_next);
+                    if constexpr (!MM) load_cols(c0, dq_next);
                 } else if (!screening) {
                     break;
                 }
+                // (`alive` is the same in every lane -- the stages lower it by rows found with a ballot or in branches the whole wavefront takes --
+                // but not provably so: said here, the loop's branches are scalar and what a step loads does not have to outlive the stages
+                // lane by lane)
+                if constexpr (MM) alive = unsigned(__builtin_amdgcn_readfirstlane(int(alive)));
                 screening = c0 < cmax && alive;
             }
         }

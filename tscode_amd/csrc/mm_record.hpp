@@ -1,5 +1,6 @@
 // mm_record.hpp -- the float16 records of a structure's descriptor that the matrix-core screen reads (mm.hpp has the scheme and its
-// error bound); written by k_open_rows (rmsd.hpp) by position, every pass.
+// error bound); written by k_open_rows (rmsd.hpp) by position, every pass -- and once per run by structure index (k_init_run, or k_mm_records of
+// mm.hpp) for the chunk-local pass, which has no opener (local_pass.hpp).
 #pragma once
 #include "common.hpp"
 

@@ -259,6 +259,12 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
         p->mm64 = c->opt.sieve_mm == 2 || (c->opt.sieve_mm == 1 && n >= c->opt.mm_min_n);
         const bool want_mm = p->mm64 || c->opt.sieve_mm16 != 0;
         if (!rc && want_mm) rc = palloc(p, size_t(n) * MM_REC_HALVES, &p->Dh);
+        // the records by structure index of the chunk-local pass's matrix-core screen ("sieve_mm16"): only where a pass of the schedule can have
+        // chunks short enough for that kernel (a rank's share of a partitioned pass may leave the longer last chunk to another rank)
+        bool local_possible = false;
+        for (int slot = 0; slot < TSC_MAX_PASSES; ++slot)
+            local_possible = local_possible || (pass_can_run(n, slot) && n / int64_t(KS[slot]) <= std::min(LP_MAX_ROWS, c->opt.local_max_chunk));
+        if (!rc && c->opt.sieve_mm16 != 0 && c->opt.local_pass != 0 && local_possible) rc = palloc(p, size_t(n) * MM_REC_HALVES, &p->Drec);
         // the float32 copy stage 1 reads (sieve.hpp, pair_stage1): from the embedding kernel where there was one, else converted here
         // (it pays where the gathers come from HBM: 41 MB of heavy atoms at C3 sit in the 256 MB infinity cache and the conversions cost the
         // VALU-bound kernel 2 %; at C4's 348 MB a step goes from 12.1 to 10.6 ms.  "stage1_f32": 0 never, 1 from 128 MB on, 2 always)
@@ -298,7 +304,12 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
         ia.zero_words = reinterpret_cast<unsigned *>(p->tickets), ia.n_zero_words = int64_t(sizeof(*p->tickets) / sizeof(unsigned));
         ia.act = p->act, ia.first_slot = first_slot, ia.first_k = first_slot >= 0 ? (long long)KS[first_slot] : 0ll, ia.first_algo = p->algo;
         ia.tile_done = p->tile_done, ia.n_tile_done = n / 16 + 8;
-        hipLaunchKernelGGL(k_init_run, dim3(grid_for(n / 8 + 1, 256, 512)), dim3(256), 0, st, ia);
+        // External descriptors (and their maximum) were enqueued on this stream in front of the run: final here, k_init_run writes the records by
+        // structure as it walks n (two structures per thread then, not eight).  A run that builds its own descriptors does so BEHIND this launch,
+        // which zeroes the maximum they raise: its records come from k_mm_records behind build_descriptors, below.
+        const bool rec_here = p->Drec && !own_desc;
+        if (rec_here) ia.Dall = p->Dall, ia.rec_dmax_bits = p->dmax_bits, ia.mm_rec = p->Drec;
+        hipLaunchKernelGGL(k_init_run, dim3(grid_for(n / (rec_here ? 2 : 8) + 1, 256, 512)), dim3(256), 0, st, ia);
         hipError_t e = hipGetLastError();
         // padded columns of the compacted layouts are read by the last column tile of a segment but never used; the
         // register-tiled kernel's buffers are zeroed once so that those reads see finite numbers
@@ -308,6 +319,10 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
         if (e != hipSuccess) rc = fail(TSC_ERR_HIP, "prune state setup failed: %s", hipGetErrorString(e));
     }
     if (!rc && p->Dall && own_desc) rc = build_descriptors(p, basis);
+    if (!rc && p->Drec && own_desc) {
+        hipLaunchKernelGGL(k_mm_records, dim3(grid_for(n, 256, 1024)), dim3(256), 0, c->stream, (const float *)p->Dall, n, (const unsigned *)p->dmax_bits, p->Drec);
+        if (hipGetLastError() != hipSuccess) rc = fail(TSC_ERR_HIP, "the records of the chunk-local pass could not be written");
+    }
     if (rc) {
         tsc_prune_destroy(p);
         return rc;
@@ -494,6 +509,8 @@ static int local_pass(tsc_prune *p, const PassGeom &g, const PassRows &r, bool r
     a.nb_regular = l.nb_regular, a.nb_last = l.nb_last;
     a.c_lo = int(r.c_lo), a.n_reg = l.n_reg;
     a.exch = range ? p->exch : nullptr;
+    // (the records exist where "sieve_mm16" was on when the run was created; the option is looked at again: a run may be stepped under another value)
+    a.rec = p->ctx->opt.sieve_mm16 != 0 ? p->Drec : nullptr;
     a.dbg = nullptr;
 #ifdef TSC_DBG_STAMPS
     if (p->ctx->opt.dbg_stamp_k == p->cur_k) TSC_TRY(stamp_buffer(p->ctx, int64_t(l.blocks) * 4, &a.dbg));
@@ -505,7 +522,7 @@ static int local_pass(tsc_prune *p, const PassGeom &g, const PassRows &r, bool r
     // events costs a small pass about 6 us)
     const PairEvents ev = pair_events(p, 2);
     // (range: the last block leaves the statistics in the exchange buffer; otherwise the pass is left open, as in walked_pass)
-    TSC_TRY(launch_pass_chunks(p->ctx->stream, unsigned(l.blocks), ev.e0, ev.e1, g, a, p->state, p->mask, p->bits, int(p->bit_words), view_of_open_pass(p), p->heavy,
+    TSC_TRY(launch_pass_chunks(a.rec != nullptr, p->ctx->stream, unsigned(l.blocks), ev.e0, ev.e1, g, a, p->state, p->mask, p->bits, int(p->bit_words), view_of_open_pass(p), p->heavy,
                                (const double *)p->Gall, (const float *)p->Dall, later_views(p), p->counters, p->bsum, SCAN_TILE, step_ctx(p, range), sa,
                                range ? &p->tickets->local : nullptr, derive_args(p)));
     if (!range) p->last_local = true;  // (last_slot stays this pass's: left open)

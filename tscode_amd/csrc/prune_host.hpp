@@ -49,6 +49,7 @@ struct tsc_prune {
     float *Dc = nullptr;     // ... in active order, rewritten by k_open_rows every pass: what the pair kernel reads
     bool mm64 = false;                      // this run takes the 64-row matrix-core kernels (mm.hpp, cull_mm.hpp); else, with records, the 16-row form
     _Float16 *Dh = nullptr;                 // ... and as the float16 records of the matrix-core screen (mm.hpp), in active order too ("sieve_mm")
+    _Float16 *Drec = nullptr;               // ... and by STRUCTURE index, written once per run: what the chunk-local pass screens with ("sieve_mm16", local_pass.hpp)
     double *Gall = nullptr;
     struct Tickets {
         PassTickets pass;
@@ -202,7 +203,8 @@ int launch_rmsd_sieve_mm16(bool fused, bool f32, int waves, hipStream_t st, dim3
 int launch_rmsd_sieve_sorted_mm(bool f32, hipStream_t st, dim3 grid, hipEvent_t e0, hipEvent_t e1, const double *heavy, const int32_t *act, const double *Gall,
                                 const int32_t *cend, int32_t *best, PassCounters *counters, const PruneState *state, const SieveArgs &a, const CullArgs &ca,
                                 const CullMmArgs &cm, int n_groups, int n_seg);
-int launch_pass_chunks(hipStream_t st, unsigned blocks, hipEvent_t e0, hipEvent_t e1, const PassGeom &g, const LocalPassArgs &a, PruneState *state, uint8_t *mask,
+// (mm: the screen on the matrix cores, from the records by structure in a.rec)
+int launch_pass_chunks(bool mm, hipStream_t st, unsigned blocks, hipEvent_t e0, hipEvent_t e1, const PassGeom &g, const LocalPassArgs &a, PruneState *state, uint8_t *mask,
                        unsigned long long *bits, int bit_words, const unsigned long long *view, const double *heavy, const double *Gall, const float *Dall,
                        const CacheViews &cv, PassCounters *counters, int32_t *bsum, int block_items, const StepCtx &sc, const StepArgs &sa, LocalTickets *tickets,
                        const DeriveArgs &dv);

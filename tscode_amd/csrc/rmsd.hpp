@@ -431,6 +431,9 @@ struct InitArgs {
     int first_slot;
     long long first_k;
     int first_algo;
+    const float *Dall;          // with mm_rec: the descriptors by structure, FINAL (with *rec_dmax_bits) before this launch -- runs that build their own
+    const unsigned *rec_dmax_bits;  // behind it get their records from k_mm_records instead (prune.hip)
+    _Float16 *mm_rec;           // the float16 records by structure index the chunk-local pass screens with ("sieve_mm16"; local_pass.hpp), or null
 };
 inline __global__ __launch_bounds__(256) void k_init_run(InitArgs a) {
     // first_slot >= 0: the first pass of the schedule is opened here as well (gate of rmsd_pruning.py:192 on the full count,
@@ -443,6 +446,18 @@ inline __global__ __launch_bounds__(256) void k_init_run(InitArgs a) {
     // every entry of the active list is a valid structure index from the start: the pair kernel gathers through
     // act[x] for x up to n without knowing the active count
     for (int64_t e = tid; e < n; e += stride) a.act[e] = int32_t(e);
+    if (a.mm_rec) {  // (once per run: the records by position are k_open_rows', every pass)
+        const float sigma = mm_scale(*a.rec_dmax_bits);
+        for (int64_t e = tid; e < n; e += stride) {
+            float d[2 * MM_KD];
+#pragma unroll
+            for (int q = 0; q < MM_KD / 2; ++q) {
+                const float4 v = *reinterpret_cast<const float4 *>(a.Dall + e * (2 * MM_KD) + 4 * q);
+                d[4 * q] = v.x, d[4 * q + 1] = v.y, d[4 * q + 2] = v.z, d[4 * q + 3] = v.w;
+            }
+            mm_write_record(d, sigma, a.mm_rec + e * MM_REC_HALVES);
+        }
+    }
     for (int64_t e = tid; e < a.bit_words; e += stride) {  // n ones, zeros behind them, in both copies
         const int64_t lo = e * 64;
         const unsigned long long w = lo + 64 <= n ? ~0ull : (lo >= n ? 0ull : ((1ull << (n - lo)) - 1ull));
