@@ -520,6 +520,46 @@ int tsc_prune_structures(tsc_ctx *ctx, const double *structures, int64_t n, int 
 int tsc_prune_rmsd_dev(tsc_ctx *ctx, const double *heavy, int64_t n, int h, double rmsd_thr, int mode, uint8_t *mask,
                        tsc_pass_stats *stats, int *n_passes); /* synchronises (the schedule gate reads counts) */
 
+/* An embed-and-prune run: the cyclical embed of tsc_cyclical_embed_groups (tscode/embeds.py:657-717 / :785-847) whose kept poses go
+ * straight into prune_conformers_rmsd (tscode/rmsd_pruning.py:164-206) without a trip through host memory.  By definition the result is
+ * that of tsc_cyclical_embed_groups over all slabs followed by tsc_prune_structures on the poses it returned: the same flags, the same
+ * verdicts and statistics, the same coordinates to the last bit.  The kept poses are never materialised on the host; the run keeps, per
+ * kept pose, its heavy atoms (gathered from the very buffer the embed's filter read) and its 100-byte-per-molecule parameter row, prunes
+ * the heavy atoms where they are and embeds again only the poses that are asked for -- recomputing a pose from its parameters is cheaper
+ * than moving it, as in tsc_pipeline_dev.  Peak device memory: one slab's passing poses plus n_kept_total * (24 n_heavy + 100 n_mols)
+ * bytes; the run's buffers grow by doubling.
+ *   tsc_embed_prune_create      fragments as in tsc_cyclical_embed_groups (n_mols 2 or 3), uploaded ONCE for all slabs; heavy_idx
+ *                               i32[n_heavy] = flatnonzero(atomnos != 1): at least one entry, increasing, below the atom count.
+ *   tsc_embed_prune_add_groups  one slab of groups, arguments, checks and messages as tsc_cyclical_embed_groups (rmsd_thr_filter is its
+ *                               rmsd_thr; N = n_groups * n_angles).  Only clash_ok u8[N], kept u8[N] and the two counts reach the host;
+ *                               the slab's kept poses are appended to the run in candidate order.  May be called any number of times.
+ *   tsc_embed_prune_count       kept poses so far, over all slabs.
+ *   tsc_embed_prune_run         tsc_prune_rmsd_dev over the kept poses' heavy atoms: mode 0 or 1, survived u8[n_kept_total] (1 = the
+ *                               pose outlives the prune), stats / n_passes (optional) as that call returns them.  With no kept pose it
+ *                               launches nothing and reports no survivor.  Closes the run for further slabs; may be repeated (another
+ *                               threshold), the latest verdicts are the ones that count.
+ *   tsc_embed_prune_poses       which = 0: the survivors, which = 1: every kept pose; poses f64[rows, n_total, 3] in candidate order,
+ *                               capacity = rows the buffer holds.  Embedded from the kept parameters by the kernel that embedded them
+ *                               for the filter, and only these rows are fetched.
+ *   tsc_embed_prune_destroy     frees the run.  A context lists its live runs and destroys them with itself: do not hand a run to
+ *                               tsc_embed_prune_destroy after its context is destroyed.
+ * Refused before the device is touched, with a message: a null pointer, n_heavy < 1, a heavy index out of range or not increasing, a
+ * capacity below the row count, a mode other than 0 or 1 (TSC_ERR_INVALID); tsc_embed_prune_add_groups after tsc_embed_prune_run, and
+ * tsc_embed_prune_poses with which = 0 before it (TSC_ERR_STATE).  The calls of one run must not overlap; they synchronise. */
+typedef struct tsc_embed_prune tsc_embed_prune;
+int tsc_embed_prune_create(tsc_ctx *ctx, const double *frags, const int64_t *frag_off, const int32_t *n_atoms, const int32_t *n_conf,
+                           int n_mols, const int32_t *heavy_idx, int n_heavy, tsc_embed_prune **run);
+int tsc_embed_prune_add_groups(tsc_embed_prune *run, const double *start, const double *end, const double *direction,
+                               const double *pivot, const double *meanpoint, const double *r0, const double *r1,
+                               const int32_t *n_reactive, const int32_t *conf_idx, const double *angles, int64_t n_groups, int n_angles,
+                               double clash_thresh, int64_t max_clashes, double rmsd_thr_filter, uint8_t *clash_ok, uint8_t *kept,
+                               int64_t *n_pass, int64_t *n_kept);
+int tsc_embed_prune_count(tsc_embed_prune *run, int64_t *n_kept_total);
+int tsc_embed_prune_run(tsc_embed_prune *run, double rmsd_thr, int mode, uint8_t *survived, tsc_pass_stats *stats, int *n_passes,
+                        int64_t *n_survived);
+int tsc_embed_prune_poses(tsc_embed_prune *run, int which, double *poses, int64_t capacity);
+int tsc_embed_prune_destroy(tsc_embed_prune *run);
+
 /* Per-pass statistics of one segment of tsc_prune_rmsd_batch (one entry per executed k of that segment's schedule). */
 typedef struct {
     int64_t k;               /* number of chunks (tscode/rmsd_pruning.py:186-188) */

@@ -11,7 +11,7 @@ include/tscode_hip.h).  There is no CPU fallback; importing this package does no
 
 from .algebra import (align_vec_pair, all_dists, norm, norm_of, quaternion_to_rotation_matrix,  # noqa: F401
                       rot_mat_from_pointer, rotation_matrix_from_vectors, transform_coords, vec_angle)
-from .embeds import (EmbedTrace, cyclical_embed_batch, cyclical_embed_params, embed_batch, filter_angular_groups, get_embed,  # noqa: F401
+from .embeds import (EmbedTrace, cyclical_embed_batch, cyclical_embed_params, cyclical_embed_prune_batch, embed_batch, filter_angular_groups, get_embed,  # noqa: F401
                      string_embed_batch, string_embed_params, string_embed_poses, trimolecular_groups_batch)
 from .utils import (TriangleError, cartesian_product, get_double_bonds_indices, molecule_check, polygonize,  # noqa: F401
                     scramble_check)

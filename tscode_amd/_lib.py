@@ -132,6 +132,12 @@ _SIGNATURES = {
     "tsc_prune_structures": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, c_i32p, C.c_int, C.c_double, C.c_int, _vp, C.POINTER(PassStats),
                                        C.POINTER(C.c_int)]),
     "tsc_prune_rmsd_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_double, C.c_int, _vp, C.POINTER(PassStats), C.POINTER(C.c_int)]),
+    "tsc_embed_prune_create": (C.c_int, [_vp, _vp, c_i64p, c_i32p, c_i32p, C.c_int, c_i32p, C.c_int, C.POINTER(_vp)]),
+    "tsc_embed_prune_add_groups": (C.c_int, [_vp] * 11 + [C.c_int64, C.c_int, C.c_double, C.c_int64, C.c_double, _vp, _vp, c_i64p, c_i64p]),
+    "tsc_embed_prune_count": (C.c_int, [_vp, c_i64p]),
+    "tsc_embed_prune_run": (C.c_int, [_vp, C.c_double, C.c_int, _vp, C.POINTER(PassStats), C.POINTER(C.c_int), c_i64p]),
+    "tsc_embed_prune_poses": (C.c_int, [_vp, C.c_int, _vp, C.c_int64]),
+    "tsc_embed_prune_destroy": (C.c_int, [_vp]),
     "tsc_prune_rmsd_batch": (C.c_int, [_vp, _vp, c_i64p, c_i32p, c_i32p, c_f64p, C.c_int64, C.c_int, _vp, C.POINTER(BatchPassStats), c_i32p, c_u8p]),
     "tsc_prune_rmsd_batch_dev": (C.c_int, [_vp, _vp, c_i64p, c_i32p, c_i32p, c_f64p, C.c_int64, C.c_int, _vp, C.POINTER(BatchPassStats), _vp, _vp]),
     "tsc_prune_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_double, C.c_int, C.POINTER(_vp)]),

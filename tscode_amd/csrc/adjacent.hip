@@ -9,6 +9,7 @@
 #include "moi.hpp"
 #include "host_order.hpp"
 #include "trimolecular.hpp"
+#include "embed_prune_plan.hpp"
 
 // --------------------------------------------------------------------------------------------------
 // greedy per-group filter
@@ -577,14 +578,24 @@ extern "C" __attribute__((visibility("default"))) int tsc_tfd_greedy_filter(tsc_
     TSC_API_GUARD_END
 }
 
-// What both drivers share once the pose parameters are on the device: clash verdicts of all candidates, the passing poses
-// embedded in candidate order, a filter over them (`filter(d_structs, n_pass, d_pos_scan, d_acc)`), the kept poses compacted
-// and copied out, both verdicts per candidate.
+// What the embed drivers share once the pose parameters are on the device, in two halves.  The front half: clash verdicts of all candidates,
+// the passing poses embedded in candidate order, a filter over them (`filter(d_structs, n_pass, d_pos_scan, d_total, d_acc)`), both verdicts
+// per candidate (clash_ok fetched, kept registered with the call) and the two counts on the host.  What it leaves on the device, in blocks of
+// the call's scratch, is what a back half reads: the passing poses and the two index lists.
+struct EmbedFiltered {
+    int32_t n_pass = 0, n_kept = 0;
+    double *structs = nullptr;    // f64[n_pass, n, 3]: the passing poses, the very buffer the filter read
+    int32_t *act = nullptr;       // i32[n_pass]: candidate of every passing pose
+    int32_t *act2 = nullptr;      // i32[n_kept]: passing pose of every kept pose
+    // (the group drivers: the parameters of every candidate, cyclical_groups_front)
+    const int32_t *ci = nullptr;
+    const double *rot = nullptr, *pos = nullptr;
+};
+
 template <typename Filter>
-static int embed_filter_run(tsc_ctx *c, HostCall &h, const double *d_frags, const FragTable &ft, const int64_t *frag_off, const int32_t *n_atoms,
-                            const int32_t *n_conf, const int32_t *d_ci, const double *d_rot, const double *d_pos, int64_t N, double clash_thresh,
-                            int64_t max_clashes, uint8_t *clash_ok, uint8_t *kept, double *poses, int64_t poses_capacity, int64_t *n_pass_out,
-                            int64_t *n_kept_out, Filter filter) {
+static int embed_filter_front(tsc_ctx *c, HostCall &h, const double *d_frags, const FragTable &ft, const int64_t *frag_off, const int32_t *n_atoms,
+                              const int32_t *n_conf, const int32_t *d_ci, const double *d_rot, const double *d_pos, int64_t N, double clash_thresh,
+                              int64_t max_clashes, uint8_t *clash_ok, uint8_t *kept, EmbedFiltered *f, Filter filter) {
     hipStream_t st = c->stream;
     Scratch &s = h.scratch();
     const int n = ft.n_total;
@@ -602,31 +613,50 @@ static int embed_filter_run(tsc_ctx *c, HostCall &h, const double *d_frags, cons
     TSC_TRY(scan_mask(st, d_mask, N, bsum, pos_scan, act, nullptr, total));
     TSC_TRY(h.fetch(clash_ok, d_mask, size_t(N)));   // (here, in front of the first wait)
     TSC_HIP(hipMemsetAsync(d_kept_full, 0, size_t(N), st));
-    int32_t n_pass = 0, n_kept = 0;
-    TSC_TRY(read_i32(c, total, &n_pass));
-    *n_pass_out = n_pass;
+    f->act = act, f->act2 = act2;
+    TSC_TRY(read_i32(c, total, &f->n_pass));
+    const int32_t n_pass = f->n_pass;
     if (n_pass > 0) {
-        double *d_structs, *d_out;
+        double *d_structs;
         TSC_TRY(s.get(size_t(n_pass) * n * 3, &d_structs));
         TSC_TRY(s.get(size_t(n_pass), &d_acc));
         hipLaunchKernelGGL(k_transform, dim3(grid_for(n_pass, TR_POSES, 256 * 64)), dim3(256), transform_lds_bytes(ft.n_mols), st, d_frags, ft, d_ci, d_rot, d_pos,
                            (const int32_t *)act, int64_t(n_pass), d_structs, (const int32_t *)nullptr, 0, (double *)nullptr, (const int32_t *)nullptr);
         TSC_HIP(hipGetLastError());
+        f->structs = d_structs;
         TSC_TRY(filter(d_structs, n_pass, pos_scan, total, d_acc));
         hipLaunchKernelGGL(k_scatter_flags, dim3(grid_for(n_pass, 256, 1024)), dim3(256), 0, st, (const uint8_t *)d_acc, (const int32_t *)act, (const int32_t *)total,
                            d_kept_full);
         TSC_TRY(scan_mask(st, d_acc, n_pass, bsum, nullptr, act2, nullptr, total2));
-        TSC_TRY(read_i32(c, total2, &n_kept));
-        if (poses && n_kept > 0) {
-            TSC_REQUIRE(n_kept <= poses_capacity, "poses holds %lld rows, %d poses were kept", (long long)poses_capacity, n_kept);
-            TSC_TRY(s.get(size_t(n_kept) * n * 3, &d_out));
-            TSC_TRY(launch_gather_rows(st, d_structs, act2, n_kept, n * 3, nullptr, n * 3, d_out));
-            TSC_TRY(h.fetch(poses, d_out, size_t(n_kept) * n * 3));
-        }
+        TSC_TRY(read_i32(c, total2, &f->n_kept));
+    }
+    return 0;
+}
+
+// The back half of the calls that hand the kept poses to the host: compacted, copied out, then the call's one wait for the stream.
+static int embed_filter_fetch(tsc_ctx *c, HostCall &h, int n, const EmbedFiltered &f, double *poses, int64_t poses_capacity, int64_t *n_kept_out) {
+    if (poses && f.n_kept > 0) {
+        double *d_out;
+        TSC_REQUIRE(f.n_kept <= poses_capacity, "poses holds %lld rows, %d poses were kept", (long long)poses_capacity, f.n_kept);
+        TSC_TRY(h.scratch().get(size_t(f.n_kept) * n * 3, &d_out));
+        TSC_TRY(launch_gather_rows(c->stream, f.structs, f.act2, f.n_kept, n * 3, nullptr, n * 3, d_out));
+        TSC_TRY(h.fetch(poses, d_out, size_t(f.n_kept) * n * 3));
     }
     TSC_TRY(h.finish());
-    *n_kept_out = n_kept;
+    *n_kept_out = f.n_kept;
     return 0;
+}
+
+template <typename Filter>
+static int embed_filter_run(tsc_ctx *c, HostCall &h, const double *d_frags, const FragTable &ft, const int64_t *frag_off, const int32_t *n_atoms,
+                            const int32_t *n_conf, const int32_t *d_ci, const double *d_rot, const double *d_pos, int64_t N, double clash_thresh,
+                            int64_t max_clashes, uint8_t *clash_ok, uint8_t *kept, double *poses, int64_t poses_capacity, int64_t *n_pass_out,
+                            int64_t *n_kept_out, Filter filter) {
+    EmbedFiltered f;
+    const int rc = embed_filter_front(c, h, d_frags, ft, frag_off, n_atoms, n_conf, d_ci, d_rot, d_pos, N, clash_thresh, max_clashes, clash_ok, kept, &f, filter);
+    *n_pass_out = f.n_pass;
+    TSC_TRY(rc);
+    return embed_filter_fetch(c, h, ft.n_total, f, poses, poses_capacity, n_kept_out);
 }
 
 extern "C" __attribute__((visibility("default"))) int tsc_string_embed(tsc_ctx *c, const double *frags, const int64_t *frag_off, const int32_t *n_atoms,
@@ -739,42 +769,37 @@ extern "C" __attribute__((visibility("default"))) int tsc_cyclical_embed(tsc_ctx
     TSC_API_GUARD_END
 }
 
-// The same embed from one record per (group, molecule) and one angle table shared by all groups: pose g * n_angles + a is record g under
-// angle set a, what tsc_cyclical_embed computes on the rows a caller would expand from them.  Per pose nothing is uploaded or checked.
-extern "C" __attribute__((visibility("default"))) int tsc_cyclical_embed_groups(tsc_ctx *c, const double *frags, const int64_t *frag_off, const int32_t *n_atoms,
-                                                                                const int32_t *n_conf, int n_mols, const double *start, const double *end,
-                                                                                const double *direction, const double *pivot, const double *meanpoint,
-                                                                                const double *r0, const double *r1, const int32_t *n_reactive,
-                                                                                const int32_t *conf_idx, const double *angles, int64_t n_groups, int n_angles,
-                                                                                double clash_thresh, int64_t max_clashes, double rmsd_thr, uint8_t *clash_ok,
-                                                                                uint8_t *kept, double *poses, int64_t poses_capacity, int64_t *n_pass,
-                                                                                int64_t *n_kept) {
-    TSC_API_GUARD_BEGIN
-    TSC_REQUIRE(c && frags && frag_off && n_atoms && n_conf && start && end && direction && pivot && meanpoint && r0 && r1 && n_reactive && conf_idx && angles &&
-                    clash_ok && kept && n_pass && n_kept,
-                "tsc_cyclical_embed_groups: null argument");
-    TSC_REQUIRE(n_mols == 2 || n_mols == 3, "tsc_cyclical_embed_groups: %d molecules, the cyclical embed takes 2 or 3", n_mols);
+// What tsc_cyclical_embed_groups and a slab of an embed-and-prune run (tsc_embed_prune_add_groups) share.  The checks of one slab of groups,
+// in two steps around the caller's "no groups: nothing to do":
+static int check_group_slab_sizes(int64_t n_groups, int n_angles, double rmsd_thr) {
     TSC_REQUIRE(n_angles >= 1 && n_angles <= GF_MAX_GROUP, "%d angle sets per group: must be in [1, %d]", n_angles, GF_MAX_GROUP);
     TSC_REQUIRE(n_groups >= 0 && n_groups < INT32_MAX / n_angles, "%lld groups of %d poses: too many candidates", (long long)n_groups, n_angles);
     TSC_REQUIRE(rmsd_thr > 0, "bad sizes");
-    *n_pass = *n_kept = 0;
-    if (n_groups == 0) return 0;
-    FragTable ft;
-    TSC_TRY(make_frag_table(frag_off, n_atoms, n_conf, n_mols, &ft));
-    const int64_t items = n_groups * n_mols, n_poses = n_groups * n_angles, rows = n_poses * n_mols;
-    for (int64_t q = 0; q < items; ++q) {
+    return 0;
+}
+static int check_group_slab_records(const int32_t *n_conf, int n_mols, const int32_t *n_reactive, const int32_t *conf_idx, int64_t n_groups) {
+    for (int64_t q = 0; q < n_groups * n_mols; ++q) {
         TSC_REQUIRE(n_reactive[q] == 1 || n_reactive[q] == 2, "group %lld, molecule %d: n_reactive must be 1 or 2", (long long)(q / n_mols), int(q % n_mols));
         TSC_REQUIRE(conf_idx[q] >= 0 && conf_idx[q] < n_conf[q % n_mols], "group %lld, molecule %d: conformer index out of range", (long long)(q / n_mols),
                     int(q % n_mols));
     }
-    std::vector<int32_t> goff(size_t(n_groups) + 1);
+    return 0;
+}
+
+// ... and the device work of one slab up to the kept flags: the records uploaded, the parameters of every pose, then embed_filter_front with
+// the greedy filter inside each group.  d_frags is on the device already (uploaded by the call, or once by the run).  `goff` is the caller's,
+// declared in front of its HostCall: it is uploaded from and must outlive the call's last wait.
+static int cyclical_groups_front(tsc_ctx *c, HostCall &h, std::vector<int32_t> &goff, const double *d_frags, const FragTable &ft, const int64_t *frag_off,
+                                 const int32_t *n_atoms, const int32_t *n_conf, const double *const host[7], const int32_t *n_reactive, const int32_t *conf_idx,
+                                 const double *angles, int64_t n_groups, int n_angles, double clash_thresh, int64_t max_clashes, double rmsd_thr,
+                                 uint8_t *clash_ok, uint8_t *kept, EmbedFiltered *f) {
+    const int n_mols = ft.n_mols;
+    const int64_t items = n_groups * n_mols, n_poses = n_groups * n_angles, rows = n_poses * n_mols;
+    goff.resize(size_t(n_groups) + 1);
     for (int64_t g = 0; g <= n_groups; ++g) goff[size_t(g)] = int32_t(g * n_angles);
-    HostCall h(c);
     Scratch &s = h.scratch();
-    const double *host[7] = {start, end, direction, pivot, meanpoint, r0, r1};
-    double *d_frags, *dev[7], *d_angles, *d_rot, *d_pos;
+    double *dev[7], *d_angles, *d_rot, *d_pos;
     int32_t *d_nr, *d_cg, *d_ci, *d_goff, *d_goff_pass;
-    TSC_TRY(h.in(frags, size_t(frags_total_doubles(frag_off, n_atoms, n_conf, n_mols)), &d_frags));
     for (int i = 0; i < 7; ++i) TSC_TRY(h.in(host[i], size_t(items) * 3, &dev[i]));
     TSC_TRY(h.in(n_reactive, size_t(items), &d_nr));
     TSC_TRY(h.in(conf_idx, size_t(items), &d_cg));
@@ -791,6 +816,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_cyclical_embed_groups(
                        (const double *)dev[5], (const double *)dev[6], (const int32_t *)d_nr, (const int32_t *)d_cg, (const double *)d_angles, n_groups, n_mols,
                        n_angles, d_rot, d_pos, d_ci);
     TSC_HIP(hipGetLastError());
+    f->ci = d_ci, f->rot = d_rot, f->pos = d_pos;
     const int n = ft.n_total;
     const int ng = int(n_groups);
     auto filter = [&](const double *d_structs, int32_t np, const int32_t *pos_scan, const int32_t *total, uint8_t *d_acc) -> int {
@@ -799,8 +825,41 @@ extern "C" __attribute__((visibility("default"))) int tsc_cyclical_embed_groups(
         TSC_HIP(hipGetLastError());
         return tsc_greedy_group_filter_dev(c, d_structs, d_goff_pass, ng, np, n, rmsd_thr, d_acc);
     };
-    return embed_filter_run(c, h, d_frags, ft, frag_off, n_atoms, n_conf, d_ci, d_rot, d_pos, n_poses, clash_thresh, max_clashes, clash_ok, kept, poses,
-                            poses_capacity, n_pass, n_kept, filter);
+    return embed_filter_front(c, h, d_frags, ft, frag_off, n_atoms, n_conf, d_ci, d_rot, d_pos, n_poses, clash_thresh, max_clashes, clash_ok, kept, f, filter);
+}
+
+// The same embed from one record per (group, molecule) and one angle table shared by all groups: pose g * n_angles + a is record g under
+// angle set a, what tsc_cyclical_embed computes on the rows a caller would expand from them.  Per pose nothing is uploaded or checked.
+extern "C" __attribute__((visibility("default"))) int tsc_cyclical_embed_groups(tsc_ctx *c, const double *frags, const int64_t *frag_off, const int32_t *n_atoms,
+                                                                                const int32_t *n_conf, int n_mols, const double *start, const double *end,
+                                                                                const double *direction, const double *pivot, const double *meanpoint,
+                                                                                const double *r0, const double *r1, const int32_t *n_reactive,
+                                                                                const int32_t *conf_idx, const double *angles, int64_t n_groups, int n_angles,
+                                                                                double clash_thresh, int64_t max_clashes, double rmsd_thr, uint8_t *clash_ok,
+                                                                                uint8_t *kept, double *poses, int64_t poses_capacity, int64_t *n_pass,
+                                                                                int64_t *n_kept) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(c && frags && frag_off && n_atoms && n_conf && start && end && direction && pivot && meanpoint && r0 && r1 && n_reactive && conf_idx && angles &&
+                    clash_ok && kept && n_pass && n_kept,
+                "tsc_cyclical_embed_groups: null argument");
+    TSC_REQUIRE(n_mols == 2 || n_mols == 3, "tsc_cyclical_embed_groups: %d molecules, the cyclical embed takes 2 or 3", n_mols);
+    TSC_TRY(check_group_slab_sizes(n_groups, n_angles, rmsd_thr));
+    *n_pass = *n_kept = 0;
+    if (n_groups == 0) return 0;
+    FragTable ft;
+    TSC_TRY(make_frag_table(frag_off, n_atoms, n_conf, n_mols, &ft));
+    TSC_TRY(check_group_slab_records(n_conf, n_mols, n_reactive, conf_idx, n_groups));
+    std::vector<int32_t> goff;
+    HostCall h(c);
+    const double *host[7] = {start, end, direction, pivot, meanpoint, r0, r1};
+    double *d_frags;
+    TSC_TRY(h.in(frags, size_t(frags_total_doubles(frag_off, n_atoms, n_conf, n_mols)), &d_frags));
+    EmbedFiltered f;
+    const int rc = cyclical_groups_front(c, h, goff, d_frags, ft, frag_off, n_atoms, n_conf, host, n_reactive, conf_idx, angles, n_groups, n_angles, clash_thresh,
+                                         max_clashes, rmsd_thr, clash_ok, kept, &f);
+    *n_pass = f.n_pass;
+    TSC_TRY(rc);
+    return embed_filter_fetch(c, h, ft.n_total, f, poses, poses_capacity, n_kept);
     TSC_API_GUARD_END
 }
 
@@ -908,6 +967,259 @@ extern "C" __attribute__((visibility("default"))) int tsc_trimolecular_groups(
     const hipError_t launched = hipGetLastError();
     if (launched == hipSuccess) tm.end(&g_trimolecular_ms);
     TSC_HIP(launched);
+    return h.finish();
+    TSC_API_GUARD_END
+}
+
+// --------------------------------------------------------------------------------------------------
+// a cyclical embed whose kept poses are pruned by RMSD where they are (tscode/embeds.py:657-717 / :785-847, then tscode/rmsd_pruning.py:164-206)
+//
+// The run owns, on the device: the fragment stacks; and per kept pose, in candidate order over all slabs, its heavy atoms (what the prune
+// reads) and its parameters (what the pose is embedded from again once the prune has spoken).  Nothing per pose crosses to the host but two
+// flag bytes per candidate and, at the end, the poses that were asked for.
+
+struct tsc_embed_prune {
+    tsc_ctx *ctx = nullptr;
+    FragTable ft;
+    int64_t frag_off[MAX_MOLS];
+    int32_t n_atoms[MAX_MOLS], n_conf[MAX_MOLS];
+    int n_heavy = 0;
+    double *frags = nullptr;
+    int32_t *sel = nullptr;          // i32[n_heavy * 3]: the doubles of a pose that are its heavy atoms' (launch_gather_rows)
+    double *heavy = nullptr, *rot = nullptr, *pos = nullptr;   // f64[cap, n_heavy * 3], [cap, n_mols * 9], [cap, n_mols * 3]
+    int32_t *ci = nullptr;           // i32[cap, n_mols]
+    uint8_t *survived = nullptr;     // u8[n_kept] once tsc_embed_prune_run has run
+    int64_t cap = 0, n_kept = 0, n_survived = 0;
+    bool pruned = false;
+    void release_all() {
+        for (void *q : {static_cast<void *>(frags), static_cast<void *>(sel), static_cast<void *>(heavy), static_cast<void *>(rot), static_cast<void *>(pos),
+                        static_cast<void *>(ci), static_cast<void *>(survived)})
+            if (q) ctx->release(q);
+    }
+};
+
+// cand[r] = act[act2[r]]: the candidate of every kept pose, from the candidate of every passing pose and the passing pose of every kept one
+static __global__ __launch_bounds__(256) void k_kept_candidates(const int32_t *__restrict__ act, const int32_t *__restrict__ act2, int n_kept,
+                                                                int32_t *__restrict__ cand) {
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < n_kept; r += gridDim.x * 256) cand[r] = act[act2[r]];
+}
+
+// dst[r][w] = src[idx[r]][w] for rows of `row` 32-bit words (k_gather_rows moves 64-bit words; a row of three conformer indices is 12 bytes)
+static __global__ __launch_bounds__(256) void k_gather_rows_i32(const int32_t *__restrict__ src, const int32_t *__restrict__ idx, int64_t n_out, int row,
+                                                                int32_t *__restrict__ dst) {
+    const int64_t total = n_out * row;
+    for (int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x; e < total; e += int64_t(gridDim.x) * 256) {
+        const int64_t r = e / row;
+        dst[e] = src[int64_t(idx[r]) * row + (e - r * row)];
+    }
+}
+
+// room for `need` rows in the run's four buffers: what they hold moves to blocks twice the size (embed_prune_plan.hpp), on the stream
+static int embed_prune_reserve(tsc_embed_prune *r, int64_t need) {
+    tsc_ctx *c = r->ctx;
+    const int64_t cap = ep_grown_capacity(r->cap, need);
+    TSC_REQUIRE(cap >= 0, "tsc_embed_prune_add_groups: %lld kept poses are more than a prune takes (%lld)", (long long)need, (long long)EP_MAX_ROWS);
+    if (cap == r->cap) return 0;
+    const int nm = r->ft.n_mols;
+    const size_t row_bytes[4] = {size_t(r->n_heavy) * 24, size_t(nm) * 72, size_t(nm) * 24, size_t(nm) * 4};
+    void *old[4] = {r->heavy, r->rot, r->pos, r->ci}, *grown[4] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = 0;
+    for (int i = 0; i < 4 && !rc; ++i) rc = c->alloc(size_t(cap) * row_bytes[i], &grown[i]);
+    for (int i = 0; i < 4 && !rc; ++i)
+        if (r->n_kept > 0 && hipMemcpyAsync(grown[i], old[i], size_t(r->n_kept) * row_bytes[i], hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+            rc = fail(TSC_ERR_HIP, "tsc_embed_prune_add_groups: the copy into the grown buffers failed");
+    if (rc) {
+        for (void *q : grown)
+            if (q) c->release(q);
+        return rc;
+    }
+    for (void *q : old)
+        if (q) c->release(q);   // (recycled in stream order: behind the copies)
+    r->heavy = static_cast<double *>(grown[0]), r->rot = static_cast<double *>(grown[1]), r->pos = static_cast<double *>(grown[2]);
+    r->ci = static_cast<int32_t *>(grown[3]);
+    r->cap = cap;
+    return 0;
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_embed_prune_destroy(tsc_embed_prune *r) {
+    TSC_API_GUARD_BEGIN
+    if (!r) return 0;
+    DeviceGuard guard(r->ctx->device);
+    (void)hipStreamSynchronize(r->ctx->stream);
+    {
+        std::lock_guard<std::mutex> lock(r->ctx->runs_mutex);
+        auto &lr = r->ctx->live_embed_prune;
+        lr.erase(std::remove(lr.begin(), lr.end(), r), lr.end());
+    }
+    r->release_all();   // (its blocks go back to the cache)
+    delete r;
+    return 0;
+    TSC_API_GUARD_END
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_embed_prune_create(tsc_ctx *c, const double *frags, const int64_t *frag_off, const int32_t *n_atoms,
+                                                                             const int32_t *n_conf, int n_mols, const int32_t *heavy_idx, int n_heavy,
+                                                                             tsc_embed_prune **out) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(c && frags && frag_off && n_atoms && n_conf && heavy_idx && out, "tsc_embed_prune_create: null argument");
+    *out = nullptr;
+    TSC_REQUIRE(n_mols == 2 || n_mols == 3, "tsc_embed_prune_create: %d molecules, the cyclical embed takes 2 or 3", n_mols);
+    FragTable ft;
+    TSC_TRY(make_frag_table(frag_off, n_atoms, n_conf, n_mols, &ft));
+    TSC_REQUIRE(n_heavy >= 1 && n_heavy <= ft.n_total, "tsc_embed_prune_create: %d heavy atoms of %d atoms: at least one, at most all", n_heavy, ft.n_total);
+    std::vector<int32_t> sel(size_t(n_heavy) * 3);
+    for (int a = 0; a < n_heavy; ++a) {
+        TSC_REQUIRE(heavy_idx[a] >= 0 && heavy_idx[a] < ft.n_total, "tsc_embed_prune_create: heavy_idx[%d] = %d is not an atom of the %d", a, heavy_idx[a],
+                    ft.n_total);
+        TSC_REQUIRE(a == 0 || heavy_idx[a] > heavy_idx[a - 1], "tsc_embed_prune_create: heavy_idx[%d] = %d does not increase", a, heavy_idx[a]);
+        for (int k = 0; k < 3; ++k) sel[size_t(a) * 3 + k] = heavy_idx[a] * 3 + k;
+    }
+    DeviceGuard guard(c->device);
+    tsc_embed_prune *r = new tsc_embed_prune();
+    r->ctx = c, r->ft = ft, r->n_heavy = n_heavy;
+    for (int m = 0; m < n_mols; ++m) r->frag_off[m] = frag_off[m], r->n_atoms[m] = n_atoms[m], r->n_conf[m] = n_conf[m];
+    const size_t n_frag = size_t(frags_total_doubles(frag_off, n_atoms, n_conf, n_mols));
+    void *q = nullptr;
+    int rc = c->alloc(n_frag * sizeof(double), &q);
+    if (!rc) {
+        r->frags = static_cast<double *>(q);
+        rc = c->alloc(sel.size() * sizeof(int32_t), &q);
+    }
+    if (!rc) {
+        r->sel = static_cast<int32_t *>(q);
+        hipError_t e = hipMemcpyAsync(r->frags, frags, n_frag * sizeof(double), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(r->sel, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+        const hipError_t waited = hipStreamSynchronize(c->stream);   // (the copies read the caller's array and a local one)
+        if (e == hipSuccess) e = waited;
+        if (e != hipSuccess) rc = fail(TSC_ERR_HIP, "tsc_embed_prune_create: the upload of the fragments failed: %s", hipGetErrorString(e));
+    }
+    if (rc) {
+        r->release_all();
+        delete r;
+        return rc;
+    }
+    {
+        std::lock_guard<std::mutex> lock(c->runs_mutex);
+        c->live_embed_prune.push_back(r);   // (destroyed with the context, tsc_ctx_destroy)
+    }
+    *out = r;
+    return 0;
+    TSC_API_GUARD_END
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_embed_prune_add_groups(tsc_embed_prune *r, const double *start, const double *end, const double *direction,
+                                                                                 const double *pivot, const double *meanpoint, const double *r0, const double *r1,
+                                                                                 const int32_t *n_reactive, const int32_t *conf_idx, const double *angles,
+                                                                                 int64_t n_groups, int n_angles, double clash_thresh, int64_t max_clashes,
+                                                                                 double rmsd_thr_filter, uint8_t *clash_ok, uint8_t *kept, int64_t *n_pass,
+                                                                                 int64_t *n_kept) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(r && start && end && direction && pivot && meanpoint && r0 && r1 && n_reactive && conf_idx && angles && clash_ok && kept && n_pass && n_kept,
+                "tsc_embed_prune_add_groups: null argument");
+    if (r->pruned) return fail(TSC_ERR_STATE, "tsc_embed_prune_add_groups: the run has been pruned (tsc_embed_prune_run); a further slab needs a new run");
+    TSC_TRY(check_group_slab_sizes(n_groups, n_angles, rmsd_thr_filter));
+    *n_pass = *n_kept = 0;
+    if (n_groups == 0) return 0;
+    tsc_ctx *c = r->ctx;
+    const int n_mols = r->ft.n_mols, n = r->ft.n_total;
+    TSC_TRY(check_group_slab_records(r->n_conf, n_mols, n_reactive, conf_idx, n_groups));
+    std::vector<int32_t> goff;
+    HostCall h(c);
+    const double *host[7] = {start, end, direction, pivot, meanpoint, r0, r1};
+    EmbedFiltered f;
+    const int rc = cyclical_groups_front(c, h, goff, r->frags, r->ft, r->frag_off, r->n_atoms, r->n_conf, host, n_reactive, conf_idx, angles, n_groups, n_angles,
+                                         clash_thresh, max_clashes, rmsd_thr_filter, clash_ok, kept, &f);
+    *n_pass = f.n_pass;
+    TSC_TRY(rc);
+    if (f.n_kept > 0) {
+        // the kept poses' heavy atoms out of the buffer the filter read, and their parameters, behind what earlier slabs left
+        TSC_TRY(embed_prune_reserve(r, r->n_kept + f.n_kept));
+        int32_t *cand;
+        TSC_TRY(h.scratch().get(size_t(f.n_kept), &cand));
+        hipLaunchKernelGGL(k_kept_candidates, dim3(grid_for(f.n_kept, 256, 1024)), dim3(256), 0, c->stream, (const int32_t *)f.act, (const int32_t *)f.act2, f.n_kept,
+                           cand);
+        TSC_HIP(hipGetLastError());
+        const int64_t at = r->n_kept;
+        TSC_TRY(launch_gather_rows(c->stream, f.structs, f.act2, f.n_kept, n * 3, r->sel, r->n_heavy * 3, r->heavy + ep_row_offset(at, r->n_heavy * 3)));
+        TSC_TRY(launch_gather_rows(c->stream, f.rot, cand, f.n_kept, n_mols * 9, nullptr, n_mols * 9, r->rot + ep_row_offset(at, n_mols * 9)));
+        TSC_TRY(launch_gather_rows(c->stream, f.pos, cand, f.n_kept, n_mols * 3, nullptr, n_mols * 3, r->pos + ep_row_offset(at, n_mols * 3)));
+        hipLaunchKernelGGL(k_gather_rows_i32, dim3(grid_for(int64_t(f.n_kept) * n_mols, 256, 1024)), dim3(256), 0, c->stream, f.ci, (const int32_t *)cand,
+                           int64_t(f.n_kept), n_mols, r->ci + ep_row_offset(at, n_mols));
+        TSC_HIP(hipGetLastError());
+    }
+    TSC_TRY(h.finish());   // (the kept flags; the slab's pose buffer goes back to the cache with the call)
+    r->n_kept += f.n_kept;
+    *n_kept = f.n_kept;
+    return 0;
+    TSC_API_GUARD_END
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_embed_prune_count(tsc_embed_prune *r, int64_t *n_kept_total) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(r && n_kept_total, "tsc_embed_prune_count: null argument");
+    *n_kept_total = r->n_kept;
+    return 0;
+    TSC_API_GUARD_END
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_embed_prune_run(tsc_embed_prune *r, double rmsd_thr, int mode, uint8_t *survived, tsc_pass_stats *stats,
+                                                                          int *n_passes, int64_t *n_survived) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(r && n_survived && (survived || r->n_kept == 0), "tsc_embed_prune_run: null argument");
+    TSC_REQUIRE(mode == 0 || mode == 1, "tsc_embed_prune_run: mode %d (0: reference-exact, 1: cache-free)", mode);
+    TSC_REQUIRE(rmsd_thr > 0, "tsc_embed_prune_run: rmsd_thr = %g must be positive", rmsd_thr);
+    *n_survived = 0;
+    if (n_passes) *n_passes = 0;
+    tsc_ctx *c = r->ctx;
+    if (r->n_kept == 0) {   // (nothing is launched)
+        r->pruned = true, r->n_survived = 0;
+        return 0;
+    }
+    DeviceGuard guard(c->device);
+    if (!r->survived) {
+        void *q = nullptr;
+        TSC_TRY(c->alloc(size_t(r->n_kept), &q));
+        r->survived = static_cast<uint8_t *>(q);
+    }
+    r->pruned = true, r->n_survived = 0;   // (from here on the set of kept poses is closed, whatever becomes of the prune)
+    TSC_TRY(tsc_prune_rmsd_dev(c, r->heavy, r->n_kept, r->n_heavy, rmsd_thr, mode, r->survived, stats, n_passes));
+    TSC_HIP(hipMemcpyAsync(survived, r->survived, size_t(r->n_kept), hipMemcpyDeviceToHost, c->stream));
+    TSC_HIP(hipStreamSynchronize(c->stream));
+    int64_t count = 0;
+    for (int64_t i = 0; i < r->n_kept; ++i) count += survived[i] != 0;
+    r->n_survived = count;
+    *n_survived = count;
+    return 0;
+    TSC_API_GUARD_END
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_embed_prune_poses(tsc_embed_prune *r, int which, double *poses, int64_t capacity) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(r && poses, "tsc_embed_prune_poses: null argument");
+    TSC_REQUIRE(which == 0 || which == 1, "tsc_embed_prune_poses: which = %d (0: the survivors, 1: every kept pose)", which);
+    if (which == 0 && !r->pruned) return fail(TSC_ERR_STATE, "tsc_embed_prune_poses: the survivors are known once tsc_embed_prune_run has run");
+    const int64_t rows = which == 0 ? r->n_survived : r->n_kept;
+    TSC_REQUIRE(capacity >= rows, "tsc_embed_prune_poses: poses holds %lld rows, %lld are asked for", (long long)capacity, (long long)rows);
+    if (rows == 0) return 0;
+    tsc_ctx *c = r->ctx;
+    const int n = r->ft.n_total;
+    HostCall h(c);
+    Scratch &s = h.scratch();
+    int32_t *act = nullptr;
+    if (which == 0) {
+        int32_t *bsum;
+        TSC_TRY(s.get(scan_bsum_count(r->n_kept), &bsum));
+        TSC_TRY(s.get(size_t(r->n_kept), &act));
+        TSC_TRY(scan_mask(c->stream, r->survived, r->n_kept, bsum, nullptr, act, nullptr, nullptr));
+    }
+    // the kernel, and the parameters, that embedded these poses for the filter: the same values come out
+    double *d_out;
+    TSC_TRY(s.get(size_t(rows) * n * 3, &d_out));
+    hipLaunchKernelGGL(k_transform, dim3(grid_for(rows, TR_POSES, 256 * 64)), dim3(256), transform_lds_bytes(r->ft.n_mols), c->stream, (const double *)r->frags, r->ft,
+                       (const int32_t *)r->ci, (const double *)r->rot, (const double *)r->pos, (const int32_t *)act, rows, d_out, (const int32_t *)nullptr, 0,
+                       (double *)nullptr, (const int32_t *)nullptr);
+    TSC_HIP(hipGetLastError());
+    TSC_TRY(h.fetch(poses, (const double *)d_out, size_t(rows) * n * 3));
     return h.finish();
     TSC_API_GUARD_END
 }

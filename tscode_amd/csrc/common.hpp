@@ -117,6 +117,7 @@ struct tsc_ctx {
     std::vector<tsc_prune *> live_runs;
     std::vector<tsc_rot_corr *> live_rot_corr;  // live runs of the symmetry-corrected prune (rot_corr.hip), destroyed with the context too
     std::vector<tsc_rot_corr_batch *> live_rot_corr_batch;  // ... and of its many-ensembles form (refine_batch.hip)
+    std::vector<tsc_embed_prune *> live_embed_prune;        // ... and the embed-and-prune runs (adjacent.hip), whose buffers are blocks of this context
     std::vector<int32_t> sample_host;     // pose indices of the basis sample of the last tsc_pipeline_dev call and their device copy
     int32_t *sample_dev = nullptr;
     double *mom_acc = nullptr;            // moment accumulators of the pipeline's basis chain (k_sample_moments adds, k_descriptor_basis clears)

@@ -82,6 +82,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_ctx_destroy(tsc_ctx *c
     while (!c->live_runs.empty()) (void)tsc_prune_destroy(c->live_runs.back());
     while (!c->live_rot_corr.empty()) (void)tsc_rot_corr_destroy(c->live_rot_corr.back());
     while (!c->live_rot_corr_batch.empty()) (void)tsc_rot_corr_batch_destroy(c->live_rot_corr_batch.back());
+    while (!c->live_embed_prune.empty()) (void)tsc_embed_prune_destroy(c->live_embed_prune.back());
     for (auto &kv : c->cache) (void)hipFree(kv.second);
     for (auto &kv : c->live) (void)hipFree(kv.first);
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);

@@ -16,7 +16,7 @@ from .engine import FragmentSet, get_engine
 from .utils import cartesian_product, polygonize
 
 __all__ = ["get_embed", "embed_batch", "string_embed_poses", "filter_angular_groups", "string_embed_batch", "cyclical_embed_batch",
-           "trimolecular_groups_batch", "EmbedTrace", "string_embed", "cyclical_embed"]
+           "cyclical_embed_prune_batch", "trimolecular_groups_batch", "EmbedTrace", "string_embed", "cyclical_embed"]
 
 
 def get_embed(mols, conf_ids):
@@ -632,27 +632,114 @@ def _run_group_records(coords, blocks, group_ids, angles, clash_thresh, max_clas
     """The groups' records as they are -> tsc_cyclical_embed_groups, one record per (group, molecule) and ONE angle table, in slabs of whole
     groups holding at most ``max_poses_per_call`` poses (groups are independent: the result does not depend on the slab size).  What
     ``_run_cyclical_groups`` returns; the trace's per-group tuples come from ``trace_groups()`` and only where a trace is wanted."""
-    if int(max_poses_per_call) < 1:
-        raise ValueError("max_poses_per_call must be at least 1")
-    n_mols, A, G = len(coords), len(angles), len(blocks)
     n_total = sum(c.shape[1] for c in coords)
     frags = FragmentSet(coords)
-    eng = get_engine() if G else None
+    pose_parts = []
+
+    def one_slab(*args):
+        ok, kept, poses = get_engine().cyclical_embed_groups(frags, *args, clash_thresh, max_clashes, rmsd_thr)
+        pose_parts.append(poses)
+        return ok, kept
+    ok, kept, group_of, constrained = _walk_group_records(len(coords), blocks, group_ids, angles, max_poses_per_call, one_slab)
+    poses = np.concatenate(pose_parts) if pose_parts else np.zeros((0, n_total, 3))
+    if trace_groups is not None:
+        return poses, constrained, EmbedTrace(clash_ok=ok, kept=kept, group_of=group_of, groups=trace_groups())
+    return poses, constrained
+
+
+def _walk_group_records(n_mols, blocks, group_ids, angles, max_poses_per_call, one_slab):
+    """What the drivers over group records share: the 23-field records cut into the arrays the library takes, walked in slabs of whole groups
+    (``_slabs``); ``one_slab(start, end, direction, pivot, meanpoint, r0, r1, n_reactive, conf_idx, angles) -> (clash_ok, kept)`` is the
+    library call of either.  Returns both flags over all candidates, the group of every candidate and the facing atoms of the kept poses."""
+    if int(max_poses_per_call) < 1:
+        raise ValueError("max_poses_per_call must be at least 1")
+    A, G = len(angles), len(blocks)
     field = lambda lo, hi, dtype=np.float64: np.ascontiguousarray(blocks[:, :, lo:hi], dtype=dtype)
     fields = [field(lo, lo + 3) for lo in range(0, 21, 3)]
     n_reactive, conf_idx = field(21, 22, np.int32).reshape(G, n_mols), field(22, 23, np.int32).reshape(G, n_mols)
-    ok_parts, kept_parts, pose_parts = [], [], []
+    ok_parts, kept_parts = [], []
     for at, end in _slabs(G, A, max_poses_per_call):
-        ok, kept, poses = eng.cyclical_embed_groups(frags, *[f[at:end] for f in fields], n_reactive[at:end], conf_idx[at:end], angles, clash_thresh, max_clashes,
-                                                    rmsd_thr)
-        ok_parts.append(ok), kept_parts.append(kept), pose_parts.append(poses)
+        ok, kept = one_slab(*[f[at:end] for f in fields], n_reactive[at:end], conf_idx[at:end], angles)
+        ok_parts.append(ok), kept_parts.append(kept)
     ok = np.concatenate(ok_parts) if ok_parts else np.zeros(0, bool)
     kept = np.concatenate(kept_parts) if kept_parts else np.zeros(0, bool)
-    poses = np.concatenate(pose_parts) if pose_parts else np.zeros((0, n_total, 3))
     group_of = np.repeat(np.arange(G), A)
     constrained = group_ids[group_of[kept]].reshape(-1, n_mols, 2)                                   # :718
-    if trace_groups is not None:
-        return poses, constrained, EmbedTrace(clash_ok=ok, kept=kept, group_of=group_of, groups=trace_groups())
+    return ok, kept, group_of, constrained
+
+
+def cyclical_embed_prune_batch(mols, systematic_angles, atomnos, rmsd_thr=0.5, mode=0, clash_thresh=1.5, max_clashes=0, rigid_shortcut=True,
+                               max_norm_delta=5, pairings=None, internal_constraints=(), filter_rmsd_thr=1, return_trace=False,
+                               max_poses_per_call=DEFAULT_MAX_POSES_PER_CALL):
+    """``cyclical_embed_batch`` followed by ``prune_conformers_rmsd`` on its poses, without the kept poses leaving the device in between.
+
+    By definition the result equals
+
+        p, c = cyclical_embed_batch(mols, systematic_angles, ..., rmsd_thr=filter_rmsd_thr)
+        out, m = prune_conformers_rmsd(p, atomnos, rmsd_thr, mode)
+        return out, c[m]
+
+    -- the same poses to the last bit -- but that composition fetches every kept pose (n_kept * n_total * 24 bytes) and uploads it again for
+    the prune.  Here the embed's slabs (``tsc_embed_prune_add_groups``) leave the heavy atoms and the 100-byte-per-molecule parameters of the
+    kept poses on the device, the prune runs on them there (``tsc_embed_prune_run``), and only the survivors are embedded again and fetched.
+
+    mols, systematic_angles, clash_thresh, max_clashes, rigid_shortcut, max_norm_delta, pairings, internal_constraints: as ``cyclical_embed_batch``
+    (two or three molecules; the groups are built as it builds them, on the device for three).  ``atomnos`` int[n_total] with at least one
+    entry that is not 1; ``rmsd_thr`` / ``mode`` as ``prune_conformers_rmsd``; ``filter_rmsd_thr`` is ``cyclical_embed_batch``'s ``rmsd_thr``.
+
+    Returns ``(poses f64[n_survived, n_total, 3], constrained_indices int[n_survived, n_mols, 2])``; with ``return_trace`` also an EmbedTrace
+    over all candidates (``clash_ok``, ``kept``, ``group_of``, ``groups``) with ``survived`` bool[n_kept] over the kept poses and ``prune_stats``,
+    the prune's per-pass statistics."""
+    get = lambda m, k: m[k] if isinstance(m, dict) else getattr(m, k)
+    if len(mols) not in (2, 3):
+        raise ValueError("cyclical_embed_prune_batch embeds two or three molecules")
+    n_mols = len(mols)
+    coords = [np.ascontiguousarray(get(m, "coords"), dtype=np.float64) for m in mols]
+    n_total = sum(c.shape[1] for c in coords)
+    atomnos = np.asarray(atomnos)
+    if atomnos.shape != (n_total,):
+        raise ValueError(f"atomnos must have one entry per atom of the embedded structure ({n_total}), got shape {atomnos.shape}")
+    heavy_idx = np.flatnonzero(atomnos != 1)
+    if not len(heavy_idx):
+        raise ValueError("atomnos names no atom that is not hydrogen: there is nothing to prune on")
+    angles = np.asarray(systematic_angles, dtype=np.float64).reshape(-1, n_mols)
+    if len(angles) > MAX_GROUP_POSES:
+        raise ValueError(f"{len(angles)} angle sets per group: tsc_embed_prune_add_groups takes groups of up to {MAX_GROUP_POSES} poses")
+    if n_mols == 3:
+        g = trimolecular_groups_batch(mols, pairings, internal_constraints)
+        blocks, group_ids = g.blocks, g.group_ids
+        trace_groups = lambda: [(tuple(int(c) for c in g.conf[q]), tuple(int(i) for i in g.pivot_index[q]), int(g.orientation[q]), g.group_ids[q].tolist())
+                                for q in range(len(blocks))]
+    else:
+        reactive = [np.atleast_1d(np.asarray(get(m, "reactive_indices"), dtype=np.int64)) for m in mols]
+        blocks, group_ids, meta = _bimolecular_groups(coords, reactive, [get(m, "pivots") for m in mols], rigid_shortcut, max_norm_delta, pairings,
+                                                      internal_constraints, return_trace)
+
+        def trace_groups():
+            flat = [(conf, pis[q], vs[q]) for conf, pis, vs in meta for q in range(len(vs))]
+            return [(tuple(int(c) for c in conf), tuple(int(i) for i in pi), int(v), group_ids[q].tolist()) for q, (conf, pi, v) in enumerate(flat)]
+    run = None
+
+    def one_slab(*args):
+        nonlocal run
+        if run is None:                                                                              # (the fragments go up once, for all slabs)
+            run = get_engine().embed_prune_run(FragmentSet(coords), heavy_idx)
+        return run.add_groups(*args, clash_thresh, max_clashes, filter_rmsd_thr)
+    try:
+        ok, kept, group_of, constrained = _walk_group_records(n_mols, blocks, group_ids, angles, max_poses_per_call, one_slab)
+        if run is None:
+            survived, stats, poses = np.zeros(0, bool), [], np.zeros((0, n_total, 3))
+        else:
+            survived, stats = run.run(float(rmsd_thr), int(mode))
+            poses = run.poses(0)
+    finally:
+        if run is not None:
+            run.close()
+    if len(survived) > 1 and stats and stats[0].get("nonfinite_input"):
+        raise np.linalg.LinAlgError("Array must not contain infs or NaNs")                           # (as prune_conformers_rmsd)
+    constrained = constrained[survived]
+    if return_trace:
+        return poses, constrained, EmbedTrace(clash_ok=ok, kept=kept, group_of=group_of, groups=trace_groups(), survived=survived, prune_stats=stats)
     return poses, constrained
 
 

@@ -509,6 +509,10 @@ class Engine:
                                                  C.c_double(float(rmsd_thr)), ptr(ok), ptr(kept), ptr(poses), C.c_int64(N), C.byref(n_pass), C.byref(n_kept)))
         return ok.astype(bool), kept.astype(bool), (poses[:n_kept.value].copy() if want_poses else None)
 
+    def embed_prune_run(self, frags: FragmentSet, heavy_idx):
+        """An embed-and-prune run (tsc_embed_prune_*): the fragments go to the device once; ``add_groups`` per slab, ``run``, ``poses``."""
+        return EmbedPruneRun(self, frags, heavy_idx)
+
     def trimolecular_groups(self, frags: FragmentSet, reactive, reactive_cumnums, conf, pivot, meanpoint, cumnums, tri_poly, tri_cost, directions, mask):
         """tsc_trimolecular_groups: the 23-field records of a three-molecule cyclical embed from per-triple arrays (tscode/embeds.py:312-465 inside
         :636-655).  ``reactive[m]`` 1 or 2 atom indices, ``reactive_cumnums[m]`` int[R <= 8, 2] = (atom, cumnum); per pivot triple ``conf`` i32[T, 3],
@@ -1055,6 +1059,76 @@ class IpcExchange:
             if getattr(self.e, "_h", None):
                 self.e.lib.tsc_xchg_destroy(self._x)
             self._x = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EmbedPruneRun:
+    """One embed-and-prune run (include/tscode_hip.h, tsc_embed_prune_*): a cyclical embed whose kept poses stay on the device, are pruned by
+    RMSD there, and of which only the poses asked for are embedded again and fetched."""
+
+    def __init__(self, engine: Engine, frags: FragmentSet, heavy_idx):
+        self.e, self.frags = engine, frags
+        heavy_idx = np.ascontiguousarray(heavy_idx, dtype=np.int32).ravel()
+        r = C.c_void_p()
+        check(engine.lib.tsc_embed_prune_create(engine._h, ptr(frags.flat), *frags.table_args(), heavy_idx.ctypes.data_as(_lib.c_i32p),
+                                                C.c_int(len(heavy_idx)), C.byref(r)))
+        self._r = r
+        self.n_survived = None
+        engine._runs.add(self)               # closed with the engine, before its context goes
+
+    def add_groups(self, start, end, direction, pivot, meanpoint, r0, r1, n_reactive, conf_idx, angles, clash_thresh, max_clashes, rmsd_thr=1.0):
+        """One slab of groups, arguments as ``Engine.cyclical_embed_groups``: (clash_ok bool[G * A], kept bool[G * A]); the kept poses stay on
+        the device, behind those of the slabs before."""
+        nm = self.frags.n_mols
+        arrs = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3) for x in (start, end, direction, pivot, meanpoint, r0, r1)]
+        n_reactive = np.ascontiguousarray(n_reactive, dtype=np.int32).ravel()
+        conf_idx = np.ascontiguousarray(conf_idx, dtype=np.int32).ravel()
+        angles = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1, nm)
+        items, A = len(n_reactive), len(angles)
+        if items % nm or any(a.shape != (items, 3) for a in arrs) or conf_idx.shape != (items,):
+            raise ValueError("every per-group input must have n_groups * n_mols rows")
+        G = items // nm
+        ok, kept = np.zeros(G * A, dtype=np.uint8), np.zeros(G * A, dtype=np.uint8)
+        n_pass, n_kept = C.c_int64(), C.c_int64()
+        check(self.e.lib.tsc_embed_prune_add_groups(self._r, *[ptr(a) for a in arrs], ptr(n_reactive), ptr(conf_idx), ptr(angles), C.c_int64(G), C.c_int(A),
+                                                    C.c_double(float(clash_thresh)), C.c_int64(int(max_clashes)), C.c_double(float(rmsd_thr)), ptr(ok),
+                                                    ptr(kept), C.byref(n_pass), C.byref(n_kept)))
+        return ok.astype(bool), kept.astype(bool)
+
+    def count(self) -> int:
+        n = C.c_int64()
+        check(self.e.lib.tsc_embed_prune_count(self._r, C.byref(n)))
+        return n.value
+
+    def run(self, rmsd_thr=0.5, mode=0):
+        """prune_conformers_rmsd over the kept poses: (survived bool[n_kept], per-pass statistics)."""
+        survived = np.zeros(max(self.count(), 1), dtype=np.uint8)
+        stats = (PassStats * TSC_MAX_PASSES)()
+        np_, ns = C.c_int(), C.c_int64()
+        check(self.e.lib.tsc_embed_prune_run(self._r, C.c_double(float(rmsd_thr)), C.c_int(int(mode)), ptr(survived), stats, C.byref(np_), C.byref(ns)))
+        self.n_survived = ns.value
+        return survived[:self.count()].astype(bool), _stats_list(stats, np_.value)
+
+    def poses(self, which=0):
+        """which = 0: the poses that survived ``run``; 1: every kept pose.  f64[rows, n_total, 3], embedded from their parameters on the device."""
+        rows = self.count() if which else self.n_survived
+        if rows is None:
+            rows = 0                         # (which = 0 before run(): the library refuses it, with its message)
+        out = np.empty((max(rows, 1), self.frags.n_total, 3))
+        if rows or not which:
+            check(self.e.lib.tsc_embed_prune_poses(self._r, C.c_int(int(which)), ptr(out), C.c_int64(rows)))
+        return out[:rows]
+
+    def close(self):
+        if getattr(self, "_r", None):
+            if getattr(self.e, "_h", None):
+                self.e.lib.tsc_embed_prune_destroy(self._r)
+            self._r = None
 
     def __del__(self):
         try:
