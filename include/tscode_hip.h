@@ -244,6 +244,10 @@ int tsc_rmsd_pairs_dev(tsc_ctx *ctx, const double *heavy, int64_t n_structs, int
  * holds them against for a squared-distance limit `limit` = h thr^2 (as a float's bit pattern; INT32_MAX - 1: nothing is dropped).
  *   D f32[n, 16] host (component 2 k + fam, as the library stores descriptors); S f32[2, 64, n] host. */
 int tsc_screen_mm_values(tsc_ctx *ctx, const float *D, int64_t n, double limit, float *S, int32_t *limit_bits, float *out_scale);
+/* The same screen's VERDICTS in the form the pair kernels compute them: the accumulator of every product starts at minus the limit and a
+ * pair is kept where both families' results come out negative (their sign bits), so the limit is one of the summed terms and the rounding
+ * is not that of comparing S with the limit afterwards.  Same inputs, records and operand loads; keep u8[64, n] host: 1 = kept. */
+int tsc_screen_mm_keeps(tsc_ctx *ctx, const float *D, int64_t n, double limit, uint8_t *keep, int32_t *limit_bits, float *out_scale);
 
 /* Torsion-fingerprint pruning (tscode/numba_functions.py:142-264).
  * tsc_torsion_fingerprints: _get_tf_mat -- out f32[n_structs, n_quads] of dihedral angles in degrees (tscode/algebra.py:24-55)

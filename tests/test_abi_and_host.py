@@ -26,6 +26,7 @@ def test_library_exports_every_header_symbol():
     lib = _lib.load()
     syms = _header_symbols()
     assert len(syms) >= 30
+    assert {"tsc_screen_mm_values", "tsc_screen_mm_keeps"} <= set(syms), "the test entry points of the matrix-core screen (csrc/mm.hpp)"
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/tscode_hip.h but not exported"
     assert sorted(_lib.EXPORTED_SYMBOLS) == syms, "ctypes prototype table and header disagree"

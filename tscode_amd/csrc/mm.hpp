@@ -20,8 +20,13 @@
 // Error bound of level 1 (screen_limit_mm_bits; scaled units, M' = sigma * max |component| < 64):
 //   * products of two float16 are exact in the fp32 accumulator; the accumulation of the 30-term form was measured on MI355X at
 //     2^-22.8 * sum |terms| worst over 10^6 sums with the cancellation of this very use (tools/probe/mfma_probe.hip); the bound takes
-//     2^-20 * sum |terms|, sum |terms| <= 2 (|x|^2 + |y|^2) <= 4 KD M'^2 (tests/test_gpu_parity.py::test_matrix_core_screen_values_and_limit
-//     holds every value of this form against it);
+//     2^-20 * sum |terms|, sum |terms| <= 2 (|x|^2 + |y|^2) <= 4 KD M'^2.  What the figure assumes: every partial sum of the MFMA is
+//     rounded to nearest (whatever the order of the terms), and in the kernels the limit is itself one of the terms -- the accumulator
+//     starts at minus the limit --, which E0 and the factor (1 + 2^-20) / (1 - 2^-20) of screen_limit_mm allow for.  Held against
+//     float64 by tests/test_gpu_parity.py::test_matrix_core_screen_values_and_limit (every value of random sets, zero accumulator) and by
+//     tests/test_screen_limit.py: pairs placed within 2^-11 .. 2^-20 of the limit, operands at float16 rounding midpoints that round
+//     apart, norms on both sides of the flush -- by value and in the kernels' own form of the compare (k_mm_screen_keeps) --, and through
+//     every route of the prune on ensembles for which h rmsd^2 equals the family-0 descriptor distance;
 //   * the norms' residuals 2^-14 each;
 //   * x against the exact scaled component: the fp32 rounding of sieve.hpp (3 * 2^-24 * 2 M' per difference) plus the float16 rounding,
 //     2^-11 M' (+ 2^-25 below the normal range) per operand: sqrt(S_exact) >= sqrt(S) - sqrt(KD) * eta.
@@ -132,6 +137,30 @@ inline __global__ __launch_bounds__(64) void k_mm_screen_dump(const _Float16 *__
             for (int i = 0; i < 4; ++i)
                 if (c0 + rc < n_cols) S[(size_t(fam) * MM_ROWS + 16 * rt + 4 * g + i) * n_cols + c0 + rc] = acc[i];
         }
+    }
+}
+
+// The screen's verdicts themselves, for tests, in the form the pair kernels compute them: the operands of mm_load_A / mm_load_B2, every
+// accumulator started at minus the limit, keep[r][c] = 1 where the sign bits of both families' results are set (rows [0, 64) against
+// columns [0, n_cols); one wavefront per 16 columns).  With the limit among the summed terms the rounding is not that of k_mm_screen_dump's
+// `S <= limit` on the host.
+inline __global__ __launch_bounds__(64) void k_mm_screen_keeps(const _Float16 *__restrict__ recs, int n_cols, const unsigned *__restrict__ dmax_bits, double limit,
+                                                         unsigned char *__restrict__ keep, int *__restrict__ limit_bits) {
+    const int lane = threadIdx.x, g = lane >> 4, rc = lane & 15, c0 = blockIdx.x * MM_STEP;
+    const float limit_mm = screen_limit_mm(*dmax_bits, limit);
+    if (blockIdx.x == 0 && lane == 0) *limit_bits = __float_as_int(limit_mm);
+    f16x4 B[NFAM];
+    mm_load_B2(recs + int64_t(min(c0 + rc, n_cols - 1)) * MM_REC_HALVES, g, B);
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) {
+        const int row = min(16 * rt + rc, n_cols - 1);
+        const f16x4 a0 = mm_load_A(recs + int64_t(row) * MM_REC_HALVES, 0, g), a1 = mm_load_A(recs + int64_t(row) * MM_REC_HALVES, 1, g);
+        const f32x4 z = {-limit_mm, -limit_mm, -limit_mm, -limit_mm};
+        const f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x16f16(a0, B[0], z, 0, 0, 0);
+        const f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x16f16(a1, B[1], z, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (c0 + rc < n_cols) keep[size_t(16 * rt + 4 * g + i) * n_cols + c0 + rc] = (unsigned char)((__float_as_uint(s0[i]) & __float_as_uint(s1[i])) >> 31);
     }
 }
 

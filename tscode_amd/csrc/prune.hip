@@ -39,10 +39,10 @@ extern "C" __attribute__((visibility("default"))) int tsc_rmsd_pairs(tsc_ctx *c,
     TSC_API_GUARD_END
 }
 
-extern "C" __attribute__((visibility("default"))) int tsc_screen_mm_values(tsc_ctx *c, const float *D, int64_t n, double limit, float *S, int32_t *limit_bits,
-                                                                           float *out_scale) {
-    TSC_API_GUARD_BEGIN
-    TSC_REQUIRE(c && D && S && limit_bits && out_scale, "tsc_screen_mm_values: null argument");
+// The two test entry points of the matrix-core screen share everything but the dump kernel: the run's largest |component| from the host's
+// descriptors, their records through k_mm_records, then S f32[2, 64, n] (k_mm_screen_dump) or keep u8[64, n] (k_mm_screen_keeps).
+static int screen_mm_dump(tsc_ctx *c, const char *who, const float *D, int64_t n, double limit, float *S, uint8_t *keep, int32_t *limit_bits, float *out_scale) {
+    TSC_REQUIRE(c && D && (S || keep) && limit_bits && out_scale, "%s: null argument", who);
     TSC_REQUIRE(n >= 1 && n <= (1 << 20), "n = %lld not supported", (long long)n);
     float dmax = 0.0f;
     for (int64_t e = 0; e < n * DW; ++e) dmax = std::fabs(D[e]) > dmax || std::isnan(D[e]) ? (std::isnan(D[e]) ? NAN : std::fabs(D[e])) : dmax;
@@ -51,6 +51,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_screen_mm_values(tsc_c
     if (std::isnan(dmax)) bits = NONFINITE_BITS;
     HostCall call(c);
     float *d_D, *d_S;
+    uint8_t *d_keep;
     unsigned *d_bits;
     int32_t *d_lim;
     _Float16 *d_rec;
@@ -58,14 +59,31 @@ extern "C" __attribute__((visibility("default"))) int tsc_screen_mm_values(tsc_c
     TSC_TRY(call.in(&bits, 1, &d_bits));
     TSC_TRY(call.scratch().get(size_t(n) * MM_REC_HALVES, &d_rec));
     TSC_TRY(call.out(S, size_t(NFAM) * MM_ROWS * n, &d_S));
+    TSC_TRY(call.out(keep, size_t(MM_ROWS) * n, &d_keep));
     TSC_TRY(call.out(limit_bits, 1, &d_lim));
     hipLaunchKernelGGL(k_mm_records, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const float *)d_D, n, (const unsigned *)d_bits, d_rec);
-    hipLaunchKernelGGL(k_mm_screen_dump, dim3(unsigned(ceil_div<int64_t>(n, MM_STEP))), dim3(64), 0, c->stream, (const _Float16 *)d_rec, int(n), (const unsigned *)d_bits,
-                       limit, d_S, d_lim);
+    const dim3 grid(unsigned(ceil_div<int64_t>(n, MM_STEP)));
+    if (S) hipLaunchKernelGGL(k_mm_screen_dump, grid, dim3(64), 0, c->stream, (const _Float16 *)d_rec, int(n), (const unsigned *)d_bits, limit, d_S, d_lim);
+    else hipLaunchKernelGGL(k_mm_screen_keeps, grid, dim3(64), 0, c->stream, (const _Float16 *)d_rec, int(n), (const unsigned *)d_bits, limit, d_keep, d_lim);
     TSC_HIP(hipGetLastError());
     TSC_TRY(call.finish());
     *out_scale = mm_scale(bits);
     return 0;
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_screen_mm_values(tsc_ctx *c, const float *D, int64_t n, double limit, float *S, int32_t *limit_bits,
+                                                                           float *out_scale) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(S, "tsc_screen_mm_values: null argument");
+    return screen_mm_dump(c, "tsc_screen_mm_values", D, n, limit, S, nullptr, limit_bits, out_scale);
+    TSC_API_GUARD_END
+}
+
+extern "C" __attribute__((visibility("default"))) int tsc_screen_mm_keeps(tsc_ctx *c, const float *D, int64_t n, double limit, uint8_t *keep, int32_t *limit_bits,
+                                                                          float *out_scale) {
+    TSC_API_GUARD_BEGIN
+    TSC_REQUIRE(keep, "tsc_screen_mm_keeps: null argument");
+    return screen_mm_dump(c, "tsc_screen_mm_keeps", D, n, limit, nullptr, keep, limit_bits, out_scale);
     TSC_API_GUARD_END
 }
 
