@@ -598,6 +598,26 @@ int tsc_prune_rmsd_batch_dev(tsc_ctx *ctx, const double *heavy, const int64_t *o
                              const double *thr_host, int64_t n_segments, int mode, uint8_t *mask, tsc_batch_pass_stats *stats,
                              int32_t *n_passes, uint8_t *nonfinite);
 
+#define TSC_PRUNE_TEAM_MAX_N 200000 /* structures per segment that tsc_prune_rmsd_team takes at most: beyond it the reference itself fails */
+
+/* The same runs of prune_conformers_rmsd (tscode/rmsd_pruning.py:164-206), one per segment, for MID-SIZE ensembles: a team of workgroups per
+ * segment instead of one.  Schedule (:186-192), chunks (:136-144), cache (:183, :65-67, :204), verdicts and the non-finite rule are those
+ * of tsc_prune_rmsd_batch, from the same device functions: masks and statistics are bit for bit the same.  A segment's state lives in
+ * device memory; every schedule slot that some segment can take by its n alone costs two launches for the WHOLE batch (a workgroup per
+ * segment closes the previous pass, decides the gate of :192 from the segment's own count and builds its cache view; then the rows of
+ * all open segments, 16 per work item), so the number of launches depends on the longest segment, never on n_segments, and the host
+ * waits once, at the end.
+ * Arguments and outputs as tsc_prune_rmsd_batch, except that a segment may hold up to TSC_PRUNE_TEAM_MAX_N structures whatever
+ * "prune_batch_max_n" says.  Refused before the device is touched, with the segment's index in the message (TSC_ERR_INVALID): a longer
+ * segment, h < 1, n < 0, offsets that do not match n * h * 3, a threshold that is not finite; and a mode other than 0 or 1.  Segments of
+ * 0 or 1 structures are legal.  The _dev form takes heavy, mask, stats, n_passes and nonfinite on the device and the four tables in host
+ * memory; it synchronises (the tables are uploaded from the call's own memory). */
+int tsc_prune_rmsd_team(tsc_ctx *ctx, const double *heavy, const int64_t *offsets, const int32_t *n, const int32_t *h, const double *thr,
+                        int64_t n_segments, int mode, uint8_t *mask, tsc_batch_pass_stats *stats, int32_t *n_passes, uint8_t *nonfinite);
+int tsc_prune_rmsd_team_dev(tsc_ctx *ctx, const double *heavy, const int64_t *offsets_host, const int32_t *n_host, const int32_t *h_host,
+                            const double *thr_host, int64_t n_segments, int mode, uint8_t *mask, tsc_batch_pass_stats *stats,
+                            int32_t *n_passes, uint8_t *nonfinite);
+
 /* Stepping form of the same run, for one-process-per-GPU sharding of a pass (rows of a pass are
  * independent: tscode/rmsd_pruning.py:92,101-113).  Every rank holds the full `heavy` array and calls
  *   tsc_prune_create; loop { k = tsc_prune_next_pass; if k == 0 break;

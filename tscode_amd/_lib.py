@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSCODE_AMD_LIB") or os.path.join(_HERE, "libtscode_hip.so")   # override: A/B builds
 
 TSC_MAX_PASSES = 18
+TSC_PRUNE_TEAM_MAX_N = 200000      # structures per segment that tsc_prune_rmsd_team takes at most
 
 c_f64p = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -141,6 +142,8 @@ _SIGNATURES = {
     "tsc_embed_prune_destroy": (C.c_int, [_vp]),
     "tsc_prune_rmsd_batch": (C.c_int, [_vp, _vp, c_i64p, c_i32p, c_i32p, c_f64p, C.c_int64, C.c_int, _vp, C.POINTER(BatchPassStats), c_i32p, c_u8p]),
     "tsc_prune_rmsd_batch_dev": (C.c_int, [_vp, _vp, c_i64p, c_i32p, c_i32p, c_f64p, C.c_int64, C.c_int, _vp, C.POINTER(BatchPassStats), _vp, _vp]),
+    "tsc_prune_rmsd_team": (C.c_int, [_vp, _vp, c_i64p, c_i32p, c_i32p, c_f64p, C.c_int64, C.c_int, _vp, C.POINTER(BatchPassStats), c_i32p, c_u8p]),
+    "tsc_prune_rmsd_team_dev": (C.c_int, [_vp, _vp, c_i64p, c_i32p, c_i32p, c_f64p, C.c_int64, C.c_int, _vp, C.POINTER(BatchPassStats), _vp, _vp]),
     "tsc_prune_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_double, C.c_int, C.POINTER(_vp)]),
     "tsc_prune_next_pass": (C.c_int, [_vp, c_i64p]),
     "tsc_prune_pass_estimate": (C.c_int, [_vp, c_i64p]),

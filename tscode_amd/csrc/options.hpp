@@ -50,7 +50,9 @@ struct tsc_options {
     int cull_xcd = 1;                     // 1 (default): the culled pair kernel keys runs of 32 row groups to XCDs (workgroup b runs on XCD b % 8): the workgroups an
                                           // XCD has in flight share their column windows in its L2 (cull.hpp; an experiment of round 5)
     int prune_batch_max_n = 2048;         // tsc_prune_rmsd_batch: structures per segment at most (prune_batch.hpp: one workgroup owns a segment); provisional,
-                                          // LP_MAX_ROWS -- the size up to which one workgroup already owns a chunk -- until the crossover is measured
+                                          // LP_MAX_ROWS -- the size up to which one workgroup already owns a chunk -- until the crossover is measured.
+                                          // A longer segment is refused there: it belongs to tsc_prune_rmsd_team (prune_team.hpp: a team of workgroups per
+                                          // segment, up to TSC_PRUNE_TEAM_MAX_N structures, no option) or to tsc_prune_rmsd on its own; the Python layer routes
     int pass_timing = 0;                  // HIP events per pass: 0 none, 1 on the pair kernel's dispatch, 2 also around the whole pass
 #ifdef TSC_DBG_STAMPS
     int64_t dbg_stamp_k = -1;             // -DTSC_DBG_STAMPS builds: the pass (by its k; -k: its k_open_rows) whose wavefronts leave time stamps

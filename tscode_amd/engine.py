@@ -66,6 +66,24 @@ def _stats_list(stats, n):
 
 _BATCH_STAT_FIELDS = tuple(f for f, _ in BatchPassStats._fields_)
 
+# Structures per ensemble up to which prune_heavy_batch sends an ensemble longer than "prune_batch_max_n" to tsc_prune_rmsd_team
+# instead of a call of its own: the largest size measured at which a call on 16 ensembles was not slower with the team route than
+# without (MEASURED.md section 30: 4096 -- level through the host-array call, where gather, packing and upload are nine tenths of the
+# time, 2.3 times faster on resident data; at 8192 the route loses on both counts).
+PRUNE_TEAM_MAX_N = 4096
+
+
+def check_team_max_n(team_max_n):
+    """The ``team_max_n`` keyword of the batched RMSD prune as a whole number 0 .. TSC_PRUNE_TEAM_MAX_N (None: PRUNE_TEAM_MAX_N).
+    No device is touched."""
+    if team_max_n is None:
+        return PRUNE_TEAM_MAX_N
+    if isinstance(team_max_n, (bool, np.bool_)) or not isinstance(team_max_n, (int, np.integer)):
+        raise ValueError(f"team_max_n must be a whole number or None, got {team_max_n!r}")
+    if not 0 <= team_max_n <= _lib.TSC_PRUNE_TEAM_MAX_N:
+        raise ValueError(f"team_max_n = {team_max_n} not in 0 .. {_lib.TSC_PRUNE_TEAM_MAX_N}")
+    return int(team_max_n)
+
 
 def pack_heavy_batch(heavies):
     """The arrays tsc_prune_rmsd_batch takes for a sequence of heavy-atom arrays f64[N_s, h_s, 3]: (flat, offsets, n, h) -- the arrays
@@ -890,39 +908,54 @@ class Engine:
                                       stats, C.byref(np_)))
         return mask.astype(bool), _stats_list(stats, np_.value)
 
-    def prune_heavy_batch(self, heavies, rmsd_thr=0.5, mode=0):
-        """prune_conformers_rmsd on many heavy-atom arrays f64[N_s, h_s, 3] (rmsd_thr a scalar or one per ensemble).  Ensembles of at
-        most "prune_batch_max_n" structures go through tsc_prune_rmsd_batch in ONE launch, a workgroup each; a longer one takes
-        prune_heavy on its own, which spreads a pass over the device.  Returns (masks, stats, nonfinite): per ensemble the mask bool[N_s],
-        the list of its passes (k, n_active_before, n_active_after, pairs_evaluated, new_keys) and whether it holds a NaN or infinite
-        coordinate (bool[S])."""
+    def _prune_segments(self, entry, heavies, thr, mode):
+        """One call of tsc_prune_rmsd_batch or tsc_prune_rmsd_team (`entry`) on heavy-atom arrays already checked: (masks, stats,
+        nonfinite) per ensemble."""
+        packed = segments.pack(heavies)
+        B = len(heavies)
+        mask = np.zeros(int(packed.row_off[-1]), dtype=np.uint8)
+        st = (BatchPassStats * (B * TSC_MAX_PASSES))()
+        np_ = np.zeros(B, dtype=np.int32)
+        nf = np.zeros(B, dtype=np.uint8)
+        t = np.ascontiguousarray(thr, dtype=np.float64)
+        check(entry(self._h, ptr(packed.flat), packed.offsets.ctypes.data_as(_lib.c_i64p), packed.n_structs.ctypes.data_as(_lib.c_i32p),
+                    packed.n_atoms.ctypes.data_as(_lib.c_i32p), t.ctypes.data_as(_lib.c_f64p), C.c_int64(B), C.c_int(int(mode)),
+                    ptr(mask), st, np_.ctypes.data_as(_lib.c_i32p), nf.ctypes.data_as(_lib.c_u8p)))
+        table = np.frombuffer(st, dtype=np.int64).reshape(B, TSC_MAX_PASSES, len(_BATCH_STAT_FIELDS))
+        masks = [m.astype(bool) for m in packed.cut(mask)]
+        stats = [[dict(zip(_BATCH_STAT_FIELDS, map(int, row))) for row in table[b, :np_[b]]] for b in range(B)]
+        return masks, stats, nf.astype(bool)
+
+    @staticmethod
+    def _checked_heavies(heavies, rmsd_thr):
         heavies = [np.ascontiguousarray(a, dtype=np.float64) for a in heavies]
-        S = len(heavies)
-        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(rmsd_thr, dtype=np.float64), (S,)))
-        masks, stats, nonfinite = [None] * S, [None] * S, np.zeros(S, dtype=bool)
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(rmsd_thr, dtype=np.float64), (len(heavies),)))
         for s, a in enumerate(heavies):
             if a.ndim != 3 or a.shape[2] != 3:
                 raise ValueError(f"ensemble {s}: heavy must be (N, h, 3), got {a.shape}")
             if a.shape[1] < 1:
                 raise ValueError(f"ensemble {s}: no heavy atoms")
+        return heavies, thr
+
+    def prune_heavy_batch(self, heavies, rmsd_thr=0.5, mode=0, team_max_n=None):
+        """prune_conformers_rmsd on many heavy-atom arrays f64[N_s, h_s, 3] (rmsd_thr a scalar or one per ensemble).  Three routes by
+        size: ensembles of at most "prune_batch_max_n" structures go through tsc_prune_rmsd_batch in ONE launch, a workgroup each; the
+        longer ones of at most ``team_max_n`` (None: PRUNE_TEAM_MAX_N; 0: nobody) through tsc_prune_rmsd_team in ONE call, a team of
+        workgroups each; a still longer one takes prune_heavy on its own, which spreads a pass over the device.  Returns (masks, stats,
+        nonfinite): per ensemble the mask bool[N_s], the list of its passes (k, n_active_before, n_active_after, pairs_evaluated,
+        new_keys) and whether it holds a NaN or infinite coordinate (bool[S])."""
+        team_max_n = check_team_max_n(team_max_n)
+        heavies, thr = self._checked_heavies(heavies, rmsd_thr)
+        S = len(heavies)
+        masks, stats, nonfinite = [None] * S, [None] * S, np.zeros(S, dtype=bool)
         max_n = self.prune_batch_max_n
         small = [s for s in range(S) if heavies[s].shape[0] <= max_n]
-        if small:
-            packed = segments.pack([heavies[s] for s in small])
-            B = len(small)
-            mask = np.zeros(int(packed.row_off[-1]), dtype=np.uint8)
-            st = (BatchPassStats * (B * TSC_MAX_PASSES))()
-            np_ = np.zeros(B, dtype=np.int32)
-            nf = np.zeros(B, dtype=np.uint8)
-            t = np.ascontiguousarray(thr[small])
-            check(self.lib.tsc_prune_rmsd_batch(self._h, ptr(packed.flat), packed.offsets.ctypes.data_as(_lib.c_i64p), packed.n_structs.ctypes.data_as(_lib.c_i32p),
-                                                packed.n_atoms.ctypes.data_as(_lib.c_i32p), t.ctypes.data_as(_lib.c_f64p), C.c_int64(B), C.c_int(int(mode)),
-                                                ptr(mask), st, np_.ctypes.data_as(_lib.c_i32p), nf.ctypes.data_as(_lib.c_u8p)))
-            table = np.frombuffer(st, dtype=np.int64).reshape(B, TSC_MAX_PASSES, len(_BATCH_STAT_FIELDS))
-            for b, (s, m) in enumerate(zip(small, packed.cut(mask))):
-                masks[s] = m.astype(bool)
-                stats[s] = [dict(zip(_BATCH_STAT_FIELDS, map(int, row))) for row in table[b, :np_[b]]]
-                nonfinite[s] = bool(nf[b])
+        mid = [s for s in range(S) if max_n < heavies[s].shape[0] <= team_max_n]
+        for entry, which in ((self.lib.tsc_prune_rmsd_batch, small), (self.lib.tsc_prune_rmsd_team, mid)):
+            if which:
+                m, st, nf = self._prune_segments(entry, [heavies[s] for s in which], thr[which], mode)
+                for b, s in enumerate(which):
+                    masks[s], stats[s], nonfinite[s] = m[b], st[b], nf[b]
         for s in range(S):
             if masks[s] is None:
                 masks[s], full = self.prune_heavy(heavies[s], float(thr[s]), mode)
@@ -930,18 +963,33 @@ class Engine:
                 nonfinite[s] = bool(full and full[0].get("nonfinite_input"))
         return masks, stats, nonfinite
 
-    def prune_heavy_batch_dev(self, heavy, offsets, n, h, rmsd_thr, mode, mask, stats=None, n_passes=None, nonfinite=None):
-        """tsc_prune_rmsd_batch_dev: heavy f64 and the outputs mask u8[sum n], stats (i64[S, TSC_MAX_PASSES, 5]), n_passes i32[S] and
-        nonfinite u8[S] on the device (torch tensors or raw pointers; the last three optional), the tables offsets / n / h / rmsd_thr
-        NumPy arrays (pack_heavy_batch).  Every ensemble must have at most "prune_batch_max_n" structures.  Synchronises."""
+    def prune_heavy_team(self, heavies, rmsd_thr=0.5, mode=0):
+        """prune_conformers_rmsd on many heavy-atom arrays f64[N_s, h_s, 3] through tsc_prune_rmsd_team alone, whatever their sizes up to
+        TSC_PRUNE_TEAM_MAX_N: one call, a team of workgroups per ensemble.  Returns (masks, stats, nonfinite) as prune_heavy_batch."""
+        heavies, thr = self._checked_heavies(heavies, rmsd_thr)
+        if not heavies:
+            return [], [], np.zeros(0, dtype=bool)
+        return self._prune_segments(self.lib.tsc_prune_rmsd_team, heavies, thr, mode)
+
+    def _prune_segments_dev(self, entry, heavy, offsets, n, h, rmsd_thr, mode, mask, stats, n_passes, nonfinite):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = np.ascontiguousarray(n, dtype=np.int32)
         h = np.ascontiguousarray(h, dtype=np.int32)
         thr = np.ascontiguousarray(np.broadcast_to(np.asarray(rmsd_thr, dtype=np.float64), n.shape))
         st = C.cast(ptr(stats), C.POINTER(BatchPassStats)) if stats is not None else None
-        check(self.lib.tsc_prune_rmsd_batch_dev(self._h, ptr(heavy), offsets.ctypes.data_as(_lib.c_i64p), n.ctypes.data_as(_lib.c_i32p),
-                                                h.ctypes.data_as(_lib.c_i32p), thr.ctypes.data_as(_lib.c_f64p), C.c_int64(len(n)), C.c_int(int(mode)),
-                                                ptr(mask), st, ptr(n_passes), ptr(nonfinite)))
+        check(entry(self._h, ptr(heavy), offsets.ctypes.data_as(_lib.c_i64p), n.ctypes.data_as(_lib.c_i32p), h.ctypes.data_as(_lib.c_i32p),
+                    thr.ctypes.data_as(_lib.c_f64p), C.c_int64(len(n)), C.c_int(int(mode)), ptr(mask), st, ptr(n_passes), ptr(nonfinite)))
+
+    def prune_heavy_batch_dev(self, heavy, offsets, n, h, rmsd_thr, mode, mask, stats=None, n_passes=None, nonfinite=None):
+        """tsc_prune_rmsd_batch_dev: heavy f64 and the outputs mask u8[sum n], stats (i64[S, TSC_MAX_PASSES, 5]), n_passes i32[S] and
+        nonfinite u8[S] on the device (torch tensors or raw pointers; the last three optional), the tables offsets / n / h / rmsd_thr
+        NumPy arrays (pack_heavy_batch).  Every ensemble must have at most "prune_batch_max_n" structures.  Synchronises."""
+        self._prune_segments_dev(self.lib.tsc_prune_rmsd_batch_dev, heavy, offsets, n, h, rmsd_thr, mode, mask, stats, n_passes, nonfinite)
+
+    def prune_heavy_team_dev(self, heavy, offsets, n, h, rmsd_thr, mode, mask, stats=None, n_passes=None, nonfinite=None):
+        """tsc_prune_rmsd_team_dev: the arguments of prune_heavy_batch_dev; every ensemble must have at most TSC_PRUNE_TEAM_MAX_N
+        structures.  Synchronises."""
+        self._prune_segments_dev(self.lib.tsc_prune_rmsd_team_dev, heavy, offsets, n, h, rmsd_thr, mode, mask, stats, n_passes, nonfinite)
 
     def prune_structures(self, structures, heavy_idx, rmsd_thr=0.5, mode=0):
         """The same from all-atom structures f64[N, n_atoms, 3] (C-contiguous) and the indices of the heavy atoms: the gather of

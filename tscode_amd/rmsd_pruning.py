@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .engine import get_engine, pack_heavy_batch  # noqa: F401  (pack_heavy_batch: the arrays tsc_prune_rmsd_batch takes)
+from .engine import check_team_max_n, get_engine, pack_heavy_batch  # noqa: F401  (pack_heavy_batch: the arrays tsc_prune_rmsd_batch takes)
 from .segments import one_or_each, scalar_or_each
 
 __all__ = ["prune_conformers_rmsd", "prune_conformers_rmsd_batch", "rmsd_and_max_numba", "_rmsd_similarity", "last_prune_stats",
@@ -77,19 +77,23 @@ def _check_batch(ensembles, atomnos, rmsd_thr):
     return ensembles, heavy_idx, thr
 
 
-def prune_conformers_rmsd_batch(ensembles, atomnos, rmsd_thr=0.5, mode=0):
-    """tscode/rmsd_pruning.py:164-206 on many ensembles at once: [prune_conformers_rmsd(e, a, thr, mode) for every ensemble], in one
-    launch for the ensembles of at most "prune_batch_max_n" structures (Engine.prune_heavy_batch).
+def prune_conformers_rmsd_batch(ensembles, atomnos, rmsd_thr=0.5, mode=0, team_max_n=None):
+    """tscode/rmsd_pruning.py:164-206 on many ensembles at once: [prune_conformers_rmsd(e, a, thr, mode) for every ensemble], by three
+    routes (Engine.prune_heavy_batch): one launch for the ensembles of at most "prune_batch_max_n" structures, a workgroup each; one
+    call for the longer ones of at most ``team_max_n`` structures, a team of workgroups each; a call of its own for every still
+    longer one.  The results do not depend on the route.
 
     ``ensembles``: a sequence of (N_s, n_s, 3) arrays; ``atomnos``: one array shared by all, or a list with one per ensemble;
-    ``rmsd_thr``: a scalar or one per ensemble.  Returns the list of (structures_s[mask_s], mask_s)."""
+    ``rmsd_thr``: a scalar or one per ensemble; ``team_max_n``: None for engine.PRUNE_TEAM_MAX_N, 0 for no team route, at most
+    TSC_PRUNE_TEAM_MAX_N.  Returns the list of (structures_s[mask_s], mask_s)."""
     global _last_batch_stats
+    team_max_n = check_team_max_n(team_max_n)
     ensembles, heavy_idx, thr = _check_batch(ensembles, atomnos, rmsd_thr)
     if not ensembles:
         _last_batch_stats = []
         return []
     heavies = [np.ascontiguousarray(e[:, idx], dtype=np.float64) for e, idx in zip(ensembles, heavy_idx)]    # :179
-    masks, _last_batch_stats, nonfinite = get_engine().prune_heavy_batch(heavies, thr, int(mode))
+    masks, _last_batch_stats, nonfinite = get_engine().prune_heavy_batch(heavies, thr, int(mode), team_max_n=team_max_n)
     for s, e in enumerate(ensembles):
         if nonfinite[s] and len(e) > 1:
             # (as prune_conformers_rmsd: the reference's np.linalg.svd raises on such a structure, rmsd_pruning.py:19)
