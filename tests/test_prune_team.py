@@ -19,7 +19,7 @@ from conftest import ROOT, load_golden, load_large_prune
 from test_prune_batch import HEAVY, MARGIN, draw_ensemble
 
 STAT_KEYS = ("k", "n_active_before", "n_active_after", "pairs_evaluated", "new_keys")
-ROWS = 16                  # PT_ROWS of csrc/prune_team.hpp: the rows of one work item, four items to a word of the masks
+ROWS = 16                  # PT_ROWS of csrc/prune_batch_plan.hpp: the rows of one work item, four items to a word of the masks
 LISTED = [65, 127, 128, 129, 191, 193, 255, 257, 401, 419, 1003, 2049, 2500, 4099]
 SIZES = LISTED + [4 * ROWS - 1, 4 * ROWS, 32 * ROWS - 1, 32 * ROWS, 32 * ROWS + 1, ROWS - 1, ROWS, ROWS + 1]       # (4 * ROWS + 1 = 65 is listed)
 GATES = ((2711, 2100, 9, 5), (2712, 4100, 4, 7), (2713, 1100, 18, 3))         # (seed, n, h, parents)
@@ -97,8 +97,8 @@ def test_header_and_library_export_the_team_entry_points():
     header = open(os.path.join(ROOT, "include", "tscode_hip.h")).read()
     cap = int(re.search(r"#define TSC_PRUNE_TEAM_MAX_N (\d+)", header).group(1))
     assert 65536 <= cap <= 200000 and cap == _lib.TSC_PRUNE_TEAM_MAX_N
-    assert "prune_team.hip" in build.SOURCES and "prune_team.hpp" in build.HEADERS
-    kernels = open(os.path.join(build.CSRC, "prune_team.hpp")).read()
+    assert "prune_batch.hip" in build.SOURCES and "prune_team.hpp" in build.HEADERS and "prune_batch_plan.hpp" in build.HEADERS
+    kernels = open(os.path.join(build.CSRC, "prune_batch_plan.hpp")).read()     # (the item table is made there)
     assert int(re.search(r"constexpr int PT_ROWS = (\d+);", kernels).group(1)) == ROWS, "the edge sizes of this file follow the work item's rows"
     build.build()
     lib = _lib.load()

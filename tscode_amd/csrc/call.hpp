@@ -1,5 +1,5 @@
 // call.hpp -- what the entry points that take host arrays and hand host arrays back share (topology, nci, orbitals, diverse,
-// rot_corr, adjacent, prune_batch, prune_team): the device side of one such call (HostCall), the event timer of the profiling option (StageTimer), the
+// rot_corr, adjacent, prune_batch): the device side of one such call (HostCall), the event timer of the profiling option (StageTimer), the
 // dispatch on a kernel's word count (with_words) and the two argument checks that topology and nci have in common.
 #pragma once
 

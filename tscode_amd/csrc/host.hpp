@@ -1,5 +1,5 @@
 // host.hpp -- host-side helpers shared by the translation units of libtscode_hip (one .hip per kernel family: ctx, embed, prune,
-// prune_batch, prune_team, pairs_*, adjacent, pipeline, xchg, rot_corr, diverse, topology, nci, orbitals; what only the entry points on host arrays need
+// prune_batch, pairs_*, adjacent, pipeline, xchg, rot_corr, diverse, topology, nci, orbitals; what only the entry points on host arrays need
 // is in call.hpp).  Functions declared here without a body are defined in exactly one of them; the library is built with
 // -fvisibility=hidden, so none of this is exported.
 #pragma once

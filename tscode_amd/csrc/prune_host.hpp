@@ -3,6 +3,7 @@
 #pragma once
 
 #include "pass_plan.hpp"
+#include "prune_schedule.hpp"
 #include "scan.hpp"
 
 // --------------------------------------------------------------------------------------------------
@@ -13,16 +14,11 @@
 // enqueued with grids sized for N structures; kernels of a pass that is gated off, and blocks beyond the number
 // of still-active structures, return at once.  The host reads the per-pass records once, at the end.
 
-static const double KS[TSC_MAX_PASSES] = {5e5, 2e5, 1e5, 5e4, 2e4, 1e4, 5000, 2000, 1000, 500, 200, 100, 50, 20, 10, 5, 2, 1};  // :186-188
-
 static_assert(MAX_SLOTS == TSC_MAX_PASSES, "one cache view per schedule slot");
 
-// Can the pass of schedule slot `slot` ever run on n structures?  count_nonzero(mask) <= n, so a pass with 20 k >= n can never pass the
-// gate of :192; the others are enqueued and gated on the device.
-static inline bool pass_can_run(int64_t n, int slot) {
-    const int64_t k = int64_t(KS[slot]);  // int(k): the reference itself fails for float k
-    return k == 1 || 20 * k < n;
-}
+// Can the pass of schedule slot `slot` (KS, prune_schedule.hpp) ever run on n structures?  count_nonzero(mask) <= n, so a pass with
+// 20 k >= n can never pass the gate of :192; the others are enqueued and gated on the device.
+static inline bool pass_can_run(int64_t n, int slot) { return pass_gate(KS[slot], n); }
 
 struct tsc_prune {
     tsc_ctx *ctx = nullptr;
