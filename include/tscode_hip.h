@@ -238,6 +238,38 @@ int tsc_rmsd_pairs(tsc_ctx *ctx, const double *heavy, int64_t n_structs, int h, 
 int tsc_rmsd_pairs_dev(tsc_ctx *ctx, const double *heavy, int64_t n_structs, int h, const int32_t *pairs, int64_t n_pairs,
                        double *rmsd, double *maxdev);
 
+/* ---- Cross-set RMSD: queries against a library (csrc/cross.hpp) ---------------------------------
+ * Every pair (query q, library l) is rmsd_and_max_numba(queries[q], library[l]) (tscode/rmsd_pruning.py:6-41): the optimal proper rotation
+ * of the query onto the library structure, no centring, rmsd = sqrt(sum |Rp - q|^2 / h), maxdev = max_a |Rp_a - q_a|.
+ *   queries f64[n_queries, n_atoms, 3]; library f64[n_library, n_atoms, 3], or NULL: the queries themselves (n_library == n_queries);
+ *   idx i32[n_idx]: the atoms compared (:178-179 compares those with atomnos != 1), or NULL with n_idx = 0: all atoms (as :208-224);
+ *   center != 0: every structure, queries and library alike, has the mean of its compared atoms subtracted first (not in the reference:
+ *   its metric counts translation as deviation).  Up to 2^31 - 1 structures per side.
+ * The forms on host arrays check idx, upload and return when the outputs are in the caller's arrays.  The _dev forms take device pointers
+ * for every array (idx included: an index outside 0 .. n_atoms - 1 reads as the origin), upload nothing, enqueue on the context's stream and
+ * return without waiting for it; coordinates that are not finite are the caller's business there (such a pair has no defined value, is
+ * similar to nothing and nearest to nothing).
+ * tsc_rmsd_cross: rmsd, maxdev f64[n_queries, n_library], contiguous along the library.  capacity: the doubles each output array has room
+ *   for; a request beyond it is refused (TSC_ERR_INVALID) -- walking a large matrix in row blocks is the caller's job, and
+ *   tsc_rmsd_cross_rows says how many query rows a call may take so that the two outputs stay within max_bytes (at least 1).
+ * tsc_rmsd_cross_first: first i32[n_queries] = the lowest l with rmsd < thr and maxdev < 2 thr (:75, :208-224: _rmsd_similarity(query,
+ *   library, thr) is first != INT32_MAX), or INT32_MAX.
+ * tsc_rmsd_cross_nearest: index i32[n_queries] = the l of the smallest rmsd (ties: the lowest l), rmsd / maxdev f64[n_queries] its values
+ *   (:6-41); n_library >= 1.  Two calls on the same input return the same bits. */
+int tsc_rmsd_cross_rows(int64_t n_library, int64_t max_bytes, int64_t *rows);
+int tsc_rmsd_cross(tsc_ctx *ctx, const double *queries, int64_t n_queries, const double *library, int64_t n_library, int n_atoms,
+                   const int32_t *idx, int n_idx, int center, double *rmsd, double *maxdev, int64_t capacity);
+int tsc_rmsd_cross_dev(tsc_ctx *ctx, const double *queries, int64_t n_queries, const double *library, int64_t n_library, int n_atoms,
+                       const int32_t *idx, int n_idx, int center, double *rmsd, double *maxdev, int64_t capacity);
+int tsc_rmsd_cross_first(tsc_ctx *ctx, const double *queries, int64_t n_queries, const double *library, int64_t n_library, int n_atoms,
+                         const int32_t *idx, int n_idx, int center, double thr, int32_t *first);
+int tsc_rmsd_cross_first_dev(tsc_ctx *ctx, const double *queries, int64_t n_queries, const double *library, int64_t n_library, int n_atoms,
+                             const int32_t *idx, int n_idx, int center, double thr, int32_t *first);
+int tsc_rmsd_cross_nearest(tsc_ctx *ctx, const double *queries, int64_t n_queries, const double *library, int64_t n_library, int n_atoms,
+                           const int32_t *idx, int n_idx, int center, int32_t *index, double *rmsd, double *maxdev);
+int tsc_rmsd_cross_nearest_dev(tsc_ctx *ctx, const double *queries, int64_t n_queries, const double *library, int64_t n_library, int n_atoms,
+                               const int32_t *idx, int n_idx, int center, int32_t *index, double *rmsd, double *maxdev);
+
 /* The descriptor screen of the prune's pair kernel as the matrix cores compute it (csrc/mm.hpp), for tests: the screen values
  * S[fam][r][c] (two feature families, rows r < 64, columns c < n) of the first 64 of n descriptors against all n, in the units the
  * kernel compares them in -- out_scale^2 times |D_fam[r] - D_fam[c]|^2 up to the error bound of mm.hpp -- and the limit the kernel

@@ -92,6 +92,13 @@ _SIGNATURES = {
     "tsc_screen_mm_values": (C.c_int, [_vp, _vp, C.c_int64, C.c_double, _vp, _vp, _vp]),
     "tsc_screen_mm_keeps": (C.c_int, [_vp, _vp, C.c_int64, C.c_double, _vp, _vp, _vp]),
     "tsc_rmsd_pairs_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, _vp, _vp]),
+    "tsc_rmsd_cross_rows": (C.c_int, [C.c_int64, C.c_int64, c_i64p]),
+    "tsc_rmsd_cross": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int64]),
+    "tsc_rmsd_cross_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int64]),
+    "tsc_rmsd_cross_first": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, C.c_double, _vp]),
+    "tsc_rmsd_cross_first_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, C.c_double, _vp]),
+    "tsc_rmsd_cross_nearest": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "tsc_rmsd_cross_nearest_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "tsc_embed_clash_compact_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, C.c_int, C.c_double, C.c_int64,
                                                _vp, _vp, _vp, _vp]),
     "tsc_basis_from_poses_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, C.c_int]),

@@ -308,6 +308,63 @@ class Engine:
                                       C.c_int64(len(pairs)), ptr(r), ptr(m)))
         return r, m
 
+    # ---- cross-set RMSD (csrc/cross.hpp; argument checks and row blocks: tscode_amd/rmsd_cross.py) ------------------------------
+    @staticmethod
+    def _cross_args(queries, library, idx):
+        """(queries, n_q, library or None, n_l, n_atoms, idx or None, n_idx) as the tsc_rmsd_cross* calls take them; library None: the
+        queries against themselves."""
+        n_l = queries.shape[0] if library is None else library.shape[0]
+        idx = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32)
+        return (ptr(queries), C.c_int64(queries.shape[0]), ptr(library), C.c_int64(n_l), C.c_int(queries.shape[1]), ptr(idx),
+                C.c_int(0 if idx is None else len(idx))), n_l, idx
+
+    def rmsd_cross_rows(self, n_library, max_bytes) -> int:
+        """tsc_rmsd_cross_rows: query rows one rmsd_cross call may take so that its two outputs stay within max_bytes (at least 1)."""
+        rows = C.c_int64()
+        check(self.lib.tsc_rmsd_cross_rows(C.c_int64(n_library), C.c_int64(max_bytes), C.byref(rows)))
+        return rows.value
+
+    def rmsd_cross(self, queries, library=None, idx=None, center=False):
+        """tsc_rmsd_cross: (rmsd, maxdev) f64[Nq, Nl] of queries f64[Nq, n, 3] against library f64[Nl, n, 3] (None: themselves) on the atoms
+        idx (None: all).  Both C-contiguous float64."""
+        args, n_l, _keep = self._cross_args(queries, library, idx)
+        r = np.empty((queries.shape[0], n_l), dtype=np.float64)
+        m = np.empty((queries.shape[0], n_l), dtype=np.float64)
+        check(self.lib.tsc_rmsd_cross(self._h, *args, C.c_int(bool(center)), ptr(r), ptr(m), C.c_int64(r.size)))
+        return r, m
+
+    def rmsd_cross_first(self, queries, library, idx=None, rmsd_thr=0.5, center=False):
+        """tsc_rmsd_cross_first: first i32[Nq], the lowest library index every query is similar to, INT32_MAX where there is none."""
+        args, _n_l, _keep = self._cross_args(queries, library, idx)
+        first = np.empty(queries.shape[0], dtype=np.int32)
+        check(self.lib.tsc_rmsd_cross_first(self._h, *args, C.c_int(bool(center)), C.c_double(rmsd_thr), ptr(first)))
+        return first
+
+    def rmsd_cross_nearest(self, queries, library, idx=None, center=False):
+        """tsc_rmsd_cross_nearest: (index i32[Nq], rmsd f64[Nq], maxdev f64[Nq]) of the nearest library member of every query."""
+        args, _n_l, _keep = self._cross_args(queries, library, idx)
+        n = queries.shape[0]
+        index, r, m = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+        check(self.lib.tsc_rmsd_cross_nearest(self._h, *args, C.c_int(bool(center)), ptr(index), ptr(r), ptr(m)))
+        return index, r, m
+
+    def rmsd_cross_dev(self, queries, n_q, library, n_l, n_atoms, idx, n_idx, center, rmsd, maxdev, capacity):
+        """tsc_rmsd_cross_dev: every array on the device (torch tensors or raw pointers; library None: the queries themselves, idx None
+        with n_idx 0: all atoms); rmsd / maxdev f64 with room for `capacity` values each.  Enqueues and returns; finite input is the
+        caller's business."""
+        check(self.lib.tsc_rmsd_cross_dev(self._h, ptr(queries), C.c_int64(n_q), ptr(library), C.c_int64(n_l), C.c_int(n_atoms), ptr(idx), C.c_int(n_idx),
+                                          C.c_int(bool(center)), ptr(rmsd), ptr(maxdev), C.c_int64(capacity)))
+
+    def rmsd_cross_first_dev(self, queries, n_q, library, n_l, n_atoms, idx, n_idx, center, rmsd_thr, first):
+        """tsc_rmsd_cross_first_dev: as rmsd_cross_dev; first i32[n_q] on the device (INT32_MAX: none).  Enqueues and returns."""
+        check(self.lib.tsc_rmsd_cross_first_dev(self._h, ptr(queries), C.c_int64(n_q), ptr(library), C.c_int64(n_l), C.c_int(n_atoms), ptr(idx), C.c_int(n_idx),
+                                                C.c_int(bool(center)), C.c_double(rmsd_thr), ptr(first)))
+
+    def rmsd_cross_nearest_dev(self, queries, n_q, library, n_l, n_atoms, idx, n_idx, center, index, rmsd, maxdev):
+        """tsc_rmsd_cross_nearest_dev: as rmsd_cross_dev; index i32[n_q], rmsd / maxdev f64[n_q] on the device.  Enqueues and returns."""
+        check(self.lib.tsc_rmsd_cross_nearest_dev(self._h, ptr(queries), C.c_int64(n_q), ptr(library), C.c_int64(n_l), C.c_int(n_atoms), ptr(idx), C.c_int(n_idx),
+                                                  C.c_int(bool(center)), ptr(index), ptr(rmsd), ptr(maxdev)))
+
     def greedy_group_filter(self, poses, group_off, rmsd_thr=1.0):
         """accepted bool[n_poses]: per group, keep a pose iff it is not similar to a pose kept before it."""
         poses = np.ascontiguousarray(poses, dtype=np.float64)
