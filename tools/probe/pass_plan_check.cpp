@@ -40,11 +40,14 @@ static int forms() {
 static int walked() {
     tsc_options c;   // default options
     {   // 57 046 structures in 5 chunks: 57 046 / 5 = 11 409, the last chunk 57 046 - 4 x 11 409 = 11 410; ceil(57 046 / 16) = 3 566 row tiles;
-        // n <= 100 000: 512 columns, and 11 410 >= 4 x 512 keeps them; ceil((11 410 + 64) / 512) = ceil(22.4) = 23 <= 64 segments: two items
-        // per workgroup, 3 566 / 2 = 1 783
+        // the 16-row matrix-core kernel: 11 410 >= 8 192 columns a row: 1 024 columns; ceil((11 410 + 64) / 1 024) = ceil(11.2) = 12 segments;
+        // 11 474 <= 64 x 512: two items per workgroup, 3 566 / 2 = 1 783
         const WalkedPlan w = plan_walked(c, 57046, 5, 0, 1, 57046, -1, MM16);
-        CHECK(w.rows == 57046 && w.n_tiles == 3566 && w.max_range == 11410 && w.seg_cols == 512 && w.n_seg == 23 && w.mm16_waves == 2);
-        CHECK(is_grid(w.grid, 1783, 23));
+        CHECK(w.rows == 57046 && w.n_tiles == 3566 && w.max_range == 11410 && w.seg_cols == 1024 && w.n_seg == 12 && w.mm16_waves == 2);
+        CHECK(is_grid(w.grid, 1783, 12));
+        // the packed-fp32 kernel: n <= 100 000: 512 columns, and 11 410 >= 4 x 512 keeps them; ceil(11 474 / 512) = 23; four wavefronts: 892
+        const WalkedPlan q = plan_walked(c, 57046, 5, 0, 1, 57046, -1, PACKED);
+        CHECK(q.seg_cols == 512 && q.n_seg == 23 && is_grid(q.grid, 892, 23));
         CHECK(pass_shape(c, 57046, 5, ALGO_SIEVE, true, false, false, 1, false, whole_pass(57046, 5)).longest_of_pass == 11410);
         CHECK(pass_shape(c, 57046, 5, ALGO_SIEVE, true, false, false, 1, false, whole_pass(57046, 5)).chunk == 11409);
     }
@@ -53,14 +56,14 @@ static int walked() {
         const WalkedPlan w = plan_walked(c, 57046, 2000, 0, 1, 57046, -1, MM16);
         CHECK(w.max_range == 1074 && w.seg_cols == 256 && w.n_seg == 5 && w.mm16_waves == 2 && is_grid(w.grid, 1783, 5));
     }
-    {   // more than MM16_LONG_SEGS = 64 segments of 512 columns: max_range + 64 > 64 x 512 = 32 768, i.e. a chunk of 32 705, which the
-        // one-chunk pass of 32 705 structures is the smallest run to have (from 100 001 structures on the segments are 1 024 columns).
-        // ceil(32 769 / 512) = 65; ceil(32 705 / 16) = 2 045 tiles, four items per workgroup: ceil(2 045 / 4) = 512
+    {   // a range of more than MM16_LONG_SEGS = 64 segments of 512 columns: max_range + 64 > 32 768, i.e. a chunk of 32 705, which the
+        // one-chunk pass of 32 705 structures is the smallest run to have: four items per workgroup, whatever the segments' own length
+        // (1 024: ceil(32 769 / 1 024) = 33); ceil(32 705 / 16) = 2 045 tiles: ceil(2 045 / 4) = 512
         const WalkedPlan w = plan_walked(c, 32705, 1, 0, 1, 32705, -1, MM16);
-        CHECK(w.n_seg == 65 && w.mm16_waves == 4 && w.n_tiles == 2045 && is_grid(w.grid, 512, 65));
-        // ... one structure fewer: 32 768 / 512 = 64 segments, two items: 2 044 / 2 = 1 022
+        CHECK(w.seg_cols == 1024 && w.n_seg == 33 && w.mm16_waves == 4 && w.n_tiles == 2045 && is_grid(w.grid, 512, 33));
+        // ... one structure fewer: 32 768 / 1 024 = 32 segments, two items: 2 044 / 2 = 1 022
         const WalkedPlan v = plan_walked(c, 32704, 1, 0, 1, 32704, -1, MM16);
-        CHECK(v.n_seg == 64 && v.mm16_waves == 2 && is_grid(v.grid, 1022, 64));
+        CHECK(v.n_seg == 32 && v.mm16_waves == 2 && is_grid(v.grid, 1022, 32));
         // the packed-fp32 kernel: four wavefronts per workgroup whatever the segments
         CHECK(plan_walked(c, 32704, 1, 0, 1, 32704, -1, PACKED).mm16_waves == 4 && is_grid(plan_walked(c, 32704, 1, 0, 1, 32704, -1, PACKED).grid, 511, 64));
     }
@@ -97,13 +100,70 @@ static int walked() {
         // items; more rows than the bound are the bound
         for (int64_t now : {0, 1}) {
             const WalkedPlan w = plan_walked(c, 57046, 5, 0, 1, 57046, now, MM16);
-            CHECK(is_grid(w.grid, 1, 23) && w.rows == 57046 && w.n_tiles == 3566);
+            CHECK(is_grid(w.grid, 1, 12) && w.rows == 57046 && w.n_tiles == 3566);
         }
-        CHECK(is_grid(plan_walked(c, 57046, 5, 0, 1, 57046, 33, MM16).grid, 2, 23) && is_grid(plan_walked(c, 57046, 5, 0, 1, 57046, 60000, MM16).grid, 1783, 23));
+        CHECK(is_grid(plan_walked(c, 57046, 5, 0, 1, 57046, 33, MM16).grid, 2, 12) && is_grid(plan_walked(c, 57046, 5, 0, 1, 57046, 60000, MM16).grid, 1783, 12));
         CHECK(is_grid(plan_walked(c, 57046, 5, 0, 1, 57046, 65, MM64).grid, 1, 12));   // (two groups of 64 rows: one workgroup)
         // a pass without rows (a rank of a partitioned pass that has no chunk): sized as one row
         const WalkedPlan e = plan_walked(c, 9000, 2, 0, 1, 0, -1, MM16);
         CHECK(e.rows == 1 && e.n_tiles == 1 && e.max_range == 1 && is_grid(e.grid, 1, 1));
+    }
+    {   // mm16_item_shape on either side of its thresholds.  8 191 columns a row: 512, ceil(8 255 / 512) = 17; 8 192: 1 024, ceil(8 256 / 1 024) = 9
+        const Mm16Shape a = mm16_item_shape(8191), b = mm16_item_shape(8192);
+        CHECK(a.seg_cols == 512 && a.waves == 2 && b.seg_cols == 1024 && b.waves == 2);
+        CHECK(plan_walked(c, 8191, 1, 0, 1, 8191, -1, MM16).n_seg == 17 && plan_walked(c, 8192, 1, 0, 1, 8192, -1, MM16).n_seg == 9);
+        // the halving: 2 048 columns keep 512 (four segments), 2 047 take 256, and so does everything shorter
+        CHECK(mm16_item_shape(2048).seg_cols == 512 && mm16_item_shape(2047).seg_cols == 256 && mm16_item_shape(1).seg_cols == 256);
+        // 57 046 structures: 10 chunks of 5 704, the last 5 710: 512, ceil(5 774 / 512) = 12; 2 chunks of 28 523: 1 024, ceil(28 587 / 1 024) = 28, two
+        // items; one chunk: ceil(57 110 / 1 024) = 56 segments, 57 110 > 32 768: four items, ceil(3 566 / 4) = 892 workgroups
+        const WalkedPlan k10 = plan_walked(c, 57046, 10, 0, 1, 57046, -1, MM16), k2 = plan_walked(c, 57046, 2, 0, 1, 57046, -1, MM16), k1 = plan_walked(c, 57046, 1, 0, 1, 57046, -1, MM16);
+        CHECK(k10.max_range == 5710 && k10.seg_cols == 512 && k10.n_seg == 12 && k10.mm16_waves == 2);
+        CHECK(k2.max_range == 28523 && k2.seg_cols == 1024 && k2.n_seg == 28 && k2.mm16_waves == 2 && is_grid(k2.grid, 1783, 28));
+        CHECK(k1.seg_cols == 1024 && k1.n_seg == 56 && k1.mm16_waves == 4 && is_grid(k1.grid, 892, 56));
+        // "seg_cols" = 256 on 16 321 structures in one chunk: ceil(16 385 / 256) = 65 segments, 16 385 > 64 x 256: four items, 1 021 tiles in
+        // ceil(1 021 / 4) = 256 workgroups; one structure fewer: 64 segments, two items, 1 020 / 2 = 510
+        tsc_options o;
+        o.seg_cols = 256;
+        const WalkedPlan s = plan_walked(o, 16321, 1, 0, 1, 16321, -1, MM16), t = plan_walked(o, 16320, 1, 0, 1, 16320, -1, MM16);
+        CHECK(s.seg_cols == 256 && s.n_seg == 65 && s.mm16_waves == 4 && is_grid(s.grid, 256, 65));
+        CHECK(t.n_seg == 64 && t.mm16_waves == 2 && is_grid(t.grid, 510, 64));
+        o.seg_cols = 512;   // ... = 512: ceil(16 385 / 512) = 33 segments, two items
+        CHECK(plan_walked(o, 16321, 1, 0, 1, 16321, -1, MM16).n_seg == 33 && plan_walked(o, 16321, 1, 0, 1, 16321, -1, MM16).mm16_waves == 2);
+    }
+    {   // the shapes of tests/test_walked_items.py: {structures, "seg_cols", the length and the segments its k = 1 pass must have}.  A forced length
+        // is halved while the range is shorter than four segments: the "end" cases stand at n + 64 = m x length - 1, + 0, + 1 with n >= 4 x length
+        const int cases[][4] = {{191, 256, 256, 1}, {192, 256, 256, 1}, {193, 256, 256, 2}, {447, 256, 256, 2}, {448, 256, 256, 2}, {449, 256, 256, 3},
+                                {2495, 512, 512, 5}, {2496, 512, 512, 5}, {2497, 512, 512, 6}, {3007, 512, 512, 6}, {3008, 512, 512, 6}, {3009, 512, 512, 7},
+                                {5055, 1024, 1024, 5}, {5056, 1024, 1024, 5}, {5057, 1024, 1024, 6}, {6079, 1024, 1024, 6}, {6080, 1024, 1024, 6},
+                                {6081, 1024, 1024, 7}, {10175, 2048, 2048, 5}, {10176, 2048, 2048, 5}, {10177, 2048, 2048, 6},
+                                {1000, 256, 256, 5}, {4200, 1024, 1024, 5}, {8256, 2048, 2048, 5},
+                                // the rule's own choice: 1 000, 2 047 -> 256; 2 048, 2 111, 3 000, 8 191 -> 512; 8 192, 9 000 -> 1 024
+                                {1000, 0, 256, 5}, {2047, 0, 256, 9}, {2048, 0, 512, 5}, {2111, 0, 512, 5}, {3000, 0, 512, 6}, {8191, 0, 512, 17},
+                                {8192, 0, 1024, 9}, {9000, 0, 1024, 9}, {16321, 256, 256, 65}};
+        const int ks[] = {2000, 1000, 500, 200, 100, 50, 20, 10, 5, 2, 1};
+        for (const auto &cs : cases) {
+            tsc_options o;
+            o.seg_cols = cs[1];
+            const WalkedPlan k1 = plan_walked(o, cs[0], 1, 0, 1, cs[0], -1, MM16);
+            CHECK(k1.max_range == cs[0] && k1.seg_cols == cs[2] && k1.n_seg == cs[3]);
+            // every pass of the schedule (rmsd_pruning.py:186-192: k chunks while 20 k < n): the segments cover a row's range from the 64-aligned
+            // column below it, and a column offset inside a segment fits MM16_OFFSET_BITS bits
+            for (int k : ks) {
+                if (k != 1 && 20 * k >= cs[0]) continue;
+                const WalkedPlan w = plan_walked(o, cs[0], k, 0, 1, cs[0], -1, MM16);
+                CHECK(int64_t(w.n_seg) * w.seg_cols >= w.max_range + 64 && w.seg_cols <= (1 << MM16_OFFSET_BITS) && w.seg_cols >= 1);
+                CHECK((w.mm16_waves == 2 || w.mm16_waves == 4) && w.grid.y == unsigned(w.n_seg) && int(w.grid.x) * w.mm16_waves >= w.n_tiles);
+            }
+        }
+        // the dense case's k = 2 pass (chunks of 4 128): the forced 2 048 halved to 1 024, ceil(4 192 / 1 024) = 5
+        tsc_options o;
+        o.seg_cols = 2048;
+        CHECK(plan_walked(o, 8256, 2, 0, 1, 8256, -1, MM16).seg_cols == 1024 && plan_walked(o, 8256, 2, 0, 1, 8256, -1, MM16).n_seg == 5);
+    }
+    {   // a run beyond 100 000 structures on the 16-row kernel keeps the length of its size as the floor: 126 000 in one chunk 1 024, 483 000 4 096;
+        // 483 000 in 100 chunks of 4 830: 4 096 halved twice, 1 024 (as the packed-fp32 kernel's above)
+        CHECK(plan_walked(c, 126000, 1, 0, 1, 126000, -1, MM16).seg_cols == 1024 && plan_walked(c, 483000, 1, 0, 1, 483000, -1, MM16).seg_cols == 4096);
+        CHECK(plan_walked(c, 483000, 100, 0, 1, 483000, -1, MM16).seg_cols == 1024 && mm16_item_shape(5000, 1024).seg_cols == 1024 && mm16_item_shape(5000).seg_cols == 512);
     }
     return 0;
 }

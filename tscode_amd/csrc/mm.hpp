@@ -497,7 +497,8 @@ inline __global__ __launch_bounds__(64 * MM_WAVES, TSC_MM_OCC) void k_rmsd_sieve
 #endif
 // work items (wavefronts) per workgroup of the 16-row kernel: 2 where most workgroups of the grid have work (a workgroup keeps its slot until
 // its longest item is through: C3's k = 100 .. 2 passes 2 - 4 us shorter than with 4), 4 where most are empty and the launch is its dispatch
-// (C3's last pass: 28 us against 44) -- the host picks by the number of column segments (launch_pair_search)
+// (C3's last pass: 28 us against 44) -- the host picks by the columns a row of the pass can have: more than MM16_LONG_SEGS segments of 512
+// (pass_plan.hpp: mm16_items_per_workgroup)
 constexpr int MM16_LONG_SEGS = 64;
 constexpr int MM16_BLOCKS = 128 / MM_STEP;   // 16-column blocks of a column tile
 

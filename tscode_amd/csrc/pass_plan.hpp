@@ -121,6 +121,50 @@ struct WalkedPlan {
     int mm16_waves;   // work items per workgroup of the 16-row matrix-core kernel
     dim3 grid;
 };
+// ---- the 16-row matrix-core kernel's work item: columns per segment and items per workgroup, from the columns a row of the pass can have ----
+// The rule (measured per pass on MI355X at 57 046 structures, tools/sweep_items.py; MEASURED.md 33):
+//   * segments of 1 024 columns where a row's range holds eight of them (max_range >= 8 192), else 512, halved to 256 while the range is
+//     shorter than four segments.  An item's screen is 1 us per 128 columns; from 11 410 columns a row on, 1 024 ends a pass 4 - 5 us sooner
+//     than 512 (half the items, each paying prologue and tail once), at 5 705 it ends it 2 us later (a pass ends with its longest item), and
+//     2 048 loses everywhere but in the last pass.  One segment per row tile (ranges up to 4 032) was measured too: level at 570 and 1 140
+//     columns a row, 6 us worse at 1 074 (the long last chunk of a pass of short chunks), 15 us worse at 2 853 -- not taken.
+//   * two items per workgroup; four where most workgroups are empty and the launch is its dispatch -- a range of more than MM16_LONG_SEGS
+//     segments of 512 columns (of the segment length itself where "seg_cols" set a shorter one), whatever length the segments have: the
+//     one-chunk pass of 57 046 takes 50 us with four items on 1 024 columns, 55 with two, 59 with four on 512.  One item per workgroup was
+//     measured as well (within 1 us of two in every pass): there is no such instantiation.
+// The sweep was of ONE run size (57 046 structures: the kernel takes runs below "mm_min_n" = 100 000).  The row tiles of the pass and the
+// wavefronts the device holds decide nothing in it -- shapes that bring the items of a pass under the 4 096 wavefront slots gained nothing
+// -- so the rule is of max_range alone.  A run this kernel is given beyond 100 000 structures ("sieve_mm" = 0, a higher "mm_min_n") was not
+// measured: by_n_cols, the length plan_walked has for a run of that size (1 024, 4 096 beyond 400 000), stays the floor there, as it was.
+// Queue entries carry the column offset inside the segment in MM16_OFFSET_BITS bits: no segment is longer than 4 096 columns.
+struct Mm16Shape {
+    int seg_cols, waves;
+};
+constexpr int MM16_OFFSET_BITS = 12;
+constexpr int MM16_WIDE_RANGE = 8 * 1024;
+// (for variant builds of a sweep, tools/build_variant.py + tools/sweep_items.py: -DTSC_MM16_ITEMS=2 or 4 gives every pass that many items per
+// workgroup, -DTSC_MM16_SEG=cols every pass of this kernel that segment length, unhalved; 0: the rule)
+#ifndef TSC_MM16_ITEMS
+#define TSC_MM16_ITEMS 0
+#endif
+#ifndef TSC_MM16_SEG
+#define TSC_MM16_SEG 0
+#endif
+static_assert(TSC_MM16_ITEMS == 0 || TSC_MM16_ITEMS == 2 || TSC_MM16_ITEMS == 4, "k_rmsd_sieve_mm16 is instantiated for 2 and 4 items per workgroup");
+static_assert(TSC_MM16_SEG >= 0 && TSC_MM16_SEG <= (1 << MM16_OFFSET_BITS) && TSC_MM16_SEG % 128 == 0, "whole column tiles, within the offset bits");
+static inline int mm16_items_per_workgroup(int max_range, int seg_cols) {
+    if (TSC_MM16_ITEMS) return TSC_MM16_ITEMS;
+    return max_range + 64 > MM16_LONG_SEGS * std::min(seg_cols, 512) ? 4 : 2;
+}
+static inline Mm16Shape mm16_item_shape(int max_range, int by_n_cols = 512) {
+    Mm16Shape m;
+    m.seg_cols = std::max(by_n_cols, max_range >= MM16_WIDE_RANGE ? 1024 : 512);
+    while (m.seg_cols > 256 && max_range < m.seg_cols * 4) m.seg_cols /= 2;
+    if (TSC_MM16_SEG) m.seg_cols = TSC_MM16_SEG;
+    m.waves = mm16_items_per_workgroup(max_range, m.seg_cols);
+    return m;
+}
+
 // rows_ub: upper bound of the rows of the pass on this device (n; in a rank-partitioned pass the structures of this rank's chunks)
 // rows_now (< 0: not known; else <= rows_ub is meant): the rows the pass really has, where the host has learnt it (a pass that waited for
 // k_cull_decide): the grid is sized for them; everything else stays with rows_ub
@@ -132,16 +176,20 @@ static inline WalkedPlan plan_walked(const tsc_options &c, int64_t n, int64_t k,
     w.max_range = int(std::min<int64_t>(A, longest_of_pass));
     // a wavefront walks its segment tile by tile: short segments keep the critical path short when a pass has little
     // work (many small chunks), long ones amortise the per-item setup when it has a lot
-    // (measured on MI355X, tools/sweep.py: 512 columns at 57k structures, 1024 at 126k, 4096 at 483k; "seg_cols" overrides)
-    w.seg_cols = c.seg_cols > 0 ? c.seg_cols : (n <= 100000 ? 512 : (n <= 400000 ? 1024 : 4096));
+    // (the packed-fp32 kernel, measured on MI355X, tools/sweep.py: 512 columns at 57k structures, 1024 at 126k, 4096 at 483k; "seg_cols" overrides)
+    const int by_n_cols = n <= 100000 ? 512 : (n <= 400000 ? 1024 : 4096);
+    w.seg_cols = c.seg_cols > 0 ? c.seg_cols : by_n_cols;
     while (w.seg_cols > 256 && w.max_range < w.seg_cols * 4) w.seg_cols /= 2;
     // the screen on the matrix cores (mm.hpp): 64 rows per work item and segments of their own length
     if (f.mm) w.seg_cols = c.mm_seg_cols > 0 ? c.mm_seg_cols : (w.max_range >= 2048 ? 1024 : 512);
+    // the 16-row matrix-core kernel: lengths of its own as well (mm16_item_shape; "seg_cols" overrides, as above)
+    if (f.mm16 && c.seg_cols <= 0) w.seg_cols = mm16_item_shape(w.max_range, by_n_cols).seg_cols;
+    static_assert((1 << MM16_OFFSET_BITS) >= 4096, "the longest segment a rule of this file returns");
     w.n_seg = ceil_div(w.max_range + 64, w.seg_cols);  // + 64: a segment starts at the 64-aligned column below r0 + 1
     const int my_tiles = (w.n_tiles - rank + world - 1) / world;
     // (mm: groups of 64 rows dealt round-robin to the ranks; the 16-row matrix-core kernel: two items per workgroup, four where most workgroups are
-    // empty -- beyond MM16_LONG_SEGS segments)
-    w.mm16_waves = f.mm16 ? (w.n_seg <= MM16_LONG_SEGS ? 2 : 4) : 4;
+    // empty -- mm16_items_per_workgroup)
+    w.mm16_waves = f.mm16 ? mm16_items_per_workgroup(w.max_range, w.seg_cols) : 4;
     const int A_grid = rows_now >= 0 ? int(std::min<int64_t>(std::max<int64_t>(rows_now, 1), A)) : A;
     const int grid_tiles = (ceil_div(A_grid, TILE_ROWS) - rank + world - 1) / world;
     w.grid = dim3(std::max(1, f.mm ? ceil_div((ceil_div(A_grid, MM_ROWS) - rank + world - 1) / world, MM_WAVES) : ceil_div(std::min(my_tiles, grid_tiles), w.mm16_waves)),
