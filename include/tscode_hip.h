@@ -865,7 +865,7 @@ int tsc_rot_corr_batch_destroy(tsc_rot_corr_batch *run);
  *   tsc_align_structures  align_structures (tscode/hypermolecule_class.py:38-72): every structure is centred on the mean of its
  *                         indexed atoms (:53-55; indices NULL or n_idx == 0: all atoms, :51) and structures 1 .. N-1 are turned by the
  *                         proper rotation that takes their indexed atoms onto structure 0's (rmsd's kabsch at :63, applied at :70).
- *                         The LinAlgError branch (:65-67) has no counterpart: the solver (Horn's quaternion, csrc/rmsd.hpp) does not
+ *                         The LinAlgError branch (:65-67) has no counterpart: the solver (Horn's quaternion, csrc/pair_math.hpp) does not
  *                         fail; where the optimum is not unique the result is finite and a proper rotation.  out f64[N, n, 3].
  *   tsc_kmeans_lloyd      what KMeans(n_clusters = k, init = <array>, n_init = 1, algorithm = "lloyd").fit(X) computes (:889-890 with
  *                         the initial centres given): X f64[N, D] and init f64[k, D] are mean-centred, tol_abs = mean(var(X, 0)) * tol;

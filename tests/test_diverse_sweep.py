@@ -37,7 +37,7 @@ Which path of diverse.hpp each shape is there for:
    k * n loop), clusters of 257 and 600 members on the energies path (a second and third trip of the 256 stride, the four-wavefront
    reduction), an empty cluster, and exact ties: copies of a row (cumdist), equal energies at positions 3 / 300 (one wavefront, two
    trips) and 70 / 130 (two wavefronts).
-5. align_structures (dv_align_structures, dv_centroid, exact_quaternion of rmsd.hpp): 1, 2, 3, 4, 63, 64, 65, 512 atoms (lane-strided
+5. align_structures (dv_align_structures, dv_centroid, exact_quaternion of pair_math.hpp): 1, 2, 3, 4, 63, 64, 65, 512 atoms (lane-strided
    loops, DV_MAX_ATOMS); 1, 2, 4, 5, 9 structures (four per workgroup); index sets sorted, unsorted, with a repeat, of one atom; noisy
    copies, unrelated structures, mirror images (det S < 0), planar molecules, structures 1000 A out.  Where Horn's top eigenvalue is
    separated by HORN_BAND relative: coordinates against numpy's SVD route.  Where it is not (1 or 2 atoms, collinear sets, and two
@@ -473,7 +473,7 @@ def horn(s, idx):
         M = M + np.triu(M, 1).T
         ev = np.linalg.eigvalsh(M)
         G = float((p * p).sum() + (q * q).sum())
-        # what rotation_quaternion_fast (rmsd.hpp) tests before it trusts the adjugate of A = M - lambda_max I: best / scale^3 > 1e-4
+        # what rotation_quaternion_fast (pair_math.hpp) tests before it trusts the adjugate of A = M - lambda_max I: best / scale^3 > 1e-4
         A = M - ev[-1] * np.eye(4)
         best = max(abs(np.linalg.det(np.delete(np.delete(A, i, 0), i, 1))) for i in range(4))
         ratio = best / np.abs(A).max() ** 3 if np.abs(A).max() > 0.0 else 0.0

@@ -26,7 +26,7 @@ B.  compact_rows_dev / gather_heavy_dev (csrc/scan.hpp) bit for bit against NumP
     of every kind, against the oracle within 4 * 2^-53 (|R| |x| + |t|) per component (three products, three sums, fused or not), the
     outputs of one kernel bit-identical whatever the entry point; the tables the context caches between calls (heavy_slot_table,
     basis_sample_table in csrc/pipeline.hip) against fresh contexts.
-C.  k_transform_describe (csrc/sieve.hpp): the structure-level cases of tests/test_screen_limit.py -- pairs PLACED at the descriptor
+C.  k_transform_describe (csrc/describe.hpp): the structure-level cases of tests/test_screen_limit.py -- pairs PLACED at the descriptor
     screens' limit -- as pose lists that embed exactly (every structure is conformer s of two fragments, identity rotations, zero
     translations), through tsc_pipeline_dev and through the multi-rank front's sequence basis_from_poses_dev -> embed_masked_dev ->
     tsc_prune_create, also with a basis forked from a foreign ensemble; random ensembles on both sides of the kernel's LDS gate.
@@ -965,7 +965,7 @@ def test_multi_rank_front_sequence_keeps_every_pair_placed_at_the_limit(oracle, 
 
 # ------------------------------------------------------------------------------------------------------------ C3: the LDS gate
 def transform_describe_lds_bytes(n_mols, h):
-    """csrc/sieve.hpp, restated: the staged pose parameters of k_transform (TR_POSES x n_mols x (12 doubles + an int) + TR_POSES indices), rounded
+    """csrc/describe.hpp, restated: the staged pose parameters of k_transform (TR_POSES x n_mols x (12 doubles + an int) + TR_POSES indices), rounded
     up to 16 bytes, the basis ([8][features of both families]) and TR_POSES rows of (3 h | 1) doubles."""
     transform = TR_POSES * n_mols * (12 * 8 + 4) + TR_POSES * 8
     features = min(h, 256) + min(h // 2, 256)

@@ -242,7 +242,7 @@ def algo(request, eng):
         opts["open_lds_blocks"] = 0
     if request.param[3] in (3, 5, 8):      # every pass of fewer than 64 chunks laid out along the Morton curve, tile pairs skipped by bounding box (cull.hpp)
         opts.update(cull_min_pairs=0, cull=2)
-    if request.param[3] in (4, 5, 7):      # H of stage 1 from the float32 copy, its own rounding bound (sieve.hpp: pair_stage1)
+    if request.param[3] in (4, 5, 7):      # H of stage 1 from the float32 copy, its own rounding bound (pair_stages.hpp: pair_stage1)
         opts["stage1_f32"] = 2
     with eng.options(**opts):
         yield request.param[0]
@@ -1027,7 +1027,7 @@ def test_prune_and_clash_far_from_the_origin(eng, oracle, offset, algo):
 
 @pytest.mark.parametrize("h", [512, 1024])
 def test_prune_hundreds_of_heavy_atoms(eng, oracle, h):
-    """h = 512 and 1024 heavy atoms per structure (the rounding bound of the quartic tests grows with h: rmsd.hpp,
+    """h = 512 and 1024 heavy atoms per structure (the rounding bound of the quartic tests grows with h: pair_math.hpp,
     quartic_kappa; the descriptor build stages 12-24 KB per structure)."""
     rng = np.random.default_rng(h)
     n_par, n = 40, 320

@@ -1,4 +1,4 @@
-"""A prune pass is closed by the first kernel of the NEXT pass (csrc/rmsd.hpp, pass_derive), not by the last wavefront of its own: the
+"""A prune pass is closed by the first kernel of the NEXT pass (csrc/pass_state.hpp, pass_derive), not by the last wavefront of its own: the
 count of active structures, the bit copy of the mask in use and the gate of rmsd_pruning.py:192 are worked out from the state block and
 the counters the pass left behind.  Checked here against oracle.prune_heavy, in both modes, through the one-call entry point: the final
 mask and, per pass, (k, n_active_before, n_active_after, pairs_evaluated).

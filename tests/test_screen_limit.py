@@ -1,5 +1,5 @@
 """The descriptor screens of the prune at their limit: the one property the survivor sets rest on is that a screen never drops a pair the
-reference would call similar (csrc/sieve.hpp, csrc/mm.hpp: screen_limit32, screen_limit32_dot, screen_limit_mm).  Random ensembles stay
+reference would call similar (csrc/descriptor.hpp, csrc/mm.hpp: screen_limit32, screen_limit32_dot, screen_limit_mm).  Random ensembles stay
 far inside the screens' margins; the inputs here are PLACED at the limit.
 
 Value level (the matrix-core form, through tsc_screen_mm_values and tsc_screen_mm_keeps).  Descriptor sets D in float32 whose exact
@@ -20,7 +20,7 @@ carry a relative 2^-50, five orders below the smallest gap.
 
 Structure level (every route, against the oracle).  Structures whose atoms move along their own radius only, x_a = r_a u_a with fixed unit
 vectors u_a: for two of them H = sum r_a r'_a u_a u_a^T is symmetric positive semidefinite, the optimal rotation about the origin is the
-identity and h rmsd^2 = sum (r_a - r'_a)^2 -- which is the family-0 feature distance (csrc/sieve.hpp, feature()): the sieve's inequality
+identity and h rmsd^2 = sum (r_a - r'_a)^2 -- which is the family-0 feature distance (csrc/descriptor.hpp, feature()): the sieve's inequality
 is an equality.  Isolated pairs at rmsd = thr (1 -+ eps), eps log-uniform in [2^-20, 2^-12], centres on a lattice of spacing 3.2 thr sqrt(h)
 (members of different pairs are more than 2 thr apart): the oracle removes the first member of every inside pair and nothing else, and a
 screen that drops one inside pair leaves one survivor too many.  At most 8 atoms breathe (the first 8), so the 8 descriptor dimensions
@@ -397,7 +397,7 @@ def test_breathing_pairs_make_the_sieve_bound_tight(oracle, name):
     assert (rm[~inside] > THR).all() and (rm[~inside] < THR * (1 + GAP_MAX)).all()
     gap = np.abs(rm / THR - 1.0)
     assert gap.min() < 2.0 ** -18 and gap.max() > 2.0 ** -14 and (gap >= 2.0 ** -20.5).all()
-    # the family-0 features (csrc/sieve.hpp: feature(), the atoms' distances from the origin) hold all of h rmsd^2
+    # the family-0 features (csrc/descriptor.hpp: feature(), the atoms' distances from the origin) hold all of h rmsd^2
     f0 = np.linalg.norm(heavy, axis=2)
     dist0 = ((f0[pairs[:, 0]] - f0[pairs[:, 1]]) ** 2).sum(axis=1)
     assert (dist0[inside] >= (1 - 2.0 ** -10) * h * THR * THR).all() and (dist0[inside] < h * THR * THR).all()

@@ -11,7 +11,7 @@ candidate has to be found and the smallest index taken).
 
 The active set of a pass is a proxy: a uniform random subset of the structures that pass the clash check, of the size the recorded
 oracle run had entering that pass (tests/golden/expected_full.json); the removed rows' exit points are drawn from the same run's
-pair-evaluation counts.  Descriptors are the kernel's (sieve.hpp): 8 principal components of the atom norms and of the half-chain pair
+pair-evaluation counts.  Descriptors are the kernel's (descriptor.hpp): 8 principal components of the atom norms and of the half-chain pair
 distances / sqrt 2, estimated from a 4096-structure sample.
 
 usage: python tools/culling_study.py [C3 C4] > profiles/r03_culling_study.json"""

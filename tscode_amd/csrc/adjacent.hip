@@ -3,6 +3,7 @@
 #include "host.hpp"
 #include "call.hpp"
 #include "scan.hpp"
+#include "prune_api.hpp"
 #include "group_filter.hpp"
 #include "csearch.hpp"
 #include "tfd.hpp"

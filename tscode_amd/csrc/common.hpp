@@ -110,7 +110,7 @@ struct tsc_ctx {
     bool xd_valid = false;
     int xd_borrowers = 0;                 // live prune runs that read the xd_* buffers (tsc_prune_create borrowed them): no release / regrow meanwhile
     // Bookkeeping that runs of one context driven from DIFFERENT host threads touch (tsc_prune_create / tsc_prune_destroy): the pinned flag
-    // words handed to runs (host.hpp: PINNED_FLAG_OFFSET; bit s set = word s is some live run's) and the list of live runs, which
+    // words handed to runs (prune_api.hpp: PINNED_FLAG_OFFSET; bit s set = word s is some live run's) and the list of live runs, which
     // tsc_ctx_destroy destroys with the context -- a host whose finalisers run in no particular order cannot leak a run's events.
     std::mutex runs_mutex;
     unsigned long long flag_slots_used = 0;

@@ -2,7 +2,7 @@
 //
 // A pair (query p, library q) is the reference's rmsd_and_max_numba(p, q) (tscode/rmsd_pruning.py:6-41): the optimal PROPER rotation of p
 // onto q about the origin, rmsd = sqrt(sum |Rp - q|^2 / h), maxdev = max_a |Rp_a - q_a|; "similar" is rmsd < thr and maxdev < 2 thr (:75,
-// :208-224).  The arithmetic is rmsd.hpp's (exact_quaternion, rmsd_and_max_pair, certainly_dissimilar); what is here is the rectangle:
+// :208-224).  The arithmetic is pair_math.hpp's (exact_quaternion, rmsd_and_max_pair, certainly_dissimilar); what is here is the rectangle:
 //
 //   k_cross_pack            (N, n, 3) structures -> the compared atoms row-major, zero-padded to the kernel's atom count (Xr), the same
 //                           transposed [pitch][ld] (Xc, register path only), the squared norms G; centred on the compared atoms' mean
@@ -14,7 +14,7 @@
 //
 // Epilogues:
 //   CX_VALUES   every pair exactly; rmsd[q][l], maxdev[q][l] contiguous along l.  No screen.
-//   CX_FIRST    certainly_dissimilar screens (a rejection is always right, rmsd.hpp), survivors take rmsd_and_max_pair; the lowest similar
+//   CX_FIRST    certainly_dissimilar screens (a rejection is always right, pair_math.hpp), survivors take rmsd_and_max_pair; the lowest similar
 //               library index of a row goes to first[q] by atomicMin (INT32_MAX: none).  A row is not visited by a segment once its
 //               first lies left of that segment.  The minimum of a set does not depend on the order of the atomics.
 //   CX_NEAREST  every pair exactly; per (segment, row) ONE wavefront walks the segment's columns in ascending order and writes the smallest
@@ -24,7 +24,7 @@
 #pragma once
 
 #include "cross_plan.hpp"
-#include "rmsd.hpp"
+#include "pair_math.hpp"
 
 namespace tsc {
 
@@ -120,7 +120,7 @@ struct CrossArgs {
     int32_t *idx;           // CX_FIRST: first[nq], INT32_MAX before the launch; CX_NEAREST: partial [n_seg][nq]
 };
 
-// residual_rmsd_maxdev (rmsd.hpp; rmsd_pruning.py:29-39) with the library structure in registers: the padded atoms are zero on both sides
+// residual_rmsd_maxdev (pair_math.hpp; rmsd_pruning.py:29-39) with the library structure in registers: the padded atoms are zero on both sides
 // and add nothing to the sum or the maximum
 template <int HP>
 __device__ inline void cross_residual_regs(const double *__restrict__ p, const double (&q)[HP * 3], int h, const double e[4], double &rmsd, double &maxdev) {

@@ -8,7 +8,7 @@
 
 namespace tsc {
 
-constexpr int CX_ROWS = 16;            // query rows of a work item (one wavefront: a lane is a library column, rmsd.hpp: k_rmsd_tile)
+constexpr int CX_ROWS = 16;            // query rows of a work item (one wavefront: a lane is a library column, rmsd_tile.hpp: k_rmsd_tile)
 constexpr int CX_WAVES = 4;            // work items of a workgroup: four consecutive row tiles on one column segment
 constexpr int CX_MAX_HP = 32;          // padded compared atoms the register path holds (96 doubles per lane); beyond: the general path
 constexpr int CX_SEG_MAX = 4096;       // columns of a segment where the rows alone fill the chip: a long walk amortises a work item's setup

@@ -10,7 +10,7 @@
 #pragma once
 #include "common.hpp"
 #include "embed_clash.hpp"
-#include "rmsd.hpp"
+#include "pair_math.hpp"
 
 namespace tsc {
 
@@ -537,7 +537,7 @@ inline __global__ __launch_bounds__(256) void k_string_embed_params(const double
 // pose parameters of the cyclical embed (tscode/embeds.py:676-713), one thread per (pose, molecule).
 // align_vec_pair (algebra.py:258-282: SVD of B = sum_j ref_j tgt_j^T, improper-rotation fix, U V^T) is the proper rotation
 // R that best maps tgt_j onto ref_j; here it is taken as the top eigenvector of Horn's quaternion matrix of
-// S = sum_j tgt_j ref_j^T (cyclic Jacobi, top_eigvec4 of rmsd.hpp) -- the same rotation wherever it is unique.
+// S = sum_j tgt_j ref_j^T (cyclic Jacobi, top_eigvec4 of pair_math.hpp) -- the same rotation wherever it is unique.
 __device__ inline void align_vec_pair_dev(const double ref0[3], const double ref1[3], const double tgt0[3], const double tgt1[3], double R[9]) {
     double S[9];
 #pragma unroll

@@ -19,7 +19,8 @@
 //     applied by k_apply_pass behind the pair kernel (not tile by tile inside it);
 //   * the number of pair evaluations the REFERENCE would have made follows from best[] and cend[] as before.
 #pragma once
-#include "rmsd.hpp"
+#include "mm_record.hpp"
+#include "shapes.hpp"
 #include "sieve.hpp"
 
 namespace tsc {
@@ -27,13 +28,8 @@ namespace tsc {
 constexpr int CULL_MORTON_BITS = 5;                         // bits per dimension of the (coarse) Morton key
 constexpr int CULL_MORTON_DIMS = 3;                         // leading components of family 0
 constexpr int CULL_BUCKETS = 1 << (CULL_MORTON_BITS * CULL_MORTON_DIMS);   // 32 768 cells: a counting sort, no comparison sort
-constexpr int CULL_MAX_CHUNKS = 64;                         // passes with more chunks are not culled (their chunks are short anyway)
-constexpr int CULL_COLS = 128;                              // columns per tile (the pair kernel's CPL = 2)
+// (CULL_MAX_CHUNKS, CULL_COLS and CULL_XCD_RUN: shapes.hpp)
 constexpr int CULL_BOX = 2 * DW;                            // floats per bounding box: lo[16], hi[16]
-#ifndef TSC_CULL_XCD_RUN
-#define TSC_CULL_XCD_RUN 32
-#endif
-constexpr int CULL_XCD_RUN = TSC_CULL_XCD_RUN;              // option "cull_xcd": consecutive row groups (of 4 tiles) that stay on one XCD
 
 // ---- once per run: the structures in (coarse) Morton order of their descriptors ---------------------------------------------
 __device__ inline unsigned morton_cell(const float *__restrict__ d, float inv_dmax) {

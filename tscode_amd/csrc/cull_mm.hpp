@@ -9,7 +9,7 @@
 
 namespace tsc {
 
-constexpr int CMM_SEG = 1024;             // columns per work item (queue entries keep the column offset in 10 bits)
+// (CMM_SEG, the columns per work item: shapes.hpp)
 constexpr int CMM_TILES = CMM_SEG / CULL_COLS;
 
 struct CullMmArgs {

@@ -6,7 +6,7 @@
 // order): no floating-point atomics, so two calls on the same input return the same bits.  The only atomics are integer counts.
 //
 //   k_align_structures    one wavefront per structure: centroids over the index set, S = tgt^T ref, Horn's quaternion by the exact
-//                         path of rmsd.hpp (exact_quaternion: Newton + adjugate, Jacobi fallback), all atoms rotated.
+//                         path of pair_math.hpp (exact_quaternion: Newton + adjugate, Jacobi fallback), all atoms rotated.
 //   k_kmeans_assign       the hot path: labels[i] = argmin_c |x_i|^2 - 2 x_i.c + |c|^2.  A workgroup owns 64 rows (16 per wavefront) and
 //                         walks D in slices of 32 through LDS, against a block of 16 NT centres; the products x.c run on the matrix
 //                         cores (v_mfma_f64_16x16x4_f64: lane l holds A[l & 15][l >> 4], B[l >> 4][l & 15]; result register r of lane l
@@ -23,7 +23,7 @@
 // takes them, and its results are the single call's bit for bit.
 #pragma once
 #include "common.hpp"
-#include "rmsd.hpp"
+#include "pair_math.hpp"
 
 namespace tsc {
 
@@ -67,7 +67,7 @@ __device__ inline void dv_align_structures(const double *__restrict__ in, int64_
         return;
     }
     dv_centroid(tgt, idx, n_idx, lane, ct);
-    double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Gp = 0.0, Gq = 0.0;   // p = target, q = reference: S = p^T q (rmsd.hpp)
+    double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Gp = 0.0, Gq = 0.0;   // p = target, q = reference: S = p^T q (pair_math.hpp)
     for (int q = lane; q < n_idx; q += 64) {
         const int a = idx ? idx[q] : q;
         const double px = tgt[3 * a] - ct[0], py = tgt[3 * a + 1] - ct[1], pz = tgt[3 * a + 2] - ct[2];

@@ -7,7 +7,7 @@
 // independent.
 #pragma once
 #include "common.hpp"
-#include "sieve.hpp"
+#include "pair_stages.hpp"
 
 namespace tsc {
 

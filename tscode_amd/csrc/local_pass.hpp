@@ -27,22 +27,15 @@
 //               another order: pairs_computed, pairs_screened and the batch counts differ between the forms; verdicts, masks, cache
 //               keys and pairs_evaluated do not (tests/test_local_pass_mm.py).
 #pragma once
-#include "rmsd.hpp"
-#include "sieve.hpp"
 #include "mm.hpp"
+#include "shapes.hpp"
+#include "sieve.hpp"
 
 namespace tsc {
 
-constexpr int LP_MAX_ROWS = 2048;  // longest chunk (structures) the chunk-local kernel takes
+// (LP_MAX_ROWS, LP_TI and LP_TILES_PER_BLOCK: shapes.hpp)
 constexpr int LP_WAVES = 4;
 constexpr int LP_THREADS = LP_WAVES * 64;
-constexpr int LP_TI = 16;                       // rows per work item
-#ifndef TSC_LP_TPB
-#define TSC_LP_TPB 4
-#endif
-// row tiles one block is sized for: one per wavefront (measured against two: a wavefront walks its tiles one after the other, and
-// a pass of this kernel is as long as its slowest wavefront -- C3's k = 500 pass 44 -> 39 us, a 20 000-structure call 0.71 -> 0.64 ms)
-constexpr int LP_TILES_PER_BLOCK = TSC_LP_TPB;
 constexpr int LP_QCAP = LP_TI * 64 + 64;
 constexpr int LP_WORDS = LP_MAX_ROWS / 64;
 constexpr int LP_TICKET_GROUPS = 16;  // two-level ticket: same-address atomics serialise (~12 ns each)
@@ -98,12 +91,12 @@ __device__ inline unsigned long long lds_extract64(const unsigned long long *bit
     return lo | hi;
 }
 
-// views_insert_wave (rmsd.hpp) for this kernel, whose launch is as long as its slowest workgroup's chain: the same bits in the same words,
+// views_insert_wave (pass_state.hpp) for this kernel, whose launch is as long as its slowest workgroup's chain: the same bits in the same words,
 // but ONE round trip for the summary words of all later views instead of one per view.  The bit of a key goes out as it is found (no
 // answer is waited for); the summary word of view j -- a load, and an or only where a bit is missing: thousands of rows would else or the
 // same word -- is left to lane j - cv.first, and the lanes go for their words together behind the loop.  Rows of one tile lie in one
 // chunk, so their keys share a summary word unless the chunk straddles a multiple of 65 536 structures: such a second word is dealt with
-// on the spot, as rmsd.hpp does.
+// on the spot, as pass_state.hpp does.
 __device__ inline void lp_views_insert_wave(const CacheViews &cv, bool removed, int a, int b) {
     if (__ballot(removed) == 0) return;
     const int lane = threadIdx.x & 63;
@@ -157,7 +150,7 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
     __shared__ int s_best[LP_MAX_ROWS];
     __shared__ unsigned short s_queue[LP_WAVES][LP_QCAP], s_exq[LP_WAVES][128];
     __shared__ __attribute__((aligned(16))) float s_rowdesc[LP_WAVES][LP_TI * DW];  // (the MM form: a tile's row operands, 16 bytes per lane)
-    __shared__ double s_jacobi[LP_WAVES][32];  // the Jacobi fallback of the exact stage (rmsd.hpp: top_eigvec4_mem), per wavefront
+    __shared__ double s_jacobi[LP_WAVES][32];  // the Jacobi fallback of the exact stage (pair_math.hpp: top_eigvec4_mem), per wavefront
     __shared__ unsigned long long s_stat[8];  // block totals of the five statistics
     __shared__ int s_A, s_anydb, s_last, s_open[2];
     static_assert(DW == 16 && LP_TI * DW == 256, "row staging: 4 rows x 16 components per 64 lanes");
@@ -193,7 +186,7 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
         w_copy1[0] = bits[bit_words + w0], w_copy1[1] = bits[bit_words + w0 + 1];
         if (a.use_cache) w_view[0] = dbit[w0], w_view[1] = dbit[w0 + 1];
     }
-    // the state block of this pass: written by whoever closed the pass before it, or -- that pass was left open (rmsd.hpp,
+    // the state block of this pass: written by whoever closed the pass before it, or -- that pass was left open (pass_state.hpp,
     // pass_derive) -- worked out here by every workgroup for itself.  The scan blocks' counts are being decremented by this very
     // launch: no prefix is derived from them here, the next kernel that opens a pass makes its own
     int open_on, open_sel;
@@ -230,7 +223,7 @@ inline __global__ __launch_bounds__(LP_THREADS, LP_OCCUPANCY) void k_pass_chunks
             if (tid == nw - 1 && w0 + 1 <= ((first + L - 1) >> 6)) atomicAnd(&mbit_next[w0 + 1], open_sel ? w_copy1[1] : w_copy0[1]);
         }
         if (tid < nw) {
-            const int sh = first & 63;  // (extract64 of rmsd.hpp on the words already here)
+            const int sh = first & 63;  // (extract64 of pass_state.hpp on the words already here)
             auto join = [sh](const unsigned long long (&w)[2]) { return (w[0] >> sh) | (sh ? (w[1] << (64 - sh)) : 0ull); };
             unsigned long long m = open_sel ? join(w_copy1) : join(w_copy0), v = join(w_view);
             const int rem = L - 64 * tid;

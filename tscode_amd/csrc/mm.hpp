@@ -28,7 +28,7 @@
 //     apart, norms on both sides of the flush -- by value and in the kernels' own form of the compare (k_mm_screen_keeps) --, and through
 //     every route of the prune on ensembles for which h rmsd^2 equals the family-0 descriptor distance;
 //   * the norms' residuals 2^-14 each;
-//   * x against the exact scaled component: the fp32 rounding of sieve.hpp (3 * 2^-24 * 2 M' per difference) plus the float16 rounding,
+//   * x against the exact scaled component: the fp32 rounding of descriptor.hpp (3 * 2^-24 * 2 M' per difference) plus the float16 rounding,
 //     2^-11 M' (+ 2^-25 below the normal range) per operand: sqrt(S_exact) >= sqrt(S) - sqrt(KD) * eta.
 // The rounding to float16 moves the limit by about 2 sqrt(KD) 2^-10 M' sqrt(h) thr sigma -- a per cent or so more pairs than the fp32
 // screen lets through reach level 2, which drops exactly those.  As with the choice of basis: what passes where only moves work, never
@@ -40,12 +40,12 @@
 // never pass.  Nothing else is masked at screen time: what lies left of the diagonal or beyond a stop column is dropped at decode time.
 #pragma once
 #include "mm_record.hpp"
+#include "shapes.hpp"
 #include "sieve.hpp"
 
 namespace tsc {
 
-constexpr int MM_ROWS = 64;                 // rows per work item
-constexpr int MM_STEP = 16;                 // columns per step
+// (MM_ROWS, MM_STEP, MM_WAVES, MM16_LONG_SEGS and the default of TSC_MM_LEVEL2: shapes.hpp)
 constexpr int MM_QCAP = 2 * MM_ROWS * MM_STEP + 64;   // a step of 32 columns can add 64 x 32 pairs on top of a remainder below 64
 static_assert(MM_KD == KD && NFAM == 2 && DW == 2 * MM_KD, "the record layout of mm_record.hpp");
 
@@ -167,14 +167,6 @@ inline __global__ __launch_bounds__(64) void k_mm_screen_keeps(const _Float16 *_
 #ifndef TSC_MM_OCC
 #define TSC_MM_OCC 4
 #endif
-#ifndef TSC_MM_LEVEL2
-#define TSC_MM_LEVEL2 0   // 1: level 2 (below) where a pair is decoded in the 64-row kernels.  Measured at C4: 6.95 ms with it, 6.74 without -- the 7 %
-                          // more pairs that reach H cost less than its eight loads in front of every batch; the 16-row kernel never had it
-#endif
-#ifndef TSC_MM_WAVES
-#define TSC_MM_WAVES 4
-#endif
-constexpr int MM_WAVES = TSC_MM_WAVES;   // wavefronts (work items) per workgroup of the walked passes' kernel
 
 // The pair kernel with the screen on the matrix cores.  Grid (groups of 64 rows / 4, column segments); everything around the screen --
 // queue, evaluation stages, the fused apply and pass closing -- as in k_rmsd_sieve (sieve.hpp), with 64 rows per work item.
@@ -473,7 +465,7 @@ inline __global__ __launch_bounds__(64 * MM_WAVES, TSC_MM_OCC) void k_rmsd_sieve
             count_add(counters, unsigned(slot), CNT_EVALUATED, ev_total);
             count_add(counters, unsigned(slot), CNT_REMOVED, rm_total);
         }
-        if (!fa.tickets) {  // the pass is left open: the first kernel of the next one closes it behind the kernel boundary (rmsd.hpp, pass_derive)
+        if (!fa.tickets) {  // the pass is left open: the first kernel of the next one closes it behind the kernel boundary (pass_state.hpp, pass_derive)
             TSC_STAMP(5);
             return;
         }
@@ -495,11 +487,7 @@ inline __global__ __launch_bounds__(64 * MM_WAVES, TSC_MM_OCC) void k_rmsd_sieve
 #ifndef TSC_MM16_OCC
 #define TSC_MM16_OCC 4
 #endif
-// work items (wavefronts) per workgroup of the 16-row kernel: 2 where most workgroups of the grid have work (a workgroup keeps its slot until
-// its longest item is through: C3's k = 100 .. 2 passes 2 - 4 us shorter than with 4), 4 where most are empty and the launch is its dispatch
-// (C3's last pass: 28 us against 44) -- the host picks by the columns a row of the pass can have: more than MM16_LONG_SEGS segments of 512
-// (pass_plan.hpp: mm16_items_per_workgroup)
-constexpr int MM16_LONG_SEGS = 64;
+// (work items per workgroup of the 16-row kernel, 2 or 4: MM16_LONG_SEGS in shapes.hpp, pass_plan.hpp: mm16_items_per_workgroup)
 constexpr int MM16_BLOCKS = 128 / MM_STEP;   // 16-column blocks of a column tile
 
 template <bool F32, int MM16_WAVES>
@@ -774,7 +762,7 @@ inline __global__ __launch_bounds__(64 * MM16_WAVES, TSC_MM16_OCC) void k_rmsd_s
             count_add(counters, unsigned(tile), CNT_EVALUATED, ev_total);
             count_add(counters, unsigned(tile), CNT_REMOVED, rm_total);
         }
-        if (!fa.tickets) {  // the pass is left open: the first kernel of the next one closes it behind the kernel boundary (rmsd.hpp, pass_derive)
+        if (!fa.tickets) {  // the pass is left open: the first kernel of the next one closes it behind the kernel boundary (pass_state.hpp, pass_derive)
             TSC_STAMP(5);
             return;
         }

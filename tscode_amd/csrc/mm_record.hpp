@@ -8,7 +8,7 @@ namespace tsc {
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
-constexpr int MM_KD = 8;                    // components per family (sieve.hpp: KD), two families
+constexpr int MM_KD = 8;                    // components per family (descriptor.hpp: KD), two families
 constexpr int MM_REC_HALVES = 32;           // float16 per structure in the column records (64 bytes): per family [-2 x0 .. -2 x7 | 1 1 1 n0 | n1 n2 0 0] in four
                                             // chunks of 4, the two families' chunks SIDE BY SIDE (chunk g of family 0, chunk g of family 1: one 16-byte load
                                             // gives a lane its K slots 4 g .. 4 g + 3 of both)
@@ -24,7 +24,7 @@ __host__ __device__ inline float mm_scale(unsigned dmax_bits) {
     return f;
 }
 
-// The records of one structure from its 16 stored components (d[2k + fam], sieve.hpp): x = the nearest float16 of sigma * d, and
+// The records of one structure from its 16 stored components (d[2k + fam], descriptor.hpp): x = the nearest float16 of sigma * d, and
 // |x|^2 (of the ROUNDED vector: exact in float64) in three float16 pieces that leave 2^-14 at most.
 __device__ inline void mm_write_record(const float d[2 * MM_KD], float sigma, _Float16 *__restrict__ col_rec) {
 #pragma unroll

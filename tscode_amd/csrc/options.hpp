@@ -34,7 +34,7 @@ struct tsc_options {
     int early_basis = 1;                  // tsc_pipeline_dev: descriptor basis from a sample of unfiltered poses, on its own stream
     int clash_first = 0;                  // ... whose chain is enqueued in front of the clash launch (0) or behind it (1: rounds 1 - 3)
     int cull_tile_block = 256;            // culled passes dealt by row tiles: consecutive tiles of the sorted layout per rank and turn
-    int stage1_f32 = 1;                   // stage 1 of the pair kernels reads a float32 copy of the coordinates first (sieve.hpp: pair_stage1): 0 never, 2 always,
+    int stage1_f32 = 1;                   // stage 1 of the pair kernels reads a float32 copy of the coordinates first (pair_stages.hpp: pair_stage1): 0 never, 2 always,
                                           // 1: from 128 MB of heavy atoms on -- and from 8 MB on where the matrix-core kernels run (want_heavy32 below)
     int local_max_chunk = 384;            // longest chunk (structures) of a pass that the chunk-local kernel takes
     int local_pass = 1;                   // passes with short chunks run in one launch (local_pass.hpp)
@@ -42,7 +42,7 @@ struct tsc_options {
     int open_lds_blocks = 1 << 30;        // k_open_rows stages the scan-block prefix in LDS up to this many blocks (tests lower it to take the other path)
     int clash_fp32 = 1;                   // clash verdicts (max_clashes = 0, no counts): packed-fp32 minimum with fp64 fallback
     int clash_lanes = 1;                  // ... of two fragments, the smaller of at most 32 atoms, fused with the embed: one pose per lane (k_clash_lanes)
-    int deterministic_basis = 0;          // the descriptor basis from fixed-order sums (sieve.hpp, k_feature_moments): a sharded run sets it -- its ranks
+    int deterministic_basis = 0;          // the descriptor basis from fixed-order sums (descriptor_kernels.hpp, k_feature_moments): a sharded run sets it -- its ranks
                                           // must derive bit-identical descriptors (the culled passes deal the tiles of a layout sorted by them)
     int cull = 1;                         // large passes of the sieve lay their structures out along a Morton curve and skip tile pairs by bounding box (cull.hpp)
     double cull_min_pairs = 2.0e9;        // ... passes of at least this many pairs (n * (n / k) / 2)

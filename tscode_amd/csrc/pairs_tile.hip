@@ -1,4 +1,4 @@
-// pairs_tile.hip -- the register-tiled all-pairs kernel k_rmsd_tile<HP, 16> (rmsd.hpp), one instantiation per padded heavy-atom count.
+// pairs_tile.hip -- the register-tiled all-pairs kernel k_rmsd_tile<HP, 16> (rmsd_tile.hpp), one instantiation per padded heavy-atom count.
 // gfx950 only.  A translation unit of its own: the eight instantiations compile beside the other pair kernels, not behind them.
 #include "prune_host.hpp"
 

@@ -3,12 +3,12 @@
 // by value and make no HIP call: prune.hip launches what they say, tools/probe/pass_plan_check.cpp checks them without a GPU.
 #pragma once
 
-#include "host.hpp"
-#include "rmsd.hpp"
-#include "local_pass.hpp"
-#include "cull.hpp"
-#include "mm.hpp"
-#include "cull_mm.hpp"
+#include <algorithm>
+
+#include "common.hpp"
+#include "shapes.hpp"
+
+using namespace tsc;
 
 static_assert(OPT_LOCAL_MAX_CHUNK_MAX == LP_MAX_ROWS, "the range of \"local_max_chunk\" (options.hpp) ends at the longest chunk the chunk-local kernel takes");
 

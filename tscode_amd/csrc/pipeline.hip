@@ -2,6 +2,10 @@
 // gfx950 only.  There is deliberately no CPU implementation behind these entry points.
 #include "host.hpp"
 #include "scan.hpp"
+#include "prune_api.hpp"
+#include "descriptor_basis.hpp"
+#include "describe.hpp"
+#include "sample_moments.hpp"
 
 // --------------------------------------------------------------------------------------------------
 // pipeline
@@ -266,7 +270,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_pipeline_dev(tsc_ctx *
     TSC_TRY(s.get(size_t(n_poses), &act));
     TSC_TRY(s.get(1, &total));
     if (timed) TSC_HIP(hipEventRecord(ev[0], st));
-    // The descriptor basis of the prune (sieve.hpp) from a sample of the UNFILTERED poses, on its own stream beside the clash
+    // The descriptor basis of the prune (descriptor.hpp) from a sample of the UNFILTERED poses, on its own stream beside the clash
     // kernel: 3 small launches and a one-wavefront kernel (about 45 us of latency at C3) leave the critical path.  Any
     // orthonormal basis gives the same verdicts; poses that fail the clash check are as good a sample of the geometry.
     double *d_basis = nullptr;
@@ -293,7 +297,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_pipeline_dev(tsc_ctx *
             if (want_heavy32(c->opt, double(n_poses) * n_heavy * 24.0))
                 TSC_TRY(s.get(size_t(n_poses) * heavy32_pitch(n_heavy), &ext.heavy32));
         }
-        // one device: the sample is embedded and reduced by ONE kernel into accumulators the context keeps zero between runs (sieve.hpp,
+        // one device: the sample is embedded and reduced by ONE kernel into accumulators the context keeps zero between runs (sample_moments.hpp,
         // k_sample_moments); a sharded run takes the fixed-order sums instead (k_transform + k_feature_moments, "deterministic_basis")
         fused_sample = !c->opt.deterministic_basis && sample_moments_lds_bytes(ft.n_mols, n_heavy) <= 64 * 1024;
         if (fused_sample) {

@@ -2,9 +2,25 @@
 // gfx950 only.  There is deliberately no CPU implementation behind these entry points.
 #include "call.hpp"
 #include "prune_host.hpp"
+#include "rmsd.hpp"
+#include "descriptor_kernels.hpp"
+#include "describe.hpp"
+#include "descriptor_basis.hpp"
 
 // --------------------------------------------------------------------------------------------------
 // K3: pairs
+
+namespace tsc {
+inline __global__ __launch_bounds__(256) void k_rmsd_pairs(const double *__restrict__ heavy, int h, const int32_t *__restrict__ pairs,
+                                                     int64_t n_pairs, double *__restrict__ rmsd, double *__restrict__ maxdev) {
+    for (int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; k < n_pairs; k += int64_t(gridDim.x) * blockDim.x) {
+        double r, m;
+        rmsd_and_max_pair(heavy + int64_t(pairs[2 * k]) * h * 3, heavy + int64_t(pairs[2 * k + 1]) * h * 3, h, r, m);
+        rmsd[k] = r;
+        maxdev[k] = m;
+    }
+}
+}  // namespace tsc
 
 extern "C" __attribute__((visibility("default"))) int tsc_rmsd_pairs_dev(tsc_ctx *c, const double *heavy, int64_t n_structs, int h, const int32_t *pairs, int64_t n_pairs,
                                   double *rmsd, double *maxdev) {
@@ -158,7 +174,7 @@ static int build_descriptors(tsc_prune *p, const double *basis) {
         const int64_t stride = std::max<int64_t>(1, p->n / n_samples);
         double *q;
         TSC_TRY(s.get(basis_doubles(h), &q));
-        if (p->n < c->opt.pca_min_n) {  // small ensemble: the identity basis, one tiny launch (sieve.hpp)
+        if (p->n < c->opt.pca_min_n) {  // small ensemble: the identity basis, one tiny launch (descriptor_kernels.hpp)
             hipLaunchKernelGGL(k_identity_basis, dim3(1), dim3(256), 0, st, nf[0], nf[1], q, q + q_doubles);
             TSC_HIP(hipGetLastError());
         } else {
@@ -283,7 +299,7 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
         for (int slot = 0; slot < TSC_MAX_PASSES; ++slot)
             local_possible = local_possible || (pass_can_run(n, slot) && n / int64_t(KS[slot]) <= std::min(LP_MAX_ROWS, c->opt.local_max_chunk));
         if (!rc && c->opt.sieve_mm16 != 0 && c->opt.local_pass != 0 && local_possible) rc = palloc(p, size_t(n) * MM_REC_HALVES, &p->Drec);
-        // the float32 copy stage 1 reads (sieve.hpp, pair_stage1): from the embedding kernel where there was one, else converted here
+        // the float32 copy stage 1 reads (pair_stages.hpp, pair_stage1): from the embedding kernel where there was one, else converted here
         // (it pays where the gathers come from HBM: 41 MB of heavy atoms at C3 sit in the 256 MB infinity cache and the conversions cost the
         // VALU-bound kernel 2 %; at C4's 348 MB a step goes from 12.1 to 10.6 ms.  "stage1_f32": 0 never, 1 from 128 MB on, 2 always)
         if (!rc && want_heavy32(c->opt, double(n) * h * 24.0)) {

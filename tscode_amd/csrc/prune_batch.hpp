@@ -18,11 +18,11 @@
 //
 // Shape: a wavefront per row, 64 columns per step, lane = column (as k_tfd_first_similar); the cached keys of the step are found
 // first and only the columns in front of the first one are evaluated; a ballot finds the first similar column.  Verdicts come from
-// the device functions of the single-ensemble path (sieve.hpp: pair_H, rmsd.hpp: pair_verdict, exact_rmsd_maxdev).
+// the device functions of the single-ensemble path (pair_stages.hpp: pair_H, pair_math.hpp: pair_verdict, exact_rmsd_maxdev).
 #pragma once
 #include "prune_batch_plan.hpp"
-#include "rmsd.hpp"
-#include "sieve.hpp"
+#include "pair_math.hpp"
+#include "pair_stages.hpp"
 
 namespace tsc {
 

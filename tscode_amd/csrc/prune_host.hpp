@@ -2,8 +2,13 @@
 // units of their own (pairs_tile.hip, pairs_sieve.hip, pairs_sorted.hip: the template instantiations are most of the library's build time).
 #pragma once
 
+#include "cull_mm.hpp"
+#include "local_pass.hpp"
 #include "pass_plan.hpp"
+#include "pass_state.hpp"
+#include "prune_api.hpp"
 #include "prune_schedule.hpp"
+#include "rmsd_tile.hpp"
 #include "scan.hpp"
 
 // --------------------------------------------------------------------------------------------------
@@ -34,7 +39,7 @@ struct tsc_prune {
     int32_t *bsum = nullptr, *boff = nullptr, *tile_cmax = nullptr, *tile_done = nullptr;
     int n_blocks = 0;                      // scan blocks (SCAN_TILE structures each) the mask is ranked by
     unsigned long long *bits = nullptr;    // two bit copies of the mask (the pass in flight reads one, clears removed rows in the other)
-    unsigned long long *views = nullptr;   // cache view of every pass of the schedule, each followed by its summary (rmsd.hpp, CacheViews)
+    unsigned long long *views = nullptr;   // cache view of every pass of the schedule, each followed by its summary (pass_state.hpp, CacheViews)
     ViewPass *view_pass = nullptr;         // device: the pass of each view (chunk count, chunk size, its division constants)
     int view_of_slot[TSC_MAX_PASSES];      // schedule slot -> view index (-1: the pass can never run)
     int n_views = 0;
@@ -57,7 +62,7 @@ struct tsc_prune {
     float *Ds = nullptr, *cbox = nullptr, *rbox = nullptr;
     int32_t *cstruct = nullptr;                // the structure at every sorted position (cull_mm.hpp)
     _Float16 *Dhs = nullptr;                   // the float16 records of the matrix-core screen by sorted position (cull_mm.hpp)
-    float *heavy32 = nullptr;            // float32 copy of the heavy atoms for stage 1 of the pair kernels (sieve.hpp: pair_stage1)
+    float *heavy32 = nullptr;            // float32 copy of the heavy atoms for stage 1 of the pair kernels (pair_stages.hpp: pair_stage1)
     bool morton_sorted = false;          // the run's Morton order exists (made when the first pass is really culled)
     // rank-partitioned passes (rmsd.hpp, k_pass_merge): set by tsc_prune_set_partition
     int part_rank = 0, part_world = 1, part_min_chunks = 0;
@@ -132,7 +137,7 @@ static inline StepCtx step_ctx(const tsc_prune *p, bool range_close = false) {
     if (range_close) sc.exch_tail = p->exch + p->bit_words;
     return sc;
 }
-// the first kernel of the open pass closes the pass that was left open in front of it (rmsd.hpp, pass_derive), or has nothing to close
+// the first kernel of the open pass closes the pass that was left open in front of it (pass_state.hpp, pass_derive), or has nothing to close
 static inline DeriveArgs derive_args(const tsc_prune *p) {
     DeriveArgs d;
     memset(&d, 0, sizeof(d));

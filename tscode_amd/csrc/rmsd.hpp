@@ -1,409 +1,14 @@
-// rmsd.hpp -- K3: Kabsch-rotation RMSD (no centring) and the per-pass kernels of prune_conformers_rmsd.
-//
-// Reference: tscode/rmsd_pruning.py.  rmsd_and_max_numba(p, q) (:6-41) rotates p onto q with the optimal
-// PROPER rotation about the origin (SVD of H = p^T q with the det sign fix, no centring) and returns the
-// RMSD and the largest per-atom deviation.  Two formulations of that same optimum are used here:
-//
-//  * the FILTER (tile kernel, every pair): the optimum satisfies  h * rmsd^2 = Gp + Gq - 2 * lmax,  where
-//    lmax = s1 + s2 + sign(det H) * s3 is the largest root of the quartic  P(l) = l^4 + c2 l^2 + c1 l + c0,
-//    c2 = -2 |H|_F^2, c1 = -8 det H, c0 = |H|_F^4 - 4 |cof H|_F^2   (characteristic polynomial of Horn's
-//    4x4 quaternion matrix).  With L = (Gp + Gq - h thr^2) / 2, rmsd >= thr  <=>  lmax <= L, and since all
-//    four roots are real, L > lmax  <=>  P(L) > 0, P'(L) > 0, P''(L) > 0 (for L > 0).  A pair is REJECTED
-//    only when the three values exceed a rounding-error bound, so a rejection is always right; every
-//    other pair goes to
-//    (a second test of the same quartic ACCEPTS near-duplicates outright, see pair_verdict)
-//  * the EXACT path (explicit rotation): the quaternion of the optimal rotation is the top eigenvector of
-//    Horn's matrix (Newton for the eigenvalue + adjugate column, cyclic Jacobi when that degenerates, fp64);
-//    p is rotated, the residual is formed atom by atom and rmsd = sqrt(sum |d|^2 / h), maxdev = max |d| are
-//    compared with the thresholds exactly as the reference does (:75).  Values agree with the reference's
-//    LAPACK path to ~1e-13.
-//
-// No MFMA, no LDS tiles for q: a lane owns one column structure q_j in registers (<= 32 heavy atoms after
-// padding), the row structure p_i is wavefront-uniform and is read through the scalar cache, so the
-// inner loop is 9 v_fma_f64 per atom with one SGPR operand each.
+// rmsd.hpp -- K3: the per-pass kernels of prune_conformers_rmsd around its pair kernels, all launched by prune.hip alone (no other unit includes
+// this): the start of a run (k_init_run), a pass step of its own (k_pass_step), the rows of a pass (k_open_rows), the coordinate layouts of the
+// register-tiled kernel (k_compact_coords), apply and merge of a finished pass (k_apply_pass, k_range_open, k_pass_merge, k_views_summaries) and
+// the end of a run (k_export_run).  The arithmetic of a pair is in pair_math.hpp, the state of a run and the device functions that step it in
+// pass_state.hpp, the register-tiled pair kernel in rmsd_tile.hpp.
 #pragma once
-#include "common.hpp"
 #include "mm_record.hpp"
+#include "pass_state.hpp"
 #include "scan.hpp"
 
 namespace tsc {
-
-// ---------------------------------------------------------------------------------------------------
-// exact path
-
-// Cyclic Jacobi on a symmetric 4x4 (full storage, constant indices only so it lives in registers).
-// Returns the eigenvector of the largest eigenvalue in q[4].
-__device__ inline void top_eigvec4(double A[4][4], double q[4]) {
-    double V[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 16; ++sweep) {
-        double off = 0.0, dia = 0.0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            dia += A[i][i] * A[i][i];
-#pragma unroll
-            for (int j = i + 1; j < 4; ++j) off += A[i][j] * A[i][j];
-        }
-        if (!(off > 1e-30 * dia)) break;
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-#pragma unroll
-            for (int r = p + 1; r < 4; ++r) {
-                double apq = A[p][r];
-                if (apq != 0.0) {
-                    double theta = (A[r][r] - A[p][p]) / (2.0 * apq);
-                    double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    t = theta < 0.0 ? -t : t;
-                    double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {  // columns p, r of A and V
-                        double akp = A[k][p], akr = A[k][r];
-                        A[k][p] = c * akp - s * akr;
-                        A[k][r] = s * akp + c * akr;
-                        double vkp = V[k][p], vkr = V[k][r];
-                        V[k][p] = c * vkp - s * vkr;
-                        V[k][r] = s * vkp + c * vkr;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {  // rows p, r of A
-                        double apk = A[p][k], ark = A[r][k];
-                        A[p][k] = c * apk - s * ark;
-                        A[r][k] = s * apk + c * ark;
-                    }
-                }
-            }
-        }
-    }
-    double best = A[0][0];
-    q[0] = V[0][0], q[1] = V[1][0], q[2] = V[2][0], q[3] = V[3][0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k) {
-        bool b = A[k][k] > best;
-        best = b ? A[k][k] : best;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) q[i] = b ? V[i][k] : q[i];
-    }
-}
-
-// The same cyclic Jacobi on matrices that live in memory (LDS): A[16], V[16] row-major, dynamic indices.  The register
-// version above costs 64 VGPRs for its two matrices; a kernel that wants a small register footprint runs this one for
-// the (rare) degenerate pairs, one lane at a time on a 256-byte area per wavefront.
-__device__ inline void top_eigvec4_mem(double *A, double *V, double q[4]) {
-#pragma nounroll
-    for (int i = 0; i < 16; ++i) V[i] = (i % 5 == 0) ? 1.0 : 0.0;
-#pragma nounroll
-    for (int sweep = 0; sweep < 16; ++sweep) {
-        double off = 0.0, dia = 0.0;
-#pragma nounroll
-        for (int i = 0; i < 4; ++i) {
-            dia += A[5 * i] * A[5 * i];
-#pragma nounroll
-            for (int j = i + 1; j < 4; ++j) off += A[4 * i + j] * A[4 * i + j];
-        }
-        if (!(off > 1e-30 * dia)) break;
-#pragma nounroll
-        for (int p = 0; p < 3; ++p)
-#pragma nounroll
-            for (int r = p + 1; r < 4; ++r) {
-                const double apq = A[4 * p + r];
-                if (apq != 0.0) {
-                    const double theta = (A[5 * r] - A[5 * p]) / (2.0 * apq);
-                    double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    t = theta < 0.0 ? -t : t;
-                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma nounroll
-                    for (int k = 0; k < 4; ++k) {  // columns p, r of A and V
-                        const double akp = A[4 * k + p], akr = A[4 * k + r];
-                        A[4 * k + p] = c * akp - s * akr;
-                        A[4 * k + r] = s * akp + c * akr;
-                        const double vkp = V[4 * k + p], vkr = V[4 * k + r];
-                        V[4 * k + p] = c * vkp - s * vkr;
-                        V[4 * k + r] = s * vkp + c * vkr;
-                    }
-#pragma nounroll
-                    for (int k = 0; k < 4; ++k) {  // rows p, r of A
-                        const double apk = A[4 * p + k], ark = A[4 * r + k];
-                        A[4 * p + k] = c * apk - s * ark;
-                        A[4 * r + k] = s * apk + c * ark;
-                    }
-                }
-            }
-    }
-    int kb = 0;
-#pragma nounroll
-    for (int k = 1; k < 4; ++k)
-        if (A[5 * k] > A[5 * kb]) kb = k;
-    for (int i = 0; i < 4; ++i) q[i] = V[4 * i + kb];
-}
-
-// 3x3 determinant of the minor of the symmetric 4x4 A that drops row I and column J, with the cofactor sign.
-template <int I, int J>
-__device__ inline double cofactor4(const double (&A)[4][4]) {
-    constexpr int r0 = (I == 0) ? 1 : 0, r1 = (I <= 1) ? 2 : 1, r2 = (I <= 2) ? 3 : 2;
-    constexpr int c0 = (J == 0) ? 1 : 0, c1 = (J <= 1) ? 2 : 1, c2 = (J <= 2) ? 3 : 2;
-    const double d = A[r0][c0] * (A[r1][c1] * A[r2][c2] - A[r1][c2] * A[r2][c1]) -
-                     A[r0][c1] * (A[r1][c0] * A[r2][c2] - A[r1][c2] * A[r2][c0]) +
-                     A[r0][c2] * (A[r1][c0] * A[r2][c1] - A[r1][c1] * A[r2][c0]);
-    return ((I + J) & 1) ? -d : d;
-}
-
-// The explicit-rotation half of rmsd_and_max_numba (rmsd_pruning.py:19-39) given S = p^T q (:15) and the squared
-// norms Gp, Gq.  The quaternion of the optimal proper rotation is the top eigenvector of Horn's matrix N(S):
-//   fast path : largest root of the characteristic quartic by Newton from the upper bound (Gp+Gq)/2 (monotone), then
-//               the eigenvector as the best-conditioned column of adj(N - l I);
-//   fallback  : cyclic Jacobi, when the top eigenvalue is (nearly) degenerate and the adjugate collapses
-//               (collinear / planar-through-origin / mirror-symmetric cases).
-// A group of `lpp` consecutive lanes (a power of two, all converged, all holding the same S) may share one pair:
-// lane `sub` of the group then takes atoms sub, sub + lpp, ... of the residual loop and the group reduces.
-// Horn's matrix N(S), row-major into 16 doubles
-__device__ inline void horn_matrix(const double S[9], double *M) {
-    M[0] = S[0] + S[4] + S[8], M[5] = S[0] - S[4] - S[8], M[10] = -S[0] + S[4] - S[8], M[15] = -S[0] - S[4] + S[8];
-    M[1] = M[4] = S[5] - S[7], M[2] = M[8] = S[6] - S[2], M[3] = M[12] = S[1] - S[3];
-    M[6] = M[9] = S[1] + S[3], M[7] = M[13] = S[6] + S[2], M[11] = M[14] = S[5] + S[7];
-}
-
-// Fast way to the rotation quaternion e (not normalised): Newton for the top eigenvalue, then the best-conditioned column
-// of adj(N - l I).  Returns false when the top eigenvalue is (nearly) degenerate and the adjugate collapses (collinear /
-// planar-through-origin / mirror-symmetric cases): the caller then runs a Jacobi eigen-solver (top_eigvec4 / _mem).
-__device__ inline bool rotation_quaternion_fast(const double S[9], double Gp, double Gq, double e[4]) {
-    // characteristic quartic l^4 + c2 l^2 + c1 l + c0 (see the sign test below)
-    const double F = S[0] * S[0] + S[1] * S[1] + S[2] * S[2] + S[3] * S[3] + S[4] * S[4] + S[5] * S[5] + S[6] * S[6] + S[7] * S[7] + S[8] * S[8];
-    const double C0 = S[4] * S[8] - S[5] * S[7], C1 = S[5] * S[6] - S[3] * S[8], C2 = S[3] * S[7] - S[4] * S[6];
-    const double C3 = S[2] * S[7] - S[1] * S[8], C4 = S[0] * S[8] - S[2] * S[6], C5 = S[1] * S[6] - S[0] * S[7];
-    const double C6 = S[1] * S[5] - S[2] * S[4], C7 = S[2] * S[3] - S[0] * S[5], C8 = S[0] * S[4] - S[1] * S[3];
-    const double det = S[0] * C0 + S[1] * C1 + S[2] * C2;
-    const double CF = C0 * C0 + C1 * C1 + C2 * C2 + C3 * C3 + C4 * C4 + C5 * C5 + C6 * C6 + C7 * C7 + C8 * C8;
-    const double c2 = -2.0 * F, c1 = -8.0 * det, c0 = F * F - 4.0 * CF;
-    double lam = 0.5 * (Gp + Gq);
-    if (!(lam > 0.0)) return false;
-    for (int it = 0; it < 40; ++it) {
-        const double l2 = lam * lam;
-        const double P = l2 * l2 + c2 * l2 + c1 * lam + c0, P1 = 4.0 * l2 * lam + 2.0 * c2 * lam + c1;
-        if (!(P1 > 0.0)) return false;
-        const double dl = P / P1;
-        lam -= dl;
-        if (fabs(dl) <= 1e-15 * fabs(lam)) break;
-    }
-    double A[4][4];
-    {
-        double M[16];
-        horn_matrix(S, M);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) A[i][j] = M[4 * i + j] - (i == j ? lam : 0.0);
-    }
-    const double d0 = cofactor4<0, 0>(A), d1 = cofactor4<1, 1>(A), d2 = cofactor4<2, 2>(A), d3 = cofactor4<3, 3>(A);
-    double scale = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = i; j < 4; ++j) scale = fmax(scale, fabs(A[i][j]));
-    const double a0 = fabs(d0), a1 = fabs(d1), a2 = fabs(d2), a3 = fabs(d3);
-    const double best = fmax(fmax(a0, a1), fmax(a2, a3));
-    if (!(best > 1e-4 * scale * scale * scale)) return false;  // adj(A) = c v v^T with |c| large enough: any big column is v
-    if (a0 == best) {
-        e[0] = d0, e[1] = cofactor4<0, 1>(A), e[2] = cofactor4<0, 2>(A), e[3] = cofactor4<0, 3>(A);
-    } else if (a1 == best) {
-        e[0] = cofactor4<1, 0>(A), e[1] = d1, e[2] = cofactor4<1, 2>(A), e[3] = cofactor4<1, 3>(A);
-    } else if (a2 == best) {
-        e[0] = cofactor4<2, 0>(A), e[1] = cofactor4<2, 1>(A), e[2] = d2, e[3] = cofactor4<2, 3>(A);
-    } else {
-        e[0] = cofactor4<3, 0>(A), e[1] = cofactor4<3, 1>(A), e[2] = cofactor4<3, 2>(A), e[3] = d3;
-    }
-    return true;
-}
-
-// rmsd and max deviation of p rotated by the quaternion e (w, x, y, z; any length) against q (rmsd_pruning.py:29-39); lpp
-// lanes share the pair (atoms sub, sub + lpp, ...) and reduce with a butterfly
-__device__ inline void residual_rmsd_maxdev(const double *__restrict__ p, const double *__restrict__ q, int h, const double e[4], double &rmsd,
-                                            double &maxdev, int sub = 0, int lpp = 1) {
-    const double nn = 1.0 / sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2] + e[3] * e[3]);
-    const double w = e[0] * nn, x = e[1] * nn, y = e[2] * nn, z = e[3] * nn;
-    const double R00 = w * w + x * x - y * y - z * z, R01 = 2 * (x * y - w * z), R02 = 2 * (x * z + w * y);
-    const double R10 = 2 * (x * y + w * z), R11 = w * w - x * x + y * y - z * z, R12 = 2 * (y * z - w * x);
-    const double R20 = 2 * (x * z - w * y), R21 = 2 * (y * z + w * x), R22 = w * w - x * x - y * y + z * z;
-    double ss = 0.0, mx = 0.0;
-#pragma unroll 2
-    for (int a = sub; a < h; a += lpp) {  // :29-39
-        const double px = p[3 * a], py = p[3 * a + 1], pz = p[3 * a + 2];
-        const double dx = R00 * px + R01 * py + R02 * pz - q[3 * a];
-        const double dy = R10 * px + R11 * py + R12 * pz - q[3 * a + 1];
-        const double dz = R20 * px + R21 * py + R22 * pz - q[3 * a + 2];
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        ss += d2;
-        mx = d2 > mx ? d2 : mx;
-    }
-    for (int off = lpp >> 1; off > 0; off >>= 1) {
-        ss += __shfl_xor(ss, off);
-        mx = fmax(mx, __shfl_xor(mx, off));
-    }
-    rmsd = sqrt(ss / double(h));
-    maxdev = sqrt(mx);  // max_a sqrt(d2_a) == sqrt(max_a d2_a): sqrt is monotone
-}
-
-// The quaternion e (w, x, y, z; any length) of the optimal proper rotation of p onto q, given S = p^T q and the squared norms
-__device__ inline void exact_quaternion(const double S[9], double Gp, double Gq, double e[4]) {
-    if (!rotation_quaternion_fast(S, Gp, Gq, e)) {
-        double N[4][4], M[16];
-        horn_matrix(S, M);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) N[i][j] = M[4 * i + j];
-        top_eigvec4(N, e);
-    }
-}
-
-__device__ inline void exact_rmsd_maxdev(const double *__restrict__ p, const double *__restrict__ q, int h, const double S[9],
-                                         double Gp, double Gq, double &rmsd, double &maxdev, int sub = 0, int lpp = 1) {
-    double e[4];
-    exact_quaternion(S, Gp, Gq, e);
-    residual_rmsd_maxdev(p, q, h, e, rmsd, maxdev, sub, lpp);
-}
-
-// rmsd_and_max_numba (rmsd_pruning.py:6-41) for one pair; p, q point at h consecutive xyz triples.
-__device__ inline void rmsd_and_max_pair(const double *__restrict__ p, const double *__restrict__ q, int h, double &rmsd,
-                                         double &maxdev) {
-    double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Gp = 0.0, Gq = 0.0;
-    for (int a = 0; a < h; ++a) {  // :15 cov_mat = p.T @ q
-        const double px = p[3 * a], py = p[3 * a + 1], pz = p[3 * a + 2];
-        const double qx = q[3 * a], qy = q[3 * a + 1], qz = q[3 * a + 2];
-        S[0] += px * qx, S[1] += px * qy, S[2] += px * qz;
-        S[3] += py * qx, S[4] += py * qy, S[5] += py * qz;
-        S[6] += pz * qx, S[7] += pz * qy, S[8] += pz * qz;
-        Gp += px * px + py * py + pz * pz;
-        Gq += qx * qx + qy * qy + qz * qz;
-    }
-    exact_rmsd_maxdev(p, q, h, S, Gp, Gq, rmsd, maxdev);
-}
-
-inline __global__ __launch_bounds__(256) void k_rmsd_pairs(const double *__restrict__ heavy, int h, const int32_t *__restrict__ pairs,
-                                                     int64_t n_pairs, double *__restrict__ rmsd, double *__restrict__ maxdev) {
-    for (int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; k < n_pairs; k += int64_t(gridDim.x) * blockDim.x) {
-        double r, m;
-        rmsd_and_max_pair(heavy + int64_t(pairs[2 * k]) * h * 3, heavy + int64_t(pairs[2 * k + 1]) * h * 3, h, r, m);
-        rmsd[k] = r;
-        maxdev[k] = m;
-    }
-}
-
-// Statistics counters of a pass (one set per schedule slot).  Thousands of wavefronts report at the end of a kernel; same-address atomics
-// serialise at ~12 ns each (MI355X_MICROARCH.md, "fanin"), which for 10^4 reports is longer than the kernels
-// themselves, so the counters are spread over 64 buckets on separate 128-byte lines and summed on the host.
-constexpr int CNT_BUCKETS = 64;
-enum { CNT_FORMED = 0, CNT_EXACT = 1, CNT_SCREENED = 2, CNT_EVALUATED = 3, CNT_REMOVED = 4, CNT_WALK = 5 /* pairs inside the rows' ranges (k_open_rows, for k_cull_decide) */, CNT_WORDS = 16 };
-struct PassCounters {
-    unsigned long long w[CNT_BUCKETS][CNT_WORDS];
-};
-__device__ inline void count_add(PassCounters *c, unsigned bucket, int what, unsigned long long v) {
-    if (v) atomicAdd(&c->w[bucket & (CNT_BUCKETS - 1)][what], v);
-}
-
-// Device-resident control block of a prune run, one per schedule slot: written by whoever opens the slot's pass, read by its kernels, so
-// that nothing a pass reads changes while it is in flight.  The host enqueues every pass that COULD run (20 k < N) without
-// waiting for counts; the kernel that closes a pass evaluates the reference's gate `k == 1 or 20*k < count_nonzero(mask)`
-// (rmsd_pruning.py:192) for the next one on the device, and the kernels of a pass that is gated off return immediately.
-struct PruneState {
-    int n_active;  // count_nonzero(mask) after the last finished pass
-    int pass_on;   // gate of the pass in flight
-    int A;         // active structures entering the pass in flight (== n_active at its start)
-    unsigned ticket;  // blocks of k_apply_pass that have finished (the last one closes the pass)
-    int bitsel;    // which of the two bit copies of the mask the pass in flight READS (it clears the rows it removes in the other)
-    int cull_on;   // a pass that MAY be culled (cull.hpp): 1 = the sorted layout + bounding boxes run it, 0 = the ordered walk does
-                   // (k_cull_decide, from the rows' ranges: a cache that ends most rows early leaves the walk little to do)
-    int row_lo;    // rank-partitioned pass (tsc_prune_pass_range): active rank of this rank's local row 0; 0 in every other pass.
-                   // In such a pass A counts only the active structures of this rank's chunks and act / cend / best / Dc are
-                   // indexed by LOCAL row (global active rank - row_lo): the pair kernel sees an ensemble of A rows
-};
-struct PassRecord {  // one per schedule slot, read back once at the end of the run
-    long long k, n_before, n_after, formed, exact, screened, evaluated, removed;
-    int on, algo;
-};
-
-// "Every unit of this pass has finished": two-level arrival counter (same-address atomics serialise at ~12 ns each, so
-// thousands of arrivals go to PT_GROUPS counters on separate 128-byte lines and only the last of a group to the top).
-constexpr int PT_GROUPS = 64;
-struct PassTickets {  // zeroed by k_init_run and again by the wavefront that closes a pass
-    unsigned group[PT_GROUPS][32];
-    unsigned top;
-    unsigned pad[31];
-};
-// one lane calls this for unit `unit` of `n_units`; true for the arrival that completes the pass
-__device__ inline bool tickets_arrive(PassTickets *tk, unsigned unit, unsigned n_units, unsigned n_groups) {
-    const unsigned grp = unit % n_groups;
-    const unsigned in_group = (n_units - grp + n_groups - 1) / n_groups;
-    if (atomicAdd(&tk->group[grp][0], 1u) != in_group - 1) return false;
-    const unsigned groups = n_units < n_groups ? n_units : n_groups;
-    return atomicAdd(&tk->top, 1u) == groups - 1;
-}
-
-// The similarity cache of the reference (rmsd_pruning.py:65-76, :204) as one bitmap PER FUTURE PASS.  A row removed in a
-// pass leaves the key (a, b) = (first, first + (j - i)); a later pass hits that key only where `a` is the start of one of
-// ITS chunks and `b` lies inside that chunk -- and then exactly for the pairs with first + (j - i) == b.  The schedule of
-// a run is known when it starts, so the kernel that removes a row sets bit b in the view of every later pass the key
-// applies to (a handful of integer divisions per removed row; few keys apply anywhere) and no pass has to walk the key
-// list before it can start.  Behind the n-bit view of a pass sits its summary, one bit per 1024 view bits: the stop-column
-// search walks only non-empty blocks.
-constexpr int MAX_SLOTS = 18;
-struct ViewPass {  // one view's pass: k chunks of cs = n // k structures; a / cs == (a * magic) >> shift for every a < 2^31
-    int k, cs;
-    unsigned magic;
-    int shift;
-};
-struct CacheViews {
-    unsigned long long *views;  // [count][stride] words
-    long long stride;           // words per view: bit_words + summary words
-    int bit_words;
-    int n;                      // structures of the run
-    int first, count;           // views first .. count - 1 belong to the passes after the one in flight
-    const ViewPass *pass;       // [count]
-};
-// Division by an invariant: m = floor(2^(31+L) / d) + 1 with L = ceil(log2 d) divides every 31-bit dividend exactly
-// (Granlund & Montgomery 1994, theorem 4.2 with N = 31); m < 2^32.
-inline ViewPass view_pass(int n, int k) {
-    ViewPass v;
-    v.k = k, v.cs = n / k;
-    int L = 0;
-    while ((1ll << L) < (long long)v.cs) ++L;
-    v.magic = unsigned(((1ull << (31 + L)) / (unsigned long long)v.cs) + 1ull);
-    v.shift = 31 + L;
-    return v;
-}
-// A whole wavefront calls this with one removed row per lane (or none): key (a, b) of lane `removed`.  The loop over the later
-// passes is wave-uniform (their parameters come by scalar loads); the summary words, which every key of a chunk shares, take
-// one atomic per wavefront and word instead of one per key (same-address atomics serialise at ~12 ns each).
-__device__ inline void views_insert_wave(const CacheViews &cv, bool removed, int a, int b) {
-    if (__ballot(removed) == 0) return;
-    const int lane = threadIdx.x & 63;
-    for (int j = cv.first; j < cv.count; ++j) {
-        const ViewPass vp = cv.pass[j];
-        bool ok = false;
-        if (removed) {
-            const int c = int(((unsigned long long)unsigned(a) * vp.magic) >> vp.shift);
-            if (c * vp.cs == a && c < vp.k) ok = b < ((c == vp.k - 1) ? cv.n : vp.cs * (c + 1));
-        }
-        unsigned long long left = __ballot(ok);
-        if (!left) continue;
-        unsigned long long *v = cv.views + int64_t(j) * cv.stride;
-        if (ok) atomicOr(&v[b >> 6], 1ull << (b & 63));
-        while (left) {
-            const int leader = __ffsll((long long)left) - 1;
-            const int word = __shfl(b >> 16, leader);
-            const bool same = ok && (b >> 16) == word;
-            unsigned long long sb = same ? 1ull << ((b >> 10) & 63) : 0ull;
-            for (int off = 32; off > 0; off >>= 1) sb |= __shfl_xor(sb, off);
-            if (lane == leader) {
-                unsigned long long *ds = v + cv.bit_words + word;
-                if ((__hip_atomic_load(ds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & sb) != sb) atomicOr(ds, sb);
-            }
-            left &= ~__ballot(same);
-        }
-    }
-}
 
 // Initial state of a run: out_mask = ones (rmsd_pruning.py:182), empty cache (:183), zeroed records, counters, tickets.
 struct InitArgs {
@@ -480,7 +85,7 @@ inline __global__ __launch_bounds__(256) void k_init_run(InitArgs a) {
     }
     if (tid < a.n_views) a.view_pass[tid] = a.sched[tid];
     if (tid == 0) {
-        if (a.dmax_bits) *a.dmax_bits = 0;  // running maximum of the descriptor build (sieve.hpp)
+        if (a.dmax_bits) *a.dmax_bits = 0;  // running maximum of the descriptor build (describe.hpp)
         // the state block of every slot starts as that of the untouched ensemble, gated off; a slot's own is written by whoever opens it
         for (int s = 0; s < MAX_SLOTS; ++s) {
             PruneState *ss = a.st + s;
@@ -497,224 +102,10 @@ inline __global__ __launch_bounds__(256) void k_init_run(InitArgs a) {
     }
 }
 
-// Closes the pass in slot `prev` (sums its counters, updates n_active, re-ranks the scan blocks, flips the bit copy) and
-// opens the pass in slot `cur` (gate, A: the state block of that slot; its counters were zeroed by k_init_run).  prev / cur = -1: nothing to close / open.  Runs in ONE
-// WAVEFRONT: of the last unit of the closing pass to finish -- a row tile of the pair kernel, a block of k_apply_pass or of
-// k_pass_chunks -- or, where no pass precedes, of k_pass_step.
-struct StepArgs {
-    int prev, cur;
-    long long k_cur;
-    int algo_cur;
-    int prev_algo;  // >= 0: the kernel that really ran the closing pass (recorded in its PassRecord), -1: as opened
-};
-struct StepCtx {
-    PruneState *st;       // state block of the slot being closed (StepArgs::prev; of the slot being opened where there is none)
-    PruneState *st_next;  // state block of the slot being opened (StepArgs::cur), null where there is none
-    PassCounters *cnt;    // counters of the slot being closed
-    PassRecord *rec;
-    int32_t *bsum, *boff;
-    int n_blocks;
-    unsigned *tickets;  // every arrival counter of the run (PassTickets and the chunk-local kernel's: one per 128-byte line), zeroed on the way out
-    int ticket_lines;
-    unsigned long long *exch_tail;  // rank-partitioned pass only (else null): the last unit of this rank's share does not close the
-                                    // pass -- it leaves this rank's five statistics here, behind the removed-row bits of the exchange
-                                    // buffer, and k_pass_merge closes the pass after the ranks' buffers have been summed
-};
-
-__device__ inline void pass_step_wave(const StepCtx &sc, const StepArgs &sa) {
-    PruneState *st = sc.st;
-    const int lane = threadIdx.x & 63;
-    static_assert(CNT_BUCKETS == 64 && CNT_REMOVED == 4, "one bucket per lane, five statistics");
-    // the buckets and block counts were written by other CUs' atomics: read at the L2, not through this CU's cache.  All
-    // loads of the step are issued before the first is used (one memory round trip, not seven)
-    const int pass_on = st->pass_on, n_before = st->n_active, bitsel = st->bitsel;
-    unsigned long long v0 = __hip_atomic_load(&sc.cnt->w[lane][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned long long v1 = __hip_atomic_load(&sc.cnt->w[lane][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned long long v2 = __hip_atomic_load(&sc.cnt->w[lane][2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned long long v3 = __hip_atomic_load(&sc.cnt->w[lane][3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned long long v4 = __hip_atomic_load(&sc.cnt->w[lane][4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int c_first = lane < sc.n_blocks ? __hip_atomic_load(&sc.bsum[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    const bool closing = sa.prev >= 0 && pass_on != 0;
-    unsigned long long sum[CNT_REMOVED + 1] = {v0, v1, v2, v3, v4};
-    if (sc.exch_tail) {  // this rank's share of a rank-partitioned pass is done: statistics into the exchange buffer
-#pragma unroll
-        for (int w = 0; w <= CNT_REMOVED; ++w)
-            for (int off = 32; off > 0; off >>= 1) sum[w] += __shfl_xor(sum[w], off);
-        if (lane == 0 && pass_on != 0) {
-#pragma unroll
-            for (int w = 0; w <= CNT_REMOVED; ++w) sc.exch_tail[w] = sum[w];
-        }
-        for (int e = lane; e < sc.ticket_lines; e += 64) sc.tickets[32 * e] = 0;
-        return;
-    }
-    if (closing) {
-#pragma unroll
-        for (int w = 0; w <= CNT_REMOVED; ++w)
-            for (int off = 32; off > 0; off >>= 1) sum[w] += __shfl_xor(sum[w], off);
-    }
-    if (sa.prev >= 0) {
-        // (also behind a pass that was gated off: a chunk-local pass further back that was left open removed rows and wrote no prefix)
-        int run = 0;
-        for (int b0 = 0; b0 < sc.n_blocks; b0 += 64) {
-            const int b = b0 + lane;
-            const int c = b0 == 0 ? c_first : (b < sc.n_blocks ? __hip_atomic_load(&sc.bsum[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0);
-            int incl = c;
-            for (int off = 1; off < 64; off <<= 1) {
-                const int t = __shfl_up(incl, off);
-                if (lane >= off) incl += t;
-            }
-            if (b < sc.n_blocks) sc.boff[b] = run + incl - c;
-            run += __shfl(incl, 63);
-        }
-        if (lane == 0) sc.boff[sc.n_blocks] = run;
-    }
-    if (lane == 0) {
-        int n_active = n_before, sel = bitsel;
-        if (closing) {
-            PassRecord &r = sc.rec[sa.prev];
-            r.formed = (long long)sum[CNT_FORMED], r.exact = (long long)sum[CNT_EXACT], r.screened = (long long)sum[CNT_SCREENED];
-            r.evaluated = (long long)sum[CNT_EVALUATED], r.removed = (long long)sum[CNT_REMOVED];
-            n_active -= int(sum[CNT_REMOVED]);
-            r.n_after = n_active;
-            if (sa.prev_algo >= 0) r.algo = sa.prev_algo;
-            sel ^= 1;  // the copy the closing pass cleared its removed rows in is the current one now
-        }
-        int on = 0;
-        if (sa.cur >= 0) {
-            on = (sa.k_cur == 1 || 20 * sa.k_cur < (long long)n_active) ? 1 : 0;  // rmsd_pruning.py:192
-            PassRecord &r = sc.rec[sa.cur];
-            r.k = sa.k_cur, r.n_before = n_active, r.n_after = n_active, r.on = on, r.algo = sa.algo_cur;
-            r.formed = r.exact = r.screened = r.evaluated = r.removed = 0;
-        }
-        // (the state block of the next slot is written whole: nothing of the closing slot's is touched, so a wavefront of the closing
-        // pass that is still on its way reads what its siblings read)
-        if (PruneState *sn = sc.st_next)
-            sn->n_active = n_active, sn->A = n_active, sn->bitsel = sel, sn->row_lo = 0, sn->pass_on = on, sn->ticket = 0, sn->cull_on = 0;
-    }
-    // the counters belong to their slot and stay; the arrival counters are shared: the first word of every 128-byte line back to zero
-    for (int e = lane; e < sc.ticket_lines; e += 64) sc.tickets[32 * e] = 0;
-}
-
-// The same step without a closing wavefront: the pass in slot `prev` was LEFT OPEN by its last kernel (its tails end after they have
-// applied their rows and added to their counters), and the kernel boundary behind it makes its counters and the scan blocks' counts
-// final.  The first kernel of the pass in slot `cur` -- k_open_rows, k_pass_chunks -- derives what pass_step_wave would have written, in
-// every workgroup for itself, in the round trip it spends on the state block anyway; workgroup 0 also writes it down (state block of
-// `cur`, the records of both slots, the prefix of the scan blocks) for the kernels behind the next kernel boundary.  No workgroup reads
-// what workgroup 0 writes in the same launch.  prev_st = null: nothing to derive, the state block of `cur` has been written already.
-struct DeriveArgs {
-    const PruneState *prev_st;
-    const PassCounters *prev_cnt;
-    PassRecord *rec;
-    int prev, cur;
-    long long k_cur;
-    int algo_cur, prev_algo;  // (as in StepArgs)
-};
-struct Derived {
-    int n_active, pass_on, bitsel;
-};
-// One wavefront calls this.  bsum (optional): the scan blocks' counts, whose exclusive prefix goes to s_boff[0 .. n_blocks] (LDS) and,
-// from the writer, to boff.  st_cur: written by the writer only.
-__device__ inline Derived pass_derive(const DeriveArgs &d, PruneState *st_cur, bool writer, const int32_t *bsum, int n_blocks, int *s_boff, int32_t *boff) {
-    const int lane = threadIdx.x & 63;
-    const PruneState *sp = d.prev_st;
-    // one round trip: the state block, the removed-row buckets (all five statistics in the writer) and the first 64 block counts
-    const int prev_on = sp->pass_on, n_before = sp->n_active, sel_before = sp->bitsel;
-    unsigned long long sum[CNT_REMOVED + 1] = {0ull, 0ull, 0ull, 0ull, 0ull};
-    sum[CNT_REMOVED] = __hip_atomic_load(&d.prev_cnt->w[lane][CNT_REMOVED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (writer) {
-#pragma unroll
-        for (int w = 0; w < CNT_REMOVED; ++w) sum[w] = __hip_atomic_load(&d.prev_cnt->w[lane][w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    const int c_first = (bsum && lane < n_blocks) ? __hip_atomic_load(&bsum[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    for (int off = 32; off > 0; off >>= 1) sum[CNT_REMOVED] += __shfl_xor(sum[CNT_REMOVED], off);
-    if (writer) {
-#pragma unroll
-        for (int w = 0; w < CNT_REMOVED; ++w)
-            for (int off = 32; off > 0; off >>= 1) sum[w] += __shfl_xor(sum[w], off);
-    }
-    if (bsum) {
-        int run = 0;
-        for (int b0 = 0; b0 < n_blocks; b0 += 64) {
-            const int b = b0 + lane;
-            const int c = b0 == 0 ? c_first : (b < n_blocks ? __hip_atomic_load(&bsum[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0);
-            int incl = c;
-            for (int off = 1; off < 64; off <<= 1) {
-                const int t = __shfl_up(incl, off);
-                if (lane >= off) incl += t;
-            }
-            if (b < n_blocks) {
-                s_boff[b] = run + incl - c;
-                if (writer) boff[b] = run + incl - c;
-            }
-            run += __shfl(incl, 63);
-        }
-        if (lane == 0) {
-            s_boff[n_blocks] = run;
-            if (writer) boff[n_blocks] = run;
-        }
-    }
-    Derived out;
-    const bool closing = prev_on != 0;
-    out.n_active = closing ? n_before - int(sum[CNT_REMOVED]) : n_before;
-    out.bitsel = closing ? sel_before ^ 1 : sel_before;  // (a pass that was gated off hands both on unchanged)
-    out.pass_on = (d.k_cur == 1 || 20 * d.k_cur < (long long)out.n_active) ? 1 : 0;  // rmsd_pruning.py:192
-    if (writer && lane == 0) {
-        if (closing) {
-            PassRecord &r = d.rec[d.prev];
-            r.formed = (long long)sum[CNT_FORMED], r.exact = (long long)sum[CNT_EXACT], r.screened = (long long)sum[CNT_SCREENED];
-            r.evaluated = (long long)sum[CNT_EVALUATED], r.removed = (long long)sum[CNT_REMOVED];
-            r.n_after = out.n_active;
-            if (d.prev_algo >= 0) r.algo = d.prev_algo;
-        }
-        PassRecord &r = d.rec[d.cur];
-        r.k = d.k_cur, r.n_before = out.n_active, r.n_after = out.n_active, r.on = out.pass_on, r.algo = d.algo_cur;
-        r.formed = r.exact = r.screened = r.evaluated = r.removed = 0;
-        st_cur->n_active = out.n_active, st_cur->A = out.n_active, st_cur->bitsel = out.bitsel, st_cur->row_lo = 0, st_cur->pass_on = out.pass_on;
-        st_cur->ticket = 0, st_cur->cull_on = 0;
-    }
-    return out;
-}
-
 inline __global__ __launch_bounds__(64) void k_pass_step(StepCtx sc, StepArgs sa) { pass_step_wave(sc, sa); }
 
 // ---------------------------------------------------------------------------------------------------
 // per-pass helper kernels (the pass sequence is in prune.hip, tsc_prune_pass_local / tsc_prune_pass_finish)
-
-struct PassGeom {
-    int n;   // structures (< 2^31)
-    int k;   // chunks in this pass
-    int cs;  // chunk size n // k (rmsd_pruning.py:136)
-};
-
-__device__ inline void chunk_of(const PassGeom &g, int64_t i, int64_t &first, int64_t &last) {
-    int c = int(i) / g.cs;  // 32-bit division: n < 2^31
-    if (c >= g.k) c = g.k - 1;
-    first = int64_t(c) * g.cs;                        // :140
-    last = (c == g.k - 1) ? g.n : first + g.cs;       // :141-144
-}
-
-__device__ inline unsigned long long extract64(const unsigned long long *__restrict__ bits, int64_t start) {
-    int64_t w = start >> 6;
-    int sh = int(start & 63);
-    unsigned long long lo = bits[w] >> sh;
-    unsigned long long hi = sh ? (bits[w + 1] << (64 - sh)) : 0ull;
-    return lo | hi;
-}
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int SCAN_BLOCK_WORDS = 32;  // a scan block (scan.hpp: SCAN_TILE = 2048 structures) as 64-bit words of the mask's bit copy
-constexpr int DESC_WORDS = 16;        // floats per descriptor (sieve.hpp: DW)
-
-// position of the k-th (0-based) set bit of w (k < popcount(w))
-__device__ inline int select64(unsigned long long w, int k) {
-    int p = 0;
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const int c = __popcll((w >> p) & ((1ull << s) - 1ull));
-        if (k >= c) k -= c, p += s;
-    }
-    return p;
-}
 
 // Everything a pass needs per ROW, in one launch with no kernel in front of it: ONE LANE per active row r, one wavefront per 64 rows
 // = four row tiles of the pair kernel, four wavefronts per block.
@@ -1105,64 +496,6 @@ inline __global__ __launch_bounds__(256) void k_open_rows(PassGeom g, OpenArgs o
     if (__ballot(fin)) pass_step_wave(sc, next);
 }
 
-// The verdicts of up to 64 rows of a finished pass, one row per lane (a whole wavefront calls this): rows with a similar
-// column are removed (:113) -- mask byte, the bit in the copy the NEXT pass reads, the count of their scan block -- and
-// leave one cache key each (:76, appended after the pass at :204), entered into the views of the later passes; counts what
-// the reference's sequential scan would have evaluated.  best[] was written by other CUs' atomics: read at the L2.
-struct ApplyArgs {
-    PassGeom g;
-    const int32_t *act, *cend;
-    const int32_t *best;
-    uint8_t *mask;
-    unsigned long long *bits;
-    int bit_words;
-    int32_t *bsum;
-    int block_items;
-    CacheViews cv;
-    unsigned long long *exch;  // rank-partitioned pass (else null): removed rows are only NOTED here, one bit each; mask, bit copy and
-                               // block counts follow in k_pass_merge, from the sum of every rank's notes
-};
-__device__ inline void apply_wave_rows(const ApplyArgs &a, int sel, int r, bool valid, unsigned long long &ev_total, unsigned long long &rm_total) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long ev = 0;
-    bool removed = false;
-    int my_block = -1;
-    int64_t first = 0, delta = 0;
-    if (valid) {
-        const int b = __hip_atomic_load(&a.best[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (b != INT_MAX) {
-            const int64_t i = a.act[r], j = a.act[b];
-            int64_t last;
-            chunk_of(a.g, i, first, last);
-            if (a.exch) {
-                atomicOr(&a.exch[i >> 6], 1ull << (i & 63));
-            } else {
-                a.mask[i] = 0;
-                atomicAnd(&a.bits[size_t(sel ^ 1) * a.bit_words + (i >> 6)], ~(1ull << (i & 63)));
-                my_block = int(i / a.block_items);
-            }
-            delta = j - i;
-            removed = true;
-            ev = (unsigned long long)(b - r);  // columns r+1 .. b were evaluated
-        } else {
-            ev = (unsigned long long)(a.cend[r] - r - 1);  // every active column before the stop column
-        }
-    }
-    // the per-block counts follow the mask: one atomic per (wavefront, scan block) -- the removed rows of a wavefront fall
-    // into one or two blocks, and thousands of single decrements of two cache lines would serialise
-    for (unsigned long long left = __ballot(removed && my_block >= 0); left;) {
-        const int l = __ffsll((long long)left) - 1;
-        const int blk = __shfl(my_block, l);
-        const unsigned long long same = __ballot(removed && my_block == blk);
-        if (lane == l) atomicSub(&a.bsum[blk], __popcll(same));
-        left &= ~same;
-    }
-    views_insert_wave(a.cv, removed, int(first), int(first + delta));
-    const int n_rm = __popcll(__ballot(removed));
-    for (int off = 32; off > 0; off >>= 1) ev += __shfl_down(ev, off);
-    ev_total += ev, rm_total += (unsigned long long)n_rm;
-}
-
 // Gather the active structures into the two layouts the tile kernel reads:
 //   Xr[r][HP3]   row-major, zero-padded to HP atoms  (row structures: wavefront-uniform scalar reads)
 //   Xc[d][ld]    coordinate-major                    (column structures: lane = column, coalesced)
@@ -1198,221 +531,6 @@ inline __global__ __launch_bounds__(256) void k_compact_coords(const double *__r
             g += v * v;
         }
         G[r0 + threadIdx.x] = g;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// the tile kernel
-
-struct TileArgs {
-    long long ld;     // leading dimension of Xc (structures per coordinate row)
-    int h;
-    int tile_begin;   // first tile of this rank
-    int tile_stride;  // world size (row tiles are dealt round-robin to ranks)
-    int seg_cols;     // columns per grid.y segment (multiple of 64)
-    double thr, maxdev_thr;
-    double half_h_thr2;  // h * thr^2 / 2
-};
-
-// Fast tests on the characteristic quartic of Horn's matrix (described at the top of this file).
-//   PAIR_DISSIMILAR  certainly rmsd >= thr:  P, P', P'' at L = (Gp + Gq - h thr^2) / 2 all exceed their rounding bounds, so
-//                    L lies above the largest root l1 and h rmsd^2 = Gp + Gq - 2 l1 > h thr^2;
-//   PAIR_SIMILAR     certainly similar (near-duplicates, the bulk of what a prune removes): with x = (Gp + Gq) / 2 - 2 thr^2 > 0,
-//                    P''(x) > 0 and P'(x) > 0 put x above the largest root of P' (the roots of P'' are +-sqrt(|H|_F^2 / 3) and
-//                    those of P' interlace them; the other region with both signs lies below the negative root of P''),
-//                    hence above the second root l2 of P, and P(x) < 0 then puts it below the largest root l1 (all with
-//                    rounding bounds), so h rmsd^2 = Gp + Gq - 2 l1 < 4 thr^2: rmsd < 2 thr / sqrt(h) <= thr
-//                    for h >= 4, and maxdev <= sqrt(sum dev^2) = sqrt(h) rmsd < 2 thr -- both conditions of
-//                    rmsd_pruning.py:75 hold without forming the rotation (needs maxdev_thr == 2 thr, as :95 sets it);
-//   PAIR_UNDECIDED   everything else takes the explicit-rotation path.
-enum { PAIR_DISSIMILAR = 0, PAIR_SIMILAR = 1, PAIR_UNDECIDED = 2 };
-
-struct Quartic {
-    double F, CF, c2, c1, c0;
-};
-__device__ inline Quartic horn_quartic(const double H[9]) {
-    Quartic q;
-    q.F = H[0] * H[0] + H[1] * H[1] + H[2] * H[2] + H[3] * H[3] + H[4] * H[4] + H[5] * H[5] + H[6] * H[6] + H[7] * H[7] + H[8] * H[8];
-    const double C0 = H[4] * H[8] - H[5] * H[7], C1 = H[5] * H[6] - H[3] * H[8], C2 = H[3] * H[7] - H[4] * H[6];
-    const double C3 = H[2] * H[7] - H[1] * H[8], C4 = H[0] * H[8] - H[2] * H[6], C5 = H[1] * H[6] - H[0] * H[7];
-    const double C6 = H[1] * H[5] - H[2] * H[4], C7 = H[2] * H[3] - H[0] * H[5], C8 = H[0] * H[4] - H[1] * H[3];
-    const double det = H[0] * C0 + H[1] * C1 + H[2] * C2;
-    q.CF = C0 * C0 + C1 * C1 + C2 * C2 + C3 * C3 + C4 * C4 + C5 * C5 + C6 * C6 + C7 * C7 + C8 * C8;
-    q.c2 = -2.0 * q.F, q.c1 = -8.0 * det, q.c0 = q.F * q.F - 4.0 * q.CF;
-    return q;
-}
-// Rounding bound of the quartic tests: every comparison below is `value > kappa * (sum of the magnitudes of its terms)`.
-// Derivation (u = 2^-53, gamma = h u, S^2 = Gp Gq, rho = ((Gp + Gq) / 2) / L >= S / L, L = the test point):
-//   * H: an h-term fma chain per entry, |dH_ij| <= gamma sum_a |p_ai q_aj| <= gamma sqrt(sum p_ai^2 sum q_aj^2), so
-//     |dH|_F <= gamma S, and |H|_F <= S (Cauchy-Schwarz);
-//   * F = |H|_F^2:  dF <= 2 |H| |dH| <= 2 gamma S^2;  det: d det <= |cof H|_F |dH|_F <= gamma S^3;  CF = |cof H|_F^2:
-//     dCF <= 2 |cof| 2 |H| |dH| <= 4 gamma S^4;  hence d(c2 L^2) <= 4 gamma S^2 L^2, d(c1 L) <= 8 gamma S^3 L,
-//     d(c0) = 2 F dF + 4 dCF <= 20 gamma S^4: together <= 32 gamma rho^4 L^4 in P, and by the same steps
-//     <= 4 gamma rho^3 (4 L^3) in P' and <= gamma rho^2 (6 L^2) in P'';
-//   * the test point itself: Gp, Gq are 3h-term sums, |dL| <= 3 gamma (Gp + Gq) / 2 = 3 gamma rho L, which moves P by at most
-//     |P'| |dL| <= 12 gamma rho L^4 (and P', P'' by less, relative to their term sums);
-//   * evaluating the three polynomials: a few u times the term sums.
-// All of it is below 64 h u rho^4 times the respective term sum (each sum contains L^4, 4 L^3, 6 L^2).  kappa is that
-// bound, and never less than the 1e-12 the recorded runs were made with (which it exceeds only beyond about 140 heavy atoms
-// or where the structures sit so close to the origin that L is small against Gp + Gq): a larger kappa only hands more pairs
-// to the explicit-rotation path, it cannot change a verdict.  Structures far from the origin (the path never centres,
-// rmsd_pruning.py:7-41) make Gp, Gq and L grow with the square of the offset while the margin P(L) ~ P'(l1) (L - l1) keeps
-// L - l1 = h (rmsd^2 - thr^2) / 2: the tests decide less and less (at 10^4 A nothing) and everything takes the exact path.
-// H FORMED FROM A FLOAT32 COPY of the coordinates (sieve.hpp, pair_H32: the first look at a pair that passed the screen reads half the
-// bytes): p32 = p (1 + d), |d| <= 2^-24, products of two floats are exact in float64 and summed there, so
-// |dH_ij| <= (2^-23 + 2^-48 + h u) sum_a |p_ai q_aj| and |dH|_F <= gamma32 S with gamma32 = 2.0001 * 2^-24 + h u.  The derivation above goes
-// through with that gamma in the H terms (32 gamma32 rho^4) while the test point keeps its float64 bound (12 h u rho): below
-// 64 gamma32 rho^4 together.  Such a test decides every pair whose margin is not tiny (|P(L)| is some 1e-3 .. 1e-1 of its term sum for
-// the pairs a prune meets, kappa about 8e-6); the others are formed again from the float64 coordinates.
-constexpr double QUARTIC_KAPPA_MIN = 1e-12;
-__device__ inline double quartic_gamma64(int h) { return 1.1102230246251565e-16 * double(h); }
-__device__ inline double quartic_gamma32(int h) { return 2.0001 * 5.9604644775390625e-08 + 1.1102230246251565e-16 * double(h); }
-__device__ inline double quartic_kappa_g(double gamma, double half_sum, double L) {
-    const double rho = half_sum / L, r2 = rho * rho;          // callers test L > 0 themselves
-    const double k = 64.0 * gamma * r2 * r2;
-    return (k > QUARTIC_KAPPA_MIN) ? k : QUARTIC_KAPPA_MIN;  // (a NaN k -- L == 0 -- keeps the minimum; the L > 0 test fails then)
-}
-__device__ inline double quartic_kappa(int h, double half_sum, double L) { return quartic_kappa_g(quartic_gamma64(h), half_sum, L); }
-
-__device__ inline bool quartic_above_top_root(const Quartic &q, double L, double kappa) {
-    const double L2 = L * L;
-    const double t4 = L2 * L2, t2 = q.c2 * L2, t1 = q.c1 * L;
-    const double P = t4 + t2 + t1 + q.c0;
-    const double eP = kappa * (t4 + fabs(t2) + fabs(t1) + fabs(q.c0) + 4.0 * q.CF + q.F * q.F);
-    const double P1 = 4.0 * L2 * L + 2.0 * q.c2 * L + q.c1;
-    const double e1 = kappa * (4.0 * L2 * fabs(L) + 2.0 * fabs(q.c2 * L) + fabs(q.c1));
-    const double P2 = 6.0 * L2 + q.c2;
-    const double e2 = kappa * (6.0 * L2 + fabs(q.c2));
-    return (L > 0.0) && (P > eP) && (P1 > e1) && (P2 > e2);
-}
-__device__ inline bool quartic_between_top_roots(const Quartic &q, double x, double kappa) {
-    const double x2 = x * x;
-    const double t4 = x2 * x2, t2 = q.c2 * x2, t1 = q.c1 * x;
-    const double P = t4 + t2 + t1 + q.c0;
-    const double eP = kappa * (t4 + fabs(t2) + fabs(t1) + fabs(q.c0) + 4.0 * q.CF + q.F * q.F);
-    const double P1 = 4.0 * x2 * x + 2.0 * q.c2 * x + q.c1;
-    const double e1 = kappa * (4.0 * x2 * fabs(x) + 2.0 * fabs(q.c2 * x) + fabs(q.c1));
-    const double P2 = 6.0 * x2 + q.c2;
-    const double e2 = kappa * (6.0 * x2 + fabs(q.c2));
-    return (x > 0.0) && (P2 > e2) && (P1 > e1) && (P < -eP);
-}
-
-// half_sum = (Gp + Gq) / 2, L = half_sum - h thr^2 / 2, h = atoms per structure
-__device__ inline bool certainly_dissimilar(const double H[9], double L, double half_sum, int h) {
-    return quartic_above_top_root(horn_quartic(H), L, quartic_kappa(h, half_sum, L));
-}
-
-// half_sum = (Gp + Gq) / 2, half_h_thr2 = h thr^2 / 2, two_thr2 = 2 thr^2 (pass a negative two_thr2 to switch the
-// near-duplicate test off: h < 4, or a maxdev threshold other than 2 thr)
-__device__ inline int pair_verdict_g(const double H[9], double half_sum, double half_h_thr2, double two_thr2, double gamma) {
-    const Quartic q = horn_quartic(H);
-    const double L = half_sum - half_h_thr2;
-    if (quartic_above_top_root(q, L, quartic_kappa_g(gamma, half_sum, L))) return PAIR_DISSIMILAR;
-    const double x = half_sum - two_thr2;
-    if (two_thr2 > 0.0 && quartic_between_top_roots(q, x, quartic_kappa_g(gamma, half_sum, x))) return PAIR_SIMILAR;
-    return PAIR_UNDECIDED;
-}
-__device__ inline int pair_verdict(const double H[9], double half_sum, double half_h_thr2, double two_thr2, int h) {
-    return pair_verdict_g(H, half_sum, half_h_thr2, two_thr2, quartic_gamma64(h));
-}
-
-// One wavefront = one work item = (row tile of TI consecutive active rows) x (one column segment).
-// Lane = column.  For every 64-column tile: load q_j into registers, then for each live row accumulate
-// H = p_i^T q_j, run the sign test, remember survivors as per-lane bits; after the row loop the few
-// survivors take the exact path and the smallest similar column of each row goes to best[] (atomicMin).
-// A row stops being visited once it has a similar column to its left (the reference returns at the
-// first similar column, rmsd_pruning.py:75-77).
-template <int HP, int TI>
-inline __global__ __launch_bounds__(256, 2) void k_rmsd_tile(const double *__restrict__ Xr, const double *__restrict__ Xc,
-                                                       const double *__restrict__ G, const int32_t *__restrict__ cend,
-                                                       int32_t *__restrict__ best, PassCounters *__restrict__ counters,
-                                                       const PruneState *__restrict__ st, TileArgs a) {
-    // Xr [n_active][HP*3] row structures; Xc [HP*3][ld] column structures; G [ld] squared norms;
-    // cend [n_active] exclusive column bound of each row; best [n_active] atomicMin target (INT_MAX = none);
-    // counters[0] pairs computed, counters[1] pairs sent to the exact path.
-    static_assert(TI <= 32, "row liveness is a 32-bit lane mask");
-    constexpr int HP3 = HP * 3;
-    const int lane = threadIdx.x & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (st->pass_on == 0) return;
-    const int n_active = st->A;
-    const int slot = blockIdx.x * 4 + wid;
-    const int tile = a.tile_begin + slot * a.tile_stride;
-    const int r0 = tile * TI;
-    if (r0 >= n_active) return;
-    const int nrows = min(TI, n_active - r0);
-    const int seg_lo = ((r0 + 1) & ~63) + int(blockIdx.y) * a.seg_cols;
-    const int seg_hi = seg_lo + a.seg_cols;
-
-    int my_cend = 0, my_best = 0;
-    if (lane < nrows) {
-        my_cend = cend[r0 + lane];
-        my_best = __hip_atomic_load(&best[r0 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    const bool live0 = lane < nrows && my_cend > max(r0 + lane + 1, seg_lo) && my_best >= seg_lo;
-    unsigned alive = unsigned(__ballot(live0));
-    if (!alive) return;
-    int cmax = live0 ? my_cend : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cmax = max(cmax, __shfl_xor(cmax, off));
-    cmax = min(__builtin_amdgcn_readfirstlane(cmax), seg_hi);
-
-    unsigned long long n_computed = 0, n_cand = 0;
-    for (int c0 = seg_lo; c0 < cmax && alive; c0 += 64) {
-        const int col = c0 + lane;
-        double q[HP3];
-        {
-            const double *xc = Xc + col;
-#pragma unroll
-            for (int d = 0; d < HP3; ++d, xc += a.ld) q[d] = *xc;
-        }
-        const double Gq = G[col];
-        unsigned mycand = 0;  // bit t: this lane's column survived the sign test against row t
-        unsigned candrows = 0;
-        for (int t = 0; t < nrows; ++t) {
-            if (!((alive >> t) & 1u)) continue;
-            const int r = r0 + t;
-            const int ce = __builtin_amdgcn_readlane(my_cend, t);
-            if (ce <= c0 || r >= c0 + 63) continue;
-            const double *__restrict__ pr = Xr + int64_t(r) * HP3;
-            double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int k = 0; k < HP; ++k) {
-                const double px = pr[3 * k], py = pr[3 * k + 1], pz = pr[3 * k + 2];
-                H[0] = fma(px, q[3 * k], H[0]), H[1] = fma(px, q[3 * k + 1], H[1]), H[2] = fma(px, q[3 * k + 2], H[2]);
-                H[3] = fma(py, q[3 * k], H[3]), H[4] = fma(py, q[3 * k + 1], H[4]), H[5] = fma(py, q[3 * k + 2], H[5]);
-                H[6] = fma(pz, q[3 * k], H[6]), H[7] = fma(pz, q[3 * k + 1], H[7]), H[8] = fma(pz, q[3 * k + 2], H[8]);
-            }
-            const double L = 0.5 * (G[r] + Gq) - a.half_h_thr2;
-            const bool valid = col > r && col < ce;
-            const bool cand = valid && !certainly_dissimilar(H, L, 0.5 * (G[r] + Gq), a.h);
-            const unsigned long long vm = __ballot(valid);
-            n_computed += __popcll(vm);
-            if (__ballot(cand)) candrows |= 1u << t;
-            mycand |= cand ? (1u << t) : 0u;
-        }
-        // exact path for the survivors of this column tile
-        while (candrows) {
-            const int t = __ffs(candrows) - 1;
-            candrows &= candrows - 1;
-            const int r = r0 + t;
-            bool sim = false;
-            if ((mycand >> t) & 1u) {
-                double rm, md;
-                rmsd_and_max_pair(Xr + int64_t(r) * HP3, Xr + int64_t(col) * HP3, a.h, rm, md);
-                sim = rm < a.thr && md < a.maxdev_thr;  // rmsd_pruning.py:75
-            }
-            n_cand += __popcll(__ballot((mycand >> t) & 1u));
-            const unsigned long long sm = __ballot(sim);
-            if (sm) {
-                if (lane == 0) atomicMin(&best[r], c0 + __ffsll((long long)sm) - 1);
-                alive &= ~(1u << t);
-            }
-        }
-    }
-    if (lane == 0) {
-        count_add(counters, unsigned(slot), CNT_FORMED, n_computed);
-        count_add(counters, unsigned(slot), CNT_EXACT, n_cand);
     }
 }
 
@@ -1463,24 +581,9 @@ inline __global__ __launch_bounds__(256) void k_apply_pass(ApplyArgs a, StepCtx 
 // blocks' counts and prefix, the record, the gate of rmsd_pruning.py:192 for the next pass and -- when that one is
 // rank-partitioned too -- which of the active structures are this rank's rows in it.
 // The cache keys of the removed rows stay with the rank that removed them: a key (a, b) can only be hit by a later pass in
-// the chunk that starts at a (rmsd.hpp, CacheViews), and the chunk that starts at a belongs to the same rank in every
+// the chunk that starts at a (pass_state.hpp, CacheViews), and the chunk that starts at a belongs to the same rank in every
 // rank-partitioned pass.  Before the first pass that is NOT partitioned this way the host sums the cache views of the
 // remaining passes over the ranks once (disjoint bits again) and k_views_summaries rebuilds their summary words.
-
-// Active structures before position pos (0 <= pos <= n) in the bit copy X: the prefix of its scan block + the set bits of
-// the block below it.  One wavefront calls this.
-__device__ inline int rank_below_wave(const int32_t *__restrict__ boff, const unsigned long long *__restrict__ X, int n_blocks, int n_active, int64_t pos) {
-    const int lane = threadIdx.x & 63;
-    const int bf = int(pos / (64 * SCAN_BLOCK_WORDS)), off = int(pos - int64_t(bf) * (64 * SCAN_BLOCK_WORDS));
-    int cnt = 0;
-    if (bf < n_blocks && lane < SCAN_BLOCK_WORDS) {
-        const int below = off - 64 * lane;
-        const unsigned long long m = below >= 64 ? ~0ull : (below > 0 ? (1ull << below) - 1ull : 0ull);
-        cnt = m ? __popcll(X[size_t(bf) * SCAN_BLOCK_WORDS + lane] & m) : 0;
-    }
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-    return (bf < n_blocks ? boff[bf] : n_active) + cnt;
-}
 
 // The rows of this rank in the OPEN pass: the active structures of [s_lo, s_hi) (whole chunks of that pass).  Needed as a
 // launch of its own only where no k_pass_merge precedes the pass (the first pass of a run).

@@ -15,13 +15,13 @@
 // j > j* evaluated in the same batch are dropped, as the reference never computes them.  Workgroups share nothing: chunks are
 // disjoint, and the cache bits of a row sit in whole 32-bit words of that row.
 //
-// The Kabsch step is the exact path of rmsd.hpp (Horn's quaternion: Newton + adjugate, Jacobi when that degenerates) on the
+// The Kabsch step is the exact path of pair_math.hpp (Horn's quaternion: Newton + adjugate, Jacobi when that degenerates) on the
 // 3x3 correlation S = ref_sub^T coord_sub reduced across the wave; the quaternion rotation of rot_mat_from_pointer_dev
 // (csearch.hpp) turns the atoms.
 #pragma once
 #include "common.hpp"
 #include "csearch.hpp"
-#include "rmsd.hpp"
+#include "pair_math.hpp"
 
 namespace tsc {
 

@@ -1,24 +1,6 @@
-// sieve.hpp -- K3 with a rotation-invariant descriptor sieve in front of the Kabsch evaluation.
-//
-// rmsd_and_max_numba (tscode/rmsd_pruning.py:6-41) rotates p onto q ABOUT THE ORIGIN (it never centres).
-// Write dev_a = |p_a R - q_a| for the deviation of atom a after the optimal rotation R; h * rmsd^2 = sum_a dev_a^2.
-// Two families of quantities are untouched by R, and each bounds the deviations from below:
-//
-//   family 0  atom norms:           n_a(x) = |x_a|                      dev_a           >= | n_a(p) - n_a(q) |
-//   family 1  atom-pair distances:  d_ab(x) = |x_a - x_b|               dev_a + dev_b   >= | d_ab(p) - d_ab(q) |
-//             over DISJOINT pairs (a, b = a + h/2), so that             dev_a^2 + dev_b^2 >= (d_ab(p) - d_ab(q))^2 / 2
-//
-// Hence, with f0(x) = (n_a)_a and f1(x) = (d_ab / sqrt 2)_(a,b):   h * rmsd(p,q)^2 >= |f(p) - f(q)|^2 >= |Q^T (f(p) - f(q))|^2
-// for either family and any Q with orthonormal columns.  A pair for which one of the two right-hand sides exceeds
-// h * thr^2 cannot have rmsd < thr (:75) and is dropped without forming H = p^T q.  Q (KD columns per family) spans the
-// leading principal axes of the feature vectors of the ensemble; the choice of Q (and of the atom pairs) only
-// changes how many pairs are dropped, never a verdict.  Everything that survives takes the same sign test and
-// explicit-rotation path as the register-tiled kernel (rmsd.hpp).
-//
-// The screen runs in fp32 on mean-centred descriptors.  With M the largest |component| of the ensemble, every computed
-// difference is within eta = 3 * 2^-24 * 2M of the exact one (rounding of both operands and of the subtraction), so
-// s_exact >= s32 (1 - 2^-20) - 2 eta sqrt(KD s32); screen_limit32 turns h thr^2 into the fp32 limit above which that
-// lower bound certainly exceeds h thr^2.  Pairs in the sliver between the two limits are simply not dropped.
+// sieve.hpp -- K3 with a rotation-invariant descriptor sieve (descriptor.hpp) in front of the Kabsch evaluation (pair_stages.hpp): the
+// packed-fp32 pair kernel of a pass and what the other pair kernels share with it (SieveArgs, FusedApply).  k_rmsd_sieve is a template:
+// pairs_sieve.hip and pairs_sieve_plain.hip instantiate it, including this header emits nothing.
 //
 // Pass kernel (k_rmsd_sieve): one wavefront = 16 rows x one column segment, lane = CPL columns of a tile.
 //   screen : descriptors are read by position from a copy in active order that k_open_rows writes on its way (one float4
@@ -35,634 +17,11 @@
 // Any number of heavy atoms is supported (no register-resident structure).
 #pragma once
 #include "common.hpp"
-#include "embed_clash.hpp"
-#include "rmsd.hpp"
+#include "descriptor.hpp"
+#include "pair_stages.hpp"
+#include "pass_state.hpp"
 
 namespace tsc {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int KD = 8;              // descriptor dimensions per family
-constexpr int NFAM = 2;            // feature families
-constexpr int DW = KD * NFAM;      // doubles per structure descriptor
-constexpr int DESC_SAMPLE = 4096;  // structures used to estimate the principal axes
-constexpr int DESC_MAX_FEAT = 256; // features per family that enter the descriptor (any subset keeps the bound valid)
-constexpr unsigned NONFINITE_BITS = 0x7fc00000u;  // what the running maximum of |descriptor| reads once a non-finite structure was seen
-
-// floats per structure of the float32 copy of the heavy atoms (pair_stage1 below): x y z of four atoms per three float4, zero-padded
-__host__ __device__ inline int heavy32_pitch(int h) { return 12 * ((h + 3) / 4); }
-
-// feature a of family fam of the structure at x (h atoms, xyz triples)
-__device__ inline double feature(const double *__restrict__ x, int h, int fam, int a) {
-    if (fam == 0) return sqrt(x[3 * a] * x[3 * a] + x[3 * a + 1] * x[3 * a + 1] + x[3 * a + 2] * x[3 * a + 2]);
-    const int b = a + h / 2;
-    const double dx = x[3 * a] - x[3 * b], dy = x[3 * a + 1] - x[3 * b + 1], dz = x[3 * a + 2] - x[3 * b + 2];
-    return sqrt(0.5 * (dx * dx + dy * dy + dz * dz));
-}
-
-inline int n_features(int h, int fam) { return std::min(fam == 0 ? h : h / 2, DESC_MAX_FEAT); }
-
-// Second-moment matrix of the sampled feature vectors of one family, with a constant 1 appended:
-// M[a][b] = sum_s f_a(s) f_b(s), a, b in [0, nf]  (index nf = the constant) -> mean and covariance on the host.
-// blockIdx.y = family: both moment matrices come out of one launch.
-// DETERMINISTIC: the sums are taken in a fixed order -- workgroup b of the MOM_BLOCKS of a family adds the chunks b, b + MOM_BLOCKS,
-// ... into a partial matrix of its own (Mfam + b * m * m: every entry has one owner thread, no atomics) and the workgroup that
-// finishes last adds the partials in index order.  The basis, the descriptors and with them the Morton order of a culled pass
-// (cull.hpp) then come out bit for bit the same on every rank of a sharded run that feeds them the same sample: the ranks deal
-// the tiles of that order among themselves, and orders that differed in one structure would let pairs go unvisited.
-constexpr int MOM_BLOCKS = 32;
-inline __global__ __launch_bounds__(256) void k_feature_moments(const double *__restrict__ heavy, int h, int nf0, int nf1, int64_t stride_structs,
-                                                          int n_samples, double *__restrict__ M0, double *__restrict__ M1, unsigned *__restrict__ tickets) {
-    // tickets == null: the fast form -- one workgroup per chunk of 32 samples, atomicAdd into the (zeroed) first partial matrix of the
-    // family: the order of the additions, and with it the last bits of the basis, differ from run to run.  Any basis gives the same
-    // verdicts; only a SHARDED run needs the same bits on every rank (option "deterministic_basis").
-    // tickets[fam] (zero on entry): the workgroup of a family that finishes LAST adds the partial matrices up, in index order, into the first
-    extern __shared__ __attribute__((aligned(16))) double s_n[];  // [chunk][nf + 1]
-    __shared__ int s_last;
-    const int fam = blockIdx.y, nf = fam == 0 ? nf0 : nf1;
-    if (nf == 0) return;
-    const int m = nf + 1;
-    double *__restrict__ Mf = fam == 0 ? M0 : M1;
-    constexpr int CHUNK = 32;
-    const int n_chunks = (n_samples + CHUNK - 1) / CHUNK;
-    if (!tickets) {
-        for (int ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
-            const int s0 = ch * CHUNK, ns = min(CHUNK, n_samples - s0);
-            for (int e = threadIdx.x; e < ns * m; e += blockDim.x) {
-                int s = e / m, a = e - s * m;
-                s_n[s * m + a] = (a < nf) ? feature(heavy + int64_t(s0 + s) * stride_structs * h * 3, h, fam, a) : 1.0;
-            }
-            __syncthreads();
-            for (int e = threadIdx.x; e < m * m; e += blockDim.x) {
-                int a = e / m, b = e - a * m;
-                if (b < a) continue;
-                double acc = 0.0;
-                for (int s = 0; s < ns; ++s) acc += s_n[s * m + a] * s_n[s * m + b];
-                atomicAdd(&Mf[e], acc);
-            }
-            __syncthreads();
-        }
-        return;
-    }
-    double *__restrict__ M = Mf + size_t(blockIdx.x) * m * m;
-    bool first = true;
-    for (int ch = blockIdx.x; ch < n_chunks || first; ch += gridDim.x) {
-        const int s0 = ch * CHUNK, ns = ch < n_chunks ? min(CHUNK, n_samples - s0) : 0;   // (a workgroup without a chunk still writes zeros)
-        for (int e = threadIdx.x; e < ns * m; e += blockDim.x) {
-            int s = e / m, a = e - s * m;
-            s_n[s * m + a] = (a < nf) ? feature(heavy + int64_t(s0 + s) * stride_structs * h * 3, h, fam, a) : 1.0;
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < m * m; e += blockDim.x) {
-            int a = e / m, b = e - a * m;
-            if (b < a) continue;
-            double acc = first ? 0.0 : M[e];
-            for (int s = 0; s < ns; ++s) acc += s_n[s * m + a] * s_n[s * m + b];
-            M[e] = acc;
-        }
-        __syncthreads();
-        first = false;
-    }
-    // Hand-off of the partial matrices to the workgroup that finishes last, in the form MI355X_MICROARCH.md lists as valid (inter-workgroup
-    // visibility): every storing wavefront drains its stores, the workgroup meets, ONE lane releases at agent scope (write-back of the XCD's
-    // L2) and -- behind an explicit wait the compiler cannot drop: its pass removes the one after buffer_wbl2 when it believes the scoreboard
-    // empty, and the ticket could then overtake the write-back -- takes the ticket; the last workgroup acquires before it loads.  (Rounds
-    // 2 - 3 had __threadfence() on both sides and no explicit wait; no wrong basis was ever traced to it.)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = (atomicAdd(&tickets[fam], 1u) == gridDim.x - 1) ? 1 : 0;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    for (int e = threadIdx.x; e < m * m; e += blockDim.x) {
-        int a = e / m, b = e - a * m;
-        if (b < a) continue;
-        // (this workgroup has not touched the other workgroups' partials before: the loads miss its CU's cache and come from the L2,
-        // where the writers' stores are since their fences; all of an entry's partials in flight at once, added in index order)
-        double v[MOM_BLOCKS], acc = 0.0;
-#pragma unroll
-        for (int u = 0; u < MOM_BLOCKS; ++u) v[u] = __builtin_nontemporal_load(&Mf[size_t(u) * m * m + e]);   // one round trip
-#pragma unroll
-        for (int u = 0; u < MOM_BLOCKS; ++u) acc += v[u];
-        Mf[e] = acc;   // (entry e of partial 0 is read by this thread alone)
-    }
-}
-
-// fp32 limit of the screen for an exact limit `limit` = h thr^2, from the largest descriptor magnitude dmax: every computed
-// difference of two components is within eta = 3 * 2^-24 * 2 dmax of the exact one, the 8-term sum of squares carries at most
-// 2^-20 relative error, so s_exact >= s32 (1 - 2^-20) - 2 eta sqrt(KD s32); the limit returned is the smallest s32 above which
-// that lower bound certainly exceeds `limit`.  A NaN / inf dmax gives a limit that drops nothing.
-__device__ inline float screen_limit32(float dmaxf, double limit) {
-    const double dmax = (dmaxf >= 0.0f && dmaxf < 3.0e38f) ? double(dmaxf) : 3.0e38;
-    const double eta = 3.0 * 5.9604644775390625e-08 * 2.0 * dmax;               // 3 * 2^-24 * 2 dmax
-    const double a = 1.0 - 9.5367431640625e-07, b = 2.0 * eta * sqrt(double(KD));  // 1 - 2^-20
-    const double x = (b + sqrt(b * b + 4.0 * a * limit)) / (2.0 * a);
-    const double l32 = x * x * (1.0 + 1e-6) + 1e-30;
-    float f = float(l32);
-    if (double(f) < l32) f = __uint_as_float(__float_as_uint(f) + 1u);  // next float up (f > 0)
-    return (l32 < 3.0e38) ? f : 3.4e38f;
-}
-
-// The same limit for the screen as the pair kernel computes it: S = fl(fl(|a|^2 + |b|^2) - 2 fl(a.b)) on the stored fp32
-// vectors a, b (8-term fma chains), which costs 10 packed instructions per column instead of 16 for sum (a_k - b_k)^2.  With
-// u = 2^-24 and g8 = 8u / (1 - 8u):  | |a|^2_fl - |a|^2 | <= g8 |a|^2,  | a.b_fl - a.b | <= g8 (|a|^2 + |b|^2) / 2,  so the
-// exact T = |a - b|^2 satisfies  T >= S (1 - 2u) - E,  E = (2 g8 + u (1 + g8)) (|a|^2 + |b|^2) <= (2 g8 + u (1 + g8)) 2 KD M^2.
-// The kernel's other association, S' = fl(|a|^2_fl - 2 fl(-|b|^2_fl / 2 + a.b)) (the chain of 8 fmas starts from the
-// halved column norm, an exact scaling), carries g8 (|b|^2 (1 + g8) / 2 + (|a|^2 + |b|^2) / 2) in the chain, twice that after
-// the exact factor, plus the two norm roundings: at most g8 (2 |a|^2 + 3 |b|^2)(1 + g8) <= 3 g8 (|a|^2 + |b|^2) (1 + g8)
-// beside the final u: the E below (3 g8 in place of 2) covers both associations.
-// The stored components are roundings of the exact descriptors, each difference within eta = 3 * 2^-24 * 2M of the exact
-// one as above, so s_exact >= T - 2 eta sqrt(KD T) (increasing in T beyond KD eta^2): a pair whose S exceeds the returned
-// value certainly has s_exact > limit.
-__device__ inline float screen_limit32_dot(float dmaxf, double limit) {
-    const double dmax = (dmaxf >= 0.0f && dmaxf < 3.0e38f) ? double(dmaxf) : 3.0e38;
-    constexpr double U = 5.9604644775390625e-08, G8 = 8.0 * U / (1.0 - 8.0 * U);
-    const double eta = 3.0 * U * 2.0 * dmax;
-    const double b = 2.0 * eta * sqrt(double(KD));
-    const double y = 0.5 * (b + sqrt(b * b + 4.0 * limit));   // sqrt of the smallest T with T - b sqrt(T) >= limit
-    const double E = (3.0 * G8 * (1.0 + G8) + U * (1.0 + G8)) * 2.0 * double(KD) * dmax * dmax;
-    const double l32 = (y * y + E) / (1.0 - 2.0 * U) * (1.0 + 1e-6) + 1e-30;
-    float f = float(l32);
-    if (double(f) < l32) f = __uint_as_float(__float_as_uint(f) + 1u);  // next float up (f > 0)
-    return (l32 < 3.0e38) ? f : 3.4e38f;
-}
-
-// The descriptor rows of the ns structures staged in LDS (s_x, `pitch` doubles apart; s_q = both bases): T = 256 / S
-// consecutive lanes share a structure (atoms sub, sub + T, ...) and reduce with shuffles.  Called by all 256 threads.
-__device__ inline void describe_from_lds(const double *s_q, const double *s_x, int pitch, int h, int nf0, int nf1, const double *__restrict__ bias,
-                                         int ns, int S, int64_t i0, float *__restrict__ D, double *__restrict__ G, unsigned *__restrict__ dmax_bits) {
-    const int T = 256 / S;
-    const int sidx = threadIdx.x / T, sub = threadIdx.x - sidx * T;
-    const bool mine = sidx < ns;
-    double d[DW], g = 0.0;
-#pragma unroll
-    for (int k = 0; k < DW; ++k) d[k] = 0.0;
-    if (mine) {
-        const double *x = s_x + sidx * pitch;
-        const double *q1 = s_q + KD * nf0;
-        for (int a = sub; a < h; a += T) {
-            const double n2 = x[3 * a] * x[3 * a] + x[3 * a + 1] * x[3 * a + 1] + x[3 * a + 2] * x[3 * a + 2];
-            g += n2;
-            if (a < nf0) {
-                const double f = sqrt(n2);
-#pragma unroll
-                for (int k = 0; k < KD; ++k) d[k] = fma(s_q[k * nf0 + a], f, d[k]);
-            }
-            if (a < nf1) {
-                const double f = feature(x, h, 1, a);
-#pragma unroll
-                for (int k = 0; k < KD; ++k) d[KD + k] = fma(q1[k * nf1 + a], f, d[KD + k]);
-            }
-        }
-    }
-    for (int off = T >> 1; off > 0; off >>= 1) {  // T <= 64 consecutive lanes of one wavefront
-#pragma unroll
-        for (int k = 0; k < DW; ++k) d[k] += __shfl_xor(d[k], off);
-        g += __shfl_xor(g, off);
-    }
-    float mx = 0.0f;
-    if (mine && sub == 0) {
-        float v[DW];
-#pragma unroll
-        for (int k = 0; k < DW; ++k) {
-            v[(k % KD) * 2 + k / KD] = float(d[k] - bias[k]);
-            mx = fmaxf(mx, fabsf(float(d[k] - bias[k])));
-        }
-        f32x4 *dst = reinterpret_cast<f32x4 *>(D + (i0 + sidx) * DW);
-#pragma unroll
-        for (int k = 0; k < DW / 4; ++k) dst[k] = f32x4{v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]};
-        G[i0 + sidx] = g;
-    }
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-    // same-address atomics serialise (about 12 ns each): only a wavefront that would raise the maximum sends one
-    if ((threadIdx.x & 63) == 0 && mx > __uint_as_float(__hip_atomic_load(dmax_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))
-        atomicMax(dmax_bits, __float_as_uint(mx));
-    // A structure with a NaN or infinite coordinate (its squared norm is not finite) raises the running maximum to the bit pattern of
-    // a NaN: the screen's limit then drops nothing (screen_limit32*), the evaluation stages find such a structure similar to nothing
-    // (every comparison with a NaN is false, rmsd_pruning.py:75), and the run reports that it saw one (tsc_pass_stats.nonfinite_input;
-    // the reference's np.linalg.svd raises LinAlgError on such input, rmsd_pruning.py:19)
-    if (__ballot(mine && sub == 0 && !(g < 1.7976931348623157e308)) != 0 && (threadIdx.x & 63) == 0) atomicMax(dmax_bits, NONFINITE_BITS);
-}
-
-// D[i][2k + fam] = sum_a Q_fam[k][a] * f_fam,a(x_i) - bias[fam*KD + k]   (fp32, original index space, the two families
-// interleaved; the bias is the projection of the mean feature vector and cancels in every difference),
-// G[i] = sum_a |x_ia|^2; *dmax_bits = max |D| over everything as the bit pattern of a non-negative float (atomicMax on the
-// integer view; zero on entry) -- the pair kernel turns it into the fp32 limit of the screen (screen_limit32).
-// A block stages S structures in LDS with coalesced loads (a thread-per-structure walk reads 64 lines per instruction and
-// thrashes the L1); T = 256 / S consecutive lanes share a structure (atoms sub, sub + T, ...) and reduce with shuffles.
-inline __global__ __launch_bounds__(256) void k_descriptors(const double *__restrict__ heavy, int64_t n, int h, int nf0, int nf1,
-                                                      const double *__restrict__ Q, const double *__restrict__ bias, float *__restrict__ D,
-                                                      double *__restrict__ G, unsigned *__restrict__ dmax_bits, int S) {
-    extern __shared__ __attribute__((aligned(16))) double s_mem[];  // [KD][nf0], [KD][nf1], then S rows of pitch doubles
-    const int h3 = h * 3, pitch = h3 | 1;
-    double *s_q = s_mem, *s_x = s_mem + KD * (nf0 + nf1);
-    for (int e = threadIdx.x; e < KD * (nf0 + nf1); e += 256) s_q[e] = Q[e];
-    const int64_t i0 = int64_t(blockIdx.x) * S;
-    const int ns = int(min<int64_t>(S, n - i0));
-    const double *src = heavy + i0 * h3;
-    // eight loads in flight per thread before the first LDS store (a plain copy loop waits for every load in turn)
-    for (int base = threadIdx.x; base < ns * h3; base += 256 * 8) {
-        double v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (base + 256 * j < ns * h3) ? src[base + 256 * j] : 0.0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int e = base + 256 * j;
-            if (e < ns * h3) {
-                const int row = e / h3;
-                s_x[row * pitch + (e - row * h3)] = v[j];
-            }
-        }
-    }
-    __syncthreads();
-    describe_from_lds(s_q, s_x, pitch, h, nf0, nf1, bias, ns, S, i0, D, G, dmax_bits);
-}
-
-// K1 with the descriptors of the prune fused in (tsc_pipeline_dev, when the basis is ready before the passing poses are
-// embedded): k_transform's workgroup of TR_POSES poses keeps the heavy atoms it has just computed in LDS and takes their
-// descriptor rows from there, so the 24 h bytes per structure are not read back by a k_descriptors launch.
-// dynamic LDS: transform_lds_bytes(n_mols), then [KD][nf0 + nf1] basis doubles, then TR_POSES rows of (3 h | 1) doubles.
-inline __global__ __launch_bounds__(256) void k_transform_describe(const double *__restrict__ frags, FragTable ft, const int32_t *__restrict__ conf_idx,
-                                                             const double *__restrict__ rot, const double *__restrict__ pos,
-                                                             const int32_t *__restrict__ idx, double *__restrict__ out,
-                                                             const int32_t *__restrict__ heavy_slot, int n_heavy, double *__restrict__ heavy_out,
-                                                             const int32_t *__restrict__ n_out_dev, int nf0, int nf1, const double *__restrict__ Q,
-                                                             const double *__restrict__ bias, float *__restrict__ D, double *__restrict__ G,
-                                                             unsigned *__restrict__ dmax_bits, float *__restrict__ heavy32_out = nullptr) {
-    // heavy32_out (optional): the float32 copy of the heavy atoms that stage 1 of the pair kernels reads (pair_stage1), zero-padded rows
-    extern __shared__ __attribute__((aligned(16))) double s_tr[];
-    const int n = ft.n_total, nm = ft.n_mols, tid = threadIdx.x, pitch = (n_heavy * 3) | 1;
-    const int pitch32 = heavy32_pitch(n_heavy), pad32 = pitch32 - 3 * n_heavy;
-    const int64_t n_out = *n_out_dev;
-    int64_t *sP = reinterpret_cast<int64_t *>(s_tr);
-    double *sR = s_tr + TR_POSES, *sT = sR + TR_POSES * nm * 9;
-    int *sC = reinterpret_cast<int *>(sT + TR_POSES * nm * 3);
-    double *s_q = s_tr + (transform_lds_bytes(nm) + 15) / 16 * 2, *s_x = s_q + KD * (nf0 + nf1);
-    for (int e = tid; e < KD * (nf0 + nf1); e += 256) s_q[e] = Q[e];
-    for (int64_t r0 = int64_t(blockIdx.x) * TR_POSES; r0 < n_out; r0 += int64_t(gridDim.x) * TR_POSES) {
-        const int np = int(min<int64_t>(TR_POSES, n_out - r0));
-        if (tid < np) sP[tid] = int64_t(idx[r0 + tid]);
-        __syncthreads();
-        for (int q = tid; q < np * nm * 9; q += 256) {
-            const int row = q / (nm * 9), w = q - row * nm * 9;
-            sR[q] = rot[sP[row] * nm * 9 + w];
-        }
-        for (int q = tid; q < np * nm * 3; q += 256) {
-            const int row = q / (nm * 3), w = q - row * nm * 3;
-            sT[q] = pos[sP[row] * nm * 3 + w];
-        }
-        for (int q = tid; q < np * nm; q += 256) {
-            const int row = q / nm, w = q - row * nm;
-            sC[q] = conf_idx[sP[row] * nm + w];
-        }
-        __syncthreads();
-        for (int e = tid; e < np * n; e += 256) {
-            const int row = e / n, a = e - row * n;
-            const int64_t r = r0 + row;
-            double v[3];
-            embed_atom_staged(frags, ft, sR, sT, sC, row, a, v);
-            if (out) {
-                double *o = out + (r * n + a) * 3;
-                o[0] = v[0], o[1] = v[1], o[2] = v[2];
-            }
-            const int hs = heavy_slot[a];
-            if (hs >= 0) {
-                double *hv = heavy_out + (r * n_heavy + hs) * 3, *x = s_x + row * pitch + hs * 3;
-                hv[0] = x[0] = v[0], hv[1] = x[1] = v[1], hv[2] = x[2] = v[2];
-                if (heavy32_out) {
-                    float *hf = heavy32_out + r * pitch32 + hs * 3;
-                    hf[0] = float(v[0]), hf[1] = float(v[1]), hf[2] = float(v[2]);
-                }
-            }
-        }
-        if (heavy32_out)
-            for (int e = tid; e < np * pad32; e += 256) heavy32_out[(r0 + e / pad32) * pitch32 + 3 * n_heavy + e % pad32] = 0.0f;
-        __syncthreads();
-        describe_from_lds(s_q, s_x, pitch, n_heavy, nf0, nf1, bias, np, TR_POSES, r0, D, G, dmax_bits);
-        __syncthreads();
-    }
-}
-
-inline size_t transform_describe_lds_bytes(int n_mols, int h) {
-    return (transform_lds_bytes(n_mols) + 15) / 16 * 16 + (size_t(KD) * (n_features(h, 0) + n_features(h, 1)) + size_t(TR_POSES) * ((h * 3) | 1)) * sizeof(double);
-}
-
-// The trivial basis for small ensembles: component k of a family = its feature k (rows of the identity: |Q x| <= |x|), no
-// centring.  Any basis gives the same verdicts; with a few thousand structures the screen has little to do, and estimating
-// principal axes (a memset, a moments launch and the one-wavefront basis kernel: about 45 us of latency) costs more than it saves.
-inline __global__ void k_identity_basis(int nf0, int nf1, double *__restrict__ Q, double *__restrict__ bias) {
-    const int total = KD * (nf0 + nf1);
-    for (int e = threadIdx.x; e < total; e += blockDim.x) {
-        const int fam = e < KD * nf0 ? 0 : 1, r = fam == 0 ? e : e - KD * nf0, nf = fam == 0 ? nf0 : nf1;
-        Q[e] = (r / nf == r % nf) ? 1.0 : 0.0;
-    }
-    for (int e = threadIdx.x; e < DW; e += blockDim.x) bias[e] = 0.0;
-    if (threadIdx.x < NFAM) bias[DW + threadIdx.x] = __builtin_inf();  // (no estimate of the descriptors' spread: k_descriptor_basis)
-}
-
-// Device-side descriptor basis: one wavefront per feature family.  Orthonormal rows spanning the leading principal
-// axes of the feature covariance by a few steps of block power iteration (the spectrum of these features decays
-// fast: one step gives the screening power of three to within 3 % of the pairs that reach H).  Rows are re-orthonormalised by
-// CholeskyQR2: lane (i, j) accumulates the Gram entry <W_i, W_j>, lane 0 factors the 8x8 Gram matrix, every lane
-// applies L^-1 to its columns -- no cross-lane reduction on the critical path.  Whatever the iteration produced,
-// the rows are finally divided by sqrt of a Gershgorin bound of |V V^T|_2, so |V x| <= |x| holds rigorously and
-// the screen can never drop a similar pair.
-//   M      second moments of the family, (nf+1)^2, upper triangle filled, index nf = the constant 1
-//   Qout   [KD][nf] rows of the basis;  bias[k] = V_k . mean
-#ifndef TSC_BASIS_ITERS
-#define TSC_BASIS_ITERS 1
-#endif
-constexpr int BASIS_ITERS = TSC_BASIS_ITERS;
-constexpr int BASIS_LDS_C = 64;  // covariance staged in LDS up to this many features
-inline __global__ __launch_bounds__(64) void k_descriptor_basis(const double *__restrict__ M0, const double *__restrict__ M1, int nf0, int nf1,
-                                                          int n_samples, double *__restrict__ Q, double *__restrict__ bias,
-                                                          unsigned *__restrict__ zero_word, double *__restrict__ spread_host = nullptr,
-                                                          int clear_moments = 0) {
-    // clear_moments: the moment matrices are accumulators that k_sample_moments adds into: this kernel, their one reader, leaves them zero
-    // spread_host (optional): host-visible copy of the two spread values written at the end (pinned memory; the host pre-sets +inf
-    // and looks without waiting: whatever finite values it finds are this kernel's)
-    // zero_word (optional): the running max |D| of a descriptor build that follows this kernel, cleared here
-    if (zero_word && blockIdx.x == 0 && threadIdx.x == 0) *zero_word = 0u;
-    __shared__ double V[KD][DESC_MAX_FEAT], Z[KD][DESC_MAX_FEAT], mu[DESC_MAX_FEAT];
-    __shared__ double Cs[BASIS_LDS_C][BASIS_LDS_C + 1];
-    __shared__ double Gm[KD][KD];  // Gram matrix of the rows being orthonormalised
-    const int fam = blockIdx.x, lane = threadIdx.x;
-    const double *M = fam == 0 ? M0 : M1;
-    const int nf = fam == 0 ? nf0 : nf1, m = nf + 1;
-    double *Qout = Q + (fam == 0 ? 0 : size_t(KD) * nf0);
-    double *bout = bias + fam * KD;
-    if (nf == 0) {
-        if (lane < KD) bout[lane] = 0.0;
-        if (lane == 0) {
-            bias[DW + fam] = 0.0;  // (a family without features separates nothing)
-            if (spread_host) spread_host[fam] = 0.0;
-        }
-        return;
-    }
-    const double inv = n_samples > 0 ? 1.0 / n_samples : 0.0;
-    for (int a = lane; a < nf; a += 64) mu[a] = M[size_t(a) * m + nf] * inv;
-    __builtin_amdgcn_wave_barrier();
-    const bool c_in_lds = nf <= BASIS_LDS_C;
-    if (c_in_lds)
-        for (int e = lane; e < nf * nf; e += 64) {
-            const int a = e / nf, b = e - a * nf;
-            Cs[a][b] = (a <= b ? M[size_t(a) * m + b] : M[size_t(b) * m + a]) * inv - mu[a] * mu[b];
-        }
-    for (int k = 0; k < KD; ++k)
-        for (int a = lane; a < nf; a += 64) V[k][a] = ((a % KD) == k ? 1.0 : 0.0) + 1e-3 * ((a * 7 + k * 13) % 11 - 5);
-    __builtin_amdgcn_wave_barrier();
-
-    // W <- rows of an orthonormal basis of span(W) (zero rows where the span is exhausted)
-    auto cholesky_qr = [&](double (*W)[DESC_MAX_FEAT]) {
-        const int gi = lane >> 3, gj = lane & 7;  // 64 lanes = the 8 x 8 Gram entries
-        double g = 0.0;
-#pragma unroll 4
-        for (int a = 0; a < nf; ++a) g = fma(W[gi][a], W[gj][a], g);
-        Gm[gi][gj] = g;
-        __builtin_amdgcn_wave_barrier();
-        // every lane factors the 8 x 8 Gram matrix in registers (constant indices only): G = L L^T, then Li = L^-1 -- in float32: this
-        // kernel is one wavefront's instruction stream (about 40 us, on the critical path of the pipeline's front half), most of it the
-        // float64 divisions and square roots of the factorisation; rows orthonormal to 1e-6 serve as well (the second pass of CholeskyQR2
-        // repairs what the first leaves, and the Gershgorin scaling below makes |V x| <= |x| hold for whatever comes out)
-        float L[KD][KD], Li[KD][KD];
-        float tr = 0.0f;
-#pragma unroll
-        for (int i = 0; i < KD; ++i) {
-#pragma unroll
-            for (int j = 0; j <= i; ++j) L[i][j] = float(Gm[i][j]);
-            tr += L[i][i];
-        }
-        bool dead[KD];
-        float rinv[KD];  // 1 / L[i][i]
-#pragma unroll
-        for (int i = 0; i < KD; ++i) {
-#pragma unroll
-            for (int j = 0; j <= i; ++j) {
-                float sacc = L[i][j];
-#pragma unroll
-                for (int t = 0; t < j; ++t) sacc = fmaf(-L[i][t], L[j][t], sacc);
-                if (i == j) {
-                    dead[i] = !(sacc > 1e-6f * tr) || !(tr > 0.0f);
-                    L[i][i] = dead[i] ? 1.0f : sqrtf(sacc);
-                    rinv[i] = 1.0f / L[i][i];
-                } else {
-                    L[i][j] = dead[j] ? 0.0f : sacc * rinv[j];
-                }
-            }
-            if (dead[i]) {
-#pragma unroll
-                for (int j = 0; j < i; ++j) L[i][j] = 0.0f;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < KD; ++j) {
-#pragma unroll
-            for (int i = j; i < KD; ++i) {
-                float sacc = (i == j) ? 1.0f : 0.0f;
-#pragma unroll
-                for (int t = j; t < i; ++t) sacc = fmaf(-L[i][t], Li[t][j], sacc);
-                Li[i][j] = dead[i] ? 0.0f : sacc * rinv[i];
-            }
-        }
-        for (int a = lane; a < nf; a += 64) {
-            double w[KD];
-#pragma unroll
-            for (int k = 0; k < KD; ++k) w[k] = W[k][a];
-#pragma unroll
-            for (int i = 0; i < KD; ++i) {
-                double acc = 0.0;
-#pragma unroll
-                for (int j = 0; j <= i; ++j) acc = fma(double(Li[i][j]), w[j], acc);
-                W[i][a] = acc;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    };
-    // (the start rows are not orthonormalised first: C V spans the same nested subspaces whether V or L^-1 V is fed in -- CholeskyQR mixes
-    // row i with rows before it only -- so the rows that come out of the step are the same, and two of the four factorisations of this
-    // one-wavefront kernel, which sits on the critical path of the pipeline's front half, are saved)
-    for (int it = 0; it < BASIS_ITERS; ++it) {
-        // Z_k = C V_k with C[a][b] = M[a][b]/ns - mu_a mu_b
-        for (int a = lane; a < nf; a += 64) {
-            double acc[KD];
-#pragma unroll
-            for (int k = 0; k < KD; ++k) acc[k] = 0.0;
-#pragma unroll 4
-            for (int b = 0; b < nf; ++b) {
-                const double cab = c_in_lds ? Cs[a][b] : ((a <= b ? M[size_t(a) * m + b] : M[size_t(b) * m + a]) * inv - mu[a] * mu[b]);
-#pragma unroll
-                for (int k = 0; k < KD; ++k) acc[k] = fma(cab, V[k][b], acc[k]);
-            }
-#pragma unroll
-            for (int k = 0; k < KD; ++k) Z[k][a] = acc[k];
-        }
-        __builtin_amdgcn_wave_barrier();
-        cholesky_qr(Z);
-        cholesky_qr(Z);
-        // a direction that C annihilated comes back as a zero row: keep the previous row there if it is still
-        // orthogonal to the new ones?  Not needed for validity -- a zero row only weakens the screen.
-        for (int k = 0; k < KD; ++k)
-            for (int a = lane; a < nf; a += 64) V[k][a] = Z[k][a];
-        __builtin_amdgcn_wave_barrier();
-    }
-    // Gershgorin bound of the largest eigenvalue of V V^T (= |V|_2^2): max_i sum_j |<V_i, V_j>|
-    {
-        const int gi = lane >> 3, gj = lane & 7;
-        double g = 0.0;
-        for (int a = 0; a < nf; ++a) g = fma(V[gi][a], V[gj][a], g);
-        Gm[gi][gj] = fabs(g);
-        __builtin_amdgcn_wave_barrier();
-    }
-    double gmax = 0.0;
-    for (int i = 0; i < KD; ++i) {
-        double row = 0.0;
-        for (int j = 0; j < KD; ++j) row += Gm[i][j];
-        gmax = fmax(gmax, row);
-    }
-    const double sc = gmax > 0.0 ? 1.0 / sqrt(gmax * (1.0 + 1e-12)) : 0.0;
-    for (int a = lane; a < nf; a += 64)
-        for (int k = 0; k < KD; ++k) {
-            const double v = V[k][a] * sc;
-            V[k][a] = v;
-            Qout[size_t(k) * nf + a] = v;
-        }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < KD) {
-        double b = 0.0;
-        for (int a = 0; a < nf; ++a) b = fma(V[lane][a], mu[a], b);
-        bout[lane] = b;
-    }
-    // How far apart two structures of the sample lie in this family's descriptor, on average: E |V (f(p) - f(q))|^2 = 2 sum_k V_k^T C V_k.
-    // The host compares it with the screen's limit h thr^2: where both families stay below it the screen can separate (almost)
-    // nothing -- every pair would reach H anyway -- and an all-pairs kernel without a screen is the faster route (host.hpp,
-    // screen_is_useless).  Only worked out where that kernel exists (up to 32 heavy atoms); +inf otherwise.
-    double spread = __builtin_inf();
-    if (nf <= 32) {  // (c_in_lds) lane = (row k of V, an eighth of the features a): 64 lanes share the nf^2 KD products
-        static_assert(KD == 8 && BASIS_LDS_C >= 32, "lane layout of the spread estimate");
-        const int k = lane & 7;
-        double lam = 0.0;
-        for (int a = lane >> 3; a < nf; a += 8) {
-            double z = 0.0;
-            for (int b = 0; b < nf; ++b) z = fma(Cs[a][b], V[k][b], z);
-            lam = fma(V[k][a], z, lam);
-        }
-        for (int off = 32; off > 0; off >>= 1) lam += __shfl_xor(lam, off);
-        spread = 2.0 * lam;
-    }
-    if (lane == 0) {
-        bias[DW + fam] = spread;
-        if (spread_host) {
-            spread_host[fam] = spread;
-            __threadfence_system();
-        }
-    }
-    if (clear_moments) {
-        double *Mw = const_cast<double *>(M);
-        for (int e = lane; e < m * m; e += 64) Mw[e] = 0.0;
-    }
-}
-
-// The first link of the pipeline's basis chain on one device: the sample poses are embedded (heavy atoms, into LDS only) and the second
-// moments of their features added up -- k_transform + k_feature_moments (fast form) in one launch, without the round trip of the sample's
-// coordinates through memory.  grid (groups of SM_CHUNKS chunks of TR_POSES samples, NFAM); M0 / M1 are zero on entry (k_descriptor_basis clears them again).
-// dynamic LDS: sample_moments_lds_bytes
-constexpr int SM_CHUNKS = 1;  // chunks of TR_POSES samples per workgroup of k_sample_moments (4: 52 us instead of 26 -- a chunk is a chain of
-                              // dependent loads, about 13 us beside the clash kernel, and the chains of a workgroup run one after the other)
-__host__ __device__ inline size_t sample_moments_lds_bytes(int n_mols, int h) {
-    return (transform_lds_bytes(n_mols) + 15) / 16 * 16 + size_t(TR_POSES) * (size_t(h) * 3 + size_t(h) + 1) * sizeof(double);
-}
-inline __global__ __launch_bounds__(256) void k_sample_moments(const double *__restrict__ frags, FragTable ft, const int32_t *__restrict__ conf_idx,
-                                                        const double *__restrict__ rot, const double *__restrict__ pos,
-                                                        const int32_t *__restrict__ sample_idx, int n_samples, const int32_t *__restrict__ heavy_slot,
-                                                        int h, int nf0, int nf1, double *__restrict__ M0, double *__restrict__ M1) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_sm_raw[];
-    const int fam = blockIdx.y, nf = fam == 0 ? nf0 : nf1;
-    if (nf == 0) return;
-    const int n = ft.n_total, nm = ft.n_mols, tid = threadIdx.x, m = nf + 1;
-    double *s_tr = reinterpret_cast<double *>(s_sm_raw);
-    int64_t *sP = reinterpret_cast<int64_t *>(s_tr);
-    double *sR = s_tr + TR_POSES, *sT = sR + TR_POSES * nm * 9;
-    int *sC = reinterpret_cast<int *>(sT + TR_POSES * nm * 3);
-    double *s_x = reinterpret_cast<double *>(s_sm_raw + (transform_lds_bytes(nm) + 15) / 16 * 16);   // [TR_POSES][h * 3]
-    double *s_n = s_x + size_t(TR_POSES) * h * 3;                                                    // [TR_POSES][m]
-    double *__restrict__ Mf = fam == 0 ? M0 : M1;
-    const int n_chunks = (n_samples + TR_POSES - 1) / TR_POSES;
-    // a workgroup takes SM_CHUNKS consecutive chunks and adds their products up in registers before it touches the accumulators
-    constexpr int ACC = 8;
-    const bool in_regs = m * m <= 256 * ACC;
-    double acc[ACC];
-#pragma unroll
-    for (int u = 0; u < ACC; ++u) acc[u] = 0.0;
-    for (int ch = blockIdx.x * SM_CHUNKS; ch < min(n_chunks, (int(blockIdx.x) + 1) * SM_CHUNKS); ++ch) {
-        const int s0 = ch * TR_POSES, ns = min(TR_POSES, n_samples - s0);
-        if (tid < ns) sP[tid] = int64_t(sample_idx[s0 + tid]);
-        __syncthreads();
-        for (int q = tid; q < ns * nm * 9; q += 256) {
-            const int row = q / (nm * 9), w = q - row * nm * 9;
-            sR[q] = rot[sP[row] * nm * 9 + w];
-        }
-        for (int q = tid; q < ns * nm * 3; q += 256) {
-            const int row = q / (nm * 3), w = q - row * nm * 3;
-            sT[q] = pos[sP[row] * nm * 3 + w];
-        }
-        for (int q = tid; q < ns * nm; q += 256) {
-            const int row = q / nm, w = q - row * nm;
-            sC[q] = conf_idx[sP[row] * nm + w];
-        }
-        __syncthreads();
-        for (int e = tid; e < ns * n; e += 256) {
-            const int row = e / n, a = e - row * n;
-            const int hs = heavy_slot[a];
-            if (hs < 0) continue;
-            double v[3];
-            embed_atom_staged(frags, ft, sR, sT, sC, row, a, v);
-            double *o = s_x + (size_t(row) * h + hs) * 3;
-            o[0] = v[0], o[1] = v[1], o[2] = v[2];
-        }
-        __syncthreads();
-        for (int e = tid; e < ns * m; e += 256) {
-            const int sm = e / m, a = e - sm * m;
-            s_n[sm * m + a] = (a < nf) ? feature(s_x + size_t(sm) * h * 3, h, fam, a) : 1.0;
-        }
-        __syncthreads();
-        if (in_regs) {
-#pragma unroll
-            for (int u = 0; u < ACC; ++u) {
-                const int e = tid + 256 * u;
-                if (e < m * m) {
-                    const int a = e / m, b = e - a * m;
-                    if (b >= a) {
-                        double t = 0.0;
-                        for (int sm = 0; sm < ns; ++sm) t += s_n[sm * m + a] * s_n[sm * m + b];
-                        acc[u] += t;
-                    }
-                }
-            }
-        } else {
-            for (int e = tid; e < m * m; e += 256) {
-                const int a = e / m, b = e - a * m;
-                if (b < a) continue;
-                double t = 0.0;
-                for (int sm = 0; sm < ns; ++sm) t += s_n[sm * m + a] * s_n[sm * m + b];
-                atomicAdd(&Mf[e], t);
-            }
-        }
-        __syncthreads();
-    }
-    if (in_regs) {
-#pragma unroll
-        for (int u = 0; u < ACC; ++u) {
-            const int e = tid + 256 * u;
-            if (e < m * m && e % m >= e / m) atomicAdd(&Mf[e], acc[u]);
-        }
-    }
-}
 
 struct SieveArgs {
     int n;   // upper bound of the active count the grid was sized for (structures of the run)
@@ -694,98 +53,6 @@ struct SieveArgs {
 #define TSC_STAMP(i) do { } while (0)
 #endif
 
-// H = p^T q of one pair read from memory.  `lpp` consecutive lanes (a power of two) share the pair: lane `sub` takes
-// atoms sub, sub + lpp, ... and the group sums H with a butterfly, so a batch of few pairs has a short critical path
-// (lpp = 64 / batch size) while a full batch runs one pair per lane (lpp = 1).
-__device__ inline void pair_H(const double *__restrict__ p, const double *__restrict__ q, int h, int sub, int lpp, double H[9]) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) H[k] = 0.0;
-#pragma unroll 2
-    for (int a = sub; a < h; a += lpp) {
-        const double px = p[3 * a], py = p[3 * a + 1], pz = p[3 * a + 2];
-        const double qx = q[3 * a], qy = q[3 * a + 1], qz = q[3 * a + 2];
-        H[0] = fma(px, qx, H[0]), H[1] = fma(px, qy, H[1]), H[2] = fma(px, qz, H[2]);
-        H[3] = fma(py, qx, H[3]), H[4] = fma(py, qy, H[4]), H[5] = fma(py, qz, H[5]);
-        H[6] = fma(pz, qx, H[6]), H[7] = fma(pz, qy, H[7]), H[8] = fma(pz, qz, H[8]);
-    }
-    for (int off = lpp >> 1; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) H[k] += __shfl_xor(H[k], off);
-    }
-}
-
-// The float32 copy of the heavy atoms that stage 1 reads first: structure i at heavy32 + i * pitch32, pitch32 = 12 * ceil(h / 4) floats
-// (x y z of four atoms per three float4; zero-padded).  The gathers of the pairs that pass the screen are what the pair kernels wait
-// for -- with the float64 loads issued twice a C4 step takes 18.8 instead of 12.2 ms, a C3 step 1.00 instead of 0.86 -- and the quartic
-// tests on H from this copy, with the rounding bound that goes with it (rmsd.hpp: quartic_gamma32), decide all but the pairs with a
-// tiny margin; those are formed again from the float64 coordinates, as is everything the explicit-rotation path needs.
-
-inline __global__ __launch_bounds__(256) void k_heavy32(const double *__restrict__ heavy, int64_t n, int h, float *__restrict__ out) {
-    const int h3 = h * 3, pitch = heavy32_pitch(h);
-    const int64_t total = n * pitch;
-    for (int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x; e < total; e += int64_t(gridDim.x) * 256) {
-        const int64_t i = e / pitch;
-        const int w = int(e - i * pitch);
-        out[e] = w < h3 ? float(heavy[i * h3 + w]) : 0.0f;
-    }
-}
-
-// H = p^T q from the float32 copy: lane `sub` of the pair's `lpp` lanes takes the groups of four atoms sub, sub + lpp, ...; the
-// products of two floats are exact in float64, the sums run there
-__device__ inline void pair_H32(const float *__restrict__ p, const float *__restrict__ q, int hq, int sub, int lpp, double H[9]) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) H[k] = 0.0;
-    for (int g = sub; g < hq; g += lpp) {
-        const f32x4 *pv = reinterpret_cast<const f32x4 *>(p + 12 * g), *qv = reinterpret_cast<const f32x4 *>(q + 12 * g);
-        const f32x4 p0 = pv[0], p1 = pv[1], p2 = pv[2], q0 = qv[0], q1 = qv[1], q2 = qv[2];
-        const float pf[12] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w, p2.x, p2.y, p2.z, p2.w};
-        const float qf[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const double px = pf[3 * a], py = pf[3 * a + 1], pz = pf[3 * a + 2];
-            const double qx = qf[3 * a], qy = qf[3 * a + 1], qz = qf[3 * a + 2];
-            H[0] = fma(px, qx, H[0]), H[1] = fma(px, qy, H[1]), H[2] = fma(px, qz, H[2]);
-            H[3] = fma(py, qx, H[3]), H[4] = fma(py, qy, H[4]), H[5] = fma(py, qz, H[5]);
-            H[6] = fma(pz, qx, H[6]), H[7] = fma(pz, qy, H[7]), H[8] = fma(pz, qz, H[8]);
-        }
-    }
-    for (int off = lpp >> 1; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) H[k] += __shfl_xor(H[k], off);
-    }
-}
-
-// Stage 1 of a pair that passed the screen: PAIR_DISSIMILAR / PAIR_SIMILAR / PAIR_UNDECIDED (rmsd.hpp).  With the float32 copy the tests
-// run on H from that copy alone, with its own rounding bound; what they leave undecided goes to the explicit-rotation stage like any
-// other undecided pair (it forms H from the float64 coordinates).  F32 = false: H from the float64 coordinates, as ever (a template
-// parameter, not a branch: with both loops in one kernel the float64 one lost a tenth of its speed to the register allocation).
-template <bool F32>
-__device__ inline int pair_stage1(const double *__restrict__ heavy, const float *__restrict__ heavy32, int64_t i, int64_t j, int h, double half_sum,
-                                  double half_h_thr2, double two_thr2, int sub, int lpp) {
-    double H[9];
-    if (F32) {
-        const int pitch = heavy32_pitch(h);
-        pair_H32(heavy32 + i * pitch, heavy32 + j * pitch, pitch / 12, sub, lpp, H);
-        return pair_verdict_g(H, half_sum, half_h_thr2, two_thr2, quartic_gamma32(h));
-    }
-    pair_H(heavy + i * h * 3, heavy + j * h * 3, h, sub, lpp, H);
-    return pair_verdict(H, half_sum, half_h_thr2, two_thr2, h);
-}
-
-// One pair end to end: true iff it is similar in the reference's sense (rmsd < thr and maxdev < 2 thr,
-// rmsd_pruning.py:75); exact_taken tells whether the explicit-rotation path ran.
-__device__ inline bool pair_is_similar(const double *__restrict__ p, const double *__restrict__ q, int h, double Gp, double Gq,
-                                       double half_h_thr2, double thr, double maxdev_thr, bool &exact_taken, int sub, int lpp) {
-    double H[9];
-    pair_H(p, q, h, sub, lpp, H);
-    exact_taken = false;
-    if (certainly_dissimilar(H, 0.5 * (Gp + Gq) - half_h_thr2, 0.5 * (Gp + Gq), h)) return false;
-    exact_taken = true;
-    double rm, md;
-    exact_rmsd_maxdev(p, q, h, H, Gp, Gq, rm, md, sub, lpp);
-    return rm < thr && md < maxdev_thr;
-}
-
 #ifndef TSC_SIEVE_OCC2
 #define TSC_SIEVE_OCC2 5
 #endif
@@ -793,8 +60,8 @@ __device__ inline bool pair_is_similar(const double *__restrict__ p, const doubl
 #define TSC_SIEVE_OCC1 6
 #endif
 // What the pair kernel of a single-rank run does when the LAST work item of a row tile finishes: it applies the tile's
-// verdicts (apply_wave_rows, rmsd.hpp) -- no k_apply_pass launch behind the pair kernel.  tickets = null: that is all, the pass is
-// left open and the first kernel of the next pass closes it (rmsd.hpp, pass_derive).  Otherwise (a rank-partitioned pass) the tile
+// verdicts (apply_wave_rows, pass_state.hpp) -- no k_apply_pass launch behind the pair kernel.  tickets = null: that is all, the pass is
+// left open and the first kernel of the next pass closes it (pass_state.hpp, pass_derive).  Otherwise (a rank-partitioned pass) the tile
 // that was the last of the pass closes it (pass_step_wave).  Work items of a tile = its column segments that start
 // below the tile's largest stop column (the others leave at their first test and do not count).
 struct FusedApply {
@@ -820,7 +87,7 @@ __device__ __forceinline__ void sieve_item(const double *__restrict__ heavy, con
     // an entry packs the row (4 bits) and the column offset inside the segment (12 bits: segments are <= 4096 columns)
     __shared__ unsigned short s_queue[4][QCAP];
     __shared__ unsigned short s_exq[4][128];  // pairs that the sign test could not reject, waiting for the exact path
-    __shared__ double s_jacobi[4][32];        // scratch of the Jacobi fallback of the exact path (rmsd.hpp), per wavefront
+    __shared__ double s_jacobi[4][32];        // scratch of the Jacobi fallback of the exact path (pair_math.hpp), per wavefront
     constexpr int RS = TRIM ? 20 : DW;  // floats per row record in LDS; TRIM: 16 components, the two squared norms, 2 of padding (80 B)
     __shared__ __attribute__((aligned(16))) float s_rowdesc[4][TI * RS];
     __shared__ f32x2 s_rownorm[4][TRIM ? 1 : TI];  // |row descriptor|^2 per family (TRIM keeps them in the row record)
@@ -1237,7 +504,7 @@ inline __global__ __launch_bounds__(256, CPL == 4 ? 4 : (CPL == 2 ? TSC_SIEVE_OC
             count_add(counters, unsigned(slot), CNT_EVALUATED, ev_total);
             count_add(counters, unsigned(slot), CNT_REMOVED, rm_total);
         }
-        if (!fa.tickets) {  // the pass is left open: the first kernel of the next one closes it behind the kernel boundary (rmsd.hpp, pass_derive)
+        if (!fa.tickets) {  // the pass is left open: the first kernel of the next one closes it behind the kernel boundary (pass_state.hpp, pass_derive)
             TSC_STAMP(5);
             return;
         }
