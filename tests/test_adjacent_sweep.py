@@ -1,4 +1,4 @@
-"""Shape sweeps of the "adjacent row" kernels (tscode_amd/csrc/tfd.hpp, moi.hpp, launched from adjacent.hip) at the sizes and edges the
+"""Shape sweeps of the "adjacent row" kernels (tscode_amd/csrc/tfd_kernels.hpp, moi_kernels.hpp, launched from adjacent.hip) at the sizes and edges the
 fixture tests do not reach: grid-stride loops past one pass of the grid, clamped chunk geometries, first hits many 64-column steps
 away, degenerate inertia tensors, signed and non-finite denominators.
 

@@ -82,13 +82,16 @@ def test_the_symbol_is_in_the_header_and_the_prototype_table():
 
 def test_every_kernel_of_diverse_hpp_is_a_wrapper_of_a_device_function_the_batch_calls_too():
     """The promise of the same bits rests on the single and the segmented kernel calling ONE function."""
-    single = open(os.path.join(ROOT, "tscode_amd", "csrc", "diverse.hpp")).read()
-    batch = open(os.path.join(ROOT, "tscode_amd", "csrc", "diverse_batch.hpp")).read()
+    csrc = os.path.join(ROOT, "tscode_amd", "csrc")
+    single = open(os.path.join(csrc, "diverse.hpp")).read()
+    # (the wrapper kernels: diverse_kernels.hpp, which diverse.hip alone includes, and k_align_structures in diverse_align_kernel.hpp)
+    wrappers = open(os.path.join(csrc, "diverse_kernels.hpp")).read() + open(os.path.join(csrc, "diverse_align_kernel.hpp")).read()
+    batch = open(os.path.join(csrc, "diverse_batch.hpp")).read()
     for body in ("dv_align_structures", "dv_col_partial", "dv_col_finish", "dv_sum_fixed", "dv_row_norms", "dv_kmeans_assign", "dv_label_count",
                  "dv_label_bucket", "dv_own_d2", "dv_kmeans_relocate", "dv_kmeans_update", "dv_kmeans_control", "dv_kmeans_seed_update",
                  "dv_kmeans_seed_pick", "dv_diverse_pick"):
         assert len(re.findall(r"__device__ inline void " + body + r"\(", single)) == 1, body
-        assert re.search(r"\n    " + body + r"(<NT>)?\(", single), f"{body}: no wrapper kernel in diverse.hpp"
+        assert re.search(r"\n    " + body + r"(<NT>)?\(", wrappers), f"{body}: no wrapper kernel in diverse_kernels.hpp"
         assert re.search(r"\b" + body + r"(<NT>)?\(", batch), f"{body}: not called by diverse_batch.hpp"
 
 

@@ -2,7 +2,7 @@
 the prune's descriptors -- at the sizes where each mechanism begins or ends.  References: the oracle (transform_batch, compenetration_mask,
 clash_margin, prune_heavy) and NumPy in float64.
 
-A.  k_clash_lanes_multi (csrc/embed_clash.hpp) through embed_clash_mask_dev, threshold 1.5, no clash allowed, against the oracle's embed +
+A.  k_clash_lanes_multi (csrc/embed_clash_kernels.hpp) through embed_clash_mask_dev, threshold 1.5, no clash allowed, against the oracle's embed +
     compenetration_mask, and the same call under clash_lanes = 0 (k_clash) and clash_fp32 = 0 (the float64 count).  Every mask starts as
     0xAA bytes and must come back as zeros and ones.
   random    fragments are Gaussian blobs (sigma 1.6 A), several conformers each, the conformer of a pose drawn at random, random rotations,
@@ -20,7 +20,7 @@ A.  k_clash_lanes_multi (csrc/embed_clash.hpp) through embed_clash_mask_dev, thr
             from 0 to +-1e-3, the rest is far away -- for each of the three pairs; then the first pair inside the band while (m1, m3) clashes
             clearly, and the reverse.  Compared from |eps| >= 1e-9 on (below that the last bits of the embedding decide);
   non-finite a NaN translation, an all-infinite pose, one infinite coordinate of a conformer: count(D < thresh) <= 0 decides.
-B.  compact_rows_dev / gather_heavy_dev (csrc/scan.hpp) bit for bit against NumPy's src[mask != 0] at the row counts around the scan's 8-byte
+B.  compact_rows_dev / gather_heavy_dev (csrc/scan_kernels.hpp, gather_rows.hpp) bit for bit against NumPy's src[mask != 0] at the row counts around the scan's 8-byte
     load, its 2048-byte tile, more than 256 scan blocks and more output words than the gather's grid holds threads; embed_clash_compact_dev
     and embed_masked_dev (k_transform with an index list and a slot table) at selected counts around TR_POSES = 32, with heavy-atom patterns
     of every kind, against the oracle within 4 * 2^-53 (|R| |x| + |t|) per component (three products, three sums, fused or not), the

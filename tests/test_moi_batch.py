@@ -1,4 +1,4 @@
-"""prune_by_moment_of_inertia_batch: the moment-of-inertia prune of many ensembles per call (tscode_amd/csrc/moi.hpp, refine_batch.hip,
+"""prune_by_moment_of_inertia_batch: the moment-of-inertia prune of many ensembles per call (tscode_amd/csrc/moi.hpp, refine_batch.hpp, refine_batch.hip,
 tscode_amd/optimization_methods.py).  The yardstick is the single-ensemble path on the same segment (Engine.inertia_moments,
 Engine.moi_first_similar, prune_by_moment_of_inertia) or the reference's recorded results (G9), never the batch code itself."""
 

@@ -1,5 +1,5 @@
 """prune_rmsd_rot_corr_arrays_batch: the symmetry-corrected RMSD prune of many ensembles per call (tscode_amd/csrc/rot_corr.hpp,
-refine_batch.hip, tscode_amd/rot_corr.py).  The yardstick is always the reference's recorded run (G19), the single-ensemble call on the
+refine_batch.hpp, refine_batch.hip, tscode_amd/rot_corr.py).  The yardstick is always the reference's recorded run (G19), the single-ensemble call on the
 same segment or the numpy restatement of test_rot_corr_sweep.py, never the batch code itself."""
 
 import os

@@ -2,12 +2,14 @@
 // gfx950 only.  There is deliberately no CPU implementation behind these entry points.
 #include "host.hpp"
 #include "call.hpp"
-#include "scan.hpp"
+#include "embed_transform.hpp"
+#include "scan_kernels.hpp"
+#include "gather_rows.hpp"
 #include "prune_api.hpp"
 #include "group_filter.hpp"
-#include "csearch.hpp"
-#include "tfd.hpp"
-#include "moi.hpp"
+#include "csearch_kernels.hpp"
+#include "tfd_kernels.hpp"
+#include "moi_kernels.hpp"
 #include "host_order.hpp"
 #include "trimolecular.hpp"
 #include "embed_prune_plan.hpp"
@@ -522,7 +524,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_cyclical_embed_params(
 // --------------------------------------------------------------------------------------------------
 // the embed loops as drivers: string_embed (tscode/embeds.py:91-120) and cyclical_embed (:636-717, :771-847)
 
-// is_new_structure over fingerprints on the device (tfd.hpp): super-blocks of TG_SUPER candidates, three launches each.
+// is_new_structure over fingerprints on the device (tfd.hpp, tfd_kernels.hpp): super-blocks of TG_SUPER candidates, three launches each.
 // d_acc u8[n], d_list i32[n], d_nk i32[1] (the number kept, on the device)
 static int launch_tfd_greedy(tsc_ctx *c, Scratch &s, const float *d_tf, int64_t n, int T, double thresh, uint8_t *d_acc, int32_t *d_list, int32_t *d_nk) {
     TSC_REQUIRE(T <= 12288, "fingerprints of %d torsions: the greedy filter takes up to 12288", T);

@@ -3,7 +3,7 @@
 // behind these entry points.
 #include "host.hpp"
 #include "call.hpp"
-#include "diverse.hpp"
+#include "diverse_kernels.hpp"
 
 #include <algorithm>
 #include <climits>

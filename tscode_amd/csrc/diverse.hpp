@@ -18,7 +18,7 @@
 //   k_kmeans_seed_update / k_kmeans_seed_pick   k-means++ without local trials, the uniforms given by the caller.
 //
 // Every kernel's body is a __device__ function (dv_*) of the problem's own pointers and sizes and of the workgroup's place in the
-// problem's own grid; the __global__ kernel here is its one-line wrapper.  The kernels of diverse_batch.hpp, which serve many ensembles
+// problem's own grid; the __global__ kernel (diverse_kernels.hpp; none here) is its one-line wrapper.  The kernels of diverse_batch.hpp, which serve many ensembles
 // per launch, look up (segment, local workgroup) and call the same function: a segment's sums are taken in the order the single call
 // takes them, and its results are the single call's bit for bit.
 #pragma once
@@ -97,10 +97,6 @@ __device__ inline void dv_align_structures(const double *__restrict__ in, int64_
         o[3 * a + 2] = R20 * px + R21 * py + R22 * pz;
     }
 }
-inline __global__ __launch_bounds__(256) void k_align_structures(const double *__restrict__ in, int64_t N, int n, const int32_t *__restrict__ idx,
-                                                                 int n_idx, double *__restrict__ out) {
-    dv_align_structures(in, N, n, idx, n_idx, out, blockIdx.x);
-}
 
 // ---------------------------------------------------------------------------------------------------
 // column statistics of X[N, D] in a fixed order: grid (ceil(D / 64), chunks), 256 threads = 64 columns x 4 row lanes
@@ -120,9 +116,6 @@ __device__ inline void dv_col_partial(const double *__restrict__ X, int64_t N, i
     __syncthreads();
     if (g == 0 && d < D) part[size_t(by) * D + d] = ((s[0][col] + s[1][col]) + s[2][col]) + s[3][col];
 }
-inline __global__ __launch_bounds__(256) void k_col_partial(const double *__restrict__ X, int64_t N, int D, int squares, double *__restrict__ part) {
-    dv_col_partial(X, N, D, squares, part, blockIdx.x, blockIdx.y, gridDim.y);
-}
 // out[d] = scale * sum over the chunks, in chunk order
 __device__ inline void dv_col_finish(const double *__restrict__ part, int chunks, int D, double scale, double *__restrict__ out, int block) {
     const int d = block * 256 + threadIdx.x;
@@ -130,18 +123,6 @@ __device__ inline void dv_col_finish(const double *__restrict__ part, int chunks
     double acc = 0.0;
     for (int q = 0; q < chunks; ++q) acc += part[size_t(q) * D + d];
     out[d] = acc * scale;
-}
-inline __global__ __launch_bounds__(256) void k_col_finish(const double *__restrict__ part, int chunks, int D, double scale, double *__restrict__ out) {
-    dv_col_finish(part, chunks, D, scale, out, blockIdx.x);
-}
-// X[i, d] += sign * v[d]
-inline __global__ __launch_bounds__(256) void k_shift_cols(double *__restrict__ X, int64_t rows, int D, const double *__restrict__ v, double sign) {
-    const int64_t total = rows * D;
-    for (int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x; e < total; e += int64_t(gridDim.x) * 256) X[e] += sign * v[e % D];
-}
-inline __global__ __launch_bounds__(256) void k_gather_rows(const double *__restrict__ X, int D, const int32_t *__restrict__ rows, int k, double *__restrict__ out) {
-    const int64_t total = int64_t(k) * D;
-    for (int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x; e < total; e += int64_t(gridDim.x) * 256) out[e] = X[int64_t(rows[e / D]) * D + e % D];
 }
 // out[0] = scale * sum v[0 .. n) in a fixed order: one workgroup of 1024, a contiguous piece per thread, then a tree
 __device__ inline void dv_sum_fixed(const double *__restrict__ v, int64_t n, double scale, double *__restrict__ out) {
@@ -157,9 +138,6 @@ __device__ inline void dv_sum_fixed(const double *__restrict__ v, int64_t n, dou
     }
     if (threadIdx.x == 0) out[0] = s[0] * scale;
 }
-inline __global__ __launch_bounds__(1024) void k_sum_fixed(const double *__restrict__ v, int64_t n, double scale, double *__restrict__ out) {
-    dv_sum_fixed(v, n, scale, out);
-}
 // out[r] = |X[r]|^2, one wavefront per row
 __device__ inline void dv_row_norms(const double *__restrict__ X, int64_t rows, int D, double *__restrict__ out, int64_t block) {
     const int lane = threadIdx.x & 63;
@@ -172,9 +150,6 @@ __device__ inline void dv_row_norms(const double *__restrict__ X, int64_t rows, 
     }
     acc = dv_wave_sum(acc);
     if (lane == 0) out[r] = acc;
-}
-inline __global__ __launch_bounds__(256) void k_row_norms(const double *__restrict__ X, int64_t rows, int D, double *__restrict__ out) {
-    dv_row_norms(X, rows, D, out, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -248,12 +223,6 @@ __device__ inline void dv_kmeans_assign(const double *__restrict__ X, int64_t N,
     }
     if (diff) atomicAdd(changed, diff);
 }
-template <int NT>
-__global__ __launch_bounds__(256) void k_kmeans_assign(const double *__restrict__ X, int64_t N, int D, const double *__restrict__ C, int k,
-                                                       const double *__restrict__ xn, const double *__restrict__ cn, int32_t *__restrict__ labels,
-                                                       double *__restrict__ own_d2, int *__restrict__ changed) {
-    dv_kmeans_assign<NT>(X, N, D, C, k, xn, cn, labels, own_d2, changed, blockIdx.x);
-}
 
 // own_d2[i] = |x_i - C[labels[i]]|^2 by direct differences, one wavefront per row.  only_if_empty: nothing to do unless a cluster is
 // empty (the relocation is what needs the exact values; the assignment's come from the expanded form)
@@ -277,11 +246,6 @@ __device__ inline void dv_own_d2(const double *__restrict__ X, int64_t N, int D,
     acc = dv_wave_sum(acc);
     if (lane == 0) own_d2[i] = acc;
 }
-inline __global__ __launch_bounds__(256) void k_own_d2(const double *__restrict__ X, int64_t N, int D, const double *__restrict__ C,
-                                                       const int32_t *__restrict__ labels, const int32_t *__restrict__ counts, int k, int only_if_empty,
-                                                       double *__restrict__ own_d2) {
-    dv_own_d2(X, N, D, C, labels, counts, k, only_if_empty, own_d2, blockIdx.x);
-}
 
 // ---------------------------------------------------------------------------------------------------
 // rows by label
@@ -301,9 +265,6 @@ __device__ inline void dv_label_count(const int32_t *__restrict__ labels, int64_
     for (int64_t i = threadIdx.x; i < N; i += 256) mine += labels[i] == c;
     const int total = dv_block_sum_int(mine, s);
     if (threadIdx.x == 0) counts[c] = total;
-}
-inline __global__ __launch_bounds__(256) void k_label_count(const int32_t *__restrict__ labels, int64_t N, int32_t *__restrict__ counts) {
-    dv_label_count(labels, N, counts, blockIdx.x);
 }
 // members[offs[c] .. offs[c] + counts[c]) = the rows of cluster c, ascending
 __device__ inline void dv_label_bucket(const int32_t *__restrict__ labels, int64_t N, const int32_t *__restrict__ counts, int k, int32_t *__restrict__ offs,
@@ -330,10 +291,6 @@ __device__ inline void dv_label_bucket(const int32_t *__restrict__ labels, int64
         if (is) members[base + pre + __popcll(b & ((1ull << lane) - 1ull))] = int32_t(i);
         base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
     }
-}
-inline __global__ __launch_bounds__(256) void k_label_bucket(const int32_t *__restrict__ labels, int64_t N, const int32_t *__restrict__ counts, int k,
-                                                             int32_t *__restrict__ offs, int32_t *__restrict__ members) {
-    dv_label_bucket(labels, N, counts, k, offs, members, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -397,10 +354,6 @@ __device__ inline void dv_kmeans_relocate(const double *__restrict__ own_d2, int
         __syncthreads();
     }
 }
-inline __global__ __launch_bounds__(256) void k_kmeans_relocate(const double *__restrict__ own_d2, int64_t N, const int32_t *__restrict__ labels,
-                                                                const int32_t *__restrict__ counts, int k, KmControl *__restrict__ ctl) {
-    dv_kmeans_relocate(own_d2, N, labels, counts, k, ctl);
-}
 
 // grid (k, ceil(D / 64)); 256 threads = 64 columns x 4 member lanes.  C is updated in place; shift_part[c * slices + slice] = the
 // slice's share of |C_new[c] - C[c]|^2
@@ -436,21 +389,12 @@ __device__ inline void dv_kmeans_update(const double *__restrict__ X, int D, con
     sh = dv_wave_sum(sh);
     if (col == 0) shift_part[size_t(c) * slices + slice] = sh;
 }
-inline __global__ __launch_bounds__(256) void k_kmeans_update(const double *__restrict__ X, int D, const int32_t *__restrict__ members,
-                                                              const int32_t *__restrict__ offs, const int32_t *__restrict__ counts,
-                                                              const KmControl *__restrict__ ctl, double *__restrict__ C, double *__restrict__ shift_part) {
-    dv_kmeans_update(X, D, members, offs, counts, ctl, C, shift_part, blockIdx.x, blockIdx.y, gridDim.y);
-}
 // one wavefront: the iteration's shift, in a fixed order
 __device__ inline void dv_kmeans_control(const double *__restrict__ shift_part, int n_part, const int *__restrict__ changed, KmControl *__restrict__ ctl) {
     double acc = 0.0;
     for (int q = threadIdx.x; q < n_part; q += 64) acc += shift_part[q];
     acc = dv_wave_sum(acc);
     if (threadIdx.x == 0) ctl->shift = acc, ctl->changed = *changed;
-}
-inline __global__ __launch_bounds__(64) void k_kmeans_control(const double *__restrict__ shift_part, int n_part, const int *__restrict__ changed,
-                                                              KmControl *__restrict__ ctl) {
-    dv_kmeans_control(shift_part, n_part, changed, ctl);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -506,12 +450,6 @@ __device__ inline void dv_diverse_pick(const double *__restrict__ X, int n, cons
         picked[c] = members[m0 + bp];
     }
 }
-inline __global__ __launch_bounds__(256) void k_diverse_pick(const double *__restrict__ X, int n, const int32_t *__restrict__ members,
-                                                             const int32_t *__restrict__ offs, const int32_t *__restrict__ counts,
-                                                             const double *__restrict__ C, int k, const double *__restrict__ energies,
-                                                             int32_t *__restrict__ picked) {
-    dv_diverse_pick(X, n, members, offs, counts, C, k, energies, picked, blockIdx.x);
-}
 
 // ---------------------------------------------------------------------------------------------------
 // k-means++ seeding without local trials.  rows[j] is the seed chosen last; min_d2[i] = min(min_d2[i], |x_i - x_rows[j]|^2)
@@ -528,10 +466,6 @@ __device__ inline void dv_kmeans_seed_update(const double *__restrict__ X, int64
     }
     acc = dv_wave_sum(acc);
     if (lane == 0) min_d2[i] = (j == 0 || acc < min_d2[i]) ? acc : min_d2[i];
-}
-inline __global__ __launch_bounds__(256) void k_kmeans_seed_update(const double *__restrict__ X, int64_t N, int D, const int32_t *__restrict__ rows, int j,
-                                                                   double *__restrict__ min_d2) {
-    dv_kmeans_seed_update(X, N, D, rows, j, min_d2, blockIdx.x);
 }
 // rows[j] = the first row whose running sum of min_d2 (row order) exceeds u[j] * total.  One workgroup of 1024: a contiguous piece
 // per thread, a scan of the pieces' sums, then the piece that crosses the target is walked again.
@@ -571,10 +505,6 @@ __device__ inline void dv_kmeans_seed_pick(const double *__restrict__ min_d2, in
         }
         rows[j] = int32_t(pick);
     }
-}
-inline __global__ __launch_bounds__(1024) void k_kmeans_seed_pick(const double *__restrict__ min_d2, int64_t N, const double *__restrict__ u, int j,
-                                                                  int32_t *__restrict__ rows) {
-    dv_kmeans_seed_pick(min_d2, N, u, j, rows);
 }
 
 // ---------------------------------------------------------------------------------------------------

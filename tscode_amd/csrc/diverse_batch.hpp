@@ -12,6 +12,7 @@
 // anything another workgroup writes inside a launch; the host reads one DvSummary per iteration and stops when no segment is live.
 #pragma once
 #include "diverse.hpp"
+#include "diverse_align_kernel.hpp"
 
 namespace tsc {
 

@@ -2,7 +2,10 @@
 // gfx950 only.  There is deliberately no CPU implementation behind these entry points.
 #include "host.hpp"
 #include "call.hpp"
-#include "scan.hpp"
+#include "embed_transform.hpp"
+#include "embed_clash_kernels.hpp"
+#include "scan_kernels.hpp"
+#include "gather_rows.hpp"
 
 // --------------------------------------------------------------------------------------------------
 // K1
@@ -105,11 +108,11 @@ static int launch_clash(tsc_ctx *c, const ClashArgs &a, const double *coords, co
                         const int32_t *conf_idx, const double *rot, const double *pos, uint8_t *mask, int32_t *counts) {
     if (a.n_poses == 0) return 0;
     if (a.self_mode) return launch_clash_impl<FUSED, true, false>(c, a, coords, frags, ft, conf_idx, rot, pos, mask, counts);
-    // verdict only and no clash allowed: the packed-fp32 minimum with its fp64 fallback (embed_clash.hpp)
+    // verdict only and no clash allowed: the packed-fp32 minimum with its fp64 fallback (embed_clash_kernels.hpp)
     const bool minmode = !counts && a.max_clashes == 0 && c->opt.clash_fp32 != 0 && 4 * clash_lds_per_wave(a.n, a.lp, true) <= 160 * 1024;
     if (minmode && FUSED && c->opt.clash_lanes != 0 && a.n_mols == 2 && ft.n_mols == 2 && a.atom_off[1] == ft.atom_off[1] && a.n == ft.n_total &&
         std::min(ft.n_atoms[0], ft.n_atoms[1]) >= 1 && std::min(ft.n_atoms[0], ft.n_atoms[1]) <= 32) {
-        // one pose per lane, the smaller fragment in registers (embed_clash.hpp, k_clash_lanes)
+        // one pose per lane, the smaller fragment in registers (embed_clash_kernels.hpp, k_clash_lanes)
         const int mA = ft.n_atoms[0] <= ft.n_atoms[1] ? 0 : 1, mB = 1 - mA, na2 = (ft.n_atoms[mA] + 1) / 2;
         const dim3 grid(unsigned(grid_for(ceil_div<int64_t>(a.n_poses, 64), 4, 256 * 32)));
 #define TSC_LAUNCH_CLASH_LANES(N)                                                                                                          \
@@ -126,7 +129,7 @@ static int launch_clash(tsc_ctx *c, const ClashArgs &a, const double *coords, co
     if (minmode && FUSED && c->opt.clash_lanes != 0 && (a.n_mols == 2 || a.n_mols == 3) && ft.n_mols == a.n_mols && a.n == ft.n_total &&
         a.atom_off[1] == ft.atom_off[1] && (a.n_mols == 2 || a.atom_off[2] == ft.atom_off[2])) {
         // one pose per lane for fragments of any size and for three of them: the "A" fragment of every pair in register tiles, the poses
-        // packed again between the fragment pairs (embed_clash.hpp, k_clash_lanes_multi).  The tile size that wastes the fewest padded
+        // packed again between the fragment pairs (embed_clash_kernels.hpp, k_clash_lanes_multi).  The tile size that wastes the fewest padded
         // distances over the pairs (numba_functions.py:87-105: (m2, m1), (m3, m2), (m1, m3)), the B atoms embedded once per tile counted in
         auto cost = [&](int na2) {
             int64_t w = 0;

@@ -5,9 +5,11 @@
 // diagonalize does), then one wavefront per row looks for the first j > i whose three moments all lie within
 // max_deviation (relative to row i's) -- the same launch shape as the torsion-fingerprint search (tfd.hpp).  The graph
 // step of prune_by_moment_of_inertia stays on the host (tscode_amd/optimization_methods.py).
+//
+// No kernel here: the device functions.  The kernels of one ensemble and k_embed_scores are in moi_kernels.hpp, those that take many
+// ensembles per launch in refine_batch.hpp.
 #pragma once
 #include "common.hpp"
-#include "tfd.hpp"
 
 namespace tsc {
 
@@ -63,14 +65,8 @@ __device__ inline void inertia_moments_of(const double *__restrict__ c, int n, c
     out[0] = e0, out[1] = e1, out[2] = e2;
 }
 
-inline __global__ __launch_bounds__(256) void k_inertia_moments(const double *__restrict__ structures, int64_t N, int n, const double *__restrict__ masses,
-                                                          double *__restrict__ out) {
-    for (int64_t s = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; s < N; s += int64_t(gridDim.x) * blockDim.x)
-        inertia_moments_of(structures + s * n * 3, n, masses, out + 3 * s);
-}
-
 // Row i of the pair search (algebra.py:188-205) over the moments mo[N][3], by one wavefront: the first j > i with
-// all(|im_i - im_j| / im_i < max_deviation), -1 if none.  The same value in every lane; both kernels below call this.
+// all(|im_i - im_j| / im_i < max_deviation), -1 if none.  The same value in every lane; k_moi_first_similar and k_moi_first_similar_seg call this.
 __device__ inline int32_t moi_first_similar_row(const double *__restrict__ mo, int64_t N, int64_t i, double max_deviation, int lane) {
     const double a0 = mo[3 * i], a1 = mo[3 * i + 1], a2 = mo[3 * i + 2];
     int32_t found = -1;
@@ -82,67 +78,6 @@ __device__ inline int32_t moi_first_similar_row(const double *__restrict__ mo, i
         if (m) found = int32_t(j0 + (__ffsll((long long)m) - 1));
     }
     return found;
-}
-
-// algebra.py:188-205: first[i] = moi_first_similar_row of row i
-inline __global__ __launch_bounds__(256) void k_moi_first_similar(const double *__restrict__ mo, int64_t N, double max_deviation, int32_t *__restrict__ first) {
-    const int lane = threadIdx.x & 63;
-    for (int64_t i = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); i < N; i += int64_t(gridDim.x) * 4) {
-        const int32_t found = moi_first_similar_row(mo, N, i, max_deviation, lane);
-        if (lane == 0) first[i] = found;
-    }
-}
-
-// ---- many ensembles per launch (refine_batch.hip) ------------------------------------------------------------------------------
-// Segment s is an ensemble of its own: N structures of n atoms at structures + coord0 with the masses at masses + mass0.  The rows of
-// all segments are numbered through (row0 is a segment's first number); a row finds its segment by that table, its moments lie at
-// out + 3 * (row0 + i), and row i searches j > i inside its own segment only: first[row0 + i] is an index INSIDE the segment.
-struct MoiSegment {
-    int64_t row0, coord0, mass0;
-    double max_deviation;
-    int32_t N, n;
-};
-
-inline __global__ __launch_bounds__(256) void k_inertia_moments_seg(const double *__restrict__ structures, const double *__restrict__ masses,
-                                                              const MoiSegment *__restrict__ segs, int n_segs, int64_t total_rows,
-                                                              double *__restrict__ out) {
-    for (int64_t r = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; r < total_rows; r += int64_t(gridDim.x) * blockDim.x) {
-        const MoiSegment g = segs[tfd_last_not_above(segs, n_segs, r, [](const MoiSegment &q) { return q.row0; })];
-        inertia_moments_of(structures + g.coord0 + (r - g.row0) * g.n * 3, g.n, masses + g.mass0, out + 3 * r);
-    }
-}
-
-inline __global__ __launch_bounds__(256) void k_moi_first_similar_seg(const double *__restrict__ mo, const MoiSegment *__restrict__ segs, int n_segs,
-                                                                int64_t total_rows, int32_t *__restrict__ first) {
-    const int lane = threadIdx.x & 63;
-    for (int64_t r = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); r < total_rows; r += int64_t(gridDim.x) * 4) {
-        const MoiSegment g = segs[tfd_last_not_above(segs, n_segs, r, [](const MoiSegment &q) { return q.row0; })];
-        const int32_t found = moi_first_similar_row(mo + 3 * g.row0, g.N, r - g.row0, g.max_deviation, lane);
-        if (lane == 0) first[r] = found;
-    }
-}
-
-// numba_functions.py:273-288 _score_embed_poses (float32 accumulator, as the reference's array) and the signed error of
-// fitness_check (optimization_methods.py:544-557; a NaN target stands for None and is skipped)
-inline __global__ __launch_bounds__(256) void k_embed_scores(const double *__restrict__ structures, int64_t N, int n, const int32_t *__restrict__ indices,
-                                                       const double *__restrict__ distances, int n_c, float *__restrict__ scores,
-                                                       double *__restrict__ fitness_error) {
-    for (int64_t s = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; s < N; s += int64_t(gridDim.x) * blockDim.x) {
-        const double *c = structures + s * n * 3;
-        float sc = 0.0f;
-        double err = 0.0;
-        for (int i = 0; i < n_c; ++i) {
-            const int a = indices[(s * n_c + i) * 2], b = indices[(s * n_c + i) * 2 + 1];
-            const double dx = c[3 * a] - c[3 * b], dy = c[3 * a + 1] - c[3 * b + 1], dz = c[3 * a + 2] - c[3 * b + 2];
-            const double dist = sqrt(dx * dx + dy * dy + dz * dz), target = distances[s * n_c + i];
-            if (target == target) {
-                sc = float(double(sc) + fabs(dist - target));
-                err += dist - target;
-            }
-        }
-        scores[s] = sc;
-        fitness_error[s] = err;
-    }
 }
 
 }  // namespace tsc

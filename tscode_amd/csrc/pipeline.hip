@@ -1,7 +1,8 @@
 // pipeline.hip -- the fused device pipeline: embed -> clash mask -> ordered compaction -> RMSD prune on resident buffers
 // gfx950 only.  There is deliberately no CPU implementation behind these entry points.
 #include "host.hpp"
-#include "scan.hpp"
+#include "embed_transform.hpp"
+#include "scan_kernels.hpp"
 #include "prune_api.hpp"
 #include "descriptor_basis.hpp"
 #include "describe.hpp"

@@ -2,6 +2,8 @@
 // gfx950 only.  There is deliberately no CPU implementation behind these entry points.
 #include "call.hpp"
 #include "prune_host.hpp"
+#include "cull_layout.hpp"
+#include "mm_kernels.hpp"
 #include "rmsd.hpp"
 #include "descriptor_kernels.hpp"
 #include "describe.hpp"

@@ -5,8 +5,7 @@
 // implementation behind these entry points.
 #include "host.hpp"
 #include "call.hpp"
-#include "moi.hpp"
-#include "rot_corr.hpp"
+#include "refine_batch.hpp"
 
 #include <algorithm>
 #include <memory>

@@ -727,8 +727,4 @@ inline __global__ __launch_bounds__(256) void k_export_run(const unsigned long l
     }
 }
 
-inline __global__ void k_fill_i32(int32_t *p, int64_t n, int32_t v) {
-    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) p[i] = v;
-}
-
 }  // namespace tsc

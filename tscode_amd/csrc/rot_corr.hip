@@ -2,7 +2,7 @@
 // gfx950 only.  There is deliberately no CPU implementation behind these entry points.
 #include "host.hpp"
 #include "call.hpp"
-#include "rot_corr.hpp"
+#include "rot_corr_kernels.hpp"
 
 #include <algorithm>
 #include <climits>

@@ -18,6 +18,9 @@
 // The Kabsch step is the exact path of pair_math.hpp (Horn's quaternion: Newton + adjugate, Jacobi when that degenerates) on the
 // 3x3 correlation S = ref_sub^T coord_sub reduced across the wave; the quaternion rotation of rot_mat_from_pointer_dev
 // (csearch.hpp) turns the atoms.
+//
+// No kernel here: arguments, device functions and the host's check of a set-up.  k_rot_corr_pass and k_rot_corr_pairs are in
+// rot_corr_kernels.hpp, k_rot_corr_pass_seg (many ensembles per launch) in refine_batch.hpp.
 #pragma once
 #include "common.hpp"
 #include "csearch.hpp"
@@ -163,65 +166,6 @@ __device__ inline void rot_corr_chunk(const RotCorrArgs &a, double *__restrict__
     }
     __syncthreads();
     if (threadIdx.x == 0 && *s_count) atomicAdd(evaluated, (unsigned long long)*s_count);
-}
-
-// One pass (:1080-1152 without the graph step): chunk blockIdx.x is [d*step, d*(step+1)), the last one [d*(k-1), num_active).
-// first[i] = the first j of row i that is similar (rmsd < thr), or -1 (left as the caller set it for rows of empty chunks).
-inline __global__ __launch_bounds__(64 * RC_WAVES) void k_rot_corr_pass(RotCorrArgs a, double *__restrict__ coords, int64_t d, int64_t k,
-                                                                        int64_t num_active, double thr, uint32_t *__restrict__ cache,
-                                                                        int64_t words, int32_t *__restrict__ first,
-                                                                        unsigned long long *__restrict__ evaluated) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-    const int64_t step = blockIdx.x;
-    const int64_t lo = d * step, hi = step == k - 1 ? num_active : d * (step + 1);   // :1093-1096
-    rot_corr_chunk(a, coords, cache, words, first, lo, hi, thr, s_raw, evaluated);
-}
-
-// ---- many ensembles per launch (refine_batch.hip) ------------------------------------------------------------------------------
-// One schedule slot of prune_conformers_rmsd_rot_corr (:1080-1152 without the graph step) for the segments whose gate is open in it.
-// Every segment is an ensemble of its own -- its own molecule, set-up, threshold and pass geometry -- with its structures at
-// coords + coord0, its cache rows of `words` words at cache + cache0 and its rows at first + row0; all open segments share k (the
-// schedule is walked in lockstep), so workgroup b serves chunk b % k of segment b / k.  first holds indices INSIDE the segment.
-// dynamic LDS: rot_corr_lds_bytes of the largest open segment; a workgroup lays out its own segment's lists and wave blocks inside it.
-struct RotCorrSegment {
-    RotCorrArgs a;
-    int64_t coord0, cache0, row0;      // in doubles, 32-bit words and rows
-    int64_t words, d, num_active;
-    double thr;
-    unsigned long long *evaluated;     // the segment's pair counter
-};
-
-inline __global__ __launch_bounds__(64 * RC_WAVES) void k_rot_corr_pass_seg(const RotCorrSegment *__restrict__ segs, int64_t k,
-                                                                            double *__restrict__ coords, uint32_t *__restrict__ cache,
-                                                                            int32_t *__restrict__ first) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-    const RotCorrSegment g = segs[blockIdx.x / k];
-    const int64_t step = blockIdx.x % k;
-    const int64_t lo = g.d * step, hi = step == k - 1 ? g.num_active : g.d * (step + 1);   // :1093-1096
-    if (lo >= hi) return;                                   // (block-uniform, in front of the first barrier)
-    rot_corr_chunk(g.a, coords + g.coord0, cache + g.cache0, g.words, first + g.row0, lo, hi, g.thr, s_raw, g.evaluated);
-}
-
-// The value-level form: one wavefront per pair, S[j] turned in LDS only (nothing is written back).
-inline __global__ __launch_bounds__(64 * RC_WAVES) void k_rot_corr_pairs(RotCorrArgs a, const double *__restrict__ coords,
-                                                                         const int32_t *__restrict__ pairs, int64_t n_pairs,
-                                                                         double *__restrict__ rmsd, double *__restrict__ best_angle) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6, n = a.n;
-    const TorsionLists L = torsion_lists_at(s_raw, a.n_tors, n);
-    build_torsion_lists(L, a.masks, a.tors, a.n_tors, n);
-    double *c = reinterpret_cast<double *>(s_raw + torsion_lists_bytes(a.n_tors, n) + size_t(wid) * rot_corr_wave_bytes(n));
-    double *best = c + size_t(n) * 3;
-    for (int64_t p = int64_t(blockIdx.x) * nw + wid; p < n_pairs; p += int64_t(gridDim.x) * nw) {
-        const double *src = coords + int64_t(pairs[2 * p + 1]) * n * 3;
-        for (int e = lane; e < n * 3; e += 64) c[e] = src[e];
-        __builtin_amdgcn_wave_barrier();
-        const double r = rot_corr_pair(a, L, coords + int64_t(pairs[2 * p]) * n * 3, c, best, lane);
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) rmsd[p] = r;
-        for (int t = lane; t < a.n_tors; t += 64) best_angle[p * a.n_tors + t] = best[t];
-        __builtin_amdgcn_wave_barrier();
-    }
 }
 
 // the limits of the ABI (include/tscode_hip.h), checked on the host arrays before anything touches the device (rot_corr.hip, and per

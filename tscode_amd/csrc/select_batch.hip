@@ -5,7 +5,7 @@
 #include "host.hpp"
 #include "call.hpp"
 #include "diverse_batch.hpp"
-#include "tfd.hpp"
+#include "tfd_batch.hpp"
 
 #include <algorithm>
 #include <numeric>

@@ -1,5 +1,5 @@
 """tscode/hypermolecule_class.py on the MI355X engine: align_structures (:38-72), one wavefront per structure
-(csrc/diverse.hpp, k_align_structures)."""
+(csrc/diverse.hpp: dv_align_structures, k_align_structures)."""
 
 from __future__ import annotations
 
