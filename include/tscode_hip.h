@@ -69,6 +69,7 @@ const char *tsc_last_error(void);
 const char *tsc_build_digest(void);
 int tsc_device_count(void); /* >= 0, or a negative tsc_status */
 int tsc_ctx_create(int device, tsc_ctx **out);
+/* (tsc_ctx_destroy takes the objects created from the context that are still alive with it: "objects created from a context", below) */
 int tsc_ctx_destroy(tsc_ctx *ctx);
 /* Run on a caller-provided hipStream_t; NULL = the library's own (non-blocking) stream.  Note that PyTorch's DEFAULT stream has
  * the handle 0 = NULL: to order this library's kernels with torch work (copies, RCCL collectives) make an explicit
@@ -152,6 +153,20 @@ int tsc_memcpy_d2h(tsc_ctx *ctx, void *dst, const void *src, size_t bytes); /* s
 /* HIP-event timing of everything enqueued on the context's stream between begin and end (ms). */
 int tsc_timer_begin(tsc_ctx *ctx);
 int tsc_timer_end(tsc_ctx *ctx, float *elapsed_ms); /* synchronises */
+
+/* ---- objects created from a context ------------------------------------------------------- */
+/* Five kinds of object are created from a context, live longer than one call and hold memory of that context: tsc_prune
+ * (tsc_prune_create), tsc_rot_corr (tsc_rot_corr_begin), tsc_rot_corr_batch (tsc_rot_corr_batch_begin), tsc_embed_prune
+ * (tsc_embed_prune_create) and tsc_xchg (tsc_xchg_create).  One rule holds for all of them:
+ *   - the context lists every such object while it lives;
+ *   - tsc_<kind>_destroy takes the object off the list and frees it: its device blocks go back to the context's scratch cache, a prune
+ *     run's events to the context's pool, an exchange closes the peers' mappings and frees its receive area.  NULL is success.  All but
+ *     tsc_prune_destroy wait for the context's stream first; tsc_prune_destroy does not wait (its blocks are recycled in stream order,
+ *     behind the kernels that still read them), so a run can be created and destroyed per step without a synchronisation;
+ *   - tsc_ctx_destroy waits for the context's streams and then destroys the objects it still lists, newest first, before it frees anything
+ *     of its own: a host whose finalisers run in no particular order leaks nothing and frees nothing twice;
+ *   - a handle is dead after its destroy AND after the destroy of its context: do not hand it to tsc_<kind>_destroy, or to anything else,
+ *     afterwards, and never destroy it twice.  Neither is detected. */
 
 /* ---- K1: batched rigid-body embedding ------------------------------------------------------
  * Replaces get_embed (tscode/embeds.py:961-969) and transform_coords (tscode/algebra.py:390-400),
@@ -577,8 +592,7 @@ int tsc_prune_rmsd_dev(tsc_ctx *ctx, const double *heavy, int64_t n, int h, doub
  *   tsc_embed_prune_poses       which = 0: the survivors, which = 1: every kept pose; poses f64[rows, n_total, 3] in candidate order,
  *                               capacity = rows the buffer holds.  Embedded from the kept parameters by the kernel that embedded them
  *                               for the filter, and only these rows are fetched.
- *   tsc_embed_prune_destroy     frees the run.  A context lists its live runs and destroys them with itself: do not hand a run to
- *                               tsc_embed_prune_destroy after its context is destroyed.
+ *   tsc_embed_prune_destroy     frees the run ("objects created from a context", above).
  * Refused before the device is touched, with a message: a null pointer, n_heavy < 1, a heavy index out of range or not increasing, a
  * capacity below the row count, a mode other than 0 or 1 (TSC_ERR_INVALID); tsc_embed_prune_add_groups after tsc_embed_prune_run, and
  * tsc_embed_prune_poses with which = 0 before it (TSC_ERR_STATE).  The calls of one run must not overlap; they synchronise. */
@@ -659,8 +673,8 @@ int tsc_prune_rmsd_team_dev(tsc_ctx *ctx, const double *heavy, const int64_t *of
  *   tsc_prune_mask_dev gives the device mask; tsc_prune_destroy frees the state. */
 /* A context serves at most 64 live runs at a time (each owns a word of the context's pinned memory; the 65th tsc_prune_create fails with
  * TSC_ERR_STATE).  tsc_prune_create / tsc_prune_destroy take the context's scratch cache: calls of them on ONE context must not overlap
- * (a context is for one thread at a time, see above); runs that exist may then be stepped from different threads.  Runs still alive
- * when their context is destroyed are destroyed with it -- do not hand them to tsc_prune_destroy afterwards. */
+ * (a context is for one thread at a time, see above); runs that exist may then be stepped from different threads.  tsc_prune_destroy and
+ * what becomes of a run that outlives its context: "objects created from a context", above. */
 int tsc_prune_create(tsc_ctx *ctx, const double *heavy_dev, int64_t n, int h, double rmsd_thr, int mode, tsc_prune **out);
 int tsc_prune_next_pass(tsc_prune *p, int64_t *k_out);            /* 0 when the schedule is exhausted; does not wait:
                                                                       the gate of rmsd_pruning.py:192 is evaluated on the
@@ -762,6 +776,7 @@ int tsc_prune_run_sharded(tsc_prune *run, int rank, int world_size, int min_chun
  *   tsc_xchg_status       exchanges made so far and how many of them gave up waiting for a peer (tsc_xchg_set_timeout, default 5 s: a
  *                         rank that died must not hang the others' GPUs); after a timeout the reduced buffers are NOT valid -- check after
  *                         the run's synchronisation.  Every rank must make the same sequence of exchanges (tsc_prune_run_sharded does).
+ *   tsc_xchg_destroy      unmaps the peers and frees the area ("objects created from a context", above)
  * What these messages are: tscode/rmsd_pruning.py:149-157 (disjoint out_mask[first:last] per chunk), :92,101-113 (rows independent). */
 typedef struct tsc_xchg tsc_xchg;
 #define TSC_XCHG_HANDLE_BYTES 64
@@ -815,8 +830,7 @@ int tsc_pipeline_dev(tsc_ctx *ctx, const double *frags, const int64_t *frag_off_
  *                         first i32[n_structs] = absolute index of row i's first similar j, or -1; pairs_evaluated = the pairs the
  *                         reference would have computed in this pass.  Synchronous.
  *   tsc_rot_corr_end      copies the run's (centred, turned) structures to coords_out f64[n_structs, n_atoms, 3].
- *   tsc_rot_corr_destroy  frees the run.  A context lists its live runs and destroys them with itself: do not hand a run to
- *                         tsc_rot_corr_destroy after its context is destroyed.
+ *   tsc_rot_corr_destroy  frees the run ("objects created from a context", above).
  *   tsc_rot_corr_pairs    the value-level form: rotationally_corrected_rmsd(ref = coords[pairs[p, 0]], coord = coords[pairs[p, 1]])
  *                         for every pair on a private copy of the coordinates (nothing is mutated): rmsd f64[n_pairs] and the best
  *                         angle of every torsion, best_angle f64[n_pairs, n_tors]. */
@@ -847,8 +861,7 @@ int tsc_rot_corr_pairs(tsc_ctx *ctx, const double *coords, int64_t n_structs, in
  *                               i32[sum n_structs]: per row of an open segment what tsc_rot_corr_pass gives the segment alone, as an
  *                               index INSIDE the segment; -1 for every other row.  pairs_evaluated i64[n_open].  Synchronous.
  *   tsc_rot_corr_batch_end      copies the structures as the passes left them to coords_out f64[offsets[n_segments]].
- *   tsc_rot_corr_batch_destroy  frees the run.  A context lists its live runs and destroys them with itself: do not hand a run to
- *                               tsc_rot_corr_batch_destroy after its context is destroyed. */
+ *   tsc_rot_corr_batch_destroy  frees the run ("objects created from a context", above). */
 int tsc_rot_corr_batch_begin(tsc_ctx *ctx, const double *coords, const int64_t *offsets, const int32_t *n_structs,
                              const int32_t *n_atoms, const int32_t *heavy, const int32_t *n_heavy, const int32_t *torsions,
                              const int32_t *n_tors, const double *angles, const int32_t *n_angles, const uint8_t *move_mask,

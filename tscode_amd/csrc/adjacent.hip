@@ -14,6 +14,8 @@
 #include "trimolecular.hpp"
 #include "embed_prune_plan.hpp"
 
+#include <memory>
+
 // --------------------------------------------------------------------------------------------------
 // greedy per-group filter
 
@@ -981,11 +983,11 @@ extern "C" __attribute__((visibility("default"))) int tsc_trimolecular_groups(
 // reads) and its parameters (what the pose is embedded from again once the prune has spoken).  Nothing per pose crosses to the host but two
 // flag bytes per candidate and, at the end, the poses that were asked for.
 
-struct tsc_embed_prune {
-    tsc_ctx *ctx = nullptr;
-    FragTable ft;
-    int64_t frag_off[MAX_MOLS];
-    int32_t n_atoms[MAX_MOLS], n_conf[MAX_MOLS];
+struct tsc_embed_prune : Owned {
+    using Owned::Owned;
+    FragTable ft{};
+    int64_t frag_off[MAX_MOLS] = {};
+    int32_t n_atoms[MAX_MOLS] = {}, n_conf[MAX_MOLS] = {};
     int n_heavy = 0;
     double *frags = nullptr;
     int32_t *sel = nullptr;          // i32[n_heavy * 3]: the doubles of a pose that are its heavy atoms' (launch_gather_rows)
@@ -994,11 +996,6 @@ struct tsc_embed_prune {
     uint8_t *survived = nullptr;     // u8[n_kept] once tsc_embed_prune_run has run
     int64_t cap = 0, n_kept = 0, n_survived = 0;
     bool pruned = false;
-    void release_all() {
-        for (void *q : {static_cast<void *>(frags), static_cast<void *>(sel), static_cast<void *>(heavy), static_cast<void *>(rot), static_cast<void *>(pos),
-                        static_cast<void *>(ci), static_cast<void *>(survived)})
-            if (q) ctx->release(q);
-    }
 };
 
 // cand[r] = act[act2[r]]: the candidate of every kept pose, from the candidate of every passing pose and the passing pose of every kept one
@@ -1027,17 +1024,14 @@ static int embed_prune_reserve(tsc_embed_prune *r, int64_t need) {
     const size_t row_bytes[4] = {size_t(r->n_heavy) * 24, size_t(nm) * 72, size_t(nm) * 24, size_t(nm) * 4};
     void *old[4] = {r->heavy, r->rot, r->pos, r->ci}, *grown[4] = {nullptr, nullptr, nullptr, nullptr};
     int rc = 0;
-    for (int i = 0; i < 4 && !rc; ++i) rc = c->alloc(size_t(cap) * row_bytes[i], &grown[i]);
+    for (int i = 0; i < 4 && !rc; ++i) rc = r->take(size_t(cap) * row_bytes[i], &grown[i]);
     for (int i = 0; i < 4 && !rc; ++i)
         if (r->n_kept > 0 && hipMemcpyAsync(grown[i], old[i], size_t(r->n_kept) * row_bytes[i], hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
             rc = fail(TSC_ERR_HIP, "tsc_embed_prune_add_groups: the copy into the grown buffers failed");
-    if (rc) {
-        for (void *q : grown)
-            if (q) c->release(q);
-        return rc;
-    }
-    for (void *q : old)
-        if (q) c->release(q);   // (recycled in stream order: behind the copies)
+    // the run keeps one set of four: the old ones are recycled in stream order, behind the copies
+    void *const *gone = rc ? grown : old;
+    for (int i = 0; i < 4; ++i) r->give_back(gone[i]);
+    if (rc) return rc;
     r->heavy = static_cast<double *>(grown[0]), r->rot = static_cast<double *>(grown[1]), r->pos = static_cast<double *>(grown[2]);
     r->ci = static_cast<int32_t *>(grown[3]);
     r->cap = cap;
@@ -1046,17 +1040,7 @@ static int embed_prune_reserve(tsc_embed_prune *r, int64_t need) {
 
 extern "C" __attribute__((visibility("default"))) int tsc_embed_prune_destroy(tsc_embed_prune *r) {
     TSC_API_GUARD_BEGIN
-    if (!r) return 0;
-    DeviceGuard guard(r->ctx->device);
-    (void)hipStreamSynchronize(r->ctx->stream);
-    {
-        std::lock_guard<std::mutex> lock(r->ctx->runs_mutex);
-        auto &lr = r->ctx->live_embed_prune;
-        lr.erase(std::remove(lr.begin(), lr.end(), r), lr.end());
-    }
-    r->release_all();   // (its blocks go back to the cache)
-    delete r;
-    return 0;
+    return destroy_owned(r);
     TSC_API_GUARD_END
 }
 
@@ -1077,35 +1061,17 @@ extern "C" __attribute__((visibility("default"))) int tsc_embed_prune_create(tsc
         TSC_REQUIRE(a == 0 || heavy_idx[a] > heavy_idx[a - 1], "tsc_embed_prune_create: heavy_idx[%d] = %d does not increase", a, heavy_idx[a]);
         for (int k = 0; k < 3; ++k) sel[size_t(a) * 3 + k] = heavy_idx[a] * 3 + k;
     }
-    DeviceGuard guard(c->device);
-    tsc_embed_prune *r = new tsc_embed_prune();
-    r->ctx = c, r->ft = ft, r->n_heavy = n_heavy;
-    for (int m = 0; m < n_mols; ++m) r->frag_off[m] = frag_off[m], r->n_atoms[m] = n_atoms[m], r->n_conf[m] = n_conf[m];
-    const size_t n_frag = size_t(frags_total_doubles(frag_off, n_atoms, n_conf, n_mols));
-    void *q = nullptr;
-    int rc = c->alloc(n_frag * sizeof(double), &q);
-    if (!rc) {
-        r->frags = static_cast<double *>(q);
-        rc = c->alloc(sel.size() * sizeof(int32_t), &q);
-    }
-    if (!rc) {
-        r->sel = static_cast<int32_t *>(q);
-        hipError_t e = hipMemcpyAsync(r->frags, frags, n_frag * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(r->sel, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-        const hipError_t waited = hipStreamSynchronize(c->stream);   // (the copies read the caller's array and a local one)
-        if (e == hipSuccess) e = waited;
-        if (e != hipSuccess) rc = fail(TSC_ERR_HIP, "tsc_embed_prune_create: the upload of the fragments failed: %s", hipGetErrorString(e));
-    }
-    if (rc) {
-        r->release_all();
-        delete r;
-        return rc;
-    }
-    {
-        std::lock_guard<std::mutex> lock(c->runs_mutex);
-        c->live_embed_prune.push_back(r);   // (destroyed with the context, tsc_ctx_destroy)
-    }
-    *out = r;
+    // the run's blocks are the call's until everything is in place: an error hands them back behind an idle stream
+    HostCall h(c);
+    std::unique_ptr<tsc_embed_prune> run(new tsc_embed_prune(c));
+    run->ft = ft, run->n_heavy = n_heavy;
+    for (int m = 0; m < n_mols; ++m) run->frag_off[m] = frag_off[m], run->n_atoms[m] = n_atoms[m], run->n_conf[m] = n_conf[m];
+    TSC_TRY(h.in(frags, size_t(frags_total_doubles(frag_off, n_atoms, n_conf, n_mols)), &run->frags));
+    TSC_TRY(h.in(sel.data(), sel.size(), &run->sel));
+    TSC_TRY(h.finish());
+    run->take_blocks(h.scratch());
+    c->owned.adopt(run.get());   // (listed once complete: destroyed with the context, tsc_ctx_destroy)
+    *out = run.release();
     return 0;
     TSC_API_GUARD_END
 }
@@ -1179,11 +1145,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_embed_prune_run(tsc_em
         return 0;
     }
     DeviceGuard guard(c->device);
-    if (!r->survived) {
-        void *q = nullptr;
-        TSC_TRY(c->alloc(size_t(r->n_kept), &q));
-        r->survived = static_cast<uint8_t *>(q);
-    }
+    if (!r->survived) TSC_TRY(r->get(size_t(r->n_kept), &r->survived));
     r->pruned = true, r->n_survived = 0;   // (from here on the set of kept poses is closed, whatever becomes of the prune)
     TSC_TRY(tsc_prune_rmsd_dev(c, r->heavy, r->n_kept, r->n_heavy, rmsd_thr, mode, r->survived, stats, n_passes));
     TSC_HIP(hipMemcpyAsync(survived, r->survived, size_t(r->n_kept), hipMemcpyDeviceToHost, c->stream));

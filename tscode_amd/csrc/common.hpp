@@ -17,6 +17,7 @@
 
 #include "../../include/tscode_hip.h"
 #include "options.hpp"
+#include "owned.hpp"
 
 namespace tsc {
 
@@ -109,15 +110,12 @@ struct tsc_ctx {
     const double *xd_heavy = nullptr;     // the heavy-atom array they describe
     bool xd_valid = false;
     int xd_borrowers = 0;                 // live prune runs that read the xd_* buffers (tsc_prune_create borrowed them): no release / regrow meanwhile
-    // Bookkeeping that runs of one context driven from DIFFERENT host threads touch (tsc_prune_create / tsc_prune_destroy): the pinned flag
-    // words handed to runs (prune_api.hpp: PINNED_FLAG_OFFSET; bit s set = word s is some live run's) and the list of live runs, which
-    // tsc_ctx_destroy destroys with the context -- a host whose finalisers run in no particular order cannot leak a run's events.
-    std::mutex runs_mutex;
+    // The objects created from this context that are alive (owned.hpp); tsc_ctx_destroy destroys them with the context -- a host whose
+    // finalisers run in no particular order cannot leak a run's blocks and events, or free them after the context.  The list's mutex also
+    // guards the bookkeeping that prune runs of one context driven from DIFFERENT host threads touch (tsc_prune_create / tsc_prune_destroy):
+    // the pinned flag words handed to runs (prune_api.hpp: PINNED_FLAG_OFFSET; bit s set = word s is some live run's) and xd_borrowers.
+    tsc::OwnedList owned;
     unsigned long long flag_slots_used = 0;
-    std::vector<tsc_prune *> live_runs;
-    std::vector<tsc_rot_corr *> live_rot_corr;  // live runs of the symmetry-corrected prune (rot_corr.hip), destroyed with the context too
-    std::vector<tsc_rot_corr_batch *> live_rot_corr_batch;  // ... and of its many-ensembles form (refine_batch.hip)
-    std::vector<tsc_embed_prune *> live_embed_prune;        // ... and the embed-and-prune runs (adjacent.hip), whose buffers are blocks of this context
     std::vector<int32_t> sample_host;     // pose indices of the basis sample of the last tsc_pipeline_dev call and their device copy
     int32_t *sample_dev = nullptr;
     double *mom_acc = nullptr;            // moment accumulators of the pipeline's basis chain (k_sample_moments adds, k_descriptor_basis clears)
@@ -166,25 +164,6 @@ struct tsc_ctx {
 
 namespace tsc {
 
-// RAII bundle of scratch blocks of one call: everything goes back to the cache on scope exit.
-struct Scratch {
-    tsc_ctx *ctx;
-    std::vector<void *> blocks;
-    explicit Scratch(tsc_ctx *c) : ctx(c) {}
-    ~Scratch() {
-        for (void *p : blocks) ctx->release(p);
-    }
-    template <typename T>
-    int get(size_t count, T **out) {
-        void *p = nullptr;
-        int rc = ctx->alloc(count * sizeof(T), &p);
-        if (rc) return rc;
-        blocks.push_back(p);
-        *out = static_cast<T *>(p);
-        return 0;
-    }
-};
-
 struct DeviceGuard {
     int prev = -1;
     explicit DeviceGuard(int dev) {
@@ -196,5 +175,34 @@ struct DeviceGuard {
         if (prev >= 0) (void)hipSetDevice(prev);
     }
 };
+
+// ---- what owned.hpp declares and only the context can do ----
+inline Scratch::~Scratch() {
+    for (void *p : blocks) ctx->release(p);
+}
+inline int Scratch::take(size_t bytes, void **out) {
+    TSC_TRY(ctx->alloc(bytes, out));
+    blocks.push_back(*out);
+    return 0;
+}
+inline void Scratch::give_back(void *p) {
+    auto it = std::find(blocks.begin(), blocks.end(), p);
+    if (it == blocks.end()) return;
+    blocks.erase(it);
+    ctx->release(p);
+}
+
+// The body of every tsc_<kind>_destroy.  What a kind holds beside its blocks goes in its destructor, what it keeps in the context in
+// unlisted(); whether it waits is said in owned.hpp (destroy_waits), nowhere else.
+template <typename T>
+int destroy_owned(T *o) {
+    if (!o) return 0;
+    tsc_ctx *c = o->ctx;
+    DeviceGuard guard(c->device);
+    if (destroy_waits<T>) (void)hipStreamSynchronize(c->stream);
+    c->owned.disown(o);
+    delete o;
+    return 0;
+}
 
 }  // namespace tsc

@@ -1,6 +1,6 @@
 // ctx.hip -- library / context entry points of include/tscode_hip.h and the tunables
 // gfx950 only.  There is deliberately no CPU implementation behind these entry points.
-#include "prune_host.hpp"
+#include "host.hpp"
 
 // --------------------------------------------------------------------------------------------------
 // library / context
@@ -76,13 +76,10 @@ extern "C" __attribute__((visibility("default"))) int tsc_ctx_destroy(tsc_ctx *c
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
     if (c->basis_stream) (void)hipStreamSynchronize(c->basis_stream);
-    // runs that are still alive go with their context (their blocks are the context's, their events join its pool below): a host whose
-    // finalisers come in no particular order -- Python collecting a run and its engine in one cycle -- must not hand a run to
-    // tsc_prune_destroy after this
-    while (!c->live_runs.empty()) (void)tsc_prune_destroy(c->live_runs.back());
-    while (!c->live_rot_corr.empty()) (void)tsc_rot_corr_destroy(c->live_rot_corr.back());
-    while (!c->live_rot_corr_batch.empty()) (void)tsc_rot_corr_batch_destroy(c->live_rot_corr_batch.back());
-    while (!c->live_embed_prune.empty()) (void)tsc_embed_prune_destroy(c->live_embed_prune.back());
+    // objects that are still alive go with their context, newest first (their blocks are the context's, a prune run's events join its
+    // pool below, an exchange closes its peers' mappings): a host whose finalisers come in no particular order -- Python collecting a run
+    // and its engine in one cycle -- must not hand one to its tsc_*_destroy after this
+    c->owned.destroy_all();
     for (auto &kv : c->cache) (void)hipFree(kv.second);
     for (auto &kv : c->live) (void)hipFree(kv.first);
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);

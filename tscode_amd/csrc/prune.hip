@@ -105,23 +105,21 @@ extern "C" __attribute__((visibility("default"))) int tsc_screen_mm_keeps(tsc_ct
     TSC_API_GUARD_END
 }
 
+// What tsc_prune_destroy and tsc_ctx_destroy undo beside the run's blocks.  In one critical section with the unlisting: the run's word of
+// pinned memory and its hold on the descriptors it borrowed (tsc_prune_create).
+void tsc_prune::unlisted() {
+    if (borrows_xd && ctx->xd_borrowers > 0) --ctx->xd_borrowers;
+    if (flag_slot >= 0) ctx->flag_slots_used &= ~(1ull << flag_slot);
+}
+tsc_prune::~tsc_prune() {
+    for (auto &slot : ev)
+        for (hipEvent_t e : slot)
+            if (e) ctx->event_pool.push_back(e);
+}
+
 extern "C" __attribute__((visibility("default"))) int tsc_prune_destroy(tsc_prune *p) {
     TSC_API_GUARD_BEGIN
-    if (!p) return 0;
-    DeviceGuard guard(p->ctx->device);
-    {
-        std::lock_guard<std::mutex> lock(p->ctx->runs_mutex);
-        if (p->borrows_xd && p->ctx->xd_borrowers > 0) --p->ctx->xd_borrowers;
-        if (p->flag_slot >= 0) p->ctx->flag_slots_used &= ~(1ull << p->flag_slot);
-        auto &lr = p->ctx->live_runs;
-        lr.erase(std::remove(lr.begin(), lr.end(), p), lr.end());
-    }
-    for (void *q : p->blocks) p->ctx->release(q);
-    for (auto &slot : p->ev)
-        for (hipEvent_t e : slot)
-            if (e) p->ctx->event_pool.push_back(e);
-    delete p;
-    return 0;
+    return destroy_owned(p);   // (without a wait for the stream: owned.hpp, destroy_waits)
     TSC_API_GUARD_END
 }
 
@@ -209,9 +207,8 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
     TSC_REQUIRE(c->opt.prune_algo != ALGO_TILE || h <= MAX_HP, "prune_algo=1 (register-tiled kernel) supports at most %d heavy atoms, got %d", MAX_HP, h);
     *out = nullptr;
     DeviceGuard guard(c->device);
-    tsc_prune *p = new (std::nothrow) tsc_prune();
+    tsc_prune *p = new (std::nothrow) tsc_prune(c);
     if (!p) return fail(TSC_ERR_NOMEM, "out of host memory");
-    p->ctx = c;
     p->heavy = heavy_dev;
     p->n = n;
     p->npad = (n + 63) / 64 * 64 + 320;  // the last column tile of a segment reads up to 255 columns past the active count
@@ -221,8 +218,8 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
     p->mode = mode;
     p->algo = (c->opt.prune_algo == ALGO_TILE) ? ALGO_TILE : ALGO_SIEVE;
     p->det_desc = c->opt.deterministic_basis != 0;
-    {   // this run's word of pinned memory (the culled-or-walked verdict of a candidate pass): its own for as long as it lives
-        std::lock_guard<std::mutex> lock(c->runs_mutex);
+    {   // this run's word of pinned memory (the culled-or-walked verdict of a candidate pass), and its entry in the context's list: early, every error path below is tsc_prune_destroy
+        std::lock_guard<std::mutex> lock(c->owned.mutex);
         static_assert(PINNED_FLAG_SLOTS == 64, "one bit per flag word");
         const int slot = ~c->flag_slots_used ? __builtin_ctzll(~c->flag_slots_used) : -1;
         if (slot < 0) {
@@ -232,7 +229,7 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
         }
         c->flag_slots_used |= 1ull << slot;
         p->flag_slot = slot;
-        c->live_runs.push_back(p);
+        c->owned.adopt_locked(p);
     }
     Scratch s_basis(c);
     if (force_algo >= 0) {
@@ -263,44 +260,44 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
     if (mask_buffer)
         p->mask = mask_buffer;  // the caller's verdict buffer serves as the working mask (8-byte aligned, n bytes)
     else if (!rc)
-        rc = palloc(p, size_t(n), &p->mask);
-    if (!rc) rc = palloc(p, size_t(n), &p->act);
-    if (!rc) rc = palloc(p, size_t(n), &p->cend);
-    if (!rc) rc = palloc(p, size_t(n), &p->best);
-    if (!rc) rc = palloc(p, size_t(p->n_blocks) + 1, &p->bsum);
-    if (!rc) rc = palloc(p, size_t(p->n_blocks) + 1, &p->boff);
-    if (!rc) rc = palloc(p, size_t(n) / 16 + 8, &p->tile_cmax);
-    if (!rc) rc = palloc(p, size_t(n) / 16 + 8, &p->tile_done);
-    if (!rc) rc = palloc(p, 2 * p->bit_words, &p->bits);
+        rc = p->get(size_t(n), &p->mask);
+    if (!rc) rc = p->get(size_t(n), &p->act);
+    if (!rc) rc = p->get(size_t(n), &p->cend);
+    if (!rc) rc = p->get(size_t(n), &p->best);
+    if (!rc) rc = p->get(size_t(p->n_blocks) + 1, &p->bsum);
+    if (!rc) rc = p->get(size_t(p->n_blocks) + 1, &p->boff);
+    if (!rc) rc = p->get(size_t(n) / 16 + 8, &p->tile_cmax);
+    if (!rc) rc = p->get(size_t(n) / 16 + 8, &p->tile_done);
+    if (!rc) rc = p->get(2 * p->bit_words, &p->bits);
     p->dsum_words = p->bit_words / 1024 + 4;  // one summary bit per 1024 cache-view bits, kept right behind the view
     p->n_views = 0;
     for (int slot = 0; slot < TSC_MAX_PASSES; ++slot) p->view_of_slot[slot] = (pass_can_run(n, slot) && mode == 0) ? p->n_views++ : -1;
-    if (!rc) rc = palloc(p, std::max<size_t>(1, size_t(p->n_views) * (p->bit_words + p->dsum_words)), &p->views);
-    if (!rc) rc = palloc(p, TSC_MAX_PASSES, &p->view_pass);
-    if (!rc) rc = palloc(p, TSC_MAX_PASSES, &p->counters_all);
-    if (!rc) rc = palloc(p, TSC_MAX_PASSES, &p->state_all);
+    if (!rc) rc = p->get(std::max<size_t>(1, size_t(p->n_views) * (p->bit_words + p->dsum_words)), &p->views);
+    if (!rc) rc = p->get(TSC_MAX_PASSES, &p->view_pass);
+    if (!rc) rc = p->get(TSC_MAX_PASSES, &p->counters_all);
+    if (!rc) rc = p->get(TSC_MAX_PASSES, &p->state_all);
     p->counters = p->counters_all, p->state = p->state_all;  // (pass_launch moves them to the slot of the pass in flight)
-    if (!rc) rc = palloc(p, TSC_MAX_PASSES, &p->records);
+    if (!rc) rc = p->get(TSC_MAX_PASSES, &p->records);
     const bool own_desc = !(ext && ext->D);  // (external descriptors: already enqueued on this stream, the caller owns the buffers)
     if (!rc && p->algo == ALGO_SIEVE) {
         if (own_desc) {
-            rc = palloc(p, size_t(n) * DW, &p->Dall);
-            if (!rc) rc = palloc(p, size_t(n), &p->Gall);
-            if (!rc) rc = palloc(p, 4, &p->dmax_bits);
+            rc = p->get(size_t(n) * DW, &p->Dall);
+            if (!rc) rc = p->get(size_t(n), &p->Gall);
+            if (!rc) rc = p->get(4, &p->dmax_bits);
         } else {
             p->Dall = ext->D, p->Gall = ext->G, p->dmax_bits = ext->dmax_bits;
         }
-        if (!rc) rc = palloc(p, size_t(n) * DW, &p->Dc);
+        if (!rc) rc = p->get(size_t(n) * DW, &p->Dc);
         // (mm.hpp; decided per run: the 64-row kernels for large runs, the 16-row form of the walked kernel -- "sieve_mm16" -- below that)
         p->mm64 = c->opt.sieve_mm == 2 || (c->opt.sieve_mm == 1 && n >= c->opt.mm_min_n);
         const bool want_mm = p->mm64 || c->opt.sieve_mm16 != 0;
-        if (!rc && want_mm) rc = palloc(p, size_t(n) * MM_REC_HALVES, &p->Dh);
+        if (!rc && want_mm) rc = p->get(size_t(n) * MM_REC_HALVES, &p->Dh);
         // the records by structure index of the chunk-local pass's matrix-core screen ("sieve_mm16"): only where a pass of the schedule can have
         // chunks short enough for that kernel (a rank's share of a partitioned pass may leave the longer last chunk to another rank)
         bool local_possible = false;
         for (int slot = 0; slot < TSC_MAX_PASSES; ++slot)
             local_possible = local_possible || (pass_can_run(n, slot) && n / int64_t(KS[slot]) <= std::min(LP_MAX_ROWS, c->opt.local_max_chunk));
-        if (!rc && c->opt.sieve_mm16 != 0 && c->opt.local_pass != 0 && local_possible) rc = palloc(p, size_t(n) * MM_REC_HALVES, &p->Drec);
+        if (!rc && c->opt.sieve_mm16 != 0 && c->opt.local_pass != 0 && local_possible) rc = p->get(size_t(n) * MM_REC_HALVES, &p->Drec);
         // the float32 copy stage 1 reads (pair_stages.hpp, pair_stage1): from the embedding kernel where there was one, else converted here
         // (it pays where the gathers come from HBM: 41 MB of heavy atoms at C3 sit in the 256 MB infinity cache and the conversions cost the
         // VALU-bound kernel 2 %; at C4's 348 MB a step goes from 12.1 to 10.6 ms.  "stage1_f32": 0 never, 1 from 128 MB on, 2 always)
@@ -308,18 +305,18 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
             if (ext && ext->heavy32) {  // written by the kernel that embedded the structures
                 p->heavy32 = ext->heavy32;
             } else {
-                rc = palloc(p, size_t(n) * heavy32_pitch(h), &p->heavy32);
+                rc = p->get(size_t(n) * heavy32_pitch(h), &p->heavy32);
                 if (!rc) hipLaunchKernelGGL(k_heavy32, dim3(unsigned(std::min<int64_t>(ceil_div<int64_t>(n * heavy32_pitch(h), 256), 65536))), dim3(256), 0, c->stream,
                                             heavy_dev, n, h, p->heavy32);
             }
         }
     }
-    if (!rc) rc = palloc(p, 1, &p->tickets);
+    if (!rc) rc = p->get(1, &p->tickets);
     if (!rc && p->algo == ALGO_TILE) {
         const size_t hp3 = size_t(p->hp) * 3;
-        rc = palloc(p, size_t(p->npad) * hp3, &p->Xr);
-        if (!rc) rc = palloc(p, size_t(p->npad) * hp3, &p->Xc);
-        if (!rc) rc = palloc(p, size_t(p->npad), &p->G);
+        rc = p->get(size_t(p->npad) * hp3, &p->Xr);
+        if (!rc) rc = p->get(size_t(p->npad) * hp3, &p->Xc);
+        if (!rc) rc = p->get(size_t(p->npad), &p->G);
     }
     if (!rc) {
         hipStream_t st = c->stream;
@@ -378,7 +375,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_create(tsc_ctx *
         ext.heavy32 = c->xd_h32_valid ? c->xd_heavy32 : nullptr;
         c->xd_valid = false;
         TSC_TRY(prune_create_impl(c, heavy_dev, n, h, rmsd_thr, mode, nullptr, out, nullptr, &ext));
-        std::lock_guard<std::mutex> lock(c->runs_mutex);
+        std::lock_guard<std::mutex> lock(c->owned.mutex);
         (*out)->borrows_xd = true;   // (tsc_embed_masked_dev will not release or regrow the buffers under this run)
         ++c->xd_borrowers;
         return 0;
@@ -606,17 +603,17 @@ static int open_rows(tsc_prune *p, const PassGeom &g, const PassShape &s, bool r
 static int cull_buffers(tsc_prune *p) {
     if (p->morton_order) return 0;
     const size_t n = size_t(p->n);
-    TSC_TRY(palloc(p, n, &p->morton_order));
-    TSC_TRY(palloc(p, n, &p->rank_of));
-    TSC_TRY(palloc(p, n + 256, &p->crank));
-    TSC_TRY(palloc(p, size_t(CULL_MAX_CHUNKS) + 1, &p->cbase));
-    TSC_TRY(palloc(p, size_t(CULL_MAX_CHUNKS) + 1, &p->cfill));
-    TSC_TRY(palloc(p, (n / CULL_LAYOUT_ITEMS + 2) * CULL_MAX_CHUNKS, &p->blk_cnt));
-    TSC_TRY(palloc(p, (n + 256) * DW, &p->Ds));
-    if (p->Dh && p->mm64) TSC_TRY(palloc(p, (n + 256) * MM_REC_HALVES, &p->Dhs));
-    if (p->Dh && p->mm64) TSC_TRY(palloc(p, n + 256, &p->cstruct));
-    TSC_TRY(palloc(p, (n / CULL_COLS + 2) * CULL_BOX, &p->cbox));
-    TSC_TRY(palloc(p, (n / CULL_COLS + 2) * 8 * CULL_BOX, &p->rbox));
+    TSC_TRY(p->get(n, &p->morton_order));
+    TSC_TRY(p->get(n, &p->rank_of));
+    TSC_TRY(p->get(n + 256, &p->crank));
+    TSC_TRY(p->get(size_t(CULL_MAX_CHUNKS) + 1, &p->cbase));
+    TSC_TRY(p->get(size_t(CULL_MAX_CHUNKS) + 1, &p->cfill));
+    TSC_TRY(p->get((n / CULL_LAYOUT_ITEMS + 2) * CULL_MAX_CHUNKS, &p->blk_cnt));
+    TSC_TRY(p->get((n + 256) * DW, &p->Ds));
+    if (p->Dh && p->mm64) TSC_TRY(p->get((n + 256) * MM_REC_HALVES, &p->Dhs));
+    if (p->Dh && p->mm64) TSC_TRY(p->get(n + 256, &p->cstruct));
+    TSC_TRY(p->get((n / CULL_COLS + 2) * CULL_BOX, &p->cbox));
+    TSC_TRY(p->get((n / CULL_COLS + 2) * 8 * CULL_BOX, &p->rbox));
     return 0;
 }
 

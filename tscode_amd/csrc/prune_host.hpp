@@ -25,8 +25,10 @@ static_assert(MAX_SLOTS == TSC_MAX_PASSES, "one cache view per schedule slot");
 // 20 k >= n can never pass the gate of :192; the others are enqueued and gated on the device.
 static inline bool pass_can_run(int64_t n, int slot) { return pass_gate(KS[slot], n); }
 
-struct tsc_prune {
-    tsc_ctx *ctx = nullptr;
+struct tsc_prune : Owned {
+    explicit tsc_prune(tsc_ctx *c) : Owned(c) {}
+    ~tsc_prune() override;   // (prune.hip: the run's events go back to the context's pool)
+    void unlisted() override;   // (prune.hip: its pinned flag word and its hold on the context's xd_* buffers)
     const double *heavy = nullptr;
     int64_t n = 0, npad = 0;
     int h = 0, hp = 0;
@@ -41,7 +43,7 @@ struct tsc_prune {
     unsigned long long *bits = nullptr;    // two bit copies of the mask (the pass in flight reads one, clears removed rows in the other)
     unsigned long long *views = nullptr;   // cache view of every pass of the schedule, each followed by its summary (pass_state.hpp, CacheViews)
     ViewPass *view_pass = nullptr;         // device: the pass of each view (chunk count, chunk size, its division constants)
-    int view_of_slot[TSC_MAX_PASSES];      // schedule slot -> view index (-1: the pass can never run)
+    int view_of_slot[TSC_MAX_PASSES] = {};  // schedule slot -> view index (-1: the pass can never run)
     int n_views = 0;
     size_t bit_words = 0, dsum_words = 0;
     bool cur_fused = false;                // the open pass is applied by the pair kernel itself
@@ -77,7 +79,6 @@ struct tsc_prune {
     PassCounters *counters = nullptr;      // the entries of the pass in flight (pass_launch) -- what every kernel of a pass is handed
     PruneState *state = nullptr;
     PassRecord *records = nullptr;  // [TSC_MAX_PASSES]
-    std::vector<void *> blocks;
     // host state
     int next_ks = 0;       // next index into KS to consider
     int cur_slot = -1;     // schedule slot of the pass in flight (-1 = none)
@@ -91,7 +92,7 @@ struct tsc_prune {
     bool local_done = false;
     bool slot_used[TSC_MAX_PASSES] = {false};
     hipEvent_t ev[TSC_MAX_PASSES][4] = {{nullptr}};  // per slot: pass begin, pair kernel begin, pair kernel end, pass end
-    tsc_pass_stats stats[TSC_MAX_PASSES];
+    tsc_pass_stats stats[TSC_MAX_PASSES] = {};
     int n_passes = 0;
     bool collected = false;
     bool borrows_xd = false;   // the descriptors (and the float32 copy) are the context's xd_* buffers, written by tsc_embed_masked_dev: the context
@@ -101,15 +102,6 @@ struct tsc_prune {
     bool auto_tile = false;    // ALGO_TILE was this run's own choice (screen_is_useless on its own basis estimate), not the caller's
     int flag_slot = -1;        // this run's word in the context's pinned buffer (the culled-or-walked verdict of a candidate pass)
 };
-
-template <typename T>
-static int palloc(tsc_prune *p, size_t count, T **out) {
-    void *q = nullptr;
-    TSC_TRY(p->ctx->alloc(count * sizeof(T), &q));
-    p->blocks.push_back(q);
-    *out = static_cast<T *>(q);
-    return 0;
-}
 
 // The pass that follows the open one (what tsc_prune_next_pass will hand out next; not consumed here): the kernel that
 // finishes a pass also closes it and opens this one on the device.

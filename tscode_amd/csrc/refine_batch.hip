@@ -14,8 +14,8 @@
 // One run over many ensembles: every segment's centred structures live on the device from tsc_rot_corr_batch_begin to
 // tsc_rot_corr_batch_end and are turned in place by the slots, as the reference turns its array; the caches of dissimilar pairs
 // (:1121-1123) lie beside them, segment after segment.
-struct tsc_rot_corr_batch {
-    tsc_ctx *ctx;
+struct tsc_rot_corr_batch : tsc::Owned {
+    using Owned::Owned;
     std::vector<tsc::RotCorrSegment> segs;   // per segment: device pointers of its set-up, its offsets and words; d, num_active, thr per slot
     std::vector<int32_t> N;
     int64_t total_rows = 0, total_doubles = 0;
@@ -23,24 +23,13 @@ struct tsc_rot_corr_batch {
     uint32_t *cache = nullptr;
     int32_t *first = nullptr;
     unsigned long long *evaluated = nullptr;   // [segments]
-    tsc::Scratch scratch;                      // every device block of the run, handed back when it is deleted
-    explicit tsc_rot_corr_batch(tsc_ctx *c) : ctx(c), scratch(c) {}
 };
 
 using namespace tsc;
 
 extern "C" __attribute__((visibility("default"))) int tsc_rot_corr_batch_destroy(tsc_rot_corr_batch *r) {
     TSC_API_GUARD_BEGIN
-    if (!r) return 0;
-    DeviceGuard guard(r->ctx->device);
-    (void)hipStreamSynchronize(r->ctx->stream);
-    {
-        std::lock_guard<std::mutex> lock(r->ctx->runs_mutex);
-        auto &lr = r->ctx->live_rot_corr_batch;
-        lr.erase(std::remove(lr.begin(), lr.end(), r), lr.end());
-    }
-    delete r;   // (its blocks go back to the cache)
-    return 0;
+    return destroy_owned(r);
     TSC_API_GUARD_END
 }
 
@@ -115,13 +104,9 @@ extern "C" __attribute__((visibility("default"))) int tsc_rot_corr_batch_begin(t
         a.n_angles = d_n_angles + tors0[s], a.masks = d_masks + mask0[s], a.sub_ptr = d_sub_ptr + ptr0[s], a.sub_idx = d_sub_idx + idx0[s];
     }
     TSC_TRY(h.finish());
-    run->scratch.blocks.swap(h.scratch().blocks);
-    tsc_rot_corr_batch *r = run.release();
-    {
-        std::lock_guard<std::mutex> lock(c->runs_mutex);
-        c->live_rot_corr_batch.push_back(r);
-    }
-    *out = r;
+    run->take_blocks(h.scratch());
+    c->owned.adopt(run.get());   // (listed once complete: destroyed with the context, tsc_ctx_destroy)
+    *out = run.release();
     return 0;
     TSC_API_GUARD_END
 }

@@ -10,16 +10,14 @@
 
 // One run: the centred structures live on the device from tsc_rot_corr_begin to tsc_rot_corr_end and are turned in place by the
 // passes, as the reference turns its array; the cache bitmap of dissimilar pairs (:1121-1123) lives beside them.
-struct tsc_rot_corr {
-    tsc_ctx *ctx;
+struct tsc_rot_corr : tsc::Owned {
+    using Owned::Owned;
     int64_t N = 0, words = 0;
     tsc::RotCorrArgs a{};
     double *coords = nullptr;
     uint32_t *cache = nullptr;
     int32_t *first = nullptr;
     unsigned long long *evaluated = nullptr;
-    tsc::Scratch scratch;   // every device block of the run, handed back when it is deleted
-    explicit tsc_rot_corr(tsc_ctx *c) : ctx(c), scratch(c) {}
 };
 
 namespace {
@@ -43,16 +41,7 @@ int upload_setup(HostCall &hc, RotCorrArgs &a, int n, const int32_t *heavy, int 
 
 extern "C" __attribute__((visibility("default"))) int tsc_rot_corr_destroy(tsc_rot_corr *r) {
     TSC_API_GUARD_BEGIN
-    if (!r) return 0;
-    DeviceGuard guard(r->ctx->device);
-    (void)hipStreamSynchronize(r->ctx->stream);
-    {
-        std::lock_guard<std::mutex> lock(r->ctx->runs_mutex);
-        auto &lr = r->ctx->live_rot_corr;
-        lr.erase(std::remove(lr.begin(), lr.end(), r), lr.end());
-    }
-    delete r;   // (its blocks go back to the cache)
-    return 0;
+    return destroy_owned(r);
     TSC_API_GUARD_END
 }
 
@@ -76,13 +65,9 @@ extern "C" __attribute__((visibility("default"))) int tsc_rot_corr_begin(tsc_ctx
     TSC_TRY(h.scratch().get(1, &run->evaluated));
     if (n_structs) TSC_HIP(hipMemsetAsync(run->cache, 0, size_t(n_structs) * run->words * sizeof(uint32_t), c->stream));
     TSC_TRY(h.finish());
-    run->scratch.blocks.swap(h.scratch().blocks);
-    tsc_rot_corr *r = run.release();
-    {
-        std::lock_guard<std::mutex> lock(c->runs_mutex);
-        c->live_rot_corr.push_back(r);
-    }
-    *out = r;
+    run->take_blocks(h.scratch());
+    c->owned.adopt(run.get());   // (listed once complete: destroyed with the context, tsc_ctx_destroy)
+    *out = run.release();
     return 0;
     TSC_API_GUARD_END
 }

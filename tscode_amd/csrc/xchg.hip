@@ -112,8 +112,8 @@ __global__ __launch_bounds__(256) void k_xchg_reduce(unsigned long long *__restr
 
 }  // namespace
 
-struct tsc_xchg {
-    tsc_ctx *ctx = nullptr;
+struct tsc_xchg : Owned {
+    using Owned::Owned;
     int rank = 0, world = 1;
     int64_t slot_bytes = 0;
     size_t slot_stride = 0, area_bytes = 0;
@@ -126,6 +126,14 @@ struct tsc_xchg {
     bool connected = false;
     double timeout_s = 5.0;
     int64_t n_exchanges = 0;
+    // (what is not the cache's: on the context's device behind an idle stream, from tsc_xchg_destroy or, still listed, tsc_ctx_destroy)
+    ~tsc_xchg() override {
+        for (int p = 0; p < world; ++p)
+            if (opened[p] && peer[p]) (void)hipIpcCloseMemHandle(peer[p]);
+        if (area) (void)hipFree(area);
+        if (ticket) (void)hipFree(ticket);
+        if (status) (void)hipHostFree(status);
+    }
 };
 
 extern "C" __attribute__((visibility("default"))) int tsc_xchg_slot_bytes(int64_t n, int mode, int64_t *bytes) {
@@ -140,16 +148,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_xchg_slot_bytes(int64_
 
 extern "C" __attribute__((visibility("default"))) int tsc_xchg_destroy(tsc_xchg *x) {
     TSC_API_GUARD_BEGIN
-    if (!x) return 0;
-    DeviceGuard guard(x->ctx->device);
-    (void)hipStreamSynchronize(x->ctx->stream);
-    for (int p = 0; p < x->world; ++p)
-        if (x->opened[p] && x->peer[p]) (void)hipIpcCloseMemHandle(x->peer[p]);
-    if (x->area) (void)hipFree(x->area);
-    if (x->ticket) (void)hipFree(x->ticket);
-    if (x->status) (void)hipHostFree(x->status);
-    delete x;
-    return 0;
+    return destroy_owned(x);
     TSC_API_GUARD_END
 }
 
@@ -161,9 +160,9 @@ extern "C" __attribute__((visibility("default"))) int tsc_xchg_create(tsc_ctx *c
     static_assert(sizeof(hipIpcMemHandle_t) == TSC_XCHG_HANDLE_BYTES, "the handle is 64 bytes");
     *out = nullptr;
     DeviceGuard guard(c->device);
-    tsc_xchg *x = new (std::nothrow) tsc_xchg();
+    tsc_xchg *x = new (std::nothrow) tsc_xchg(c);
     if (!x) return fail(TSC_ERR_NOMEM, "out of host memory");
-    x->ctx = c, x->rank = rank, x->world = world, x->slot_bytes = slot_bytes;
+    x->rank = rank, x->world = world, x->slot_bytes = slot_bytes;
     x->slot_stride = (size_t(slot_bytes) + 255) & ~size_t(255);
     x->area_bytes = XCHG_HEADER + 2 * size_t(world) * x->slot_stride;
     hipError_t e = hipExtMallocWithFlags(reinterpret_cast<void **>(&x->area), x->area_bytes, hipDeviceMallocUncached);
@@ -189,6 +188,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_xchg_create(tsc_ctx *c
     }
     memcpy(handle_out, &h, sizeof(h));
     x->peer[rank] = x->area;
+    c->owned.adopt(x);   // (listed once complete: destroyed with the context, tsc_ctx_destroy)
     *out = x;
     return 0;
     TSC_API_GUARD_END

@@ -137,7 +137,7 @@ class Engine:
         check(self.lib.tsc_ctx_create(int(device), C.byref(h)))
         self._h = h
         self.device = int(device)
-        self._runs = weakref.WeakSet()      # live PruneSteppers / IpcExchanges: they hold blocks and events of this context
+        self._runs = weakref.WeakSet()      # the live ContextObjects: they hold blocks, events or mappings of this context
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1107,19 +1107,46 @@ class Engine:
         return run
 
 
-class IpcExchange:
+class ContextObject:
+    """What every object created from an engine's context is (include/tscode_hip.h, "objects created from a context"): the engine, the
+    library's handle and the name of the tsc_*_destroy that takes it.  The engine knows its objects and closes them before its context
+    goes; ``close()`` may be called any number of times, and after it the handle is ``None``."""
+
+    _handle = None                           # (until _own: a constructor that raised leaves nothing to close)
+    _r = _p = _x = property(lambda self: self._handle)     # the names the classes call their handle by
+
+    def _own(self, engine, handle, destroy):
+        self.e, self._handle, self._destroy = engine, handle, destroy
+        engine._runs.add(self)               # closed with the engine, before its context goes
+
+    def close(self):
+        if self._handle:
+            # a closed engine has destroyed its objects already: tsc_ctx_destroy destroys what the context still lists, also an
+            # object the engine no longer knew (Engine.close), and the handle is not to be used again
+            if getattr(self.e, "_h", None):
+                getattr(self.e.lib, self._destroy)(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class IpcExchange(ContextObject):
     """The exchange inside the library (include/tscode_hip.h, tsc_xchg_*): a receive area of fine-grained device memory per rank, mapped
     into every other rank of the node; an all-reduce is one kernel that writes into all peers and one that waits for their flags and
     folds what they delivered.  ``handle`` (64 bytes) has to reach every other rank -- the caller's business (``connect_over`` does it
     with torch.distributed) -- then ``connect(handles in rank order)``."""
 
     def __init__(self, engine: Engine, rank, world, slot_bytes):
-        self.e, self.rank, self.world = engine, int(rank), int(world)
+        self.rank, self.world = int(rank), int(world)
         x = C.c_void_p()
         buf = C.create_string_buffer(_lib.XCHG_HANDLE_BYTES)
         check(engine.lib.tsc_xchg_create(engine._h, C.c_int(rank), C.c_int(world), C.c_int64(int(slot_bytes)), C.byref(x), buf))
-        self._x, self.handle = x, bytes(buf.raw)
-        engine._runs.add(self)               # closed with the engine, before its context goes
+        self.handle = bytes(buf.raw)
+        self._own(engine, x, "tsc_xchg_destroy")
 
     @staticmethod
     def slot_bytes(lib, n, mode=0) -> int:
@@ -1159,32 +1186,19 @@ class IpcExchange:
             raise _lib.TscodeHipError(-5, f"{t} of {n} in-library exchanges gave up waiting for a peer rank (tsc_xchg_set_timeout): the results of "
                                      "the runs they belonged to are not valid")
 
-    def close(self):
-        if getattr(self, "_x", None):
-            if getattr(self.e, "_h", None):
-                self.e.lib.tsc_xchg_destroy(self._x)
-            self._x = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class EmbedPruneRun:
+class EmbedPruneRun(ContextObject):
     """One embed-and-prune run (include/tscode_hip.h, tsc_embed_prune_*): a cyclical embed whose kept poses stay on the device, are pruned by
     RMSD there, and of which only the poses asked for are embedded again and fetched."""
 
     def __init__(self, engine: Engine, frags: FragmentSet, heavy_idx):
-        self.e, self.frags = engine, frags
+        self.frags = frags
         heavy_idx = np.ascontiguousarray(heavy_idx, dtype=np.int32).ravel()
         r = C.c_void_p()
         check(engine.lib.tsc_embed_prune_create(engine._h, ptr(frags.flat), *frags.table_args(), heavy_idx.ctypes.data_as(_lib.c_i32p),
                                                 C.c_int(len(heavy_idx)), C.byref(r)))
-        self._r = r
         self.n_survived = None
-        engine._runs.add(self)               # closed with the engine, before its context goes
+        self._own(engine, r, "tsc_embed_prune_destroy")
 
     def add_groups(self, start, end, direction, pivot, meanpoint, r0, r1, n_reactive, conf_idx, angles, clash_thresh, max_clashes, rmsd_thr=1.0):
         """One slab of groups, arguments as ``Engine.cyclical_embed_groups``: (clash_ok bool[G * A], kept bool[G * A]); the kept poses stay on
@@ -1229,31 +1243,17 @@ class EmbedPruneRun:
             check(self.e.lib.tsc_embed_prune_poses(self._r, C.c_int(int(which)), ptr(out), C.c_int64(rows)))
         return out[:rows]
 
-    def close(self):
-        if getattr(self, "_r", None):
-            if getattr(self.e, "_h", None):
-                self.e.lib.tsc_embed_prune_destroy(self._r)
-            self._r = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PruneStepper:
+class PruneStepper(ContextObject):
     """Stepping form of one prune run (tsc_prune_*), used to shard a pass over ranks."""
 
     def __init__(self, engine: Engine, heavy_dev, n, h, rmsd_thr, mode):
-        self.e = engine
         self.n = int(n)
         h_ = C.c_void_p()
         check(engine.lib.tsc_prune_create(engine._h, ptr(heavy_dev), C.c_int64(n), C.c_int(h), C.c_double(rmsd_thr), C.c_int(mode),
                                           C.byref(h_)))
-        self._p = h_
         self._keep = heavy_dev
-        engine._runs.add(self)
+        self._own(engine, h_, "tsc_prune_destroy")
 
     def next_pass(self) -> int:
         k = C.c_int64()
@@ -1373,18 +1373,6 @@ class PruneStepper:
         np_ = C.c_int()
         check(self.e.lib.tsc_prune_stats(self._p, stats, C.byref(np_)))
         return _stats_list(stats, np_.value)
-
-    def close(self):
-        if getattr(self, "_p", None):
-            if getattr(self.e, "_h", None):      # (a closed engine has closed its runs already)
-                self.e.lib.tsc_prune_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _engines = {}

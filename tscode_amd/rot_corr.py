@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, ptr
-from .engine import get_engine
+from .engine import ContextObject, get_engine
 from .numba_functions import TFD_KS, _pass_schedule, _tfd_schedule_batch
 from .segments import byte_slices, ensemble_list, one_or_each, pack, scalar_or_each
 
@@ -77,18 +77,16 @@ class _Setup:
                 ptr(self.masks), ptr(self.sub_ptr), ptr(self.sub_idx))
 
 
-class _Run:
+class _Run(ContextObject):
     """One tsc_rot_corr run: the structures live on the device, turned in place by the passes."""
 
     def __init__(self, engine, structures, setup):
-        self.e = engine
         self.structures = np.ascontiguousarray(structures, dtype=np.float64)
         self.setup = setup
         h = C.c_void_p()
         check(engine.lib.tsc_rot_corr_begin(engine._h, ptr(self.structures), C.c_int64(len(self.structures)), C.c_int(self.structures.shape[1]),
                                             *setup.args(), C.byref(h)))
-        self._r = h
-        engine._runs.add(self)
+        self._own(engine, h, "tsc_rot_corr_destroy")
 
     def run_pass(self, d, k, num_active, max_rmsd):
         first = np.empty(len(self.structures), dtype=np.int32)
@@ -101,18 +99,6 @@ class _Run:
         out = np.empty_like(self.structures)
         check(self.e.lib.tsc_rot_corr_end(self._r, ptr(out)))
         return out
-
-    def close(self):
-        if getattr(self, "_r", None):
-            if getattr(self.e, "_h", None):      # (a closed engine has destroyed its runs already)
-                self.e.lib.tsc_rot_corr_destroy(self._r)
-            self._r = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def prune_rmsd_rot_corr_arrays(structures, atomnos, torsions, angles, move_masks, sub_nodes, max_rmsd=0.25, max_structures=750,
@@ -161,11 +147,10 @@ def last_rot_corr_batch_stats():
     return [list(s) for s in _last_batch_stats]
 
 
-class _BatchRun:
+class _BatchRun(ContextObject):
     """One tsc_rot_corr_batch run: the structures of every segment live on the device, turned in place by the slots."""
 
     def __init__(self, engine, ensembles, setups):
-        self.e = engine
         self.packed = pack([np.ascontiguousarray(e, dtype=np.float64) for e in ensembles])
         self.total_rows = int(self.packed.row_off[-1])
 
@@ -177,8 +162,7 @@ class _BatchRun:
         h = C.c_void_p()
         check(engine.lib.tsc_rot_corr_batch_begin(engine._h, *[ptr(a) for a in self.packed[:4]], *[ptr(a) for a in self.arrays],
                                                   C.c_int64(len(ensembles)), C.byref(h)))
-        self._r = h
-        engine._runs.add(self)
+        self._own(engine, h, "tsc_rot_corr_batch_destroy")
 
     def run_slot(self, open_segs, d, k, num_active, max_rmsd):
         """(first i32[total rows]: indices inside each segment, pairs evaluated i64[open segments])"""
@@ -196,18 +180,6 @@ class _BatchRun:
         out = np.empty_like(self.packed.flat)
         check(self.e.lib.tsc_rot_corr_batch_end(self._r, ptr(out)))
         return self.packed.cut(out, doubles=True)
-
-    def close(self):
-        if getattr(self, "_r", None):
-            if getattr(self.e, "_h", None):      # (a closed engine has destroyed its runs already)
-                self.e.lib.tsc_rot_corr_batch_destroy(self._r)
-            self._r = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _batch_setup(s, n_atoms, atomnos, setup):
