@@ -138,7 +138,12 @@ int tsc_ctx_synchronize(tsc_ctx *ctx);
  *   "pass_timing": HIP events for tsc_pass_stats.gpu_ms / tile_ms and the pipeline's stage timings: 0 = none (default; an
  *      event record in the stream costs about 4 us on MI355X), 1 = the pair kernel's own start/stop events (tile_ms; passes run by the
  *      chunk-local kernel carry theirs at level 2 only), 2 = also around every whole pass (gpu_ms) and the stages of tsc_pipeline_dev.
- * (A library built with -DTSC_DBG_STAMPS has one more, dbg_stamp_k: tools/stamps.py.) */
+ * (A library built with -DTSC_DBG_STAMPS has one more, dbg_stamp_k: tools/stamps.py.)
+ * One A/B switch is set and read by name in the same way but is not listed by tsc_option_info -- it changes how a result is reached, never
+ * the result: skip_known, 1 (default) = in the walked passes of a one-rank run a row starts behind the columns that an earlier pass of
+ * the run already found dissimilar to it (a pair's verdict depends on its two structures alone, and the mask only shrinks), where the
+ * pass's pair kernel takes the hint (the 16-row matrix-core kernel); 0 = every row starts behind its diagonal.  Masks, pairs_evaluated,
+ * new_keys and the cache keys are the same either way; tsc_pass_stats.pairs_known says how many pairs a pass left out. */
 int tsc_ctx_set_option(tsc_ctx *ctx, const char *name, double value);
 /* The current value of a tunable as it is stored: every option can be read ("deterministic_basis" set to 5 reads 1). */
 int tsc_ctx_get_option(tsc_ctx *ctx, const char *name, double *value);
@@ -550,6 +555,8 @@ typedef struct {
     int32_t nonfinite_input; /* 1: the run met a structure with a NaN or infinite coordinate (the same in every entry of a run; descriptor-sieve
                                 runs only).  Such a structure is similar to nothing -- every comparison of :75 with a NaN is false -- and is
                                 kept; the reference itself raises LinAlgError there (np.linalg.svd, :19), and so does the Python drop-in */
+    int64_t pairs_known;     /* of pairs_screened: pairs inside the rows' ranges that the pass did NOT look at again -- an earlier pass of the run
+                                found them dissimilar (switch skip_known, below).  pairs_screened - pairs_known is what the screen multiplied */
 } tsc_pass_stats;
 
 #define TSC_MAX_PASSES 18

@@ -132,7 +132,7 @@ inline __global__ __launch_bounds__(64 * MM_WAVES, TSC_MM_OCC) void k_rmsd_sieve
     if (R0 >= a.n || seg_lo >= a.n) return;
     // largest stop columns of the group's four row tiles (0 for tiles beyond the bound the grid was sized for: their entries are stale)
     int tcm_t = 0;
-    if (lane < 4 && R0 + 16 * lane < a.n) tcm_t = a.tile_cmax[4 * grp + lane];
+    if (lane < 4 && R0 + 16 * lane < a.n) tcm_t = a.tile_cmax[2 * (4 * grp + lane)];
     int tcm = tcm_t;
     tcm = max(tcm, __shfl_xor(tcm, 1)), tcm = max(tcm, __shfl_xor(tcm, 2));
     tcm = __builtin_amdgcn_readfirstlane(tcm);
@@ -435,13 +435,16 @@ template <bool F32, int MM16_WAVES>
 __device__ __forceinline__ void sieve_item_mm16(const double *__restrict__ heavy, const int32_t *__restrict__ act, const double *__restrict__ Gall,
                                                 const _Float16 *__restrict__ Dh,
                                                 const int32_t *__restrict__ cend, int32_t *__restrict__ best, PassCounters *__restrict__ counters,
-                                                const PruneState *__restrict__ st, const SieveArgs &a, int &A_out, int &bitsel_out, const int tile, const int seg) {
+                                                const PruneState *__restrict__ st, const SieveArgs &a, int &A_out, int &bitsel_out, const int tile, const int seg,
+                                                const int tcmin) {
+    // tcmin: the smallest first column of the tile's rows with columns left (k_open_rows; 0 where the pass starts every row behind its diagonal)
     constexpr int TI = 16, TILE_COLS = 128;
     constexpr int QCAP = TI * TILE_COLS + 64;
     __shared__ unsigned short s_queue[MM16_WAVES][QCAP];
     __shared__ unsigned short s_exq[MM16_WAVES][128];
     __shared__ double s_jacobi[MM16_WAVES][32];
     __shared__ int s_cend[MM16_WAVES][TI];   // stop column of every row that was looking when the item began (else 0)
+    __shared__ int s_cbeg[MM16_WAVES][TI];   // ... and its first column: what lies before it an earlier pass found dissimilar (k_open_rows; r + 1 where the pass does not skip)
     const int lane = threadIdx.x & 63, g = lane >> 4, rc = lane & 15;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int slot = tile;
@@ -450,11 +453,14 @@ __device__ __forceinline__ void sieve_item_mm16(const double *__restrict__ heavy
     const int seg_hi = seg_lo + a.seg_cols;
     const int pass_on = st->pass_on, n_active = st->A;
     A_out = n_active, bitsel_out = st->bitsel;
-    int my_cend = 0, my_best = 0;
+    int my_cend = 0, my_best = 0, my_cbeg = r0 + lane + 1;
     if (lane < TI && r0 + lane < a.n) {
         my_cend = cend[r0 + lane];
+        my_cbeg = a.cbeg[r0 + lane];
         my_best = __hip_atomic_load(&best[r0 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    // the first column tile that holds a column some row of the tile still has to look at (known from one scalar load, before the rows' own)
+    const int c_start = seg_lo + (max(tcmin, seg_lo) - seg_lo) / TILE_COLS * TILE_COLS;
     // the rows' operands and the first column tile: requested with the stop columns (one trip for an item of a light pass)
     f16x4 Ar[NFAM];
     {
@@ -469,15 +475,16 @@ __device__ __forceinline__ void sieve_item_mm16(const double *__restrict__ heavy
             mm_load_B2(Dh + int64_t(min(c0 + MM_STEP * b + rc, a.n - 1)) * MM_REC_HALVES, g, B[b]);
         }
     };
-    load_tile(seg_lo);
+    load_tile(c_start);
     if (pass_on == 0 || r0 >= n_active) return;
     const int nrows = min(TI, n_active - r0);
-    const bool live0 = lane < nrows && my_cend > max(r0 + lane + 1, seg_lo) && my_best >= seg_lo;
+    const bool live0 = lane < nrows && my_cend > max(my_cbeg, seg_lo) && my_cbeg < seg_hi && my_best >= seg_lo;
     unsigned alive = unsigned(__ballot(live0));
     if (!alive) return;
     const float limit_mm = screen_limit_mm(*a.dmax_bits, a.desc_limit);
     int *scend = s_cend[wid];
-    if (lane < TI) scend[lane] = live0 ? my_cend : 0;
+    int *scbeg = s_cbeg[wid];
+    if (lane < TI) scend[lane] = live0 ? my_cend : 0, scbeg[lane] = my_cbeg;
     int cmax = live0 ? my_cend : 0;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) cmax = max(cmax, __shfl_xor(cmax, off));
@@ -606,7 +613,7 @@ __device__ __forceinline__ void sieve_item_mm16(const double *__restrict__ heavy
     };
 
     unsigned marked = alive;
-    for (int c0 = seg_lo; c0 < cmax;) {   // (alive != 0 here)
+    for (int c0 = c_start; c0 < cmax;) {   // (alive != 0 here)
         // every accumulator starts at -limit: a pair is kept iff both families come out negative; sign bits into a mask per family, value
         // j = 4 b + i of the tile -- row 4 g + i, column 16 b + rc -- at bit 31 - j
         unsigned m0 = 0, m1 = 0;
@@ -622,17 +629,18 @@ __device__ __forceinline__ void sieve_item_mm16(const double *__restrict__ heavy
             }
         }
         // (statistics: the pairs of this tile inside the live rows' ranges, as k_rmsd_sieve counts them)
-        my_screened += (lane < TI && ((alive >> lane) & 1u)) ? max(0, min(my_cend, c0 + TILE_COLS) - max(r0 + lane + 1, c0)) : 0;
+        my_screened += (lane < TI && ((alive >> lane) & 1u)) ? max(0, min(my_cend, c0 + TILE_COLS) - max(my_cbeg, c0)) : 0;
         unsigned hits = m0 & m1;
         while (__builtin_amdgcn_ballot_w64(hits != 0u)) {
-            // one pair per lane and turn; kept if it lies right of the diagonal and before its row's stop column (k_rmsd_sieve_mm)
+            // one pair per lane and turn; kept if it lies at or behind its row's first column (which is right of the diagonal) and before its
+            // stop column (k_rmsd_sieve_mm)
             bool keep = false;
             unsigned ent = 0;
             if (hits) {
                 const int j = __builtin_clz(hits);
                 hits &= ~(0x80000000u >> j);
                 const int row = 4 * g + (j & 3), col = c0 + MM_STEP * (j >> 2) + rc;
-                keep = col > r0 + row && col < scend[row];
+                keep = col >= scbeg[row] && col < scend[row];
                 ent = (unsigned(row) << 12) | unsigned(col - seg_lo);
             }
             const unsigned long long km = __builtin_amdgcn_ballot_w64(keep);
@@ -681,14 +689,19 @@ inline __global__ __launch_bounds__(64 * MM16_WAVES, TSC_MM16_OCC) void k_rmsd_s
     const int seg_lo = seg_base + int(blockIdx.y) * a.seg_cols;
     TSC_STAMP(0);  // the wavefront has started
     if (r0 >= a.n || seg_lo >= a.n) return;
-    const int tcm = a.tile_cmax[tile];
+    // the tile's largest stop column and smallest first column (0 where the pass starts its rows behind the diagonal): one scalar load
+    const int2 tc = *reinterpret_cast<const int2 *>(a.tile_cmax + 2 * tile);
+    const int tcm = tc.x, tcmin = tc.y;
     if (tcm <= seg_lo) return;
+    if (seg_lo + a.seg_cols <= tcmin) return;   // the segment ends before the first column any row of the tile still has to look at
     int A = 0, bitsel = 0;
-    sieve_item_mm16<F32, MM16_WAVES>(heavy, act, Gall, Dh, cend, best, counters, st, a, A, bitsel, tile, int(blockIdx.y));
+    sieve_item_mm16<F32, MM16_WAVES>(heavy, act, Gall, Dh, cend, best, counters, st, a, A, bitsel, tile, int(blockIdx.y), tcmin);
     if constexpr (FUSED) {   // (k_rmsd_sieve's tail, sieve.hpp)
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        // the tile's items that got here: its segments from the one that holds tcmin (a live row's first column, so below lim) to the one that
+        // holds the last column before lim
         const int lim = min(a.n, tcm);
-        const int n_live = min(int(gridDim.y), (lim - seg_base + a.seg_cols - 1) / a.seg_cols);
+        const int n_live = min(int(gridDim.y), (lim - seg_base + a.seg_cols - 1) / a.seg_cols) - max(0, tcmin - seg_base) / a.seg_cols;
         if (n_live > 1) {
             int last = 0;
             if (lane == 0) last = (atomicAdd(&fa.tile_done[tile], 1) == n_live - 1) ? 1 : 0;

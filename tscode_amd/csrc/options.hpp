@@ -39,6 +39,8 @@ struct tsc_options {
     int local_max_chunk = 384;            // longest chunk (structures) of a pass that the chunk-local kernel takes
     int local_pass = 1;                   // passes with short chunks run in one launch (local_pass.hpp)
     int fused_apply = 1;                  // single-rank sieve passes: the pair kernel applies the verdicts tile by tile and closes the pass (sieve.hpp)
+    int skip_known = 1;                   // walked passes of a one-rank run: a row starts behind the columns an earlier pass found dissimilar to it (rmsd.hpp: known[],
+                                          // k_open_rows; honoured by the 16-row matrix-core kernel).  0: every row starts behind its diagonal, as the reference walks
     int open_lds_blocks = 1 << 30;        // k_open_rows stages the scan-block prefix in LDS up to this many blocks (tests lower it to take the other path)
     int clash_fp32 = 1;                   // clash verdicts (max_clashes = 0, no counts): packed-fp32 minimum with fp64 fallback
     int clash_lanes = 1;                  // ... of two fragments, the smaller of at most 32 atoms, fused with the embed: one pose per lane (k_clash_lanes)
@@ -144,9 +146,16 @@ inline const OptionRow OPTION_TABLE[] = {
     TSC_OPTION(dbg_stamp_k, OPT_ANY),
 #endif
 };
+// A/B switches: set and read by name like the rows above, but not part of the listing (tsc_option_info, whose set of names
+// tests/test_options.py pins value by value): they change how a result is reached, never the result, and exist to be measured against.
+inline const OptionRow OPTION_SWITCHES[] = {
+    TSC_OPTION(skip_known, OPT_ONE_OF, 0, 1, 1),
+};
 
 inline const OptionRow *find_option(const char *name, char *msg, size_t len) {
     for (const OptionRow &r : OPTION_TABLE)
+        if (strcmp(name, r.name) == 0) return &r;
+    for (const OptionRow &r : OPTION_SWITCHES)
         if (strcmp(name, r.name) == 0) return &r;
     snprintf(msg, len, "unknown option '%s'", name);
     return nullptr;

@@ -266,8 +266,10 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
     if (!rc) rc = p->get(size_t(n), &p->best);
     if (!rc) rc = p->get(size_t(p->n_blocks) + 1, &p->bsum);
     if (!rc) rc = p->get(size_t(p->n_blocks) + 1, &p->boff);
-    if (!rc) rc = p->get(size_t(n) / 16 + 8, &p->tile_cmax);
+    if (!rc) rc = p->get(2 * (size_t(n) / 16 + 8), &p->tile_cmax);  // (per tile: largest stop column, smallest first column)
     if (!rc) rc = p->get(size_t(n) / 16 + 8, &p->tile_done);
+    if (!rc) rc = p->get(size_t(n), &p->known);
+    if (!rc) rc = p->get(size_t(n), &p->cbeg);
     if (!rc) rc = p->get(2 * p->bit_words, &p->bits);
     p->dsum_words = p->bit_words / 1024 + 4;  // one summary bit per 1024 cache-view bits, kept right behind the view
     p->n_views = 0;
@@ -337,6 +339,7 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
         ia.zero_words = reinterpret_cast<unsigned *>(p->tickets), ia.n_zero_words = int64_t(sizeof(*p->tickets) / sizeof(unsigned));
         ia.act = p->act, ia.first_slot = first_slot, ia.first_k = first_slot >= 0 ? (long long)KS[first_slot] : 0ll, ia.first_algo = p->algo;
         ia.tile_done = p->tile_done, ia.n_tile_done = n / 16 + 8;
+        ia.known = p->known;
         // External descriptors (and their maximum) were enqueued on this stream in front of the run: final here, k_init_run writes the records by
         // structure as it walks n (two structures per thread then, not eight).  A run that builds its own descriptors does so BEHIND this launch,
         // which zeroes the maximum they raise: its records come from k_mm_records behind build_descriptors, below.
@@ -458,7 +461,7 @@ static SieveArgs sieve_args(const tsc_prune *p, int rows, int rank, int world, i
     a.tile_begin = rank, a.tile_stride = world, a.seg_cols = seg_cols;
     put_screen_thresholds(p, a);
     a.heavy32 = p->heavy32;
-    a.tile_cmax = tile_cmax;
+    a.tile_cmax = tile_cmax, a.cbeg = p->cbeg;   // (both written by this pass's k_open_rows)
     a.drain_min = p->ctx->opt.drain_min;
     return a;
 }
@@ -565,7 +568,7 @@ static int local_pass(tsc_prune *p, const PassGeom &g, const PassRows &r, bool r
 // ---- what the culled and the walked pass have in front of them ----
 // 1. per row: which structure it is, its stop column, best[] = none, its descriptor by position (k_open_rows, rmsd.hpp); the coordinates by
 // position for the register-tiled kernel
-static int open_rows(tsc_prune *p, const PassGeom &g, const PassShape &s, bool range) {
+static int open_rows(tsc_prune *p, const PassGeom &g, const PassShape &s, bool range, int world) {
     tsc_ctx *c = p->ctx;
     hipStream_t st = c->stream;
     const OpenPlan o = plan_open_rows(s.rows_ub);
@@ -578,6 +581,13 @@ static int open_rows(tsc_prune *p, const PassGeom &g, const PassShape &s, bool r
     oa.dv = derive_args(p), oa.bsum = p->bsum, oa.boff_out = p->boff;
     oa.rank_of = s.culled ? p->rank_of : nullptr;
     oa.Dh = p->Dh, oa.dmax_bits = p->dmax_bits;
+    // known[]: read and raised where every row of the pass is opened and applied on this device (a rank's share of a partitioned pass, and a
+    // pass dealt to several ranks, leave it alone: too small is always safe).  The rows' first columns are HONOURED -- a tile with nothing
+    // left is declared dead here, the known pairs are counted -- where the kernel behind this launch is the 16-row matrix-core kernel
+    // applying its own tiles: a candidate for culling may end in another kernel, and k_apply_pass counts every row itself
+    const bool track = c->opt.skip_known != 0 && !range && world == 1;
+    const bool skip = track && s.fused && !s.culled && pair_form(c->opt, p->algo, p->Dh != nullptr, p->mm64).mm16;
+    oa.known = track ? p->known : nullptr, oa.cbeg = p->cbeg, oa.skip = skip ? 1 : 0;
     oa.dbg = nullptr;
 #ifdef TSC_DBG_STAMPS
     if (c->opt.dbg_stamp_k == -p->cur_k) TSC_TRY(stamp_buffer(c, int64_t(o.stamp_blocks) * 4, &oa.dbg));  // (a negative k selects k_open_rows of pass k)
@@ -761,7 +771,7 @@ static int pass_launch(tsc_prune *p, int rank, int world, bool range) {
                                    "choose differently -- create the runs under deterministic_basis = 1, or force prune_algo 1 or 2 on every rank");
     if (s.culled) TSC_TRY(cull_buffers(p));
     p->cur_fused = s.fused;
-    TSC_TRY(open_rows(p, g, s, range));
+    TSC_TRY(open_rows(p, g, s, range, world));
     bool ran_culled = false;
     int64_t rows_now = -1;   // (the pass's rows, where the host has waited for the device anyway)
     if (s.culled) TSC_TRY(culled_pass(p, rank, world, range, g, s, r, &ran_culled, &rows_now));
@@ -1095,6 +1105,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_stats(tsc_prune 
             s.k = rec[slot].k, s.n_active_before = rec[slot].n_before, s.n_active_after = rec[slot].n_after;
             s.pairs_evaluated = rec[slot].evaluated, s.pairs_computed = rec[slot].formed, s.candidates = rec[slot].exact;
             s.pairs_screened = rec[slot].screened, s.new_keys = rec[slot].removed, s.algo = rec[slot].algo;
+            s.pairs_known = rec[slot].known;
             s.nonfinite_input = nonfinite ? 1 : 0;
             float ms = 0;
             if (c->opt.pass_timing >= 2 && hipEventElapsedTime(&ms, p->ev[slot][0], p->ev[slot][3]) == hipSuccess) s.gpu_ms = ms;

@@ -39,6 +39,8 @@ struct tsc_prune : Owned {
     uint8_t *mask = nullptr;
     int32_t *act = nullptr, *cend = nullptr, *best = nullptr;
     int32_t *bsum = nullptr, *boff = nullptr, *tile_cmax = nullptr, *tile_done = nullptr;
+    int32_t *known = nullptr;              // per structure: every still-active column before this position was found dissimilar to it (rmsd.hpp, k_open_rows)
+    int32_t *cbeg = nullptr;               // ... as the first column a row of the open pass still has to look at (a tile's smallest: tile_cmax[2 t + 1])
     int n_blocks = 0;                      // scan blocks (SCAN_TILE structures each) the mask is ranked by
     unsigned long long *bits = nullptr;    // two bit copies of the mask (the pass in flight reads one, clears removed rows in the other)
     unsigned long long *views = nullptr;   // cache view of every pass of the schedule, each followed by its summary (pass_state.hpp, CacheViews)

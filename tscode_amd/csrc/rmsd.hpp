@@ -33,6 +33,7 @@ struct InitArgs {
     int32_t *tile_done;         // arrivals per row tile of the fused pair kernel
     int64_t n_tile_done;
     int32_t *act;
+    int32_t *known;             // known[i]: every still-active column at a position in (i, known[i]) has been found dissimilar to i (k_open_rows); i + 1 here
     int first_slot;
     long long first_k;
     int first_algo;
@@ -50,7 +51,7 @@ inline __global__ __launch_bounds__(256) void k_init_run(InitArgs a) {
     for (int64_t e = (n / 8) * 8 + tid; e < n; e += stride) a.mask[e] = 1;
     // every entry of the active list is a valid structure index from the start: the pair kernel gathers through
     // act[x] for x up to n without knowing the active count
-    for (int64_t e = tid; e < n; e += stride) a.act[e] = int32_t(e);
+    for (int64_t e = tid; e < n; e += stride) a.act[e] = int32_t(e), a.known[e] = int32_t(e + 1);
     if (a.mm_rec) {  // (once per run: the records by position are k_open_rows', every pass)
         const float sigma = mm_scale(*a.rec_dmax_bits);
         for (int64_t e = tid; e < n; e += stride) {
@@ -96,7 +97,7 @@ inline __global__ __launch_bounds__(256) void k_init_run(InitArgs a) {
             const int on = (a.first_k == 1 || 20 * a.first_k < (long long)n) ? 1 : 0;
             PassRecord &fr = a.rec[a.first_slot];
             fr.k = a.first_k, fr.n_before = fr.n_after = (long long)n, fr.on = on, fr.algo = a.first_algo;
-            fr.formed = fr.exact = fr.screened = fr.evaluated = fr.removed = 0;
+            fr.formed = fr.exact = fr.screened = fr.evaluated = fr.removed = fr.known = 0;
             st->pass_on = on;
         }
     }
@@ -146,6 +147,16 @@ struct OpenArgs {
     int32_t *rank_of;                // (optional) rank_of[structure] = its active rank: what a culled pass (cull.hpp) lays its sorted order out from
     _Float16 *Dh;                    // (optional) the float16 records of the matrix-core screen (mm.hpp), by position like Dc
     const unsigned *dmax_bits;       // ... and the largest |descriptor component| of the run that scales them
+    // What earlier passes of the run know about a row (null: nothing is read or kept).  A row i that SURVIVES a pass had every column that was
+    // active between it and its stop position found dissimilar; a pair's verdict depends on its two structures alone and the mask only
+    // shrinks, so no later pass needs to look at the active columns before known[i] = the furthest such stop position again.  cbeg[r] = the
+    // rank of the first active position >= known[i] (>= r + 1), written beside cend[r]; the smallest cbeg of a tile's rows that have columns
+    // left goes beside the tile's largest stop column (tile_cmax[2 t + 1]).  Without `skip`: r + 1 and 0.  A hint: too small a known[] costs work, never a verdict -- too large a one would.
+    int32_t *known;
+    int32_t *cbeg;
+    int skip;                        // the pair kernel behind this launch starts its rows at cbeg and applies its own tiles: a tile whose rows all have
+                                     // cbeg >= cend is dead HERE (tile_cmax = 0) and its rows' cend - r - 1 pairs go to CNT_EVALUATED here; the pairs
+                                     // before cbeg are summed into CNT_KNOWN
     unsigned long long *dbg;         // -DTSC_DBG_STAMPS builds only: 8 time stamps per wavefront (tools/stamps.py), else null
 };
 #ifdef TSC_DBG_STAMPS
@@ -206,6 +217,7 @@ inline __global__ __launch_bounds__(256) void k_open_rows(PassGeom g, OpenArgs o
     if (wave * 4 >= oa.n_tiles) return;  // (padding of the last block)
     TSC_OPEN_STAMP(1);  // bit copy made, prefix staged
     int my_c = 0;        // stop column of this lane's row (0 for lanes without one: the tile maxima below)
+    int my_cb = 0;       // ... and its first column
     if (pass_on && R0 < A) {
         // The kernel is a chain of dependent memory round trips (a light pass is bound by it, not by work): loads that do not depend on
         // each other are issued TOGETHER -- (1) state + prefix, above; (2) the words of the rows' scan blocks; (3) descriptors, the cache
@@ -293,6 +305,7 @@ inline __global__ __launch_bounds__(256) void k_open_rows(PassGeom g, OpenArgs o
         const unsigned long long sum_first = walk ? dsum[(p_lo >> 10) >> 6] : 0ull;
         const int bl_first = __builtin_amdgcn_readfirstlane(int(last / oa.block_items));
         const unsigned long long wl_first = load_block(bl_first);
+        const int64_t known_i = oa.known ? int64_t(oa.known[i]) : i + 1;   // (i + 1 <= known_i <= n)
         // The stop column is the end of the chunk unless the cache view has a hit: the first delta d >= 1 whose key (first, first + d) is in the
         // view AND whose column i + d is active (rmsd_pruning.py:65-67).
         // Rows of ONE chunk (every wavefront of a late pass) look at the same view bits, shifted against the mask by their own position: the
@@ -302,6 +315,11 @@ inline __global__ __launch_bounds__(256) void k_open_rows(PassGeom g, OpenArgs o
         // (the k = 1 pass of C3: 68 us for 21 000 rows).  Wavefronts whose rows lie in several chunks (early passes: short chunks, nearly empty
         // views) walk lane by lane, below.
         const bool one_chunk = __ballot(first != __shfl(first, 0)) == 0;
+        // (the scan block that ranks known_i: requested with the cache view's loads.  The rows of a wavefront mostly share an earlier chunk's end.
+        // Only where the pass's pair kernel starts its rows there, oa.skip: any other tracked pass -- the 64-row and packed-fp32 kernels, a
+        // candidate for culling, k_apply_pass behind the pair kernel -- only RAISES known[], for a later pass of the run that may skip)
+        const int bk = int(known_i / oa.block_items), bk_first = __builtin_amdgcn_readfirstlane(bk);
+        const unsigned long long wk_first = (oa.skip && bk_first != bl_first) ? load_block(bk_first) : 0ull;
         int64_t found = last;
         if (oa.use_cache != 0 && one_chunk) {
             int *list = s_list[wid];
@@ -441,18 +459,24 @@ inline __global__ __launch_bounds__(256) void k_open_rows(PassGeom g, OpenArgs o
         // rank of the stop position = active structures before it: the prefix of its scan block + the set bits of the block below it.
         // The rows of a wavefront share their targets' scan blocks (the chunk's end; a hit a few positions behind its row): one staging
         // per distinct block
+        int my_b = 0;        // first column this row still has to look at (the rank of known_i; r + 1 where nothing is known)
         {
             const int bf = int(found / oa.block_items), off = int(found - int64_t(bf) * oa.block_items);
-            for (unsigned long long pending = __ballot(true); pending;) {
-                const int b = __builtin_amdgcn_readlane(bf, __ffsll((long long)pending) - 1);
-                stage_words(b == bl_first ? wl_first : load_block(b));
-                if (bf == b) {
-                    const int u = off >> 6, below = off & 63;
-                    const int cnt = sp[u] + __popcll(sw[u] & (below ? (~0ull >> (64 - below)) : 0ull));
-                    my_c = (b < oa.n_blocks ? before(b) : n_all) + cnt - row_lo;
-                }
+            const int offk = int(known_i - int64_t(bk) * oa.block_items);
+            auto rank_in = [&](int b, int o) {   // active structures before offset o of the staged block b
+                const int u = o >> 6, below = o & 63;
+                return (b < oa.n_blocks ? before(b) : n_all) + sp[u] + __popcll(sw[u] & (below ? (~0ull >> (64 - below)) : 0ull)) - row_lo;
+            };
+            unsigned long long pend_k = oa.skip ? __ballot(true) : 0ull;
+            for (unsigned long long pending = __ballot(true); pending | pend_k;) {
+                const int b = pending ? __builtin_amdgcn_readlane(bf, __ffsll((long long)pending) - 1) : __builtin_amdgcn_readlane(bk, __ffsll((long long)pend_k) - 1);
+                stage_words(b == bl_first ? wl_first : ((oa.skip && b == bk_first) ? wk_first : load_block(b)));
+                if (bf == b) my_c = rank_in(b, off);
+                if (oa.skip && bk == b) my_b = rank_in(b, offk);
                 pending &= ~__ballot(bf == b);
+                pend_k &= ~__ballot(bk == b);
             }
+            if (!oa.skip) my_b = r + 1;
         }
         TSC_OPEN_STAMP(4);  // stop column's rank
         if (mine) {
@@ -469,6 +493,8 @@ inline __global__ __launch_bounds__(256) void k_open_rows(PassGeom g, OpenArgs o
             }
             act[r] = int32_t(i);
             cend[r] = my_c;
+            oa.cbeg[r] = my_b;
+            if (oa.known && found > known_i) oa.known[i] = int32_t(found);   // (a row this pass removes is never a row again: its entry is never read)
             best[r] = INT_MAX;  // atomicMin target of the pair kernel: no similar column found yet
             if (oa.rank_of) oa.rank_of[i] = r;
         }
@@ -477,17 +503,31 @@ inline __global__ __launch_bounds__(256) void k_open_rows(PassGeom g, OpenArgs o
             for (int off = 32; off > 0; off >>= 1) w += __shfl_xor(w, off);
             if (lane == 0) count_add(sc.cnt, wave, CNT_WALK, (unsigned long long)w);
         }
-        if (!mine) my_c = 0;
+        if (!mine) my_c = 0, my_b = 0;
+        my_cb = my_b;
         TSC_OPEN_STAMP(5);  // everything written
     }
     // largest stop column of the 16 rows of every tile: lets a work item of the pair kernel whose column segment lies
     // beyond it leave after one scalar load (0: every work item of the tile leaves at its first test -- also for a pass that is
     // gated off and for tiles beyond the active count)
-    int cmax = my_c;
+    // ... and the smallest first column of the rows that have columns left (INT_MAX: none has -- under oa.skip the tile is dead, cmax = 0, and
+    // what its rows' verdicts would have counted as evaluated, cend - r - 1 each, is counted here: nobody applies a dead tile)
+    int cmax = my_c, cmin = my_cb < my_c ? my_cb : INT_MAX;
 #pragma unroll
-    for (int off = 8; off > 0; off >>= 1) cmax = max(cmax, __shfl_xor(cmax, off));
+    for (int off = 8; off > 0; off >>= 1) cmax = max(cmax, __shfl_xor(cmax, off)), cmin = min(cmin, __shfl_xor(cmin, off));
+    if (oa.skip) {
+        const int r_lane = int(wave) * OPEN_ROWS + lane;
+        const bool owes = cmin == INT_MAX && my_c > r_lane + 1;               // (my_c = 0 for lanes without a row)
+        unsigned long long ev = owes ? (unsigned long long)(my_c - r_lane - 1) : 0ull;
+        unsigned long long kn = my_c > 0 ? (unsigned long long)max(0, min(my_cb, my_c) - r_lane - 1) : 0ull;
+        if (__ballot(ev != 0ull || kn != 0ull)) {
+            for (int off = 32; off > 0; off >>= 1) ev += __shfl_xor(ev, off), kn += __shfl_xor(kn, off);
+            if (lane == 0) count_add(sc.cnt, wave, CNT_EVALUATED, ev), count_add(sc.cnt, wave, CNT_KNOWN, kn);
+        }
+        if (cmin == INT_MAX) cmax = 0;
+    }
     const bool tile_lane = (lane & 15) == 0 && tile < oa.n_tiles;
-    if (tile_lane) tile_cmax[tile] = cmax;
+    if (tile_lane) tile_cmax[2 * tile] = cmax, tile_cmax[2 * tile + 1] = oa.skip ? cmin : 0;
     // no work item of the pair kernel will find a column for this tile: it has nothing to apply and arrives here
     const bool dead = tile_lane && cmax <= ((int(tile) * 16 + 1) & ~63);
     if (!oa.fused || !__ballot(dead)) return;
@@ -680,7 +720,7 @@ inline __global__ __launch_bounds__(1024) void k_pass_merge(MergeArgs a, StepCtx
             on = (sa.k_cur == 1 || 20 * sa.k_cur < (long long)n_active) ? 1 : 0;  // rmsd_pruning.py:192
             PassRecord &r = sc.rec[sa.cur];
             r.k = sa.k_cur, r.n_before = n_active, r.n_after = n_active, r.on = on, r.algo = sa.algo_cur;
-            r.formed = r.exact = r.screened = r.evaluated = r.removed = 0;
+            r.formed = r.exact = r.screened = r.evaluated = r.removed = r.known = 0;
         }
         sn->pass_on = on;
         sn->ticket = 0;

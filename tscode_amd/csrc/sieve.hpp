@@ -33,7 +33,11 @@ struct SieveArgs {
     double half_h_thr2;   // h * thr^2 / 2
     double two_thr2;      // 2 thr^2 when the near-duplicate test applies (h >= 4), else -1
     int drain_min;        // queue length that triggers a drain between column tiles (1..64)
-    const int32_t *tile_cmax;   // device: per row tile, the largest stop column of its 16 rows (k_open_rows)
+    const int32_t *tile_cmax;   // device: per row tile a pair -- [2 t] the largest stop column of its 16 rows, [2 t + 1] the smallest first column of its
+                                // rows that have columns left (k_open_rows; 0 where the pass's rows start behind their diagonal)
+    const int32_t *cbeg;        // device: per row, the first column the pass still has to look at -- the columns before it were found dissimilar by
+                                // an earlier pass (k_open_rows, known[]); r + 1 where the pass does not skip.  A HINT: a kernel that ignores it and
+                                // the tiles' smallest evaluates known pairs again, to the same verdicts
     const unsigned *dmax_bits;  // device: largest |descriptor component| of the run (bit pattern of a float), see screen_limit32
     double desc_limit;          // h thr^2: exact squared descriptor distance above which a pair is certainly dissimilar
     const float *heavy32;       // float32 copy of the heavy atoms (heavy32_pitch(h) floats per structure), or null: stage 1 in float64 only
@@ -479,7 +483,7 @@ inline __global__ __launch_bounds__(256, CPL == 4 ? 4 : (CPL == 2 ? TSC_SIEVE_OC
     if (r0 >= a.n || seg_lo >= a.n) return;  // beyond the upper bound the grid was sized for: nothing to read
     // most items of a pass with long chunks start beyond every stop column of their row tile (0 for a tile without rows or
     // a pass that is gated off: k_open_rows): one scalar load and out
-    const int tcm = a.tile_cmax[tile];
+    const int tcm = a.tile_cmax[2 * tile];
     if (tcm <= seg_lo) return;
     int A = 0, bitsel = 0;
     sieve_item<TI, CPL, TRIM, F32>(heavy, act, Gall, D, cend, best, counters, st, a, A, bitsel);
