@@ -122,7 +122,7 @@ def test_units_outside_the_prune_depend_on_none_of_its_headers(unit, unit_depend
 PROBES = {"pass_plan_check.cpp": ["pass_plan.hpp", "shapes.hpp"], "prune_batch_plan_check.cpp": ["pass_plan.hpp", "shapes.hpp"],
           "call_host_check.cpp": ["call.hpp", "embed_clash.hpp"], "cross_plan_check.cpp": ["cross_plan.hpp"],
           "embed_prune_plan_check.cpp": ["embed_prune_plan.hpp"], "options_check.cpp": ["options.hpp"],
-          "owned_check.cpp": ["owned.hpp", "common.hpp"]}
+          "owned_check.cpp": ["owned.hpp", "common.hpp"], "pass_cursor_check.cpp": ["pass_cursor.hpp"]}
 
 
 @pytest.mark.parametrize("probe", list(PROBES))

@@ -197,8 +197,11 @@ static int build_descriptors(tsc_prune *p, const double *basis) {
     return 0;  // the scratch blocks go back to the stream-ordered cache: later users run after these kernels
 }
 
-static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int h, double rmsd_thr, int mode, uint8_t *mask_buffer, tsc_prune **out,
-                             const double *basis = nullptr, const ExternalDescriptors *ext = nullptr, int force_algo = -1) {
+// ---- tsc_prune_create in steps; every error behind the first is undone by tsc_prune_destroy, at the one caller (prune_create_impl) ----
+
+// 1. the argument checks and the registration: the run with its word of pinned memory (the culled-or-walked verdict of a candidate pass)
+// and its entry in the context's list
+static int prune_register(tsc_ctx *c, const double *heavy_dev, int64_t n, int h, double rmsd_thr, int mode, tsc_prune **out, tsc_prune **run) {
     TSC_REQUIRE(c && heavy_dev && out, "tsc_prune_create: null argument");
     TSC_REQUIRE(n > 0 && n < INT32_MAX - 4096, "n = %lld not supported", (long long)n);
     TSC_REQUIRE(h > 0, "no heavy atoms: the reference divides by zero here (rmsd_pruning.py:35)");
@@ -206,7 +209,6 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
     TSC_REQUIRE(rmsd_thr > 0, "rmsd_thr must be positive");
     TSC_REQUIRE(c->opt.prune_algo != ALGO_TILE || h <= MAX_HP, "prune_algo=1 (register-tiled kernel) supports at most %d heavy atoms, got %d", MAX_HP, h);
     *out = nullptr;
-    DeviceGuard guard(c->device);
     tsc_prune *p = new (std::nothrow) tsc_prune(c);
     if (!p) return fail(TSC_ERR_NOMEM, "out of host memory");
     p->heavy = heavy_dev;
@@ -218,147 +220,176 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
     p->mode = mode;
     p->algo = (c->opt.prune_algo == ALGO_TILE) ? ALGO_TILE : ALGO_SIEVE;
     p->det_desc = c->opt.deterministic_basis != 0;
-    {   // this run's word of pinned memory (the culled-or-walked verdict of a candidate pass), and its entry in the context's list: early, every error path below is tsc_prune_destroy
-        std::lock_guard<std::mutex> lock(c->owned.mutex);
-        static_assert(PINNED_FLAG_SLOTS == 64, "one bit per flag word");
-        const int slot = ~c->flag_slots_used ? __builtin_ctzll(~c->flag_slots_used) : -1;
-        if (slot < 0) {
-            delete p;
-            return fail(TSC_ERR_STATE, "tsc_prune_create: %d prune runs are alive on this context, the most it serves at a time (destroy some, or use a "
-                                       "context per thread)", PINNED_FLAG_SLOTS);
-        }
-        c->flag_slots_used |= 1ull << slot;
-        p->flag_slot = slot;
-        c->owned.adopt_locked(p);
+    p->cur.start(n);   // (the first pass of the schedule is opened by k_init_run itself)
+    std::lock_guard<std::mutex> lock(c->owned.mutex);
+    static_assert(PINNED_FLAG_SLOTS == 64, "one bit per flag word");
+    const int slot = ~c->flag_slots_used ? __builtin_ctzll(~c->flag_slots_used) : -1;
+    if (slot < 0) {
+        delete p;
+        return fail(TSC_ERR_STATE, "tsc_prune_create: %d prune runs are alive on this context, the most it serves at a time (destroy some, or use a "
+                                   "context per thread)", PINNED_FLAG_SLOTS);
     }
-    Scratch s_basis(c);
-    if (force_algo >= 0) {
-        p->algo = force_algo;
-    } else if (c->opt.prune_algo == ALGO_AUTO && mode == 1 && h <= MAX_HP && n >= AUTO_TILE_MIN_N && !basis && !(ext && ext->D)) {
-        // automatic choice, no basis from a pipeline around this run: estimate it now and ask whether the screen can separate
-        // anything (one synchronisation, some 20 us, on a run of at least 30 000 structures)
-        const int n_samples = int(std::min<int64_t>(n, DESC_SAMPLE));
-        double *q = nullptr;
-        int rc0 = s_basis.get(basis_doubles(h), &q);
-        if (!rc0) rc0 = build_basis(c, c->stream, s_basis, heavy_dev, h, n_samples, std::max<int64_t>(1, n / n_samples), q);
-        if (!rc0) {
-            double *host = reinterpret_cast<double *>(static_cast<char *>(c->pinned) + PINNED_SPREAD_OFFSET);
-            hipError_t e = hipMemcpyAsync(host, q + basis_spread_offset(h), NFAM * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) rc0 = fail(TSC_ERR_HIP, "descriptor spread read-back failed: %s", hipGetErrorString(e));
-            else if (screen_is_useless(host, h, rmsd_thr)) p->algo = ALGO_TILE, p->auto_tile = true;
-            else basis = q;  // (the sieve's descriptors are built from it further down)
-        }
-        if (rc0) {
-            tsc_prune_destroy(p);
-            return rc0;
-        }
-    }
-    p->bit_words = size_t(n / 64 + 40);  // (k_open_rows reads the 32 words of a whole scan block, also of the last, partial one)
-    p->n_blocks = int(scan_bsum_count(n));
-    int rc = 0;
-    if (mask_buffer)
-        p->mask = mask_buffer;  // the caller's verdict buffer serves as the working mask (8-byte aligned, n bytes)
-    else if (!rc)
-        rc = p->get(size_t(n), &p->mask);
-    if (!rc) rc = p->get(size_t(n), &p->act);
-    if (!rc) rc = p->get(size_t(n), &p->cend);
-    if (!rc) rc = p->get(size_t(n), &p->best);
-    if (!rc) rc = p->get(size_t(p->n_blocks) + 1, &p->bsum);
-    if (!rc) rc = p->get(size_t(p->n_blocks) + 1, &p->boff);
-    if (!rc) rc = p->get(2 * (size_t(n) / 16 + 8), &p->tile_cmax);  // (per tile: largest stop column, smallest first column)
-    if (!rc) rc = p->get(size_t(n) / 16 + 8, &p->tile_done);
-    if (!rc) rc = p->get(size_t(n), &p->known);
-    if (!rc) rc = p->get(size_t(n), &p->cbeg);
-    if (!rc) rc = p->get(2 * p->bit_words, &p->bits);
-    p->dsum_words = p->bit_words / 1024 + 4;  // one summary bit per 1024 cache-view bits, kept right behind the view
-    p->n_views = 0;
-    for (int slot = 0; slot < TSC_MAX_PASSES; ++slot) p->view_of_slot[slot] = (pass_can_run(n, slot) && mode == 0) ? p->n_views++ : -1;
-    if (!rc) rc = p->get(std::max<size_t>(1, size_t(p->n_views) * (p->bit_words + p->dsum_words)), &p->views);
-    if (!rc) rc = p->get(TSC_MAX_PASSES, &p->view_pass);
-    if (!rc) rc = p->get(TSC_MAX_PASSES, &p->counters_all);
-    if (!rc) rc = p->get(TSC_MAX_PASSES, &p->state_all);
+    c->flag_slots_used |= 1ull << slot;
+    p->flag_slot = slot;
+    c->owned.adopt_locked(p);
+    *run = p;
+    return 0;
+}
+
+// 2. the pair kernel of the run, where neither the caller nor the options name it and no basis comes from a pipeline around the run: estimate
+// the basis now and ask whether the screen can separate anything (one synchronisation, some 20 us, on a run of at least 30 000 structures).
+// *basis: the estimate, where the sieve's descriptors are to be built from it
+static int choose_kernel(tsc_prune *p, Scratch &s_basis, const double **basis, const ExternalDescriptors *ext, int force_algo) {
+    tsc_ctx *c = p->ctx;
+    if (force_algo >= 0) p->algo = force_algo;
+    if (force_algo >= 0 || !(c->opt.prune_algo == ALGO_AUTO && p->mode == 1 && p->h <= MAX_HP && p->n >= AUTO_TILE_MIN_N && !*basis && !(ext && ext->D))) return 0;
+    const int n_samples = int(std::min<int64_t>(p->n, DESC_SAMPLE));
+    double *q = nullptr;
+    TSC_TRY(s_basis.get(basis_doubles(p->h), &q));
+    TSC_TRY(build_basis(c, c->stream, s_basis, p->heavy, p->h, n_samples, std::max<int64_t>(1, p->n / n_samples), q));
+    double *host = reinterpret_cast<double *>(static_cast<char *>(c->pinned) + PINNED_SPREAD_OFFSET);
+    hipError_t e = hipMemcpyAsync(host, q + basis_spread_offset(p->h), NFAM * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(TSC_ERR_HIP, "descriptor spread read-back failed: %s", hipGetErrorString(e));
+    if (screen_is_useless(host, p->h, p->thr)) p->algo = ALGO_TILE, p->auto_tile = true;
+    else *basis = q;  // (the sieve's descriptors are built from it further down)
+    return 0;
+}
+
+// 3. the run's blocks: what every run has ...
+static int alloc_always(tsc_prune *p, uint8_t *mask_buffer) {
+    const size_t n = size_t(p->n);
+    p->bit_words = bit_words_of(p->n), p->dsum_words = dsum_words_of(p->bit_words);
+    p->n_blocks = int(scan_bsum_count(p->n));
+    if (mask_buffer) p->mask = mask_buffer;  // the caller's verdict buffer serves as the working mask (8-byte aligned, n bytes)
+    else TSC_TRY(p->get(n, &p->mask));
+    TSC_TRY(p->get(n, &p->act));
+    TSC_TRY(p->get(n, &p->cend));
+    TSC_TRY(p->get(n, &p->best));
+    TSC_TRY(p->get(size_t(p->n_blocks) + 1, &p->bsum));
+    TSC_TRY(p->get(size_t(p->n_blocks) + 1, &p->boff));
+    TSC_TRY(p->get(2 * (n / 16 + 8), &p->tile_cmax));  // (per tile: largest stop column, smallest first column)
+    TSC_TRY(p->get(n / 16 + 8, &p->tile_done));
+    TSC_TRY(p->get(n, &p->known));
+    TSC_TRY(p->get(n, &p->cbeg));
+    TSC_TRY(p->get(2 * p->bit_words, &p->bits));
+    int v = 0;
+    for (int slot = 0; slot < TSC_MAX_PASSES; ++slot) p->view_of_slot[slot] = (pass_can_run(p->n, slot) && p->mode == 0) ? v++ : -1;
+    p->n_views = n_views_of(p->n, p->mode);
+    TSC_TRY(p->get(std::max<size_t>(1, size_t(p->n_views) * view_stride(p->bit_words)), &p->views));
+    TSC_TRY(p->get(TSC_MAX_PASSES, &p->view_pass));
+    TSC_TRY(p->get(TSC_MAX_PASSES, &p->counters_all));
+    TSC_TRY(p->get(TSC_MAX_PASSES, &p->state_all));
     p->counters = p->counters_all, p->state = p->state_all;  // (pass_launch moves them to the slot of the pass in flight)
-    if (!rc) rc = p->get(TSC_MAX_PASSES, &p->records);
-    const bool own_desc = !(ext && ext->D);  // (external descriptors: already enqueued on this stream, the caller owns the buffers)
-    if (!rc && p->algo == ALGO_SIEVE) {
-        if (own_desc) {
-            rc = p->get(size_t(n) * DW, &p->Dall);
-            if (!rc) rc = p->get(size_t(n), &p->Gall);
-            if (!rc) rc = p->get(4, &p->dmax_bits);
-        } else {
-            p->Dall = ext->D, p->Gall = ext->G, p->dmax_bits = ext->dmax_bits;
-        }
-        if (!rc) rc = p->get(size_t(n) * DW, &p->Dc);
-        // (mm.hpp; decided per run: the 64-row kernels for large runs, the 16-row form of the walked kernel -- "sieve_mm16" -- below that)
-        p->mm64 = c->opt.sieve_mm == 2 || (c->opt.sieve_mm == 1 && n >= c->opt.mm_min_n);
-        const bool want_mm = p->mm64 || c->opt.sieve_mm16 != 0;
-        if (!rc && want_mm) rc = p->get(size_t(n) * MM_REC_HALVES, &p->Dh);
-        // the records by structure index of the chunk-local pass's matrix-core screen ("sieve_mm16"): only where a pass of the schedule can have
-        // chunks short enough for that kernel (a rank's share of a partitioned pass may leave the longer last chunk to another rank)
-        bool local_possible = false;
-        for (int slot = 0; slot < TSC_MAX_PASSES; ++slot)
-            local_possible = local_possible || (pass_can_run(n, slot) && n / int64_t(KS[slot]) <= std::min(LP_MAX_ROWS, c->opt.local_max_chunk));
-        if (!rc && c->opt.sieve_mm16 != 0 && c->opt.local_pass != 0 && local_possible) rc = p->get(size_t(n) * MM_REC_HALVES, &p->Drec);
-        // the float32 copy stage 1 reads (pair_stages.hpp, pair_stage1): from the embedding kernel where there was one, else converted here
-        // (it pays where the gathers come from HBM: 41 MB of heavy atoms at C3 sit in the 256 MB infinity cache and the conversions cost the
-        // VALU-bound kernel 2 %; at C4's 348 MB a step goes from 12.1 to 10.6 ms.  "stage1_f32": 0 never, 1 from 128 MB on, 2 always)
-        if (!rc && want_heavy32(c->opt, double(n) * h * 24.0)) {
-            if (ext && ext->heavy32) {  // written by the kernel that embedded the structures
-                p->heavy32 = ext->heavy32;
-            } else {
-                rc = p->get(size_t(n) * heavy32_pitch(h), &p->heavy32);
-                if (!rc) hipLaunchKernelGGL(k_heavy32, dim3(unsigned(std::min<int64_t>(ceil_div<int64_t>(n * heavy32_pitch(h), 256), 65536))), dim3(256), 0, c->stream,
-                                            heavy_dev, n, h, p->heavy32);
-            }
-        }
+    TSC_TRY(p->get(TSC_MAX_PASSES, &p->records));
+    return 0;
+}
+
+// ... what the sieve kernels read (external descriptors: already enqueued on this stream, the caller owns the buffers) ...
+static int alloc_sieve(tsc_prune *p, const ExternalDescriptors *ext) {
+    tsc_ctx *c = p->ctx;
+    const int64_t n = p->n;
+    if (ext && ext->D) {
+        p->Dall = ext->D, p->Gall = ext->G, p->dmax_bits = ext->dmax_bits;
+    } else {
+        TSC_TRY(p->get(size_t(n) * DW, &p->Dall));
+        TSC_TRY(p->get(size_t(n), &p->Gall));
+        TSC_TRY(p->get(4, &p->dmax_bits));
     }
-    if (!rc) rc = p->get(1, &p->tickets);
-    if (!rc && p->algo == ALGO_TILE) {
-        const size_t hp3 = size_t(p->hp) * 3;
-        rc = p->get(size_t(p->npad) * hp3, &p->Xr);
-        if (!rc) rc = p->get(size_t(p->npad) * hp3, &p->Xc);
-        if (!rc) rc = p->get(size_t(p->npad), &p->G);
+    TSC_TRY(p->get(size_t(n) * DW, &p->Dc));
+    // (mm.hpp; decided per run: the 64-row kernels for large runs, the 16-row form of the walked kernel -- "sieve_mm16" -- below that)
+    p->mm64 = c->opt.sieve_mm == 2 || (c->opt.sieve_mm == 1 && n >= c->opt.mm_min_n);
+    if (p->mm64 || c->opt.sieve_mm16 != 0) TSC_TRY(p->get(size_t(n) * MM_REC_HALVES, &p->Dh));
+    // the records by structure index of the chunk-local pass's matrix-core screen ("sieve_mm16"): only where a pass of the schedule can have
+    // chunks short enough for that kernel (a rank's share of a partitioned pass may leave the longer last chunk to another rank)
+    bool local_possible = false;
+    for (int slot = 0; slot < TSC_MAX_PASSES; ++slot)
+        local_possible = local_possible || (pass_can_run(n, slot) && n / int64_t(KS[slot]) <= std::min(LP_MAX_ROWS, c->opt.local_max_chunk));
+    if (c->opt.sieve_mm16 != 0 && c->opt.local_pass != 0 && local_possible) TSC_TRY(p->get(size_t(n) * MM_REC_HALVES, &p->Drec));
+    // the float32 copy stage 1 reads (pair_stages.hpp, pair_stage1): from the embedding kernel where there was one, else converted here
+    // (it pays where the gathers come from HBM: 41 MB of heavy atoms at C3 sit in the 256 MB infinity cache and the conversions cost the
+    // VALU-bound kernel 2 %; at C4's 348 MB a step goes from 12.1 to 10.6 ms.  "stage1_f32": 0 never, 1 from 128 MB on, 2 always)
+    if (!want_heavy32(c->opt, double(n) * p->h * 24.0)) return 0;
+    if (ext && ext->heavy32) {  // written by the kernel that embedded the structures
+        p->heavy32 = ext->heavy32;
+        return 0;
     }
-    if (!rc) {
-        hipStream_t st = c->stream;
-        int first_slot = -1;  // the pass tsc_prune_next_pass will hand out first: opened by k_init_run itself
-        for (int slot = 0; slot < TSC_MAX_PASSES && first_slot < 0; ++slot)
-            if (pass_can_run(n, slot)) first_slot = slot;
-        p->opened_slot = first_slot;
-        InitArgs ia;
-        memset(&ia, 0, sizeof(ia));
-        ia.n = n, ia.mask = p->mask, ia.bits = p->bits, ia.bit_words = int(p->bit_words);
-        ia.views = p->views, ia.view_words = int64_t(p->n_views) * int64_t(p->bit_words + p->dsum_words), ia.view_pass = p->view_pass, ia.n_views = p->n_views;
-        for (int slot = 0; slot < TSC_MAX_PASSES; ++slot)
-            if (p->view_of_slot[slot] >= 0) ia.sched[p->view_of_slot[slot]] = view_pass(int(n), int(KS[slot]));
-        ia.st = p->state_all, ia.rec = p->records, ia.n_rec = TSC_MAX_PASSES, ia.cnt = p->counters_all;  // (every slot's)
-        ia.bsum = p->bsum, ia.boff = p->boff, ia.n_blocks = p->n_blocks, ia.block_items = SCAN_TILE;
-        ia.dmax_bits = own_desc ? p->dmax_bits : nullptr;
-        // the arrival counters and the per-tile ones lie in two blocks: the tickets are zeroed here, tile_done by its own loop below
-        ia.zero_words = reinterpret_cast<unsigned *>(p->tickets), ia.n_zero_words = int64_t(sizeof(*p->tickets) / sizeof(unsigned));
-        ia.act = p->act, ia.first_slot = first_slot, ia.first_k = first_slot >= 0 ? (long long)KS[first_slot] : 0ll, ia.first_algo = p->algo;
-        ia.tile_done = p->tile_done, ia.n_tile_done = n / 16 + 8;
-        ia.known = p->known;
-        // External descriptors (and their maximum) were enqueued on this stream in front of the run: final here, k_init_run writes the records by
-        // structure as it walks n (two structures per thread then, not eight).  A run that builds its own descriptors does so BEHIND this launch,
-        // which zeroes the maximum they raise: its records come from k_mm_records behind build_descriptors, below.
-        const bool rec_here = p->Drec && !own_desc;
-        if (rec_here) ia.Dall = p->Dall, ia.rec_dmax_bits = p->dmax_bits, ia.mm_rec = p->Drec;
-        hipLaunchKernelGGL(k_init_run, dim3(grid_for(n / (rec_here ? 2 : 8) + 1, 256, 512)), dim3(256), 0, st, ia);
-        hipError_t e = hipGetLastError();
-        // padded columns of the compacted layouts are read by the last column tile of a segment but never used; the
-        // register-tiled kernel's buffers are zeroed once so that those reads see finite numbers
-        if (e == hipSuccess && p->Xc) e = hipMemsetAsync(p->Xc, 0, size_t(p->npad) * p->hp * 3 * sizeof(double), st);
-        if (e == hipSuccess && p->Xr) e = hipMemsetAsync(p->Xr, 0, size_t(p->npad) * p->hp * 3 * sizeof(double), st);
-        if (e == hipSuccess && p->G) e = hipMemsetAsync(p->G, 0, size_t(p->npad) * sizeof(double), st);
-        if (e != hipSuccess) rc = fail(TSC_ERR_HIP, "prune state setup failed: %s", hipGetErrorString(e));
+    TSC_TRY(p->get(size_t(n) * heavy32_pitch(p->h), &p->heavy32));
+    hipLaunchKernelGGL(k_heavy32, dim3(unsigned(std::min<int64_t>(ceil_div<int64_t>(n * heavy32_pitch(p->h), 256), 65536))), dim3(256), 0, c->stream, p->heavy, n,
+                       p->h, p->heavy32);
+    return 0;
+}
+
+// ... and the compacted layouts of the register-tiled kernel
+static int alloc_tile(tsc_prune *p) {
+    const size_t hp3 = size_t(p->hp) * 3;
+    TSC_TRY(p->get(size_t(p->npad) * hp3, &p->Xr));
+    TSC_TRY(p->get(size_t(p->npad) * hp3, &p->Xc));
+    TSC_TRY(p->get(size_t(p->npad), &p->G));
+    return 0;
+}
+
+// 4. what k_init_run is handed.  rec_here: it also writes the records by structure (two structures per thread then, not eight)
+static InitArgs init_args(const tsc_prune *p, bool own_desc, bool rec_here) {
+    const int first_slot = p->cur.opened;  // the pass tsc_prune_next_pass will hand out first: opened by k_init_run itself
+    InitArgs ia;
+    memset(&ia, 0, sizeof(ia));
+    ia.n = p->n, ia.mask = p->mask, ia.bits = p->bits, ia.bit_words = int(p->bit_words);
+    ia.views = p->views, ia.view_words = int64_t(p->n_views) * int64_t(view_stride(p->bit_words)), ia.view_pass = p->view_pass, ia.n_views = p->n_views;
+    for (int slot = 0; slot < TSC_MAX_PASSES; ++slot)
+        if (p->view_of_slot[slot] >= 0) ia.sched[p->view_of_slot[slot]] = view_pass(int(p->n), int(KS[slot]));
+    ia.st = p->state_all, ia.rec = p->records, ia.n_rec = TSC_MAX_PASSES, ia.cnt = p->counters_all;  // (every slot's)
+    ia.bsum = p->bsum, ia.boff = p->boff, ia.n_blocks = p->n_blocks, ia.block_items = SCAN_TILE;
+    ia.dmax_bits = own_desc ? p->dmax_bits : nullptr;
+    // the arrival counters and the per-tile ones lie in two blocks: the tickets are zeroed here, tile_done by its own loop below
+    ia.zero_words = reinterpret_cast<unsigned *>(p->tickets), ia.n_zero_words = int64_t(sizeof(*p->tickets) / sizeof(unsigned));
+    ia.act = p->act, ia.first_slot = first_slot, ia.first_k = first_slot >= 0 ? (long long)KS[first_slot] : 0ll, ia.first_algo = p->algo;
+    ia.tile_done = p->tile_done, ia.n_tile_done = p->n / 16 + 8;
+    ia.known = p->known;
+    if (rec_here) ia.Dall = p->Dall, ia.rec_dmax_bits = p->dmax_bits, ia.mm_rec = p->Drec;
+    return ia;
+}
+
+// 5. the launches: the state of every slot, then the descriptors and records of a run that builds its own
+static int first_launches(tsc_prune *p, const double *basis, bool own_desc) {
+    hipStream_t st = p->ctx->stream;
+    const int64_t n = p->n;
+    // External descriptors (and their maximum) were enqueued on this stream in front of the run: final here, k_init_run writes the records by
+    // structure as it walks n.  A run that builds its own descriptors does so BEHIND this launch, which zeroes the maximum they raise: its
+    // records come from k_mm_records behind build_descriptors, below.
+    const bool rec_here = p->Drec && !own_desc;
+    hipLaunchKernelGGL(k_init_run, dim3(grid_for(n / (rec_here ? 2 : 8) + 1, 256, 512)), dim3(256), 0, st, init_args(p, own_desc, rec_here));
+    hipError_t e = hipGetLastError();
+    // padded columns of the compacted layouts are read by the last column tile of a segment but never used; the
+    // register-tiled kernel's buffers are zeroed once so that those reads see finite numbers
+    if (e == hipSuccess && p->Xc) e = hipMemsetAsync(p->Xc, 0, size_t(p->npad) * p->hp * 3 * sizeof(double), st);
+    if (e == hipSuccess && p->Xr) e = hipMemsetAsync(p->Xr, 0, size_t(p->npad) * p->hp * 3 * sizeof(double), st);
+    if (e == hipSuccess && p->G) e = hipMemsetAsync(p->G, 0, size_t(p->npad) * sizeof(double), st);
+    if (e != hipSuccess) return fail(TSC_ERR_HIP, "prune state setup failed: %s", hipGetErrorString(e));
+    if (p->Dall && own_desc) TSC_TRY(build_descriptors(p, basis));
+    if (p->Drec && own_desc) {
+        hipLaunchKernelGGL(k_mm_records, dim3(grid_for(n, 256, 1024)), dim3(256), 0, st, (const float *)p->Dall, n, (const unsigned *)p->dmax_bits, p->Drec);
+        if (hipGetLastError() != hipSuccess) return fail(TSC_ERR_HIP, "the records of the chunk-local pass could not be written");
     }
-    if (!rc && p->Dall && own_desc) rc = build_descriptors(p, basis);
-    if (!rc && p->Drec && own_desc) {
-        hipLaunchKernelGGL(k_mm_records, dim3(grid_for(n, 256, 1024)), dim3(256), 0, c->stream, (const float *)p->Dall, n, (const unsigned *)p->dmax_bits, p->Drec);
-        if (hipGetLastError() != hipSuccess) rc = fail(TSC_ERR_HIP, "the records of the chunk-local pass could not be written");
-    }
+    return 0;
+}
+
+static int prune_setup(tsc_prune *p, uint8_t *mask_buffer, const double *basis, const ExternalDescriptors *ext, int force_algo) {
+    Scratch s_basis(p->ctx);
+    TSC_TRY(choose_kernel(p, s_basis, &basis, ext, force_algo));
+    TSC_TRY(alloc_always(p, mask_buffer));
+    if (p->algo == ALGO_SIEVE) TSC_TRY(alloc_sieve(p, ext));
+    TSC_TRY(p->get(1, &p->tickets));
+    if (p->algo == ALGO_TILE) TSC_TRY(alloc_tile(p));
+    return first_launches(p, basis, !(ext && ext->D));
+}
+
+static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int h, double rmsd_thr, int mode, uint8_t *mask_buffer, tsc_prune **out,
+                             const double *basis = nullptr, const ExternalDescriptors *ext = nullptr, int force_algo = -1) {
+    tsc_prune *p = nullptr;
+    TSC_TRY(prune_register(c, heavy_dev, n, h, rmsd_thr, mode, out, &p));
+    DeviceGuard guard(c->device);
+    const int rc = prune_setup(p, mask_buffer, basis, ext, force_algo);
     if (rc) {
         tsc_prune_destroy(p);
         return rc;
@@ -366,7 +397,6 @@ static int prune_create_impl(tsc_ctx *c, const double *heavy_dev, int64_t n, int
     *out = p;
     return 0;
 }
-
 
 extern "C" __attribute__((visibility("default"))) int tsc_prune_create(tsc_ctx *c, const double *heavy_dev, int64_t n, int h, double rmsd_thr, int mode, tsc_prune **out) {
     TSC_API_GUARD_BEGIN
@@ -395,22 +425,19 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_create(tsc_ctx *
     TSC_API_GUARD_END
 }
 
+// the call order of the stepping API (pass_cursor.hpp: refusal): 0, or TSC_ERR_STATE with the message of the entry point
+static int allowed(const tsc_prune *p, StepCall call) {
+    const char *why = p->cur.refusal(call);
+    return why ? fail(TSC_ERR_STATE, "%s", why) : 0;
+}
+
 extern "C" __attribute__((visibility("default"))) int tsc_prune_next_pass(tsc_prune *p, int64_t *k_out) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p && k_out, "null argument");
-    if (p->cur_k != 0) return fail(TSC_ERR_STATE, "tsc_prune_next_pass: previous pass not finished");
-    *k_out = 0;
-    while (p->next_ks < TSC_MAX_PASSES) {
-        const int slot = p->next_ks++;
-        if (pass_can_run(p->n, slot)) {
-            const int64_t k = int64_t(KS[slot]);
-            p->cur_k = k;
-            p->cur_slot = slot;
-            p->local_done = false;
-            *k_out = k;
-            return 0;
-        }
-    }
+    TSC_TRY(allowed(p, StepCall::NextPass));
+    const int slot = p->cur.next_slot();
+    p->cur.begin(slot);
+    *k_out = slot >= 0 ? p->cur.k : 0;
     return 0;
     TSC_API_GUARD_END
 }
@@ -420,8 +447,8 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_next_pass(tsc_pr
 extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_estimate(tsc_prune *p, int64_t *pairs) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p && pairs, "null argument");
-    if (p->cur_k == 0) return fail(TSC_ERR_STATE, "tsc_prune_pass_estimate: no pass open");
-    *pairs = p->n * (p->n / p->cur_k) / 2;
+    TSC_TRY(allowed(p, StepCall::Estimate));
+    *pairs = p->n * (p->n / p->cur.k) / 2;
     return 0;
     TSC_API_GUARD_END
 }
@@ -435,7 +462,7 @@ struct PairEvents {
 };
 static PairEvents pair_events(const tsc_prune *p, int level) {
     const bool on = p->ctx->opt.pass_timing >= level;
-    return PairEvents{on ? p->ev[p->cur_slot][1] : nullptr, on ? p->ev[p->cur_slot][2] : nullptr};
+    return PairEvents{on ? p->ev[p->cur.slot][1] : nullptr, on ? p->ev[p->cur.slot][2] : nullptr};
 }
 
 // the thresholds of the open run, the same in every argument block that has them (pass_plan.hpp: thresholds)
@@ -483,12 +510,12 @@ static int stamp_buffer(tsc_ctx *c, int64_t waves, unsigned long long **dbg) {
 #endif
 
 // ---- the walked pass: the pair search of one rank's row tiles of the open pass, in index order (step 3 of a pass; steps 1-2 have run) ----
-// rows_ub, rows_now: pass_plan.hpp, plan_walked
-static int walked_pass(tsc_prune *p, int rank, int world, int64_t rows_ub, int64_t rows_now = -1) {
+// fused: the pair kernel applies the rows of its own tiles; rows_ub, rows_now: pass_plan.hpp, plan_walked
+static int walked_pass(tsc_prune *p, int rank, int world, bool fused, int64_t rows_ub, int64_t rows_now = -1) {
     tsc_ctx *c = p->ctx;
     hipStream_t st = c->stream;
     const PairForm form = pair_form(c->opt, p->algo, p->Dh != nullptr, p->mm64);
-    const WalkedPlan w = plan_walked(c->opt, p->n, p->cur_k, rank, world, rows_ub, rows_now, form);
+    const WalkedPlan w = plan_walked(c->opt, p->n, p->cur.k, rank, world, rows_ub, rows_now, form);
     const PairEvents ev = pair_events(p, 1);
     if (p->algo == ALGO_TILE) {
         TileArgs a;
@@ -502,35 +529,33 @@ static int walked_pass(tsc_prune *p, int rank, int world, int64_t rows_ub, int64
     }
     SieveArgs a = sieve_args(p, w.rows, rank, world, w.seg_cols, p->tile_cmax);
 #ifdef TSC_DBG_STAMPS
-    if (c->opt.dbg_stamp_k == p->cur_k) TSC_TRY(stamp_buffer(c, int64_t(w.grid.x) * w.grid.y * 4, &a.dbg));
+    if (c->opt.dbg_stamp_k == p->cur.k) TSC_TRY(stamp_buffer(c, int64_t(w.grid.x) * w.grid.y * 4, &a.dbg));
 #endif
     FusedApply fa;
     memset(&fa, 0, sizeof(fa));
-    if (p->cur_fused) {
+    if (fused) {
         fa.ap = apply_args(p);
         // a rank-partitioned pass is closed by the pair kernel's last tile (its statistics go to the exchange buffer); any other is left
         // open -- no arrivals, no closing wavefront -- and closed behind the kernel boundary by the first kernel of the next pass
-        fa.tile_done = p->tile_done, fa.tickets = p->cur_range ? &p->tickets->pass : nullptr, fa.n_tiles = unsigned(w.n_tiles);
-        fa.sc = step_ctx(p, p->cur_range);
-        int nxt = -1;
-        fa.next = next_step_args(p, &nxt);
-        if (!p->cur_range) p->last_local = false;  // (last_slot stays this pass's: left open)
+        fa.tile_done = p->tile_done, fa.tickets = p->cur.range ? &p->tickets->pass : nullptr, fa.n_tiles = unsigned(w.n_tiles);
+        fa.sc = step_ctx(p, p->cur.range);
+        fa.next = next_step_args(p);
     }
     const bool trim = c->opt.sieve_cpl == 2 && c->opt.sieve_trim;
     if (form.mm16) {
-        TSC_TRY(launch_rmsd_sieve_mm16(p->cur_fused, a.heavy32 != nullptr, w.mm16_waves, st, w.grid, ev.e0, ev.e1, p->heavy, (const int32_t *)p->act,
+        TSC_TRY(launch_rmsd_sieve_mm16(fused, a.heavy32 != nullptr, w.mm16_waves, st, w.grid, ev.e0, ev.e1, p->heavy, (const int32_t *)p->act,
                                        (const double *)p->Gall, (const _Float16 *)p->Dh, (const int32_t *)p->cend, p->best, p->counters,
                                        (const PruneState *)p->state, a, fa));
         return 0;
     }
     if (form.mm) {
-        TSC_TRY(launch_rmsd_sieve_mm(p->cur_fused, a.heavy32 != nullptr, st, w.grid, ev.e0, ev.e1, p->heavy, (const int32_t *)p->act, (const double *)p->Gall,
+        TSC_TRY(launch_rmsd_sieve_mm(fused, a.heavy32 != nullptr, st, w.grid, ev.e0, ev.e1, p->heavy, (const int32_t *)p->act, (const double *)p->Gall,
                                      (const float *)p->Dc, (const _Float16 *)p->Dh, (const int32_t *)p->cend, p->best, p->counters, (const PruneState *)p->state, a,
                                      fa));
         return 0;
     }
     // (stage 1 on the float32 copy exists for the default shape of the kernel only)
-    TSC_TRY((p->cur_fused ? launch_rmsd_sieve_fused : launch_rmsd_sieve_plain)(
+    TSC_TRY((fused ? launch_rmsd_sieve_fused : launch_rmsd_sieve_plain)(
         c->opt.sieve_cpl, trim, trim && a.heavy32 != nullptr, st, w.grid, ev.e0, ev.e1, p->heavy, (const int32_t *)p->act, (const double *)p->Gall, (const float *)p->Dc,
         (const int32_t *)p->cend, p->best, p->counters, (const PruneState *)p->state, a, fa));
     TSC_HIP(hipGetLastError());
@@ -539,7 +564,7 @@ static int walked_pass(tsc_prune *p, int rank, int world, int64_t rows_ub, int64
 
 // ---- the chunk-local pass: the whole pass in one launch, a workgroup (or a few) per chunk (local_pass.hpp) ----
 static int local_pass(tsc_prune *p, const PassGeom &g, const PassRows &r, bool range) {
-    const LocalPlan l = plan_local(p->n, p->cur_k, r);
+    const LocalPlan l = plan_local(p->n, p->cur.k, r);
     LocalPassArgs a;
     a.h = p->h, a.use_cache = (p->mode == 0);
     a.nb_regular = l.nb_regular, a.nb_last = l.nb_last;
@@ -549,11 +574,10 @@ static int local_pass(tsc_prune *p, const PassGeom &g, const PassRows &r, bool r
     a.rec = p->ctx->opt.sieve_mm16 != 0 ? p->Drec : nullptr;
     a.dbg = nullptr;
 #ifdef TSC_DBG_STAMPS
-    if (p->ctx->opt.dbg_stamp_k == p->cur_k) TSC_TRY(stamp_buffer(p->ctx, int64_t(l.blocks) * 4, &a.dbg));
+    if (p->ctx->opt.dbg_stamp_k == p->cur.k) TSC_TRY(stamp_buffer(p->ctx, int64_t(l.blocks) * 4, &a.dbg));
 #endif
     put_screen_thresholds(p, a);
-    int nxt = -1;
-    const StepArgs sa = next_step_args(p, &nxt);
+    const StepArgs sa = next_step_args(p, true);
     // (its own events only at pass_timing 2: level 1 is what a timed region carries for the PAIR kernel's durations, and a pair of
     // events costs a small pass about 6 us)
     const PairEvents ev = pair_events(p, 2);
@@ -561,7 +585,6 @@ static int local_pass(tsc_prune *p, const PassGeom &g, const PassRows &r, bool r
     TSC_TRY(launch_pass_chunks(a.rec != nullptr, p->ctx->stream, unsigned(l.blocks), ev.e0, ev.e1, g, a, p->state, p->mask, p->bits, int(p->bit_words), view_of_open_pass(p), p->heavy,
                                (const double *)p->Gall, (const float *)p->Dall, later_views(p), p->counters, p->bsum, SCAN_TILE, step_ctx(p, range), sa,
                                range ? &p->tickets->local : nullptr, derive_args(p)));
-    if (!range) p->last_local = true;  // (last_slot stays this pass's: left open)
     return 0;
 }
 
@@ -590,10 +613,9 @@ static int open_rows(tsc_prune *p, const PassGeom &g, const PassShape &s, bool r
     oa.known = track ? p->known : nullptr, oa.cbeg = p->cbeg, oa.skip = skip ? 1 : 0;
     oa.dbg = nullptr;
 #ifdef TSC_DBG_STAMPS
-    if (c->opt.dbg_stamp_k == -p->cur_k) TSC_TRY(stamp_buffer(c, int64_t(o.stamp_blocks) * 4, &oa.dbg));  // (a negative k selects k_open_rows of pass k)
+    if (c->opt.dbg_stamp_k == -p->cur.k) TSC_TRY(stamp_buffer(c, int64_t(o.stamp_blocks) * 4, &oa.dbg));  // (a negative k selects k_open_rows of pass k)
 #endif
-    int nxt = -1;
-    const StepArgs sa = s.fused ? next_step_args(p, &nxt) : StepArgs{-1, -1, 0ll, 0, -1};
+    const StepArgs sa = s.fused ? next_step_args(p) : StepArgs{-1, -1, 0ll, 0, -1};
     static_assert(SCAN_TILE == 64 * SCAN_BLOCK_WORDS && DW == DESC_WORDS, "k_open_rows");
     hipLaunchKernelGGL(k_open_rows, dim3(o.blocks), dim3(256), 0, st, g, oa, step_ctx(p, range), sa, p->act, p->cend, p->best, p->tile_cmax, (const float *)p->Dall,
                        s.need_dc ? p->Dc : nullptr);
@@ -675,13 +697,12 @@ static int cull_verdict(tsc_prune *p, const PassGeom &g, bool *run_culled, int64
 static int culled_pass(tsc_prune *p, int rank, int world, bool range, const PassGeom &g, const PassShape &s, const PassRows &r, bool *ran, int64_t *rows_now) {
     tsc_ctx *c = p->ctx;
     hipStream_t st = c->stream;
-    const int64_t n = p->n, k = p->cur_k;
+    const int64_t n = p->n, k = p->cur.k;
     TSC_TRY(cull_verdict(p, g, ran, rows_now));
     if (!*ran) return 0;
     if (!p->morton_sorted) TSC_TRY(morton_sort(p));
     // (the culled pass with the screen on the matrix cores: groups of 64 rows of the layout, dealt to the ranks in runs of tile_block / 4)
     const bool cull_mm = p->Dhs && p->mm64;
-    p->cur_fused = false;  // rows collect verdicts as columns of other tiles too: the pass is applied behind the pair kernel (k_apply_pass)
     const int n_lb = int(ceil_div<int64_t>(n, CULL_LAYOUT_ITEMS));
     const LayoutRange lr{int(r.s_lo), int(r.s_hi)};
     hipLaunchKernelGGL(k_layout_count, dim3(unsigned(n_lb)), dim3(256), 0, st, g, lr, (const PruneState *)p->state, (const int32_t *)p->morton_order,
@@ -711,72 +732,72 @@ static int culled_pass(tsc_prune *p, int rank, int world, bool range, const Pass
     if (range) {
         // a partitioned pass is closed by tsc_prune_pass_merge after the exchange: this rank's verdicts go into the exchange buffer
         // now (k_apply_pass in its noting form), its last block leaves the statistics there
-        int nxt = -1;
-        const StepArgs sa = next_step_args(p, &nxt);
         const int blocks = int(std::min<int64_t>(ceil_div<int64_t>(s.rows_ub, 256), 512));
-        hipLaunchKernelGGL(k_apply_pass, dim3(blocks), dim3(256), 0, st, apply_args(p), step_ctx(p, true), sa);
+        hipLaunchKernelGGL(k_apply_pass, dim3(blocks), dim3(256), 0, st, apply_args(p), step_ctx(p, true), next_step_args(p));
         TSC_HIP(hipGetLastError());
     }
     return 0;
 }
 
-// The launches of a pass on this device: what every pass has (events, opening the slot on the device where the pass before it has not,
-// the slot flags), then one of the three shapes (pass_plan.hpp: pass_shape).  range = false: the rows dealt to (rank, world) by tiles, of
+// a one-block launch closes the pass that was left open and opens the slot behind it (pass_cursor.hpp: Opener::Step)
+static void launch_pass_step(const tsc_prune *p, const Handover &h) {
+    hipLaunchKernelGGL(k_pass_step, dim3(1), dim3(64), 0, p->ctx->stream, step_ctx_of(p, h.prev, h.next), step_args_of(p, h));
+}
+
+// The launches of a pass on this device: what every pass has (events, opening the slot on the device where the pass before it has not),
+// then one of the three shapes (pass_plan.hpp: pass_shape).  range = false: the rows dealt to (rank, world) by tiles, of
 // all chunks (tsc_prune_pass_local).  range = true: every row of the chunks that belong to this rank (tsc_prune_pass_range); rank / world
 // are then 0 / 1 for the kernels -- they see an ensemble made of this rank's rows.
 static int pass_launch(tsc_prune *p, int rank, int world, bool range) {
     tsc_ctx *c = p->ctx;
     DeviceGuard guard(c->device);
     hipStream_t st = c->stream;
-    const int64_t n = p->n, k = p->cur_k;
-    const int slot = p->cur_slot;
+    const int64_t n = p->n, k = p->cur.k;
+    const int slot = p->cur.slot;
     const PassRows r = range ? partition_bounds(n, k, p->part_rank, p->part_world) : whole_pass(n, k);
     const PassShape s = pass_shape(c->opt, n, k, p->algo, p->Dh != nullptr, p->mm64, p->det_desc, world, range, r);
     const PassGeom g{int(n), int(k), int(n / k)};
-    p->cur_range = range;
     for (int i = 0; i < 4; ++i)
         if (!p->ev[slot][i]) TSC_TRY(get_event(c, &p->ev[slot][i]));
     if (c->opt.pass_timing >= 2) TSC_HIP(hipEventRecord(p->ev[slot][0], st));
     p->state = p->state_all + slot, p->counters = p->counters_all + slot;
     // 0. open this pass: gate (:192), record, state block of its slot -- already done by the kernel that closed the pass before it (its
     //    last block; k_init_run for the first pass of a run), or the pass before it was left open: then the first kernel of this pass
-    //    closes it and opens this one in its first round trip (pass_derive) -- k_pass_chunks, or k_open_rows where the prefix of the scan
-    //    blocks fits its LDS array; a one-block launch where neither is the first kernel
-    p->derive_prev = false;
-    if (p->opened_slot != slot) {
-        if (p->last_slot < 0) return fail(TSC_ERR_STATE, "prune pass k = %lld: no pass in front of it was left open and nothing has opened its slot", (long long)k);
-        if (!range && (s.local || p->n_blocks <= std::min(c->opt.open_lds_blocks, OPEN_LDS_BLOCKS))) {
-            p->derive_prev = true, p->derive_slot = p->last_slot, p->derive_local = p->last_local;
-        } else {
-            StepArgs sa{p->last_slot, slot, (long long)k, p->algo, p->last_local ? ALGO_LOCAL : -1};
-            hipLaunchKernelGGL(k_pass_step, dim3(1), dim3(64), 0, st, step_ctx_of(p, p->last_slot, slot), sa);
-        }
-        p->opened_slot = slot;
-    }
-    if (range && p->range_ready_slot != slot)  // no k_pass_merge in front of this pass (the first of a run): which rows are this rank's
+    //    closes it and opens this one in its first round trip (pass_derive; derive_args reads the cursor) -- k_pass_chunks, or k_open_rows
+    //    where the prefix of the scan blocks fits its LDS array; a one-block launch where neither is the first kernel
+    const Handover h = p->cur.open_slot(range, !range && (s.local || p->n_blocks <= std::min(c->opt.open_lds_blocks, OPEN_LDS_BLOCKS)));
+    if (h.how == Opener::Nothing)
+        return fail(TSC_ERR_STATE, "prune pass k = %lld: no pass in front of it was left open and nothing has opened its slot", (long long)k);
+    if (h.how == Opener::Step) launch_pass_step(p, h);
+    if (range && !p->cur.rows_ready())  // no k_pass_merge in front of this pass (the first of a run): which rows are this rank's
         hipLaunchKernelGGL(k_range_open, dim3(1), dim3(64), 0, st, p->state, (const int32_t *)p->boff, (const unsigned long long *)p->bits, int(p->bit_words),
                            p->n_blocks, int(r.s_lo), int(r.s_hi));
-    p->last_slot = slot;
-    p->last_local = false;
-    p->slot_used[slot] = true;
-    p->cur_local = s.local;
-    p->cur_fused = false;
     if (s.local) {
         TSC_TRY(local_pass(p, g, r, range));
-        p->local_done = true;
+        p->cur.launched(PassKind::Local);
         return 0;
     }
     if (world > 1 && p->auto_tile && !p->det_desc)
         return fail(TSC_ERR_STATE, "tsc_prune_pass_local: this run chose the all-pairs kernel from its own basis estimate; ranks of a sharded run could "
                                    "choose differently -- create the runs under deterministic_basis = 1, or force prune_algo 1 or 2 on every rank");
     if (s.culled) TSC_TRY(cull_buffers(p));
-    p->cur_fused = s.fused;
     TSC_TRY(open_rows(p, g, s, range, world));
+    // (in a culled pass rows collect verdicts as columns of other tiles too: it is applied behind the pair kernel, by k_apply_pass)
     bool ran_culled = false;
     int64_t rows_now = -1;   // (the pass's rows, where the host has waited for the device anyway)
     if (s.culled) TSC_TRY(culled_pass(p, rank, world, range, g, s, r, &ran_culled, &rows_now));
-    if (!ran_culled) TSC_TRY(walked_pass(p, rank, world, s.rows_ub, rows_now));
-    p->local_done = true;
+    const bool fused = s.fused && !ran_culled;
+    if (!ran_culled) TSC_TRY(walked_pass(p, rank, world, fused, s.rows_ub, rows_now));
+    p->cur.launched(fused ? PassKind::Fused : PassKind::Behind);
+    return 0;
+}
+
+// The open pass ends on the host (tsc_prune_pass_finish, tsc_prune_pass_merge).  closed: the last kernel enqueued for it has closed it on the
+// device and opened the pass that follows; otherwise it is left open
+static int end_pass(tsc_prune *p, bool closed) {
+    if (closed) p->cur.closed_on_device();
+    if (p->ctx->opt.pass_timing >= 2) TSC_HIP(hipEventRecord(p->ev[p->cur.slot][3], p->ctx->stream));
+    p->cur.end_pass();
     return 0;
 }
 
@@ -784,8 +805,8 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_local(tsc_p
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p != nullptr, "null argument");
     TSC_REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad rank %d / world %d", rank, world);
-    if (p->cur_k == 0 || p->local_done) return fail(TSC_ERR_STATE, "tsc_prune_pass_local: no pass open (call tsc_prune_next_pass)");
-    if (p->views_split && p->mode == 0)
+    TSC_TRY(allowed(p, StepCall::PassLocal));
+    if (p->cur.split && p->mode == 0)
         return fail(TSC_ERR_STATE, "tsc_prune_pass_local: rank-partitioned passes have run; sum the cache views over the ranks first "
                                    "(tsc_prune_views_ptr, tsc_prune_views_merged)");
     return pass_launch(p, rank, world, false);
@@ -793,20 +814,11 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_local(tsc_p
 }
 
 // ---- rank-partitioned passes (rmsd.hpp, k_pass_merge) ----
-// words of the exchange buffer of a run over n structures: the removed-row bits of a pass (bit_words of prune_create_impl), eight
-// words of statistics, then -- reference-exact mode -- the storage of every cache view of the run (so that the host can sum the
-// views of the remaining passes over the ranks in place, as part of a buffer it owns)
-static int64_t views_words_of(int64_t n, int mode) {
-    if (mode != 0) return 0;
-    int n_views = 0;
-    for (int slot = 0; slot < TSC_MAX_PASSES; ++slot) n_views += pass_can_run(n, slot) ? 1 : 0;
-    const int64_t bit_words = n / 64 + 40;
-    return int64_t(n_views) * (bit_words + bit_words / 1024 + 4);
-}
+// (the words of the exchange buffer: pass_cursor.hpp, exchange_words_of)
 extern "C" __attribute__((visibility("default"))) int tsc_prune_exchange_words(int64_t n, int mode, int64_t *words) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(words && n > 0, "bad argument");
-    *words = n / 64 + 40 + 8 + views_words_of(n, mode);
+    *words = exchange_words_of(n, mode);
     return 0;
     TSC_API_GUARD_END
 }
@@ -817,14 +829,14 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_set_partition(ts
     TSC_REQUIRE(p && exch_dev, "null argument");
     TSC_REQUIRE(world >= 1 && rank >= 0 && rank < world && min_chunks_per_rank >= 1, "bad rank %d / world %d / min_chunks_per_rank %d", rank, world,
                 min_chunks_per_rank);
-    const int64_t need = int64_t(p->bit_words) + 8 + views_words_of(p->n, p->mode);
+    const int64_t need = exchange_words_of(p->n, p->mode);
     TSC_REQUIRE(exch_words >= need, "exchange buffer of %lld words, %lld needed (tsc_prune_exchange_words)", (long long)exch_words, (long long)need);
-    if (p->cur_k != 0 || p->next_ks != 0) return fail(TSC_ERR_STATE, "tsc_prune_set_partition: call it right after tsc_prune_create");
+    TSC_TRY(allowed(p, StepCall::SetPartition));
     DeviceGuard guard(p->ctx->device);
     p->part_rank = rank, p->part_world = world, p->part_min_chunks = min_chunks_per_rank;
     p->exch = static_cast<unsigned long long *>(exch_dev);
     TSC_HIP(hipMemsetAsync(p->exch, 0, size_t(need) * sizeof(unsigned long long), p->ctx->stream));
-    if (p->mode == 0) p->views = p->exch + p->bit_words + 8;  // the cache views live in the caller's buffer from here on (still empty)
+    if (p->mode == 0) p->views = p->exch + p->bit_words + EXCH_STAT_WORDS;  // the cache views live in the caller's buffer from here on (still empty)
     return 0;
     TSC_API_GUARD_END
 }
@@ -832,8 +844,8 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_set_partition(ts
 extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_partitioned(tsc_prune *p, int *flag) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p && flag, "null argument");
-    if (p->cur_k == 0) return fail(TSC_ERR_STATE, "tsc_prune_pass_partitioned: no pass open");
-    *flag = pass_is_partitioned(p, p->cur_k) ? 1 : 0;
+    TSC_TRY(allowed(p, StepCall::Partitioned));
+    *flag = pass_is_partitioned(p, p->cur.k) ? 1 : 0;
     return 0;
     TSC_API_GUARD_END
 }
@@ -841,10 +853,10 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_partitioned
 extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_range(tsc_prune *p) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p != nullptr, "null argument");
-    if (p->cur_k == 0 || p->local_done) return fail(TSC_ERR_STATE, "tsc_prune_pass_range: no pass open (call tsc_prune_next_pass)");
-    if (!pass_is_partitioned(p, p->cur_k)) return fail(TSC_ERR_STATE, "tsc_prune_pass_range: the open pass (k = %lld) is not rank-partitioned", (long long)p->cur_k);
+    TSC_TRY(allowed(p, StepCall::PassRange));
+    if (!pass_is_partitioned(p, p->cur.k)) return fail(TSC_ERR_STATE, "tsc_prune_pass_range: the open pass (k = %lld) is not rank-partitioned", (long long)p->cur.k);
     TSC_TRY(pass_launch(p, 0, 1, true));
-    p->views_split = true;
+    p->cur.split_views();
     return 0;
     TSC_API_GUARD_END
 }
@@ -852,29 +864,21 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_range(tsc_p
 extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_merge(tsc_prune *p) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p != nullptr, "null argument");
-    if (p->cur_k == 0 || !p->local_done || !p->cur_range) return fail(TSC_ERR_STATE, "tsc_prune_pass_merge: tsc_prune_pass_range has not run");
+    TSC_TRY(allowed(p, StepCall::PassMerge));
     tsc_ctx *c = p->ctx;
     DeviceGuard guard(c->device);
-    int nxt = -1;
-    const StepArgs sa = next_step_args(p, &nxt);
+    const int nxt = p->cur.next_slot();
     MergeArgs ma;
     ma.n = int(p->n), ma.bit_words = int(p->bit_words), ma.n_blocks = p->n_blocks, ma.bits = p->bits, ma.exch = p->exch, ma.mask = p->mask;
     ma.next_s_lo = ma.next_s_hi = -1;
     if (nxt >= 0 && pass_is_partitioned(p, int64_t(KS[nxt]))) {
         const PassRows next = partition_bounds(p->n, int64_t(KS[nxt]), p->part_rank, p->part_world);
         ma.next_s_lo = int(next.s_lo), ma.next_s_hi = int(next.s_hi);
-        p->range_ready_slot = nxt;
+        p->cur.range_ready(nxt);
     }
-    hipLaunchKernelGGL(k_pass_merge, dim3(1), dim3(1024), 0, c->stream, ma, step_ctx(p), sa);
+    hipLaunchKernelGGL(k_pass_merge, dim3(1), dim3(1024), 0, c->stream, ma, step_ctx(p), next_step_args(p, p->cur.kind == PassKind::Local));
     TSC_HIP(hipGetLastError());
-    p->opened_slot = nxt;
-    p->last_slot = -1;  // closed on the device
-    if (c->opt.pass_timing >= 2) TSC_HIP(hipEventRecord(p->ev[p->cur_slot][3], c->stream));
-    p->cur_k = 0;
-    p->cur_slot = -1;
-    p->cur_range = false;
-    p->collected = false;
-    return 0;
+    return end_pass(p, true);
     TSC_API_GUARD_END
 }
 
@@ -884,13 +888,12 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_merge(tsc_p
 extern "C" __attribute__((visibility("default"))) int tsc_prune_views_ptr(tsc_prune *p, void **views_dev, int64_t *offset_words, int64_t *words) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p && views_dev && offset_words && words, "null argument");
-    if (p->cur_k == 0) return fail(TSC_ERR_STATE, "tsc_prune_views_ptr: no pass open");
+    TSC_TRY(allowed(p, StepCall::ViewsPtr));
     *views_dev = nullptr, *offset_words = 0, *words = 0;
-    if (!p->views_split || p->mode != 0) return 0;
-    const int v = p->view_of_slot[p->cur_slot];
-    *views_dev = p->views + size_t(v) * (p->bit_words + p->dsum_words);
-    *offset_words = int64_t(p->views - p->exch) + int64_t(v) * int64_t(p->bit_words + p->dsum_words);
-    *words = int64_t(p->n_views - v) * int64_t(p->bit_words + p->dsum_words);
+    if (!p->cur.split || p->mode != 0) return 0;
+    *views_dev = view_of_open_pass(p);
+    *offset_words = int64_t(view_of_open_pass(p) - p->exch);
+    *words = int64_t(p->n_views - p->view_of_slot[p->cur.slot]) * int64_t(view_stride(p->bit_words));
     return 0;
     TSC_API_GUARD_END
 }
@@ -898,16 +901,15 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_views_ptr(tsc_pr
 extern "C" __attribute__((visibility("default"))) int tsc_prune_views_merged(tsc_prune *p) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p != nullptr, "null argument");
-    if (p->cur_k == 0) return fail(TSC_ERR_STATE, "tsc_prune_views_merged: no pass open");
-    if (p->views_split && p->mode == 0) {
+    TSC_TRY(allowed(p, StepCall::ViewsMerged));
+    if (p->cur.split && p->mode == 0) {
         DeviceGuard guard(p->ctx->device);
-        const int v = p->view_of_slot[p->cur_slot], count = p->n_views - v;
+        const int count = p->n_views - p->view_of_slot[p->cur.slot];
         hipLaunchKernelGGL(k_views_summaries, dim3(unsigned(std::min<int64_t>(ceil_div<int64_t>(int64_t(count) * p->dsum_words * 64, 256), 2048))), dim3(256), 0, p->ctx->stream,
-                           p->views + size_t(v) * (p->bit_words + p->dsum_words), (long long)(p->bit_words + p->dsum_words), int(p->bit_words),
-                           int(p->dsum_words), count);
+                           view_of_open_pass(p), (long long)view_stride(p->bit_words), int(p->bit_words), int(p->dsum_words), count);
         TSC_HIP(hipGetLastError());
     }
-    p->views_split = false;
+    p->cur.merged_views();
     return 0;
     TSC_API_GUARD_END
 }
@@ -916,17 +918,16 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_rows(tsc_pr
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p != nullptr, "null argument");
     TSC_REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad rank %d / world %d", rank, world);
-    if (p->cur_k == 0 || !p->local_done || p->cur_local || p->cur_fused)
-        return fail(TSC_ERR_STATE, "tsc_prune_pass_rows: needs an open pass whose tsc_prune_pass_local ran with world_size > 1");
+    TSC_TRY(allowed(p, StepCall::PassRows));
     DeviceGuard guard(p->ctx->device);
-    return walked_pass(p, rank, world, p->n);
+    return walked_pass(p, rank, world, false, p->n);
     TSC_API_GUARD_END
 }
 
 extern "C" __attribute__((visibility("default"))) int tsc_prune_best_ptr(tsc_prune *p, void **best_dev, int64_t *n_entries) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p && best_dev && n_entries, "null argument");
-    if (p->cur_k == 0) return fail(TSC_ERR_STATE, "tsc_prune_best_ptr: no pass open");
+    TSC_TRY(allowed(p, StepCall::BestPtr));
     *best_dev = p->best;
     *n_entries = p->n;  // entries beyond the (device-side) active count are not touched by the pass
     return 0;
@@ -936,7 +937,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_best_ptr(tsc_pru
 extern "C" __attribute__((visibility("default"))) int tsc_prune_use_best_buffer(tsc_prune *p, void *best_dev) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p && best_dev, "null argument");
-    if (p->cur_k != 0 || p->next_ks != 0) return fail(TSC_ERR_STATE, "tsc_prune_use_best_buffer: call it right after tsc_prune_create");
+    TSC_TRY(allowed(p, StepCall::UseBestBuffer));
     p->best = static_cast<int32_t *>(best_dev);
     return 0;
     TSC_API_GUARD_END
@@ -945,24 +946,15 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_use_best_buffer(
 extern "C" __attribute__((visibility("default"))) int tsc_prune_pass_finish(tsc_prune *p) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p != nullptr, "null argument");
-    if (p->cur_k == 0 || !p->local_done) return fail(TSC_ERR_STATE, "tsc_prune_pass_finish: tsc_prune_pass_local has not run");
-    if (p->cur_range) return fail(TSC_ERR_STATE, "tsc_prune_pass_finish: a rank-partitioned pass is closed by tsc_prune_pass_merge");
-    tsc_ctx *c = p->ctx;
-    DeviceGuard guard(c->device);
-    if (!p->cur_local && !p->cur_fused) {  // (a chunk-local pass, and the pair kernel of a fused one, have applied the verdicts already)
-        int nxt = -1;
-        const StepArgs sa = next_step_args(p, &nxt);
+    TSC_TRY(allowed(p, StepCall::PassFinish));
+    DeviceGuard guard(p->ctx->device);
+    const bool behind = p->cur.kind == PassKind::Behind;  // (a chunk-local pass, and the pair kernel of a fused one, have applied the verdicts already)
+    if (behind) {
         const int blocks = int(std::min<int64_t>(ceil_div<int64_t>(p->n, 256), 512));
-        hipLaunchKernelGGL(k_apply_pass, dim3(blocks), dim3(256), 0, c->stream, apply_args(p), step_ctx(p), sa);
-        p->opened_slot = nxt;
-        p->last_slot = -1;  // closed on the device
+        hipLaunchKernelGGL(k_apply_pass, dim3(blocks), dim3(256), 0, p->ctx->stream, apply_args(p), step_ctx(p), next_step_args(p));
         TSC_HIP(hipGetLastError());
     }
-    if (c->opt.pass_timing >= 2) TSC_HIP(hipEventRecord(p->ev[p->cur_slot][3], c->stream));
-    p->cur_k = 0;
-    p->cur_slot = -1;
-    p->collected = false;
-    return 0;
+    return end_pass(p, behind);
     TSC_API_GUARD_END
 }
 
@@ -980,7 +972,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_run_replicated(t
         if (k == 0) return 0;
         // (a partitioned pass, or the first pass after partitioned ones -- the cache views must be summed over the ranks first --
         // goes back to the caller as well)
-        if (world > 1 && (pass_is_partitioned(p, k) || (p->views_split && p->mode == 0) || p->n * (p->n / k) / 2 >= min_pairs)) return 0;
+        if (world > 1 && (pass_is_partitioned(p, k) || (p->cur.split && p->mode == 0) || p->n * (p->n / k) / 2 >= min_pairs)) return 0;
         TSC_TRY(tsc_prune_pass_local(p, 0, 1));
         TSC_TRY(tsc_prune_pass_finish(p));
     }
@@ -1023,11 +1015,11 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_run_sharded(tsc_
         if (pass_is_partitioned(p, k)) {
             // the whole pass on this rank's chunks; what the ranks tell each other is which rows they removed (+ the statistics)
             TSC_TRY(tsc_prune_pass_range(p));
-            TSC_TRY(xchg(TSC_XCHG_SUM_I64, p->exch, int64_t(p->bit_words) + 8, k));
+            TSC_TRY(xchg(TSC_XCHG_SUM_I64, p->exch, int64_t(p->bit_words) + EXCH_STAT_WORDS, k));
             TSC_TRY(tsc_prune_pass_merge(p));
             continue;
         }
-        if (p->views_split && p->mode == 0) {
+        if (p->cur.split && p->mode == 0) {
             // first pass after the partitioned ones: every rank needs every rank's cache keys from here on
             void *views = nullptr;
             int64_t off = 0, words = 0;
@@ -1069,20 +1061,13 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_copy_mask_dev(ts
 extern "C" __attribute__((visibility("default"))) int tsc_prune_stats(tsc_prune *p, tsc_pass_stats *stats, int *n_passes) {
     TSC_API_GUARD_BEGIN
     TSC_REQUIRE(p != nullptr, "null argument");
-    if (p->cur_k != 0) return fail(TSC_ERR_STATE, "tsc_prune_stats: a pass is still open");
+    TSC_TRY(allowed(p, StepCall::Stats));
     tsc_ctx *c = p->ctx;
     DeviceGuard guard(c->device);
-    if (!p->collected) {
+    if (!p->cur.exported) {
         hipStream_t st = c->stream;
-        if (p->last_slot >= 0) {  // the last pass was left open: close it, and open the one that follows where the run goes on
-            int nxt = -1;
-            for (int s = p->next_ks; s < TSC_MAX_PASSES && nxt < 0; ++s)
-                if (pass_can_run(p->n, s)) nxt = s;
-            StepArgs sa{p->last_slot, nxt, nxt >= 0 ? (long long)KS[nxt] : 0ll, p->algo, p->last_local ? ALGO_LOCAL : -1};
-            hipLaunchKernelGGL(k_pass_step, dim3(1), dim3(64), 0, st, step_ctx_of(p, p->last_slot, nxt), sa);
-            p->last_slot = -1;
-            p->opened_slot = nxt;
-        }
+        const Handover h = p->cur.close_for_export();  // the last pass was left open: close it, and open the one that follows where the run goes on
+        if (h.how == Opener::Step) launch_pass_step(p, h);
         static_assert(sizeof(PassRecord) * TSC_MAX_PASSES <= 4096 && sizeof(PassRecord) % 8 == 0, "records fit the pinned staging buffer");
         {
             const int rec_words = int(sizeof(PassRecord) * TSC_MAX_PASSES / 8);
@@ -1099,7 +1084,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_stats(tsc_prune 
         const bool nonfinite = unsigned(static_cast<const unsigned long long *>(c->pinned)[sizeof(PassRecord) * TSC_MAX_PASSES / 8]) >= 0x7f800000u;
         p->n_passes = 0;
         for (int slot = 0; slot < TSC_MAX_PASSES; ++slot) {
-            if (!p->slot_used[slot] || !rec[slot].on) continue;
+            if (!p->cur.ran[slot] || !rec[slot].on) continue;
             tsc_pass_stats &s = p->stats[p->n_passes++];
             memset(&s, 0, sizeof(s));
             s.k = rec[slot].k, s.n_active_before = rec[slot].n_before, s.n_active_after = rec[slot].n_after;
@@ -1111,7 +1096,7 @@ extern "C" __attribute__((visibility("default"))) int tsc_prune_stats(tsc_prune 
             if (c->opt.pass_timing >= 2 && hipEventElapsedTime(&ms, p->ev[slot][0], p->ev[slot][3]) == hipSuccess) s.gpu_ms = ms;
             if (c->opt.pass_timing >= (rec[slot].algo == ALGO_LOCAL ? 2 : 1) && hipEventElapsedTime(&ms, p->ev[slot][1], p->ev[slot][2]) == hipSuccess) s.tile_ms = ms;
         }
-        p->collected = true;
+        p->cur.exported = true;
     }
     if (stats) memcpy(stats, p->stats, sizeof(tsc_pass_stats) * size_t(p->n_passes));
     if (n_passes) *n_passes = p->n_passes;

@@ -4,6 +4,7 @@
 
 #include "cull_mm.hpp"
 #include "local_pass.hpp"
+#include "pass_cursor.hpp"
 #include "pass_plan.hpp"
 #include "pass_state.hpp"
 #include "prune_api.hpp"
@@ -20,10 +21,6 @@
 // of still-active structures, return at once.  The host reads the per-pass records once, at the end.
 
 static_assert(MAX_SLOTS == TSC_MAX_PASSES, "one cache view per schedule slot");
-
-// Can the pass of schedule slot `slot` (KS, prune_schedule.hpp) ever run on n structures?  count_nonzero(mask) <= n, so a pass with
-// 20 k >= n can never pass the gate of :192; the others are enqueued and gated on the device.
-static inline bool pass_can_run(int64_t n, int slot) { return pass_gate(KS[slot], n); }
 
 struct tsc_prune : Owned {
     explicit tsc_prune(tsc_ctx *c) : Owned(c) {}
@@ -47,8 +44,7 @@ struct tsc_prune : Owned {
     ViewPass *view_pass = nullptr;         // device: the pass of each view (chunk count, chunk size, its division constants)
     int view_of_slot[TSC_MAX_PASSES] = {};  // schedule slot -> view index (-1: the pass can never run)
     int n_views = 0;
-    size_t bit_words = 0, dsum_words = 0;
-    bool cur_fused = false;                // the open pass is applied by the pair kernel itself
+    size_t bit_words = 0, dsum_words = 0;   // (pass_cursor.hpp: bit_words_of, dsum_words_of)
     double *Xr = nullptr, *Xc = nullptr, *G = nullptr;                       // register-tiled kernel
     float *Dall = nullptr;   // sieve kernel: fp32 descriptors of every structure, [n][DW]
     float *Dc = nullptr;     // ... in active order, rewritten by k_open_rows every pass: what the pair kernel reads
@@ -60,7 +56,6 @@ struct tsc_prune : Owned {
         PassTickets pass;
         LocalTickets local;
     } *tickets = nullptr;  // arrival counters of the fused pair kernel and of the chunk-local pass kernel
-    bool cur_local = false;           // the open pass ran (whole) in tsc_prune_pass_local
     // culled passes (cull.hpp): allocated when the first one comes up
     int32_t *morton_order = nullptr, *rank_of = nullptr, *crank = nullptr, *cbase = nullptr, *cfill = nullptr, *blk_cnt = nullptr;
     float *Ds = nullptr, *cbox = nullptr, *rbox = nullptr;
@@ -71,9 +66,6 @@ struct tsc_prune : Owned {
     // rank-partitioned passes (rmsd.hpp, k_pass_merge): set by tsc_prune_set_partition
     int part_rank = 0, part_world = 1, part_min_chunks = 0;
     unsigned long long *exch = nullptr;  // caller-owned exchange buffer: bit_words words of removed rows + 8 of statistics
-    bool cur_range = false;              // the open pass is run by tsc_prune_pass_range / tsc_prune_pass_merge
-    int range_ready_slot = -1;           // slot whose row range the device already holds (set by the k_pass_merge before it)
-    bool views_split = false;            // partitioned passes have run: the cache views of the remaining passes hold this rank's keys only
     uint8_t *export_mask_host = nullptr;  // set by prune_run: pinned host buffer that receives the mask with the statistics
     unsigned *dmax_bits = nullptr;  // device scalar: largest |descriptor component| as float bits (zeroed by k_init_run)
     PassCounters *counters_all = nullptr;  // [TSC_MAX_PASSES]: a slot's counters are zeroed once, by k_init_run, and only ever added to
@@ -82,21 +74,10 @@ struct tsc_prune : Owned {
     PruneState *state = nullptr;
     PassRecord *records = nullptr;  // [TSC_MAX_PASSES]
     // host state
-    int next_ks = 0;       // next index into KS to consider
-    int cur_slot = -1;     // schedule slot of the pass in flight (-1 = none)
-    int last_slot = -1;    // slot of the last pass that was enqueued and LEFT OPEN on the device: its tails end after their rows are applied,
-                           // and the first kernel of the next pass (pass_derive), or a k_pass_step launch, closes it behind a kernel boundary
-    int opened_slot = -1;  // slot whose state block the device has already written (by the kernel that closed the pass before it)
-    bool derive_prev = false;  // the open pass's first kernel closes last pass's slot (set by pass_launch for open_rows / local_pass)
-    int derive_slot = -1;
-    bool last_local = false, derive_local = false;  // the pass left open in last_slot / derive_slot ran in k_pass_chunks (its record says so)
-    int64_t cur_k = 0;
-    bool local_done = false;
-    bool slot_used[TSC_MAX_PASSES] = {false};
+    PassCursor cur;   // where the run is in the schedule, what is launched of the open pass, who closes and opens a slot on the device
     hipEvent_t ev[TSC_MAX_PASSES][4] = {{nullptr}};  // per slot: pass begin, pair kernel begin, pair kernel end, pass end
     tsc_pass_stats stats[TSC_MAX_PASSES] = {};
     int n_passes = 0;
-    bool collected = false;
     bool borrows_xd = false;   // the descriptors (and the float32 copy) are the context's xd_* buffers, written by tsc_embed_masked_dev: the context
                                // must not release them while this run lives (tsc_ctx::xd_borrowers)
     bool det_desc = false;     // the descriptors were built with fixed-order sums ("deterministic_basis"): every rank of a sharded run that fed
@@ -105,14 +86,15 @@ struct tsc_prune : Owned {
     int flag_slot = -1;        // this run's word in the context's pinned buffer (the culled-or-walked verdict of a candidate pass)
 };
 
-// The pass that follows the open one (what tsc_prune_next_pass will hand out next; not consumed here): the kernel that
-// finishes a pass also closes it and opens this one on the device.
-static inline StepArgs next_step_args(const tsc_prune *p, int *next_slot) {
-    int nxt = -1;
-    for (int s = p->next_ks; s < TSC_MAX_PASSES && nxt < 0; ++s)
-        if (pass_can_run(p->n, s)) nxt = s;
-    *next_slot = nxt;
-    return StepArgs{p->cur_slot, nxt, nxt >= 0 ? (long long)KS[nxt] : 0ll, p->algo, p->cur_local ? ALGO_LOCAL : -1};
+// The pass that follows the open one (what tsc_prune_next_pass will hand out next): the kernel that finishes a pass also closes it and opens
+// this one on the device.  local: the open pass runs in the chunk-local kernel (its record says so)
+static inline StepArgs next_step_args(const tsc_prune *p, bool local = false) {
+    const int nxt = p->cur.next_slot();
+    return StepArgs{p->cur.slot, nxt, nxt >= 0 ? (long long)KS[nxt] : 0ll, p->algo, local ? ALGO_LOCAL : -1};
+}
+// a k_pass_step launch: closes h.prev, opens h.next
+static inline StepArgs step_args_of(const tsc_prune *p, const Handover &h) {
+    return StepArgs{h.prev, h.next, h.next >= 0 ? (long long)KS[h.next] : 0ll, p->algo, h.prev_local ? ALGO_LOCAL : -1};
 }
 
 // range_close: the context of the kernels of a rank-partitioned pass -- their last unit leaves the statistics in the exchange buffer
@@ -125,9 +107,7 @@ static inline StepCtx step_ctx_of(const tsc_prune *p, int prev, int cur) {
 }
 // the step behind the open pass (next_step_args)
 static inline StepCtx step_ctx(const tsc_prune *p, bool range_close = false) {
-    int nxt = -1;
-    (void)next_step_args(p, &nxt);
-    StepCtx sc = step_ctx_of(p, p->cur_slot, nxt);
+    StepCtx sc = step_ctx_of(p, p->cur.slot, p->cur.next_slot());
     if (range_close) sc.exch_tail = p->exch + p->bit_words;
     return sc;
 }
@@ -136,10 +116,11 @@ static inline DeriveArgs derive_args(const tsc_prune *p) {
     DeriveArgs d;
     memset(&d, 0, sizeof(d));
     d.prev = d.cur = -1, d.prev_algo = -1;
-    if (!p->derive_prev) return d;
-    d.prev_st = p->state_all + p->derive_slot, d.prev_cnt = p->counters_all + p->derive_slot, d.rec = p->records;
-    d.prev = p->derive_slot, d.cur = p->cur_slot, d.k_cur = (long long)p->cur_k, d.algo_cur = p->algo;
-    d.prev_algo = p->derive_local ? ALGO_LOCAL : -1;
+    const int prev = p->cur.closes;
+    if (prev < 0) return d;
+    d.prev_st = p->state_all + prev, d.prev_cnt = p->counters_all + prev, d.rec = p->records;
+    d.prev = prev, d.cur = p->cur.slot, d.k_cur = (long long)p->cur.k, d.algo_cur = p->algo;
+    d.prev_algo = p->cur.closes_local ? ALGO_LOCAL : -1;
     return d;
 }
 
@@ -147,26 +128,26 @@ static inline bool pass_is_partitioned(const tsc_prune *p, int64_t k) {
     return p->part_world > 1 && p->exch && p->algo == ALGO_SIEVE && k >= int64_t(p->part_min_chunks) * p->part_world;
 }
 
+// the view of the open pass and of those behind it (reference-exact mode)
+static inline unsigned long long *view_of_open_pass(const tsc_prune *p) {
+    return p->mode == 0 ? p->views + size_t(p->view_of_slot[p->cur.slot]) * view_stride(p->bit_words) : p->views;
+}
 // Views of the passes AFTER the open one (where the rows it removes leave their cache keys); none in cache-free mode.
 static inline CacheViews later_views(const tsc_prune *p) {
     CacheViews cv;
-    cv.views = p->views, cv.stride = (long long)(p->bit_words + p->dsum_words), cv.bit_words = int(p->bit_words), cv.n = int(p->n);
-    cv.first = p->mode == 0 ? p->view_of_slot[p->cur_slot] + 1 : 0;
+    cv.views = p->views, cv.stride = (long long)view_stride(p->bit_words), cv.bit_words = int(p->bit_words), cv.n = int(p->n);
+    cv.first = p->mode == 0 ? p->view_of_slot[p->cur.slot] + 1 : 0;
     cv.count = p->mode == 0 ? p->n_views : 0;
     cv.pass = p->view_pass;
     return cv;
 }
 
-static inline const unsigned long long *view_of_open_pass(const tsc_prune *p) {
-    return p->mode == 0 ? p->views + size_t(p->view_of_slot[p->cur_slot]) * (p->bit_words + p->dsum_words) : p->views;
-}
-
 static inline ApplyArgs apply_args(const tsc_prune *p) {
     ApplyArgs a;
-    a.g = PassGeom{int(p->n), int(p->cur_k), int(p->n / p->cur_k)};
+    a.g = PassGeom{int(p->n), int(p->cur.k), int(p->n / p->cur.k)};
     a.act = p->act, a.cend = p->cend, a.best = p->best, a.mask = p->mask, a.bits = p->bits, a.bit_words = int(p->bit_words);
     a.bsum = p->bsum, a.block_items = SCAN_TILE, a.cv = later_views(p);
-    a.exch = p->cur_range ? p->exch : nullptr;
+    a.exch = p->cur.range ? p->exch : nullptr;
     return a;
 }
 
