@@ -290,6 +290,29 @@ int tsc_rmsd_cross_nearest(tsc_ctx *ctx, const double *queries, int64_t n_querie
 int tsc_rmsd_cross_nearest_dev(tsc_ctx *ctx, const double *queries, int64_t n_queries, const double *library, int64_t n_library, int n_atoms,
                                const int32_t *idx, int n_idx, int center, int32_t *index, double *rmsd, double *maxdev);
 
+/* ---- Energy-ordered RMSD prune: every cluster collapses to its first member (csrc/leader.hpp) -----
+ * The greedy filter of the embed loops (tscode/embeds.py:715, :843) for a whole ensemble, with an optional library that is never removed:
+ *     for s in order:  s is removed iff some row KEPT before it -- the library rows in index order, then this call's kept rows in the order
+ *                      they were kept -- is similar to it: rmsd_and_max_numba(s, k) (tscode/rmsd_pruning.py:6-41: s turned onto k, no
+ *                      centring) has rmsd < thr and maxdev < 2 thr (:75, :208-224); it is represented by the first such k.
+ * A removed row never covers anything.  structures f64[n, n_atoms, 3]; library f64[n_library, n_atoms, 3] or NULL with n_library = 0; idx /
+ * n_idx / center as the cross-set calls above take them; order i32[n], a permutation of 0 .. n - 1 (ascending energy), or NULL: the rows
+ * as they lie.  n, n_library and n + n_library up to 2^31 - 1.  Outputs, indexed by the CALLER's rows: mask u8[n] (1: kept); rep i32[n]: a
+ * kept row itself, a removed row the kept row of this call it fell to, -1 where a library row covered it; lib_rep i32[n]: that library
+ * row, else -1; *n_kept (host): the rows kept.
+ * tsc_prune_rmsd_ordered takes host arrays, checks idx and that order is a permutation, uploads and returns when the outputs are in the
+ * caller's arrays.  tsc_prune_rmsd_ordered_dev takes device pointers for every array (order included, unchecked), uploads nothing and
+ * enqueues on the context's stream; the rule is walked in blocks of tsc_leader_block() rows of the order and the kept count of a block
+ * (4 bytes) comes back to the host before the next block is enqueued, so the stream is idle and the outputs complete when it returns.
+ * Coordinates that are not finite are the caller's business there. */
+int tsc_leader_block(void);
+int tsc_prune_rmsd_ordered(tsc_ctx *ctx, const double *structures, int64_t n, const double *library, int64_t n_library, int n_atoms,
+                           const int32_t *idx, int n_idx, int center, const int32_t *order, double thr, uint8_t *mask, int32_t *rep,
+                           int32_t *lib_rep, int64_t *n_kept);
+int tsc_prune_rmsd_ordered_dev(tsc_ctx *ctx, const double *structures, int64_t n, const double *library, int64_t n_library, int n_atoms,
+                               const int32_t *idx, int n_idx, int center, const int32_t *order, double thr, uint8_t *mask, int32_t *rep,
+                               int32_t *lib_rep, int64_t *n_kept);
+
 /* The descriptor screen of the prune's pair kernel as the matrix cores compute it (csrc/mm.hpp), for tests: the screen values
  * S[fam][r][c] (two feature families, rows r < 64, columns c < n) of the first 64 of n descriptors against all n, in the units the
  * kernel compares them in -- out_scale^2 times |D_fam[r] - D_fam[c]|^2 up to the error bound of mm.hpp -- and the limit the kernel

@@ -38,5 +38,6 @@ from .rot_corr import (last_rot_corr_batch_stats, last_rot_corr_stats, prune_con
 from .rmsd_pruning import (_rmsd_similarity, last_prune_batch_stats, last_prune_stats, pack_heavy_batch, prune_conformers_rmsd,  # noqa: F401
                            prune_conformers_rmsd_batch, rmsd_and_max_numba)
 from .rmsd_cross import assign_to_kept, nearest_structures, prune_conformers_rmsd_against, rmsd_matrix, rmsd_similarity_mask  # noqa: F401
+from .rmsd_ordered import leader_clusters, prune_conformers_rmsd_ordered  # noqa: F401
 
 __version__ = "0.1.0"

@@ -99,6 +99,9 @@ _SIGNATURES = {
     "tsc_rmsd_cross_first_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, C.c_double, _vp]),
     "tsc_rmsd_cross_nearest": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "tsc_rmsd_cross_nearest_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "tsc_leader_block": (C.c_int, []),
+    "tsc_prune_rmsd_ordered": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_double, _vp, _vp, _vp, c_i64p]),
+    "tsc_prune_rmsd_ordered_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_double, _vp, _vp, _vp, c_i64p]),
     "tsc_embed_clash_compact_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, C.c_int, C.c_double, C.c_int64,
                                                _vp, _vp, _vp, _vp]),
     "tsc_basis_from_poses_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, C.c_int]),

@@ -2,6 +2,7 @@
 // query, as the nearest library member of every query.  gfx950 only; there is no CPU implementation behind these entry points.
 #include "call.hpp"
 #include "cross.hpp"
+#include "cross_reduce.hpp"
 #include "host.hpp"
 
 namespace {

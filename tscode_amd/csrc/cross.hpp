@@ -10,7 +10,8 @@
 //   k_cross_tile<HP, EPI>   register path, h <= 32: a wavefront owns CX_ROWS query rows and one column segment of the library, a lane a
 //                           library column whose HP x 3 coordinates sit in registers; H = p^T q by fma from the wavefront-uniform query row
 //   k_cross_general<EPI>    any h: the same work items and epilogues, a pair per lane from the row-major packs (rmsd_and_max_pair)
-//   k_cross_nearest_reduce  the `nearest` epilogue's second step
+//   k_cross_nearest_reduce  the `nearest` epilogue's second step (cross_reduce.hpp: only cross.hip launches it; leader.hip includes this header
+//                           for the CX_FIRST rectangle alone)
 //
 // Epilogues:
 //   CX_VALUES   every pair exactly; rmsd[q][l], maxdev[q][l] contiguous along l.  No screen.
@@ -326,23 +327,6 @@ inline __global__ __launch_bounds__(256) void k_cross_general(CrossArgs a) {
             const long long o = (long long)blockIdx.y * a.nq + r0 + lane;
             a.rmsd[o] = best_r, a.maxdev[o] = best_m, a.idx[o] = best_i;
         }
-    }
-}
-
-// Second step of CX_NEAREST: a thread per query row takes the segments in ascending order (ascending library indices); a strictly smaller
-// rmsd wins, so that ties stay with the lowest index.  index -1: no pair of the row compared below +inf (an empty or non-finite row).
-inline __global__ __launch_bounds__(256) void k_cross_nearest_reduce(const double *__restrict__ pr, const double *__restrict__ pm, const int32_t *__restrict__ pi,
-                                                               int n_seg, long long nq, int32_t *__restrict__ index, double *__restrict__ rmsd,
-                                                               double *__restrict__ maxdev) {
-    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < nq; r += (long long)gridDim.x * blockDim.x) {
-        double br = INFINITY, bm = INFINITY;
-        int bi = -1;
-        for (int s = 0; s < n_seg; ++s) {
-            const long long o = (long long)s * nq + r;
-            const double v = pr[o];
-            if (v < br) br = v, bm = pm[o], bi = pi[o];
-        }
-        index[r] = bi, rmsd[r] = br, maxdev[r] = bm;
     }
 }
 

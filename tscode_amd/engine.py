@@ -365,6 +365,30 @@ class Engine:
         check(self.lib.tsc_rmsd_cross_nearest_dev(self._h, ptr(queries), C.c_int64(n_q), ptr(library), C.c_int64(n_l), C.c_int(n_atoms), ptr(idx), C.c_int(n_idx),
                                                   C.c_int(bool(center)), ptr(index), ptr(rmsd), ptr(maxdev)))
 
+    # ---- energy-ordered RMSD prune (csrc/leader.hpp; argument checks: tscode_amd/rmsd_ordered.py) -------------------------------
+    def prune_rmsd_ordered(self, structures, library=None, idx=None, order=None, rmsd_thr=0.5, center=False):
+        """tsc_prune_rmsd_ordered: (mask u8[N], rep i32[N], lib_rep i32[N], n_kept) of structures f64[N, n, 3] walked in ``order`` (i32[N],
+        a permutation; None: as they lie) against library f64[Nl, n, 3] (None: none) on the atoms idx (None: all).  C-contiguous float64."""
+        n = structures.shape[0]
+        n_l = 0 if library is None else library.shape[0]
+        idx = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32)
+        order = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
+        mask, rep, lib_rep = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        n_kept = C.c_int64()
+        check(self.lib.tsc_prune_rmsd_ordered(self._h, ptr(structures), C.c_int64(n), ptr(library) if n_l else None, C.c_int64(n_l), C.c_int(structures.shape[1]),
+                                              ptr(idx), C.c_int(0 if idx is None else len(idx)), C.c_int(bool(center)), ptr(order), C.c_double(rmsd_thr),
+                                              ptr(mask), ptr(rep), ptr(lib_rep), C.byref(n_kept)))
+        return mask, rep, lib_rep, n_kept.value
+
+    def prune_rmsd_ordered_dev(self, structures, n, library, n_l, n_atoms, idx, n_idx, center, order, rmsd_thr, mask, rep, lib_rep) -> int:
+        """tsc_prune_rmsd_ordered_dev: every array on the device (torch tensors or raw pointers; library None with n_l 0: none, idx None with
+        n_idx 0: all atoms, order None: the rows as they lie); mask u8[n], rep / lib_rep i32[n] on the device.  Returns the kept count; the
+        stream is idle and the outputs are complete when it returns.  Finite input and a valid order are the caller's business."""
+        n_kept = C.c_int64()
+        check(self.lib.tsc_prune_rmsd_ordered_dev(self._h, ptr(structures), C.c_int64(n), ptr(library), C.c_int64(n_l), C.c_int(n_atoms), ptr(idx), C.c_int(n_idx),
+                                                  C.c_int(bool(center)), ptr(order), C.c_double(rmsd_thr), ptr(mask), ptr(rep), ptr(lib_rep), C.byref(n_kept)))
+        return n_kept.value
+
     def greedy_group_filter(self, poses, group_off, rmsd_thr=1.0):
         """accepted bool[n_poses]: per group, keep a pose iff it is not similar to a pose kept before it."""
         poses = np.ascontiguousarray(poses, dtype=np.float64)
